@@ -15,9 +15,13 @@ nlist=4096, nprobe=128, k=1024, open window +-500 Da, fragment tolerance 0.02 Da
 
 With N>1 the IVF lists are sharded over the ranks (ann_solo_amd/distributed.py) and
 every rank contributes its own 32 768-query slice per step (weak scaling).
-Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for how roofline.achieved
-(algorithmic bytes of the PQ scan / HIP-event kernel time) and cpu_baseline (the
-oracle on the host cores, bounded sample) are defined.
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the steps and prints
+`value` / `ms_per_step`; `--full` adds every other leg of the record (recall, fixed
+recall, reference geometry, stage times, roofline, CPU baseline, cascade, parity checks).
+See DESIGN.md "Measurement" for how roofline.achieved (algorithmic bytes of the PQ scan /
+HIP-event kernel time) and cpu_baseline (the oracle on the host cores, bounded sample)
+are defined. `--dump-outputs DIR` writes what the last timed step returned as
+DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -61,6 +65,41 @@ def emit_line(line):
     out.flush()
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6        # "64 MB" read either way (64e6 < 64 MiB)
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """``--dump-outputs``: every array of ``arrays`` (name -> device tensor or numpy array) as
+    ``path/<name>.npy``. 1-D arrays are written as float64 (every int32 id and the float64 scores
+    exactly); arrays of higher rank (the peak-match pairs: peak indices < 2^24) as float32. If the
+    total would exceed ``limit``, the higher-rank arrays keep a seeded sample of their rows (the same
+    rows from run to run), named by ``<name>_rows.npy``."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        a = a.cpu().numpy() if hasattr(a, 'cpu') else np.asarray(a)
+        out[name] = a.astype(np.float64 if a.ndim == 1 else np.float32)
+    flat = sum(a.nbytes for a in out.values() if a.ndim == 1)
+    wide = [n for n, a in out.items() if a.ndim > 1]
+    if flat + sum(out[n].nbytes for n in wide) > limit:
+        # every wide array shrinks by the same factor; a kept row costs its bytes + 8 B of `_rows`,
+        # and 1 MiB stays free for the .npy headers
+        cost = sum(out[n].nbytes + 8 * out[n].shape[0] for n in wide)
+        share = max(0.0, (limit - (1 << 20) - flat) / cost)
+        for n in wide:
+            a = out[n]
+            keep = max(1, min(a.shape[0], int(a.shape[0] * share)))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            out[n] = a[rows]
+            out[n + '_rows'] = rows.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    log(f'[bench] --dump-outputs: {len(out)} arrays, {sum(a.nbytes for a in out.values()) / 1e6:.1f} MB in {path}')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -88,7 +127,7 @@ def main():
                          'HARD synthetic queries, calibrated to the reference\'s exact-search hit@1024 of 75 %%)')
     ap.add_argument('--no-fixed-recall', action='store_true',
                     help='skip the IVF-Flat measurement at the fixed-recall operating point '
-                         '(default run, N = 1, IVF-PQ: same library, same coarse quantiser)')
+                         '(--full run, N = 1, IVF-PQ: same library, same coarse quantiser)')
     ap.add_argument('--no-pipeline', action='store_true',
                     help='run the stages of consecutive batches strictly one after the other '
                          '(default: two-stream software pipeline, asl_set_pipeline)')
@@ -133,16 +172,26 @@ def main():
                          'configs[1] = a 9 k-spectrum library, and the 2.1 M library, both IVF-Flat nlist 256 / '
                          'nprobe 128, src/ann_solo/config.py:188-211)')
     ap.add_argument('--beyond-llc-chunks', type=int, default=16,
-                    help='default N = 1 IVF-PQ run: the same scan kernel over an index grown to this many '
+                    help='--full N = 1 IVF-PQ run: the same scan kernel over an index grown to this many '
                          'library-sized chunks (16 x 2.1 M = 33.6 M vectors: 1.08 GB of codes, four times the 256 MiB '
                          'Infinity Cache) -- `roofline.beyond_llc`, the figure that IS served by HBM; 0 = skip')
     ap.add_argument('--no-cascade', action='store_true',
-                    help='skip the configs[4] cascade pass of the default N = 1 run (JSON field `cascade`)')
+                    help='skip the configs[4] cascade pass of the --full N = 1 run (JSON field `cascade`)')
     ap.add_argument('--ring', type=int, default=4,
                     help='distinct query batches the timed loop cycles through (step i searches batch '
                          'i mod ring; every leg that is not `value` uses batch 0)')
     ap.add_argument('--cpu-seconds', type=float, default=20.0,
                     help='target core-seconds of the CPU baseline sample (0 = skip)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the timed steps, run every other leg of the record: recall, fixed recall, '
+                         'reference geometry, the reference batch size, stage times, roofline, post-path, CPU '
+                         'baseline, cascade pass, parity checks (N > 1: unsharded parity, replicas layout, '
+                         'collectives alone). Without it a run reports only what the timed steps measure; the '
+                         '--no-* and leg options above apply to a --full run')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy '
+                         '(float64, or float32 for the peak-match pairs; at most 64 MB, larger outputs as a seeded '
+                         'sample of their rows)')
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -267,7 +316,7 @@ def main():
     recall = None
     recall_hard, hard_ctx = None, None
     recall_ctx = None
-    if rank == 0 and args.recall_queries > 0:
+    if rank == 0 and args.full and args.recall_queries > 0:
         nr = min(args.recall_queries, q.n)
         qs = q.select(torch.arange(nr, device=dev))
         r = sl._search_batch(qs, charge, 'open', want_knn=True, device_out=True)
@@ -391,9 +440,10 @@ def main():
     if world > 1:
         degree = args.shard_degree or world
         ns = min(256, q.n)
-        ref = sl._search_batch(q.select(torch.arange(ns, device=dev)), charge, 'open',
-                               device_out=True)          # unsharded result of my first queries
-        if degree > 1:
+        if args.full:
+            ref = sl._search_batch(q.select(torch.arange(ns, device=dev)), charge, 'open',
+                                   device_out=True)          # unsharded result of my first queries
+        if degree > 1 and args.full:
             # the other layout the library supports, for the record (not `value`): every
             # rank a full replica serving its own slice, no collective on the data path --
             # pipelined as a replica would run (the sharded step below is not)
@@ -457,12 +507,13 @@ def main():
             raise RuntimeError('injected failure of the sharded path')
         if degree > 1 and os.environ.get('ASL_BENCH_INJECT') == 'hang':
             time.sleep(1e6)
-        got = step()                     # (ring element 0 = q)
-        same = bool(torch.equal(got.best_row[:ns], ref.best_row) and
-                    torch.equal(got.best_score[:ns], ref.best_score))
-        flag = torch.tensor([int(same)])
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)              # control plane
-        shard_check = {'queries_per_rank': ns, 'sharded_equals_unsharded': bool(flag.item())}
+        if args.full:
+            got = step()                     # (ring element 0 = q)
+            same = bool(torch.equal(got.best_row[:ns], ref.best_row) and
+                        torch.equal(got.best_score[:ns], ref.best_score))
+            flag = torch.tensor([int(same)])
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)              # control plane
+            shard_check = {'queries_per_rank': ns, 'sharded_equals_unsharded': bool(flag.item())}
     else:
         step = unsharded_step
 
@@ -483,13 +534,55 @@ def main():
     # inside the timed region only the dominant kernel -- the list scan -- is bracketed by HIP
     # events on the stream it is launched on (two per step: `roofline.achieved`); the other stages
     # are timed in a second pass of the same steps right after it (events around every stage keep
-    # a pipelined step's kernels from being dispatched back to back: 0.3 ms of 7.9 in round 4)
-    L.asl_profile_enable(2)
-    L.asl_profile_reset()
+    # a pipelined step's kernels from being dispatched back to back: 0.3 ms of 7.9 in round 4).
+    # Without --full nothing is bracketed: the scan's events serve the roofline alone
+    if args.full:
+        L.asl_profile_enable(2)
+        L.asl_profile_reset()
     _FALLBACK['stage'] = 'timed steps'
     elapsed, res = timed(step, args.steps)
     _FALLBACK['stage'] = 'after the timed steps (collectives alone, second pass, legs)'
     sl.synchronize()            # reports any error a pipelined batch deferred
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {name: getattr(res, name) for name in
+                                         ('best_row', 'best_score', 'n_candidates', 'pm_count', 'pm_pairs')})
+
+    def headline():
+        """The fields of the result line that the timed steps alone determine (the whole line without --full)."""
+        return {
+            'metric': 'query spectra/sec + recall@k vs brute-force, open-mod search on MassIVE-KB',
+            'value': round(world * args.batch * args.steps / elapsed, 2),
+            'unit': 'query spectra/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+            'ms_per_step': round(elapsed / args.steps * 1e3, 3),
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+            'dtype': 'f32', 'data': 'synthetic',
+            'batch_per_step': args.batch,
+            'config': {'workload': f'configs[2]: MassIVE-KB-scale synthetic library '
+                                   f'({args.library_size} spectra, one charge-{charge} partition), '
+                                   f'{args.index} m={args.pq_m} nlist={args.nlist} nprobe={args.nprobe} '
+                                   f'k={args.k}{f" (exact re-rank of {args.refine_k})" if args.refine_k else ""}, open +-{args.open_da:g} Da, shifted dot, '
+                                   f'fragment tol 0.02 Da',
+                       'library_size': args.library_size, 'batch_per_gpu': args.batch,
+                       'reference_default_batch_size': 16384,
+                       'distinct_batches_in_the_timed_loop': ring,
+                       'global_batch': world * args.batch, 'index': args.index,
+                       'nlist': args.nlist, 'nprobe': args.nprobe, 'k': args.k,
+                       'refine_k': args.refine_k or None,
+                       'parallelism': 'single' if world == 1 else
+                       (f'ivf-list-shard x{degree}' if degree == world else
+                        f'replicas x{world}' if degree == 1 else
+                        f'ivf-list-shard x{degree} in {world // degree} replica groups')},
+        }
+
+    if not args.full:
+        sl.set_pipeline(False)
+        if rank == 0:
+            emit_line(json.dumps(dict(headline(), pipeline={'streams': 2 if pipelined else 1})))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     if world > 1 and degree > 1:
         # bytes every collective of a step moved (counted inside the timed steps) and what each
         # costs on its own at its real per-chunk size (outside the timed region, after it)
@@ -817,7 +910,6 @@ def main():
             f'query scans half of the library), open +-{args.open_da:g} Da, shifted dot')
 
     if rank == 0:
-        total_queries = world * args.batch * args.steps
         scan = stages['scan']
         roofline = None
         if scan['launches'] > 0 and scan['ms_total'] > 0:
@@ -889,7 +981,8 @@ def main():
         cascade = None
         if world == 1 and not args.no_cascade:
             from argparse import Namespace
-            a_c = Namespace(**{**vars(args), 'steps': max(1, min(args.steps, 10)), 'warmup': max(1, min(args.warmup, 2))})
+            a_c = Namespace(**{**vars(args), 'steps': max(1, min(args.steps, 10)), 'warmup': max(1, min(args.warmup, 2)),
+                               'dump_outputs': None})
             c = cascade_pass(a_c, 1, 0, dev, backend, sl, lib, aux, charge, cfg,
                              parity_seconds=min(args.cpu_seconds, 8.0), oracle_ctx=ctx)
             cascade = {'workload': c['config']['workload'], 'value': c['value'], 'unit': c['unit'],
@@ -898,18 +991,11 @@ def main():
                        'identifications': c['identifications'],
                        'parity_vs_oracle': c.get('parity_vs_oracle'),
                        'device_stages_ms_per_pass': c['device_stages_ms_per_step']}
-        out = {
-            'metric': 'query spectra/sec + recall@k vs brute-force, open-mod search on MassIVE-KB',
-            'value': round(total_queries / elapsed, 2),
-            'unit': 'query spectra/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': round(elapsed / args.steps * 1e3, 3),
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'f32', 'data': 'synthetic',
+        out = headline()
+        out.update({
             # the metric is "spectra/s + recall@k" and the north star asks for it "at fixed recall@k":
             # the companions of `value`, at the top level (details in `recall`, `fixed_recall`,
             # `at_reference_batch_size`)
-            'batch_per_step': args.batch,
             'recall_at_k': None if recall is None else round(recall['recall_at_k_vs_exact_ip'], 5),
             'hit_at_k': None if recall is None else round(recall['hit_at_k_source_spectrum'], 5),
             'meets_fixed_recall_criterion': None if recall is None else recall.get('meets_criterion'),
@@ -917,21 +1003,6 @@ def main():
             'recall_at_k_at_fixed_recall': None if fixed_recall is None else fixed_recall.get('recall_at_k_vs_exact_ip'),
             'value_at_reference_batch': None if ref_batch is None else ref_batch['value'],
             'reference_batch': None if ref_batch is None else ref_batch['batch'],
-            'config': {'workload': f'configs[2]: MassIVE-KB-scale synthetic library '
-                                   f'({args.library_size} spectra, one charge-{charge} partition), '
-                                   f'{args.index} m={args.pq_m} nlist={args.nlist} nprobe={args.nprobe} '
-                                   f'k={args.k}{f" (exact re-rank of {args.refine_k})" if args.refine_k else ""}, open +-{args.open_da:g} Da, shifted dot, '
-                                   f'fragment tol 0.02 Da',
-                       'library_size': args.library_size, 'batch_per_gpu': args.batch,
-                       'reference_default_batch_size': 16384,
-                       'distinct_batches_in_the_timed_loop': ring,
-                       'global_batch': world * args.batch, 'index': args.index,
-                       'nlist': args.nlist, 'nprobe': args.nprobe, 'k': args.k,
-                       'refine_k': args.refine_k or None,
-                       'parallelism': 'single' if world == 1 else
-                       (f'ivf-list-shard x{degree}' if degree == world else
-                        f'replicas x{world}' if degree == 1 else
-                        f'ivf-list-shard x{degree} in {world // degree} replica groups')},
             'pipeline': {'streams': 2 if pipelined else 1,
                          'note': 'stage times overlap across consecutive steps when true: their '
                                  'sum exceeds ms_per_step',
@@ -969,7 +1040,7 @@ def main():
             'at_reference_batch_size': ref_batch,
             'roofline': roofline,
             'cpu_baseline': cpu,
-        }
+        })
         _disarm_fallback()
         emit_line(json.dumps(out))
     _disarm_fallback()
@@ -1005,12 +1076,13 @@ def cascade_pass(args, world, rank, dev, backend, sl, lib, aux, charge, cfg, dat
     """BASELINE configs[4]: the reference's two-level cascade (spectral_library.py:237-259) --
     standard search (20 ppm window, no ANN) of every query, a gate standing for the mokapot FDR
     filter, then the open search (ANN + +-open Da window, shifted dot) of the unidentified
-    remainder -- through ``SpectralLibrary.search`` (results as a columnar SSM table; the
-    reference-shaped SSM records are materialised after the timed pass and reported). With N > 1 the
+    remainder -- through ``SpectralLibrary.search`` (results as a columnar SSM table). With N > 1 the
     library's IVF lists are sharded over the ranks (``enable_sharding``): level 1 is data-parallel
     over the queries, level 2 is the list-sharded search. One "step" = one pass over
-    ``cascade_batches`` x ``batch`` queries per GPU. Returns the JSON object (rank 0; None elsewhere);
-    ``parity_seconds`` > 0 adds ``parity_vs_oracle``: a sample of the pass's queries through the
+    ``cascade_batches`` x ``batch`` queries per GPU. Returns the JSON object (rank 0; None elsewhere).
+    With ``args.full`` also: the sharded-vs-unsharded check (N > 1), the device stages of one more
+    pass, the reference-shaped SSM records materialised after the timed pass, and -- for
+    ``parity_seconds`` > 0 -- ``parity_vs_oracle``: a sample of the pass's queries through the
     oracle's two levels (``cascade_parity``)."""
     import numpy as np
     import torch
@@ -1041,17 +1113,20 @@ def cascade_pass(args, world, rank, dev, backend, sl, lib, aux, charge, cfg, dat
         o = np.argsort(t.qrow, kind='stable')
         return t.qrow[o], t.lib_row[o], t.score[o], t.q[o]
     check = None
-    if world > 1:                   # the same queries through one GPU, before the index is sharded
-        ns = min(2 * args.batch // 8 + 37, nq)          # ragged against batch and world
-        qs, qm = sub(ns)
-        ref = key(sl.search(qs, qm, lmeta, score_ssms=gate))
+    full = args.full
+    if world > 1:
+        if full:                    # the same queries through one GPU, before the index is sharded
+            ns = min(2 * args.batch // 8 + 37, nq)          # ragged against batch and world
+            qs, qm = sub(ns)
+            ref = key(sl.search(qs, qm, lmeta, score_ssms=gate))
         sl.enable_sharding(data_group)       # the data plane's group (RCCL; None = the default gloo group)
-        got = key(sl.search(qs, qm, lmeta, score_ssms=gate))
-        same = all(np.array_equal(a, b) for a, b in zip(ref, got))
-        flag = torch.tensor([int(same)])
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)          # control plane: gloo, host tensor
-        check = {'queries': ns, 'identifications': int(len(ref[0])),
-                 'sharded_cascade_equals_unsharded': bool(flag.item())}
+        if full:
+            got = key(sl.search(qs, qm, lmeta, score_ssms=gate))
+            same = all(np.array_equal(a, b) for a, b in zip(ref, got))
+            flag = torch.tensor([int(same)])
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)          # control plane: gloo, host tensor
+            check = {'queries': ns, 'identifications': int(len(ref[0])),
+                     'sharded_cascade_equals_unsharded': bool(flag.item())}
     for _ in range(args.warmup):
         qs, qm = sub(min(nq, 2 * args.batch))
         sl.search(qs, qm, lmeta, score_ssms=gate)
@@ -1073,27 +1148,27 @@ def cascade_pass(args, world, rank, dev, backend, sl, lib, aux, charge, cfg, dat
         t = torch.tensor([el], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
-    # the device stages of ONE more pass, events around every stage (not part of `value`)
-    level_seconds, sl.level_seconds = sl.level_seconds, {}
-    L.asl_profile_reset()
-    L.asl_profile_enable(1)
-    sl.search({charge: q}, qmeta, lmeta, score_ssms=gate)
-    barrier()
-    L.asl_profile_enable(0)
-    sl.level_seconds = level_seconds
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(('qrow', 'lib_row', 'score', 'q'), key(ids))))
+    if full:
+        # the device stages of ONE more pass, events around every stage (not part of `value`)
+        level_seconds, sl.level_seconds = sl.level_seconds, {}
+        L.asl_profile_reset()
+        L.asl_profile_enable(1)
+        sl.search({charge: q}, qmeta, lmeta, score_ssms=gate)
+        barrier()
+        L.asl_profile_enable(0)
+        sl.level_seconds = level_seconds
     if rank != 0:
         return None
-    stages = {}
-    for name in ('encode', 'coarse_gemm', 'coarse_select', 'scan', 'filter', 'rescore',
-                 'rescore_matches'):
-        ms, n = C.c_double(), C.c_int64()
-        L.asl_profile_get(name.encode(), C.byref(ms), C.byref(n))
-        stages[name] = round(ms.value, 3)
     src = truth['source_row'].cpu().numpy()
     correct = int((ids.lib_row == src[ids.qrow]).sum())
-    t0 = time.perf_counter()
-    n_obj = len(ids.materialize())          # the reference-shaped SSM records, outside the timed pass
-    t_obj = time.perf_counter() - t0
+    identifications = {'total': len(ids), 'source_spectrum_identified': correct, 'queries': nq}
+    if full:
+        t0 = time.perf_counter()
+        n_obj = len(ids.materialize())          # the reference-shaped SSM records, outside the timed pass
+        identifications.update(ssm_records_materialised_after_the_pass=n_obj,
+                               materialise_seconds=round(time.perf_counter() - t0, 3))
     lv = {}
     for mode, (sec, n_in, n_out) in sl.level_seconds.items():
         lv[mode] = {'queries_in_per_step': n_in // args.steps, 'ssms_out_per_step': n_out // args.steps,
@@ -1114,13 +1189,17 @@ def cascade_pass(args, world, rank, dev, backend, sl, lib, aux, charge, cfg, dat
                    'parallelism': 'single' if world == 1 else
                    f'level 1 query-parallel x{world}, level 2 ivf-list-shard x{world}'},
         'levels': lv,
-        'identifications': {'total': len(ids), 'source_spectrum_identified': correct,
-                            'queries': nq,
-                            'ssm_records_materialised_after_the_pass': n_obj,
-                            'materialise_seconds': round(t_obj, 3)},
-        'cascade_check': check,
-        'device_stages_ms_per_step': stages,
+        'identifications': identifications,
     }
+    if not full:
+        return out
+    stages = {}
+    for name in ('encode', 'coarse_gemm', 'coarse_select', 'scan', 'filter', 'rescore',
+                 'rescore_matches'):
+        ms, n = C.c_double(), C.c_int64()
+        L.asl_profile_get(name.encode(), C.byref(ms), C.byref(n))
+        stages[name] = round(ms.value, 3)
+    out.update(cascade_check=check, device_stages_ms_per_step=stages)
     if parity_seconds > 0 and world == 1:
         out['parity_vs_oracle'] = cascade_parity(args, sl, part, charge, cfg, q, ids, thr, parity_seconds,
                                                  oracle_ctx, nprobe)

@@ -12,8 +12,8 @@ timeout 300 python3 scripts/fuzz_pre.py 180 $((seed+4)) 2>&1 | grep -v amdgpu.id
 tail -n 2 $out/fuzz_*.log
 timeout 1500 python -m pytest tests -q -m gpu 2>&1 | tail -4 > $out/pytest_gpu.log
 cat $out/pytest_gpu.log
-python3 bench.py > $out/bench.json 2> $out/bench.err
-python3 bench.py --index ivfflat --nprobe 112 > $out/ivfflat_np112_bench.json 2> $out/ivfflat_np112_bench.err
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
+python3 bench.py --full --index ivfflat --nprobe 112 > $out/ivfflat_np112_bench.json 2> $out/ivfflat_np112_bench.err
 python3 -c "
 import json
 d=json.load(open('$out/bench.json')); print({k:d[k] for k in ('value','ms_per_step','value_at_fixed_recall','value_at_reference_batch')}, d['roofline']['frac'], d['roofline']['traffic'], d['roofline']['beyond_llc']['frac'])

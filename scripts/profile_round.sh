@@ -4,6 +4,7 @@
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 tag=$1; shift
+set -- --full "$@"          # the bench lines for profiles/ carry every leg (roofline, stages, ...)
 mkdir -p gpurun_out/$tag
 python3 bench.py "$@" > gpurun_out/$tag/bench.json 2> gpurun_out/$tag/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -o x -- python3 bench.py --cpu-seconds 0 --no-reference-geometry "$@" > gpurun_out/$tag/bench_under_rocprof.json 2> /tmp/prof_$tag.err

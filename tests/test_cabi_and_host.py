@@ -410,3 +410,32 @@ def test_bench_help_prints():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True,
                          timeout=120)
     assert out.returncode == 0 and '--beyond-llc-chunks' in out.stdout, out.stderr[-500:]
+    assert '--full' in out.stdout and '--dump-outputs' in out.stdout
+
+
+def test_bench_dump_outputs_exact_and_bounded(tmp_path):
+    """bench.dump_outputs (--dump-outputs): ids and scores come back exactly (float64; the peak-match
+    pairs as float32), and an output above the 64 MB bound keeps the same seeded rows in every run."""
+    import glob
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(5)
+    n = 1 << 17
+    small = {'best_row': rng.integers(-1, 2 ** 31 - 1, 1000).astype(np.int32), 'best_score': rng.random(1000),
+             'pm_pairs': rng.integers(0, 1 << 20, (1000, 50, 2)).astype(np.int32), 'knn': None}
+    bench.dump_outputs(str(tmp_path / 's'), small)
+    got = {os.path.basename(f)[:-4]: np.load(f) for f in glob.glob(str(tmp_path / 's' / '*.npy'))}
+    assert set(got) == {'best_row', 'best_score', 'pm_pairs'}
+    assert got['best_row'].dtype == np.float64 and np.array_equal(got['best_row'], small['best_row'])
+    assert np.array_equal(got['best_score'], small['best_score'])
+    assert got['pm_pairs'].dtype == np.float32 and np.array_equal(got['pm_pairs'], small['pm_pairs'])
+    big = {'best_row': np.arange(n, dtype=np.int32), 'pm_pairs': rng.integers(0, 300, (n, 256, 2)).astype(np.int32)}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), big)
+        files = glob.glob(str(tmp_path / d / '*.npy'))
+        assert sum(os.path.getsize(f) for f in files) <= 64e6
+    rows = np.load(str(tmp_path / 'a' / 'pm_pairs_rows.npy'))
+    assert 0 < len(rows) < n and np.array_equal(rows, np.load(str(tmp_path / 'b' / 'pm_pairs_rows.npy')))
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'pm_pairs.npy')), big['pm_pairs'][rows.astype(np.int64)])
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'best_row.npy')), big['best_row'])

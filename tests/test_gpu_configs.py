@@ -98,7 +98,7 @@ def test_config1_ivfflat_default_parameters(O, iprg):
 
 
 def test_default_bench_line_at_small_size():
-    """The driver's `python bench.py` line, at a size that takes seconds: every block the round-4
+    """`python bench.py --full` at a size that takes seconds: every block the round-4
     line carries must be there and its parity flags true -- recall with the exact hit@k fields,
     the fixed-recall leg with its own roofline / parity / CPU baseline, the configs[4] cascade
     pass with oracle parity, the stage rates with the candidate count the kernel reports."""
@@ -109,7 +109,7 @@ def test_default_bench_line_at_small_size():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--library-size', '60000', '--nlist', '256',
            '--niter', '4', '--batch', '1024', '--steps', '2', '--warmup', '1', '--cpu-seconds', '2',
-           '--recall-queries', '64', '--cascade-batches', '2', '--nprobe', '32', '--k', '256']
+           '--recall-queries', '64', '--cascade-batches', '2', '--nprobe', '32', '--k', '256', '--full']
     out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
     line = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert line, out.stderr[-3000:]
@@ -131,3 +131,47 @@ def test_default_bench_line_at_small_size():
     assert c['parity_vs_oracle']['all_equal'] is True and c['parity_vs_oracle']['queries'] >= 64
     g = d['stages_gbs']
     assert g['rescore']['candidate_count_equals_the_kernels'] is True and g['encode']['GBps'] > 0
+
+
+@pytest.mark.parametrize('workload', ['batch', 'cascade'])
+def test_plain_bench_line_and_dumped_outputs(tmp_path, workload):
+    """`python bench.py` without --full: one line with the headline fields and none of the other legs;
+    --dump-outputs writes what the last timed step returned, and two runs with the same arguments
+    write the same arrays."""
+    import glob
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n_batch, steps = 1024, 3
+
+    def run(out_dir):
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--library-size', '60000', '--nlist', '256',
+               '--niter', '4', '--batch', str(n_batch), '--steps', str(steps), '--warmup', '1', '--nprobe', '32',
+               '--k', '256', '--workload', workload, '--dump-outputs', str(out_dir)]
+        out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1 and lines[0].startswith('{'), (out.stdout[:500], out.stderr[-2000:])
+        files = sorted(glob.glob(os.path.join(str(out_dir), '*.npy')))
+        assert sum(os.path.getsize(f) for f in files) <= 64e6
+        return json.loads(lines[0]), {os.path.basename(f)[:-4]: np.load(f) for f in files}
+    d, a = run(tmp_path / 'a')
+    assert d['metric'].startswith('query spectra/sec') and d['unit'] == 'query spectra/s'
+    assert d['higher_is_better'] is True and d['dtype'] == 'f32' and d['steps'] == steps and d['n_gpus'] == 1
+    assert d['value'] > 0 and d['ms_per_step'] > 0
+    for leg in ('recall', 'fixed_recall', 'roofline', 'cpu_baseline', 'cascade', 'parity_vs_oracle',
+                'device_stages_ms_per_step'):
+        assert leg not in d, leg
+    if workload == 'batch':
+        nq = d['batch_per_step']
+        assert d['value'] == pytest.approx(nq / (d['ms_per_step'] * 1e-3), rel=1e-3)
+        assert set(a) == {'best_row', 'best_score', 'n_candidates', 'pm_count', 'pm_pairs'}
+        assert all(a[k].shape == (nq,) and a[k].dtype == np.float64 for k in a if k != 'pm_pairs')
+        assert a['pm_pairs'].dtype == np.float32 and a['pm_pairs'].shape[0] == nq
+        assert (a['best_row'] >= -1).all() and (a['best_row'] < 60000).all() and (a['best_row'] >= 0).any()
+    else:
+        assert set(a) == {'qrow', 'lib_row', 'score', 'q'} and len(a['qrow']) == d['identifications']['total']
+    _, b = run(tmp_path / 'b')
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k], equal_nan=True) for k in a)

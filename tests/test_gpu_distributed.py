@@ -33,7 +33,7 @@ def test_two_rank_sharded_bench_path(degree, index, extra):
            str(29517 + degree + (5 if index == 'ivfflat' else 0)),
            os.path.join(ROOT, 'bench.py'),
            '--gpus', '2', '--steps', '1', '--warmup', '1', '--library-size', '60000', '--nlist',
-           '256', '--niter', '4', '--batch', '1024', '--recall-queries', '64',
+           '256', '--niter', '4', '--batch', '1024', '--recall-queries', '64', '--full',
            '--shard-degree', str(degree), '--index', index] + extra
     cmd[cmd.index('--master-port') + 1] = str(int(cmd[cmd.index('--master-port') + 1]) + 20 * len(extra))
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -80,7 +80,8 @@ def test_a_failing_sharded_path_still_yields_the_replicas_line(how):
     env.update(ASL_BENCH_BACKEND='gloo', ASL_BENCH_INJECT=how)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'),
            '--gpus', '2', '--steps', '1', '--warmup', '1', '--library-size', '60000', '--nlist',
-           '256', '--niter', '4', '--batch', '1024', '--recall-queries', '64', '--sharded-watchdog-seconds', '15']
+           '256', '--niter', '4', '--batch', '1024', '--recall-queries', '64', '--sharded-watchdog-seconds', '15',
+           '--full']
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -98,7 +99,7 @@ def test_plain_bench_command_starts_two_ranks():
     env['ASL_BENCH_BACKEND'] = 'gloo'
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'),
            '--gpus', '2', '--steps', '1', '--warmup', '1', '--library-size', '60000', '--nlist',
-           '256', '--niter', '4', '--batch', '1024', '--recall-queries', '64']
+           '256', '--niter', '4', '--batch', '1024', '--recall-queries', '64', '--full']
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.strip()]
@@ -106,6 +107,27 @@ def test_plain_bench_command_starts_two_ranks():
     d = json.loads(line[0])
     assert d['n_gpus'] == 2 and d['config']['global_batch'] == 2048
     assert d['shard_check']['sharded_equals_unsharded'] is True and d['value'] > 0
+
+
+def test_plain_two_rank_bench_line_and_dumped_outputs(tmp_path):
+    """Without --full the list-sharded run times its steps and prints the headline alone; rank 0 dumps its
+    slice of the last timed step (--dump-outputs), whose winners lie in the unsharded library."""
+    env = {k: v for k, v in os.environ.items()
+           if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
+    env['ASL_BENCH_BACKEND'] = 'gloo'
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'),
+           '--gpus', '2', '--steps', '2', '--warmup', '1', '--library-size', '60000', '--nlist',
+           '256', '--niter', '4', '--batch', '1024', '--dump-outputs', str(tmp_path)]
+    out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(line) == 1 and line[0].startswith('{'), (out.stdout[:500], out.stderr[-2000:])
+    d = json.loads(line[0])
+    assert d['n_gpus'] == 2 and d['steps'] == 2 and d['config']['parallelism'] == 'ivf-list-shard x2'
+    assert d['value'] > 0 and d['ms_per_step'] > 0
+    assert 'shard_check' not in d and 'comm' not in d and 'roofline' not in d
+    best = np.load(str(tmp_path / 'best_row.npy'))
+    assert best.shape == (1024,) and (best >= -1).all() and (best < 60000).all() and (best >= 0).any()
 
 
 @pytest.mark.parametrize('index,extra', [
@@ -121,7 +143,7 @@ def test_two_rank_sharded_bench_path_rccl_form_of_the_collectives(index, extra):
            '--master-addr', '127.0.0.1', '--master-port', str(29611 + len(extra) + (3 if index == 'ivfflat' else 0)),
            os.path.join(ROOT, 'bench.py'),
            '--gpus', '2', '--steps', '2', '--warmup', '1', '--library-size', '60000', '--nlist',
-           '256', '--niter', '4', '--batch', '1024', '--recall-queries', '64', '--index', index] + extra
+           '256', '--niter', '4', '--batch', '1024', '--recall-queries', '64', '--full', '--index', index] + extra
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     line = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert line, out.stderr[-2000:]
@@ -150,7 +172,7 @@ def test_two_rank_sharded_cascade(index):
            str((29541 if index == 'ivfpq' else 29542) + 2 * int(env.get('MASTER_PORT_SHIFT', 0))),
            os.path.join(ROOT, 'bench.py'), '--workload', 'cascade',
            '--gpus', '2', '--steps', '1', '--warmup', '1', '--library-size', '60000', '--nlist',
-           '256', '--niter', '4', '--batch', '1024', '--cascade-batches', '2', '--index', index]
+           '256', '--niter', '4', '--batch', '1024', '--cascade-batches', '2', '--full', '--index', index]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     line = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert line, out.stderr[-3000:]
