@@ -61,7 +61,7 @@ class AslIndexInfo(C.Structure):
 
 EXPORTS = [
     'asl_last_error', 'asl_version', 'asl_get_num_gpus', 'asl_set_device', 'asl_set_stream',
-    'asl_synchronize', 'asl_set_pipeline', 'asl_set_scan_postfilter', 'asl_get_dim', 'asl_hash_idx', 'asl_encode_batch', 'asl_index_create',
+    'asl_synchronize', 'asl_set_pipeline', 'asl_set_scan_postfilter', 'asl_set_window_pair_budget', 'asl_get_dim', 'asl_hash_idx', 'asl_encode_batch', 'asl_index_create',
     'asl_index_free', 'asl_index_train', 'asl_index_add', 'asl_index_add_preassigned', 'asl_index_search',
     'asl_index_reset', 'asl_index_ntotal', 'asl_index_is_trained', 'asl_index_save',
     'asl_index_load', 'asl_index_set_niter', 'asl_index_info', 'asl_index_get_centroids',
@@ -231,6 +231,8 @@ def lib():
         L.asl_window_candidates.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                             C.c_double, C.c_int32, C.c_void_p, C.c_void_p]
         L.asl_set_stream.argtypes = [C.c_void_p]
+        L.asl_set_window_pair_budget.argtypes = [C.c_int64]
+        L.asl_set_window_pair_budget.restype = C.c_int64
         L.asl_profile_get.argtypes = [C.c_char_p, c_f64p, c_i64p]
         L.asl_profile_scanned_vectors.restype = C.c_int64
         _lib = L

@@ -38,7 +38,7 @@ constexpr int RS_WAVES = 4;
 constexpr int RS_MAXP = 256;   // peaks per spectrum the kernels accept
 constexpr int RS_MCAP = 512;   // generated peak matches per pair the kernels accept
 
-enum { RS_STATUS_OK = 0, RS_STATUS_PEAKS = 1, RS_STATUS_MATCHES = 2 };
+enum { RS_STATUS_OK = 0, RS_STATUS_PEAKS = 1, RS_STATUS_MATCHES = 2, RS_STATUS_WINDOW = 4 };
 
 template <int MAXP_, int MCAP_>
 struct WaveLdsT {
@@ -320,7 +320,9 @@ __device__ __forceinline__ void load_query(int tid, int nthreads, const DevPeaks
   }
 }
 
-// Candidate addressing: CSR (cand_offsets != null) or fixed stride.
+// Candidate addressing: CSR (cand_offsets != null) or fixed stride; the CSR form either lists
+// row ids (rows64 / rows32) or, for the window-only modes, is a run of the precursor-sorted view
+// per query (win_begin: rescore.hpp, WindowRows).
 struct CandView {
   const int64_t *rows64;
   const int32_t *rows32;
@@ -331,10 +333,13 @@ struct CandView {
   // ScanPostFilter): counts[q] >= 0: the row holds that many hits, ALREADY filtered by the
   // precursor window; -1: the row holds `stride` unfiltered hits (filter here, as without counts)
   const int32_t *counts = nullptr;
+  const int32_t *win_begin = nullptr;   // WindowRows::begin / sorted_row / valid
+  const int32_t *win_rows = nullptr;
+  const uint8_t *win_valid = nullptr;
   __device__ __forceinline__ bool prefiltered(int q) const { return counts != nullptr && counts[q] >= 0; }
-  // row of slot c if it is a candidate of the query (in range, passes the filter), else -1
-  __device__ __forceinline__ long long cand(long long c, double q_pmz, int n_lib) const {
-    const long long r = row(c);
+  // row of query q's slot c if it is a candidate of the query (in range, passes the filter), else -1
+  __device__ __forceinline__ long long cand(int q, long long c, double q_pmz, int n_lib) const {
+    const long long r = row(q, c);
     return (r >= 0 && r < n_lib && filter_pass(flt, q_pmz, r)) ? r : -1;
   }
   __device__ __forceinline__ void range(int q, long long &c0, long long &c1) const {
@@ -351,7 +356,13 @@ struct CandView {
       c1 = c0 + len;
     }
   }
-  __device__ __forceinline__ long long row(long long c) const {
+  // library row of query q's slot c (-1: none; an invalid row of a window, as window_fill_kernel
+  // marks it)
+  __device__ __forceinline__ long long row(int q, long long c) const {
+    if (win_begin) {
+      const int32_t r = win_rows[(long long)win_begin[q] + (c - offsets[q])];
+      return (!win_valid || win_valid[r]) ? (long long)r : -1;
+    }
     return rows64 ? rows64[c] : (long long)rows32[c];
   }
 };
@@ -392,7 +403,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_score_kernel(
     const long long step = (long long)RS_WAVES * gridDim.y;
     for (long long c = c0 + (long long)blockIdx.y * RS_WAVES + wave; c < c1; c += step) {
       if (q_defer && pair_score[c] != -3.0) continue;
-      const long long row = cv.cand(c, q_pmz, L.n);
+      const long long row = cv.cand(q, c, q_pmz, L.n);
       double s = -1.0;
       if (row >= 0)
         s = dot_pair_wave<false>(lane, Q, qn, q_pmz, L, (int)row, tol, allow_shift, W[wave],
@@ -664,10 +675,11 @@ __device__ __forceinline__ void score_two(int lane, const QueryLds2 &Q, const Ha
                       : 0.0;
 }
 
-// FORM: the two shapes the search path calls with -- fixed-stride neighbour lists (1: int32
-// rows, 2: int64 rows), packed row records for the precursor filter, annotated library peaks --
+// FORM: the shapes the search path calls with -- fixed-stride neighbour lists (1: int32
+// rows, 2: int64 rows), packed row records for the precursor filter, annotated library peaks;
+// 3: the window-only modes' CSR runs of the precursor-sorted view (CandView::win_begin) --
 // are compiled with those facts folded in (each open "is this pointer null" question is a
-// wave-uniform predicate held in scalar registers across the hot loops); 0 = any shape.
+// wave-uniform predicate held in scalar registers across the hot loops); 0 = any shape but 3.
 // DEF: second-launch mode behind rescore_flat_kernel -- only the slots that kernel marked
 // RS_DEFER, only for queries whose q_defer has RS_QD_PAIR; what this kernel cannot resolve
 // either goes on to the binary-search kernel (RS_DEFER_BS / RS_QD_BS).
@@ -687,7 +699,19 @@ __global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel
     if ((int)blockIdx.y >= ny) return;
   }
   cv.flt.wcol = nullptr;      // this kernel wants filter column and metadata from ONE gather
-  if (FORM != 0) {
+  if (FORM != 3) cv.win_begin = nullptr;
+  if (FORM == 3) {            // window-only lists: a run of the precursor-sorted view per query
+    cv.rows64 = nullptr;
+    cv.rows32 = nullptr;
+    cv.counts = nullptr;
+    cv.flt.lib_pmz = nullptr;
+    cv.flt.valid = nullptr;
+    cv.flt.pass_all = true;
+    __builtin_assume(cv.offsets != nullptr);
+    __builtin_assume(cv.win_begin != nullptr);
+    __builtin_assume(cv.flt.meta != nullptr);
+    __builtin_assume(L.charge != nullptr);
+  } else if (FORM != 0) {
     cv.offsets = nullptr;
     cv.flt.lib_pmz = nullptr;
     cv.flt.valid = nullptr;
@@ -718,7 +742,7 @@ __global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel
   if (!(tol > 0.0) || qn > RS_HQ_MAX || margin > 0.45) {   // uniform: whole query deferred
     for (long long c = c0 + (long long)blockIdx.y * blockDim.x + tid; c < c1;
          c += (long long)blockDim.x * gridDim.y) {
-      pair_score[c] = cv.cand(c, q_pmz, L.n) >= 0 ? RS_DEFER_BS : -1.0;
+      pair_score[c] = cv.cand(q, c, q_pmz, L.n) >= 0 ? RS_DEFER_BS : -1.0;
     }
     if (tid == 0) atomicOr(&q_defer[q], RS_QD_BS);
     return;
@@ -767,7 +791,7 @@ __global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel
         if (DEF) {
           ok = pair_score[sb + i] == RS_DEFER;     // a valid candidate: the first launch checked
         } else {
-          ok = cv.cand(sb + i, q_pmz, L.n) >= 0;
+          ok = cv.cand(q, sb + i, q_pmz, L.n) >= 0;
           if (!ok && blockIdx.y == 0) pair_score[sb + i] = -1.0;
         }
         // several blocks per query: each takes the slots of every ny-th group of 32 (the order
@@ -792,7 +816,7 @@ __global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel
       int m_co = 0, m_cn = 0, m_chg = 0;
       double m_pmz = 0.0;
       if (okr) {
-        const long long row = cv.row(sb + slot);
+        const long long row = cv.row(q, sb + slot);
         if (cv.flt.meta) {     // one 32-byte sector per candidate
           const RowMeta *mr = meta_row(cv.flt, row);
           const uint4 a = *reinterpret_cast<const uint4 *>(mr);
@@ -907,7 +931,21 @@ template <int FORM>
 __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
     DevPeaks Qs, DevPeaks L, CandView cv, double tol, int allow_shift,
     double *__restrict__ pair_score, int *__restrict__ q_defer, int *status) {
-  if (FORM != 0) {
+  if (FORM != 3) cv.win_begin = nullptr;
+  if (FORM == 3) {            // window-only lists: a run of the precursor-sorted view per query
+    cv.rows64 = nullptr;
+    cv.rows32 = nullptr;
+    cv.counts = nullptr;
+    cv.flt.lib_pmz = nullptr;
+    cv.flt.valid = nullptr;
+    cv.flt.wcol = nullptr;
+    cv.flt.pass_all = true;
+    __builtin_assume(cv.offsets != nullptr);
+    __builtin_assume(cv.win_begin != nullptr);
+    __builtin_assume(cv.flt.meta != nullptr);
+    __builtin_assume(L.charge != nullptr);
+    __builtin_assume(L.records != nullptr);
+  } else if (FORM != 0) {
     cv.offsets = nullptr;
     cv.flt.lib_pmz = nullptr;
     cv.flt.valid = nullptr;
@@ -938,10 +976,10 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
   const bool pre = cv.prefiltered(q);
   auto is_cand = [&](long long c) -> bool {
     if (pre) {
-      const long long r = cv.row(c);
+      const long long r = cv.row(q, c);
       return r >= 0 && r < L.n;
     }
-    return cv.cand(c, q_pmz, L.n) >= 0;
+    return cv.cand(q, c, q_pmz, L.n) >= 0;
   };
   // (same bin filter as the pair kernel: see there)
   const double margin = 1e-3 + (tol > 0.0 ? (0.5 / tol) * (3.75e-4 + 2600.0 * 1.2e-7) : 1.0);
@@ -1018,7 +1056,7 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
       int m_co = 0, m_cn = 0, m_chg = 0;
       double m_pmz = 0.0;
       if (okr) {
-        const long long row = cv.row(sb + slot);
+        const long long row = cv.row(q, sb + slot);
         if (cv.flt.meta) {     // one 32-byte sector per candidate
           const RowMeta *mr = meta_row(cv.flt, row);
           const uint4 a = *reinterpret_cast<const uint4 *>(mr);
@@ -1245,7 +1283,7 @@ __global__ __launch_bounds__(64) void rescore_argmax_kernel(
     const double s = pair_score[c];
     if (s < 0.0) continue;
     ++cnt;
-    const long long key = tie_by_row ? cv.row(c) : c;
+    const long long key = tie_by_row ? cv.row(q, c) : c;
     if (s > bs || (s == bs && key < bkey)) {
       bs = s;
       bkey = key;
@@ -1286,7 +1324,7 @@ __device__ __forceinline__ void matches_one(int q, int lane, QL &Qw, WL &Ww, int
                                             int pm_stride, int32_t *__restrict__ best_row, int *status,
                                             int *__restrict__ m_defer) {
   const long long slot = best_slot[q];
-  const long long row = slot >= 0 ? cv.row(slot) : -1;
+  const long long row = slot >= 0 ? cv.row(q, slot) : -1;
   if (best_row && lane == 0) best_row[q] = (int32_t)row;
   if (row < 0) {
     if (pm_count && lane == 0) pm_count[q] = 0;
@@ -1364,13 +1402,21 @@ int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
                    int32_t *best_row, double *best_score, int32_t *n_valid,
                    int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride, int *status,
                    const PrecFilter &filter, bool clear_status, RescoreScratch *scratch,
-                   const int32_t *row_counts) {
+                   const int32_t *row_counts, const WindowRows *window, bool emit_matches) {
   const int nq = Q.n;
   if (nq == 0) return ASL_OK;
   if (!scratch) return fail(ASL_ERR_INVALID, "rescore: no scratch (internal)");
+  if (window && (!cand_offsets || rows64 || rows32 || !window->begin || !window->sorted_row ||
+                 !filter.meta || !L.charge || !L.records))
+    return fail(ASL_ERR_INVALID, "rescore: window lists need CSR offsets and packed rows (internal)");
   DevBuf<int> &q_defer = scratch->q_defer, &m_defer = scratch->m_defer;
   CandView cv{rows64, rows32, cand_offsets, stride, filter};
   cv.counts = cand_offsets ? nullptr : row_counts;
+  if (window) {
+    cv.win_begin = window->begin;
+    cv.win_rows = window->sorted_row;
+    cv.win_valid = window->valid;
+  }
   if (clear_status) HIP_TRY(hipMemsetAsync(status, 0, sizeof(int), stream()));
   {
     ProfScope ps("rescore");
@@ -1387,11 +1433,13 @@ int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
                           (rows64 || rows32);
       // 1. flat kernel; 2. pair kernel on what it marked RS_DEFER; 3. binary-search kernel on
       // RS_DEFER_BS (blocks of 2 / 3 return at once for queries without such slots)
-      auto flat = !shaped ? rescore_flat_kernel<0> : rows64 ? rescore_flat_kernel<2> : rescore_flat_kernel<1>;
+      auto flat = window ? rescore_flat_kernel<3>
+                  : !shaped ? rescore_flat_kernel<0> : rows64 ? rescore_flat_kernel<2> : rescore_flat_kernel<1>;
       hipLaunchKernelGGL(flat, dim3(nq, ysplit), dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, tol,
                          allow_shift, pair_score, q_defer.p, status);
       ASL_CHECK_LAUNCH();
-      auto kern = !shaped ? rescore_score_v2_kernel<0, true>
+      auto kern = window    ? rescore_score_v2_kernel<3, true>
+                  : !shaped ? rescore_score_v2_kernel<0, true>
                   : rows64 ? rescore_score_v2_kernel<2, true>
                            : rescore_score_v2_kernel<1, true>;
       hipLaunchKernelGGL(kern, dim3(nq, std::max(ysplit, RS_DEF_Y)), dim3(64 * RS_WAVES), 0, stream(), Q,
@@ -1409,7 +1457,7 @@ int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
                        pair_score, tie_by_row, best_cand, best_slot, best_score, n_valid);
     ASL_CHECK_LAUNCH();
   }
-  {
+  if (emit_matches) {
     ProfScope ps("rescore_matches");
     ASL_TRY(m_defer.reserve((size_t)nq));
     hipLaunchKernelGGL(rescore_matches_kernel<true>, dim3((unsigned)cdiv(nq, RS_WAVES)),
@@ -1424,11 +1472,68 @@ int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
   return ASL_OK;
 }
 
+// Tiled window search (search.hip): one thread per query of the tile. Each query's tiles are
+// folded in stream order, so the running best needs no atomics.
+__global__ __launch_bounds__(256) void window_merge_kernel(
+    CandView cv, int nq, const long long *__restrict__ best_slot, const double *__restrict__ best_score,
+    const int32_t *__restrict__ n_valid, double *__restrict__ run_score, int32_t *__restrict__ run_row,
+    int32_t *__restrict__ run_n) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  run_n[q] += n_valid[q];
+  const long long slot = best_slot[q];
+  if (slot < 0) return;
+  const int32_t r = (int32_t)cv.row(q, slot);
+  const double s = best_score[q];
+  const int32_t rr = run_row[q];
+  if (rr < 0 || s > run_score[q] || (s == run_score[q] && r < rr)) {   // tie_by_row = 1
+    run_score[q] = s;
+    run_row[q] = r;
+  }
+}
+
+__global__ __launch_bounds__(256) void window_finish_kernel(
+    int nq, const double *__restrict__ run_score, const int32_t *__restrict__ run_row,
+    const int32_t *__restrict__ run_n, const double *__restrict__ rescored, double *__restrict__ best_score,
+    int32_t *__restrict__ n_cand, int *status) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  const bool won = run_row[q] >= 0;
+  if (won && rescored[q] != run_score[q]) atomicOr(status, RS_STATUS_WINDOW);
+  if (best_score) best_score[q] = won ? run_score[q] : 0.0;
+  if (n_cand) n_cand[q] = run_n[q];
+}
+
+int rescore_window_merge(const WindowRows &window, const int32_t *cand_offsets, int nq,
+                         const long long *best_slot, const double *best_score, const int32_t *n_valid,
+                         double *run_score, int32_t *run_row, int32_t *run_n) {
+  if (nq <= 0) return ASL_OK;
+  CandView cv{nullptr, nullptr, cand_offsets, 0, PrecFilter()};
+  cv.win_begin = window.begin;
+  cv.win_rows = window.sorted_row;
+  cv.win_valid = window.valid;
+  hipLaunchKernelGGL(window_merge_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(), cv, nq,
+                     best_slot, best_score, n_valid, run_score, run_row, run_n);
+  ASL_CHECK_LAUNCH();
+  return ASL_OK;
+}
+
+int rescore_window_finish(int nq, const double *run_score, const int32_t *run_row, const int32_t *run_n,
+                          const double *rescored, double *best_score, int32_t *n_cand, int *status) {
+  if (nq <= 0) return ASL_OK;
+  hipLaunchKernelGGL(window_finish_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(), nq,
+                     run_score, run_row, run_n, rescored, best_score, n_cand, status);
+  ASL_CHECK_LAUNCH();
+  return ASL_OK;
+}
+
 int rescore_status_error(int st) {
   if (st & RS_STATUS_PEAKS)
     return fail(ASL_ERR_CAPACITY, "rescore: a spectrum has more than %d peaks", RS_MAXP);
   if (st & RS_STATUS_MATCHES)
     return fail(ASL_ERR_CAPACITY, "rescore: a pair generated more than %d peak matches", RS_MCAP);
+  if (st & RS_STATUS_WINDOW)
+    return fail(ASL_ERR_STATE, "rescore: a tiled window search's winner rescored to another score (internal)");
   return ASL_OK;
 }
 
@@ -1436,11 +1541,7 @@ int rescore_check_status(const int *status_dev) {
   int st = 0;
   HIP_TRY(hipMemcpyAsync(&st, status_dev, sizeof(int), hipMemcpyDeviceToHost, stream()));
   ASL_TRY(sync_stream());
-  if (st & RS_STATUS_PEAKS)
-    return fail(ASL_ERR_CAPACITY, "rescore: a spectrum has more than %d peaks", RS_MAXP);
-  if (st & RS_STATUS_MATCHES)
-    return fail(ASL_ERR_CAPACITY, "rescore: a pair generated more than %d peak matches", RS_MCAP);
-  return ASL_OK;
+  return rescore_status_error(st);
 }
 
 }  // namespace asl

@@ -65,6 +65,16 @@ struct RescoreScratch {
   DevBuf<int> q_defer, m_defer;
 };
 
+// Window-only candidate lists (asl_search_batch with use_ann = 0): no list of row ids, a query's
+// window is a run of the library's precursor-sorted view. With the CSR offsets of the call (32-bit,
+// tile-local), slot c of query q is the row sorted_row[begin[q] + (c - offsets[q])]; a row with
+// valid[row] == 0 is not a candidate (valid == nullptr: every row is).
+struct WindowRows {
+  const int32_t *begin = nullptr;
+  const int32_t *sorted_row = nullptr;
+  const uint8_t *valid = nullptr;
+};
+
 // Host driver shared by asl_rescore_batch, asl_search_batch and asl_rescore_knn. All pointers
 // are device pointers. pair_score scratch must hold one double per candidate slot.
 int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
@@ -76,7 +86,25 @@ int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
                    const PrecFilter &filter = PrecFilter(), bool clear_status = true,
                    RescoreScratch *scratch = nullptr,
                    // fixed-stride rows: their lengths as the scans' post-filter wrote them (-1: unfiltered row)
-                   const int32_t *row_counts = nullptr);
+                   const int32_t *row_counts = nullptr,
+                   // window-only lists (rows64 = rows32 = nullptr, cand_offsets tile-local; the
+                   // filter's packed row records and annotated library peaks required)
+                   const WindowRows *window = nullptr,
+                   // false: stop after the argmax (no best_row, pm_count, pm_pairs written)
+                   bool emit_matches = true);
+// Tiled window search: folds one tile's argmax (rescore_device's best_slot / best_score / n_valid
+// over the tile's nq queries, slots of the same window lists) into the running best of those
+// queries: a higher score wins, equal scores go to the lower library row, counts add up.
+// run_row < 0: no winner yet.
+int rescore_window_merge(const WindowRows &window, const int32_t *cand_offsets, int nq,
+                         const long long *best_slot, const double *best_score, const int32_t *n_valid,
+                         double *run_score, int32_t *run_row, int32_t *run_n);
+// After the last tile and the one-candidate pass over the winners (`rescored`: its best_score):
+// best_score = the merged score (0 without a winner), n_cand = the summed counts; a winner whose
+// rescored score differs from the merged one flags the status (an internal error).
+int rescore_window_finish(int nq, const double *run_score, const int32_t *run_row,
+                          const int32_t *run_n, const double *rescored, double *best_score,
+                          int32_t *n_cand, int *status);
 int rescore_check_status(const int *status_dev);   // reads the flags back: synchronises
 int rescore_status_error(int status_bits);         // ASL_OK or the error the flags stand for
 

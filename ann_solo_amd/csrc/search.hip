@@ -106,6 +106,9 @@ struct asl_library {
   bool p_have_ent[2] = {false, false};
   DevBuf<double> pair_score;
   DevBuf<long long> best_slot;
+  // tiled window search: per-tile CSR offsets + begins into sorted_row, running best of the batch
+  DevBuf<int32_t> wtile, run_row, run_n, tile_n;
+  DevBuf<double> run_score, tile_score;
   DevBuf<int> status;
   RescoreScratch rs_scratch;       // per-query flags between the rescoring launches of THIS handle's stream
 };
@@ -150,6 +153,13 @@ static int &scan_postfilter_flag() {
   return on;
 }
 static bool scan_postfilter_on() { return scan_postfilter_flag() == 1; }
+
+// Pairs one rescoring pass of a window-only search may hold (asl_set_window_pair_budget): 2^28
+// pair scores are 2 GiB of scratch. Capped at 2^31-1 where used: the tile-local offsets are 32-bit.
+static int64_t &window_pair_budget() {
+  static int64_t b = 1ll << 28;
+  return b;
+}
 static void offer_post_filter(asl_library *L, asl_index *idx, const DevPeaks &Q, const asl_search_params_t *P,
                               int32_t *row_len) {
   IndexPostFilter pf;
@@ -177,6 +187,15 @@ int asl_set_scan_postfilter(int on) {
   int &f = scan_postfilter_flag();
   const int prev = f;
   f = on ? 1 : 0;
+  return prev;
+}
+
+int64_t asl_set_window_pair_budget(int64_t pairs) {
+  clear_error();
+  if (pairs <= 0) return fail(ASL_ERR_INVALID, "set_window_pair_budget: the budget must be positive");
+  int64_t &b = window_pair_budget();
+  const int64_t prev = b;
+  b = pairs;
   return prev;
 }
 
@@ -323,6 +342,125 @@ static int window_candidates_device(asl_library *L, int nq, const double *q_pmz_
                      L->sorted_row.p, L->has_valid ? L->valid.p : nullptr, L->cand.p);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
+}
+
+// Window-only search of one batch (use_ann = 0: cascade level 'std', --mode bf). A query's
+// candidates are the run sorted_row[lo[q], lo[q] + cnt[q]) of the precursor-sorted view, read in
+// place by the rescoring kernels (rescore.hpp: WindowRows) -- no candidate list. The batch's pairs,
+// counted in 64 bits, are cut into tiles of at most window_pair_budget() pairs; a tile is a run of
+// queries whose first and last may bring only part of their window. One tile (every batch whose
+// pairs fit): the rescoring as for any list. Several: each tile's argmax is folded into a running
+// best (rescore_window_merge), then one pass over a one-candidate list per query -- its winner --
+// emits the peak matches. Scratch: pair scores of one tile, 12 bytes per query.
+static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_search_params_t *P,
+                                int32_t *best_row, double *best_score, int32_t *n_cand,
+                                int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride) {
+  const int nq = Q.n;
+  std::vector<int32_t> h_lo((size_t)nq), h_cnt((size_t)nq);
+  {
+    ProfScope ps("filter");
+    ASL_TRY(L->lo.reserve((size_t)nq));
+    ASL_TRY(L->cnt.reserve((size_t)nq));
+    hipLaunchKernelGGL(window_range_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(),
+                       Q.precursor_mz, nq, L->sorted_pmz.p, (int)L->n, P->charge, P->precursor_tol,
+                       P->precursor_mode, L->lo.p, L->cnt.p);
+    ASL_CHECK_LAUNCH();
+    ASL_TRY(L->lo.download(h_lo.data(), (size_t)nq));
+    ASL_TRY(L->cnt.download(h_cnt.data(), (size_t)nq));
+    ASL_TRY(sync_stream());
+  }
+  std::vector<int64_t> pre((size_t)nq + 1, 0);     // exclusive prefix of the window sizes
+  for (int q = 0; q < nq; q++) pre[(size_t)q + 1] = pre[(size_t)q] + h_cnt[(size_t)q];
+  const int64_t total = pre[(size_t)nq];
+  if (total == 0) {   // what the rescoring writes for empty lists
+    HIP_TRY(hipMemsetAsync(L->status.p, 0, sizeof(int), stream()));
+    if (best_row) HIP_TRY(hipMemsetAsync(best_row, 0xff, (size_t)nq * 4, stream()));
+    if (best_score) HIP_TRY(hipMemsetAsync(best_score, 0, (size_t)nq * 8, stream()));
+    if (n_cand) HIP_TRY(hipMemsetAsync(n_cand, 0, (size_t)nq * 4, stream()));
+    if (pm_count) HIP_TRY(hipMemsetAsync(pm_count, 0, (size_t)nq * 4, stream()));
+    if (pm_pairs) HIP_TRY(hipMemsetAsync(pm_pairs, 0, (size_t)nq * pm_stride * 8, stream()));
+    return ASL_OK;
+  }
+  const int64_t B = std::min<int64_t>(window_pair_budget(), 0x7fffffffLL);
+  PrecFilter rows_only;       // packed row records for the kernels, no second filtering
+  library_filter(L, rows_only);
+  rows_only.wcol = nullptr;
+  rows_only.pass_all = true;
+  WindowRows win;
+  win.sorted_row = L->sorted_row.p;
+  win.valid = L->has_valid ? L->valid.p : nullptr;
+  // every buffer before the first launch (growing one synchronises the device)
+  // (the winners' pass after several tiles scores one slot per query)
+  ASL_TRY(L->pair_score.reserve((size_t)(total <= B ? total : std::max<int64_t>(B, nq))));
+  ASL_TRY(L->rs_scratch.q_defer.reserve((size_t)nq));
+  ASL_TRY(L->rs_scratch.m_defer.reserve((size_t)nq));
+  if (total <= B) {   // one tile: the whole batch
+    std::vector<int32_t> h((size_t)2 * nq + 1);
+    for (int q = 0; q <= nq; q++) h[(size_t)q] = (int32_t)pre[(size_t)q];
+    for (int q = 0; q < nq; q++) h[(size_t)nq + 1 + q] = h_lo[(size_t)q];
+    ASL_TRY(L->wtile.upload(h.data(), h.size()));
+    win.begin = L->wtile.p + nq + 1;
+    return rescore_device(Q, L->dev, nullptr, nullptr, L->wtile.p, 0, total, P->fragment_mz_tolerance,
+                          P->allow_shift, 1, L->pair_score.p, L->best_slot.p, nullptr, best_row,
+                          best_score, n_cand, pm_count, pm_pairs, pm_stride, L->status.p, rows_only,
+                          true, &L->rs_scratch, nullptr, &win, true);
+  }
+  // tiles [t0, t1) of the global pair range; queries qa..qb (the query of pair t0 .. that of t1-1)
+  struct Tile {
+    int qa, nq;
+    int64_t pairs;
+    size_t idx;       // its offsets [nq + 1] and begins [nq] in wtile
+  };
+  std::vector<Tile> tiles;
+  std::vector<int32_t> h;
+  for (int64_t t0 = 0; t0 < total; t0 += B) {
+    const int64_t t1 = std::min(total, t0 + B);
+    const int qa = (int)(std::upper_bound(pre.begin(), pre.end(), t0) - pre.begin()) - 1;
+    const int qb = (int)(std::upper_bound(pre.begin(), pre.end(), t1 - 1) - pre.begin()) - 1;
+    Tile T{qa, qb - qa + 1, t1 - t0, h.size()};
+    h.resize(h.size() + 2 * (size_t)T.nq + 1);
+    int32_t *off = h.data() + T.idx, *beg = off + T.nq + 1;
+    for (int i = 0; i < T.nq; i++) {
+      const int q = qa + i;
+      const int64_t s = std::max(pre[(size_t)q], t0);
+      off[i] = (int32_t)(s - t0);
+      beg[i] = (int32_t)(h_lo[(size_t)q] + (s - pre[(size_t)q]));
+    }
+    off[T.nq] = (int32_t)(t1 - t0);
+    tiles.push_back(T);
+  }
+  ASL_TRY(L->wtile.upload(h.data(), h.size()));
+  ASL_TRY(L->run_score.reserve((size_t)nq));
+  ASL_TRY(L->run_row.reserve((size_t)nq));
+  ASL_TRY(L->run_n.reserve((size_t)nq));
+  ASL_TRY(L->tile_score.reserve((size_t)nq));
+  ASL_TRY(L->tile_n.reserve((size_t)nq));
+  HIP_TRY(hipMemsetAsync(L->run_score.p, 0, (size_t)nq * 8, stream()));
+  HIP_TRY(hipMemsetAsync(L->run_row.p, 0xff, (size_t)nq * 4, stream()));
+  HIP_TRY(hipMemsetAsync(L->run_n.p, 0, (size_t)nq * 4, stream()));
+  HIP_TRY(hipMemsetAsync(L->status.p, 0, sizeof(int), stream()));
+  for (const Tile &T : tiles) {
+    DevPeaks Qt = Q;            // the tile's queries: a view of the batch from query qa on
+    Qt.n = T.nq;
+    Qt.offsets += T.qa;
+    Qt.precursor_mz += T.qa;
+    if (Qt.precursor_charge) Qt.precursor_charge += T.qa;
+    const int32_t *off = L->wtile.p + T.idx;
+    win.begin = off + T.nq + 1;
+    ASL_TRY(rescore_device(Qt, L->dev, nullptr, nullptr, off, 0, T.pairs, P->fragment_mz_tolerance,
+                           P->allow_shift, 1, L->pair_score.p, L->best_slot.p, nullptr, nullptr,
+                           L->tile_score.p, L->tile_n.p, nullptr, nullptr, pm_stride, L->status.p,
+                           rows_only, false, &L->rs_scratch, nullptr, &win, false));
+    ASL_TRY(rescore_window_merge(win, off, T.nq, L->best_slot.p, L->tile_score.p, L->tile_n.p,
+                                 L->run_score.p + T.qa, L->run_row.p + T.qa, L->run_n.p + T.qa));
+  }
+  // the winners once more, as a one-candidate list per query (-1: none): rows and peak matches
+  ASL_TRY(rescore_device(Q, L->dev, nullptr, L->run_row.p, nullptr, 1, nq, P->fragment_mz_tolerance,
+                         P->allow_shift, 1, L->pair_score.p, L->best_slot.p, nullptr, best_row,
+                         L->tile_score.p, nullptr, pm_count, pm_pairs, pm_stride, L->status.p, rows_only,
+                         false, &L->rs_scratch));
+  return rescore_window_finish(nq, L->run_score.p, L->run_row.p, L->run_n.p, L->tile_score.p, best_score,
+                               n_cand, L->status.p);
 }
 
 int asl_window_candidates(asl_library_t *L, int32_t nq, const double *query_pmz, int32_t charge,
@@ -575,21 +713,8 @@ int asl_search_batch(asl_library_t *L, asl_index_t *idx, const asl_peaks_t *quer
                            o_pairs.d, pm_stride, L->status.p, flt, true, &L->rs_scratch,
                            rows_filtered ? L->rows_len.p : nullptr));
   } else {
-    int64_t total = 0;
-    {
-      ProfScope ps("filter");
-      ASL_TRY(window_candidates_device(L, nq, Q.dev.precursor_mz, P->charge, P->precursor_tol,
-                                       P->precursor_mode, &total));
-    }
-    ASL_TRY(L->pair_score.reserve((size_t)std::max<int64_t>(total, 1)));
-    PrecFilter rows_only;       // packed row records for the kernels, no second filtering
-    library_filter(L, rows_only);
-    rows_only.wcol = nullptr;
-    rows_only.pass_all = true;
-    ASL_TRY(rescore_device(Q.dev, L->dev, nullptr, L->cand.p, L->woff.p, 0, total,
-                           P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p,
-                           L->best_slot.p, nullptr, o_row.d, o_score.d, o_ncand.d, o_cnt.d,
-                           o_pairs.d, pm_stride, L->status.p, rows_only, true, &L->rs_scratch));
+    ASL_TRY(window_search_device(L, Q.dev, P, o_row.d, o_score.d, o_ncand.d, o_cnt.d, o_pairs.d,
+                                 pm_stride));
   }
   ASL_TRY(o_row.finish());
   ASL_TRY(o_score.finish());

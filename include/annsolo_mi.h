@@ -74,6 +74,14 @@ int asl_set_pipeline(int on);
  * Results are bit-identical. Returns the previous setting; environment ASL_SCAN_POSTFILTER=0 sets
  * the initial value. */
 int asl_set_scan_postfilter(int on);
+/* Pair budget of the window-only searches (asl_search_batch with use_ann = 0: cascade level 'std',
+ * brute-force open search): a batch whose (query, library row) pairs of the precursor windows
+ * number more than `pairs` is rescored in tiles of at most that many pairs (values above
+ * 2^31 - 1 act as 2^31 - 1), so the scratch of a batch -- 8 bytes per pair of a tile -- is bounded
+ * whatever its size and window width. Results do not depend on it. Default 2^28 (2 GiB).
+ * Returns the previous budget; pairs <= 0 is ASL_ERR_INVALID (returned, message in
+ * asl_last_error). Does not touch the device. */
+int64_t asl_set_window_pair_budget(int64_t pairs);
 
 /* ------------------------------------------------------------------ encoder
  * Replaces spectrum_to_vector / get_dim / hash_idx, src/ann_solo/spectrum.py:122-214
