@@ -76,6 +76,7 @@ EXPORTS = [
     'asl_keys_split', 'asl_keys_merge_heads', 'asl_keys_extras', 'asl_keys_merge_final',
     'asl_keys_rescan_list', 'asl_shard_k', 'asl_index_search_gated', 'asl_index_search_entries',
     'asl_encode_entries_batch', 'asl_index_search_sharded_ex',
+    'asl_index_set_window_key', 'asl_index_search_window', 'asl_index_set_window_scan',
 ]
 
 
@@ -171,6 +172,11 @@ def lib():
         L.asl_index_load.restype = C.c_void_p
         L.asl_index_set_niter.argtypes = [C.c_void_p, C.c_int32]
         L.asl_index_set_scan_variant.argtypes = [C.c_void_p, C.c_int32]
+        L.asl_index_set_window_key.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.asl_index_search_window.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_void_p]
+        L.asl_index_set_window_scan.argtypes = [C.c_void_p, C.c_int32]
         L.asl_index_set_flat_storage.argtypes = [C.c_void_p, C.c_int32]
         L.asl_index_flat_layout.argtypes = [C.c_void_p]
         L.asl_index_get_flat_storage.argtypes = [C.c_void_p]

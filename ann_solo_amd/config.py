@@ -77,6 +77,9 @@ class Config:
     flat_storage: str = 'fp32'              # IVF-Flat component storage: 'fp32' (as given: the reference's
                                             # CPU index) | 'fx22' (opt-in: 22-bit fixed point for
                                             # components in [0, 1), 4-byte postings, |dx| <= 1.2e-7)
+    ann_window: str = 'post'                # open search: 'post' (the reference's order: k best of the probed
+                                            # lists, then the precursor window) | 'pre' (opt-in, IVF-PQ: the k
+                                            # best in-window vectors of the probed lists)
 
     MAX_PEAKS = 256      # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
@@ -94,6 +97,16 @@ class Config:
                 raise ValueError(f'{name} = {v}: the device top-k holds at most {lim} entries')
         if self.flat_storage not in ('fx22', 'fp32'):
             raise ValueError(f"flat_storage = {self.flat_storage!r}: 'fx22' or 'fp32'")
+        if self.ann_window not in ('post', 'pre'):
+            raise ValueError(f"ann_window = {self.ann_window!r}: 'post' or 'pre'")
+        if self.ann_window == 'pre':
+            if self.index != 'ivfpq' or int(self.pq_m) != 32 or int(self.pq_bits) != 8:
+                raise ValueError("ann_window = 'pre' needs index = 'ivfpq' with pq_m = 32, pq_bits = 8 "
+                                 '(the window scan of the tiled IVF-PQ layout)')
+            if self.num_gpus and int(self.num_gpus) > 1:
+                raise ValueError("ann_window = 'pre' does not run on a sharded index (num_gpus > 1)")
+            if self.refine_k:
+                raise ValueError("ann_window = 'pre' does not combine with refine_k")
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -177,3 +190,8 @@ def add_arguments(parser) -> None:
                              'runs one process per GPU (torchrun --nproc-per-node N) and N must '
                              'equal this value; 0 or 1: every process searches the whole index '
                              '(default: %(default)s)')
+    parser.add_argument('--ann_window', default=d.ann_window, type=str, choices=['post', 'pre'],
+                        help="open search with the ANN index: 'post' keeps the k best vectors of the "
+                             "probed lists, then those in the precursor window (the reference); 'pre' "
+                             'keeps the k best vectors of the probed lists that are in the window '
+                             '(IVF-PQ, m = 32, 8 bits; one GPU) (default: %(default)s)')

@@ -217,6 +217,15 @@ __device__ __forceinline__ bool precursor_ok(double q, float lib, int charge, do
 // window column for that id; NaN = never a candidate): the value arrives with the id the finish
 // gathers anyway. count[q] = -1: the row holds the k UNFILTERED hits (the exact-flush fallback of a
 // row with mass ties emits through another path): the rescoring filters that row itself.
+// The window scan (asl_index_set_window_scan / asl_index_search_window): per (query, probe) the run
+// [lo, hi) of the probed list's positions, in the window-ordered layout, that pass the query's window;
+// set-mode rows then hold in-window hits only and row_len[q] their number (-1: not known, the row is
+// -1 padded).
+struct ScanRanges {
+  const int2 *range = nullptr;      // [nq, nprobe]; nullptr: whole lists
+  int32_t *row_len = nullptr;       // per query, out (set mode; may be nullptr)
+};
+
 struct ScanPostFilter {
   const int2 *idpay = nullptr;      // nullptr: no filter (every other field unused)
   const double *q_pmz = nullptr;    // per query
@@ -237,6 +246,16 @@ struct IndexPostFilter {
   int64_t n = 0;
   const double *q_pmz = nullptr;
   int32_t *count = nullptr;
+  double tol = 0.0;
+  int mode = ASL_TOL_DA;
+  int charge = 0;
+};
+
+// What an index in window-scan mode needs for its NEXT search (index_set_window): the queries'
+// precursor m/z (device), the window, and (set mode) where the rows' lengths go.
+struct IndexWindow {
+  const double *q_pmz = nullptr;
+  int32_t *row_len = nullptr;
   double tol = 0.0;
   int mode = ASL_TOL_DA;
   int charge = 0;

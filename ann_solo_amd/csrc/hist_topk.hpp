@@ -314,15 +314,17 @@ struct HistTopK {
   // gather instead of slot_ids' 4), only the passing hits are written (I32, unordered, compacted at
   // the front of the row through an LDS counter) and pf->count[q] says how many. The SELECTION of the
   // k hits is untouched (filter after top-k). Needs CAP more bytes of scratch behind the CAP keys.
-  __device__ __forceinline__ void finish_set(float *D, int64_t *I64, int32_t *I32, u64 *scratch,
-                                             const ScanPostFilter *pf = nullptr, int q = 0) {
+  // Returns (block-uniform) the number of hits written at the front of the row, or -1 where that is
+  // not known here (exact flushes were in use; with pf, pf->count holds it).
+  __device__ __forceinline__ int finish_set(float *D, int64_t *I64, int32_t *I32, u64 *scratch,
+                                            const ScanPostFilter *pf = nullptr, int q = 0) {
     __syncthreads();
     const bool filt = pf != nullptr && pf->idpay != nullptr && !out_keys && I32 != nullptr;
     if (sort_mode) {               // exact flushes were in use: the sorted row is a valid set
       tk.emit_keys = out_keys;
       tk.finish(out_keys ? nullptr : D, I64, out_keys ? nullptr : I32, tid);
       if (filt && tid == 0) pf->count[q] = -1;       // the k unfiltered hits: the rescoring filters this row
-      return;
+      return -1;
     }
     double f_q = 0.0;
     uint8_t *sflag = reinterpret_cast<uint8_t *>(scratch + CAP);
@@ -436,7 +438,7 @@ struct HistTopK {
     if (filt) {                 // the row's length; nothing is padded behind it
       __syncthreads();
       if (tid == 0) pf->count[q] = ctl[C_USER];
-      return;
+      return -1;
     }
     for (int i = n_above + take + tid; i < k; i += NT) {
       if (out_keys) {
@@ -447,6 +449,7 @@ struct HistTopK {
       if (I64) I64[i] = -1;
       if (I32) I32[i] = -1;
     }
+    return n_above + take;
   }
 
   __device__ __forceinline__ void finish(float *D, int64_t *I64, int32_t *I32) {

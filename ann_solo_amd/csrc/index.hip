@@ -102,6 +102,18 @@ struct asl_index {
   IndexPostFilter post;          // for the next search only
   bool post_set = false, post_applied = false;
   bool has_tiles = false;
+  // window-ordered copy of the tiled layout (window_install): each list's vectors by a float32 key per
+  // vector, ascending, NaN last -- same list and tile offsets as the default layout, which stays as it
+  // is. Derived, never saved; build_lists drops it (add, add_preassigned, reset and shard all rebuild).
+  DevBuf<uint8_t> wcodes_tiled;
+  DevBuf<int32_t> wids_tiled;
+  DevBuf<float> wkey_tiled;      // the key per tile slot (NaN in a list's last tile behind its end)
+  bool win_ready = false;
+  uint64_t win_serial = 0;       // serial of the library whose window column is the key; 0: a caller's key
+  int window_scan = 0;           // asl_index_set_window_scan: asl_search_batch scans each query's window only
+  IndexWindow win;               // for the next search only
+  bool win_set = false;
+  DevBuf<int2> win_ranges;       // [nq, nprobe] in-window run of each probed list
   // dimension-major postings for flat_inv_scan (IVF-Flat): blocks of FI_BLK vectors
   DevBuf<int32_t> blk_offsets;   // [nlist + 1] first block of each list
   DevBuf<uint32_t> blk_base;     // [nblocks] start of the block's postings, 64-byte units
@@ -299,6 +311,8 @@ static int build_lists(asl_index *ix) {
   if (!ix->lists_dirty) return ASL_OK;
   ix->agreed_val = -1;
   ix->idpay_ready = false;
+  ix->win_ready = false;
+  ix->win_serial = 0;
   const int64_t n = ix->n_store;
   std::vector<int32_t> h_vlist((size_t)n), h_order((size_t)n), h_ids;
   ix->h_list_offsets.assign((size_t)ix->nlist + 1, 0);
@@ -562,6 +576,70 @@ static int take_post_filter(asl_index *ix, bool usable, const int32_t *slot_ids,
   return ASL_OK;
 }
 
+// ---- window scan (asl_index_set_window_key / _search_window / _set_window_scan)
+// nullptr when the index can hold the window-ordered layout, else why not
+static const char *window_unsupported(const asl_index *ix) {
+  if (ix->kind != ASL_INDEX_IVFPQ) return "the window scan needs an IVF-PQ index (not IVF-Flat or Flat)";
+  if (ix->pq_m != 32 || ix->ksub != 256) return "the window scan needs the tiled IVF-PQ scan (m = 32, 8 bits)";
+  if (ix->shard_world > 1 || ix->has_vids) return "the window scan does not run on a sharded index";
+  return nullptr;
+}
+
+// The window-ordered layout from key[id] (n == ntotal; host or device): every list's vectors sorted by
+// (key ascending, NaN last, id ascending) and tiled by tile_codes_kernel into that slot order, plus the
+// key per slot. `serial` records where the key came from (asl_library serial; 0: the caller's).
+static int window_install(asl_index *ix, int64_t n, const float *key, uint64_t serial) {
+  if (const char *why = window_unsupported(ix)) return fail(ASL_ERR_STATE, "%s", why);
+  if (!ix->trained) return fail(ASL_ERR_STATE, "window key: index is not trained");
+  if (n != ix->ntotal) return fail(ASL_ERR_INVALID, "window key: %lld keys for %lld vectors", (long long)n,
+                                   (long long)ix->ntotal);
+  if (n > 0 && !key) return fail(ASL_ERR_INVALID, "window key: null key");
+  ASL_TRY(build_lists(ix));
+  if (!ix->has_tiles) return fail(ASL_ERR_STATE, "window key: the index has no tiled layout");
+  ix->win_ready = false;
+  std::vector<float> h_key((size_t)n);
+  std::vector<int32_t> h_ids((size_t)n);
+  if (n) {
+    HIP_TRY(hipMemcpy(h_key.data(), key, (size_t)n * 4, hipMemcpyDefault));
+    ASL_TRY(ix->ids.download(h_ids.data(), (size_t)n));
+    ASL_TRY(sync_stream());
+  }
+  const auto &off = ix->h_list_offsets;
+  std::vector<int32_t> tile_off((size_t)ix->nlist + 1, 0), dst_slot((size_t)n), perm;
+  for (int l = 0; l < ix->nlist; l++)
+    tile_off[(size_t)l + 1] = tile_off[(size_t)l] + (off[(size_t)l + 1] - off[(size_t)l] + 63) / 64;
+  const int64_t ntiles = std::max<int64_t>(tile_off[(size_t)ix->nlist], 1);
+  std::vector<float> h_wkey((size_t)ntiles * 64, __builtin_nanf(""));
+  auto kv = [&](int32_t i) { return h_key[(size_t)h_ids[(size_t)i]]; };
+  for (int l = 0; l < ix->nlist; l++) {
+    const int32_t b = off[(size_t)l], e = off[(size_t)l + 1];
+    perm.resize((size_t)(e - b));
+    std::iota(perm.begin(), perm.end(), b);
+    std::sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) {
+      const float kx = kv(x), ky = kv(y);
+      const bool nx = std::isnan(kx), ny = std::isnan(ky);
+      if (nx != ny) return ny;
+      if (!nx && kx != ky) return kx < ky;
+      return h_ids[(size_t)x] < h_ids[(size_t)y];
+    });
+    for (int32_t r = 0; r < e - b; r++) {
+      const int64_t slot = (int64_t)tile_off[(size_t)l] * 64 + r;
+      dst_slot[(size_t)perm[(size_t)r]] = (int32_t)slot;
+      h_wkey[(size_t)slot] = kv(perm[(size_t)r]);
+    }
+  }
+  DevBuf<int32_t> slot_dev;
+  ASL_TRY(slot_dev.upload(dst_slot.data(), (size_t)n));
+  ASL_TRY(ix->wcodes_tiled.reserve((size_t)ntiles * 2048));
+  ASL_TRY(ix->wids_tiled.reserve((size_t)ntiles * 64));
+  ASL_TRY(ix->wkey_tiled.upload(h_wkey.data(), h_wkey.size()));
+  ASL_TRY(tile_codes(ix->codes.p, ix->ids.p, slot_dev.p, n, ntiles, ix->wcodes_tiled.p, ix->wids_tiled.p));
+  ASL_TRY(sync_stream());
+  ix->win_ready = true;
+  ix->win_serial = serial;
+  return ASL_OK;
+}
+
 // k > TK_MAX_K: ceil(k / TK_MAX_K) bounded passes of the generic kernels. Every hit has a unique
 // 64-bit key (score, ~id); a pass keeps the TK_MAX_K best keys strictly below the row's bound = the
 // smallest key the pass before it wrote (0 once a row is exhausted), and writes them behind the
@@ -634,6 +712,20 @@ int index_search_device(asl_index *ix, int nq, const float *xq, int k, int nprob
                         int64_t *I64, int32_t *I32, const float *pre_D = nullptr,
                         const int32_t *pre_I = nullptr, bool set_mode = false, const int *gate = nullptr,
                         const uint2 *pre_ent = nullptr, const int32_t *pre_cnt = nullptr) {
+  // the window of this search (index_set_window): only the in-window run of every probed list is
+  // scanned, in the window-ordered layout; whatever cannot do that is an error, never the whole lists
+  const bool win = ix->win_set;
+  const IndexWindow wq = ix->win;
+  ix->win_set = false;
+  if (win) {
+    if (const char *why = window_unsupported(ix)) return fail(ASL_ERR_STATE, "%s", why);
+    if (ix->scan_variant != 0)
+      return fail(ASL_ERR_STATE, "the window scan needs the layout-specific scan (scan_variant 0), not the generic kernels");
+    if (k > TK_MAX_K - 768) return fail(ASL_ERR_STATE, "the window scan holds k <= %d (k=%d)", TK_MAX_K - 768, k);
+    if (gate || ix->unordered == 2 || (ix->refine_k > k && ix->refine_rows && ix->unordered == 0))
+      return fail(ASL_ERR_STATE, "the window scan takes no gate, packed keys or exact re-rank");
+    if (!wq.q_pmz) return fail(ASL_ERR_INVALID, "window scan: null precursor m/z");
+  }
   if (nq <= 0) return ASL_OK;
   // pre_ent / pre_cnt: the queries as ENTRY LISTS (list_nonzeros / encode_entries_device); xq may
   // then be null -- only the layout-specific scans read their queries in that form, and a row
@@ -811,13 +903,30 @@ int index_search_device(asl_index *ix, int nq, const float *xq, int k, int nprob
       }
       const int mode_ = ix->unordered ? ix->unordered : (set_mode ? 1 : 0);
       ScanPostFilter pf;
-      ASL_TRY(take_post_filter(ix, mode_ == 1 && I32 && !I64 && !D && !gate && !refine && k + 768 <= 2048,
-                               ix->ids_tiled.p, ix->n_tile_slots, pf));
+      ScanRanges rg;
+      if (win) {                // the rows are in-window already: no post-filter
+        ix->post_set = ix->post_applied = false;
+        if (!ix->win_ready)
+          return fail(ASL_ERR_STATE, "window scan: no window key (asl_index_set_window_key), or the lists changed "
+                                     "since it was set");
+        ASL_TRY(ix->win_ranges.reserve((size_t)nq * nprobe));
+        ProfScope ps("window_ranges");
+        ASL_TRY(window_ranges(wq.q_pmz, nq, cI, nprobe, ix->list_offsets.p, ix->tile_offsets.p, ix->wkey_tiled.p,
+                              wq.charge, wq.tol, wq.mode, ix->win_ranges.p,
+                              prof_counts() ? prof_scanned_dev() : nullptr));   // work: sum of hi - lo
+        rg.range = ix->win_ranges.p;
+        rg.row_len = mode_ == 1 ? wq.row_len : nullptr;
+      } else {
+        ASL_TRY(take_post_filter(ix, mode_ == 1 && I32 && !I64 && !D && !gate && !refine && k + 768 <= 2048,
+                                 ix->ids_tiled.p, ix->n_tile_slots, pf));
+      }
       ProfScope ps("scan");     // the scan kernel itself
       ASL_TRY(pq_scan_v3(xq, nq, d, ix->codebooks_t.p, ix->dsub, cD, cI,
-                         nprobe, ix->list_offsets.p, ix->tile_offsets.p, ix->codes_tiled.p,
-                         ix->ids_tiled.p, k, D, I64, I32, mode_, q_ent, q_cnt, gate, &pf));
+                         nprobe, ix->list_offsets.p, ix->tile_offsets.p,
+                         win ? ix->wcodes_tiled.p : ix->codes_tiled.p, win ? ix->wids_tiled.p : ix->ids_tiled.p,
+                         k, D, I64, I32, mode_, q_ent, q_cnt, gate, &pf, &rg));
     } else {
+      if (win) return fail(ASL_ERR_STATE, "the window scan needs the tiled IVF-PQ scan (m = 32, 8 bits)");
       ix->post_set = ix->post_applied = false;      // the generic kernel takes no post-filter
       ProfScope ps("scan");
       ASL_TRY(pq_scan(xq, nq, d, ix->codebooks.p, ix->pq_m, ix->ksub, ix->dsub, cD,
@@ -825,7 +934,7 @@ int index_search_device(asl_index *ix, int nq, const float *xq, int k, int nprob
                       I64, I32));
     }
   }
-  if (prof_counts() && !gate) {
+  if (prof_counts() && !gate && !win) {   // (the window scan's ranges counted its own work)
     // vectors scored by this launch, summed on the device (nothing waits inside a step)
     if (unsigned long long *acc = prof_scanned_dev())
       ASL_TRY(scanned_count(cI, (int64_t)nq * nprobe, ix->list_offsets.p, acc));
@@ -839,6 +948,23 @@ int index_search_device(asl_index *ix, int nq, const float *xq, int k, int nprob
 }
 
 int index_dim(const asl_index *ix) { return ix->d; }
+// window scan of asl_search_batch: the index's mode, the key of library `serial` (installed when the
+// layout holds another key or the lists changed; synchronises -- call before the batch forks into
+// streams), the window of the next search
+bool index_window_scan_on(const asl_index *ix) { return ix->window_scan != 0; }
+int index_window_prepare(asl_index *ix, uint64_t serial, const float *key, int64_t n, int nq, int nprobe) {
+  if (!ix->trained) return fail(ASL_ERR_STATE, "search: index is not trained");
+  ASL_TRY(build_lists(ix));
+  if (!ix->win_ready || ix->win_serial != serial) {
+    ASL_TRY(pipeline_drain());     // batches in flight may still scan the layout about to be rewritten
+    ASL_TRY(window_install(ix, n, key, serial));
+  }
+  return ix->win_ranges.reserve((size_t)std::max(nq, 1) * std::max(1, std::min(nprobe, ix->nlist)));
+}
+void index_set_window(asl_index *ix, const IndexWindow &w) {
+  ix->win = w;
+  ix->win_set = true;
+}
 void index_set_post_filter(asl_index *ix, const IndexPostFilter &p) {
   ix->post = p;
   ix->post_set = true;
@@ -956,6 +1082,57 @@ int asl_index_set_scan_variant(asl_index_t *ix, int32_t variant) {
     return fail(ASL_ERR_INVALID, "set_scan_variant: 0 (layout-specific scan) or 1 (generic kernels)");
   ix->scan_variant = variant;
   ix->agreed_val = -1;      // asl_index_supports_keys depends on the variant: the ranks agree again
+  return ASL_OK;
+}
+
+int asl_index_set_window_key(asl_index_t *ix, int64_t n, const float *key) {
+  clear_error();
+  ASL_TRY(ensure_device());
+  if (!ix) return fail(ASL_ERR_INVALID, "set_window_key: null index");
+  return window_install(ix, n, key, 0);
+}
+
+int asl_index_search_window(asl_index_t *ix, int32_t nq, const float *xq, const double *q_pmz, int32_t charge,
+                            double tol, int32_t mode, int32_t k, int32_t nprobe, float *D, int64_t *I) {
+  clear_error();
+  ASL_TRY(ensure_device());
+  if (!ix) return fail(ASL_ERR_INVALID, "search_window: null index");
+  if (nq <= 0) return ASL_OK;
+  if (!xq || !q_pmz || !I) return fail(ASL_ERR_INVALID, "search_window: null xq / q_pmz / I");
+  if (mode != ASL_TOL_DA && mode != ASL_TOL_PPM) return fail(ASL_ERR_INVALID, "search_window: mode must be Da or ppm");
+  if (const char *why = window_unsupported(ix)) return fail(ASL_ERR_STATE, "%s", why);
+  if (!ix->trained) return fail(ASL_ERR_STATE, "search: index is not trained");
+  ASL_TRY(build_lists(ix));
+  if (!ix->win_ready)
+    return fail(ASL_ERR_STATE, "search_window: no window key (asl_index_set_window_key), or the lists changed since");
+  In<float> dq;
+  In<double> dp;
+  Out<float> dD;
+  Out<int64_t> dI;
+  ASL_TRY(dq.init(xq, (size_t)nq * ix->d));
+  ASL_TRY(dp.init(q_pmz, (size_t)nq));
+  ASL_TRY(dD.init(D, (size_t)nq * k));
+  ASL_TRY(dI.init(I, (size_t)nq * k));
+  IndexWindow w;
+  w.q_pmz = dp.d;
+  w.tol = tol;
+  w.mode = mode;
+  w.charge = charge;
+  index_set_window(ix, w);
+  ASL_TRY(index_search_device(ix, nq, dq.d, k, nprobe, dD.d, dI.d, nullptr));
+  ASL_TRY(dD.finish());
+  ASL_TRY(dI.finish());
+  if (dD.to_host() || dI.to_host() || dq.own.p || dp.own.p) ASL_TRY(sync_stream());
+  return ASL_OK;
+}
+
+int asl_index_set_window_scan(asl_index_t *ix, int32_t on) {
+  clear_error();
+  if (!ix) return fail(ASL_ERR_INVALID, "set_window_scan: null index");
+  if (on != 0 && on != 1) return fail(ASL_ERR_INVALID, "set_window_scan: 0 (post-filter) or 1 (window scan)");
+  if (on)
+    if (const char *why = window_unsupported(ix)) return fail(ASL_ERR_STATE, "%s", why);
+  ix->window_scan = on;
   return ASL_OK;
 }
 

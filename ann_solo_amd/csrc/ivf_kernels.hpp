@@ -66,7 +66,12 @@ int pq_scan_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
                int64_t *I64, int32_t *I32, int set_mode, const uint2 *ent = nullptr,
                const int32_t *ent_cnt = nullptr,    // ent / ent_cnt: list_nonzeros (64 entries per query)
                const int *gate = nullptr,
-               const ScanPostFilter *post = nullptr);   // (common.hpp) set-mode int32 rows, k <= 1280 only          // device-side row count: workgroups past it return at once
+               const ScanPostFilter *post = nullptr,   // (common.hpp) set-mode int32 rows, k <= 1280 only          // device-side row count: workgroups past it return at once
+               const ScanRanges *ranges = nullptr);   // (common.hpp) window scan of the window-ordered layout, k <= 1280
+// [lo, hi) of the in-window run of every (query, probe) in the window-ordered layout (pq_scan_v3.hip)
+int window_ranges(const double *q_pmz, int nq, const int32_t *coarse_I, int nprobe,
+                  const int32_t *list_offsets, const int32_t *tile_offsets, const float *wkey, int charge,
+                  double tol, int mode, int2 *ranges, unsigned long long *acc);
 int tile_codes(const uint8_t *codes, const int32_t *ids, const int32_t *dst_slot, int64_t n,
                int64_t ntiles, uint8_t *codes_tiled, int32_t *ids_tiled);
 // dimension-major IVF-Flat (flat_scan.hip): blocks of FI_BLK vectors with per-dimension postings

@@ -65,12 +65,28 @@ struct TileEnt8 {
   float coarse;
 };
 
+// The RANGED instantiations (asl_index_search_window / window scan of asl_search_batch)
+// scan, of each probed list of the window-ordered layout, only the run [lo, hi) of the vectors that
+// pass the query's precursor window: its tiles, the first of them from lane lo & 63 on, the last up to
+// lane (hi - 1) & 63. TileEnt8 has no bit left for a first lane, so the entry is 12 bytes, and a chunk
+// holds 168 of them (21 rounds of 8 tiles) in the 2 KB the 256 entries of TileEnt8 take: the workgroup
+// keeps the LDS of the 2048-key instantiation to the byte (53 504 B, three per CU within 160 KiB
+// whatever the allocation granule); only the table is refilled 1.5 times as often.
+struct TileEnt12 {
+  uint32_t tile_nv;   // tile (26 bits) | end lane - 1 (6 bits), as TileEnt8
+  float coarse;
+  uint32_t first;     // first lane of the run in this tile (0 except in the run's first tile)
+};
+constexpr int V3_CHUNK_RANGED = 168;
+static_assert(V3_CHUNK_RANGED * sizeof(TileEnt12) <= V3_CHUNK * sizeof(TileEnt8), "the ranged table fits the 2 KB");
+
 // NW = waves per workgroup. LDS (LUT 32 KB + keys 16 KB + ...) allows three workgroups per CU
 // whatever their size, so 8 waves per workgroup (one tile per wave and round) double the
 // waves that share one LUT and one key buffer: 24 waves per CU at 80 VGPRs instead of 12 at
 // 157 -- measured 8.28 -> 7.46 ms at the bench config (with ONE round of prefetch: at this
 // occupancy the second prefetch stage only costs registers).
-template <int CAP, int T, int NW, int DEPTH, bool WIDE>
+// RANGED: the tile table comes from rg.range instead of the whole lists (see TileEnt12)
+template <int CAP, int T, int NW, int DEPTH, bool WIDE, bool RANGED = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIMD : 4) : (CAP <= 2048 ? 3 : 1))) void pq_scan_v3_kernel(
     const float *__restrict__ xq, int d, const float *__restrict__ codebooks, int dsub,
     const float *__restrict__ coarse_D, const int32_t *__restrict__ coarse_I, int nprobe,
@@ -78,16 +94,17 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     const uint8_t *__restrict__ codes_tiled, const int32_t *__restrict__ ids_tiled, int k,
     float *__restrict__ D, int64_t *__restrict__ I64, int32_t *__restrict__ I32, int set_mode,
     const uint2 *__restrict__ ent, const int32_t *__restrict__ ent_cnt, const int *__restrict__ gate,
-    const ScanPostFilter pf) {
+    const ScanPostFilter pf, const ScanRanges rg) {
   // gate: a device-side row count -- workgroups past it leave at once (a launch of fixed size over
   // a list whose length only the device knows: the shard-side rescans of exchange.hip)
   if (gate && (int)blockIdx.x >= *gate) return;
   static_assert(DEPTH >= 1 && DEPTH <= 3, "rounds of prefetch");
   constexpr int NT = 64 * NW, ROUND_TILES = NW * T, ROUND_VECS = ROUND_TILES * 64;
   using TopK = HistTopK<CAP, ROUND_VECS, NT>;
+  using Ent = typename std::conditional<RANGED, TileEnt12, TileEnt8>::type;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float *s_lut = reinterpret_cast<float *>(smem + TopK::lds_bytes());
-  TileEnt8 *table = reinterpret_cast<TileEnt8 *>(s_lut + PQT_KSUB * PQT_M);
+  Ent *table = reinterpret_cast<Ent *>(s_lut + PQT_KSUB * PQT_M);
   float *s_q = reinterpret_cast<float *>(smem);  // aliases the key buffer during the LUT build
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = blockIdx.x;
@@ -96,16 +113,26 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
   // table build and complete under it
   constexpr int PP = WIDE ? 2 : 1;
   int my_len[PP], my_tile0[PP], my_nt[PP], my_pre[PP];
+  int my_first[PP];      // RANGED: first lane of the run's first tile
   float my_coarse[PP];
 #pragma unroll
   for (int pp = 0; pp < PP; ++pp) {
-    my_len[pp] = 0, my_tile0[pp] = 0, my_nt[pp] = 0, my_coarse[pp] = 0.0f;
+    my_len[pp] = 0, my_tile0[pp] = 0, my_nt[pp] = 0, my_coarse[pp] = 0.0f, my_first[pp] = 0;
     const int p = tid + pp * NT;
     if (p < nprobe) {
       const int l = coarse_I[(size_t)q * nprobe + p];
       if (l >= 0) {
-        my_len[pp] = list_offsets[l + 1] - list_offsets[l];
-        my_tile0[pp] = tile_offsets[l];
+        if constexpr (RANGED) {
+          // the run [lo, hi) of the list, counted from lane 0 of the tile that holds lo: the tile
+          // count and the end lane of every tile follow from my_len as for a whole list
+          const int2 r = rg.range[(size_t)q * nprobe + p];
+          my_first[pp] = r.x & 63;
+          my_len[pp] = r.y > r.x ? r.y - (r.x & ~63) : 0;
+          my_tile0[pp] = tile_offsets[l] + (r.x >> 6);
+        } else {
+          my_len[pp] = list_offsets[l + 1] - list_offsets[l];
+          my_tile0[pp] = tile_offsets[l];
+        }
         my_nt[pp] = (my_len[pp] + 63) >> 6;
         my_coarse[pp] = coarse_D[(size_t)q * nprobe + p];
       }
@@ -139,20 +166,22 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
   const uint32_t offA = (uint32_t)ma * 4u, offB = (uint32_t)mb * 4u;
   const uint32_t chunkA = (uint32_t)(rho * 512 + ma * 16), chunkB = (uint32_t)(rho * 512 + mb * 16);
 
-  for (int c0 = 0; c0 < total; c0 += V3_CHUNK) {
+  constexpr int CHUNK = RANGED ? V3_CHUNK_RANGED : V3_CHUNK;
+  for (int c0 = 0; c0 < total; c0 += CHUNK) {
 #pragma unroll
     for (int pp = 0; pp < PP; ++pp) {
-      const int lo = max(my_pre[pp], c0), hi = min(my_pre[pp] + my_nt[pp], c0 + V3_CHUNK);
+      const int lo = max(my_pre[pp], c0), hi = min(my_pre[pp] + my_nt[pp], c0 + CHUNK);
       for (int t = lo; t < hi; ++t) {
         const int local = t - my_pre[pp];
-        TileEnt8 e;
+        Ent e;
         e.tile_nv = (uint32_t)(my_tile0[pp] + local) | ((uint32_t)(min(64, my_len[pp] - local * 64) - 1) << 26);
         e.coarse = my_coarse[pp];
+        if constexpr (RANGED) e.first = local == 0 ? (uint32_t)my_first[pp] : 0u;
         table[t - c0] = e;
       }
     }
     __syncthreads();
-    const int nent = min(V3_CHUNK, total - c0);
+    const int nent = min(CHUNK, total - c0);
     const int nrounds = (nent + ROUND_TILES - 1) / ROUND_TILES;
     // Register pipeline, DEPTH rounds deep (the codes of rounds rr + 1 .. rr + DEPTH are in flight
     // while round rr is scored). DEPTH + 1 register sets, rotated by full unrolling: every index
@@ -165,12 +194,13 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
       for (int u = 0; u < T; ++u) {
         // the entry is the same for the whole wave: keep it in scalar registers
         const int i = rr * ROUND_TILES + wave_u * T + u;
-        const TileEnt8 t = table[i < nent ? i : 0];
+        const Ent t = table[i < nent ? i : 0];
         const uint32_t tn = __builtin_amdgcn_readfirstlane(t.tile_nv);
         en[u].tile = tn & 0x3ffffffu;
         en[u].coarse = __builtin_bit_cast(
             float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t.coarse)));
         en[u].nvalid = i < nent ? (int)(tn >> 26) + 1 : 0;
+        if constexpr (RANGED) en[u].pad = (int)__builtin_amdgcn_readfirstlane(t.first);   // first lane
         const uint8_t *base = codes_tiled + (size_t)en[u].tile * 2048;
         a[u] = load_codes16<V3_NT>(base + chunkA);
         b[u] = load_codes16<V3_NT>(base + chunkB);
@@ -183,8 +213,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
       for (int u = 0; u < T; ++u) {
         if (en[u].nvalid > 0) {  // wave-uniform
           const float score = en[u].coarse + tile_adc(lut_bytes, a[u], b[u], offA, offB);
-          const bool take = top.offer(lane < en[u].nvalid, score,
-                                      en[u].tile * 64u + (uint32_t)lane);
+          const bool in = RANGED ? (lane < en[u].nvalid && lane >= en[u].pad) : lane < en[u].nvalid;
+          const bool take = top.offer(in, score, en[u].tile * 64u + (uint32_t)lane);
           appended += __popcll(__ballot(take));
         }
       }
@@ -205,7 +235,19 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     }
     __syncthreads();
   }
-  if (set_mode && CAP * 9 <= PQT_KSUB * PQT_M * 4)   // unordered exact top-k; the LUT is dead: scratch
+  if constexpr (RANGED) {
+    // set mode: the row holds in-window hits only, so its length goes to the rescoring as it is
+    // (rescore.hip: prefiltered rows; -1 after exact flushes: the row is -1 padded and the
+    // rescoring's own filter, which every hit passes, finds its end)
+    if (set_mode) {
+      const int n = top.finish_set(D ? D + (size_t)q * k : nullptr, I64 ? I64 + (size_t)q * k : nullptr,
+                                   I32 ? I32 + (size_t)q * k : nullptr, reinterpret_cast<u64 *>(s_lut));
+      if (rg.row_len && tid == 0) rg.row_len[q] = n;
+    } else {
+      top.finish(D ? D + (size_t)q * k : nullptr, I64 ? I64 + (size_t)q * k : nullptr,
+                 I32 ? I32 + (size_t)q * k : nullptr);
+    }
+  } else if (set_mode && CAP * 9 <= PQT_KSUB * PQT_M * 4)   // unordered exact top-k; the LUT is dead: scratch
     top.finish_set(D ? D + (size_t)q * k : nullptr, I64 ? I64 + (size_t)q * k : nullptr,
                    I32 ? I32 + (size_t)q * k : nullptr, reinterpret_cast<u64 *>(s_lut), &pf, q);
   else if (set_mode && CAP * 8 <= PQT_KSUB * PQT_M * 4)
@@ -216,25 +258,27 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
                I32 ? I32 + (size_t)q * k : nullptr);
 }
 
-template <int CAP, int T, int NW, int DEPTH, bool WIDE>
+template <int CAP, int T, int NW, int DEPTH, bool WIDE, bool RANGED = false>
 static int launch_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
                      const float *coarse_D, const int32_t *coarse_I, int nprobe,
                      const int32_t *list_offsets, const int32_t *tile_offsets,
                      const uint8_t *codes_tiled, const int32_t *ids_tiled, int k, float *D,
                      int64_t *I64, int32_t *I32, int set_mode, const uint2 *ent,
-                     const int32_t *ent_cnt, const int *gate, const ScanPostFilter &pf) {
-  if ((size_t)d * 4 > (size_t)CAP * 8 || dsub > 64 ||
-      (size_t)d * 2 + 8 > (size_t)V3_CHUNK * sizeof(TileEnt8) || d != PQT_M * dsub)
+                     const int32_t *ent_cnt, const int *gate, const ScanPostFilter &pf,
+                     const ScanRanges &rg) {
+  // (the ranged table -- V3_CHUNK_RANGED entries of TileEnt12 -- fits the same bytes)
+  constexpr size_t TABLE = RANGED ? V3_CHUNK_RANGED * sizeof(TileEnt12) : V3_CHUNK * sizeof(TileEnt8);
+  if ((size_t)d * 4 > (size_t)CAP * 8 || dsub > 64 || (size_t)d * 2 + 8 > TABLE || d != PQT_M * dsub)
     return fail(ASL_ERR_CAPACITY, "pq scan: d=%d too large for the LDS staging", d);
   const size_t lds = HistTopK<CAP, NW * T * 64, 64 * NW>::lds_bytes() + (size_t)PQT_KSUB * PQT_M * 4 +
                      (size_t)V3_CHUNK * sizeof(TileEnt8);
   if (lds > 160 * 1024) return fail(ASL_ERR_CAPACITY, "pq scan: k=%d does not fit LDS", k);
   if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute((const void *)pq_scan_v3_kernel<CAP, T, NW, DEPTH, WIDE>,
+    HIP_TRY(hipFuncSetAttribute((const void *)pq_scan_v3_kernel<CAP, T, NW, DEPTH, WIDE, RANGED>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((pq_scan_v3_kernel<CAP, T, NW, DEPTH, WIDE>), dim3(nq), dim3(64 * NW), lds, stream(), xq, d,
-                     codebooks, dsub, coarse_D, coarse_I, nprobe, list_offsets, tile_offsets,
-                     codes_tiled, ids_tiled, k, D, I64, I32, set_mode, ent, ent_cnt, gate, pf);
+  hipLaunchKernelGGL((pq_scan_v3_kernel<CAP, T, NW, DEPTH, WIDE, RANGED>), dim3(nq), dim3(64 * NW), lds, stream(),
+                     xq, d, codebooks, dsub, coarse_D, coarse_I, nprobe, list_offsets, tile_offsets,
+                     codes_tiled, ids_tiled, k, D, I64, I32, set_mode, ent, ent_cnt, gate, pf, rg);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }
@@ -249,7 +293,7 @@ int pq_scan_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
                const int32_t *list_offsets, const int32_t *tile_offsets,
                const uint8_t *codes_tiled, const int32_t *ids_tiled, int k, float *D,
                int64_t *I64, int32_t *I32, int set_mode, const uint2 *ent, const int32_t *ent_cnt,
-               const int *gate, const ScanPostFilter *post) {
+               const int *gate, const ScanPostFilter *post, const ScanRanges *ranges) {
   if (nq <= 0) return ASL_OK;
   // the post-filter needs the set-mode finish of the 2048-key instantiation (its scratch behind the keys)
   ScanPostFilter pf;
@@ -258,15 +302,86 @@ int pq_scan_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
       return fail(ASL_ERR_STATE, "pq scan: a post-filter needs set-mode int32 rows and k <= 1280");
     pf = *post;
   }
+  const ScanRanges none;
 #define V3_ARGS xq, nq, d, codebooks, dsub, coarse_D, coarse_I, nprobe, list_offsets, tile_offsets, \
                 codes_tiled, ids_tiled, k, D, I64, I32, set_mode, ent, ent_cnt, gate, pf
-  if (nprobe > 512) {         // two probes per thread (the one-probe form keeps its registers)
-    if (k + 256 + 512 <= 2048) return launch_v3<2048, 1, 8, V3_DEPTH, true>(V3_ARGS);
-    return launch_v3<4096, 1, 8, V3_DEPTH, true>(V3_ARGS);
+  if (ranges && ranges->range) {   // the window-ordered layout, one run per probed list
+    if (pf.idpay || set_mode == 2 || k + 256 + 512 > 2048)
+      return fail(ASL_ERR_STATE, "pq scan: the window scan needs k <= 1280, rows of ids and no post-filter");
+    if (nprobe > 512) return launch_v3<2048, 1, 8, V3_DEPTH, true, true>(V3_ARGS, *ranges);
+    return launch_v3<2048, 1, 8, V3_DEPTH, false, true>(V3_ARGS, *ranges);
   }
-  if (k + 256 + 512 <= 2048) return launch_v3<2048, 1, 8, V3_DEPTH, false>(V3_ARGS);
-  return launch_v3<4096, 1, 8, V3_DEPTH, false>(V3_ARGS);
+  if (nprobe > 512) {         // two probes per thread (the one-probe form keeps its registers)
+    if (k + 256 + 512 <= 2048) return launch_v3<2048, 1, 8, V3_DEPTH, true>(V3_ARGS, none);
+    return launch_v3<4096, 1, 8, V3_DEPTH, true>(V3_ARGS, none);
+  }
+  if (k + 256 + 512 <= 2048) return launch_v3<2048, 1, 8, V3_DEPTH, false>(V3_ARGS, none);
+  return launch_v3<4096, 1, 8, V3_DEPTH, false>(V3_ARGS, none);
 #undef V3_ARGS
+}
+
+// [lo, hi) per (query, probe): the positions of the probed list, in the window-ordered layout (keys
+// ascending, NaN last), whose key passes the query's window -- two binary searches with precursor_ok
+// itself as the predicate, so the run holds exactly the vectors the reference's filter keeps (a
+// precomputed interval q +- tol / z would round differently at its edges). The run is contiguous:
+// left of the query's m/z, fabs(q - l) is a correctly rounded difference, non-increasing as l grows,
+// and so are its product with the charge and its quotient by the growing l (ppm); right of it the
+// same terms are non-decreasing (l - q is exact up to l = 2q, Sterbenz; beyond that a float32 step
+// of l is still far above the double rounding of l - q). Correctly rounded operations are monotone,
+// so on either side the predicate changes value once. NaN keys (sorted last) never pass.
+// acc (optional): += sum of hi - lo (asl_profile_scanned_vectors).
+__global__ void window_ranges_kernel(const double *__restrict__ q_pmz, int nq,
+                                     const int32_t *__restrict__ coarse_I, int nprobe,
+                                     const int32_t *__restrict__ list_offsets,
+                                     const int32_t *__restrict__ tile_offsets,
+                                     const float *__restrict__ wkey, int charge, double tol, int mode,
+                                     int2 *__restrict__ ranges, unsigned long long *__restrict__ acc) {
+  const int64_t i = block_linear() * blockDim.x + threadIdx.x;
+  unsigned long long cnt = 0;
+  if (i < (int64_t)nq * nprobe) {
+    const int l = coarse_I[i];
+    int2 r = make_int2(0, 0);
+    if (l >= 0) {
+      const float *key = wkey + (size_t)tile_offsets[l] * 64;
+      const int n = list_offsets[l + 1] - list_offsets[l];
+      const double qm = q_pmz[i / nprobe];
+      int a = 0, b = n;   // p0 = first key with (double)key >= qm (NaN: not below)
+      while (a < b) {
+        const int mid = (a + b) >> 1;
+        if ((double)key[mid] < qm) a = mid + 1; else b = mid;
+      }
+      const int p0 = a;
+      a = 0, b = p0;      // left side: first key that passes
+      while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (precursor_ok(qm, key[mid], charge, tol, mode)) b = mid; else a = mid + 1;
+      }
+      const int lo = a;
+      a = p0, b = n;      // right side: first key that fails
+      while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (precursor_ok(qm, key[mid], charge, tol, mode)) a = mid + 1; else b = mid;
+      }
+      r = make_int2(lo, a);
+      cnt = (unsigned long long)(a - lo);
+    }
+    ranges[i] = r;
+  }
+  if (acc) {
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(acc, cnt);
+  }
+}
+
+int window_ranges(const double *q_pmz, int nq, const int32_t *coarse_I, int nprobe,
+                  const int32_t *list_offsets, const int32_t *tile_offsets, const float *wkey, int charge,
+                  double tol, int mode, int2 *ranges, unsigned long long *acc) {
+  const int64_t n = (int64_t)nq * nprobe;
+  if (n <= 0) return ASL_OK;
+  hipLaunchKernelGGL(window_ranges_kernel, grid_2d(cdiv(n, 256)), dim3(256), 0, stream(), q_pmz, nq, coarse_I,
+                     nprobe, list_offsets, tile_offsets, wkey, charge, tol, mode, ranges, acc);
+  ASL_CHECK_LAUNCH();
+  return ASL_OK;
 }
 
 // list-ordered codes [n,32] -> 64-vector tiles (see file header); dst_slot[i] = tile*64 + v

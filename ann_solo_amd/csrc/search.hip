@@ -11,6 +11,7 @@
 // (cascade level 'std', --mode bf) binary-search a precursor-sorted copy of the
 // library, so nothing is O(nq*N).
 #include <algorithm>
+#include <atomic>
 
 #include "common.hpp"
 #include "ivf_kernels.hpp"
@@ -32,6 +33,9 @@ int index_prepare(asl_index *ix);
 int index_coarse_device(asl_index *ix, int nq, const float *xq, int nprobe, float *out_D,
                         int32_t *out_I, uint2 *ent_out = nullptr, int32_t *cnt_out = nullptr,
                         bool *have_ent = nullptr);
+bool index_window_scan_on(const asl_index *ix);
+int index_window_prepare(asl_index *ix, uint64_t serial, const float *key, int64_t n, int nq, int nprobe);
+void index_set_window(asl_index *ix, const IndexWindow &w);
 // Window [lo,hi) of each query inside the precursor-sorted library.
 __global__ void window_range_kernel(const double *__restrict__ q_pmz, int nq,
                                     const float *__restrict__ sorted_pmz, int n, int charge,
@@ -78,6 +82,7 @@ using namespace asl;
 
 struct asl_library {
   int64_t n = 0;
+  uint64_t serial = 0;    // unique in the process, never reused: what an index's window key came from
   DevBuf<int32_t> offsets, pcharge;
   DevBuf<float> mz, intensity, pmz32;
   DevBuf<uint8_t> charge, valid;
@@ -160,6 +165,16 @@ static int64_t &window_pair_budget() {
   static int64_t b = 1ll << 28;
   return b;
 }
+// window-scan mode (asl_index_set_window_scan): the window of the next scan; row_len: set-mode rows
+static void offer_window(asl_index *idx, const DevPeaks &Q, const asl_search_params_t *P, int32_t *row_len) {
+  IndexWindow w;
+  w.q_pmz = Q.precursor_mz;
+  w.row_len = row_len;
+  w.tol = P->precursor_tol;
+  w.mode = P->precursor_mode;
+  w.charge = P->charge;
+  index_set_window(idx, w);
+}
 static void offer_post_filter(asl_library *L, asl_index *idx, const DevPeaks &Q, const asl_search_params_t *P,
                               int32_t *row_len) {
   IndexPostFilter pf;
@@ -210,6 +225,8 @@ asl_library_t *asl_library_create(const asl_peaks_t *p, const float *lib_pmz_f32
   PeaksStage st;
   if (st.init(p) != ASL_OK) return nullptr;
   asl_library *L = new asl_library();
+  static std::atomic<uint64_t> next_serial{1};
+  L->serial = next_serial.fetch_add(1);
   L->n = p->n;
   const size_t n = (size_t)p->n, np = (size_t)st.dev.n_peaks;
   bool ok = true;
@@ -569,6 +586,8 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
   const int par = pp.parity;
   // allocations first (growing a buffer synchronises the device: only ever on the first batches)
   ASL_TRY(index_prepare(idx));
+  const bool win = index_window_scan_on(idx);      // (the window-ordered layout of THIS library, up front)
+  if (win) ASL_TRY(index_window_prepare(idx, L->serial, L->wcol.p, L->n, nq, nprobe));
   ASL_TRY(L->p_qvec[par].reserve((size_t)nq * d));
   ASL_TRY(L->p_cD[par].reserve((size_t)nq * nprobe));
   ASL_TRY(L->p_cI[par].reserve((size_t)nq * nprobe));
@@ -605,12 +624,14 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
     HIP_TRY(hipStreamWaitEvent(pp.B, pp.ev_front[par], 0));
     if (pp.resc_recorded[par]) HIP_TRY(hipStreamWaitEvent(pp.B, pp.ev_resc[par], 0));
     // (the entry lists of the coarse stage, when it made them: the scan does not list the rows again)
-    if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(L, idx, Q.dev, P, L->p_rows[par].p);
+    if (win) offer_window(idx, Q.dev, P, knn_I == nullptr ? L->p_rows[par].p : nullptr);
+    else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(L, idx, Q.dev, P, L->p_rows[par].p);
     const int rc_scan = index_search_device(idx, nq, L->p_qvec[par].p, k, nprobe, nullptr, knn_I,
                                             L->p_knn[par].p, L->p_cD[par].p, L->p_cI[par].p,
                                             knn_I == nullptr, nullptr, L->p_have_ent[par] ? L->p_ent[par].p : nullptr,
                                             L->p_have_ent[par] ? L->p_cnt[par].p : nullptr);
-    rows_filtered = index_post_filter_applied(idx);
+    // (window scan: set-mode rows hold in-window hits only, and their lengths)
+    rows_filtered = index_post_filter_applied(idx) || (win && knn_I == nullptr);
     ASL_TRY(rc_scan);
     HIP_TRY(hipEventRecord(pp.ev_scan[par], pp.B));
     pp.scan_recorded[par] = true;
@@ -690,15 +711,18 @@ int asl_search_batch(asl_library_t *L, asl_index_t *idx, const asl_peaks_t *quer
     ASL_TRY(L->qvec.reserve((size_t)nq * d));
     ASL_TRY(L->knn.reserve((size_t)nq * k));
     ASL_TRY(L->pair_score.reserve((size_t)nq * k));
+    const bool win = index_window_scan_on(idx);
+    if (win) ASL_TRY(index_window_prepare(idx, L->serial, L->wcol.p, L->n, nq, P->nprobe));
     ASL_TRY(encode_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
                           d, P->hash_seed, 1, L->qvec.p));
     // the candidates are consumed as a set (filter + best match): no final sort unless the
     // caller asked for the ordered neighbour list
     ASL_TRY(L->rows_len.reserve((size_t)nq));
-    if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(L, idx, Q.dev, P, L->rows_len.p);
+    if (win) offer_window(idx, Q.dev, P, knn_I == nullptr ? L->rows_len.p : nullptr);
+    else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(L, idx, Q.dev, P, L->rows_len.p);
     const int rc_scan = index_search_device(idx, nq, L->qvec.p, k, P->nprobe, nullptr, o_knn.d, L->knn.p,
                                             nullptr, nullptr, knn_I == nullptr);
-    const bool rows_filtered = index_post_filter_applied(idx);
+    const bool rows_filtered = index_post_filter_applied(idx) || (win && knn_I == nullptr);
     ASL_TRY(rc_scan);
     PrecFilter flt;
     flt.lib_pmz = L->pmz32.p;

@@ -112,6 +112,40 @@ class Index:
                                                _lib.ptr(D), _lib.ptr(I)))
         return D, I
 
+    def set_window_key(self, key):
+        """Window-ordered copy of the IVF-PQ layout: every list sorted by ``key`` (float32 per vector
+        id, NaN = never a candidate; len(key) == ntotal). Derived, never saved; add / reset / shard
+        drop it."""
+        key = key.float().contiguous() if hasattr(key, 'data_ptr') else np.ascontiguousarray(key, np.float32)
+        _lib.check(_lib.lib().asl_index_set_window_key(self._h, int(key.shape[0]), _lib.ptr(key)))
+
+    def search_window(self, x, k, precursor_mz, charge, tol, mode='Da', D=None, I=None):
+        """``search`` restricted to the vectors whose key (``set_window_key``) passes each query's
+        precursor window -- FAISS' ``search(x, k, params=SearchParametersIVF(sel=IDSelectorRange(...)))``
+        over a key-sorted id range: (D, I), rows (score desc, id asc) of the k best in-window vectors of
+        the probed lists, -1 padded. ``mode``: 'Da' or 'ppm' (the reference's window test)."""
+        x = _as_f32(x, self.d)
+        nq = x.shape[0]
+        pmz = (precursor_mz.double().contiguous() if hasattr(precursor_mz, 'data_ptr')
+               else np.ascontiguousarray(precursor_mz, np.float64))
+        if D is None and I is None:
+            if isinstance(x, np.ndarray):
+                D = np.empty((nq, k), np.float32)
+                I = np.empty((nq, k), np.int64)
+            else:
+                import torch
+                D = torch.empty((nq, k), dtype=torch.float32, device=x.device)
+                I = torch.empty((nq, k), dtype=torch.int64, device=x.device)
+        _lib.check(_lib.lib().asl_index_search_window(self._h, nq, _lib.ptr(x), _lib.ptr(pmz), int(charge),
+                                                      float(tol), {'Da': 0, 'ppm': 1}[mode], int(k),
+                                                      int(self.nprobe), _lib.ptr(D), _lib.ptr(I)))
+        return D, I
+
+    def set_window_scan(self, on: bool):
+        """True: ``asl_search_batch`` scans each query's precursor window only (``Config.ann_window =
+        'pre'``); False (default): the reference's post-filter."""
+        _lib.check(_lib.lib().asl_index_set_window_scan(self._h, int(bool(on))))
+
     def reset(self):
         self.epoch += 1
         _lib.check(_lib.lib().asl_index_reset(self._h))

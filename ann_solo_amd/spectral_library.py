@@ -340,6 +340,7 @@ class SpectralLibrary:
             if d is not None and d.world > 1:
                 part.index.shard(d.rank, d.world)
         part.index.nprobe = self._num_probe
+        part.index.set_window_scan(self.config.ann_window == 'pre')     # per index handle
         self._current_index = charge, part.index
         return part.index
 
@@ -351,6 +352,8 @@ class SpectralLibrary:
         search scans this rank's inverted lists for the whole batch and exchanges per-shard
         top-k, the standard search is data-parallel over the queries; every rank ends up with
         the results of the whole batch. Every rank must call ``search`` with the same queries."""
+        if self.config.ann_window == 'pre':
+            raise ValueError("enable_sharding: ann_window = 'pre' does not run on a sharded index")
         import torch.distributed as dist
         world = dist.get_world_size(group) if dist.is_initialized() else 1
         rank = dist.get_rank(group) if dist.is_initialized() else 0

@@ -151,6 +151,28 @@ int asl_index_get_refine(const asl_index_t *idx);
 int asl_index_refine(asl_index_t *idx, int32_t nq, const float *xq, int32_t kprime,
                      const int64_t *I_in /* [nq,kprime], -1 = empty */, int32_t k, float *D, int64_t *I);
 
+/* Window scan (FAISS: search(..., params=SearchParametersIVF(sel=IDSelectorRange(..., assume_sorted=true)))).
+ * The index keeps a second, derived copy of its tiled IVF-PQ layout in which every inverted list is
+ * ordered by a float32 key per vector (the library's precursor m/z), ascending, NaN last; a query's
+ * precursor window is then one contiguous run of every list, and only that run is scanned. Never
+ * saved; add, add_preassigned, reset and shard drop it. Unsupported (ASL_ERR_STATE, never a silent
+ * post-filter): IVF-Flat and Flat, the generic PQ kernel (scan_variant 1, m != 32, bits != 8),
+ * k > 1280, a sharded index.
+ * asl_index_set_window_key: sort key per vector id (float32 precursor m/z, NaN = never a candidate),
+ * n == ntotal: copied, and the window-ordered layout built (IVF-PQ, trained, unsharded, no caller ids). */
+int asl_index_set_window_key(asl_index_t *idx, int64_t n, const float *key);
+/* top-k (score desc, id asc) among the probed lists' vectors whose key passes
+ * precursor_ok(q_pmz[i], key, charge, tol, mode) -- the window test of asl_search_batch, same double
+ * arithmetic; -1 / -FLT_MAX padded. Same coarse quantiser and nprobe as asl_index_search. */
+int asl_index_search_window(asl_index_t *idx, int32_t nq, const float *xq, const double *q_pmz,
+                            int32_t charge, double tol, int32_t mode, int32_t k, int32_t nprobe,
+                            float *D, int64_t *I);
+/* 0 (default): asl_search_batch post-filters as the reference (the k best of the probed lists,
+ * then the window); 1: it scans each query's window only (the k best in-window vectors of the
+ * probed lists), with the window column of the library handle it is given as the key (installed
+ * whenever the layout holds another library's key or the lists changed). Per handle. */
+int asl_index_set_window_scan(asl_index_t *idx, int32_t on);
+
 /* IVF-Flat component storage. ASL_FLAT_F32 (the default since round 5) keeps every component as
  * given: the float32 vectors FAISS' CPU IndexIVFFlat stores (spectral_library.py:174-181) -- ids
  * and scores are those of an index over the unquantised vectors. ASL_FLAT_FX22 (opt-in; no FAISS
