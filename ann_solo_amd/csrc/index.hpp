@@ -1,0 +1,162 @@
+// index.hpp -- the index object (struct asl_index) and the index's internal interface: what
+// the index_*.hip units share and what search.hip / sharded.hip call. Private to the library.
+#pragma once
+#include "common.hpp"
+#include "ivf_kernels.hpp"
+
+namespace asl {
+
+constexpr size_t SCORE_CHUNK_BYTES = (size_t)1 << 30;
+constexpr int FLAT_KEYS_SLACK = 768;      // packed-key rows of the postings scan: k + 768 <= its 2048-key buffer
+
+// scratch of asl_index_search_sharded (sharded.hip), grow-only: steady-state calls allocate nothing
+struct ShardScratch {
+  DevBuf<float> x_all, cD, cD_all, Dp, Dr, Dtmp, Dfin, x3, cD3;
+  DevBuf<int32_t> cI, cI_all, cI3, mine, everyone;       // (mine / everyone: a few ints every rank must see the same way)
+  DevBuf<int64_t> Ip, Ir, Im;
+  // the queries as entry lists (coarse_sparse.hip: list_nonzeros): own, everybody's, second scans
+  DevBuf<uint2> e_loc, e_all, e3;
+  DevBuf<int32_t> c_loc, c_all, c3, over;
+  // the exact key exchange (exchange.hip)
+  DevBuf<int64_t> Kp, Hs, Hr, Ko, Bs, Br, Xs, Xr, Mn, rowlist, K3;
+  DevBuf<int32_t> need, flag, Fl, rmap;
+  DevBuf<unsigned int> cursor;
+};
+
+// what the rows of a search hold: ORDERED (score desc, id asc), -1 padded; SET: the same hits in any order;
+// SET_RAW / KEYS: as under asl_index_set_unordered(1) / (2) -- a set never re-ranked / packed 64-bit keys in I64
+enum IndexRows { ROWS_ORDERED = 0, ROWS_SET, ROWS_SET_RAW, ROWS_KEYS };
+
+// One search of index_search_device. Value-initialised: a dense ordered search with the index's own
+// coarse stage. All pointers are device memory that stays valid until the scan has run.
+struct IndexSearch {
+  int nq = 0;
+  const float *xq = nullptr;        // [nq, d] dense queries; may be null when pre_ent is given
+  int k = 0, nprobe = 0;
+  float *D = nullptr;               // outputs [nq, k]; any may be null
+  int64_t *I64 = nullptr;
+  int32_t *I32 = nullptr;
+  const float *pre_D = nullptr;     // the caller's probe lists [nq, nprobe] (null: the coarse stage runs here);
+  const int32_t *pre_I = nullptr;   // IVF-Flat reads pre_I alone
+  const uint2 *pre_ent = nullptr;   // the queries as entry lists [nq, 64] + counts [nq] (list_nonzeros /
+  const int32_t *pre_cnt = nullptr; // encode_entries_device); a hint when xq is given as well
+  const int *gate = nullptr;        // device-side count: only the first *gate rows are searched
+  int rows = ROWS_ORDERED;          // IndexRows; a mode set with asl_index_set_unordered goes before ORDERED / SET
+  const IndexPostFilter *post = nullptr;   // precursor window applied in the scan's finish where the scan can
+  uint64_t serial = 0;              // ... of the library (asl_library serial) that owns post->payload
+  const IndexWindow *win = nullptr; // scan the in-window run of every probed list only (window-ordered layout)
+  bool rows_filtered = false;       // OUT: the rows hold in-window hits only, their lengths in count / row_len
+};
+
+}  // namespace asl
+
+struct asl_index {
+  int d = 0, nlist = 0, kind = 0, pq_m = 0, pq_bits = 8, ksub = 0, dsub = 0;
+  int niter = 25;
+  bool trained = false;
+  int64_t ntotal = 0;   // global vectors added
+  int64_t n_store = 0;  // vectors stored here
+  int shard_rank = 0, shard_world = 1;
+  asl::DevBuf<float> centroids, codebooks;
+  asl::DevBuf<float> codebooks_t;  // [m][dsub][ksub] copy for the tiled scan's LUT build
+  bool cbt_ready = false;
+  // sparse coarse quantiser (coarse_sparse.hip): transposed centroids [d][nlist] + per-batch scratch
+  asl::DevBuf<float> centroids_t;
+  bool cent_t_ready = false;
+  asl::DevBuf<float> kmeans_ct;       // transposed centroids of the running k-means iteration
+  asl::DevBuf<uint2> scan_ent;        // the scan's own entry lists (the coarse stage of the NEXT batch
+  asl::DevBuf<int32_t> scan_cnt;      // overwrites cs_ent on the other stream of the pipeline)
+  asl::DevBuf<int> scan_over;
+  asl::DevBuf<uint2> cs_ent;
+  asl::DevBuf<int32_t> cs_cnt;
+  asl::DevBuf<int> cs_over;
+  // add-order storage
+  asl::DevBuf<float> vecs;        // FLAT, IVFFLAT
+  asl::DevBuf<int32_t> vlist;     // IVF kinds: inverted list of each stored vector
+  asl::DevBuf<int32_t> vids;      // global id of each stored vector (only when sharded)
+  bool has_vids = false;
+  asl::DevBuf<uint8_t> codes_add; // IVFPQ
+  // list-order storage (IVFPQ scan layout)
+  asl::DevBuf<uint8_t> codes;
+  asl::DevBuf<int32_t> ids, list_offsets;
+  std::vector<int32_t> h_list_offsets;
+  // 64-vector tiles for the tiled scan, pq_scan_v3.hip (m = 32)
+  asl::DevBuf<uint8_t> codes_tiled;
+  asl::DevBuf<int32_t> ids_tiled, tile_offsets;
+  // post-filter in the scan's finish (common.hpp: ScanPostFilter): (id, window value) per storage slot
+  // -- per tile slot (IVF-PQ) or per list position (IVF-Flat) --, built on demand
+  asl::DevBuf<int2> idpay;
+  int64_t n_tile_slots = 0;
+  uint64_t pay_serial = 0;       // serial of the library whose window column the pairs hold
+  int64_t pay_n = 0;
+  bool idpay_ready = false;
+  bool has_tiles = false;
+  // window-ordered copy of the tiled layout (window_install): each list's vectors by a float32 key per
+  // vector, ascending, NaN last -- same list and tile offsets as the default layout, which stays as it
+  // is. Derived, never saved; build_lists drops it (add, add_preassigned, reset and shard all rebuild).
+  asl::DevBuf<uint8_t> wcodes_tiled;
+  asl::DevBuf<int32_t> wids_tiled;
+  asl::DevBuf<float> wkey_tiled;      // the key per tile slot (NaN in a list's last tile behind its end)
+  bool win_ready = false;
+  uint64_t win_serial = 0;       // serial of the library whose window column is the key; 0: a caller's key
+  int window_scan = 0;           // asl_index_set_window_scan: asl_search_batch scans each query's window only
+  asl::DevBuf<int2> win_ranges;       // [nq, nprobe] in-window run of each probed list
+  // dimension-major postings for flat_inv_scan (IVF-Flat): blocks of FI_BLK vectors
+  asl::DevBuf<int32_t> blk_offsets;   // [nlist + 1] first block of each list
+  asl::DevBuf<uint32_t> blk_base;     // [nblocks] start of the block's postings, 64-byte units
+  asl::DevBuf<uint32_t> inv_tab;      // [nblocks * d] (start from the block's base in 64-byte units) << 16 | postings
+  asl::DevBuf<char> inv_data;         // segments: c values (f32) then c local vector indices (u16), placed by 128-byte line
+  bool has_inv = false;
+  // the fixed-point layout (inv_layout 2): blk_base in 128-byte lines, one byte per (block,
+  // dimension) = lines of the segment, posting words (numerator << 10 | local index) in inv_data
+  int flat_storage = ASL_FLAT_F32;   // ASL_FLAT_F32 (default): components as given; ASL_FLAT_FX22: add() rounds
+                                     // components in [0, 1) to 22 fractional bits
+  int inv_layout = 0;            // what build_lists found the data fit for: 0 none, 1 float postings, 2 fixed-point words
+  int tab_stride = 0;            // bytes per block of inv_tab8 (d rounded up to a 128-byte line)
+  asl::DevBuf<uint8_t> inv_tab8;
+  asl::DevBuf<uint16_t> inv_cnt16;    // postings per (block, dimension): work accounting only (asl_index_postings_work)
+  int scan_variant = 0;  // 0 = the layout-specific scan when the shape allows; 1 = the generic kernels
+  int unordered = 0;  // 1: search rows = exact top-k as a set, unspecified order (no final sort); 2: rows of packed keys
+  bool lists_dirty = true;
+  // asl_index_search_sharded: did every rank's shard answer asl_index_supports_keys with 1 for this
+  // (k, nprobe, world)? -1 = not agreed yet (reset whenever the lists are rebuilt)
+  int agreed_k = -1, agreed_np = -1, agreed_world = -1, agreed_val = -1;
+  // exact re-rank of the IVF-PQ short-list (refine.hip): sparse copies of the added vectors,
+  // add order = global id; kept whole on every shard
+  int refine_k = 0;            // 0 = off; else the short-list size k' (> k) that is re-ranked
+  bool refine_rows = false;    // rows are being stored on add()
+  bool refine_bad = false;     // a vector had more non-zeros than a row holds
+  int64_t r_n = 0;
+  asl::DevBuf<uint16_t> r_dim;
+  asl::DevBuf<float> r_val;
+  asl::DevBuf<uint8_t> r_cnt;
+  asl::DevBuf<int32_t> ws_short;
+  // scratch
+  asl::DevBuf<float> ws_scores, coarse_D, ws_x;
+  asl::DevBuf<int32_t> coarse_I, ws_assign;
+  asl::DevBuf<uint32_t> bitmap;
+  asl::DevBuf<uint64_t> ws_upper;     // k > TK_MAX_K: the bound of every row between the passes
+  asl::ShardScratch shard;       // asl_index_search_sharded
+};
+
+namespace asl {
+
+// index_train.hip
+int assign_ip(asl_index *ix, const float *x, int64_t ld, int64_t n, const float *cent, int k, int d,
+              int32_t *assign_dev);
+// index_lists.hip
+int build_lists(asl_index *ix);
+const char *window_unsupported(const asl_index *ix);
+int window_install(asl_index *ix, int64_t n, const float *key, uint64_t serial);
+int post_filter_pairs(asl_index *ix, const IndexPostFilter &p, uint64_t serial, const int32_t *slot_ids,
+                      int64_t nslots);
+// index_search.hip
+int index_search_device(asl_index *ix, IndexSearch &rq);
+int index_nprobe(const asl_index *ix, int nprobe);
+int index_prepare(asl_index *ix);
+int coarse_search(asl_index *ix, const float *xq, int nq, int nprobe, float *out_D, int32_t *out_I, uint2 *ent_out,
+                  int32_t *cnt_out, bool *have_ent);
+int index_window_prepare(asl_index *ix, uint64_t serial, const float *key, int64_t n, int nq, int nprobe);
+int index_refine_k(const asl_index *ix);
+
+}  // namespace asl

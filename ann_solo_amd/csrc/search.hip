@@ -13,29 +13,13 @@
 #include <algorithm>
 #include <atomic>
 
-#include "common.hpp"
-#include "ivf_kernels.hpp"
+#include "index.hpp"
 #include "rescore.hpp"
 
 namespace asl {
 int encode_device(const float *mz, const float *inten, const int32_t *offsets, int32_t n,
                   double min_bound, double bin_size, int32_t hash_len, uint32_t seed,
                   int norm, float *out);
-int index_search_device(asl_index *ix, int nq, const float *xq, int k, int nprobe, float *D,
-                        int64_t *I64, int32_t *I32, const float *pre_D, const int32_t *pre_I,
-                        bool set_mode, const int *gate = nullptr, const uint2 *pre_ent = nullptr,
-                        const int32_t *pre_cnt = nullptr);
-int index_dim(const asl_index *ix);
-void index_set_post_filter(asl_index *ix, const IndexPostFilter &p);
-bool index_post_filter_applied(asl_index *ix);
-int index_nprobe(const asl_index *ix, int nprobe);
-int index_prepare(asl_index *ix);
-int index_coarse_device(asl_index *ix, int nq, const float *xq, int nprobe, float *out_D,
-                        int32_t *out_I, uint2 *ent_out = nullptr, int32_t *cnt_out = nullptr,
-                        bool *have_ent = nullptr);
-bool index_window_scan_on(const asl_index *ix);
-int index_window_prepare(asl_index *ix, uint64_t serial, const float *key, int64_t n, int nq, int nprobe);
-void index_set_window(asl_index *ix, const IndexWindow &w);
 // Window [lo,hi) of each query inside the precursor-sorted library.
 __global__ void window_range_kernel(const double *__restrict__ q_pmz, int nq,
                                     const float *__restrict__ sorted_pmz, int n, int charge,
@@ -165,27 +149,21 @@ static int64_t &window_pair_budget() {
   static int64_t b = 1ll << 28;
   return b;
 }
-// window-scan mode (asl_index_set_window_scan): the window of the next scan; row_len: set-mode rows
-static void offer_window(asl_index *idx, const DevPeaks &Q, const asl_search_params_t *P, int32_t *row_len) {
-  IndexWindow w;
-  w.q_pmz = Q.precursor_mz;
-  w.row_len = row_len;
-  w.tol = P->precursor_tol;
-  w.mode = P->precursor_mode;
-  w.charge = P->charge;
-  index_set_window(idx, w);
+// The precursor window of a batch's scan, into its request: the window scan (asl_index_set_window_scan)
+// when the index is in that mode, else -- no ordered neighbour list asked for -- the scan-side
+// post-filter of THIS library's window column. row_len: the lengths of the set-mode rows.
+static void offer_window(IndexSearch &rq, IndexWindow &w, const DevPeaks &Q, const asl_search_params_t *P,
+                         int32_t *row_len) {
+  w = {.q_pmz = Q.precursor_mz, .row_len = row_len, .tol = P->precursor_tol, .mode = P->precursor_mode,
+       .charge = P->charge};
+  rq.win = &w;
 }
-static void offer_post_filter(asl_library *L, asl_index *idx, const DevPeaks &Q, const asl_search_params_t *P,
-                              int32_t *row_len) {
-  IndexPostFilter pf;
-  pf.payload = L->wcol.p;
-  pf.n = L->n;
-  pf.q_pmz = Q.precursor_mz;
-  pf.count = row_len;
-  pf.tol = P->precursor_tol;
-  pf.mode = P->precursor_mode;
-  pf.charge = P->charge;
-  index_set_post_filter(idx, pf);
+static void offer_post_filter(IndexSearch &rq, IndexPostFilter &pf, const asl_library *L, const DevPeaks &Q,
+                              const asl_search_params_t *P, int32_t *row_len) {
+  pf = {.payload = L->wcol.p, .n = L->n, .q_pmz = Q.precursor_mz, .count = row_len, .tol = P->precursor_tol,
+        .mode = P->precursor_mode, .charge = P->charge};
+  rq.post = &pf;
+  rq.serial = L->serial;
 }
 
 // the precursor filter / row records of a library handle
@@ -193,6 +171,14 @@ static void library_filter(const asl_library *L, PrecFilter &flt) {
   flt.meta = reinterpret_cast<const RowMeta *>(L->records.p);
   flt.meta_stride = L->slot;
   flt.wcol = L->wcol.p;
+}
+static void batch_filter(const asl_library *L, const asl_search_params_t *P, PrecFilter &flt) {
+  flt.lib_pmz = L->pmz32.p;
+  flt.valid = L->has_valid ? L->valid.p : nullptr;
+  library_filter(L, flt);
+  flt.tol = P->precursor_tol;
+  flt.mode = P->precursor_mode;
+  flt.charge = P->charge;
 }
 
 extern "C" {
@@ -540,12 +526,7 @@ int asl_rescore_knn(asl_library_t *L, const asl_peaks_t *queries, const asl_sear
   ASL_TRY(L->pair_score.reserve((size_t)nq * k));
   // the precursor filter runs inside the rescoring kernel's compaction stage
   PrecFilter flt;
-  flt.lib_pmz = L->pmz32.p;
-  flt.valid = L->has_valid ? L->valid.p : nullptr;
-  library_filter(L, flt);
-  flt.tol = P->precursor_tol;
-  flt.mode = P->precursor_mode;
-  flt.charge = P->charge;
+  batch_filter(L, P, flt);
   ASL_TRY(rescore_device(Q.dev, L->dev, knn.d, nullptr, nullptr, k, (int64_t)nq * k,
                          P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p,
                          L->best_slot.p, nullptr, o_row.d, o_score.d, o_ncand.d, o_cnt.d,
@@ -579,14 +560,14 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
     explicit InCall(Pipeline &q) : p(q) { p.in_call = true; }
     ~InCall() { p.in_call = false; }
   } guard(pp);
-  const int nq = queries->n, k = P->k, d = index_dim(idx);
+  const int nq = queries->n, k = P->k, d = idx->d;
   const int nprobe = index_nprobe(idx, P->nprobe);
   PeaksStage Q;
   ASL_TRY(Q.init(queries));   // device pointers + known peak count: no copy, no wait
   const int par = pp.parity;
   // allocations first (growing a buffer synchronises the device: only ever on the first batches)
   ASL_TRY(index_prepare(idx));
-  const bool win = index_window_scan_on(idx);      // (the window-ordered layout of THIS library, up front)
+  const bool win = idx->window_scan != 0;      // (the window-ordered layout of THIS library, up front)
   if (win) ASL_TRY(index_window_prepare(idx, L->serial, L->wcol.p, L->n, nq, nprobe));
   ASL_TRY(L->p_qvec[par].reserve((size_t)nq * d));
   ASL_TRY(L->p_cD[par].reserve((size_t)nq * nprobe));
@@ -615,7 +596,7 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
     if (pp.scan_recorded[par]) HIP_TRY(hipStreamWaitEvent(pp.A, pp.ev_scan[par], 0));
     ASL_TRY(encode_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
                           d, P->hash_seed, 1, L->p_qvec[par].p));
-    ASL_TRY(index_coarse_device(idx, nq, L->p_qvec[par].p, nprobe, L->p_cD[par].p, L->p_cI[par].p,
+    ASL_TRY(coarse_search(idx, L->p_qvec[par].p, nq, nprobe, L->p_cD[par].p, L->p_cI[par].p,
                                 L->p_ent[par].p, L->p_cnt[par].p, &L->p_have_ent[par]));
     HIP_TRY(hipEventRecord(pp.ev_front[par], pp.A));
   }
@@ -624,15 +605,18 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
     HIP_TRY(hipStreamWaitEvent(pp.B, pp.ev_front[par], 0));
     if (pp.resc_recorded[par]) HIP_TRY(hipStreamWaitEvent(pp.B, pp.ev_resc[par], 0));
     // (the entry lists of the coarse stage, when it made them: the scan does not list the rows again)
-    if (win) offer_window(idx, Q.dev, P, knn_I == nullptr ? L->p_rows[par].p : nullptr);
-    else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(L, idx, Q.dev, P, L->p_rows[par].p);
-    const int rc_scan = index_search_device(idx, nq, L->p_qvec[par].p, k, nprobe, nullptr, knn_I,
-                                            L->p_knn[par].p, L->p_cD[par].p, L->p_cI[par].p,
-                                            knn_I == nullptr, nullptr, L->p_have_ent[par] ? L->p_ent[par].p : nullptr,
-                                            L->p_have_ent[par] ? L->p_cnt[par].p : nullptr);
+    IndexSearch rq{.nq = nq, .xq = L->p_qvec[par].p, .k = k, .nprobe = nprobe, .I64 = knn_I, .I32 = L->p_knn[par].p,
+                   .pre_D = L->p_cD[par].p, .pre_I = L->p_cI[par].p,
+                   .pre_ent = L->p_have_ent[par] ? L->p_ent[par].p : nullptr,
+                   .pre_cnt = L->p_have_ent[par] ? L->p_cnt[par].p : nullptr,
+                   .rows = knn_I == nullptr ? ROWS_SET : ROWS_ORDERED};
+    IndexWindow w;
+    IndexPostFilter pf;
+    if (win) offer_window(rq, w, Q.dev, P, knn_I == nullptr ? L->p_rows[par].p : nullptr);
+    else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(rq, pf, L, Q.dev, P, L->p_rows[par].p);
+    ASL_TRY(index_search_device(idx, rq));
     // (window scan: set-mode rows hold in-window hits only, and their lengths)
-    rows_filtered = index_post_filter_applied(idx) || (win && knn_I == nullptr);
-    ASL_TRY(rc_scan);
+    rows_filtered = rq.rows_filtered;
     HIP_TRY(hipEventRecord(pp.ev_scan[par], pp.B));
     pp.scan_recorded[par] = true;
   }
@@ -643,12 +627,7 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
     StreamScope on_c(sc);
     HIP_TRY(hipStreamWaitEvent(sc, pp.ev_scan[par], 0));
     PrecFilter flt;
-    flt.lib_pmz = L->pmz32.p;
-    flt.valid = L->has_valid ? L->valid.p : nullptr;
-    library_filter(L, flt);
-    flt.tol = P->precursor_tol;
-    flt.mode = P->precursor_mode;
-    flt.charge = P->charge;
+    batch_filter(L, P, flt);
     ASL_TRY(rescore_device(Q.dev, L->dev, nullptr, L->p_knn[par].p, nullptr, k, (int64_t)nq * k,
                            P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p,
                            L->best_slot.p, nullptr, best_row, best_score, n_cand, pm_count,
@@ -705,32 +684,29 @@ int asl_search_batch(asl_library_t *L, asl_index_t *idx, const asl_peaks_t *quer
   ASL_TRY(L->best_slot.reserve((size_t)nq));
   ASL_TRY(L->status.reserve(1));
   if (P->use_ann) {
-    const int d = index_dim(idx), k = P->k;
+    const int d = idx->d, k = P->k;
     if (k <= 0) return fail(ASL_ERR_INVALID, "search_batch: k must be positive");
     ASL_TRY(o_knn.init(knn_I, (size_t)nq * k));
     ASL_TRY(L->qvec.reserve((size_t)nq * d));
     ASL_TRY(L->knn.reserve((size_t)nq * k));
     ASL_TRY(L->pair_score.reserve((size_t)nq * k));
-    const bool win = index_window_scan_on(idx);
+    const bool win = idx->window_scan != 0;
     if (win) ASL_TRY(index_window_prepare(idx, L->serial, L->wcol.p, L->n, nq, P->nprobe));
     ASL_TRY(encode_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
                           d, P->hash_seed, 1, L->qvec.p));
     // the candidates are consumed as a set (filter + best match): no final sort unless the
     // caller asked for the ordered neighbour list
     ASL_TRY(L->rows_len.reserve((size_t)nq));
-    if (win) offer_window(idx, Q.dev, P, knn_I == nullptr ? L->rows_len.p : nullptr);
-    else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(L, idx, Q.dev, P, L->rows_len.p);
-    const int rc_scan = index_search_device(idx, nq, L->qvec.p, k, P->nprobe, nullptr, o_knn.d, L->knn.p,
-                                            nullptr, nullptr, knn_I == nullptr);
-    const bool rows_filtered = index_post_filter_applied(idx) || (win && knn_I == nullptr);
-    ASL_TRY(rc_scan);
+    IndexSearch rq{.nq = nq, .xq = L->qvec.p, .k = k, .nprobe = P->nprobe, .I64 = o_knn.d, .I32 = L->knn.p,
+                   .rows = knn_I == nullptr ? ROWS_SET : ROWS_ORDERED};
+    IndexWindow w;
+    IndexPostFilter pf;
+    if (win) offer_window(rq, w, Q.dev, P, knn_I == nullptr ? L->rows_len.p : nullptr);
+    else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(rq, pf, L, Q.dev, P, L->rows_len.p);
+    ASL_TRY(index_search_device(idx, rq));
+    const bool rows_filtered = rq.rows_filtered;
     PrecFilter flt;
-    flt.lib_pmz = L->pmz32.p;
-    flt.valid = L->has_valid ? L->valid.p : nullptr;
-    library_filter(L, flt);
-    flt.tol = P->precursor_tol;
-    flt.mode = P->precursor_mode;
-    flt.charge = P->charge;
+    batch_filter(L, P, flt);
     ASL_TRY(rescore_device(Q.dev, L->dev, nullptr, L->knn.p, nullptr, k, (int64_t)nq * k,
                            P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p,
                            L->best_slot.p, nullptr, o_row.d, o_score.d, o_ncand.d, o_cnt.d,

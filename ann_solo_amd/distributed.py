@@ -199,7 +199,7 @@ class HipShardBackend:
     # packed 8-byte hits for the exchange (instead of 4-byte score + 8-byte id)
     @property
     def supports_keys(self):
-        """Packed-key rows come from the tiled IVF-PQ scan (index.hip: m = 32, 8-bit codes,
+        """Packed-key rows come from the tiled IVF-PQ scan (index_search.hip: m = 32, 8-bit codes,
         automatic scan variant, nprobe within the tiled kernel's limit, k + 768 <= 2048) and from
         the postings scan of IVF-Flat -- which THIS shard has only if it stores sparse vectors;
         every other configuration exchanges (D, I) rows. The value is local: the driver agrees

@@ -47,7 +47,7 @@ def score_bucket(s):
 
 
 def shard_k(k, world):
-    """asl_shard_k (csrc/index.hip): the shards' own k."""
+    """asl_shard_k (csrc/index_shard.hip): the shards' own k."""
     if k < 1 or world < 4:
         return k
     raw = (k + 1) // 2 if world >= 8 else (5 * k + 7) // 8

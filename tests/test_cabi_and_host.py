@@ -91,7 +91,7 @@ def test_config_refuses_what_the_kernels_cannot_hold():
     with pytest.raises(ValueError):
         Config.from_reference(dict(max_peaks_used=500))
     assert Config(max_peaks_used=256, num_candidates=2048).max_peaks_used == 256
-    assert Config(num_candidates=5000).num_candidates == 5000      # beyond 2 048: bounded passes (index.hip)
+    assert Config(num_candidates=5000).num_candidates == 5000      # beyond 2 048: bounded passes (index_search.hip)
 
 
 def test_hyperparameter_hash_formula():

@@ -166,7 +166,9 @@ def test_plain_bench_line_and_dumped_outputs(tmp_path, workload):
         assert leg not in d, leg
     if workload == 'batch':
         nq = d['batch_per_step']
-        assert d['value'] == pytest.approx(nq / (d['ms_per_step'] * 1e-3), rel=1e-3)
+        # (ms_per_step is printed with 3 decimals: at a fraction of a millisecond per step its rounding, up to
+        # 0.0005 ms, is more than 1e-3 of it -- the two figures agree to 1e-3 beyond what that rounding moves)
+        assert d['value'] == pytest.approx(nq / (d['ms_per_step'] * 1e-3), rel=1e-3 + 0.0005 / d['ms_per_step'])
         assert set(a) == {'best_row', 'best_score', 'n_candidates', 'pm_count', 'pm_pairs'}
         assert all(a[k].shape == (nq,) and a[k].dtype == np.float64 for k in a if k != 'pm_pairs')
         assert a['pm_pairs'].dtype == np.float32 and a['pm_pairs'].shape[0] == nq

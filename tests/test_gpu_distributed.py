@@ -404,6 +404,33 @@ for index in ('ivfpq', 'ivfflat', 'ivfpq+refine'):
     host = np.zeros((q.n, 256), np.int64)
     assert L.asl_index_search_sharded(idx._h, comm, q.n, _lib.ptr(vec), 256, 16, _lib.ptr(D), _lib.ptr(host)) < 0
     sl.shutdown()
+# two index handles of different size in one process, their calls interleaved (no wait between them):
+# the exchange's scratch belongs to a handle, so each returns what it returns alone
+pair = []
+for n_, nq_, nlist_, seed_ in ((20000, 300, 64, 5), (7000, 120, 32, 9)):
+    lib_, aux_ = synthetic.make_library(n_, seed=seed_, device=dev, charges=(2,), charge_p=(1.0,))
+    q_, _ = synthetic.make_queries(lib_, aux_, nq_, seed=seed_ + 1, open_range=300.0, charge=2)
+    sl_ = SpectralLibrary(lib_, config=Config.open_search(num_list=nlist_, num_probe=16, num_candidates=256,
+                                                          index='ivfpq', kmeans_niter=4), device=dev)
+    idx_ = sl_._get_ann_index(2)
+    vec_ = sl_._encode(q_)
+    idx_.nprobe = 16
+    D0_, I0_ = idx_.search(vec_, 256)
+    idx_.shard(0, 1)
+    pair.append((sl_, idx_, vec_, D0_, I0_, torch.empty_like(D0_), torch.empty_like(I0_)))
+for head, sk, xper in ((0, 0, -1), (100, 160, 256), (100, 0, 0), (0, 0, -1)):
+    for sl_, idx_, vec_, D0_, I0_, D_, I_ in pair:
+        D_.fill_(-5.0)
+        I_.fill_(-5)
+    for sl_, idx_, vec_, D0_, I0_, D_, I_ in pair:
+        rc = L.asl_index_search_sharded_ex(idx_._h, comm, vec_.shape[0], _lib.ptr(vec_), 256, 16, _lib.ptr(D_),
+                                           _lib.ptr(I_), head, sk, xper)
+        assert rc == 0, (L.asl_last_error(), head, sk, xper)
+    torch.cuda.synchronize()
+    for sl_, idx_, vec_, D0_, I0_, D_, I_ in pair:
+        assert torch.equal(I_, I0_) and torch.equal(D_, D0_), ('two handles', vec_.shape[0], head, sk, xper)
+for p_ in pair:
+    p_[0].shutdown()
 rccl.ncclCommDestroy.argtypes = [C.c_void_p]
 rccl.ncclCommDestroy(comm)
 print('rccl-cabi-ok')

@@ -733,7 +733,7 @@ def test_more_than_512_probes_equal_the_oracle(O, kind):
 def test_k_beyond_the_lds_top_k_in_bounded_passes(O, vecs, trained, kind):
     """The reference's CPU path has no bound on --num_candidates (config.py:188-192; its notebooks look at
     5 000+ neighbours, notebooks/iprg2012_num_candidates.ipynb:282-288). Beyond 2 048 the index searches
-    in ceil(k / 2048) bounded passes (csrc/index.hip: index_search_large_k): rows equal the oracle's --
+    in ceil(k / 2048) bounded passes (csrc/index_search.hip: pass_bounds): rows equal the oracle's --
     ids, score bits, (score desc, id asc) order, -1 padding where a query reaches fewer than k vectors
     (4 000 stored) -- on every index kind, with host and device outputs."""
     import torch

@@ -332,3 +332,72 @@ def test_window_filter_inside_the_scan_equals_the_filter_inside_the_rescoring(O,
         if tol == 1e9:
             assert res[1].n_candidates.max() == 1024
         sl.shutdown()
+
+
+@pytest.mark.parametrize('index', ['ivfpq', 'ivfflat'])
+def test_scan_filter_follows_the_library_not_its_address(O, index):
+    """One index handle, two libraries of the SAME size, one after the other: library A is searched
+    with the scan-side precursor filter on and freed, library B -- the same spectra under other
+    precursor m/z -- is created (the allocator may hand it A's addresses) and searched through the
+    same index handle. The (id, window value) pairs the index caches for the filter belong to a
+    library, not to an address: B's winners, scores, candidate counts and peak matches equal the
+    oracle's and those of the same search with the filter in the rescoring, synchronous and pipelined."""
+    from ann_solo_amd import _lib, synthetic
+    from ann_solo_amd.packed import PackedSpectra
+    from ann_solo_amd.spectral_library import Config, SpectralLibrary
+    lib_a, aux = synthetic.make_library(5000, seed=171, device='cpu', charges=(2,), charge_p=(1.0,))
+    q, _ = synthetic.make_queries(lib_a, aux, 200, seed=172, charge=2)
+    q = PackedSpectra.from_numpy(*q.numpy())
+    cfg = Config.open_search(num_list=16, num_probe=8, num_candidates=1024, index=index, kmeans_niter=4,
+                             precursor_tolerance_mass_open=100.0, precursor_tolerance_mode_open='Da')
+    sl = SpectralLibrary(lib_a, config=cfg)
+    L = _lib.lib()
+    fields = ('best_row', 'best_score', 'n_candidates', 'pm_count', 'pm_pairs')
+
+    def run(on):
+        L.asl_set_scan_postfilter(on)
+        sync = sl._search_batch(q, 2, 'open')
+        sl.set_pipeline(True)
+        pipe = [sl._search_batch(q.to('cuda:0'), 2, 'open', device_out=True) for _ in range(2)]
+        sl.synchronize()
+        sl.set_pipeline(False)
+        for r in pipe:
+            for f in fields:
+                got = getattr(r, f).cpu().numpy()
+                assert np.array_equal(got.astype(getattr(sync, f).dtype), getattr(sync, f)), (on, f)
+        return sync
+
+    def check(res):
+        Lo, pmz32, ivf = _oracle_partition(O, sl, 2)
+        ref = O.search_batch(O.Spectra(*q.numpy()), Lo, pmz32, 2, ivf, 1024, 8, 100.0, 'Da', 0.02, True,
+                             pm_stride=res.pm_pairs.shape[1])
+        for f, g in zip(fields[:4], ('best_row', 'best_score', 'n_cand', 'pm_count')):
+            assert np.array_equal(getattr(res, f), ref[g]), f
+        for i in range(q.n):
+            n = ref['pm_count'][i]
+            assert np.array_equal(res.pm_pairs[i, :n], ref['pm_pairs'][i, :n]), i
+    try:
+        a_on = run(1)
+        check(a_on)
+        a_off = run(0)
+        for f in fields:
+            assert np.array_equal(getattr(a_on, f), getattr(a_off, f)), f
+        # library B: A's spectra, the precursor m/z reversed over the rows (same size, other masses)
+        part = sl.partitions[2]
+        idx = sl._get_ann_index(2)
+        o, mz, it, chg, pmz, pz = part.spectra.to('cpu').numpy()
+        lib_b = PackedSpectra.from_numpy(o, mz, it, chg, np.ascontiguousarray(pmz[::-1]), pz)
+        L.asl_library_free(part.handle)
+        part.handle = None
+        sl._add_partition(2, lib_b, part.ids, np.ones(lib_b.n, bool), None)
+        sl.partitions[2].index = idx                     # the SAME index handle
+        assert sl._get_ann_index(2) is idx
+        b_on = run(1)
+        b_off = run(0)
+        for f in fields:
+            assert np.array_equal(getattr(b_on, f), getattr(b_off, f)), f
+        check(b_on)
+        assert not np.array_equal(a_on.best_row, b_on.best_row)      # the masses did change the answer
+    finally:
+        L.asl_set_scan_postfilter(1)
+        sl.shutdown()
