@@ -77,6 +77,7 @@ EXPORTS = [
     'asl_keys_rescan_list', 'asl_shard_k', 'asl_index_search_gated', 'asl_index_search_entries',
     'asl_encode_entries_batch', 'asl_index_search_sharded_ex',
     'asl_index_set_window_key', 'asl_index_search_window', 'asl_index_set_window_scan',
+    'asl_rescore_batch_topn', 'asl_search_batch_topn', 'asl_rescore_knn_topn',
 ]
 
 
@@ -233,6 +234,17 @@ def lib():
         L.asl_rescore_knn.argtypes = [C.c_void_p, C.POINTER(AslPeaks),
                                       C.POINTER(AslSearchParams), C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        L.asl_rescore_batch_topn.argtypes = [C.POINTER(AslPeaks), C.POINTER(AslPeaks), C.c_void_p,
+                                             C.c_void_p, C.c_double, C.c_int, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        L.asl_search_batch_topn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(AslPeaks),
+                                            C.POINTER(AslSearchParams), C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.c_void_p]
+        L.asl_rescore_knn_topn.argtypes = [C.c_void_p, C.POINTER(AslPeaks),
+                                           C.POINTER(AslSearchParams), C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int32]
         L.asl_lpt_owner.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         L.asl_window_candidates.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                             C.c_double, C.c_int32, C.c_void_p, C.c_void_p]

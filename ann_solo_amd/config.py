@@ -3,7 +3,7 @@
 ``Config`` carries the reference's flags under the reference's names
 (/root/reference/src/ann_solo/config.py:62-216) plus the ADDITIVE flags of this implementation
 (``index``, ``pq_m``, ``pq_bits``, ``refine_k``, ``kmeans_niter``, ``ann_seed``, ``num_gpus``,
-``flat_storage``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``flat_storage``, ``ann_window``, ``num_matches``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -80,10 +80,14 @@ class Config:
     ann_window: str = 'post'                # open search: 'post' (the reference's order: k best of the probed
                                             # lists, then the precursor window) | 'pre' (opt-in, IVF-PQ: the k
                                             # best in-window vectors of the probed lists)
+    num_matches: int = 1                    # library matches reported per query: 1 (the reference: the best
+                                            # match) .. 16; > 1 adds the runners-up and the score gap to the
+                                            # SSMs (top-n rescoring), identifications and FDR stay rank 0's
 
     MAX_PEAKS = 256      # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
     MAX_CANDIDATES = 16384   # largest num_candidates: beyond MAX_TOPK in bounded passes (TK_MAX_K_PASSES)
+    MAX_MATCHES = 16     # largest num_matches (include/annsolo_mi.h: ASL_MAX_BEST)
 
     def __post_init__(self):
         for name in ('max_peaks_used', 'max_peaks_used_library'):
@@ -107,6 +111,10 @@ class Config:
                 raise ValueError("ann_window = 'pre' does not run on a sharded index (num_gpus > 1)")
             if self.refine_k:
                 raise ValueError("ann_window = 'pre' does not combine with refine_k")
+        if not 1 <= int(self.num_matches) <= self.MAX_MATCHES:
+            raise ValueError(f'num_matches = {self.num_matches}: 1 .. {self.MAX_MATCHES}')
+        if int(self.num_matches) > 1 and self.num_gpus and int(self.num_gpus) > 1:
+            raise ValueError('num_matches > 1 does not run on a sharded index (num_gpus > 1)')
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -195,3 +203,8 @@ def add_arguments(parser) -> None:
                              "probed lists, then those in the precursor window (the reference); 'pre' "
                              'keeps the k best vectors of the probed lists that are in the window '
                              '(IVF-PQ, m = 32, 8 bits; one GPU) (default: %(default)s)')
+    parser.add_argument('--num_matches', default=d.num_matches, type=int,
+                        help='library matches reported per query, best first (1 .. 16): above 1 every '
+                             'SSM also carries its runners-up and the score gap to the second best; '
+                             'identifications, scores and FDR are those of the best match; one GPU '
+                             '(default: %(default)s)')

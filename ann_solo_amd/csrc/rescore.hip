@@ -20,6 +20,8 @@
 // Pass 2 (rescore_argmax_kernel): per query first-strict-maximum (cpp:118-129).
 // Pass 3 (rescore_matches_kernel): the winning pair is re-run once per query to
 // emit its peak_matches in greedy order.
+// Top-n (asl_*_topn, n_best > 0 in rescore_device): Pass 2 is rescore_topn_kernel, the n best slots
+// per query in one pass over the scores; Pass 3 rescore_matches_topn_kernel over nq * n winners.
 //
 // Arithmetic mirrors the reference: window tests in double on float->double
 // promoted m/z (cpp:42,53); product = (float)(mult * (double)q_int * (double)c_int)
@@ -1309,32 +1311,118 @@ __global__ __launch_bounds__(64) void rescore_argmax_kernel(
   }
 }
 
+// Top-n selection (asl_*_topn): the n best slots of a query instead of the single best, in the
+// argmax's order -- score descending, then the tie key ascending (tie_by_row as above), then the
+// slot position (only a row that a caller's list names twice under tie_by_row = 1 gets that far).
+// One wave per query, ONE pass over the list whatever n is: every lane keeps the best n of the
+// slots it reads, sorted, in an LDS array laid out [n][64] (lane-strided: a lane's entries sit in
+// its own banks); a slot is inserted only when it beats the lane's n-th, which after the first few
+// hundred slots is rare, so the pass costs the argmax's coalesced read of pair_score. Then the 64
+// sorted lane lists are merged: n rounds of a wave arg-max over the lanes' heads. Positions and
+// rows are kept as 32-bit values (positions relative to the list's first slot; lists and library
+// rows are 32-bit everywhere in the callers). Dynamic LDS: n * 64 * 16 bytes.
+// Outputs [nq, n]; ranks beyond the valid slots: slot -1, score 0.
+__global__ __launch_bounds__(64) void rescore_topn_kernel(
+    CandView cv, int nq, int n, const double *__restrict__ pair_score, int tie_by_row,
+    int32_t *__restrict__ best_cand, long long *__restrict__ best_slot,
+    double *__restrict__ best_score, int32_t *__restrict__ n_valid) {
+  extern __shared__ __attribute__((aligned(16))) double topn_lds[];      // (no static LDS in front of it)
+  double *S = topn_lds;                                      // [n][64] scores
+  int32_t *K = reinterpret_cast<int32_t *>(S + n * 64);      // [n][64] tie keys
+  int32_t *P = K + n * 64;                                   // [n][64] positions
+  const int q = blockIdx.x;
+  const int lane = threadIdx.x;
+  long long c0, c1;
+  cv.range(q, c0, c1);
+  int have = 0, cnt = 0;
+  double ts = -1.0;          // the lane's n-th entry once it holds n
+  int32_t tk = 0, tp = 0;
+  for (long long c = c0 + lane; c < c1; c += 64) {
+    const double s = pair_score[c];
+    if (s < 0.0) continue;
+    ++cnt;
+    if (have == n && s < ts) continue;
+    const int32_t pos = (int32_t)(c - c0);
+    const int32_t key = tie_by_row ? (int32_t)cv.row(q, c) : pos;
+    if (have == n && s == ts && !(key < tk || (key == tk && pos < tp))) continue;
+    int i = have < n ? have : n - 1;
+    while (i > 0) {
+      const double ps = S[(i - 1) * 64 + lane];
+      const int32_t pk = K[(i - 1) * 64 + lane], pp = P[(i - 1) * 64 + lane];
+      if (!(s > ps || (s == ps && (key < pk || (key == pk && pos < pp))))) break;
+      S[i * 64 + lane] = ps;
+      K[i * 64 + lane] = pk;
+      P[i * 64 + lane] = pp;
+      --i;
+    }
+    S[i * 64 + lane] = s;
+    K[i * 64 + lane] = key;
+    P[i * 64 + lane] = pos;
+    if (have < n) ++have;
+    if (have == n) {
+      ts = S[(n - 1) * 64 + lane];
+      tk = K[(n - 1) * 64 + lane];
+      tp = P[(n - 1) * 64 + lane];
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+  int head = 0;
+  for (int r = 0; r < n; ++r) {
+    const bool live = head < have;
+    const double ms = live ? S[head * 64 + lane] : -1.0;
+    const int32_t mk = live ? K[head * 64 + lane] : 0x7fffffff;
+    const int32_t mp = live ? P[head * 64 + lane] : 0x7fffffff;
+    double bs = ms;
+    int32_t bk = mk, bp = mp;
+    for (int off = 32; off > 0; off >>= 1) {
+      const double os = __shfl_xor(bs, off);
+      const int32_t ok = __shfl_xor(bk, off), op = __shfl_xor(bp, off);
+      if (os > bs || (os == bs && (ok < bk || (ok == bk && op < bp)))) {
+        bs = os;
+        bk = ok;
+        bp = op;
+      }
+    }
+    const bool any = bs >= 0.0;               // wave-uniform: positions are unique, the order is total
+    if (any && live && mp == bp) ++head;      // the lane that held the winner moves on
+    if (lane == 0) {
+      const size_t o = (size_t)q * n + r;
+      if (best_cand) best_cand[o] = any ? bp : -1;
+      if (best_slot) best_slot[o] = any ? c0 + bp : -1;
+      if (best_score) best_score[o] = any ? bs : 0.0;
+    }
+  }
+  if (lane == 0 && n_valid) n_valid[q] = cnt;
+}
+
 // One wave per query, and a wave is a chain of dependent memory round trips (winner's slot -> its
 // row -> its peaks) around little arithmetic: the kernel lives on the number of waves in flight,
 // i.e. on the LDS a wave needs. SMALL: structures for spectra of <= 128 peaks and <= 128
 // generated matches (4 KB per wave instead of 11: 32 waves per CU instead of 12); a query beyond
 // them is marked in m_defer and done by the full-size instantiation, which runs second and only
 // looks at marked queries.
+// `w` is the winner's index in best_slot and in the outputs: the query itself for the single-winner
+// kernels, q * n_best + rank for the top-n ones.
 constexpr int RS_SMALL_P = 128, RS_SMALL_M = 128;
 template <bool SMALL, class QL, class WL>
-__device__ __forceinline__ void matches_one(int q, int lane, QL &Qw, WL &Ww, int *s_cnt_w, const DevPeaks &Qs,
+__device__ __forceinline__ void matches_one(int q, int w, int lane, QL &Qw, WL &Ww, int *s_cnt_w, const DevPeaks &Qs,
                                             const DevPeaks &L, const CandView &cv,
                                             const long long *__restrict__ best_slot, double tol, int allow_shift,
                                             int32_t *__restrict__ pm_count, uint32_t *__restrict__ pm_pairs,
                                             int pm_stride, int32_t *__restrict__ best_row, int *status,
                                             int *__restrict__ m_defer) {
-  const long long slot = best_slot[q];
+  const long long slot = best_slot[w];
   const long long row = slot >= 0 ? cv.row(q, slot) : -1;
-  if (best_row && lane == 0) best_row[q] = (int32_t)row;
+  if (best_row && lane == 0) best_row[w] = (int32_t)row;
   if (row < 0) {
-    if (pm_count && lane == 0) pm_count[q] = 0;
+    if (pm_count && lane == 0) pm_count[w] = 0;
     if (pm_pairs)   // rows are fully defined: zero beyond the matches (callers may pass raw memory)
-      for (int t = lane; t < 2 * pm_stride; t += 64) pm_pairs[(size_t)q * pm_stride * 2 + t] = 0u;
+      for (int t = lane; t < 2 * pm_stride; t += 64) pm_pairs[(size_t)w * pm_stride * 2 + t] = 0u;
     return;
   }
   if (!pm_count && !pm_pairs) return;
   if (SMALL && Qs.offsets[q + 1] - Qs.offsets[q] > RS_SMALL_P) {
-    if (lane == 0) m_defer[q] = 1;
+    if (lane == 0) m_defer[w] = 1;
     return;
   }
   int qn;
@@ -1342,18 +1430,18 @@ __device__ __forceinline__ void matches_one(int q, int lane, QL &Qw, WL &Ww, int
   wave_sync();
   int cnt_tmp = 0;
   const double sc = dot_pair_wave<true, SMALL>(lane, Qw, qn, Qs.precursor_mz[q], L, (int)row, tol, allow_shift,
-                                               Ww, pm_pairs ? pm_pairs + (size_t)q * pm_stride * 2 : nullptr,
+                                               Ww, pm_pairs ? pm_pairs + (size_t)w * pm_stride * 2 : nullptr,
                                                pm_pairs ? pm_stride : 0, s_cnt_w, status);
   if (SMALL && sc < 0.0) {        // (wave-uniform) does not fit: the second launch does this query
-    if (lane == 0) m_defer[q] = 1;
+    if (lane == 0) m_defer[w] = 1;
     return;
   }
   wave_sync();
   cnt_tmp = *s_cnt_w;
-  if (pm_count && lane == 0) pm_count[q] = cnt_tmp;
+  if (pm_count && lane == 0) pm_count[w] = cnt_tmp;
   if (pm_pairs)
     for (int t = 2 * (cnt_tmp < pm_stride ? cnt_tmp : pm_stride) + lane; t < 2 * pm_stride; t += 64)
-      pm_pairs[(size_t)q * pm_stride * 2 + t] = 0u;
+      pm_pairs[(size_t)w * pm_stride * 2 + t] = 0u;
 }
 
 // SMALL: a wave per query. Full size: a wave per RS_MF_GROUP queries, which reads their flags at once
@@ -1376,7 +1464,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_matches_kernel(
     const int q = blockIdx.x * RS_WAVES + wave;
     if (q >= nq) return;
     if (lane == 0) m_defer[q] = 0;
-    matches_one<true>(q, lane, Q[wave], W[wave], &s_cnt[wave], Qs, L, cv, best_slot, tol, allow_shift, pm_count,
+    matches_one<true>(q, q, lane, Q[wave], W[wave], &s_cnt[wave], Qs, L, cv, best_slot, tol, allow_shift, pm_count,
                       pm_pairs, pm_stride, best_row, status, m_defer);
     return;
   }
@@ -1387,8 +1475,43 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_matches_kernel(
   while (todo) {          // wave-uniform
     const int l = __builtin_ctzll(todo);
     todo &= todo - 1ull;
-    matches_one<false>(base + l, lane, Q[wave], W[wave], &s_cnt[wave], Qs, L, cv, best_slot, tol, allow_shift,
+    matches_one<false>(base + l, base + l, lane, Q[wave], W[wave], &s_cnt[wave], Qs, L, cv, best_slot, tol, allow_shift,
                        pm_count, pm_pairs, pm_stride, best_row, status, m_defer);
+    wave_sync();
+  }
+}
+
+// The peak matches of n winners per query (asl_*_topn): the kernel above over nq * n winners,
+// winner w = q * n + rank (best_slot, m_defer and every output are [nq, n]); the same two launches.
+template <bool SMALL>
+__global__ __launch_bounds__(64 * RS_WAVES) void rescore_matches_topn_kernel(
+    DevPeaks Qs, DevPeaks L, CandView cv, int nq, int n, const long long *__restrict__ best_slot,
+    double tol, int allow_shift, int32_t *__restrict__ pm_count,
+    uint32_t *__restrict__ pm_pairs, int pm_stride, int32_t *__restrict__ best_row,
+    int *status, int *__restrict__ m_defer) {
+  typedef QueryLdsT<SMALL ? RS_SMALL_P : RS_MAXP> QL;
+  typedef WaveLdsT<SMALL ? RS_SMALL_P : RS_MAXP, SMALL ? RS_SMALL_M : RS_MCAP> WL;
+  __shared__ QL Q[RS_WAVES];
+  __shared__ WL W[RS_WAVES];
+  __shared__ int s_cnt[RS_WAVES];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long nw = (long long)nq * n;
+  if (SMALL) {
+    const long long w = (long long)blockIdx.x * RS_WAVES + wave;
+    if (w >= nw) return;
+    if (lane == 0) m_defer[w] = 0;
+    matches_one<true>((int)(w / n), (int)w, lane, Q[wave], W[wave], &s_cnt[wave], Qs, L, cv, best_slot, tol,
+                      allow_shift, pm_count, pm_pairs, pm_stride, best_row, status, m_defer);
+    return;
+  }
+  const long long base = ((long long)blockIdx.x * RS_WAVES + wave) * RS_MF_GROUP;
+  unsigned long long todo = __ballot(lane < RS_MF_GROUP && base + lane < nw && m_defer[base + lane] != 0);
+  while (todo) {          // wave-uniform
+    const int l = __builtin_ctzll(todo);
+    todo &= todo - 1ull;
+    const long long w = base + l;
+    matches_one<false>((int)(w / n), (int)w, lane, Q[wave], W[wave], &s_cnt[wave], Qs, L, cv, best_slot, tol,
+                       allow_shift, pm_count, pm_pairs, pm_stride, best_row, status, m_defer);
     wave_sync();
   }
 }
@@ -1402,10 +1525,11 @@ int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
                    int32_t *best_row, double *best_score, int32_t *n_valid,
                    int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride, int *status,
                    const PrecFilter &filter, bool clear_status, RescoreScratch *scratch,
-                   const int32_t *row_counts, const WindowRows *window, bool emit_matches) {
+                   const int32_t *row_counts, const WindowRows *window, bool emit_matches, int n_best) {
   const int nq = Q.n;
   if (nq == 0) return ASL_OK;
   if (!scratch) return fail(ASL_ERR_INVALID, "rescore: no scratch (internal)");
+  if (n_best < 0 || n_best > ASL_MAX_BEST) return fail(ASL_ERR_INVALID, "rescore: n_best (internal)");
   if (window && (!cand_offsets || rows64 || rows32 || !window->begin || !window->sorted_row ||
                  !filter.meta || !L.charge || !L.records))
     return fail(ASL_ERR_INVALID, "rescore: window lists need CSR offsets and packed rows (internal)");
@@ -1453,11 +1577,27 @@ int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
                          (const int *)q_defer.p, status, bs_group);
     }
     ASL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(rescore_argmax_kernel, dim3(nq), dim3(64), 0, stream(), cv, nq,
-                       pair_score, tie_by_row, best_cand, best_slot, best_score, n_valid);
+    if (n_best > 0)
+      hipLaunchKernelGGL(rescore_topn_kernel, dim3(nq), dim3(64), (size_t)n_best * 64 * 16, stream(), cv, nq,
+                         n_best, pair_score, tie_by_row, best_cand, best_slot, best_score, n_valid);
+    else
+      hipLaunchKernelGGL(rescore_argmax_kernel, dim3(nq), dim3(64), 0, stream(), cv, nq,
+                         pair_score, tie_by_row, best_cand, best_slot, best_score, n_valid);
     ASL_CHECK_LAUNCH();
   }
-  if (emit_matches) {
+  if (emit_matches && n_best > 0) {
+    ProfScope ps("rescore_matches");
+    const long long nw = (long long)nq * n_best;
+    ASL_TRY(m_defer.reserve((size_t)nw));
+    hipLaunchKernelGGL(rescore_matches_topn_kernel<true>, dim3((unsigned)cdiv(nw, RS_WAVES)),
+                       dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, n_best, best_slot, tol,
+                       allow_shift, pm_count, pm_pairs, pm_stride, best_row, status, m_defer.p);
+    ASL_CHECK_LAUNCH();
+    hipLaunchKernelGGL(rescore_matches_topn_kernel<false>, dim3((unsigned)cdiv(nw, RS_MF_GROUP * RS_WAVES)),
+                       dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, n_best, best_slot, tol,
+                       allow_shift, pm_count, pm_pairs, pm_stride, best_row, status, m_defer.p);
+    ASL_CHECK_LAUNCH();
+  } else if (emit_matches) {
     ProfScope ps("rescore_matches");
     ASL_TRY(m_defer.reserve((size_t)nq));
     hipLaunchKernelGGL(rescore_matches_kernel<true>, dim3((unsigned)cdiv(nq, RS_WAVES)),
@@ -1527,6 +1667,87 @@ int rescore_window_finish(int nq, const double *run_score, const int32_t *run_ro
   return ASL_OK;
 }
 
+// Top-n fold of a tile (asl_search_batch_topn): the tile's n best (slots, scores: rescore_topn_kernel,
+// sorted) and the running n best of the query (rows, scores, sorted, row -1 beyond the filled
+// ranks) are two sorted lists of at most n over disjoint rows, so merging them by (score
+// descending, row ascending) and keeping n is exact whatever the tile cuts were. One thread per
+// query, in place: a forward pass counts how many of each list survive, a backward pass writes them.
+__global__ __launch_bounds__(256) void window_merge_topn_kernel(
+    CandView cv, int nq, int n, const long long *__restrict__ best_slot, const double *__restrict__ best_score,
+    const int32_t *__restrict__ n_valid, double *__restrict__ run_score, int32_t *__restrict__ run_row,
+    int32_t *__restrict__ run_n) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  run_n[q] += n_valid[q];
+  const long long *ts = best_slot + (size_t)q * n;
+  const double *tsc = best_score + (size_t)q * n;
+  double *rs = run_score + (size_t)q * n;
+  int32_t *rr = run_row + (size_t)q * n;
+  int la = 0, lb = 0;
+  while (la < n && rr[la] >= 0) ++la;
+  while (lb < n && ts[lb] >= 0) ++lb;
+  if (lb == 0) return;
+  // a (running) before b (tile) when its score is higher, or equal with the lower row
+  auto a_first = [&](int ia, int ib) {
+    const double sa = rs[ia], sb = tsc[ib];
+    return sa > sb || (sa == sb && rr[ia] < (int32_t)cv.row(q, ts[ib]));
+  };
+  int na = 0, nb = 0;
+  while (na + nb < n && (na < la || nb < lb)) {
+    if (nb >= lb || (na < la && a_first(na, nb))) ++na; else ++nb;
+  }
+  for (int k = na + nb - 1; k >= 0; --k) {       // k >= na - 1: no unread running entry is overwritten
+    if (nb == 0) break;                          // the rest of the running list is in place
+    if (na > 0 && !a_first(na - 1, nb - 1)) {
+      --na;
+      rs[k] = rs[na];
+      rr[k] = rr[na];
+    } else {
+      --nb;
+      rs[k] = tsc[nb];
+      rr[k] = (int32_t)cv.row(q, ts[nb]);
+    }
+  }
+}
+
+// After the last tile and the n-candidate pass over the running lists (`rescored`: its best_score
+// [nq, n], the same order): every filled rank's rescored score must be the merged one.
+__global__ __launch_bounds__(256) void window_finish_topn_kernel(
+    int nq, int n, const double *__restrict__ run_score, const int32_t *__restrict__ run_row,
+    const int32_t *__restrict__ run_n, const double *__restrict__ rescored, double *__restrict__ best_score,
+    int32_t *__restrict__ n_cand, int *status) {
+  const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= (long long)nq * n) return;
+  const bool won = run_row[w] >= 0;
+  if (won && rescored[w] != run_score[w]) atomicOr(status, RS_STATUS_WINDOW);
+  if (best_score) best_score[w] = won ? run_score[w] : 0.0;
+  if (n_cand && w % n == 0) n_cand[w / n] = run_n[w / n];
+}
+
+int rescore_window_merge_topn(const WindowRows &window, const int32_t *cand_offsets, int nq, int n,
+                              const long long *best_slot, const double *best_score, const int32_t *n_valid,
+                              double *run_score, int32_t *run_row, int32_t *run_n) {
+  if (nq <= 0) return ASL_OK;
+  CandView cv{nullptr, nullptr, cand_offsets, 0, PrecFilter()};
+  cv.win_begin = window.begin;
+  cv.win_rows = window.sorted_row;
+  cv.win_valid = window.valid;
+  hipLaunchKernelGGL(window_merge_topn_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(), cv, nq, n,
+                     best_slot, best_score, n_valid, run_score, run_row, run_n);
+  ASL_CHECK_LAUNCH();
+  return ASL_OK;
+}
+
+int rescore_window_finish_topn(int nq, int n, const double *run_score, const int32_t *run_row,
+                               const int32_t *run_n, const double *rescored, double *best_score,
+                               int32_t *n_cand, int *status) {
+  if (nq <= 0) return ASL_OK;
+  hipLaunchKernelGGL(window_finish_topn_kernel, dim3((unsigned)cdiv((long long)nq * n, 256)), dim3(256), 0,
+                     stream(), nq, n, run_score, run_row, run_n, rescored, best_score, n_cand, status);
+  ASL_CHECK_LAUNCH();
+  return ASL_OK;
+}
+
 int rescore_status_error(int st) {
   if (st & RS_STATUS_PEAKS)
     return fail(ASL_ERR_CAPACITY, "rescore: a spectrum has more than %d peaks", RS_MAXP);
@@ -1548,14 +1769,14 @@ int rescore_check_status(const int *status_dev) {
 
 using namespace asl;
 
-extern "C" int asl_rescore_batch(const asl_peaks_t *queries, const asl_peaks_t *library,
-                                 const int64_t *cand_rows, const int32_t *cand_offsets,
-                                 double tol, int allow_shift, int32_t *best_cand,
-                                 double *best_score, int32_t *pm_count, uint32_t *pm_pairs,
-                                 int32_t pm_stride) {
-  clear_error();
+// asl_rescore_batch (n_best = 0) and asl_rescore_batch_topn (outputs [nq, n_best])
+static int rescore_batch_sync(const asl_peaks_t *queries, const asl_peaks_t *library,
+                              const int64_t *cand_rows, const int32_t *cand_offsets, double tol,
+                              int allow_shift, int n_best, int32_t *best_cand, double *best_score,
+                              int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride) {
   if (!queries || !library) return fail(ASL_ERR_INVALID, "rescore_batch: null spectra");
   const int nq = queries->n;
+  const size_t nw = (size_t)nq * (size_t)std::max(n_best, 1);
   if (nq == 0) return ASL_OK;
   if (!cand_offsets) return fail(ASL_ERR_INVALID, "rescore_batch: null cand_offsets");
   if (pm_pairs && pm_stride <= 0) return fail(ASL_ERR_INVALID, "rescore_batch: pm_stride");
@@ -1580,23 +1801,47 @@ extern "C" int asl_rescore_batch(const asl_peaks_t *queries, const asl_peaks_t *
   Out<int32_t> o_best, o_cnt;
   Out<double> o_score;
   Out<uint32_t> o_pairs;
-  ASL_TRY(o_best.init(best_cand, nq));
-  ASL_TRY(o_score.init(best_score, nq));
-  ASL_TRY(o_cnt.init(pm_count, nq));
-  ASL_TRY(o_pairs.init(pm_pairs, (size_t)nq * (pm_pairs ? pm_stride : 0) * 2));
+  ASL_TRY(o_best.init(best_cand, nw));
+  ASL_TRY(o_score.init(best_score, nw));
+  ASL_TRY(o_cnt.init(pm_count, nw));
+  ASL_TRY(o_pairs.init(pm_pairs, nw * (pm_pairs ? pm_stride : 0) * 2));
   DevBuf<double> pair_score;
   DevBuf<long long> best_slot;
   DevBuf<int> status;
   ASL_TRY(pair_score.reserve((size_t)std::max(total, 1)));
-  ASL_TRY(best_slot.reserve(nq));
+  ASL_TRY(best_slot.reserve(nw));
   ASL_TRY(status.reserve(1));
   RescoreScratch scratch;      // lives until rescore_check_status below has synchronised
   ASL_TRY(rescore_device(Q.dev, L.dev, rows.d, nullptr, off.d, 0, total, tol, allow_shift, 0,
                          pair_score.p, best_slot.p, o_best.d, nullptr, o_score.d, nullptr,
-                         o_cnt.d, o_pairs.d, pm_stride, status.p, PrecFilter(), true, &scratch));
+                         o_cnt.d, o_pairs.d, pm_stride, status.p, PrecFilter(), true, &scratch,
+                         nullptr, nullptr, true, n_best));
   ASL_TRY(o_best.finish());
   ASL_TRY(o_score.finish());
   ASL_TRY(o_cnt.finish());
   ASL_TRY(o_pairs.finish());
   return rescore_check_status(status.p);  // synchronises
+}
+
+extern "C" int asl_rescore_batch(const asl_peaks_t *queries, const asl_peaks_t *library,
+                                 const int64_t *cand_rows, const int32_t *cand_offsets,
+                                 double tol, int allow_shift, int32_t *best_cand,
+                                 double *best_score, int32_t *pm_count, uint32_t *pm_pairs,
+                                 int32_t pm_stride) {
+  clear_error();
+  return rescore_batch_sync(queries, library, cand_rows, cand_offsets, tol, allow_shift, 0, best_cand,
+                            best_score, pm_count, pm_pairs, pm_stride);
+}
+
+extern "C" int asl_rescore_batch_topn(const asl_peaks_t *queries, const asl_peaks_t *library,
+                                      const int64_t *cand_rows, const int32_t *cand_offsets,
+                                      double tol, int allow_shift, int32_t n_best, int32_t *best_cand,
+                                      double *best_score, int32_t *pm_count, uint32_t *pm_pairs,
+                                      int32_t pm_stride) {
+  clear_error();
+  if (n_best < 1 || n_best > ASL_MAX_BEST)
+    return fail(ASL_ERR_INVALID, "rescore_batch_topn: n_best must be in [1, %d]", ASL_MAX_BEST);
+  ASL_TRY(ensure_device());     // (no device: ASL_ERR_NO_DEVICE whatever else was passed)
+  return rescore_batch_sync(queries, library, cand_rows, cand_offsets, tol, allow_shift, n_best, best_cand,
+                            best_score, pm_count, pm_pairs, pm_stride);
 }

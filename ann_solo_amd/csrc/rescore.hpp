@@ -91,7 +91,12 @@ int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
                    // filter's packed row records and annotated library peaks required)
                    const WindowRows *window = nullptr,
                    // false: stop after the argmax (no best_row, pm_count, pm_pairs written)
-                   bool emit_matches = true);
+                   bool emit_matches = true,
+                   // 0: the single winner. 1..ASL_MAX_BEST (asl_*_topn): the n best slots per query
+                   // (rescore_topn_kernel instead of the argmax, the matches kernels over nq * n
+                   // winners); best_slot / best_cand / best_row / best_score / pm_count are then
+                   // [nq, n_best], pm_pairs [nq, n_best, pm_stride, 2], n_valid stays [nq]
+                   int n_best = 0);
 // Tiled window search: folds one tile's argmax (rescore_device's best_slot / best_score / n_valid
 // over the tile's nq queries, slots of the same window lists) into the running best of those
 // queries: a higher score wins, equal scores go to the lower library row, counts add up.
@@ -105,6 +110,15 @@ int rescore_window_merge(const WindowRows &window, const int32_t *cand_offsets, 
 int rescore_window_finish(int nq, const double *run_score, const int32_t *run_row,
                           const int32_t *run_n, const double *rescored, double *best_score,
                           int32_t *n_cand, int *status);
+// The same fold and finish for the n best (asl_search_batch_topn): the tile's best_slot / best_score
+// and the running run_score / run_row are [nq, n], sorted by (score descending, row ascending),
+// run_row -1 beyond the filled ranks; `rescored` is [nq, n].
+int rescore_window_merge_topn(const WindowRows &window, const int32_t *cand_offsets, int nq, int n,
+                              const long long *best_slot, const double *best_score, const int32_t *n_valid,
+                              double *run_score, int32_t *run_row, int32_t *run_n);
+int rescore_window_finish_topn(int nq, int n, const double *run_score, const int32_t *run_row,
+                               const int32_t *run_n, const double *rescored, double *best_score,
+                               int32_t *n_cand, int *status);
 int rescore_check_status(const int *status_dev);   // reads the flags back: synchronises
 int rescore_status_error(int status_bits);         // ASL_OK or the error the flags stand for
 

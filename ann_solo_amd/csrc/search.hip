@@ -355,10 +355,14 @@ static int window_candidates_device(asl_library *L, int nq, const double *q_pmz_
 // pairs fit): the rescoring as for any list. Several: each tile's argmax is folded into a running
 // best (rescore_window_merge), then one pass over a one-candidate list per query -- its winner --
 // emits the peak matches. Scratch: pair scores of one tile, 12 bytes per query.
+// n_best > 0 (asl_search_batch_topn): the same tiles with the n best per query -- outputs [nq, n_best],
+// each tile's top-n folded into a running top-n (rescore_window_merge_topn), the final pass over an
+// n-candidate list per query. n_best = 0 is the single-winner search, launch for launch.
 static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_search_params_t *P,
                                 int32_t *best_row, double *best_score, int32_t *n_cand,
-                                int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride) {
+                                int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride, int n_best = 0) {
   const int nq = Q.n;
+  const size_t nw = (size_t)nq * (size_t)std::max(n_best, 1);     // winners of the batch
   std::vector<int32_t> h_lo((size_t)nq), h_cnt((size_t)nq);
   {
     ProfScope ps("filter");
@@ -377,11 +381,11 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
   const int64_t total = pre[(size_t)nq];
   if (total == 0) {   // what the rescoring writes for empty lists
     HIP_TRY(hipMemsetAsync(L->status.p, 0, sizeof(int), stream()));
-    if (best_row) HIP_TRY(hipMemsetAsync(best_row, 0xff, (size_t)nq * 4, stream()));
-    if (best_score) HIP_TRY(hipMemsetAsync(best_score, 0, (size_t)nq * 8, stream()));
+    if (best_row) HIP_TRY(hipMemsetAsync(best_row, 0xff, nw * 4, stream()));
+    if (best_score) HIP_TRY(hipMemsetAsync(best_score, 0, nw * 8, stream()));
     if (n_cand) HIP_TRY(hipMemsetAsync(n_cand, 0, (size_t)nq * 4, stream()));
-    if (pm_count) HIP_TRY(hipMemsetAsync(pm_count, 0, (size_t)nq * 4, stream()));
-    if (pm_pairs) HIP_TRY(hipMemsetAsync(pm_pairs, 0, (size_t)nq * pm_stride * 8, stream()));
+    if (pm_count) HIP_TRY(hipMemsetAsync(pm_count, 0, nw * 4, stream()));
+    if (pm_pairs) HIP_TRY(hipMemsetAsync(pm_pairs, 0, nw * pm_stride * 8, stream()));
     return ASL_OK;
   }
   const int64_t B = std::min<int64_t>(window_pair_budget(), 0x7fffffffLL);
@@ -393,10 +397,10 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
   win.sorted_row = L->sorted_row.p;
   win.valid = L->has_valid ? L->valid.p : nullptr;
   // every buffer before the first launch (growing one synchronises the device)
-  // (the winners' pass after several tiles scores one slot per query)
-  ASL_TRY(L->pair_score.reserve((size_t)(total <= B ? total : std::max<int64_t>(B, nq))));
+  // (the winners' pass after several tiles scores one slot per winner)
+  ASL_TRY(L->pair_score.reserve((size_t)(total <= B ? total : std::max<int64_t>(B, (int64_t)nw))));
   ASL_TRY(L->rs_scratch.q_defer.reserve((size_t)nq));
-  ASL_TRY(L->rs_scratch.m_defer.reserve((size_t)nq));
+  ASL_TRY(L->rs_scratch.m_defer.reserve(nw));
   if (total <= B) {   // one tile: the whole batch
     std::vector<int32_t> h((size_t)2 * nq + 1);
     for (int q = 0; q <= nq; q++) h[(size_t)q] = (int32_t)pre[(size_t)q];
@@ -406,7 +410,7 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
     return rescore_device(Q, L->dev, nullptr, nullptr, L->wtile.p, 0, total, P->fragment_mz_tolerance,
                           P->allow_shift, 1, L->pair_score.p, L->best_slot.p, nullptr, best_row,
                           best_score, n_cand, pm_count, pm_pairs, pm_stride, L->status.p, rows_only,
-                          true, &L->rs_scratch, nullptr, &win, true);
+                          true, &L->rs_scratch, nullptr, &win, true, n_best);
   }
   // tiles [t0, t1) of the global pair range; queries qa..qb (the query of pair t0 .. that of t1-1)
   struct Tile {
@@ -433,13 +437,13 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
     tiles.push_back(T);
   }
   ASL_TRY(L->wtile.upload(h.data(), h.size()));
-  ASL_TRY(L->run_score.reserve((size_t)nq));
-  ASL_TRY(L->run_row.reserve((size_t)nq));
+  ASL_TRY(L->run_score.reserve(nw));
+  ASL_TRY(L->run_row.reserve(nw));
   ASL_TRY(L->run_n.reserve((size_t)nq));
-  ASL_TRY(L->tile_score.reserve((size_t)nq));
+  ASL_TRY(L->tile_score.reserve(nw));
   ASL_TRY(L->tile_n.reserve((size_t)nq));
-  HIP_TRY(hipMemsetAsync(L->run_score.p, 0, (size_t)nq * 8, stream()));
-  HIP_TRY(hipMemsetAsync(L->run_row.p, 0xff, (size_t)nq * 4, stream()));
+  HIP_TRY(hipMemsetAsync(L->run_score.p, 0, nw * 8, stream()));
+  HIP_TRY(hipMemsetAsync(L->run_row.p, 0xff, nw * 4, stream()));
   HIP_TRY(hipMemsetAsync(L->run_n.p, 0, (size_t)nq * 4, stream()));
   HIP_TRY(hipMemsetAsync(L->status.p, 0, sizeof(int), stream()));
   for (const Tile &T : tiles) {
@@ -453,9 +457,24 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
     ASL_TRY(rescore_device(Qt, L->dev, nullptr, nullptr, off, 0, T.pairs, P->fragment_mz_tolerance,
                            P->allow_shift, 1, L->pair_score.p, L->best_slot.p, nullptr, nullptr,
                            L->tile_score.p, L->tile_n.p, nullptr, nullptr, pm_stride, L->status.p,
-                           rows_only, false, &L->rs_scratch, nullptr, &win, false));
-    ASL_TRY(rescore_window_merge(win, off, T.nq, L->best_slot.p, L->tile_score.p, L->tile_n.p,
-                                 L->run_score.p + T.qa, L->run_row.p + T.qa, L->run_n.p + T.qa));
+                           rows_only, false, &L->rs_scratch, nullptr, &win, false, n_best));
+    if (n_best > 0)
+      ASL_TRY(rescore_window_merge_topn(win, off, T.nq, n_best, L->best_slot.p, L->tile_score.p, L->tile_n.p,
+                                        L->run_score.p + (size_t)T.qa * n_best,
+                                        L->run_row.p + (size_t)T.qa * n_best, L->run_n.p + T.qa));
+    else
+      ASL_TRY(rescore_window_merge(win, off, T.nq, L->best_slot.p, L->tile_score.p, L->tile_n.p,
+                                   L->run_score.p + T.qa, L->run_row.p + T.qa, L->run_n.p + T.qa));
+  }
+  if (n_best > 0) {
+    // the running lists once more, as an n-candidate list per query (-1: an empty rank): the same
+    // order comes out again, with rows and peak matches
+    ASL_TRY(rescore_device(Q, L->dev, nullptr, L->run_row.p, nullptr, n_best, (int64_t)nw,
+                           P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p, L->best_slot.p,
+                           nullptr, best_row, L->tile_score.p, nullptr, pm_count, pm_pairs, pm_stride,
+                           L->status.p, rows_only, false, &L->rs_scratch, nullptr, nullptr, true, n_best));
+    return rescore_window_finish_topn(nq, n_best, L->run_score.p, L->run_row.p, L->run_n.p, L->tile_score.p,
+                                      best_score, n_cand, L->status.p);
   }
   // the winners once more, as a one-candidate list per query (-1: none): rows and peak matches
   ASL_TRY(rescore_device(Q, L->dev, nullptr, L->run_row.p, nullptr, 1, nq, P->fragment_mz_tolerance,
@@ -499,12 +518,13 @@ int asl_window_candidates(asl_library_t *L, int32_t nq, const double *query_pmz,
   return ASL_OK;
 }
 
-int asl_rescore_knn(asl_library_t *L, const asl_peaks_t *queries, const asl_search_params_t *P,
-                    const int64_t *knn_I, int32_t *best_row, double *best_score,
-                    int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride) {
-  clear_error();
+// asl_rescore_knn (n_best = 0) and asl_rescore_knn_topn (outputs [nq, n_best] except n_cand)
+static int rescore_knn_sync(asl_library_t *L, const asl_peaks_t *queries, const asl_search_params_t *P,
+                            const int64_t *knn_I, int n_best, int32_t *best_row, double *best_score,
+                            int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride) {
   if (!L || !queries || !P || !knn_I) return fail(ASL_ERR_INVALID, "rescore_knn: null argument");
   const int nq = queries->n, k = P->k;
+  const size_t nw = (size_t)nq * (size_t)std::max(n_best, 1);
   if (nq == 0) return ASL_OK;
   if (k <= 0) return fail(ASL_ERR_INVALID, "rescore_knn: k must be positive");
   if (pm_pairs && pm_stride <= 0) return fail(ASL_ERR_INVALID, "rescore_knn: pm_stride");
@@ -516,12 +536,12 @@ int asl_rescore_knn(asl_library_t *L, const asl_peaks_t *queries, const asl_sear
   Out<int32_t> o_row, o_ncand, o_cnt;
   Out<double> o_score;
   Out<uint32_t> o_pairs;
-  ASL_TRY(o_row.init(best_row, nq));
-  ASL_TRY(o_score.init(best_score, nq));
+  ASL_TRY(o_row.init(best_row, nw));
+  ASL_TRY(o_score.init(best_score, nw));
   ASL_TRY(o_ncand.init(n_cand, nq));
-  ASL_TRY(o_cnt.init(pm_count, nq));
-  ASL_TRY(o_pairs.init(pm_pairs, (size_t)nq * (pm_pairs ? pm_stride : 0) * 2));
-  ASL_TRY(L->best_slot.reserve((size_t)nq));
+  ASL_TRY(o_cnt.init(pm_count, nw));
+  ASL_TRY(o_pairs.init(pm_pairs, nw * (pm_pairs ? pm_stride : 0) * 2));
+  ASL_TRY(L->best_slot.reserve(nw));
   ASL_TRY(L->status.reserve(1));
   ASL_TRY(L->pair_score.reserve((size_t)nq * k));
   // the precursor filter runs inside the rescoring kernel's compaction stage
@@ -530,13 +550,96 @@ int asl_rescore_knn(asl_library_t *L, const asl_peaks_t *queries, const asl_sear
   ASL_TRY(rescore_device(Q.dev, L->dev, knn.d, nullptr, nullptr, k, (int64_t)nq * k,
                          P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p,
                          L->best_slot.p, nullptr, o_row.d, o_score.d, o_ncand.d, o_cnt.d,
-                         o_pairs.d, pm_stride, L->status.p, flt, true, &L->rs_scratch));
+                         o_pairs.d, pm_stride, L->status.p, flt, true, &L->rs_scratch, nullptr, nullptr,
+                         true, n_best));
   ASL_TRY(o_row.finish());
   ASL_TRY(o_score.finish());
   ASL_TRY(o_ncand.finish());
   ASL_TRY(o_cnt.finish());
   ASL_TRY(o_pairs.finish());
   return rescore_check_status(L->status.p);
+}
+
+int asl_rescore_knn(asl_library_t *L, const asl_peaks_t *queries, const asl_search_params_t *P,
+                    const int64_t *knn_I, int32_t *best_row, double *best_score,
+                    int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride) {
+  clear_error();
+  return rescore_knn_sync(L, queries, P, knn_I, 0, best_row, best_score, n_cand, pm_count, pm_pairs, pm_stride);
+}
+
+int asl_rescore_knn_topn(asl_library_t *L, const asl_peaks_t *queries, const asl_search_params_t *P,
+                         const int64_t *knn_I, int32_t n_best, int32_t *best_row, double *best_score,
+                         int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride) {
+  clear_error();
+  if (n_best < 1 || n_best > ASL_MAX_BEST)
+    return fail(ASL_ERR_INVALID, "rescore_knn_topn: n_best must be in [1, %d]", ASL_MAX_BEST);
+  ASL_TRY(ensure_device());     // (no device: ASL_ERR_NO_DEVICE whatever else was passed)
+  return rescore_knn_sync(L, queries, P, knn_I, n_best, best_row, best_score, n_cand, pm_count, pm_pairs,
+                          pm_stride);
+}
+
+// The synchronous batch: asl_search_batch outside pipeline mode (n_best = 0, the single winner) and
+// asl_search_batch_topn (outputs [nq, n_best] except n_cand and knn_I). The arguments are checked.
+static int search_batch_sync(asl_library_t *L, asl_index_t *idx, const asl_peaks_t *queries,
+                             const asl_search_params_t *P, int n_best, int32_t *best_row, double *best_score,
+                             int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride,
+                             int64_t *knn_I) {
+  const int nq = queries->n;
+  const size_t nw = (size_t)nq * (size_t)std::max(n_best, 1);
+  ASL_TRY(ensure_device());
+  PeaksStage Q;
+  ASL_TRY(Q.init(queries));
+  Out<int32_t> o_row, o_ncand, o_cnt;
+  Out<double> o_score;
+  Out<uint32_t> o_pairs;
+  Out<int64_t> o_knn;
+  ASL_TRY(o_row.init(best_row, nw));
+  ASL_TRY(o_score.init(best_score, nw));
+  ASL_TRY(o_ncand.init(n_cand, nq));
+  ASL_TRY(o_cnt.init(pm_count, nw));
+  ASL_TRY(o_pairs.init(pm_pairs, nw * (pm_pairs ? pm_stride : 0) * 2));
+  ASL_TRY(L->best_slot.reserve(nw));
+  ASL_TRY(L->status.reserve(1));
+  if (P->use_ann) {
+    const int d = idx->d, k = P->k;
+    if (k <= 0) return fail(ASL_ERR_INVALID, "search_batch: k must be positive");
+    ASL_TRY(o_knn.init(knn_I, (size_t)nq * k));
+    ASL_TRY(L->qvec.reserve((size_t)nq * d));
+    ASL_TRY(L->knn.reserve((size_t)nq * k));
+    ASL_TRY(L->pair_score.reserve((size_t)nq * k));
+    const bool win = idx->window_scan != 0;
+    if (win) ASL_TRY(index_window_prepare(idx, L->serial, L->wcol.p, L->n, nq, P->nprobe));
+    ASL_TRY(encode_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
+                          d, P->hash_seed, 1, L->qvec.p));
+    // the candidates are consumed as a set (filter + best match): no final sort unless the
+    // caller asked for the ordered neighbour list
+    ASL_TRY(L->rows_len.reserve((size_t)nq));
+    IndexSearch rq{.nq = nq, .xq = L->qvec.p, .k = k, .nprobe = P->nprobe, .I64 = o_knn.d, .I32 = L->knn.p,
+                   .rows = knn_I == nullptr ? ROWS_SET : ROWS_ORDERED};
+    IndexWindow w;
+    IndexPostFilter pf;
+    if (win) offer_window(rq, w, Q.dev, P, knn_I == nullptr ? L->rows_len.p : nullptr);
+    else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(rq, pf, L, Q.dev, P, L->rows_len.p);
+    ASL_TRY(index_search_device(idx, rq));
+    const bool rows_filtered = rq.rows_filtered;
+    PrecFilter flt;
+    batch_filter(L, P, flt);
+    ASL_TRY(rescore_device(Q.dev, L->dev, nullptr, L->knn.p, nullptr, k, (int64_t)nq * k,
+                           P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p,
+                           L->best_slot.p, nullptr, o_row.d, o_score.d, o_ncand.d, o_cnt.d,
+                           o_pairs.d, pm_stride, L->status.p, flt, true, &L->rs_scratch,
+                           rows_filtered ? L->rows_len.p : nullptr, nullptr, true, n_best));
+  } else {
+    ASL_TRY(window_search_device(L, Q.dev, P, o_row.d, o_score.d, o_ncand.d, o_cnt.d, o_pairs.d,
+                                 pm_stride, n_best));
+  }
+  ASL_TRY(o_row.finish());
+  ASL_TRY(o_score.finish());
+  ASL_TRY(o_ncand.finish());
+  ASL_TRY(o_cnt.finish());
+  ASL_TRY(o_pairs.finish());
+  ASL_TRY(o_knn.finish());
+  return rescore_check_status(L->status.p);  // synchronises the stream
 }
 
 // asl_search_batch in pipeline mode (asl_set_pipeline): nothing here waits for the device.
@@ -669,60 +772,27 @@ int asl_search_batch(asl_library_t *L, asl_index_t *idx, const asl_peaks_t *quer
                                     pm_pairs, pm_stride, knn_I);
     }
   }
+  return search_batch_sync(L, idx, queries, P, 0, best_row, best_score, n_cand, pm_count, pm_pairs, pm_stride,
+                           knn_I);
+}
+
+int asl_search_batch_topn(asl_library_t *L, asl_index_t *idx, const asl_peaks_t *queries,
+                          const asl_search_params_t *P, int32_t n_best, int32_t *best_row, double *best_score,
+                          int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride,
+                          int64_t *knn_I) {
+  clear_error();
+  if (n_best < 1 || n_best > ASL_MAX_BEST)
+    return fail(ASL_ERR_INVALID, "search_batch_topn: n_best must be in [1, %d]", ASL_MAX_BEST);
+  // (no device: ASL_ERR_NO_DEVICE whatever else was passed.) Never pipelined: this waits for the
+  // batches of asl_set_pipeline in flight
   ASL_TRY(ensure_device());
-  PeaksStage Q;
-  ASL_TRY(Q.init(queries));
-  Out<int32_t> o_row, o_ncand, o_cnt;
-  Out<double> o_score;
-  Out<uint32_t> o_pairs;
-  Out<int64_t> o_knn;
-  ASL_TRY(o_row.init(best_row, nq));
-  ASL_TRY(o_score.init(best_score, nq));
-  ASL_TRY(o_ncand.init(n_cand, nq));
-  ASL_TRY(o_cnt.init(pm_count, nq));
-  ASL_TRY(o_pairs.init(pm_pairs, (size_t)nq * (pm_pairs ? pm_stride : 0) * 2));
-  ASL_TRY(L->best_slot.reserve((size_t)nq));
-  ASL_TRY(L->status.reserve(1));
-  if (P->use_ann) {
-    const int d = idx->d, k = P->k;
-    if (k <= 0) return fail(ASL_ERR_INVALID, "search_batch: k must be positive");
-    ASL_TRY(o_knn.init(knn_I, (size_t)nq * k));
-    ASL_TRY(L->qvec.reserve((size_t)nq * d));
-    ASL_TRY(L->knn.reserve((size_t)nq * k));
-    ASL_TRY(L->pair_score.reserve((size_t)nq * k));
-    const bool win = idx->window_scan != 0;
-    if (win) ASL_TRY(index_window_prepare(idx, L->serial, L->wcol.p, L->n, nq, P->nprobe));
-    ASL_TRY(encode_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
-                          d, P->hash_seed, 1, L->qvec.p));
-    // the candidates are consumed as a set (filter + best match): no final sort unless the
-    // caller asked for the ordered neighbour list
-    ASL_TRY(L->rows_len.reserve((size_t)nq));
-    IndexSearch rq{.nq = nq, .xq = L->qvec.p, .k = k, .nprobe = P->nprobe, .I64 = o_knn.d, .I32 = L->knn.p,
-                   .rows = knn_I == nullptr ? ROWS_SET : ROWS_ORDERED};
-    IndexWindow w;
-    IndexPostFilter pf;
-    if (win) offer_window(rq, w, Q.dev, P, knn_I == nullptr ? L->rows_len.p : nullptr);
-    else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(rq, pf, L, Q.dev, P, L->rows_len.p);
-    ASL_TRY(index_search_device(idx, rq));
-    const bool rows_filtered = rq.rows_filtered;
-    PrecFilter flt;
-    batch_filter(L, P, flt);
-    ASL_TRY(rescore_device(Q.dev, L->dev, nullptr, L->knn.p, nullptr, k, (int64_t)nq * k,
-                           P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p,
-                           L->best_slot.p, nullptr, o_row.d, o_score.d, o_ncand.d, o_cnt.d,
-                           o_pairs.d, pm_stride, L->status.p, flt, true, &L->rs_scratch,
-                           rows_filtered ? L->rows_len.p : nullptr));
-  } else {
-    ASL_TRY(window_search_device(L, Q.dev, P, o_row.d, o_score.d, o_ncand.d, o_cnt.d, o_pairs.d,
-                                 pm_stride));
-  }
-  ASL_TRY(o_row.finish());
-  ASL_TRY(o_score.finish());
-  ASL_TRY(o_ncand.finish());
-  ASL_TRY(o_cnt.finish());
-  ASL_TRY(o_pairs.finish());
-  ASL_TRY(o_knn.finish());
-  return rescore_check_status(L->status.p);  // synchronises the stream
+  if (!L || !queries || !P) return fail(ASL_ERR_INVALID, "search_batch_topn: null argument");
+  if (queries->n == 0) return ASL_OK;
+  if (pm_pairs && pm_stride <= 0) return fail(ASL_ERR_INVALID, "search_batch_topn: pm_stride");
+  if (P->use_ann && !idx) return fail(ASL_ERR_INVALID, "search_batch_topn: use_ann needs an index");
+  if (P->use_ann && P->k <= 0) return fail(ASL_ERR_INVALID, "search_batch_topn: k must be positive");
+  return search_batch_sync(L, idx, queries, P, n_best, best_row, best_score, n_cand, pm_count, pm_pairs,
+                           pm_stride, knn_I);
 }
 
 }  // extern "C"

@@ -60,6 +60,28 @@ class BatchResult:
         return self.pm_pairs[i, :self.pm_count[i]].astype(np.int64)
 
 
+@dataclass
+class TopnBatchResult:
+    """Per-query outputs of one top-n batch: the ``n_best`` best library matches of every query,
+    best first (score descending, equal scores to the lower library row). Numpy arrays or device
+    tensors; ranks beyond a query's candidates hold row -1, score 0.0, count 0."""
+    best_row: np.ndarray            # [nq, n_best] rows inside the charge partition
+    best_score: np.ndarray          # [nq, n_best] shifted-dot scores
+    n_candidates: np.ndarray        # [nq]
+    pm_count: np.ndarray            # [nq, n_best]
+    pm_pairs: np.ndarray            # [nq, n_best, stride, 2]
+    knn: Optional[np.ndarray] = None
+
+    def peak_matches(self, i, r=0) -> np.ndarray:
+        return _to_np(self.pm_pairs[i, r, :int(self.pm_count[i, r])]).astype(np.int64)
+
+    def rank0(self) -> 'BatchResult':
+        """The best matches alone, as the single-winner batch returns them (same values)."""
+        c = (lambda a: a.contiguous()) if hasattr(self.best_row, 'contiguous') else np.ascontiguousarray
+        return BatchResult(c(self.best_row[:, 0]), c(self.best_score[:, 0]), self.n_candidates,
+                           c(self.pm_count[:, 0]), c(self.pm_pairs[:, 0]), self.knn)
+
+
 INDEX_EXT = '.idxmi'      # own container; the reference's FAISS files keep '.idxann' untouched
 
 
@@ -483,6 +505,50 @@ class SpectralLibrary:
             self._hold(q, best_row, best_score, n_cand, pm_count, pm_pairs, knn)
         return BatchResult(best_row, best_score, n_cand, pm_count, pm_pairs, knn)
 
+    def search_batch_topn(self, queries: PackedSpectra, charge: int, mode: str, n_best: int,
+                          want_knn: bool = False, device_out: bool = False,
+                          pm_stride: Optional[int] = None) -> Optional[TopnBatchResult]:
+        """``_search_batch_local`` for the ``n_best`` (1 .. 16) best library matches of every query
+        (``asl_search_batch_topn``): every cascade level and index mode, on this GPU alone.
+        Synchronous -- the call never joins the two-stream pipeline. Rank 0 (and ``n_candidates``,
+        ``knn``) is what ``_search_batch_local`` returns, bit for bit."""
+        d = getattr(self, '_dist', None)
+        if d is not None and d.world > 1:
+            raise ValueError('search_batch_topn does not run on a sharded index')
+        tol_val, tol_mode = self._tolerance(mode)
+        if tol_mode not in ('Da', 'ppm'):
+            raise ValueError('Unknown precursor tolerance mode')
+        if charge not in self.partitions:
+            return None
+        cfg = self.config
+        part = self.partitions[charge]
+        use_ann = self._uses_ann(charge, mode)
+        idx = self._get_ann_index(charge) if use_ann else None
+        q = queries.to(self.device).contiguous()
+        nq, n = q.n, int(n_best)
+        k = self._num_candidates
+        stride = pm_stride or q.max_peaks()
+        xp = torch if device_out else np
+        mk = (lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)) if device_out else \
+             (lambda shape, dt: np.empty(shape, dt))
+        shape = (nq, max(n, 0))
+        best_row = mk(shape, xp.int32)
+        best_score = mk(shape, xp.float64)
+        n_cand = mk((nq,), xp.int32)
+        pm_count = mk(shape, xp.int32)
+        pm_pairs = mk(shape + (stride, 2), torch.int32 if device_out else np.uint32)
+        knn = mk((nq, k), xp.int64) if (want_knn and use_ann) else None
+        _, min_bound, _ = get_dim(cfg.min_mz, cfg.max_mz, cfg.bin_size)
+        P = _lib.AslSearchParams(min_bound, cfg.bin_size, HASH_SEED, k, self._num_probe, charge,
+                                 float(tol_val), 0 if tol_mode == 'Da' else 1,
+                                 cfg.fragment_mz_tolerance, int(cfg.allow_peak_shifts),
+                                 int(use_ann))
+        _lib.check(_lib.lib().asl_search_batch_topn(
+            part.handle, idx._h if idx is not None else None, C.byref(_lib.peaks_struct(q)),
+            C.byref(P), n, _lib.ptr(best_row), _lib.ptr(best_score), _lib.ptr(n_cand),
+            _lib.ptr(pm_count), _lib.ptr(pm_pairs), stride, _lib.ptr(knn)))
+        return TopnBatchResult(best_row, best_score, n_cand, pm_count, pm_pairs, knn)
+
     def _get_library_candidates(self, queries: PackedSpectra, charge: int, mode: str):
         """CSR candidate lists (library rows of the charge partition, ascending) after the
         precursor filter -- and, in open+ann mode, after the ANN filter. Diagnostic
@@ -615,12 +681,14 @@ class SpectralLibrary:
         bs = self.config.batch_size
         t_level = time.perf_counter()
         n_in = sum(len(r) for r in rows_by_charge.values())
-        table = SSMTable(query_meta, library_meta)
+        n_best = int(self.config.num_matches)
+        table = SSMTable(query_meta, library_meta, n_best - 1)
         # Phase 1 issues every batch of the level; on one GPU the open-search batches go through
         # the two-stream pipeline (front of batch i+1 under the scan of batch i, no host wait
         # between batches). Phase 2, after one synchronisation, scores the winners and files them.
         d = getattr(self, '_dist', None)
-        piped = (self.device.type == 'cuda' and (d is None or d.world == 1) and
+        # (num_matches > 1: the top-n entry point is synchronous, the batches are not pipelined)
+        piped = (self.device.type == 'cuda' and (d is None or d.world == 1) and n_best == 1 and
                  not getattr(self, '_pipeline_on', False) and getattr(self, 'pipeline_cascade', True) and
                  any(self._uses_ann(z, mode) for z in rows_by_charge))
         if piped:
@@ -636,7 +704,13 @@ class SpectralLibrary:
                         continue
                     whole = len(sel) == qs.n and sel[0] == 0 and sel[-1] == qs.n - 1
                     q = (qs if whole else qs.select(torch.as_tensor(sel))).to(self.device)
-                    res = self._search_batch(q, charge, mode, device_out=True)
+                    if n_best > 1:      # rank 0 goes the single winner's way, the rest rides along
+                        top = self.search_batch_topn(q, charge, mode, n_best, device_out=True)
+                        res = None if top is None else top.rank0()
+                        if res is not None:
+                            res.topn = top
+                    else:
+                        res = self._search_batch(q, charge, mode, device_out=True)
                     if res is not None:
                         pending.append((charge, sel, q, res))
         finally:
@@ -707,10 +781,20 @@ class SSMTable:
     charge partition), ``score`` (search_engine_score), ``q``. Behaves as a sequence of the
     reference's SSM records (``spectrum.SpectrumSpectrumMatch``: the attributes writer.py:129-148
     reads), built on access from the query / library metadata and the peak matches the device
-    emitted (kept per batch, fetched from the device when first needed)."""
+    emitted (kept per batch, fetched from the device when first needed).
 
-    def __init__(self, query_meta, library_meta):
+    With ``num_matches = n > 1`` (``n_alt = n - 1``) every match also carries its runners-up:
+    ``alt_lib_row[len, n_alt]`` (-1 padded) and ``alt_score[len, n_alt]`` (shifted-dot scores of
+    ranks 1..), ``delta_score[len]`` (the rank-0 shifted-dot score minus rank 1's; the rank-0 score
+    itself without a runner-up; NaN when ``n_alt = 0``) and ``alt_peak_matches(i, r)``."""
+
+    def __init__(self, query_meta, library_meta, n_alt: int = 0):
         self.query_meta, self.library_meta = query_meta, library_meta
+        self.n_alt = int(n_alt)
+        self.alt_lib_row = np.zeros((0, self.n_alt), np.int32)
+        self.alt_score = np.zeros((0, self.n_alt), np.float64)
+        self.delta_score = np.zeros(0, np.float64)
+        self._alt_batches: list = []             # per batch: its TopnBatchResult (None: single winner)
         self.charge = np.zeros(0, np.int32)
         self.qrow = np.zeros(0, np.int64)
         self.lib_row = np.zeros(0, np.int32)
@@ -725,6 +809,18 @@ class SSMTable:
         hit = np.nonzero(best_row >= 0)[0]       # queries without a candidate: no SSM (:359)
         b = len(self._batches)
         self._batches.append(res)
+        top = getattr(res, 'topn', None)
+        self._alt_batches.append(top)
+        alt_row = np.full((len(hit), self.n_alt), -1, np.int32)
+        alt_score = np.zeros((len(hit), self.n_alt), np.float64)
+        delta = np.full(len(hit), np.nan)
+        if top is not None and self.n_alt > 0:
+            rows, scores = _to_np(top.best_row)[hit], _to_np(top.best_score)[hit]
+            alt_row, alt_score = rows[:, 1:].astype(np.int32), scores[:, 1:].astype(np.float64)
+            delta = scores[:, 0] - scores[:, 1]      # (an empty rank's score is 0.0)
+        self.alt_lib_row = np.concatenate([self.alt_lib_row, alt_row])
+        self.alt_score = np.concatenate([self.alt_score, alt_score])
+        self.delta_score = np.concatenate([self.delta_score, delta])
         self._pending.append((np.full(len(hit), charge, np.int32), np.asarray(qrows, np.int64)[hit],
                               best_row[hit].astype(np.int32), np.asarray(score, np.float64)[hit],
                               np.full(len(hit), b, np.int32), hit.astype(np.int32)))
@@ -748,19 +844,24 @@ class SSMTable:
         """Rows ``sel`` (boolean mask or indices, order kept); shares the per-batch storage."""
         sel = np.asarray(sel)
         idx = np.nonzero(sel)[0] if sel.dtype == bool else sel.astype(np.int64)
-        out = SSMTable(self.query_meta, self.library_meta)
-        out._batches = self._batches
-        for name in ('charge', 'qrow', 'lib_row', 'score', 'q', 'batch', 'pos'):
+        out = SSMTable(self.query_meta, self.library_meta, self.n_alt)
+        out._batches, out._alt_batches = self._batches, self._alt_batches
+        for name in ('charge', 'qrow', 'lib_row', 'score', 'q', 'batch', 'pos', 'alt_lib_row', 'alt_score',
+                     'delta_score'):
             setattr(out, name, getattr(self, name)[idx])
         return out
 
     @staticmethod
     def concat(tables) -> 'SSMTable':
-        out = SSMTable(tables[0].query_meta, tables[0].library_meta)
+        out = SSMTable(tables[0].query_meta, tables[0].library_meta, max(t.n_alt for t in tables))
         shift = 0
         for t in tables:
             out._batches = out._batches + t._batches
-            for name in ('charge', 'qrow', 'lib_row', 'score', 'q', 'pos'):
+            out._alt_batches = out._alt_batches + t._alt_batches
+            pad = ((0, 0), (0, out.n_alt - t.n_alt))
+            out.alt_lib_row = np.concatenate([out.alt_lib_row, np.pad(t.alt_lib_row, pad, constant_values=-1)])
+            out.alt_score = np.concatenate([out.alt_score, np.pad(t.alt_score, pad)])
+            for name in ('charge', 'qrow', 'lib_row', 'score', 'q', 'pos', 'delta_score'):
                 setattr(out, name, np.concatenate([getattr(out, name), getattr(t, name)]))
             out.batch = np.concatenate([out.batch, t.batch + shift])
             shift += len(t._batches)
@@ -823,6 +924,25 @@ class SSMTable:
         p = int(self.pos[i])
         return b[1][p, :b[0][p]].astype(np.int64)
 
+    def alt_peak_matches(self, i, r) -> np.ndarray:
+        """Peak matches ``[n, 2]`` of match ``i``'s rank ``r`` (1 .. n_alt) runner-up; empty when
+        the query had no such rank."""
+        if not 1 <= r <= self.n_alt:
+            raise IndexError(f'rank {r}: this table holds ranks 1 .. {self.n_alt}')
+        b = self._alt_batches[int(self.batch[i])]
+        if b is None:
+            return np.zeros((0, 2), np.int64)
+        if not isinstance(b, tuple):             # first access: one device -> host copy per batch
+            b = (_to_np(b.pm_count), _to_np(b.pm_pairs))
+            self._alt_batches[int(self.batch[i])] = b
+        p = int(self.pos[i])
+        return b[1][p, r, :b[0][p, r]].astype(np.int64)
+
+    def _alternatives(self, i) -> tuple:
+        lm = self.library_meta[int(self.charge[i])]
+        return tuple((lm[int(row)]['identifier'], float(self.alt_score[i, r]), self.alt_peak_matches(i, r + 1))
+                     for r, row in enumerate(self.alt_lib_row[i]) if row >= 0)
+
     def __getitem__(self, i):
         from .spectrum import SpectrumSpectrumMatch
         if isinstance(i, slice):
@@ -835,7 +955,7 @@ class SSMTable:
             lm['peptide'], qm['identifier'], qm['index'], lm['identifier'],
             qm.get('retention_time'), qm['precursor_charge'], qm['precursor_mz'],
             lm['precursor_mz'], lm.get('is_decoy', False), float(self.score[i]), float(self.q[i]),
-            self._peak_matches(i))
+            self._peak_matches(i), float(self.delta_score[i]), self._alternatives(i))
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))

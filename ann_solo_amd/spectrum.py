@@ -139,6 +139,11 @@ class SpectrumSpectrumMatch:
     search_engine_score: float = float('nan')
     q: float = float('nan')
     peak_matches: Optional[np.ndarray] = None
+    # num_matches > 1 (top-n rescoring): the shifted-dot score of this match minus the runner-up's
+    # (the score itself without a runner-up), and the runners-up, best first, as
+    # (library_identifier, shifted-dot score, peak_matches[n, 2])
+    delta_score: float = float('nan')
+    alternatives: tuple = ()
 
 
 def ssms_from_batch(result, query_meta, library_meta, scores=None, q_values=None

@@ -1,6 +1,7 @@
 """(Shifted) dot-product rescoring -- host-side mirror of the reference's
 ``ann_solo/spectrum_match.pyx`` (``get_best_match`` :28-108) on top of the HIP
-kernels behind ``asl_rescore_batch``.
+kernels behind ``asl_rescore_batch``; ``get_best_matches`` / ``rescore_batch_topn`` report the
+n best candidates instead of the single best (``asl_rescore_batch_topn``).
 """
 import numpy as np
 
@@ -25,6 +26,24 @@ def get_best_match(query, candidates, fragment_mz_tolerance, allow_shift):
             [(int(a), int(b)) for a, b in pairs[0, :n]])
 
 
+def get_best_matches(query, candidates, fragment_mz_tolerance, allow_shift, n):
+    """The ``n`` best candidates of ``get_best_match``'s ranking, best first: a list of up to ``n``
+    ``(candidate object, score, [(query_peak, candidate_peak), ...])`` (fewer when there are fewer
+    candidates). Equal scores go to the earlier candidate; entry 0 is ``get_best_match``'s answer."""
+    if len(candidates) == 0:
+        raise ValueError('get_best_matches needs at least one candidate '
+                         '(the reference guards this at spectral_library.py:359)')
+    q = PackedSpectra.from_spectra([query])
+    lib = PackedSpectra.from_spectra(candidates)
+    offsets = np.array([0, len(candidates)], np.int32)
+    rows = np.arange(len(candidates), dtype=np.int64)
+    best, score, counts, pairs = rescore_batch_topn(q, lib, rows, offsets, fragment_mz_tolerance,
+                                                    allow_shift, n)
+    return [(candidates[int(best[0, r])], float(score[0, r]),
+             [(int(a), int(b)) for a, b in pairs[0, r, :int(counts[0, r])]])
+            for r in range(best.shape[1]) if best[0, r] >= 0]
+
+
 def rescore_batch(queries: PackedSpectra, library: PackedSpectra, cand_rows, cand_offsets,
                   fragment_mz_tolerance, allow_shift, pm_stride=None):
     """Batched ``get_best_match``: candidates of query q are
@@ -46,5 +65,32 @@ def rescore_batch(queries: PackedSpectra, library: PackedSpectra, cand_rows, can
     _lib.check(_lib.lib().asl_rescore_batch(
         qs, ls, _lib.ptr(cand_rows), _lib.ptr(cand_offsets), float(fragment_mz_tolerance),
         int(bool(allow_shift)), _lib.ptr(best), _lib.ptr(score), _lib.ptr(count),
+        _lib.ptr(pairs), pm_stride))
+    return best, score, count, pairs
+
+
+def rescore_batch_topn(queries: PackedSpectra, library: PackedSpectra, cand_rows, cand_offsets,
+                       fragment_mz_tolerance, allow_shift, n_best, pm_stride=None):
+    """``rescore_batch`` for the ``n_best`` (1 .. 16) best candidates of every query, ordered by
+    score descending, equal scores by position in the query's list. Returns numpy
+    ``(best_cand[nq, n], best_score[nq, n], pm_count[nq, n], pm_pairs[nq, n, pm_stride, 2])``;
+    ranks beyond a list's valid entries hold -1 / 0.0 / 0 / zeros."""
+    nq, n = queries.n, int(n_best)
+    if pm_stride is None:
+        cnt = np.diff(np.asarray(queries.offsets.cpu()))
+        pm_stride = int(cnt.max()) if nq else 1
+    cand_rows = np.ascontiguousarray(cand_rows, np.int64) if isinstance(
+        cand_rows, (list, np.ndarray)) else cand_rows
+    cand_offsets = np.ascontiguousarray(cand_offsets, np.int32) if isinstance(
+        cand_offsets, (list, np.ndarray)) else cand_offsets
+    shape = (nq, max(n, 0))
+    best = np.empty(shape, np.int32)
+    score = np.empty(shape, np.float64)
+    count = np.empty(shape, np.int32)
+    pairs = np.zeros(shape + (pm_stride, 2), np.uint32)
+    qs, ls = _lib.peaks_struct(queries), _lib.peaks_struct(library)
+    _lib.check(_lib.lib().asl_rescore_batch_topn(
+        qs, ls, _lib.ptr(cand_rows), _lib.ptr(cand_offsets), float(fragment_mz_tolerance),
+        int(bool(allow_shift)), n, _lib.ptr(best), _lib.ptr(score), _lib.ptr(count),
         _lib.ptr(pairs), pm_stride))
     return best, score, count, pairs

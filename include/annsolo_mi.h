@@ -393,6 +393,23 @@ int asl_rescore_batch(const asl_peaks_t *queries, const asl_peaks_t *library,
                       double *best_score, int32_t *pm_count, uint32_t *pm_pairs,
                       int32_t pm_stride);
 
+/* The n best candidates of every query instead of the single best (top-n rescoring), 1 <= n_best <=
+ * ASL_MAX_BEST (anything else: ASL_ERR_INVALID). Every candidate slot is scored once, as in
+ * asl_rescore_batch; one more pass over the scores selects the n best in the order
+ *   score descending, then position in the query's list ascending
+ * (rank 0 is asl_rescore_batch's winner, bit for bit), and the peak matches of each are emitted.
+ * Every slot of a list is a candidate of its own: a row listed twice can take two ranks, the
+ * earlier position first. Outputs (each may be NULL, host or device memory, every element written):
+ *   best_cand  [nq, n_best]  position inside the query's list; -1 for the ranks beyond the list's
+ *                            valid entries (then score 0.0, count 0, zero pairs)
+ *   best_score [nq, n_best], pm_count [nq, n_best], pm_pairs [nq, n_best, pm_stride, 2] */
+#define ASL_MAX_BEST 16
+int asl_rescore_batch_topn(const asl_peaks_t *queries, const asl_peaks_t *library,
+                           const int64_t *cand_rows, const int32_t *cand_offsets,
+                           double fragment_mz_tolerance, int allow_shift, int32_t n_best,
+                           int32_t *best_cand, double *best_score, int32_t *pm_count,
+                           uint32_t *pm_pairs, int32_t pm_stride);
+
 /* ------------------------------------------------------------------ peak preprocessing
  * Replaces process_spectrum (src/ann_solo/spectrum.py:57-119: spectrum_utils set_mz_range,
  * round(resolution,'sum'), remove_precursor_peak(tol,'Da',2), filter_intensity,
@@ -495,6 +512,29 @@ int asl_rescore_knn(asl_library_t *lib, const asl_peaks_t *queries,
                     const asl_search_params_t *params, const int64_t *knn_I,
                     int32_t *best_row, double *best_score, int32_t *n_cand,
                     int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride);
+
+/* asl_search_batch for the n best library matches of every query, 1 <= n_best <= ASL_MAX_BEST
+ * (anything else: ASL_ERR_INVALID): best_row / best_score / pm_count are [nq, n_best], pm_pairs is
+ * [nq, n_best, pm_stride, 2], n_cand [nq] and knn_I [nq, k] as in asl_search_batch. Ranks are ordered
+ * by score descending, equal scores by the lower library row; ranks beyond the query's candidates
+ * hold row -1, score 0.0, count 0 and zero pairs. Column 0 of every output, n_cand and knn_I equal
+ * asl_search_batch's outputs bit for bit. Every mode of asl_search_batch is covered: use_ann = 1 on any
+ * index kind, with the scan-side post-filter on or off and in window-scan mode, and use_ann = 0 at
+ * any pair budget (each tile's n best are folded into a running n best per query on the device).
+ * NOT pipelined: like every entry point other than asl_search_batch the call first waits for the
+ * batches of asl_set_pipeline in flight, then runs on the library's stream and returns when its
+ * outputs are written. */
+int asl_search_batch_topn(asl_library_t *lib, asl_index_t *idx, const asl_peaks_t *queries,
+                          const asl_search_params_t *params, int32_t n_best, int32_t *best_row,
+                          double *best_score, int32_t *n_cand, int32_t *pm_count,
+                          uint32_t *pm_pairs, int32_t pm_stride, int64_t *knn_I);
+
+/* asl_rescore_knn for the n best matches: outputs as in asl_search_batch_topn (equal to it when
+ * knn_I holds the ids it searched). An id that knn_I names twice is two candidates. */
+int asl_rescore_knn_topn(asl_library_t *lib, const asl_peaks_t *queries,
+                         const asl_search_params_t *params, const int64_t *knn_I, int32_t n_best,
+                         int32_t *best_row, double *best_score, int32_t *n_cand,
+                         int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride);
 
 /* Precursor-window candidate generation alone (spectral_library.py:417-429):
  * CSR lists of library rows (ascending) whose precursor passes the window. Two-call

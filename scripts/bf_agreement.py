@@ -9,7 +9,9 @@ query set:
     reference notebook's measure);
   * bf_winner_in_topk: fraction whose brute-force winner is among the ANN top-k ids;
   * score gap brute force - ANN (mean, 99th percentile, fraction of queries with a gap);
-and the brute-force time per batch and pairs scored per second.
+and the brute-force time per batch and pairs scored per second. With `--ranks N` (2 .. 16) also
+  * bf_winner_in_top_ranks: fraction whose brute-force winner is among the ANN path's N best
+    rescored matches (the top-n rescoring, SpectralLibrary.search_batch_topn).
 
   python scripts/bf_agreement.py --out profiles/bf_agreement.json
 """
@@ -39,6 +41,8 @@ def main():
     ap.add_argument('--library-size', type=int, default=2_100_000)
     ap.add_argument('--queries', type=int, default=16384)
     ap.add_argument('--open-da', type=float, default=500.0)
+    ap.add_argument('--ranks', type=int, default=0,
+                    help='also report whether the brute-force winner is among the N best rescored ANN matches')
     ap.add_argument('--out', default='bf_agreement.json')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
@@ -88,6 +92,10 @@ def main():
                 'fraction_with_score_gap': float((gap[has] > 0).mean()),
                 'ann_score_above_bf': int((gap < 0).sum()),     # must be 0: the ANN lists are inside the window
                 'ann_seconds_per_batch_unpipelined': dt}
+            if args.ranks > 1:
+                top = sl.search_batch_topn(q, 2, 'open', args.ranks)
+                among = (top.best_row == b.best_row[:, None]).any(1)
+                out['engines'][ename][name].update(ranks=args.ranks, bf_winner_in_top_ranks=float(among[has].mean()))
             print(f'[{ename}] {name}: {out["engines"][ename][name]}', flush=True)
         sl.shutdown()
     with open(args.out, 'w') as f:
