@@ -15,6 +15,9 @@
 // Calling discipline (all 256 threads, uniform control flow):
 //   init();  per round: { b = begin_round(); ... offer() per candidate ...; end_round(n_appended_by_my_wave); }
 //   finish(D, I64, I32);
+// or, without a barrier per round (flat_scan.hip, pq_scan_v3.hip): the free_* protocol below --
+//   init();  per wave: free_reserve / free_write (or free_append); all waves: free_sync() when a
+//   reservation fails; free_done(); finish(...)
 #pragma once
 #include "topk.hpp"
 
@@ -71,7 +74,8 @@ template <int CAP, int ROUND_VECS, int NT = HT_NT>
 struct HistTopK {
   static constexpr int NW = NT / 64;
   enum { C_FILL = 0, C_BSTAR = 1, C_WCNT = 2 /* 2*NW <= 16 */, C_PART_B = 18 /* NW <= 8 */,
-         C_PART_C = 26 /* NW <= 8 */, C_USER = 34 /* 4 ints for the caller */ };
+         C_PART_C = 26 /* NW <= 8 */, C_USER = 34 /* 4 ints for the caller */,
+         C_COUNTED = 38 /* lazy counts: keys [0, C_COUNTED) are in the histogram */ };
   static constexpr int PER = CAP / NT;
   u64 *keys;
   u64 *thr_p;
@@ -105,7 +109,10 @@ struct HistTopK {
     sort_mode = false;
     tk.init(keys, ctl, thr_p, CAP, k, tid);
     for (int i = tid; i < HT_NB; i += NT) hist[i] = 0;
-    if (tid == 0) ctl[C_BSTAR] = 0;
+    if (tid == 0) {
+      ctl[C_BSTAR] = 0;
+      ctl[C_COUNTED] = 0;
+    }
     __syncthreads();
     bstar = 0;
     thr_hi = 0;
@@ -216,22 +223,38 @@ struct HistTopK {
     base = __builtin_amdgcn_readfirstlane(base);
     return base + c > CAP ? -1 : base;
   }
+  // count = false: LAZY COUNTS -- the key is not entered into the histogram here; free_sync(true)
+  // and free_done(true) count the keys appended since the last sync where the histogram is read.
+  // Both are exact: the histogram is only ever read inside a sync or a finish, where it then
+  // holds every stored key either way. A stream uses one of the two forms throughout.
   __device__ __forceinline__ void free_write(bool p, unsigned long long m, float score, uint32_t slot,
-                                             int base) {
+                                             int base, bool count = true) {
     if (p) {
       keys[base + __popcll(m & ((1ull << lane) - 1ull))] = ((u64)f2ord(score) << 32) | (u64)slot;
-      if (!sort_mode) atomicAdd(&hist[score_bucket(score)], 1);
+      if (count && !sort_mode) atomicAdd(&hist[score_bucket(score)], 1);
     }
   }
+  // lazy counts: the keys at [C_COUNTED, fill) are not in the histogram yet (empty slots of failed
+  // reservations are skipped). All threads; `fill` is up to date and every append has landed.
+  // (The mark lives in LDS: it is read once per sync and would cost the scan loop a register.)
+  __device__ __forceinline__ void count_appended() {
+    for (int i = ctl[C_COUNTED] + tid; i < fill; i += NT) {
+      const u64 key = keys[i];
+      if (key != 0ull) atomicAdd(&hist[score_bucket(ord2f((uint32_t)(key >> 32)))], 1);
+    }
+    __syncthreads();
+  }
   // all threads, after a barrier that every wave reached
-  __device__ __forceinline__ void free_sync() {
+  __device__ __forceinline__ void free_sync(bool lazy = false) {
     const int cf = ctl[C_FILL];
     __syncthreads();
     fill = cf < CAP ? cf : CAP;
     if (tid == 0) ctl[C_FILL] = fill;
     __syncthreads();
     if (!sort_mode) {
+      if (lazy) count_appended();
       fill = compact();
+      if (lazy && tid == 0) ctl[C_COUNTED] = fill;   // what the compaction keeps has been counted (read behind the next sync's barriers)
       if (fill > CAP - ROUND_VECS) {   // ties defeat the buckets: exact flushes from now on
         sort_mode = true;
         tk.slot_ids = slot_ids;
@@ -244,13 +267,14 @@ struct HistTopK {
     refresh_threshold();
   }
   // before finish(): the fill level as the appends left it (no reservation is pending)
-  __device__ __forceinline__ void free_done() {
+  __device__ __forceinline__ void free_done(bool lazy = false) {
     __syncthreads();
     const int cf = ctl[C_FILL];
     fill = cf < CAP ? cf : CAP;
     __syncthreads();
     if (tid == 0) ctl[C_FILL] = fill;
     __syncthreads();
+    if (lazy && !sort_mode) count_appended();
   }
 
   // drop every buffered key whose bucket is below bstar; returns the new fill

@@ -28,6 +28,9 @@
 // have been turned into ids -- (score desc, id asc), identical to the oracle.
 // If compaction cannot free the buffer (thousands of bit-identical scores) the kernel
 // switches, for that query, to exact sort-and-truncate flushes.
+// The waves append on their own (one reservation per tile that holds a candidate) and meet only
+// when the key buffer is full and at the end of a table chunk; the histogram is brought up to
+// date where it is read, in that sync (see "free-running appends" in the kernel).
 //
 // LDS: LUT 32 KB + key buffer (2048 or 4096 keys) + histogram + tile table => three (two)
 // workgroups of 8 waves per CU.
@@ -99,7 +102,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
   // a list whose length only the device knows: the shard-side rescans of exchange.hip)
   if (gate && (int)blockIdx.x >= *gate) return;
   static_assert(DEPTH >= 1 && DEPTH <= 3, "rounds of prefetch");
-  constexpr int NT = 64 * NW, ROUND_TILES = NW * T, ROUND_VECS = ROUND_TILES * 64;
+  static_assert(T == 1, "one tile per wave at a time (two lost on registers: profiles/HISTORY.md)");
+  constexpr int NT = 64 * NW, ROUND_VECS = NW * 64;
   using TopK = HistTopK<CAP, ROUND_VECS, NT>;
   using Ent = typename std::conditional<RANGED, TileEnt12, TileEnt8>::type;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -154,6 +158,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     total += part_total;
     __syncthreads();
   }
+  total = __builtin_amdgcn_readfirstlane(total);   // the same in every thread: the loops below are scalar
 
   TopK top;   // init zeroes the keys (which aliased s_q)
   top.init(smem, k, ids_tiled, tid);
@@ -164,12 +169,53 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
   const int rho = lane >> 4, j = lane & 15;
   const int ma = (rho & 1) ? j + 16 : j, mb = ma ^ 16;
   const uint32_t offA = (uint32_t)ma * 4u, offB = (uint32_t)mb * 4u;
-  const uint32_t chunkA = (uint32_t)(rho * 512 + ma * 16), chunkB = (uint32_t)(rho * 512 + mb * 16);
+  const uint32_t chunkA = (uint32_t)(rho * 512 + ma * 16);
+
+  // ---- free-running appends (HistTopK's free_* protocol, as in flat_scan.hip) -------------------
+  // A wave walks its own share of a table chunk (entries wave, wave + NW, ...) with its own register
+  // prefetch pipeline and appends what passes the threshold with one reservation per tile; the waves
+  // meet only when the key buffer is full (a sync) and at the end of a chunk. The histogram is not
+  // touched per tile: the sync counts what was appended since the last one (lazy counts).
+  //
+  // The tile loop rotates the register sets of the prefetch pipeline by unrolling; the sync has ONE
+  // place, behind that loop (free_sync inlines a compaction and a sort: a copy per register set cost
+  // the instantiations their registers). A wave that has to meet the others -- its reservation was
+  // refused, or the flag is up -- leaves the rotation with the tile in flight moved to set 0, joins the
+  // sync, offers a refused tile again (its scores wait in a register) against the new threshold, and
+  // starts the rotation over.
+  //
+  // No deadlock, whatever the data: the workgroup's barriers are (a) the fixed sequence of one
+  // sync and (b) the one barrier that ends a chunk. A wave enters (a) only with the flag raised --
+  // by itself, right before its first barrier, or seen raised by another wave, which is then on its
+  // way to that barrier and waits there -- and the flag is lowered behind the first barrier of the
+  // sequence, before the barriers of free_sync, so no wave sees it raised once the sync is over
+  // (a value read ahead of the sync is dropped in it). Every wave looks at the flag with every tile
+  // and in the wait at the end of its share, so every wave joins every sync. A wave enters (b) only
+  // after s_done says that all NW waves have finished their share of this chunk; a finished wave
+  // raises the flag only to join, and each request of an unfinished wave was answered by a complete
+  // sync before that wave could finish, so at that point no sync is open or can open. The retry of
+  // a refused tile ends: a sync leaves at least ROUND_VECS = NW * 64 free slots.
+  int *s_flag = top.ctl + TopK::C_USER;            // a wave asks for a sync (C_USER is free until finish_set)
+  int *s_done = top.ctl + TopK::C_USER + 1;        // waves that finished their share, summed over the chunks
+  if (tid == 0) {
+    *s_flag = 0;
+    *s_done = 0;
+  }
+  // (relaxed workgroup-scope accesses: plain LDS reads and writes that the compiler neither caches nor merges)
+  auto flag_up = [&]() -> int { return __hip_atomic_load(s_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
+  auto flag_set = [&](int v) { __hip_atomic_store(s_flag, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
+  // the threshold snapshot, wave-uniform: it only changes inside a sync
+  float thr_u = -INFINITY;
+  uint32_t thr_hi_u = 0;          // != 0 exactly while exact flushes are in use (a flush then leaves k keys)
+  int flag_u = 0;
 
   constexpr int CHUNK = RANGED ? V3_CHUNK_RANGED : V3_CHUNK;
   for (int c0 = 0; c0 < total; c0 += CHUNK) {
 #pragma unroll
     for (int pp = 0; pp < PP; ++pp) {
+      // (my probe as values of their own: what the fill derives from them is made here, once per chunk,
+      // not kept in registers across the tile loop)
+      asm volatile("" : "+v"(my_pre[pp]), "+v"(my_nt[pp]), "+v"(my_tile0[pp]), "+v"(my_len[pp]));
       const int lo = max(my_pre[pp], c0), hi = min(my_pre[pp] + my_nt[pp], c0 + CHUNK);
       for (int t = lo; t < hi; ++t) {
         const int local = t - my_pre[pp];
@@ -182,59 +228,132 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     }
     __syncthreads();
     const int nent = min(CHUNK, total - c0);
-    const int nrounds = (nent + ROUND_TILES - 1) / ROUND_TILES;
-    // Register pipeline, DEPTH rounds deep (the codes of rounds rr + 1 .. rr + DEPTH are in flight
-    // while round rr is scored). DEPTH + 1 register sets, rotated by full unrolling: every index
-    // below is a compile-time constant.
+    // Register pipeline over my wave's entries, DEPTH tiles deep (the codes of the next DEPTH tiles
+    // are in flight while one is scored). DEPTH + 1 register sets; `set` says which holds the tile to
+    // score, and the step is instantiated per set, so every register index is a compile-time constant.
     constexpr int NS = DEPTH + 1;
-    uint4 A[NS][T], B[NS][T];
-    TileEnt e[NS][T];
-    auto fetch = [&](int rr, uint4 *a, uint4 *b, TileEnt *en) {
-#pragma unroll
-      for (int u = 0; u < T; ++u) {
-        // the entry is the same for the whole wave: keep it in scalar registers
-        const int i = rr * ROUND_TILES + wave_u * T + u;
-        const Ent t = table[i < nent ? i : 0];
-        const uint32_t tn = __builtin_amdgcn_readfirstlane(t.tile_nv);
-        en[u].tile = tn & 0x3ffffffu;
-        en[u].coarse = __builtin_bit_cast(
-            float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t.coarse)));
-        en[u].nvalid = i < nent ? (int)(tn >> 26) + 1 : 0;
-        if constexpr (RANGED) en[u].pad = (int)__builtin_amdgcn_readfirstlane(t.first);   // first lane
-        const uint8_t *base = codes_tiled + (size_t)en[u].tile * 2048;
-        a[u] = load_codes16<V3_NT>(base + chunkA);
-        b[u] = load_codes16<V3_NT>(base + chunkB);
-      }
+    uint4 A[NS], B[NS];
+    struct Tile {         // the entry is the same for the whole wave: scalar registers
+      uint32_t tile_nv;   // tile | last lane << 26
+      float coarse;
+      uint32_t first;     // RANGED: first lane
+    } e[NS];
+    auto fetch = [&](int i, uint4 &a, uint4 &b, Tile &en) {
+      const Ent t = table[i];
+      en.tile_nv = __builtin_amdgcn_readfirstlane(t.tile_nv);
+      en.coarse = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t.coarse)));
+      if constexpr (RANGED) en.first = __builtin_amdgcn_readfirstlane(t.first);
+      // the tile's address is a scalar and the lane's part a 32-bit offset of its own: the loads take
+      // them as they are (scalar base + lane offset), no 64-bit lane addresses to keep or add up per tile
+      // (the second chunk's offset is made here from the first: a lane constant less to keep)
+      const uint8_t *base = codes_tiled + (size_t)(en.tile_nv & 0x3ffffffu) * 2048;
+      uint32_t offa = chunkA;
+      asm volatile("" : "+v"(offa));
+      const uint32_t offb = offa ^ 256u;       // mb = ma ^ 16
+      a = load_codes16<V3_NT>(base + offa);
+      b = load_codes16<V3_NT>(base + offb);
     };
-    auto process = [&](const uint4 *a, const uint4 *b, const TileEnt *en) {
-      top.begin_round();
-      int appended = 0;
-#pragma unroll
-      for (int u = 0; u < T; ++u) {
-        if (en[u].nvalid > 0) {  // wave-uniform
-          const float score = en[u].coarse + tile_adc(lut_bytes, a[u], b[u], offA, offB);
-          const bool in = RANGED ? (lane < en[u].nvalid && lane >= en[u].pad) : lane < en[u].nvalid;
-          const bool take = top.offer(in, score, en[u].tile * 64u + (uint32_t)lane);
-          appended += __popcll(__ballot(take));
-        }
+    // the tile whose candidates wait to be appended: its scores and (scalar) its entry
+    float p_score = 0.0f;
+    uint32_t p_tile_nv = 0, p_first = 0;
+    bool pending = false;
+    // A tile costs the ADC and one compare against the snapshot; the ordered key is only made for the
+    // lanes that pass (free_write), under the branch a tile without a passer skips.
+    auto append = [&]() {
+      const int end = (int)(p_tile_nv >> 26);
+      const bool in = RANGED ? (lane <= end && lane >= (int)p_first) : lane <= end;
+      bool p;
+      if (thr_hi_u != 0) {        // wave-uniform; exact flushes are in use: the ordered-key test
+        // (the score as a value of its own: keeps this a scalar branch and its ordered key in here,
+        // not three selects and a key per tile)
+        float sc = p_score;
+        asm volatile("; exact flushes" : "+v"(sc));
+        p = in && f2ord(sc) >= thr_hi_u;
+      } else {
+        p = in && p_score >= thr_u;
       }
-      top.end_round(appended);
+      const unsigned long long m = __ballot(p);
+      // (the reservation's verdict is settled before the lanes part to write their keys: `pending`
+      // stays a scalar, and with it every branch of the wave's loop)
+      int base = -2;              // nothing passes
+      if (m) base = top.free_reserve(__popcll(m));   // wave-uniform; -1: the buffer is full
+      pending = base == -1;
+      if (base >= 0) top.free_write(p, m, p_score, (p_tile_nv << 6) + (uint32_t)lane, base, false);
     };
+    // one tile: the codes of tile i are in set s; the flag is read ahead, with the table entry of the
+    // fetch (one LDS wait for both)
+    auto step = [&](int i, int s) {
+      const int fl = flag_up();
+      if (i + DEPTH * NW < nent)
+        fetch(i + DEPTH * NW, A[(s + DEPTH) % NS], B[(s + DEPTH) % NS], e[(s + DEPTH) % NS]);
+      flag_u = __builtin_amdgcn_readfirstlane(fl);
+      p_score = e[s].coarse + tile_adc(lut_bytes, A[s], B[s], offA, offB);
+      p_tile_nv = e[s].tile_nv;
+      if constexpr (RANGED) p_first = e[s].first;
+      append();
+    };
+    int i = wave_u;               // my next entry; between syncs its codes are in set 0, the next tiles' behind
 #pragma unroll
     for (int s = 0; s < DEPTH; ++s)
-      if (s < nrounds) fetch(s, A[s], B[s], e[s]);
-    for (int rr = 0; rr < nrounds; rr += NS) {
+      if (i + s * NW < nent) fetch(i + s * NW, A[s], B[s], e[s]);
+    bool finished = false;
+    for (;;) {                    // every condition below is wave-uniform
+      bool meet = false;
+      while (i < nent && !meet) {
 #pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        const int r = rr + s;
-        if (r < nrounds) {          // block-uniform
-          if (r + DEPTH < nrounds) fetch(r + DEPTH, A[(s + DEPTH) % NS], B[(s + DEPTH) % NS], e[(s + DEPTH) % NS]);
-          process(A[s], B[s], e[s]);
+        for (int s = 0; s < NS; ++s) {
+          if (i < nent && !meet) {
+            step(i, s);
+            i += NW;
+            if (pending || flag_u) {
+              // to the sync, from wherever in the rotation: the tiles in flight move to the front
+              // sets (register moves, once per sync), so that the loop starts over at set 0
+              meet = true;
+              if (s + 1 < NS) {
+#pragma unroll
+                for (int u = 0; u < DEPTH; ++u) {
+                  A[u] = A[(s + 1 + u) % NS];
+                  B[u] = B[(s + 1 + u) % NS];
+                  e[u] = e[(s + 1 + u) % NS];
+                }
+              }
+            }
+          }
         }
       }
+      if (!meet) {
+        // my share is done: wait for the other waves, joining the syncs they ask for
+        if (!finished) {
+          if (lane == 0) atomicAdd(s_done, 1);
+          finished = true;
+        }
+        for (;;) {
+          flag_u = __builtin_amdgcn_readfirstlane(flag_up());
+          if (flag_u ||
+              __builtin_amdgcn_readfirstlane(__hip_atomic_load(s_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >=
+                  NW * (c0 / CHUNK + 1))
+            break;
+          __builtin_amdgcn_s_sleep(4);
+        }
+        if (!flag_u) break;       // the chunk is done
+      }
+      do {                        // raise the flag, meet the other waves, count, compact; a refused tile again
+        if (lane == 0) flag_set(1);
+        __syncthreads();
+        if (tid == 0) flag_set(0);
+        // (the thread index as a value of its own: what the compaction and the sort derive from it --
+        // addresses, wave predicates -- is then made here, not kept in registers across the tile loop)
+        asm volatile("" : "+v"(top.tid));
+        top.free_sync(true);
+        thr_u = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, top.thr_f)));
+        thr_hi_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)top.thr_hi);
+        flag_u = 0;               // read before this sync
+        if (pending) append();
+      } while (pending);
     }
     __syncthreads();
   }
+  top.free_done(true);
   if constexpr (RANGED) {
     // set mode: the row holds in-window hits only, so its length goes to the rescoring as it is
     // (rescore.hip: prefiltered rows; -1 after exact flushes: the row is -1 padded and the
