@@ -26,6 +26,26 @@ static int dev_append(DevBuf<T> &buf, size_t old_n, const T *src_dev, size_t n) 
   return ASL_OK;
 }
 
+int index_shape_check(const char *who, int d, int nlist, int kind, int pq_m, int pq_bits) {
+  if (d <= 0 || kind < ASL_INDEX_FLAT || kind > ASL_INDEX_IVFPQ) return fail(ASL_ERR_INVALID, "%s: bad d/kind", who);
+  if (kind != ASL_INDEX_FLAT && nlist <= 0) return fail(ASL_ERR_INVALID, "%s: nlist must be positive", who);
+  if (kind != ASL_INDEX_IVFPQ) return ASL_OK;
+  if (pq_bits < 1 || pq_bits > 8) return fail(ASL_ERR_INVALID, "%s: pq_bits=%d outside 1..8", who, pq_bits);
+  if (!(pq_m == 4 || pq_m == 8 || pq_m == 16 || pq_m == 32 || pq_m == 64))
+    return fail(ASL_ERR_INVALID, "%s: pq_m=%d is not one of 4, 8, 16, 32, 64", who, pq_m);
+  if (d % pq_m != 0) return fail(ASL_ERR_INVALID, "%s: pq_m=%d does not divide d=%d", who, pq_m, d);
+  // the generic scan keeps a query, its ADC table and a top-k buffer in LDS: an index beyond that could be
+  // trained and filled but never searched (and a code of d / pq_m < 10 240 floats always fits the 64 KB
+  // rounds of the training / encoding kernels). The tiled scan has a tighter limit of its own, which
+  // tiled_index() applies: past it, m = 32 at 8 bits is scanned by the generic kernel as well.
+  const size_t lds = pq_scan_lds_bytes(pq_m, 1 << pq_bits, d, 1);
+  if (lds > (size_t)PQ_MAX_LDS_BYTES)
+    return fail(ASL_ERR_CAPACITY, "%s: d=%d, pq_m=%d, pq_bits=%d: a query, its look-up table and the smallest "
+                                  "top-k buffer take %lld bytes of LDS, a workgroup has %d KB",
+                who, d, pq_m, pq_bits, (long long)lds, PQ_MAX_LDS_BYTES / 1024);
+  return ASL_OK;
+}
+
 }  // namespace asl
 
 using namespace asl;
@@ -35,22 +55,8 @@ extern "C" {
 asl_index_t *asl_index_create(int32_t d, int32_t nlist, int32_t kind, int32_t pq_m,
                               int32_t pq_bits) {
   clear_error();
-  if (d <= 0 || kind < ASL_INDEX_FLAT || kind > ASL_INDEX_IVFPQ) {
-    fail(ASL_ERR_INVALID, "index_create: bad d/kind");
-    return nullptr;
-  }
-  if (kind != ASL_INDEX_FLAT && nlist <= 0) {
-    fail(ASL_ERR_INVALID, "index_create: nlist must be positive");
-    return nullptr;
-  }
-  if (kind == ASL_INDEX_IVFPQ) {
-    if (pq_bits <= 0) pq_bits = 8;
-    if (pq_bits > 8 || pq_m <= 0 || d % pq_m != 0 ||
-        !(pq_m == 4 || pq_m == 8 || pq_m == 16 || pq_m == 32 || pq_m == 64)) {
-      fail(ASL_ERR_INVALID, "index_create: pq_m must be 4/8/16/32/64 and divide d; pq_bits <= 8");
-      return nullptr;
-    }
-  }
+  if (kind == ASL_INDEX_IVFPQ && pq_bits <= 0) pq_bits = 8;
+  if (index_shape_check("index_create", d, nlist, kind, pq_m, pq_bits) != ASL_OK) return nullptr;
   if (ensure_device() != ASL_OK) return nullptr;
   asl_index *ix = new asl_index();
   ix->d = d;

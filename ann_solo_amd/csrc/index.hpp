@@ -141,6 +141,16 @@ struct asl_index {
 
 namespace asl {
 
+// index.hip: the one check of an index's shape, for asl_index_create and asl_index_load (`who`): ASL_OK
+// when (d, nlist, kind, pq_m, pq_bits) can be trained, filled and searched, else fail() names what cannot.
+int index_shape_check(const char *who, int d, int nlist, int kind, int pq_m, int pq_bits);
+// The tiled scan (pq_scan_v3.hip) is built for m = 32 and 8 bits, and keeps a query's components as
+// 2-byte entries behind an 8-byte head in the 2 KB of its tile table: d * 2 + 8 <= 2048. A wider index
+// of that m and bits gets no tiles and is scanned by the generic kernel, like every other shape.
+constexpr int PQ_TILED_MAX_D = 1020;
+inline bool tiled_index(const asl_index *ix) {
+  return ix->kind == ASL_INDEX_IVFPQ && ix->pq_m == 32 && ix->ksub == 256 && ix->d <= PQ_TILED_MAX_D;
+}
 // index_train.hip
 int assign_ip(asl_index *ix, const float *x, int64_t ld, int64_t n, const float *cent, int k, int d,
               int32_t *assign_dev);

@@ -90,16 +90,18 @@ asl_index_t *asl_index_load(const char *path) {
     fail(ASL_ERR_IO, "load: %s is not an annsolo_mi index", path);
     return nullptr;
   }
-  {  // never trust a file: every count below sizes a host vector or a device allocation
+  // never trust a file. Its shape passes the check asl_index_create makes, so that what loads can be searched ...
+  if (index_shape_check("load", h.d, h.nlist, h.kind, h.pq_m, h.pq_bits) != ASL_OK) {
+    fclose(f);
+    return nullptr;
+  }
+  {  // ... and every count below sizes a host vector or a device allocation
     const char *bad = nullptr;
     const bool ivf = h.kind == ASL_INDEX_IVFFLAT || h.kind == ASL_INDEX_IVFPQ;
     if (h.version != 1 && h.version != 2) bad = "unsupported version";
     else if (h.kind < ASL_INDEX_FLAT || h.kind > ASL_INDEX_IVFPQ) bad = "unknown index kind";
     else if (h.d <= 0 || h.d > (1 << 20)) bad = "bad dimension";
     else if (ivf && (h.nlist <= 0 || h.nlist > (1 << 24))) bad = "bad nlist";
-    else if (h.kind == ASL_INDEX_IVFPQ &&
-             (!(h.pq_m == 4 || h.pq_m == 8 || h.pq_m == 16 || h.pq_m == 32 || h.pq_m == 64) ||
-              h.d % h.pq_m != 0 || h.pq_bits < 1 || h.pq_bits > 8)) bad = "bad product quantiser";
     else if (h.n_store < 0 || h.ntotal < h.n_store || h.ntotal >= ((int64_t)1 << 31)) bad = "bad vector counts";
     else if (h.niter < 0 || (h.trained != 0 && h.trained != 1) || (h.has_vids != 0 && h.has_vids != 1)) bad = "bad flags";
     else if (h.shard_world < 1 || h.shard_rank < 0 || h.shard_rank >= h.shard_world) bad = "bad shard fields";

@@ -49,7 +49,7 @@ int build_lists(asl_index *ix) {
     ASL_TRY(ix->ids.upload(h_order.data(), (size_t)n));
   }
   ix->has_tiles = false;
-  if (ix->kind == ASL_INDEX_IVFPQ && ix->pq_m == 32 && ix->ksub == 256) {
+  if (tiled_index(ix)) {
     std::vector<int32_t> tile_off((size_t)ix->nlist + 1, 0), dst_slot((size_t)n);
     for (int l = 0; l < ix->nlist; l++)
       tile_off[(size_t)l + 1] = tile_off[(size_t)l] + (off[(size_t)l + 1] - off[(size_t)l] + 63) / 64;
@@ -210,7 +210,7 @@ int post_filter_pairs(asl_index *ix, const IndexPostFilter &p, uint64_t serial, 
 // nullptr when the index can hold the window-ordered layout, else why not
 const char *window_unsupported(const asl_index *ix) {
   if (ix->kind != ASL_INDEX_IVFPQ) return "the window scan needs an IVF-PQ index (not IVF-Flat or Flat)";
-  if (ix->pq_m != 32 || ix->ksub != 256) return "the window scan needs the tiled IVF-PQ scan (m = 32, 8 bits)";
+  if (!tiled_index(ix)) return "the window scan needs the tiled IVF-PQ scan (m = 32, 8 bits, d <= 1020)";
   if (ix->shard_world > 1 || ix->has_vids) return "the window scan does not run on a sharded index";
   return nullptr;
 }

@@ -70,7 +70,7 @@ static bool postings_ok(const asl_index *ix, int k, int nprobe) {      // dimens
   return ix->has_inv && ix->scan_variant == 0 && flat_inv_supported(ix->d, k, nprobe);
 }
 static bool tiled_shape_ok(const asl_index *ix, int k, int nprobe) {   // tiled IVF-PQ scan, once the lists are tiled
-  return ix->scan_variant == 0 && pq_scan_tiled_supported(ix->pq_m, ix->ksub, k, nprobe);
+  return ix->scan_variant == 0 && tiled_index(ix) && pq_scan_tiled_supported(ix->pq_m, ix->ksub, k, nprobe);
 }
 static bool keys_fit(int k) { return k + FLAT_KEYS_SLACK <= TK_MAX_K; }  // packed-key and post-filtered rows
 

@@ -466,7 +466,7 @@ int renorm_rows(float *c, int k, int d) {
 }
 
 // ------------------------------------------------------------------ L2 assignment (PQ)
-// x: [n, ld] (sub-vector view, dsub <= 32), cb: [ksub, dsub]. Chain
+// x: [n, ld] (sub-vector view), cb: [ksub, dsub]. Chain
 // acc = fmaf(x-c, x-c, acc) ascending, arg-min with lowest-index ties.
 __global__ __launch_bounds__(256) void l2_assign_kernel(const float *__restrict__ x,
                                                         int64_t ld, int64_t n, int dsub,
@@ -512,11 +512,60 @@ __global__ __launch_bounds__(256) void l2_assign_kernel(const float *__restrict_
   }
   assign[i] = best;
 }
+// A codebook beyond the 64 KB of LDS every kernel may ask for (wide sub-vectors only: d = 800 with
+// m = 4 is 204 800 B, m = 8 102 400 B): staged `chunk` codes at a time, (bs, best) carried from one
+// round to the next by l2_argmin_wide -- the slow path's loop, so the same arg-min. Kernels of their own,
+// and a loop of their own: l2_assign_kernel and pq_encode_kernel, which every codebook within 64 KB still
+// takes in one piece (the default shape among them), stay as they were to the instruction: built on this
+// helper as well, pq_encode_kernel takes 44 VGPRs instead of 42 (profiles/pq_shapes_resource_usage.txt).
+// Launcher and kernel compute `chunk` alike.
+// One round of that slow path, for the two rounds kernels (RES: the operand is the residual xi[t] - ci[t]):
+// codes [c0, c0 + nc) staged at s_cb, ascending c, strict <, the running (bs, best) carried in and out.
+template <bool RES>
+__device__ __forceinline__ void l2_argmin_wide(const float *xi, const float *ci, int dsub,
+                                               const float *s_cb, int c0, int nc, float &bs, int &best) {
+  for (int c = 0; c < nc; ++c) {
+    float acc = 0.0f;
+    for (int t = 0; t < dsub; ++t) {
+      const float df = (RES ? xi[t] - ci[t] : xi[t]) - s_cb[c * dsub + t];
+      acc = __builtin_fmaf(df, df, acc);
+    }
+    if (acc < bs) {
+      bs = acc;
+      best = c0 + c;
+    }
+  }
+}
+__host__ __device__ static inline int pq_cb_chunk(int ksub, int dsub) {
+  const int fit = 64 * 1024 / 4 / dsub;      // (0: not even one code; asl_index_create accepts no such index)
+  return ksub < fit ? ksub : fit;
+}
+__global__ __launch_bounds__(256) void l2_assign_rounds_kernel(const float *__restrict__ x,
+                                                               int64_t ld, int64_t n, int dsub,
+                                                               const float *__restrict__ cb, int ksub,
+                                                               int32_t *__restrict__ assign) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float *s_cb = reinterpret_cast<float *>(smem);
+  const int64_t i = block_linear() * 256 + threadIdx.x;
+  const int chunk = pq_cb_chunk(ksub, dsub);
+  float bs = INFINITY;
+  int best = 0;
+  for (int c0 = 0; c0 < ksub; c0 += chunk) {
+    const int nc = min(chunk, ksub - c0);
+    if (c0) __syncthreads();      // every lane is done with the codes before
+    for (int j = threadIdx.x; j < nc * dsub; j += 256) s_cb[j] = cb[(size_t)c0 * dsub + j];
+    __syncthreads();
+    if (i < n) l2_argmin_wide<false>(x + i * ld, nullptr, dsub, s_cb, c0, nc, bs, best);
+  }
+  if (i < n) assign[i] = best;
+}
 int l2_assign(const float *x, int64_t ld, int64_t n, int dsub, const float *cb, int ksub,
               int32_t *assign) {
   if (n <= 0) return ASL_OK;
-  hipLaunchKernelGGL(l2_assign_kernel, grid_2d(cdiv(n, 256)), dim3(256),
-                     (size_t)ksub * dsub * 4, stream(), x, ld, n, dsub, cb, ksub, assign);
+  const int chunk = pq_cb_chunk(ksub, dsub);
+  if (chunk < 1) return fail(ASL_ERR_CAPACITY, "l2_assign: a sub-vector of %d floats does not fit LDS", dsub);
+  hipLaunchKernelGGL(chunk == ksub ? l2_assign_kernel : l2_assign_rounds_kernel, grid_2d(cdiv(n, 256)),
+                     dim3(256), (size_t)chunk * dsub * 4, stream(), x, ld, n, dsub, cb, ksub, assign);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }
@@ -589,13 +638,40 @@ __global__ __launch_bounds__(256) void pq_encode_kernel(
   }
   codes[(size_t)i * m + mi] = (uint8_t)best;
 }
+// (a codebook beyond 64 KB in rounds of pq_cb_chunk codes, as l2_assign_rounds_kernel)
+__global__ __launch_bounds__(256) void pq_encode_rounds_kernel(
+    const float *__restrict__ x, const int32_t *__restrict__ assign,
+    const float *__restrict__ centroids, const float *__restrict__ codebooks, int64_t n, int d,
+    int m, int ksub, int dsub, uint8_t *__restrict__ codes) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float *s_cb = reinterpret_cast<float *>(smem);
+  const int mi = blockIdx.y;
+  const float *cb = codebooks + (size_t)mi * ksub * dsub;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = i < n;
+  const float *xi = x + (size_t)(live ? i : 0) * d + (size_t)mi * dsub;
+  const float *ci = centroids + (size_t)(live ? assign[i] : 0) * d + (size_t)mi * dsub;
+  const int chunk = pq_cb_chunk(ksub, dsub);
+  float bs = INFINITY;
+  int best = 0;
+  for (int c0 = 0; c0 < ksub; c0 += chunk) {
+    const int nc = min(chunk, ksub - c0);
+    if (c0) __syncthreads();      // every lane is done with the codes before
+    for (int j = threadIdx.x; j < nc * dsub; j += 256) s_cb[j] = cb[(size_t)c0 * dsub + j];
+    __syncthreads();
+    if (live) l2_argmin_wide<true>(xi, ci, dsub, s_cb, c0, nc, bs, best);
+  }
+  if (live) codes[(size_t)i * m + mi] = (uint8_t)best;
+}
 int pq_encode(const float *x, const int32_t *assign, const float *centroids,
               const float *codebooks, int64_t n, int d, int m, int ksub, int dsub,
               uint8_t *codes) {
   if (n <= 0) return ASL_OK;
-  hipLaunchKernelGGL(pq_encode_kernel, dim3((unsigned)cdiv(n, 256), m), dim3(256),
-                     (size_t)ksub * dsub * 4, stream(), x, assign, centroids, codebooks, n, d,
-                     m, ksub, dsub, codes);
+  const int chunk = pq_cb_chunk(ksub, dsub);
+  if (chunk < 1) return fail(ASL_ERR_CAPACITY, "pq_encode: a sub-vector of %d floats does not fit LDS", dsub);
+  hipLaunchKernelGGL(chunk == ksub ? pq_encode_kernel : pq_encode_rounds_kernel,
+                     dim3((unsigned)cdiv(n, 256), m), dim3(256), (size_t)chunk * dsub * 4, stream(), x,
+                     assign, centroids, codebooks, n, d, m, ksub, dsub, codes);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }
@@ -635,6 +711,7 @@ int pq_lut(const float *xq, int nq, int d, const float *codebooks, int m, int ks
            float *lut_out) {
   if (nq <= 0) return ASL_OK;
   const size_t lds = ((size_t)m * ksub + d) * 4;
+  if (lds > (size_t)PQ_MAX_LDS_BYTES) return fail(ASL_ERR_CAPACITY, "pq lut: d=%d / m=%d do not fit LDS", d, m);
   if (lds > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute((const void *)pq_lut_kernel,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -721,6 +798,10 @@ __global__ __launch_bounds__(TK_NT) void pq_scan_kernel(
   if (upper_out && tid == 0) upper_out[q] = ctl[0] >= k ? buf[k - 1] : 0ull;
 }
 
+size_t pq_scan_lds_bytes(int m, int ksub, int d, int k) {
+  return (size_t)topk_cap_for(k) * 8 + 16 + ((size_t)m * ksub + d) * 4;
+}
+
 template <int M>
 static int launch_pq_scan(const float *xq, int nq, int d, const float *codebooks, int ksub,
                           int dsub, const float *coarse_D, const int32_t *coarse_I, int nprobe,
@@ -728,8 +809,8 @@ static int launch_pq_scan(const float *xq, int nq, int d, const float *codebooks
                           int k, float *D, int64_t *I64, int32_t *I32, int64_t out_ld,
                           const uint64_t *upper_in, uint64_t *upper_out) {
   const int cap = topk_cap_for(k);
-  const size_t lds = (size_t)cap * 8 + 16 + ((size_t)M * ksub + d) * 4;
-  if (lds > 160 * 1024) return fail(ASL_ERR_CAPACITY, "pq scan: k=%d / m=%d do not fit LDS", k, M);
+  const size_t lds = pq_scan_lds_bytes(M, ksub, d, k);
+  if (lds > (size_t)PQ_MAX_LDS_BYTES) return fail(ASL_ERR_CAPACITY, "pq scan: k=%d / m=%d do not fit LDS", k, M);
   if (lds > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute((const void *)pq_scan_kernel<M>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -13,6 +13,7 @@ constexpr int TK_NT = 256;        // threads per top-k workgroup
 constexpr int TK_MAX_K = 2048;    // largest k / nprobe the LDS top-k supports
 constexpr int TK_MAX_K_PASSES = 16384;   // largest k of a search: beyond TK_MAX_K in bounded passes of the generic kernels
 constexpr int PQ_MAX_DSUB = 32;   // register fast path of the PQ L2 kernels
+constexpr int PQ_MAX_LDS_BYTES = 160 * 1024;   // a workgroup's LDS: what pq_scan_lds_bytes may come to
 
 // gate != nullptr: the kernel returns at once when *gate <= gate_max (device-side choice
 // between this GEMM and the sparse coarse quantiser)
@@ -59,6 +60,8 @@ int pq_scan(const float *xq, int nq, int d, const float *codebooks, int m, int k
             const uint64_t *upper_in = nullptr, uint64_t *upper_out = nullptr);
 // tiled IVF-PQ scan (pq_scan_v3.hip): m = 32 sub-quantisers of 8 bits
 bool pq_scan_tiled_supported(int m, int ksub, int k, int nprobe);
+// LDS of a pq_scan workgroup: the top-k buffer of k, the ADC table and the query
+size_t pq_scan_lds_bytes(int m, int ksub, int d, int k);
 int pq_scan_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
                const float *coarse_D, const int32_t *coarse_I, int nprobe,
                const int32_t *list_offsets, const int32_t *tile_offsets,

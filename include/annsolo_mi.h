@@ -112,7 +112,15 @@ int asl_encode_entries_batch(const float *mz, const float *intensity, const int3
  * 443-445,487-497: IndexFlatIP, IndexIVFFlat(quantizer, d, nlist, IP), train, add,
  * search, nprobe, reset, write_index/read_index. Row ids are implicit 0..ntotal-1
  * in add order. search(): rows sorted by (score desc, id asc); missing results
- * are I = -1, D = -FLT_MAX. */
+ * are I = -1, D = -FLT_MAX.
+ * IVF-PQ shapes: pq_m in {4, 8, 16, 32, 64} dividing d, pq_bits 1..8 (0: 8), and
+ * pq_m * 2^pq_bits + d <= 38 908 floats (a query, its look-up table and the smallest top-k
+ * buffer share the 160 KB of LDS of a workgroup); asl_index_create refuses anything else
+ * (NULL, asl_last_error says why), and asl_index_load makes the same check of a file. Every
+ * accepted shape trains, encodes and searches; how large a k its scan holds shrinks with d
+ * (asl_index_search says so where k does not fit). The tiled scan, and with it the window scan,
+ * packed-key rows and gated / entry-list searches, serves pq_m = 32 at 8 bits up to d = 1020;
+ * a wider index of that shape is searched by the generic kernel, like every other shape. */
 typedef struct asl_index asl_index_t;
 
 asl_index_t *asl_index_create(int32_t d, int32_t nlist, int32_t kind, int32_t pq_m,

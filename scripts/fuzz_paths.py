@@ -30,8 +30,8 @@ while time.time() < t_end and trials < int(os.environ.get('FUZZ_MAX', 10 ** 9)):
     nprobe = int(rng.integers(1, nlist + 1))
     k = int(rng.choice([1, 17, 128, 512, 1024, 2048, 1024, 2049, 3000, 5000]))   # > 2048: bounded passes
     index = str(rng.choice(['ivfpq', 'ivfflat']))
-    pq_m = int(rng.choice([8, 16, 32]))
-    pq_bits = int(rng.choice([6, 8])) if pq_m != 32 or rng.random() < 0.3 else 8
+    pq_m = int(rng.choice([4, 8, 16, 32]))          # every pq_m that divides d = 800 (64 does not); n >= 1500 >= 2^pq_bits trains any of them
+    pq_bits = int(rng.choice([4, 6, 8])) if pq_m != 32 or rng.random() < 0.3 else 8
     tol_mode = str(rng.choice(['Da', 'ppm']))
     tol = float(rng.choice([0.05, 5.0, 300.0, 500.0])) if tol_mode == 'Da' else float(rng.choice([10.0, 2e4, 2e5]))
     shifts = bool(rng.random() < 0.8)
