@@ -78,6 +78,7 @@ EXPORTS = [
     'asl_encode_entries_batch', 'asl_index_search_sharded_ex',
     'asl_index_set_window_key', 'asl_index_search_window', 'asl_index_set_window_scan',
     'asl_rescore_batch_topn', 'asl_search_batch_topn', 'asl_rescore_knn_topn',
+    'asl_index_rank',
 ]
 
 
@@ -178,6 +179,9 @@ def lib():
                                               C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                               C.c_void_p]
         L.asl_index_set_window_scan.argtypes = [C.c_void_p, C.c_int32]
+        L.asl_index_rank.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
         L.asl_index_set_flat_storage.argtypes = [C.c_void_p, C.c_int32]
         L.asl_index_flat_layout.argtypes = [C.c_void_p]
         L.asl_index_get_flat_storage.argtypes = [C.c_void_p]

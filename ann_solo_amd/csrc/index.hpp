@@ -168,5 +168,7 @@ int coarse_search(asl_index *ix, const float *xq, int nq, int nprobe, float *out
                   int32_t *cnt_out, bool *have_ent);
 int index_window_prepare(asl_index *ix, uint64_t serial, const float *key, int64_t n, int nq, int nprobe);
 int index_refine_k(const asl_index *ix);
+int coarse_scores_all(asl_index *ix, const float *xq, int m, float *scores, uint2 *ent = nullptr, int32_t *cnt = nullptr);
+int index_codebooks_transposed(asl_index *ix);
 
 }  // namespace asl

@@ -15,6 +15,26 @@ static int coarse_transposed(asl_index *ix) {
   return ASL_OK;
 }
 
+// q . centroid of EVERY list for rows [0, m) of xq -> scores [m, nlist]: what coarse_search selects its probes
+// from (and asl_index_rank's exhaustive IVF-PQ scope takes its coarse terms from). Hashed spectra are sparse
+// (<= ~50 of 800 components): the scores come from the sparse kernel, bit-identical to the GEMM. Both are
+// enqueued; a device-side count of dense rows (more than 64 non-zeros) decides which of the two does the
+// work (the other returns at once). ent / cnt (may be null: the index's own buffers): the rows' entry lists.
+int coarse_scores_all(asl_index *ix, const float *xq, int m, float *scores, uint2 *ent, int32_t *cnt) {
+  const int nlist = ix->nlist, d = ix->d;
+  const bool sparse = ix->scan_variant == 0 && coarse_sparse_supported(d, nlist);
+  const int over_max = m / 64;
+  if (sparse) {
+    ASL_TRY(coarse_transposed(ix));
+    ASL_TRY(ix->cs_ent.reserve((size_t)m * coarse_sparse_cap()));
+    ASL_TRY(ix->cs_cnt.reserve((size_t)m));
+    ASL_TRY(ix->cs_over.reserve(1));
+    ASL_TRY(coarse_sparse(xq, m, d, ix->centroids_t.p, nlist, ent ? ent : ix->cs_ent.p, cnt ? cnt : ix->cs_cnt.p,
+                          ix->cs_over.p, over_max, scores, nlist));
+  }
+  return gemm_nt_f32(xq, ix->centroids.p, scores, m, nlist, d, d, d, nlist, sparse ? ix->cs_over.p : nullptr, over_max);
+}
+
 // coarse quantiser: top-nprobe centroids by inner product -> ix->coarse_D / coarse_I
 // ent_out / cnt_out (caller buffers [nq * 64] / [nq], may be null): the queries' entry lists, which
 // the sparse coarse kernel lists anyway, for the scan that follows (*have_ent says whether they were
@@ -31,28 +51,13 @@ int coarse_search(asl_index *ix, const float *xq, int nq, int nprobe, float *out
   }
   int rows = (int)std::min<int64_t>(nq, std::max<int64_t>(1, (int64_t)(SCORE_CHUNK_BYTES / ((size_t)nlist * 4))));
   ASL_TRY(ix->ws_scores.reserve((size_t)rows * nlist));
-  // Hashed spectra are sparse (<= ~50 of 800 components): the scores come from the sparse
-  // kernel, bit-identical to the GEMM. Both are enqueued; a device-side count of dense rows
-  // (more than 64 non-zeros) decides which of the two does the work (the other returns at once).
   const bool sparse = ix->scan_variant == 0 && coarse_sparse_supported(d, nlist);
-  if (sparse) {
-    ASL_TRY(coarse_transposed(ix));
-    ASL_TRY(ix->cs_ent.reserve((size_t)rows * coarse_sparse_cap()));
-    ASL_TRY(ix->cs_cnt.reserve((size_t)rows));
-    ASL_TRY(ix->cs_over.reserve(1));
-  }
   for (int r0 = 0; r0 < nq; r0 += rows) {
     const int m = std::min(rows, nq - r0);
     {
       ProfScope ps("coarse_gemm");
-      const int over_max = m / 64;
-      if (sparse)
-        ASL_TRY(coarse_sparse(xq + (size_t)r0 * d, m, d, ix->centroids_t.p, nlist,
-                              ent_out ? ent_out + (size_t)r0 * 64 : ix->cs_ent.p,
-                              cnt_out ? cnt_out + (size_t)r0 : ix->cs_cnt.p,
-                              ix->cs_over.p, over_max, ix->ws_scores.p, nlist));
-      ASL_TRY(gemm_nt_f32(xq + (size_t)r0 * d, ix->centroids.p, ix->ws_scores.p, m, nlist, d, d, d, nlist,
-                          sparse ? ix->cs_over.p : nullptr, over_max));
+      ASL_TRY(coarse_scores_all(ix, xq + (size_t)r0 * d, m, ix->ws_scores.p, ent_out ? ent_out + (size_t)r0 * 64 : nullptr,
+                                cnt_out ? cnt_out + (size_t)r0 : nullptr));
     }
     {
       ProfScope ps("coarse_select");
@@ -291,7 +296,7 @@ static int search_ivfflat(asl_index *ix, IndexSearch &rq, const SearchPlan &pl) 
 }
 
 // [m][dsub][ksub] copy of the codebooks for the tiled scan's LUT build (rebuilt after train / set_trained)
-static int codebooks_transposed(asl_index *ix) {
+int index_codebooks_transposed(asl_index *ix) {
   if (ix->cbt_ready) return ASL_OK;
   const size_t ncb = (size_t)ix->pq_m * ix->ksub * ix->dsub;
   std::vector<float> h((size_t)ncb), ht((size_t)ncb);
@@ -312,7 +317,7 @@ static int codebooks_transposed(asl_index *ix) {
 static int scan_pq_tiled(asl_index *ix, IndexSearch &rq, const SearchPlan &pl, const float *cD, const int32_t *cI,
                          bool own_ent) {
   const int nq = rq.nq, nprobe = pl.nprobe;
-  ASL_TRY(codebooks_transposed(ix));
+  ASL_TRY(index_codebooks_transposed(ix));
   const uint2 *q_ent;
   const int32_t *q_cnt;
   ASL_TRY(query_entries(ix, rq, own_ent, &q_ent, &q_cnt));

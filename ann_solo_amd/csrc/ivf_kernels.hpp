@@ -138,5 +138,27 @@ int inv_order(int64_t nblocks, int d, const uint32_t *blk_base, const uint32_t *
 int count_nnz(const float *vecs, int d, int64_t n, int32_t *nnz, int32_t *nnz_max_dev);
 int scanned_count(const int32_t *coarse_I, int64_t n, const int32_t *list_offsets,
                   unsigned long long *out_dev);
+// rank of a target vector in the scans' (score desc, id asc) order (rank_scan.hip; asl_index_rank)
+struct RankWindow {                 // the scope's precursor window; key_slot == nullptr: none
+  const float *key_slot = nullptr;  // the key column by storage slot (rank_slot_keys)
+  const double *q_pmz = nullptr;    // per query
+  double tol = 0.0;
+  int mode = 0, charge = 0;
+};
+int rank_invert(const int32_t *slot_ids, int64_t nslots, int64_t ntotal, int32_t *inv);
+int rank_slot_keys(const int32_t *slot_ids, int64_t nslots, const float *key, int64_t ntotal, float *key_slot);
+// tkey [nq] (0: the target is not in scope) / tscore [nq] are written, counts [nq][2] (rank, scope) added to
+int rank_flat(const float *xq, int nq, int d, int nlist, int64_t ntotal, const int32_t *coarse_I, int nprobe,
+              const int32_t *list_offsets, const int32_t *blk_offsets, const uint32_t *blk_base,
+              const uint32_t *seg_tab, const char *seg_bytes, const int32_t *ids, const int64_t *target,
+              const int32_t *inv, const RankWindow &win, unsigned long long *tkey, float *tscore,
+              unsigned long long *counts, int want_scope);
+int rank_pq(const float *xq, int nq, int d, const float *cbT, int dsub, int nlist, int64_t ntotal,
+            const float *coarse_D, const int32_t *coarse_I, int nprobe, const float *coarse_all,
+            const int32_t *list_offsets, const int32_t *tile_offsets, const uint8_t *codes_tiled,
+            const int32_t *ids_tiled, const int64_t *target, const int32_t *inv, const RankWindow &win,
+            unsigned long long *tkey, float *tscore, unsigned long long *counts, int want_scope);
+int rank_finish(const unsigned long long *tkey, const float *tscore, const unsigned long long *counts, int nq,
+                int64_t *rank, float *score, int64_t *scope);
 
 }  // namespace asl

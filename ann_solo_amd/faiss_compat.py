@@ -141,6 +141,46 @@ class Index:
                                                       int(self.nprobe), _lib.ptr(D), _lib.ptr(I)))
         return D, I
 
+    def rank_of(self, x, target, nprobe=None, window=None):
+        """Where library vector ``target[i]`` stands in the neighbour order of query ``x[i]``
+        (``asl_index_rank``): ``(rank, score, scope)``, int64 / float32 / int64 [nq]. ``rank`` counts the
+        vectors of the scope that come before the target in (score desc, id asc) order, scores being the
+        bits of this index's own scan -- so ``search(x, k)`` holds the target for every k > rank and for
+        no k <= rank; -1: the target is not in the scope (``score`` is NaN there). ``scope``: the number
+        of vectors in the scope. ``nprobe``: None = ``self.nprobe``, 0 = every list (exhaustive: the
+        order of the reference's IndexFlatIP measurement, at any library size). ``window``: None, or
+        ``(key, precursor_mz, charge, tol, mode)`` -- ``key`` float32 per vector id, the rest as in
+        ``search_window`` -- restricts the scope to the vectors whose key passes each query's precursor
+        window. IVF-Flat with float postings and the tiled IVF-PQ only. numpy in -> numpy out; torch
+        device tensors stay in HBM."""
+        x = _as_f32(x, self.d)
+        nq = x.shape[0]
+        on_host = isinstance(x, np.ndarray)
+        if on_host:
+            target = np.ascontiguousarray(target, np.int64)
+            rank, score, scope = np.empty(nq, np.int64), np.empty(nq, np.float32), np.empty(nq, np.int64)
+        else:
+            import torch
+            target = torch.as_tensor(target, dtype=torch.int64, device=x.device).contiguous()
+            rank = torch.empty(nq, dtype=torch.int64, device=x.device)
+            score = torch.empty(nq, dtype=torch.float32, device=x.device)
+            scope = torch.empty(nq, dtype=torch.int64, device=x.device)
+        if target.shape != (nq,):
+            raise ValueError('rank_of: one target per query')
+        key = pmz = None
+        charge, tol, mode = 0, 0.0, 'Da'
+        if window is not None:
+            key, pmz, charge, tol, mode = window
+            key = key.float().contiguous() if hasattr(key, 'data_ptr') else np.ascontiguousarray(key, np.float32)
+            pmz = pmz.double().contiguous() if hasattr(pmz, 'data_ptr') else np.ascontiguousarray(pmz, np.float64)
+            if key.shape != (self.ntotal,) or pmz.shape != (nq,):
+                raise ValueError('rank_of: the window needs one key per vector id and one precursor m/z per query')
+        nprobe = self.nprobe if nprobe is None else nprobe
+        _lib.check(_lib.lib().asl_index_rank(self._h, nq, _lib.ptr(x), _lib.ptr(target), int(nprobe), _lib.ptr(key),
+                                             _lib.ptr(pmz), int(charge), float(tol), {'Da': 0, 'ppm': 1}[mode],
+                                             _lib.ptr(rank), _lib.ptr(score), _lib.ptr(scope)))
+        return rank, score, scope
+
     def set_window_scan(self, on: bool):
         """True: ``asl_search_batch`` scans each query's precursor window only (``Config.ann_window =
         'pre'``); False (default): the reference's post-filter."""

@@ -575,6 +575,35 @@ class SpectralLibrary:
             lists = [np.intersect1d(l, I[i][I[i] >= 0]) for i, l in enumerate(lists)]
         return lists
 
+    def candidate_rank(self, queries: PackedSpectra, charge: int, rows, nprobe: Optional[int] = None,
+                       window: bool = False):
+        """Where library row ``rows[i]`` of the charge partition stands in the ANN index's neighbour
+        order for query i (``faiss_compat.Index.rank_of``): ``(rank, score, scope)`` as numpy arrays.
+        The query is retrieved by the open search for every ``num_candidates > rank`` and for no
+        smaller one; -1: it never is (its list is not probed, or -- ``window=True`` -- it fails the
+        open-level precursor window). ``nprobe``: None = the configured ``num_probe``, 0 = every list.
+        ``window=False`` ranks over the probed lists as the post-filter search does (``ann_window =
+        'post'``: the needed k); ``window=True`` over their in-window vectors only (``'pre'``), with
+        the partition's precursor column as the key. This is the measurement the reference's
+        notebooks/iprg2012_num_candidates.ipynb makes with ``num_neighbors = 1000000``."""
+        if charge not in self.partitions:
+            return None
+        if getattr(self, '_dist', None) is not None and self._dist.world > 1:
+            raise ValueError('candidate_rank: does not run on a sharded index')
+        part = self.partitions[charge]
+        idx = self._get_ann_index(charge)
+        q = queries.to(self.device).contiguous()
+        rows = torch.as_tensor(np.asarray(rows, np.int64), device=self.device)
+        win = None
+        if window:
+            tol_val, tol_mode = self._tolerance('open')
+            if tol_mode not in ('Da', 'ppm'):
+                raise ValueError('Unknown precursor tolerance mode')
+            win = (torch.as_tensor(part.precursor_mz, device=self.device), q.precursor_mz.double(), charge,
+                   float(tol_val), tol_mode)
+        rank, score, scope = idx.rank_of(self._encode(q), rows, self._num_probe if nprobe is None else nprobe, win)
+        return rank.cpu().numpy(), score.cpu().numpy(), scope.cpu().numpy()
+
     def search_charge_batches(self, query_spectra: Dict[int, PackedSpectra], mode: str
                               ) -> Iterator[Tuple[int, int, int, np.ndarray, float]]:
         """One cascade level over per-charge query sets, batched like

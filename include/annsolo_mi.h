@@ -181,6 +181,26 @@ int asl_index_search_window(asl_index_t *idx, int32_t nq, const float *xq, const
  * whenever the layout holds another library's key or the lists changed). Per handle. */
 int asl_index_set_window_scan(asl_index_t *idx, int32_t on);
 
+/* Rank of a given vector in the index's neighbour order (replaces the measurement of the reference's
+ * notebooks/iprg2012_num_candidates.ipynb, the cell that searches IndexFlatIP with num_neighbors =
+ * 1000000 and looks up where the brute-force match stands): rank[i] = the number of vectors v of the
+ * scope with key(score(q_i, v), v) > key(score(q_i, t), t), t = target[i], key = (score desc, id asc),
+ * scores being the bits the index's own scan produces. The scope is the vectors of the probed lists
+ * -- nprobe = 0: of every list (exhaustive), else of the coarse quantiser's top-nprobe, the lists
+ * asl_index_search scans -- and, with key != NULL (float32 per vector id, [ntotal]), of those only the
+ * ones that pass precursor_ok(q_pmz[i], key[v], charge, tol, mode), as asl_index_search_window keeps
+ * them. rank[i] = -1 when the target is not in the scope (target < 0 or >= ntotal, its list not
+ * probed, its key NaN or outside the window). So with the same probes and window the target is in the
+ * rows of a search for every k > rank and for no k <= rank. score (optional): the target's score, NaN
+ * where rank is -1; scope (optional): the number of vectors in the scope. Nothing is kept on the
+ * handle. IVF-Flat with float postings and the tiled IVF-PQ (m = 32, 8 bits) only; ASL_ERR_STATE for
+ * fixed-point postings, dense-row IVF-Flat, the generic kernels (scan_variant 1, other PQ shapes), a
+ * Flat index and a sharded one. */
+int asl_index_rank(asl_index_t *idx, int32_t nq, const float *xq, const int64_t *target /* [nq] */,
+                   int32_t nprobe /* 0: all lists */, const float *key /* [ntotal] or NULL: no window */,
+                   const double *q_pmz, int32_t charge, double tol, int32_t mode, int64_t *rank /* [nq] */,
+                   float *score /* [nq], optional */, int64_t *scope /* [nq], optional */);
+
 /* IVF-Flat component storage. ASL_FLAT_F32 (the default since round 5) keeps every component as
  * given: the float32 vectors FAISS' CPU IndexIVFFlat stores (spectral_library.py:174-181) -- ids
  * and scores are those of an index over the unquantised vectors. ASL_FLAT_FX22 (opt-in; no FAISS
