@@ -450,6 +450,38 @@ enum { RS_QD_PAIR = 1, RS_QD_BS = 2 };   // q_defer bits: the query has slots ma
                                          // bits 2.. count the RS_DEFER slots (work split of the second launch)
 constexpr int RS_DEF_Y = 8;             // blocks per query the second launch may use
 
+// The bin filter's numeric envelope. The fast kernels compute the bin of a shifted candidate peak
+// in fp32, b = floorf(fl(fl(cm + fl(md)) * fl(inv_w))) with inv_w = 1 / (2 tol), where the exact
+// window test is done on x = cm + md in fp64. With u = 2^-24 (round to nearest, fp32) the three
+// roundings are
+//   fl(md)          = md + e1,                  |e1| <= u |md|        ((float)md)
+//   fl(cm + fl(md)) = (x + e1) (1 + d2),        |d2| <= u             (the fp32 sum)
+//   the product     = ... * inv_w (1 + d3) (1 + d4), |d3|, |d4| <= u  ((float)inv_w, the fp32 product)
+// so, in bins, |b_fp32 - x inv_w| <= inv_w (u |md| + 3 u |x|) (1 + 3 u). A peak that matches query
+// peak qm has |x| <= |qm| + tol, and |md| = |pmd / s| <= |pmd|: filing every query peak under the
+// bins of [qm - tol, qm + tol] widened by
+//   margin = 1e-3 + (0.5 / tol) * 6.0e-8 * (RS_MD_ENV + 3 (max|qm| + tol))          (6.0e-8 > u (1 + 3 u))
+// on both sides covers every candidate with |pmd| <= RS_MD_ENV (the 1e-3 takes the fp64 rounding of
+// the filing itself and fp32 underflow near zero). The accepted envelope is therefore
+//   * per candidate: |pmd| <= RS_MD_ENV (4096: an open-search window of +-500 Da at any charge
+//     the kernels take fits eight times), beyond it the candidate is marked RS_DEFER_BS;
+//   * per query: margin <= RS_MARGIN_MAX with max|qm| its own largest peak (peaks ascend: the first
+//     or the last), so that a peak still files under <= 3 bins (1 + 2 * 0.45 < 2 bin widths); beyond
+//     it the whole query goes to the binary-search kernel, which has no filter. At m/z 2000 that is
+//     tol >= 6.8e-4, at 20 000 tol >= 4.3e-3, at 100 000 tol >= 2.04e-2.
+// Nothing is scored through a filter whose margin does not cover it; inside the envelope the
+// bins, and so the exact test's inputs, are the same whatever the margin.
+// (The kernels take the margin from the query's peaks once they are in LDS: two loads from memory
+// in front of the peak load, to decide first, were a dependent round trip per workgroup and cost the
+// rescoring stage 0.08 ms of 2.1 at 32 768 queries -- profiles/rescore_envelope_ab.txt.)
+constexpr double RS_MD_ENV = 4096.0;
+constexpr double RS_MARGIN_MAX = 0.45;
+__device__ __forceinline__ double rs_bin_margin(float q_first, float q_last, double tol) {
+  if (!(tol > 0.0)) return 1.0;
+  const double q_abs = (double)fmaxf(fabsf(q_first), fabsf(q_last));
+  return 1e-3 + (0.5 / tol) * 6.0e-8 * (RS_MD_ENV + 3.0 * (q_abs + tol));
+}
+
 struct QueryLds2 {   // hash path: at most RS_HQ_MAX query peaks
   float mz[128];
   float inten[128];
@@ -613,7 +645,7 @@ __device__ __forceinline__ void score_two(int lane, const QueryLds2 &Q, const Ha
     for (int s = 0; s < Smax; ++s) {        // wave-uniform
       const double md = Wv.mdt[half * 32 + s];
       // bin of the shifted peak in fp32 (the query was filed with a margin that covers the
-      // fp32 rounding); bitmap reject first, the exact fp64 window test on the rare hits
+      // fp32 rounding: rs_bin_margin); bitmap reject first, the exact fp64 window test on the rare hits
       const bool can = (smask >> s) & 1u;
       const int b = (int)floorf((cm + (float)md) * inv_w_f);
       const bool maybe = can && bm_test(H, b);
@@ -738,15 +770,17 @@ __global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel
   const int qo = Qs.offsets[q];
   const int qn = Qs.offsets[q + 1] - qo;
   const double q_pmz = Qs.precursor_mz[q];
-  // fp32 evaluation of a probe bin (m/z <= ~2600): error bound in bin units; the query
+  // fp32 evaluation of a probe bin: its error bound in bin units (rs_bin_margin); the query
   // peaks are filed with that margin on both sides (still <= 3 bins per peak)
-  const double margin = 1e-3 + (tol > 0.0 ? (0.5 / tol) * (3.75e-4 + 2600.0 * 1.2e-7) : 1.0);
-  if (!(tol > 0.0) || qn > RS_HQ_MAX || margin > 0.45) {   // uniform: whole query deferred
+  auto defer_query = [&]() {      // uniform: the whole query goes to the binary-search kernel
     for (long long c = c0 + (long long)blockIdx.y * blockDim.x + tid; c < c1;
          c += (long long)blockDim.x * gridDim.y) {
       pair_score[c] = cv.cand(q, c, q_pmz, L.n) >= 0 ? RS_DEFER_BS : -1.0;
     }
     if (tid == 0) atomicOr(&q_defer[q], RS_QD_BS);
+  };
+  if (!(tol > 0.0) || qn > RS_HQ_MAX) {
+    defer_query();
     return;
   }
   for (int i = tid; i < qn; i += blockDim.x) {   // qn <= RS_HQ_MAX here
@@ -757,6 +791,13 @@ __global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel
   for (int i = tid; i < RS_BM_BITS / 32; i += blockDim.x) H.bm[i] = 0u;
   if (tid == 0) s_defer = 0;
   __syncthreads();
+  // the margin of this query's own m/z range, from the peaks just loaded (no extra trip to memory
+  // in front of the load); beyond RS_MARGIN_MAX the query leaves the hash path (uniform)
+  const double margin = qn > 0 ? rs_bin_margin(Q.mz[0], Q.mz[qn - 1], tol) : 0.0;
+  if (!(margin <= RS_MARGIN_MAX)) {
+    defer_query();
+    return;
+  }
   const double inv_w = 1.0 / (2.0 * tol);
   if (tid < qn) {
     const double qm = (double)Q.mz[tid];
@@ -833,6 +874,8 @@ __global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel
           m_pmz = L.precursor_mz[row];
         }
       }
+      // a shifted candidate beyond the bin filter's envelope (RS_MD_ENV) is not scored here
+      const int m_far = (allow_shift && !(fabs((q_pmz - m_pmz) * (double)(unsigned)m_chg) <= RS_MD_ENV)) ? 1 : 0;
       double my_score = 0.0;
       const int cnt = we - base < 64 ? we - base : 64;
       // Bursts of RS_PF candidates: all their peak loads are issued back to back (straight
@@ -863,7 +906,8 @@ __global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel
           const bool vA = lA < cnt, vB = lB < cnt;   // wave-uniform
           const int cnA = vA ? rl_i(m_cn, lA) : 0, cnB = vB ? rl_i(m_cn, lB) : 0;
           const int chA = vA ? rl_i(m_chg, lA) : 0, chB = vB ? rl_i(m_chg, lB) : 0;
-          const bool defA = cnA > 64 || chA >= 31, defB = cnB > 64 || chB >= 31;
+          const bool defA = cnA > 64 || chA >= 31 || (vA && rl_i(m_far, lA));
+          const bool defB = cnB > 64 || chB >= 31 || (vB && rl_i(m_far, lB));
           const bool runA = vA && !defA && cnA > 0 && qn > 0;
           const bool runB = vB && !defB && cnB > 0 && qn > 0;
           double sA = 0.0, sB = 0.0;
@@ -984,13 +1028,15 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
     return cv.cand(q, c, q_pmz, L.n) >= 0;
   };
   // (same bin filter as the pair kernel: see there)
-  const double margin = 1e-3 + (tol > 0.0 ? (0.5 / tol) * (3.75e-4 + 2600.0 * 1.2e-7) : 1.0);
-  if (!(tol > 0.0) || qn > RS_HQ_MAX || margin > 0.45) {   // uniform: whole query deferred
+  auto defer_query = [&]() {      // uniform: the whole query goes to the binary-search kernel
     for (long long c = c0 + (long long)blockIdx.y * blockDim.x + tid; c < c1;
          c += (long long)blockDim.x * gridDim.y) {
       pair_score[c] = is_cand(c) ? RS_DEFER_BS : -1.0;
     }
     if (tid == 0) atomicOr(&q_defer[q], RS_QD_BS);
+  };
+  if (!(tol > 0.0) || qn > RS_HQ_MAX) {
+    defer_query();
     return;
   }
   for (int i = tid; i < qn; i += blockDim.x) {
@@ -1001,6 +1047,13 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
   for (int i = tid; i < RS_BM_BITS / 32; i += blockDim.x) H.bm[i] = 0u;
   if (tid == 0) s_defer = s_ndef = 0;
   __syncthreads();
+  // the margin of this query's own m/z range, from the peaks just loaded (no extra trip to memory
+  // in front of the load); beyond RS_MARGIN_MAX the query leaves the hash path (uniform)
+  const double margin = qn > 0 ? rs_bin_margin(Q.mz[0], Q.mz[qn - 1], tol) : 0.0;
+  if (!(margin <= RS_MARGIN_MAX)) {
+    defer_query();
+    return;
+  }
   const double inv_w = 1.0 / (2.0 * tol);
   if (tid < qn) {
     const double qm = (double)Q.mz[tid];
@@ -1076,7 +1129,8 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
       }
       const double pmd = (q_pmz - m_pmz) * (double)(unsigned)m_chg;            // cpp:18
       const int S = (allow_shift && fabs(pmd) >= tol) ? m_chg + 1 : 1;          // cpp:20
-      const bool def_bs = okr && (m_cn > 64 || m_chg >= 31);
+      // (a shift beyond the bin filter's envelope: RS_MD_ENV)
+      const bool def_bs = okr && (m_cn > 64 || m_chg >= 31 || (S > 1 && !(fabs(pmd) <= RS_MD_ENV)));
       const bool def_pair = okr && !def_bs && S > RF_SMAX;
       const int cn_eff = (okr && !def_bs && !def_pair && qn > 0) ? m_cn : 0;
       // prefix sums over the 32 candidates: both halves of the wave hold the same values, so the
