@@ -79,6 +79,8 @@ EXPORTS = [
     'asl_index_set_window_key', 'asl_index_search_window', 'asl_index_set_window_scan',
     'asl_rescore_batch_topn', 'asl_search_batch_topn', 'asl_rescore_knn_topn',
     'asl_index_rank',
+    'asl_library_set_groups', 'asl_rescore_batch_topn_distinct', 'asl_search_batch_topn_distinct',
+    'asl_rescore_knn_topn_distinct',
 ]
 
 
@@ -249,6 +251,15 @@ def lib():
                                            C.POINTER(AslSearchParams), C.c_void_p, C.c_int32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int32]
+        # (an ASL_LIB_PATH build from before these exports still loads, for A/B runs of the calls it
+        # has; calling a missing one raises AttributeError)
+        if hasattr(L, 'asl_library_set_groups'):
+            L.asl_library_set_groups.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+            L.asl_rescore_batch_topn_distinct.argtypes = [C.POINTER(AslPeaks), C.POINTER(AslPeaks), C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int32,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+            L.asl_search_batch_topn_distinct.argtypes = L.asl_search_batch_topn.argtypes
+            L.asl_rescore_knn_topn_distinct.argtypes = L.asl_rescore_knn_topn.argtypes
         L.asl_lpt_owner.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         L.asl_window_candidates.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                             C.c_double, C.c_int32, C.c_void_p, C.c_void_p]

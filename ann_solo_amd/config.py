@@ -3,7 +3,7 @@
 ``Config`` carries the reference's flags under the reference's names
 (/root/reference/src/ann_solo/config.py:62-216) plus the ADDITIVE flags of this implementation
 (``index``, ``pq_m``, ``pq_bits``, ``refine_k``, ``kmeans_niter``, ``ann_seed``, ``num_gpus``,
-``flat_storage``, ``ann_window``, ``num_matches``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -83,6 +83,9 @@ class Config:
     num_matches: int = 1                    # library matches reported per query: 1 (the reference: the best
                                             # match) .. 16; > 1 adds the runners-up and the score gap to the
                                             # SSMs (top-n rescoring), identifications and FDR stay rank 0's
+    distinct_matches: bool = False          # num_matches > 1: the runners-up are the best matches of OTHER
+                                            # peptides (one rank per peptide; the score gap is the gap to the
+                                            # next different identification), not other spectra of the winner's
 
     MAX_PEAKS = 256      # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
@@ -115,6 +118,8 @@ class Config:
             raise ValueError(f'num_matches = {self.num_matches}: 1 .. {self.MAX_MATCHES}')
         if int(self.num_matches) > 1 and self.num_gpus and int(self.num_gpus) > 1:
             raise ValueError('num_matches > 1 does not run on a sharded index (num_gpus > 1)')
+        if self.distinct_matches and self.num_gpus and int(self.num_gpus) > 1:
+            raise ValueError('distinct_matches does not run on a sharded index (num_gpus > 1)')
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -208,3 +213,8 @@ def add_arguments(parser) -> None:
                              'SSM also carries its runners-up and the score gap to the second best; '
                              'identifications, scores and FDR are those of the best match; one GPU '
                              '(default: %(default)s)')
+    parser.add_argument('--distinct_matches', action='store_true', default=d.distinct_matches,
+                        help='with --num_matches above 1: one rank per library peptide -- the '
+                             "runners-up are the best matches of other peptides and the score gap is "
+                             'the gap to the next different identification; one GPU '
+                             '(default: every library spectrum is a rank of its own)')

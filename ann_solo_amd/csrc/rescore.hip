@@ -22,6 +22,8 @@
 // emit its peak_matches in greedy order.
 // Top-n (asl_*_topn, n_best > 0 in rescore_device): Pass 2 is rescore_topn_kernel, the n best slots
 // per query in one pass over the scores; Pass 3 rescore_matches_topn_kernel over nq * n winners.
+// Distinct top-n (asl_*_topn_distinct, a group id per library row): Pass 2 is
+// rescore_topn_distinct_kernel, the n best slots of n different groups.
 //
 // Arithmetic mirrors the reference: window tests in double on float->double
 // promoted m/z (cpp:42,53); product = (float)(mult * (double)q_int * (double)c_int)
@@ -1449,6 +1451,19 @@ __global__ __launch_bounds__(64) void rescore_topn_kernel(
   if (lane == 0 && n_valid) n_valid[q] = cnt;
 }
 
+// (rescore_topn_distinct_kernel, the selection of the distinct ranked matches, and
+// window_merge_topn_distinct_kernel, their fold, are defined behind the drivers below: the kernels
+// above and below this line keep their places in the code object)
+__global__ void rescore_topn_distinct_kernel(CandView cv, int nq, int n, const double *__restrict__ pair_score,
+                                             int tie_by_row, const int32_t *__restrict__ group, int n_lib,
+                                             int32_t *__restrict__ best_cand, long long *__restrict__ best_slot,
+                                             double *__restrict__ best_score, int32_t *__restrict__ n_valid);
+__global__ void window_merge_topn_distinct_kernel(CandView cv, int nq, int n, const long long *__restrict__ best_slot,
+                                                  const double *__restrict__ best_score,
+                                                  const int32_t *__restrict__ n_valid,
+                                                  const int32_t *__restrict__ group, double *__restrict__ run_score,
+                                                  int32_t *__restrict__ run_row, int32_t *__restrict__ run_n);
+
 // One wave per query, and a wave is a chain of dependent memory round trips (winner's slot -> its
 // row -> its peaks) around little arithmetic: the kernel lives on the number of waves in flight,
 // i.e. on the LDS a wave needs. SMALL: structures for spectra of <= 128 peaks and <= 128
@@ -1579,11 +1594,13 @@ int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
                    int32_t *best_row, double *best_score, int32_t *n_valid,
                    int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride, int *status,
                    const PrecFilter &filter, bool clear_status, RescoreScratch *scratch,
-                   const int32_t *row_counts, const WindowRows *window, bool emit_matches, int n_best) {
+                   const int32_t *row_counts, const WindowRows *window, bool emit_matches, int n_best,
+                   const int32_t *group) {
   const int nq = Q.n;
   if (nq == 0) return ASL_OK;
   if (!scratch) return fail(ASL_ERR_INVALID, "rescore: no scratch (internal)");
   if (n_best < 0 || n_best > ASL_MAX_BEST) return fail(ASL_ERR_INVALID, "rescore: n_best (internal)");
+  if (group && n_best == 0) return fail(ASL_ERR_INVALID, "rescore: groups without n_best (internal)");
   if (window && (!cand_offsets || rows64 || rows32 || !window->begin || !window->sorted_row ||
                  !filter.meta || !L.charge || !L.records))
     return fail(ASL_ERR_INVALID, "rescore: window lists need CSR offsets and packed rows (internal)");
@@ -1631,7 +1648,11 @@ int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
                          (const int *)q_defer.p, status, bs_group);
     }
     ASL_CHECK_LAUNCH();
-    if (n_best > 0)
+    if (group)
+      hipLaunchKernelGGL(rescore_topn_distinct_kernel, dim3(nq), dim3(64), (size_t)n_best * 64 * 20 + 64, stream(),
+                         cv, nq, n_best, pair_score, tie_by_row, group, (int)L.n, best_cand, best_slot, best_score,
+                         n_valid);
+    else if (n_best > 0)
       hipLaunchKernelGGL(rescore_topn_kernel, dim3(nq), dim3(64), (size_t)n_best * 64 * 16, stream(), cv, nq,
                          n_best, pair_score, tie_by_row, best_cand, best_slot, best_score, n_valid);
     else
@@ -1780,14 +1801,18 @@ __global__ __launch_bounds__(256) void window_finish_topn_kernel(
 
 int rescore_window_merge_topn(const WindowRows &window, const int32_t *cand_offsets, int nq, int n,
                               const long long *best_slot, const double *best_score, const int32_t *n_valid,
-                              double *run_score, int32_t *run_row, int32_t *run_n) {
+                              double *run_score, int32_t *run_row, int32_t *run_n, const int32_t *group) {
   if (nq <= 0) return ASL_OK;
   CandView cv{nullptr, nullptr, cand_offsets, 0, PrecFilter()};
   cv.win_begin = window.begin;
   cv.win_rows = window.sorted_row;
   cv.win_valid = window.valid;
-  hipLaunchKernelGGL(window_merge_topn_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(), cv, nq, n,
-                     best_slot, best_score, n_valid, run_score, run_row, run_n);
+  if (group)
+    hipLaunchKernelGGL(window_merge_topn_distinct_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(), cv,
+                       nq, n, best_slot, best_score, n_valid, group, run_score, run_row, run_n);
+  else
+    hipLaunchKernelGGL(window_merge_topn_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(), cv, nq, n,
+                       best_slot, best_score, n_valid, run_score, run_row, run_n);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }
@@ -1800,6 +1825,192 @@ int rescore_window_finish_topn(int nq, int n, const double *run_score, const int
                      stream(), nq, n, run_score, run_row, run_n, rescored, best_score, n_cand, status);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
+}
+
+// Distinct top-n selection (asl_*_topn_distinct): the ranking above with one rule added -- walking
+// the slots in that order, a slot is skipped when an earlier rank holds a row of the same group
+// (group[row], 32 bits per library row; a negative id is "ungrouped" and collides with nothing, not
+// even with itself listed twice). The same single pass: every lane keeps the best n of its slots
+// WITH DISTINCT GROUPS (a fourth LDS plane [n][64] of group ids). A slot whose group the lane holds
+// replaces that entry if it beats it and is dropped otherwise; a slot with a new group is inserted
+// as above. The `s < ts` cut stands: a lane that holds n groups, all ahead of the slot, has no use
+// for it whatever its group -- so group[row] is gathered only for the slots that pass the cut.
+// Merge: n rounds of the wave arg-max over the lanes' heads; the winner's group (wave-uniform, at
+// most n of them) goes to a 16-entry LDS line, and every lane moves its head past entries whose
+// group is on that line.
+// Exact: an element of the answer is the best of its group among all slots, hence in its lane, and
+// the groups ahead of it in its lane are ahead of it in the answer too, fewer than n: the lane kept
+// it. In the merge the best slot of a group not yet emitted is its lane's first entry off the line
+// (everything ahead of it in the lane beats it and would otherwise be that best slot), so it is
+// the arg-max of the heads. Rank 0 is the plain winner; with every group negative nothing ever
+// collides and the outputs are the plain kernel's byte for byte.
+// Dynamic LDS: n * 64 * 20 + 64 bytes (20 KB at n = 16).
+__global__ __launch_bounds__(64) void rescore_topn_distinct_kernel(
+    CandView cv, int nq, int n, const double *__restrict__ pair_score, int tie_by_row,
+    const int32_t *__restrict__ group, int n_lib, int32_t *__restrict__ best_cand, long long *__restrict__ best_slot,
+    double *__restrict__ best_score, int32_t *__restrict__ n_valid) {
+  extern __shared__ __attribute__((aligned(16))) double topn_lds[];
+  double *S = topn_lds;                                      // [n][64] scores
+  int32_t *K = reinterpret_cast<int32_t *>(S + n * 64);      // [n][64] tie keys
+  int32_t *P = K + n * 64;                                   // [n][64] positions
+  int32_t *G = P + n * 64;                                   // [n][64] group ids
+  int32_t *E = G + n * 64;                                   // [16] groups emitted so far (merge)
+  const int q = blockIdx.x;
+  const int lane = threadIdx.x;
+  long long c0, c1;
+  cv.range(q, c0, c1);
+  int have = 0, cnt = 0;
+  double ts = -1.0;          // the lane's n-th entry once it holds n
+  int32_t tk = 0, tp = 0;
+  for (long long c = c0 + lane; c < c1; c += 64) {
+    const double s = pair_score[c];
+    if (s < 0.0) continue;
+    ++cnt;
+    if (have == n && s < ts) continue;
+    const int32_t pos = (int32_t)(c - c0);
+    const int32_t row = (int32_t)cv.row(q, c);       // (a scored slot: a row of the library)
+    const int32_t key = tie_by_row ? row : pos;
+    if (have == n && s == ts && !(key < tk || (key == tk && pos < tp))) continue;
+    const int32_t g = (uint32_t)row < (uint32_t)n_lib ? group[row] : -1;
+    int i = have < n ? have : n - 1;                 // a new group: from the end, the n-th falls out
+    bool held = false;
+    if (g >= 0) {
+      for (int j = 0; j < have; ++j) {
+        if (G[j * 64 + lane] == g) {
+          i = j;                                     // the group's entry: replaced in place or kept
+          held = true;
+          break;
+        }
+      }
+    }
+    if (held) {
+      const double ps = S[i * 64 + lane];
+      const int32_t pk = K[i * 64 + lane], pp = P[i * 64 + lane];
+      if (!(s > ps || (s == ps && (key < pk || (key == pk && pos < pp))))) continue;
+    }
+    while (i > 0) {
+      const double ps = S[(i - 1) * 64 + lane];
+      const int32_t pk = K[(i - 1) * 64 + lane], pp = P[(i - 1) * 64 + lane];
+      if (!(s > ps || (s == ps && (key < pk || (key == pk && pos < pp))))) break;
+      S[i * 64 + lane] = ps;
+      K[i * 64 + lane] = pk;
+      P[i * 64 + lane] = pp;
+      G[i * 64 + lane] = G[(i - 1) * 64 + lane];
+      --i;
+    }
+    S[i * 64 + lane] = s;
+    K[i * 64 + lane] = key;
+    P[i * 64 + lane] = pos;
+    G[i * 64 + lane] = g;
+    if (!held && have < n) ++have;
+    if (have == n) {
+      ts = S[(n - 1) * 64 + lane];
+      tk = K[(n - 1) * 64 + lane];
+      tp = P[(n - 1) * 64 + lane];
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+  int head = 0, ne = 0;      // ne: groups on the line (wave-uniform)
+  for (int r = 0; r < n; ++r) {
+    const bool live = head < have;
+    const double ms = live ? S[head * 64 + lane] : -1.0;
+    const int32_t mk = live ? K[head * 64 + lane] : 0x7fffffff;
+    const int32_t mp = live ? P[head * 64 + lane] : 0x7fffffff;
+    double bs = ms;
+    int32_t bk = mk, bp = mp;
+    for (int off = 32; off > 0; off >>= 1) {
+      const double os = __shfl_xor(bs, off);
+      const int32_t ok = __shfl_xor(bk, off), op = __shfl_xor(bp, off);
+      if (os > bs || (os == bs && (ok < bk || (ok == bk && op < bp)))) {
+        bs = os;
+        bk = ok;
+        bp = op;
+      }
+    }
+    const bool any = bs >= 0.0;               // wave-uniform: positions are unique, the order is total
+    if (lane == 0) {
+      const size_t o = (size_t)q * n + r;
+      if (best_cand) best_cand[o] = any ? bp : -1;
+      if (best_slot) best_slot[o] = any ? c0 + bp : -1;
+      if (best_score) best_score[o] = any ? bs : 0.0;
+    }
+    if (!any) continue;                       // (every later round is empty too)
+    const bool mine = live && mp == bp;       // the lane that held the winner
+    const unsigned long long who = __ballot(mine);
+    const int32_t wg = __shfl(live ? G[head * 64 + lane] : -1, __builtin_ctzll(who));
+    if (mine) ++head;
+    if (wg >= 0) {
+      if (lane == 0) E[ne] = wg;
+      ++ne;
+      wave_sync();
+    }
+    while (head < have) {                     // past the entries whose group has a rank already
+      const int32_t hg = G[head * 64 + lane];
+      bool out = false;
+      if (hg >= 0)
+        for (int e = 0; e < ne; ++e) out = out || E[e] == hg;
+      if (!out) break;
+      ++head;
+    }
+  }
+  if (lane == 0 && n_valid) n_valid[q] = cnt;
+}
+
+// The distinct fold (asl_search_batch_topn_distinct): both lists are sorted and hold one row per
+// group (rescore_topn_distinct_kernel; the running list by induction), over disjoint rows. They are
+// merged by (score descending, row ascending), an entry whose group the output already holds is
+// skipped, and n are kept: an element of the distinct top-n of the union is the best of its group in
+// its own list with fewer than n groups ahead of it there, so it is in that list's distinct top-n,
+// and the walk meets the two lists' entries in the order of the union. Skipping moves entries by
+// more than the in-place passes above allow: the result is built in a local array and written back.
+__global__ __launch_bounds__(256) void window_merge_topn_distinct_kernel(
+    CandView cv, int nq, int n, const long long *__restrict__ best_slot, const double *__restrict__ best_score,
+    const int32_t *__restrict__ n_valid, const int32_t *__restrict__ group, double *__restrict__ run_score,
+    int32_t *__restrict__ run_row, int32_t *__restrict__ run_n) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  run_n[q] += n_valid[q];
+  const long long *ts = best_slot + (size_t)q * n;
+  const double *tsc = best_score + (size_t)q * n;
+  double *rs = run_score + (size_t)q * n;
+  int32_t *rr = run_row + (size_t)q * n;
+  int la = 0, lb = 0;
+  while (la < n && rr[la] >= 0) ++la;
+  while (lb < n && ts[lb] >= 0) ++lb;
+  if (lb == 0) return;
+  double os[ASL_MAX_BEST];
+  int32_t orow[ASL_MAX_BEST], og[ASL_MAX_BEST];
+  int no = 0, ia = 0, ib = 0;
+  while (no < n && (ia < la || ib < lb)) {
+    double s;
+    int32_t r;
+    bool a = ib >= lb;
+    if (!a) {
+      s = tsc[ib];
+      r = (int32_t)cv.row(q, ts[ib]);
+      a = ia < la && (rs[ia] > s || (rs[ia] == s && rr[ia] < r));
+    }
+    if (a) {
+      s = rs[ia];
+      r = rr[ia];
+      ++ia;
+    } else {
+      ++ib;
+    }
+    const int32_t g = group[r];
+    bool dup = false;
+    if (g >= 0)
+      for (int k = 0; k < no; ++k) dup = dup || og[k] == g;
+    if (dup) continue;
+    os[no] = s;
+    orow[no] = r;
+    og[no] = g;
+    ++no;
+  }
+  for (int k = 0; k < no; ++k) {      // (no >= la: nothing of the running list is left behind)
+    rs[k] = os[k];
+    rr[k] = orow[k];
+  }
 }
 
 int rescore_status_error(int st) {
@@ -1823,11 +2034,13 @@ int rescore_check_status(const int *status_dev) {
 
 using namespace asl;
 
-// asl_rescore_batch (n_best = 0) and asl_rescore_batch_topn (outputs [nq, n_best])
+// asl_rescore_batch (n_best = 0), asl_rescore_batch_topn (outputs [nq, n_best]) and
+// asl_rescore_batch_topn_distinct (lib_group: [library->n] group ids, host or device; null: plain)
 static int rescore_batch_sync(const asl_peaks_t *queries, const asl_peaks_t *library,
                               const int64_t *cand_rows, const int32_t *cand_offsets, double tol,
                               int allow_shift, int n_best, int32_t *best_cand, double *best_score,
-                              int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride) {
+                              int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride,
+                              const int32_t *lib_group = nullptr) {
   if (!queries || !library) return fail(ASL_ERR_INVALID, "rescore_batch: null spectra");
   const int nq = queries->n;
   const size_t nw = (size_t)nq * (size_t)std::max(n_best, 1);
@@ -1852,6 +2065,8 @@ static int rescore_batch_sync(const asl_peaks_t *queries, const asl_peaks_t *lib
   if (total > 0 && !cand_rows) return fail(ASL_ERR_INVALID, "rescore_batch: null cand_rows");
   In<int64_t> rows;
   ASL_TRY(rows.init(cand_rows, (size_t)total));
+  In<int32_t> grp;
+  if (lib_group) ASL_TRY(grp.init(lib_group, (size_t)library->n));
   Out<int32_t> o_best, o_cnt;
   Out<double> o_score;
   Out<uint32_t> o_pairs;
@@ -1869,7 +2084,7 @@ static int rescore_batch_sync(const asl_peaks_t *queries, const asl_peaks_t *lib
   ASL_TRY(rescore_device(Q.dev, L.dev, rows.d, nullptr, off.d, 0, total, tol, allow_shift, 0,
                          pair_score.p, best_slot.p, o_best.d, nullptr, o_score.d, nullptr,
                          o_cnt.d, o_pairs.d, pm_stride, status.p, PrecFilter(), true, &scratch,
-                         nullptr, nullptr, true, n_best));
+                         nullptr, nullptr, true, n_best, lib_group ? grp.d : nullptr));
   ASL_TRY(o_best.finish());
   ASL_TRY(o_score.finish());
   ASL_TRY(o_cnt.finish());
@@ -1898,4 +2113,18 @@ extern "C" int asl_rescore_batch_topn(const asl_peaks_t *queries, const asl_peak
   ASL_TRY(ensure_device());     // (no device: ASL_ERR_NO_DEVICE whatever else was passed)
   return rescore_batch_sync(queries, library, cand_rows, cand_offsets, tol, allow_shift, n_best, best_cand,
                             best_score, pm_count, pm_pairs, pm_stride);
+}
+
+extern "C" int asl_rescore_batch_topn_distinct(const asl_peaks_t *queries, const asl_peaks_t *library,
+                                               const int64_t *cand_rows, const int32_t *cand_offsets,
+                                               const int32_t *lib_group, double tol, int allow_shift,
+                                               int32_t n_best, int32_t *best_cand, double *best_score,
+                                               int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride) {
+  clear_error();
+  if (n_best < 1 || n_best > ASL_MAX_BEST)
+    return fail(ASL_ERR_INVALID, "rescore_batch_topn_distinct: n_best must be in [1, %d]", ASL_MAX_BEST);
+  ASL_TRY(ensure_device());     // (no device: ASL_ERR_NO_DEVICE whatever else was passed)
+  if (!lib_group) return fail(ASL_ERR_INVALID, "rescore_batch_topn_distinct: null lib_group");
+  return rescore_batch_sync(queries, library, cand_rows, cand_offsets, tol, allow_shift, n_best, best_cand,
+                            best_score, pm_count, pm_pairs, pm_stride, lib_group);
 }

@@ -96,7 +96,10 @@ int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
                    // (rescore_topn_kernel instead of the argmax, the matches kernels over nq * n
                    // winners); best_slot / best_cand / best_row / best_score / pm_count are then
                    // [nq, n_best], pm_pairs [nq, n_best, pm_stride, 2], n_valid stays [nq]
-                   int n_best = 0);
+                   int n_best = 0,
+                   // n_best > 0, non-null (asl_*_topn_distinct): group id of every library row, [L.n]; the
+                   // ranks then hold distinct groups (rescore_topn_distinct_kernel). nullptr: plain ranks
+                   const int32_t *group = nullptr);
 // Tiled window search: folds one tile's argmax (rescore_device's best_slot / best_score / n_valid
 // over the tile's nq queries, slots of the same window lists) into the running best of those
 // queries: a higher score wins, equal scores go to the lower library row, counts add up.
@@ -112,10 +115,12 @@ int rescore_window_finish(int nq, const double *run_score, const int32_t *run_ro
                           int32_t *n_cand, int *status);
 // The same fold and finish for the n best (asl_search_batch_topn): the tile's best_slot / best_score
 // and the running run_score / run_row are [nq, n], sorted by (score descending, row ascending),
-// run_row -1 beyond the filled ranks; `rescored` is [nq, n].
+// run_row -1 beyond the filled ranks; `rescored` is [nq, n]. group (non-null: the distinct fold):
+// the library rows' group ids, both lists then hold one row per group and so does the result.
 int rescore_window_merge_topn(const WindowRows &window, const int32_t *cand_offsets, int nq, int n,
                               const long long *best_slot, const double *best_score, const int32_t *n_valid,
-                              double *run_score, int32_t *run_row, int32_t *run_n);
+                              double *run_score, int32_t *run_row, int32_t *run_n,
+                              const int32_t *group = nullptr);
 int rescore_window_finish_topn(int nq, int n, const double *run_score, const int32_t *run_row,
                                const int32_t *run_n, const double *rescored, double *best_score,
                                int32_t *n_cand, int *status);

@@ -80,6 +80,9 @@ struct asl_library {
   uint32_t slot = 0;         // bytes per row (a multiple of 128)
   DevBuf<float> wcol;     // window column alone, NaN for invalid spectra
   bool has_valid = false;
+  // group id per row (asl_library_set_groups; the *_topn_distinct calls rank one row per group)
+  DevBuf<int32_t> group;
+  bool has_group = false;
   DevPeaks dev;
   // precursor-sorted view (window search)
   DevBuf<float> sorted_pmz;
@@ -317,6 +320,26 @@ asl_library_t *asl_library_create(const asl_peaks_t *p, const float *lib_pmz_f32
 void asl_library_free(asl_library_t *L) { delete L; }
 int64_t asl_library_size(const asl_library_t *L) { return L ? L->n : 0; }
 
+int asl_library_set_groups(asl_library_t *L, int64_t n, const int32_t *group) {
+  clear_error();
+  if (!L) return fail(ASL_ERR_INVALID, "library_set_groups: null library");
+  if (!group) {
+    ASL_TRY(ensure_device());     // (batches in flight may still read the column)
+    L->group.release();
+    L->has_group = false;
+    return ASL_OK;
+  }
+  if (n != L->n)
+    return fail(ASL_ERR_INVALID, "library_set_groups: %lld group ids for a library of %lld rows", (long long)n,
+                (long long)L->n);
+  ASL_TRY(ensure_device());
+  ASL_TRY(L->group.reserve((size_t)std::max<int64_t>(n, 1)));   // (an empty library keeps a column too)
+  ASL_TRY(L->group.upload(group, (size_t)n));
+  ASL_TRY(sync_stream());         // a host array is the caller's again on return
+  L->has_group = true;
+  return ASL_OK;
+}
+
 // CSR window candidates on the device: fills L->woff ([nq+1]) and L->cand; total -> *total.
 static int window_candidates_device(asl_library *L, int nq, const double *q_pmz_dev, int charge,
                                     double tol, int mode, int64_t *total) {
@@ -360,8 +383,12 @@ static int window_candidates_device(asl_library *L, int nq, const double *q_pmz_
 // n-candidate list per query. n_best = 0 is the single-winner search, launch for launch.
 static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_search_params_t *P,
                                 int32_t *best_row, double *best_score, int32_t *n_cand,
-                                int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride, int n_best = 0) {
+                                int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride, int n_best = 0,
+                                bool distinct = false) {
   const int nq = Q.n;
+  // distinct (asl_search_batch_topn_distinct): every tile's ranks and the fold hold one row per group;
+  // the final pass over the n-candidate lists, already distinct, is the plain one
+  const int32_t *group = distinct ? L->group.p : nullptr;
   const size_t nw = (size_t)nq * (size_t)std::max(n_best, 1);     // winners of the batch
   std::vector<int32_t> h_lo((size_t)nq), h_cnt((size_t)nq);
   {
@@ -410,7 +437,7 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
     return rescore_device(Q, L->dev, nullptr, nullptr, L->wtile.p, 0, total, P->fragment_mz_tolerance,
                           P->allow_shift, 1, L->pair_score.p, L->best_slot.p, nullptr, best_row,
                           best_score, n_cand, pm_count, pm_pairs, pm_stride, L->status.p, rows_only,
-                          true, &L->rs_scratch, nullptr, &win, true, n_best);
+                          true, &L->rs_scratch, nullptr, &win, true, n_best, group);
   }
   // tiles [t0, t1) of the global pair range; queries qa..qb (the query of pair t0 .. that of t1-1)
   struct Tile {
@@ -457,11 +484,11 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
     ASL_TRY(rescore_device(Qt, L->dev, nullptr, nullptr, off, 0, T.pairs, P->fragment_mz_tolerance,
                            P->allow_shift, 1, L->pair_score.p, L->best_slot.p, nullptr, nullptr,
                            L->tile_score.p, L->tile_n.p, nullptr, nullptr, pm_stride, L->status.p,
-                           rows_only, false, &L->rs_scratch, nullptr, &win, false, n_best));
+                           rows_only, false, &L->rs_scratch, nullptr, &win, false, n_best, group));
     if (n_best > 0)
       ASL_TRY(rescore_window_merge_topn(win, off, T.nq, n_best, L->best_slot.p, L->tile_score.p, L->tile_n.p,
                                         L->run_score.p + (size_t)T.qa * n_best,
-                                        L->run_row.p + (size_t)T.qa * n_best, L->run_n.p + T.qa));
+                                        L->run_row.p + (size_t)T.qa * n_best, L->run_n.p + T.qa, group));
     else
       ASL_TRY(rescore_window_merge(win, off, T.nq, L->best_slot.p, L->tile_score.p, L->tile_n.p,
                                    L->run_score.p + T.qa, L->run_row.p + T.qa, L->run_n.p + T.qa));
@@ -521,8 +548,11 @@ int asl_window_candidates(asl_library_t *L, int32_t nq, const double *query_pmz,
 // asl_rescore_knn (n_best = 0) and asl_rescore_knn_topn (outputs [nq, n_best] except n_cand)
 static int rescore_knn_sync(asl_library_t *L, const asl_peaks_t *queries, const asl_search_params_t *P,
                             const int64_t *knn_I, int n_best, int32_t *best_row, double *best_score,
-                            int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride) {
+                            int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride,
+                            bool distinct = false) {
   if (!L || !queries || !P || !knn_I) return fail(ASL_ERR_INVALID, "rescore_knn: null argument");
+  if (distinct && !L->has_group)
+    return fail(ASL_ERR_STATE, "rescore_knn_topn_distinct: the library has no group column (asl_library_set_groups)");
   const int nq = queries->n, k = P->k;
   const size_t nw = (size_t)nq * (size_t)std::max(n_best, 1);
   if (nq == 0) return ASL_OK;
@@ -551,7 +581,7 @@ static int rescore_knn_sync(asl_library_t *L, const asl_peaks_t *queries, const 
                          P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p,
                          L->best_slot.p, nullptr, o_row.d, o_score.d, o_ncand.d, o_cnt.d,
                          o_pairs.d, pm_stride, L->status.p, flt, true, &L->rs_scratch, nullptr, nullptr,
-                         true, n_best));
+                         true, n_best, distinct ? L->group.p : nullptr));
   ASL_TRY(o_row.finish());
   ASL_TRY(o_score.finish());
   ASL_TRY(o_ncand.finish());
@@ -583,7 +613,7 @@ int asl_rescore_knn_topn(asl_library_t *L, const asl_peaks_t *queries, const asl
 static int search_batch_sync(asl_library_t *L, asl_index_t *idx, const asl_peaks_t *queries,
                              const asl_search_params_t *P, int n_best, int32_t *best_row, double *best_score,
                              int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride,
-                             int64_t *knn_I) {
+                             int64_t *knn_I, bool distinct = false) {
   const int nq = queries->n;
   const size_t nw = (size_t)nq * (size_t)std::max(n_best, 1);
   ASL_TRY(ensure_device());
@@ -628,10 +658,11 @@ static int search_batch_sync(asl_library_t *L, asl_index_t *idx, const asl_peaks
                            P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p,
                            L->best_slot.p, nullptr, o_row.d, o_score.d, o_ncand.d, o_cnt.d,
                            o_pairs.d, pm_stride, L->status.p, flt, true, &L->rs_scratch,
-                           rows_filtered ? L->rows_len.p : nullptr, nullptr, true, n_best));
+                           rows_filtered ? L->rows_len.p : nullptr, nullptr, true, n_best,
+                           distinct ? L->group.p : nullptr));
   } else {
     ASL_TRY(window_search_device(L, Q.dev, P, o_row.d, o_score.d, o_ncand.d, o_cnt.d, o_pairs.d,
-                                 pm_stride, n_best));
+                                 pm_stride, n_best, distinct));
   }
   ASL_TRY(o_row.finish());
   ASL_TRY(o_score.finish());
@@ -793,6 +824,37 @@ int asl_search_batch_topn(asl_library_t *L, asl_index_t *idx, const asl_peaks_t 
   if (P->use_ann && P->k <= 0) return fail(ASL_ERR_INVALID, "search_batch_topn: k must be positive");
   return search_batch_sync(L, idx, queries, P, n_best, best_row, best_score, n_cand, pm_count, pm_pairs,
                            pm_stride, knn_I);
+}
+
+int asl_search_batch_topn_distinct(asl_library_t *L, asl_index_t *idx, const asl_peaks_t *queries,
+                                   const asl_search_params_t *P, int32_t n_best, int32_t *best_row,
+                                   double *best_score, int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs,
+                                   int32_t pm_stride, int64_t *knn_I) {
+  clear_error();
+  if (n_best < 1 || n_best > ASL_MAX_BEST)
+    return fail(ASL_ERR_INVALID, "search_batch_topn_distinct: n_best must be in [1, %d]", ASL_MAX_BEST);
+  ASL_TRY(ensure_device());     // as asl_search_batch_topn: never pipelined
+  if (!L || !queries || !P) return fail(ASL_ERR_INVALID, "search_batch_topn_distinct: null argument");
+  if (!L->has_group)
+    return fail(ASL_ERR_STATE,
+                "search_batch_topn_distinct: the library has no group column (asl_library_set_groups)");
+  if (queries->n == 0) return ASL_OK;
+  if (pm_pairs && pm_stride <= 0) return fail(ASL_ERR_INVALID, "search_batch_topn_distinct: pm_stride");
+  if (P->use_ann && !idx) return fail(ASL_ERR_INVALID, "search_batch_topn_distinct: use_ann needs an index");
+  if (P->use_ann && P->k <= 0) return fail(ASL_ERR_INVALID, "search_batch_topn_distinct: k must be positive");
+  return search_batch_sync(L, idx, queries, P, n_best, best_row, best_score, n_cand, pm_count, pm_pairs,
+                           pm_stride, knn_I, true);
+}
+
+int asl_rescore_knn_topn_distinct(asl_library_t *L, const asl_peaks_t *queries, const asl_search_params_t *P,
+                                  const int64_t *knn_I, int32_t n_best, int32_t *best_row, double *best_score,
+                                  int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride) {
+  clear_error();
+  if (n_best < 1 || n_best > ASL_MAX_BEST)
+    return fail(ASL_ERR_INVALID, "rescore_knn_topn_distinct: n_best must be in [1, %d]", ASL_MAX_BEST);
+  ASL_TRY(ensure_device());     // (no device: ASL_ERR_NO_DEVICE whatever else was passed)
+  return rescore_knn_sync(L, queries, P, knn_I, n_best, best_row, best_score, n_cand, pm_count, pm_pairs,
+                          pm_stride, true);
 }
 
 }  // extern "C"

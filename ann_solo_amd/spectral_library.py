@@ -505,13 +505,53 @@ class SpectralLibrary:
             self._hold(q, best_row, best_score, n_cand, pm_count, pm_pairs, knn)
         return BatchResult(best_row, best_score, n_cand, pm_count, pm_pairs, knn)
 
+    def set_match_groups(self, groups: Optional[Dict[int, np.ndarray]]) -> None:
+        """Group ids of the library rows for distinct ranked matches: ``{charge: int32 array}``, one
+        id per row of that charge partition (e.g. its peptide; negative: ungrouped), copied to the
+        partition's device handle (``asl_library_set_groups``). Every partition must be named;
+        ``None`` drops the columns again."""
+        L = _lib.lib()
+        self._match_groups_from = None
+        if groups is None:
+            for part in self.partitions.values():
+                _lib.check(L.asl_library_set_groups(part.handle, 0, None))
+            return
+        missing = sorted(set(self.partitions) - set(groups))
+        if missing:
+            raise ValueError(f'set_match_groups: no group ids for charge(s) {missing}')
+        for z, part in self.partitions.items():
+            g = groups[z]
+            if isinstance(g, (list, tuple, np.ndarray)):
+                g = np.ascontiguousarray(g, np.int32)
+            _lib.check(L.asl_library_set_groups(part.handle, len(g), _lib.ptr(g)))
+
+    def _match_groups_from_peptides(self, library_meta) -> None:
+        """``distinct_matches``: the group of a library row is its peptide (``library_meta[charge]
+        [row]['peptide']``) -- equal strings share an id, ``None`` is ungrouped (-1); ids are
+        assigned per charge partition. Done once per metadata object."""
+        if getattr(self, '_match_groups_from', None) is library_meta:
+            return
+        groups = {}
+        for z, part in self.partitions.items():
+            cont, n = library_meta[z], len(part.ids)
+            if hasattr(cont, 'column'):
+                pep = list(cont.column('peptide', np.arange(n)))
+            else:
+                pep = [cont[i].get('peptide') for i in range(n)]
+            ids: Dict = {}
+            groups[z] = np.fromiter((-1 if p is None else ids.setdefault(p, len(ids)) for p in pep),
+                                    np.int32, n)
+        self.set_match_groups(groups)
+        self._match_groups_from = library_meta
+
     def search_batch_topn(self, queries: PackedSpectra, charge: int, mode: str, n_best: int,
                           want_knn: bool = False, device_out: bool = False,
-                          pm_stride: Optional[int] = None) -> Optional[TopnBatchResult]:
+                          pm_stride: Optional[int] = None, distinct: bool = False) -> Optional[TopnBatchResult]:
         """``_search_batch_local`` for the ``n_best`` (1 .. 16) best library matches of every query
         (``asl_search_batch_topn``): every cascade level and index mode, on this GPU alone.
         Synchronous -- the call never joins the two-stream pipeline. Rank 0 (and ``n_candidates``,
-        ``knn``) is what ``_search_batch_local`` returns, bit for bit."""
+        ``knn``) is what ``_search_batch_local`` returns, bit for bit. ``distinct``: one rank per
+        group of ``set_match_groups`` (``asl_search_batch_topn_distinct``; an error without groups)."""
         d = getattr(self, '_dist', None)
         if d is not None and d.world > 1:
             raise ValueError('search_batch_topn does not run on a sharded index')
@@ -543,7 +583,8 @@ class SpectralLibrary:
                                  float(tol_val), 0 if tol_mode == 'Da' else 1,
                                  cfg.fragment_mz_tolerance, int(cfg.allow_peak_shifts),
                                  int(use_ann))
-        _lib.check(_lib.lib().asl_search_batch_topn(
+        call = _lib.lib().asl_search_batch_topn_distinct if distinct else _lib.lib().asl_search_batch_topn
+        _lib.check(call(
             part.handle, idx._h if idx is not None else None, C.byref(_lib.peaks_struct(q)),
             C.byref(P), n, _lib.ptr(best_row), _lib.ptr(best_score), _lib.ptr(n_cand),
             _lib.ptr(pm_count), _lib.ptr(pm_pairs), stride, _lib.ptr(knn)))
@@ -669,6 +710,8 @@ class SpectralLibrary:
         ``writer.write_mztab``; its columns (``charge, qrow, lib_row, score, q``) are there for
         consumers that do not want 10^5 Python objects."""
         cfg = self.config
+        if cfg.distinct_matches and int(cfg.num_matches) > 1:
+            self._match_groups_from_peptides(library_meta)
         score_ssms = score_ssms or getattr(self, '_score_ssms', None)
         do_cascade_open = (cfg.precursor_tolerance_mass_open is not None and
                            cfg.precursor_tolerance_mode_open is not None)
@@ -711,6 +754,7 @@ class SpectralLibrary:
         t_level = time.perf_counter()
         n_in = sum(len(r) for r in rows_by_charge.values())
         n_best = int(self.config.num_matches)
+        distinct = bool(self.config.distinct_matches)
         table = SSMTable(query_meta, library_meta, n_best - 1)
         # Phase 1 issues every batch of the level; on one GPU the open-search batches go through
         # the two-stream pipeline (front of batch i+1 under the scan of batch i, no host wait
@@ -734,7 +778,8 @@ class SpectralLibrary:
                     whole = len(sel) == qs.n and sel[0] == 0 and sel[-1] == qs.n - 1
                     q = (qs if whole else qs.select(torch.as_tensor(sel))).to(self.device)
                     if n_best > 1:      # rank 0 goes the single winner's way, the rest rides along
-                        top = self.search_batch_topn(q, charge, mode, n_best, device_out=True)
+                        top = self.search_batch_topn(q, charge, mode, n_best, device_out=True,
+                                                     distinct=distinct)
                         res = None if top is None else top.rank0()
                         if res is not None:
                             res.topn = top
@@ -815,7 +860,11 @@ class SSMTable:
     With ``num_matches = n > 1`` (``n_alt = n - 1``) every match also carries its runners-up:
     ``alt_lib_row[len, n_alt]`` (-1 padded) and ``alt_score[len, n_alt]`` (shifted-dot scores of
     ranks 1..), ``delta_score[len]`` (the rank-0 shifted-dot score minus rank 1's; the rank-0 score
-    itself without a runner-up; NaN when ``n_alt = 0``) and ``alt_peak_matches(i, r)``."""
+    itself without a runner-up; NaN when ``n_alt = 0``) and ``alt_peak_matches(i, r)``.
+    With ``distinct_matches`` the ranks are distinct identifications: ``alt_lib_row`` / ``alt_score``
+    / ``alt_peak_matches`` name the best library spectrum of each of the next ``n_alt`` OTHER
+    peptides (never another spectrum of the winner's or of an earlier runner-up's peptide), and
+    ``delta_score`` is the gap to the best match of a different peptide."""
 
     def __init__(self, query_meta, library_meta, n_alt: int = 0):
         self.query_meta, self.library_meta = query_meta, library_meta

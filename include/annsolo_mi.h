@@ -438,6 +438,23 @@ int asl_rescore_batch_topn(const asl_peaks_t *queries, const asl_peaks_t *librar
                            int32_t *best_cand, double *best_score, int32_t *pm_count,
                            uint32_t *pm_pairs, int32_t pm_stride);
 
+/* DISTINCT ranked matches: asl_rescore_batch_topn with one rule added. Every library row carries a
+ * 32-bit group id (lib_group [library->n], host or device memory; e.g. its peptide). The slots of a
+ * list are walked in asl_rescore_batch_topn's order -- score descending, then position ascending --
+ * and a slot is skipped when an earlier rank already holds a row of the same group, so the ranks
+ * name n different groups, each by its best slot. A negative id means "ungrouped": such a row
+ * collides with nothing, not even with itself listed twice. Rank 0 is asl_rescore_batch's winner,
+ * bit for bit; ranks beyond the last distinct group hold -1 / 0.0 / 0 / zero pairs; with every id
+ * negative the outputs equal asl_rescore_batch_topn's byte for byte. Exact: the selection keeps,
+ * per lane and per tile, the best slot of every group it may still need.
+ * lib_group == NULL is ASL_ERR_INVALID; n_best as in asl_rescore_batch_topn. */
+int asl_rescore_batch_topn_distinct(const asl_peaks_t *queries, const asl_peaks_t *library,
+                                    const int64_t *cand_rows, const int32_t *cand_offsets,
+                                    const int32_t *lib_group /* [library->n] */,
+                                    double fragment_mz_tolerance, int allow_shift, int32_t n_best,
+                                    int32_t *best_cand, double *best_score, int32_t *pm_count,
+                                    uint32_t *pm_pairs, int32_t pm_stride);
+
 /* ------------------------------------------------------------------ peak preprocessing
  * Replaces process_spectrum (src/ann_solo/spectrum.py:57-119: spectrum_utils set_mz_range,
  * round(resolution,'sum'), remove_precursor_peak(tol,'Da',2), filter_intensity,
@@ -511,6 +528,11 @@ asl_library_t *asl_library_create(const asl_peaks_t *library, const float *lib_p
                                   const uint8_t *valid);
 void asl_library_free(asl_library_t *lib);
 int64_t asl_library_size(const asl_library_t *lib);
+/* The group column of a library handle (asl_*_topn_distinct): group[n], one 32-bit id per row, host
+ * or device memory, n == asl_library_size(lib) (anything else: ASL_ERR_INVALID). The ids are copied
+ * to the device; the array is the caller's again on return. group == NULL drops the column (n is
+ * ignored). Setting it again replaces it. No other entry point reads it. */
+int asl_library_set_groups(asl_library_t *lib, int64_t n, const int32_t *group);
 
 typedef struct {
   double min_bound, bin_size; /* encoder grid (get_dim) */
@@ -563,6 +585,25 @@ int asl_rescore_knn_topn(asl_library_t *lib, const asl_peaks_t *queries,
                          const asl_search_params_t *params, const int64_t *knn_I, int32_t n_best,
                          int32_t *best_row, double *best_score, int32_t *n_cand,
                          int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride);
+
+/* asl_search_batch_topn / asl_rescore_knn_topn with DISTINCT ranks (asl_rescore_batch_topn_distinct's
+ * rule, ties to the lower library row): same arguments, same output shapes, the groups are the
+ * library handle's column (asl_library_set_groups). Without a column: ASL_ERR_STATE, never a silent
+ * fall-back to the plain ranks. Column 0 of every output, n_cand and knn_I equal asl_search_batch's
+ * bit for bit; the ranks below name the best row of the next groups, -1 / 0.0 / 0 / zero pairs beyond
+ * the last one. Every mode asl_search_batch_topn covers, use_ann = 0 at any pair budget included
+ * (each tile's distinct ranks are folded into the running ones, skipping groups already held).
+ * Synchronous and not pipelined, like the plain calls. */
+int asl_search_batch_topn_distinct(asl_library_t *lib, asl_index_t *idx, const asl_peaks_t *queries,
+                                   const asl_search_params_t *params, int32_t n_best,
+                                   int32_t *best_row, double *best_score, int32_t *n_cand,
+                                   int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride,
+                                   int64_t *knn_I);
+int asl_rescore_knn_topn_distinct(asl_library_t *lib, const asl_peaks_t *queries,
+                                  const asl_search_params_t *params, const int64_t *knn_I,
+                                  int32_t n_best, int32_t *best_row, double *best_score,
+                                  int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs,
+                                  int32_t pm_stride);
 
 /* Precursor-window candidate generation alone (spectral_library.py:417-429):
  * CSR lists of library rows (ascending) whose precursor passes the window. Two-call
