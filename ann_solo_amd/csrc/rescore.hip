@@ -18,12 +18,11 @@
 // peaks, cursor by binary search (same cursor value as the reference's running cursor
 // because both peak lists ascend).
 // Pass 2 (rescore_argmax_kernel): per query first-strict-maximum (cpp:118-129).
-// Pass 3 (rescore_matches_kernel): the winning pair is re-run once per query to
+// Pass 3 (rescore_matches_kernel): the winning pair is re-run once per winner to
 // emit its peak_matches in greedy order.
-// Top-n (asl_*_topn, n_best > 0 in rescore_device): Pass 2 is rescore_topn_kernel, the n best slots
-// per query in one pass over the scores; Pass 3 rescore_matches_topn_kernel over nq * n winners.
-// Distinct top-n (asl_*_topn_distinct, a group id per library row): Pass 2 is
-// rescore_topn_distinct_kernel, the n best slots of n different groups.
+// Ranked matches (asl_*_topn, asl_*_topn_distinct; n_best > 0 in the request): Pass 2 is
+// rescore_topn_kernel (rescore_rank.hip), the n best slots per query in one pass over the scores, of n
+// different groups where the library rows carry group ids; Pass 3 then runs over nq * n winners.
 //
 // Arithmetic mirrors the reference: window tests in double on float->double
 // promoted m/z (cpp:42,53); product = (float)(mult * (double)q_int * (double)c_int)
@@ -31,7 +30,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
-#include "rescore.hpp"
+#include "rescore_cand.hpp"
 
 namespace asl {
 
@@ -41,8 +40,6 @@ constexpr int RS_WAVES = 4;
 #endif
 constexpr int RS_MAXP = 256;   // peaks per spectrum the kernels accept
 constexpr int RS_MCAP = 512;   // generated peak matches per pair the kernels accept
-
-enum { RS_STATUS_OK = 0, RS_STATUS_PEAKS = 1, RS_STATUS_MATCHES = 2, RS_STATUS_WINDOW = 4 };
 
 template <int MAXP_, int MCAP_>
 struct WaveLdsT {
@@ -66,12 +63,6 @@ struct QueryLdsT {
   float inten[MAXP_];
 };
 typedef QueryLdsT<RS_MAXP> QueryLds;
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <int CTRL>
 __device__ __forceinline__ uint32_t rs_dpp(uint32_t v) {
@@ -323,53 +314,6 @@ __device__ __forceinline__ void load_query(int tid, int nthreads, const DevPeaks
     Q.inten[i] = Qs.intensity[qo + i];
   }
 }
-
-// Candidate addressing: CSR (cand_offsets != null) or fixed stride; the CSR form either lists
-// row ids (rows64 / rows32) or, for the window-only modes, is a run of the precursor-sorted view
-// per query (win_begin: rescore.hpp, WindowRows).
-struct CandView {
-  const int64_t *rows64;
-  const int32_t *rows32;
-  const int32_t *offsets;
-  int32_t stride;
-  PrecFilter flt;
-  // fixed-stride rows whose length the producer wrote (the scans' post-filter, common.hpp:
-  // ScanPostFilter): counts[q] >= 0: the row holds that many hits, ALREADY filtered by the
-  // precursor window; -1: the row holds `stride` unfiltered hits (filter here, as without counts)
-  const int32_t *counts = nullptr;
-  const int32_t *win_begin = nullptr;   // WindowRows::begin / sorted_row / valid
-  const int32_t *win_rows = nullptr;
-  const uint8_t *win_valid = nullptr;
-  __device__ __forceinline__ bool prefiltered(int q) const { return counts != nullptr && counts[q] >= 0; }
-  // row of query q's slot c if it is a candidate of the query (in range, passes the filter), else -1
-  __device__ __forceinline__ long long cand(int q, long long c, double q_pmz, int n_lib) const {
-    const long long r = row(q, c);
-    return (r >= 0 && r < n_lib && filter_pass(flt, q_pmz, r)) ? r : -1;
-  }
-  __device__ __forceinline__ void range(int q, long long &c0, long long &c1) const {
-    if (offsets) {
-      c0 = offsets[q];
-      c1 = offsets[q + 1];
-    } else {
-      c0 = (long long)q * stride;
-      int len = stride;
-      if (counts) {
-        const int c = counts[q];
-        if (c >= 0) len = c < stride ? c : stride;
-      }
-      c1 = c0 + len;
-    }
-  }
-  // library row of query q's slot c (-1: none; an invalid row of a window, as window_fill_kernel
-  // marks it)
-  __device__ __forceinline__ long long row(int q, long long c) const {
-    if (win_begin) {
-      const int32_t r = win_rows[(long long)win_begin[q] + (c - offsets[q])];
-      return (!win_valid || win_valid[r]) ? (long long)r : -1;
-    }
-    return rows64 ? rows64[c] : (long long)rows32[c];
-  }
-};
 
 constexpr int RS_BS_GROUP = 16;      // queries per workgroup of the binary-search kernel
 __global__ __launch_bounds__(64 * RS_WAVES) void rescore_score_kernel(
@@ -1367,111 +1311,14 @@ __global__ __launch_bounds__(64) void rescore_argmax_kernel(
   }
 }
 
-// Top-n selection (asl_*_topn): the n best slots of a query instead of the single best, in the
-// argmax's order -- score descending, then the tie key ascending (tie_by_row as above), then the
-// slot position (only a row that a caller's list names twice under tie_by_row = 1 gets that far).
-// One wave per query, ONE pass over the list whatever n is: every lane keeps the best n of the
-// slots it reads, sorted, in an LDS array laid out [n][64] (lane-strided: a lane's entries sit in
-// its own banks); a slot is inserted only when it beats the lane's n-th, which after the first few
-// hundred slots is rare, so the pass costs the argmax's coalesced read of pair_score. Then the 64
-// sorted lane lists are merged: n rounds of a wave arg-max over the lanes' heads. Positions and
-// rows are kept as 32-bit values (positions relative to the list's first slot; lists and library
-// rows are 32-bit everywhere in the callers). Dynamic LDS: n * 64 * 16 bytes.
-// Outputs [nq, n]; ranks beyond the valid slots: slot -1, score 0.
-__global__ __launch_bounds__(64) void rescore_topn_kernel(
-    CandView cv, int nq, int n, const double *__restrict__ pair_score, int tie_by_row,
-    int32_t *__restrict__ best_cand, long long *__restrict__ best_slot,
-    double *__restrict__ best_score, int32_t *__restrict__ n_valid) {
-  extern __shared__ __attribute__((aligned(16))) double topn_lds[];      // (no static LDS in front of it)
-  double *S = topn_lds;                                      // [n][64] scores
-  int32_t *K = reinterpret_cast<int32_t *>(S + n * 64);      // [n][64] tie keys
-  int32_t *P = K + n * 64;                                   // [n][64] positions
-  const int q = blockIdx.x;
-  const int lane = threadIdx.x;
-  long long c0, c1;
-  cv.range(q, c0, c1);
-  int have = 0, cnt = 0;
-  double ts = -1.0;          // the lane's n-th entry once it holds n
-  int32_t tk = 0, tp = 0;
-  for (long long c = c0 + lane; c < c1; c += 64) {
-    const double s = pair_score[c];
-    if (s < 0.0) continue;
-    ++cnt;
-    if (have == n && s < ts) continue;
-    const int32_t pos = (int32_t)(c - c0);
-    const int32_t key = tie_by_row ? (int32_t)cv.row(q, c) : pos;
-    if (have == n && s == ts && !(key < tk || (key == tk && pos < tp))) continue;
-    int i = have < n ? have : n - 1;
-    while (i > 0) {
-      const double ps = S[(i - 1) * 64 + lane];
-      const int32_t pk = K[(i - 1) * 64 + lane], pp = P[(i - 1) * 64 + lane];
-      if (!(s > ps || (s == ps && (key < pk || (key == pk && pos < pp))))) break;
-      S[i * 64 + lane] = ps;
-      K[i * 64 + lane] = pk;
-      P[i * 64 + lane] = pp;
-      --i;
-    }
-    S[i * 64 + lane] = s;
-    K[i * 64 + lane] = key;
-    P[i * 64 + lane] = pos;
-    if (have < n) ++have;
-    if (have == n) {
-      ts = S[(n - 1) * 64 + lane];
-      tk = K[(n - 1) * 64 + lane];
-      tp = P[(n - 1) * 64 + lane];
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-  int head = 0;
-  for (int r = 0; r < n; ++r) {
-    const bool live = head < have;
-    const double ms = live ? S[head * 64 + lane] : -1.0;
-    const int32_t mk = live ? K[head * 64 + lane] : 0x7fffffff;
-    const int32_t mp = live ? P[head * 64 + lane] : 0x7fffffff;
-    double bs = ms;
-    int32_t bk = mk, bp = mp;
-    for (int off = 32; off > 0; off >>= 1) {
-      const double os = __shfl_xor(bs, off);
-      const int32_t ok = __shfl_xor(bk, off), op = __shfl_xor(bp, off);
-      if (os > bs || (os == bs && (ok < bk || (ok == bk && op < bp)))) {
-        bs = os;
-        bk = ok;
-        bp = op;
-      }
-    }
-    const bool any = bs >= 0.0;               // wave-uniform: positions are unique, the order is total
-    if (any && live && mp == bp) ++head;      // the lane that held the winner moves on
-    if (lane == 0) {
-      const size_t o = (size_t)q * n + r;
-      if (best_cand) best_cand[o] = any ? bp : -1;
-      if (best_slot) best_slot[o] = any ? c0 + bp : -1;
-      if (best_score) best_score[o] = any ? bs : 0.0;
-    }
-  }
-  if (lane == 0 && n_valid) n_valid[q] = cnt;
-}
-
-// (rescore_topn_distinct_kernel, the selection of the distinct ranked matches, and
-// window_merge_topn_distinct_kernel, their fold, are defined behind the drivers below: the kernels
-// above and below this line keep their places in the code object)
-__global__ void rescore_topn_distinct_kernel(CandView cv, int nq, int n, const double *__restrict__ pair_score,
-                                             int tie_by_row, const int32_t *__restrict__ group, int n_lib,
-                                             int32_t *__restrict__ best_cand, long long *__restrict__ best_slot,
-                                             double *__restrict__ best_score, int32_t *__restrict__ n_valid);
-__global__ void window_merge_topn_distinct_kernel(CandView cv, int nq, int n, const long long *__restrict__ best_slot,
-                                                  const double *__restrict__ best_score,
-                                                  const int32_t *__restrict__ n_valid,
-                                                  const int32_t *__restrict__ group, double *__restrict__ run_score,
-                                                  int32_t *__restrict__ run_row, int32_t *__restrict__ run_n);
-
-// One wave per query, and a wave is a chain of dependent memory round trips (winner's slot -> its
+// One wave per winner, and a wave is a chain of dependent memory round trips (winner's slot -> its
 // row -> its peaks) around little arithmetic: the kernel lives on the number of waves in flight,
 // i.e. on the LDS a wave needs. SMALL: structures for spectra of <= 128 peaks and <= 128
-// generated matches (4 KB per wave instead of 11: 32 waves per CU instead of 12); a query beyond
+// generated matches (4 KB per wave instead of 11: 32 waves per CU instead of 12); a winner beyond
 // them is marked in m_defer and done by the full-size instantiation, which runs second and only
-// looks at marked queries.
-// `w` is the winner's index in best_slot and in the outputs: the query itself for the single-winner
-// kernels, q * n_best + rank for the top-n ones.
+// looks at marked winners.
+// `w` is the winner's index in best_slot, in m_defer and in every output, [nq, n]: q * n + rank
+// (n = 1, the single winner: the query itself).
 constexpr int RS_SMALL_P = 128, RS_SMALL_M = 128;
 template <bool SMALL, class QL, class WL>
 __device__ __forceinline__ void matches_one(int q, int w, int lane, QL &Qw, WL &Ww, int *s_cnt_w, const DevPeaks &Qs,
@@ -1513,47 +1360,12 @@ __device__ __forceinline__ void matches_one(int q, int w, int lane, QL &Qw, WL &
       pm_pairs[(size_t)w * pm_stride * 2 + t] = 0u;
 }
 
-// SMALL: a wave per query. Full size: a wave per RS_MF_GROUP queries, which reads their flags at once
+// SMALL: a wave per winner. Full size: a wave per RS_MF_GROUP winners, which reads their flags at once
 // and does the marked ones (normally none: a 44 KB workgroup per four queries -- one per 64 now --, placed only to
 // return, took 0.04 ms of a step).
 constexpr int RS_MF_GROUP = 16;
 template <bool SMALL>
 __global__ __launch_bounds__(64 * RS_WAVES) void rescore_matches_kernel(
-    DevPeaks Qs, DevPeaks L, CandView cv, int nq, const long long *__restrict__ best_slot,
-    double tol, int allow_shift, int32_t *__restrict__ pm_count,
-    uint32_t *__restrict__ pm_pairs, int pm_stride, int32_t *__restrict__ best_row,
-    int *status, int *__restrict__ m_defer) {
-  typedef QueryLdsT<SMALL ? RS_SMALL_P : RS_MAXP> QL;
-  typedef WaveLdsT<SMALL ? RS_SMALL_P : RS_MAXP, SMALL ? RS_SMALL_M : RS_MCAP> WL;
-  __shared__ QL Q[RS_WAVES];
-  __shared__ WL W[RS_WAVES];
-  __shared__ int s_cnt[RS_WAVES];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (SMALL) {
-    const int q = blockIdx.x * RS_WAVES + wave;
-    if (q >= nq) return;
-    if (lane == 0) m_defer[q] = 0;
-    matches_one<true>(q, q, lane, Q[wave], W[wave], &s_cnt[wave], Qs, L, cv, best_slot, tol, allow_shift, pm_count,
-                      pm_pairs, pm_stride, best_row, status, m_defer);
-    return;
-  }
-  // a wave takes RS_MF_GROUP consecutive queries: one read of their flags; if every query is marked
-  // (spectra of more than 128 peaks) the grid still holds nq / 16 workgroups
-  const int base = (blockIdx.x * RS_WAVES + wave) * RS_MF_GROUP;
-  unsigned long long todo = __ballot(lane < RS_MF_GROUP && base + lane < nq && m_defer[base + lane] != 0);
-  while (todo) {          // wave-uniform
-    const int l = __builtin_ctzll(todo);
-    todo &= todo - 1ull;
-    matches_one<false>(base + l, base + l, lane, Q[wave], W[wave], &s_cnt[wave], Qs, L, cv, best_slot, tol, allow_shift,
-                       pm_count, pm_pairs, pm_stride, best_row, status, m_defer);
-    wave_sync();
-  }
-}
-
-// The peak matches of n winners per query (asl_*_topn): the kernel above over nq * n winners,
-// winner w = q * n + rank (best_slot, m_defer and every output are [nq, n]); the same two launches.
-template <bool SMALL>
-__global__ __launch_bounds__(64 * RS_WAVES) void rescore_matches_topn_kernel(
     DevPeaks Qs, DevPeaks L, CandView cv, int nq, int n, const long long *__restrict__ best_slot,
     double tol, int allow_shift, int32_t *__restrict__ pm_count,
     uint32_t *__restrict__ pm_pairs, int pm_stride, int32_t *__restrict__ best_row,
@@ -1573,6 +1385,8 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_matches_topn_kernel(
                       allow_shift, pm_count, pm_pairs, pm_stride, best_row, status, m_defer);
     return;
   }
+  // a wave takes RS_MF_GROUP consecutive winners: one read of their flags; if every one is marked
+  // (spectra of more than 128 peaks) the grid still holds nw / 16 workgroups
   const long long base = ((long long)blockIdx.x * RS_WAVES + wave) * RS_MF_GROUP;
   unsigned long long todo = __ballot(lane < RS_MF_GROUP && base + lane < nw && m_defer[base + lane] != 0);
   while (todo) {          // wave-uniform
@@ -1585,38 +1399,26 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_matches_topn_kernel(
   }
 }
 
-// Host driver shared by asl_rescore_batch and asl_search_batch. All pointers are
-// device pointers. pair_score scratch must hold one double per candidate slot.
-int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
-                   const int32_t *rows32, const int32_t *cand_offsets, int32_t stride,
-                   int64_t total_slots, double tol, int allow_shift, int tie_by_row,
-                   double *pair_score, long long *best_slot, int32_t *best_cand,
-                   int32_t *best_row, double *best_score, int32_t *n_valid,
-                   int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride, int *status,
-                   const PrecFilter &filter, bool clear_status, RescoreScratch *scratch,
-                   const int32_t *row_counts, const WindowRows *window, bool emit_matches, int n_best,
-                   const int32_t *group) {
-  const int nq = Q.n;
+// Host driver shared by asl_rescore_batch and asl_search_batch (rescore.hpp: RescoreRequest).
+int rescore_device(const RescoreRequest &rq) {
+  const DevPeaks &Q = rq.Q, &L = rq.L;
+  const CandList &cand = rq.cand;
+  const PrecFilter &filter = rq.filter;
+  const int nq = Q.n, n_best = rq.n_best;
   if (nq == 0) return ASL_OK;
-  if (!scratch) return fail(ASL_ERR_INVALID, "rescore: no scratch (internal)");
+  if (!rq.scratch) return fail(ASL_ERR_INVALID, "rescore: no scratch (internal)");
   if (n_best < 0 || n_best > ASL_MAX_BEST) return fail(ASL_ERR_INVALID, "rescore: n_best (internal)");
-  if (group && n_best == 0) return fail(ASL_ERR_INVALID, "rescore: groups without n_best (internal)");
-  if (window && (!cand_offsets || rows64 || rows32 || !window->begin || !window->sorted_row ||
-                 !filter.meta || !L.charge || !L.records))
+  if (rq.group && n_best == 0) return fail(ASL_ERR_INVALID, "rescore: groups without n_best (internal)");
+  if (cand.window && (!cand.offsets || cand.rows64 || cand.rows32 || !cand.window->begin ||
+                      !cand.window->sorted_row || !filter.meta || !L.charge || !L.records))
     return fail(ASL_ERR_INVALID, "rescore: window lists need CSR offsets and packed rows (internal)");
-  DevBuf<int> &q_defer = scratch->q_defer, &m_defer = scratch->m_defer;
-  CandView cv{rows64, rows32, cand_offsets, stride, filter};
-  cv.counts = cand_offsets ? nullptr : row_counts;
-  if (window) {
-    cv.win_begin = window->begin;
-    cv.win_rows = window->sorted_row;
-    cv.win_valid = window->valid;
-  }
-  if (clear_status) HIP_TRY(hipMemsetAsync(status, 0, sizeof(int), stream()));
+  DevBuf<int> &q_defer = rq.scratch->q_defer, &m_defer = rq.scratch->m_defer;
+  const CandView cv = make_cand_view(cand, filter);
+  if (rq.clear_status) HIP_TRY(hipMemsetAsync(rq.status, 0, sizeof(int), stream()));
   {
     ProfScope ps("rescore");
     // split long candidate lists over blockIdx.y when there are few queries
-    int64_t avg = total_slots / (nq > 0 ? nq : 1);
+    int64_t avg = cand.total_slots / (nq > 0 ? nq : 1);
     int ysplit = 1;
     if (nq < 2048 && avg > 4096) ysplit = (int)std::min<int64_t>(64, cdiv(avg, 4096));
     {
@@ -1624,393 +1426,55 @@ int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
       // return at once for queries with nothing deferred)
       ASL_TRY(q_defer.reserve((size_t)nq));
       HIP_TRY(hipMemsetAsync(q_defer.p, 0, sizeof(int) * (size_t)nq, stream()));
-      const bool shaped = !cand_offsets && filter.meta && filter.wcol && L.charge && L.records &&
-                          (rows64 || rows32);
+      const bool shaped = !cand.offsets && filter.meta && filter.wcol && L.charge && L.records &&
+                          (cand.rows64 || cand.rows32);
       // 1. flat kernel; 2. pair kernel on what it marked RS_DEFER; 3. binary-search kernel on
       // RS_DEFER_BS (blocks of 2 / 3 return at once for queries without such slots)
-      auto flat = window ? rescore_flat_kernel<3>
-                  : !shaped ? rescore_flat_kernel<0> : rows64 ? rescore_flat_kernel<2> : rescore_flat_kernel<1>;
-      hipLaunchKernelGGL(flat, dim3(nq, ysplit), dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, tol,
-                         allow_shift, pair_score, q_defer.p, status);
+      auto flat = cand.window ? rescore_flat_kernel<3>
+                  : !shaped   ? rescore_flat_kernel<0>
+                  : cand.rows64 ? rescore_flat_kernel<2> : rescore_flat_kernel<1>;
+      hipLaunchKernelGGL(flat, dim3(nq, ysplit), dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, rq.tol,
+                         rq.allow_shift, rq.pair_score, q_defer.p, rq.status);
       ASL_CHECK_LAUNCH();
-      auto kern = window    ? rescore_score_v2_kernel<3, true>
-                  : !shaped ? rescore_score_v2_kernel<0, true>
-                  : rows64 ? rescore_score_v2_kernel<2, true>
-                           : rescore_score_v2_kernel<1, true>;
+      auto kern = cand.window ? rescore_score_v2_kernel<3, true>
+                  : !shaped   ? rescore_score_v2_kernel<0, true>
+                  : cand.rows64 ? rescore_score_v2_kernel<2, true>
+                                : rescore_score_v2_kernel<1, true>;
       hipLaunchKernelGGL(kern, dim3(nq, std::max(ysplit, RS_DEF_Y)), dim3(64 * RS_WAVES), 0, stream(), Q,
-                         L, cv, tol, allow_shift, pair_score, q_defer.p, status);
+                         L, cv, rq.tol, rq.allow_shift, rq.pair_score, q_defer.p, rq.status);
       ASL_CHECK_LAUNCH();
       // (small batches keep a workgroup per query: when every query is marked -- tol <= 0, queries
       // of more than 100 peaks -- they need all the parallelism there is)
       const int bs_group = nq >= 4096 ? RS_BS_GROUP : 1;
       hipLaunchKernelGGL(rescore_score_kernel, dim3((unsigned)cdiv(nq, bs_group), ysplit), dim3(64 * RS_WAVES), 0,
-                         stream(), Q, L, cv, tol, allow_shift, pair_score,
-                         (const int *)q_defer.p, status, bs_group);
+                         stream(), Q, L, cv, rq.tol, rq.allow_shift, rq.pair_score,
+                         (const int *)q_defer.p, rq.status, bs_group);
     }
     ASL_CHECK_LAUNCH();
-    if (group)
-      hipLaunchKernelGGL(rescore_topn_distinct_kernel, dim3(nq), dim3(64), (size_t)n_best * 64 * 20 + 64, stream(),
-                         cv, nq, n_best, pair_score, tie_by_row, group, (int)L.n, best_cand, best_slot, best_score,
-                         n_valid);
-    else if (n_best > 0)
-      hipLaunchKernelGGL(rescore_topn_kernel, dim3(nq), dim3(64), (size_t)n_best * 64 * 16, stream(), cv, nq,
-                         n_best, pair_score, tie_by_row, best_cand, best_slot, best_score, n_valid);
-    else
+    if (n_best > 0) {
+      ASL_TRY(rescore_select_ranked(cv, nq, n_best, rq.pair_score, rq.tie_by_row, rq.group, (int)L.n, rq.best_cand,
+                                    rq.best_slot, rq.best_score, rq.n_valid));
+    } else {
       hipLaunchKernelGGL(rescore_argmax_kernel, dim3(nq), dim3(64), 0, stream(), cv, nq,
-                         pair_score, tie_by_row, best_cand, best_slot, best_score, n_valid);
-    ASL_CHECK_LAUNCH();
+                         rq.pair_score, rq.tie_by_row, rq.best_cand, rq.best_slot, rq.best_score, rq.n_valid);
+      ASL_CHECK_LAUNCH();
+    }
   }
-  if (emit_matches && n_best > 0) {
+  if (rq.emit_matches) {
     ProfScope ps("rescore_matches");
-    const long long nw = (long long)nq * n_best;
+    const int n = std::max(n_best, 1);
+    const long long nw = (long long)nq * n;
     ASL_TRY(m_defer.reserve((size_t)nw));
-    hipLaunchKernelGGL(rescore_matches_topn_kernel<true>, dim3((unsigned)cdiv(nw, RS_WAVES)),
-                       dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, n_best, best_slot, tol,
-                       allow_shift, pm_count, pm_pairs, pm_stride, best_row, status, m_defer.p);
+    hipLaunchKernelGGL(rescore_matches_kernel<true>, dim3((unsigned)cdiv(nw, RS_WAVES)),
+                       dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, n, rq.best_slot, rq.tol,
+                       rq.allow_shift, rq.pm_count, rq.pm_pairs, rq.pm_stride, rq.best_row, rq.status, m_defer.p);
     ASL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(rescore_matches_topn_kernel<false>, dim3((unsigned)cdiv(nw, RS_MF_GROUP * RS_WAVES)),
-                       dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, n_best, best_slot, tol,
-                       allow_shift, pm_count, pm_pairs, pm_stride, best_row, status, m_defer.p);
-    ASL_CHECK_LAUNCH();
-  } else if (emit_matches) {
-    ProfScope ps("rescore_matches");
-    ASL_TRY(m_defer.reserve((size_t)nq));
-    hipLaunchKernelGGL(rescore_matches_kernel<true>, dim3((unsigned)cdiv(nq, RS_WAVES)),
-                       dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, best_slot, tol,
-                       allow_shift, pm_count, pm_pairs, pm_stride, best_row, status, m_defer.p);
-    ASL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(rescore_matches_kernel<false>, dim3((unsigned)cdiv(nq, RS_MF_GROUP * RS_WAVES)),
-                       dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, best_slot, tol,
-                       allow_shift, pm_count, pm_pairs, pm_stride, best_row, status, m_defer.p);
+    hipLaunchKernelGGL(rescore_matches_kernel<false>, dim3((unsigned)cdiv(nw, RS_MF_GROUP * RS_WAVES)),
+                       dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, n, rq.best_slot, rq.tol,
+                       rq.allow_shift, rq.pm_count, rq.pm_pairs, rq.pm_stride, rq.best_row, rq.status, m_defer.p);
     ASL_CHECK_LAUNCH();
   }
   return ASL_OK;
-}
-
-// Tiled window search (search.hip): one thread per query of the tile. Each query's tiles are
-// folded in stream order, so the running best needs no atomics.
-__global__ __launch_bounds__(256) void window_merge_kernel(
-    CandView cv, int nq, const long long *__restrict__ best_slot, const double *__restrict__ best_score,
-    const int32_t *__restrict__ n_valid, double *__restrict__ run_score, int32_t *__restrict__ run_row,
-    int32_t *__restrict__ run_n) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= nq) return;
-  run_n[q] += n_valid[q];
-  const long long slot = best_slot[q];
-  if (slot < 0) return;
-  const int32_t r = (int32_t)cv.row(q, slot);
-  const double s = best_score[q];
-  const int32_t rr = run_row[q];
-  if (rr < 0 || s > run_score[q] || (s == run_score[q] && r < rr)) {   // tie_by_row = 1
-    run_score[q] = s;
-    run_row[q] = r;
-  }
-}
-
-__global__ __launch_bounds__(256) void window_finish_kernel(
-    int nq, const double *__restrict__ run_score, const int32_t *__restrict__ run_row,
-    const int32_t *__restrict__ run_n, const double *__restrict__ rescored, double *__restrict__ best_score,
-    int32_t *__restrict__ n_cand, int *status) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= nq) return;
-  const bool won = run_row[q] >= 0;
-  if (won && rescored[q] != run_score[q]) atomicOr(status, RS_STATUS_WINDOW);
-  if (best_score) best_score[q] = won ? run_score[q] : 0.0;
-  if (n_cand) n_cand[q] = run_n[q];
-}
-
-int rescore_window_merge(const WindowRows &window, const int32_t *cand_offsets, int nq,
-                         const long long *best_slot, const double *best_score, const int32_t *n_valid,
-                         double *run_score, int32_t *run_row, int32_t *run_n) {
-  if (nq <= 0) return ASL_OK;
-  CandView cv{nullptr, nullptr, cand_offsets, 0, PrecFilter()};
-  cv.win_begin = window.begin;
-  cv.win_rows = window.sorted_row;
-  cv.win_valid = window.valid;
-  hipLaunchKernelGGL(window_merge_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(), cv, nq,
-                     best_slot, best_score, n_valid, run_score, run_row, run_n);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-int rescore_window_finish(int nq, const double *run_score, const int32_t *run_row, const int32_t *run_n,
-                          const double *rescored, double *best_score, int32_t *n_cand, int *status) {
-  if (nq <= 0) return ASL_OK;
-  hipLaunchKernelGGL(window_finish_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(), nq,
-                     run_score, run_row, run_n, rescored, best_score, n_cand, status);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-// Top-n fold of a tile (asl_search_batch_topn): the tile's n best (slots, scores: rescore_topn_kernel,
-// sorted) and the running n best of the query (rows, scores, sorted, row -1 beyond the filled
-// ranks) are two sorted lists of at most n over disjoint rows, so merging them by (score
-// descending, row ascending) and keeping n is exact whatever the tile cuts were. One thread per
-// query, in place: a forward pass counts how many of each list survive, a backward pass writes them.
-__global__ __launch_bounds__(256) void window_merge_topn_kernel(
-    CandView cv, int nq, int n, const long long *__restrict__ best_slot, const double *__restrict__ best_score,
-    const int32_t *__restrict__ n_valid, double *__restrict__ run_score, int32_t *__restrict__ run_row,
-    int32_t *__restrict__ run_n) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= nq) return;
-  run_n[q] += n_valid[q];
-  const long long *ts = best_slot + (size_t)q * n;
-  const double *tsc = best_score + (size_t)q * n;
-  double *rs = run_score + (size_t)q * n;
-  int32_t *rr = run_row + (size_t)q * n;
-  int la = 0, lb = 0;
-  while (la < n && rr[la] >= 0) ++la;
-  while (lb < n && ts[lb] >= 0) ++lb;
-  if (lb == 0) return;
-  // a (running) before b (tile) when its score is higher, or equal with the lower row
-  auto a_first = [&](int ia, int ib) {
-    const double sa = rs[ia], sb = tsc[ib];
-    return sa > sb || (sa == sb && rr[ia] < (int32_t)cv.row(q, ts[ib]));
-  };
-  int na = 0, nb = 0;
-  while (na + nb < n && (na < la || nb < lb)) {
-    if (nb >= lb || (na < la && a_first(na, nb))) ++na; else ++nb;
-  }
-  for (int k = na + nb - 1; k >= 0; --k) {       // k >= na - 1: no unread running entry is overwritten
-    if (nb == 0) break;                          // the rest of the running list is in place
-    if (na > 0 && !a_first(na - 1, nb - 1)) {
-      --na;
-      rs[k] = rs[na];
-      rr[k] = rr[na];
-    } else {
-      --nb;
-      rs[k] = tsc[nb];
-      rr[k] = (int32_t)cv.row(q, ts[nb]);
-    }
-  }
-}
-
-// After the last tile and the n-candidate pass over the running lists (`rescored`: its best_score
-// [nq, n], the same order): every filled rank's rescored score must be the merged one.
-__global__ __launch_bounds__(256) void window_finish_topn_kernel(
-    int nq, int n, const double *__restrict__ run_score, const int32_t *__restrict__ run_row,
-    const int32_t *__restrict__ run_n, const double *__restrict__ rescored, double *__restrict__ best_score,
-    int32_t *__restrict__ n_cand, int *status) {
-  const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= (long long)nq * n) return;
-  const bool won = run_row[w] >= 0;
-  if (won && rescored[w] != run_score[w]) atomicOr(status, RS_STATUS_WINDOW);
-  if (best_score) best_score[w] = won ? run_score[w] : 0.0;
-  if (n_cand && w % n == 0) n_cand[w / n] = run_n[w / n];
-}
-
-int rescore_window_merge_topn(const WindowRows &window, const int32_t *cand_offsets, int nq, int n,
-                              const long long *best_slot, const double *best_score, const int32_t *n_valid,
-                              double *run_score, int32_t *run_row, int32_t *run_n, const int32_t *group) {
-  if (nq <= 0) return ASL_OK;
-  CandView cv{nullptr, nullptr, cand_offsets, 0, PrecFilter()};
-  cv.win_begin = window.begin;
-  cv.win_rows = window.sorted_row;
-  cv.win_valid = window.valid;
-  if (group)
-    hipLaunchKernelGGL(window_merge_topn_distinct_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(), cv,
-                       nq, n, best_slot, best_score, n_valid, group, run_score, run_row, run_n);
-  else
-    hipLaunchKernelGGL(window_merge_topn_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(), cv, nq, n,
-                       best_slot, best_score, n_valid, run_score, run_row, run_n);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-int rescore_window_finish_topn(int nq, int n, const double *run_score, const int32_t *run_row,
-                               const int32_t *run_n, const double *rescored, double *best_score,
-                               int32_t *n_cand, int *status) {
-  if (nq <= 0) return ASL_OK;
-  hipLaunchKernelGGL(window_finish_topn_kernel, dim3((unsigned)cdiv((long long)nq * n, 256)), dim3(256), 0,
-                     stream(), nq, n, run_score, run_row, run_n, rescored, best_score, n_cand, status);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-// Distinct top-n selection (asl_*_topn_distinct): the ranking above with one rule added -- walking
-// the slots in that order, a slot is skipped when an earlier rank holds a row of the same group
-// (group[row], 32 bits per library row; a negative id is "ungrouped" and collides with nothing, not
-// even with itself listed twice). The same single pass: every lane keeps the best n of its slots
-// WITH DISTINCT GROUPS (a fourth LDS plane [n][64] of group ids). A slot whose group the lane holds
-// replaces that entry if it beats it and is dropped otherwise; a slot with a new group is inserted
-// as above. The `s < ts` cut stands: a lane that holds n groups, all ahead of the slot, has no use
-// for it whatever its group -- so group[row] is gathered only for the slots that pass the cut.
-// Merge: n rounds of the wave arg-max over the lanes' heads; the winner's group (wave-uniform, at
-// most n of them) goes to a 16-entry LDS line, and every lane moves its head past entries whose
-// group is on that line.
-// Exact: an element of the answer is the best of its group among all slots, hence in its lane, and
-// the groups ahead of it in its lane are ahead of it in the answer too, fewer than n: the lane kept
-// it. In the merge the best slot of a group not yet emitted is its lane's first entry off the line
-// (everything ahead of it in the lane beats it and would otherwise be that best slot), so it is
-// the arg-max of the heads. Rank 0 is the plain winner; with every group negative nothing ever
-// collides and the outputs are the plain kernel's byte for byte.
-// Dynamic LDS: n * 64 * 20 + 64 bytes (20 KB at n = 16).
-__global__ __launch_bounds__(64) void rescore_topn_distinct_kernel(
-    CandView cv, int nq, int n, const double *__restrict__ pair_score, int tie_by_row,
-    const int32_t *__restrict__ group, int n_lib, int32_t *__restrict__ best_cand, long long *__restrict__ best_slot,
-    double *__restrict__ best_score, int32_t *__restrict__ n_valid) {
-  extern __shared__ __attribute__((aligned(16))) double topn_lds[];
-  double *S = topn_lds;                                      // [n][64] scores
-  int32_t *K = reinterpret_cast<int32_t *>(S + n * 64);      // [n][64] tie keys
-  int32_t *P = K + n * 64;                                   // [n][64] positions
-  int32_t *G = P + n * 64;                                   // [n][64] group ids
-  int32_t *E = G + n * 64;                                   // [16] groups emitted so far (merge)
-  const int q = blockIdx.x;
-  const int lane = threadIdx.x;
-  long long c0, c1;
-  cv.range(q, c0, c1);
-  int have = 0, cnt = 0;
-  double ts = -1.0;          // the lane's n-th entry once it holds n
-  int32_t tk = 0, tp = 0;
-  for (long long c = c0 + lane; c < c1; c += 64) {
-    const double s = pair_score[c];
-    if (s < 0.0) continue;
-    ++cnt;
-    if (have == n && s < ts) continue;
-    const int32_t pos = (int32_t)(c - c0);
-    const int32_t row = (int32_t)cv.row(q, c);       // (a scored slot: a row of the library)
-    const int32_t key = tie_by_row ? row : pos;
-    if (have == n && s == ts && !(key < tk || (key == tk && pos < tp))) continue;
-    const int32_t g = (uint32_t)row < (uint32_t)n_lib ? group[row] : -1;
-    int i = have < n ? have : n - 1;                 // a new group: from the end, the n-th falls out
-    bool held = false;
-    if (g >= 0) {
-      for (int j = 0; j < have; ++j) {
-        if (G[j * 64 + lane] == g) {
-          i = j;                                     // the group's entry: replaced in place or kept
-          held = true;
-          break;
-        }
-      }
-    }
-    if (held) {
-      const double ps = S[i * 64 + lane];
-      const int32_t pk = K[i * 64 + lane], pp = P[i * 64 + lane];
-      if (!(s > ps || (s == ps && (key < pk || (key == pk && pos < pp))))) continue;
-    }
-    while (i > 0) {
-      const double ps = S[(i - 1) * 64 + lane];
-      const int32_t pk = K[(i - 1) * 64 + lane], pp = P[(i - 1) * 64 + lane];
-      if (!(s > ps || (s == ps && (key < pk || (key == pk && pos < pp))))) break;
-      S[i * 64 + lane] = ps;
-      K[i * 64 + lane] = pk;
-      P[i * 64 + lane] = pp;
-      G[i * 64 + lane] = G[(i - 1) * 64 + lane];
-      --i;
-    }
-    S[i * 64 + lane] = s;
-    K[i * 64 + lane] = key;
-    P[i * 64 + lane] = pos;
-    G[i * 64 + lane] = g;
-    if (!held && have < n) ++have;
-    if (have == n) {
-      ts = S[(n - 1) * 64 + lane];
-      tk = K[(n - 1) * 64 + lane];
-      tp = P[(n - 1) * 64 + lane];
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-  int head = 0, ne = 0;      // ne: groups on the line (wave-uniform)
-  for (int r = 0; r < n; ++r) {
-    const bool live = head < have;
-    const double ms = live ? S[head * 64 + lane] : -1.0;
-    const int32_t mk = live ? K[head * 64 + lane] : 0x7fffffff;
-    const int32_t mp = live ? P[head * 64 + lane] : 0x7fffffff;
-    double bs = ms;
-    int32_t bk = mk, bp = mp;
-    for (int off = 32; off > 0; off >>= 1) {
-      const double os = __shfl_xor(bs, off);
-      const int32_t ok = __shfl_xor(bk, off), op = __shfl_xor(bp, off);
-      if (os > bs || (os == bs && (ok < bk || (ok == bk && op < bp)))) {
-        bs = os;
-        bk = ok;
-        bp = op;
-      }
-    }
-    const bool any = bs >= 0.0;               // wave-uniform: positions are unique, the order is total
-    if (lane == 0) {
-      const size_t o = (size_t)q * n + r;
-      if (best_cand) best_cand[o] = any ? bp : -1;
-      if (best_slot) best_slot[o] = any ? c0 + bp : -1;
-      if (best_score) best_score[o] = any ? bs : 0.0;
-    }
-    if (!any) continue;                       // (every later round is empty too)
-    const bool mine = live && mp == bp;       // the lane that held the winner
-    const unsigned long long who = __ballot(mine);
-    const int32_t wg = __shfl(live ? G[head * 64 + lane] : -1, __builtin_ctzll(who));
-    if (mine) ++head;
-    if (wg >= 0) {
-      if (lane == 0) E[ne] = wg;
-      ++ne;
-      wave_sync();
-    }
-    while (head < have) {                     // past the entries whose group has a rank already
-      const int32_t hg = G[head * 64 + lane];
-      bool out = false;
-      if (hg >= 0)
-        for (int e = 0; e < ne; ++e) out = out || E[e] == hg;
-      if (!out) break;
-      ++head;
-    }
-  }
-  if (lane == 0 && n_valid) n_valid[q] = cnt;
-}
-
-// The distinct fold (asl_search_batch_topn_distinct): both lists are sorted and hold one row per
-// group (rescore_topn_distinct_kernel; the running list by induction), over disjoint rows. They are
-// merged by (score descending, row ascending), an entry whose group the output already holds is
-// skipped, and n are kept: an element of the distinct top-n of the union is the best of its group in
-// its own list with fewer than n groups ahead of it there, so it is in that list's distinct top-n,
-// and the walk meets the two lists' entries in the order of the union. Skipping moves entries by
-// more than the in-place passes above allow: the result is built in a local array and written back.
-__global__ __launch_bounds__(256) void window_merge_topn_distinct_kernel(
-    CandView cv, int nq, int n, const long long *__restrict__ best_slot, const double *__restrict__ best_score,
-    const int32_t *__restrict__ n_valid, const int32_t *__restrict__ group, double *__restrict__ run_score,
-    int32_t *__restrict__ run_row, int32_t *__restrict__ run_n) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= nq) return;
-  run_n[q] += n_valid[q];
-  const long long *ts = best_slot + (size_t)q * n;
-  const double *tsc = best_score + (size_t)q * n;
-  double *rs = run_score + (size_t)q * n;
-  int32_t *rr = run_row + (size_t)q * n;
-  int la = 0, lb = 0;
-  while (la < n && rr[la] >= 0) ++la;
-  while (lb < n && ts[lb] >= 0) ++lb;
-  if (lb == 0) return;
-  double os[ASL_MAX_BEST];
-  int32_t orow[ASL_MAX_BEST], og[ASL_MAX_BEST];
-  int no = 0, ia = 0, ib = 0;
-  while (no < n && (ia < la || ib < lb)) {
-    double s;
-    int32_t r;
-    bool a = ib >= lb;
-    if (!a) {
-      s = tsc[ib];
-      r = (int32_t)cv.row(q, ts[ib]);
-      a = ia < la && (rs[ia] > s || (rs[ia] == s && rr[ia] < r));
-    }
-    if (a) {
-      s = rs[ia];
-      r = rr[ia];
-      ++ia;
-    } else {
-      ++ib;
-    }
-    const int32_t g = group[r];
-    bool dup = false;
-    if (g >= 0)
-      for (int k = 0; k < no; ++k) dup = dup || og[k] == g;
-    if (dup) continue;
-    os[no] = s;
-    orow[no] = r;
-    og[no] = g;
-    ++no;
-  }
-  for (int k = 0; k < no; ++k) {      // (no >= la: nothing of the running list is left behind)
-    rs[k] = os[k];
-    rr[k] = orow[k];
-  }
 }
 
 int rescore_status_error(int st) {
@@ -2081,10 +1545,14 @@ static int rescore_batch_sync(const asl_peaks_t *queries, const asl_peaks_t *lib
   ASL_TRY(best_slot.reserve(nw));
   ASL_TRY(status.reserve(1));
   RescoreScratch scratch;      // lives until rescore_check_status below has synchronised
-  ASL_TRY(rescore_device(Q.dev, L.dev, rows.d, nullptr, off.d, 0, total, tol, allow_shift, 0,
-                         pair_score.p, best_slot.p, o_best.d, nullptr, o_score.d, nullptr,
-                         o_cnt.d, o_pairs.d, pm_stride, status.p, PrecFilter(), true, &scratch,
-                         nullptr, nullptr, true, n_best, lib_group ? grp.d : nullptr));
+  ASL_TRY(rescore_device({.Q = Q.dev, .L = L.dev,
+                          .cand = {.rows64 = rows.d, .offsets = off.d, .total_slots = total},
+                          .tol = tol, .allow_shift = allow_shift, .n_best = n_best,
+                          .group = lib_group ? grp.d : nullptr,
+                          .pair_score = pair_score.p, .best_slot = best_slot.p, .scratch = &scratch,
+                          .status = status.p,
+                          .best_cand = o_best.d, .best_score = o_score.d,
+                          .pm_count = o_cnt.d, .pm_pairs = o_pairs.d, .pm_stride = pm_stride}));
   ASL_TRY(o_best.finish());
   ASL_TRY(o_score.finish());
   ASL_TRY(o_cnt.finish());

@@ -75,55 +75,77 @@ struct WindowRows {
   const uint8_t *valid = nullptr;
 };
 
-// Host driver shared by asl_rescore_batch, asl_search_batch and asl_rescore_knn. All pointers
-// are device pointers. pair_score scratch must hold one double per candidate slot.
-int rescore_device(const DevPeaks &Q, const DevPeaks &L, const int64_t *rows64,
-                   const int32_t *rows32, const int32_t *cand_offsets, int32_t stride,
-                   int64_t total_slots, double tol, int allow_shift, int tie_by_row,
-                   double *pair_score, long long *best_slot, int32_t *best_cand,
-                   int32_t *best_row, double *best_score, int32_t *n_valid,
-                   int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride, int *status,
-                   const PrecFilter &filter = PrecFilter(), bool clear_status = true,
-                   RescoreScratch *scratch = nullptr,
-                   // fixed-stride rows: their lengths as the scans' post-filter wrote them (-1: unfiltered row)
-                   const int32_t *row_counts = nullptr,
-                   // window-only lists (rows64 = rows32 = nullptr, cand_offsets tile-local; the
-                   // filter's packed row records and annotated library peaks required)
-                   const WindowRows *window = nullptr,
-                   // false: stop after the argmax (no best_row, pm_count, pm_pairs written)
-                   bool emit_matches = true,
-                   // 0: the single winner. 1..ASL_MAX_BEST (asl_*_topn): the n best slots per query
-                   // (rescore_topn_kernel instead of the argmax, the matches kernels over nq * n
-                   // winners); best_slot / best_cand / best_row / best_score / pm_count are then
-                   // [nq, n_best], pm_pairs [nq, n_best, pm_stride, 2], n_valid stays [nq]
-                   int n_best = 0,
-                   // n_best > 0, non-null (asl_*_topn_distinct): group id of every library row, [L.n]; the
-                   // ranks then hold distinct groups (rescore_topn_distinct_kernel). nullptr: plain ranks
-                   const int32_t *group = nullptr);
-// Tiled window search: folds one tile's argmax (rescore_device's best_slot / best_score / n_valid
-// over the tile's nq queries, slots of the same window lists) into the running best of those
-// queries: a higher score wins, equal scores go to the lower library row, counts add up.
-// run_row < 0: no winner yet.
-int rescore_window_merge(const WindowRows &window, const int32_t *cand_offsets, int nq,
-                         const long long *best_slot, const double *best_score, const int32_t *n_valid,
-                         double *run_score, int32_t *run_row, int32_t *run_n);
-// After the last tile and the one-candidate pass over the winners (`rescored`: its best_score):
-// best_score = the merged score (0 without a winner), n_cand = the summed counts; a winner whose
-// rescored score differs from the merged one flags the status (an internal error).
-int rescore_window_finish(int nq, const double *run_score, const int32_t *run_row,
+// One list of candidate slots per query. CSR (offsets non-null) or fixed stride; the slots name
+// library rows (rows64 or rows32) or, for a window-only list, are runs of the precursor-sorted view.
+struct CandList {
+  const int64_t *rows64 = nullptr;      // row ids, 64- or 32-bit: one of the two, neither with `window`
+  const int32_t *rows32 = nullptr;
+  const int32_t *offsets = nullptr;     // CSR [nq + 1]; nullptr: query q's slots are [q * stride, (q + 1) * stride)
+  int32_t stride = 0;
+  int64_t total_slots = 0;              // slots of all queries (offsets[nq] or nq * stride)
+  // fixed-stride rows: their lengths as the scans' post-filter wrote them (-1: unfiltered row)
+  const int32_t *row_counts = nullptr;
+  // window-only lists (rows64 = rows32 = nullptr, offsets tile-local; the filter's packed row
+  // records and annotated library peaks required)
+  const WindowRows *window = nullptr;
+};
+
+// One call of the rescoring driver (rescore_device). All pointers are device pointers.
+struct RescoreRequest {
+  // -- spectra
+  DevPeaks Q, L;                        // queries, library
+  // -- candidate list
+  CandList cand;
+  // -- scoring
+  double tol = 0.0;                     // fragment m/z tolerance
+  int allow_shift = 0;
+  int tie_by_row = 0;                   // equal scores: 0 the first slot wins, 1 the lowest library row
+  PrecFilter filter;                    // precursor window applied to the slots (default: none)
+  // -- selection
+  // 0: the single winner (rescore_argmax_kernel). 1..ASL_MAX_BEST (asl_*_topn): the n best slots per
+  // query (rescore_topn_kernel, the matches kernel over nq * n winners); best_slot / best_cand /
+  // best_row / best_score / pm_count are then [nq, n_best], pm_pairs [nq, n_best, pm_stride, 2],
+  // n_valid stays [nq]
+  int n_best = 0;
+  // n_best > 0, non-null (asl_*_topn_distinct): group id of every library row, [L.n]; the ranks then
+  // hold distinct groups. nullptr: plain ranks
+  const int32_t *group = nullptr;
+  // -- work memory
+  double *pair_score = nullptr;         // one double per candidate slot
+  long long *best_slot = nullptr;       // one per winner
+  RescoreScratch *scratch = nullptr;    // required
+  int *status = nullptr;                // RS_STATUS_* flags, or-ed in (rescore_check_status)
+  bool clear_status = true;             // zero the flags first
+  // -- outputs (one per winner; any may be null)
+  int32_t *best_cand = nullptr;         // the winner's position in its query's list (-1: none)
+  int32_t *best_row = nullptr;          // its library row (-1: none)
+  double *best_score = nullptr;
+  int32_t *n_valid = nullptr;           // [nq] candidates of the query that were scored
+  int32_t *pm_count = nullptr;          // the winner's peak matches in greedy order: their number,
+  uint32_t *pm_pairs = nullptr;         // (query peak, library peak) pairs [pm_stride, 2]
+  int32_t pm_stride = 0;
+  bool emit_matches = true;             // false: stop after the selection (no best_row, pm_count, pm_pairs written)
+};
+
+// Host driver shared by asl_rescore_batch, asl_search_batch and asl_rescore_knn.
+int rescore_device(const RescoreRequest &rq);
+// Tiled window search: folds one tile's n best (rescore_device's best_slot / best_score [nq, n], sorted,
+// and n_valid over the tile's nq queries; `cand` is the tile's window list, whose slots best_slot
+// names) into the running n best of those queries, run_score / run_row [nq, n], sorted by (score
+// descending, row ascending), run_row -1 beyond the filled ranks: a higher score goes first, equal
+// scores go to the lower library row, counts add up. n = 1 is the single winner. group (non-null:
+// the distinct fold): the library rows' group ids, both lists then hold one row per group and so
+// does the result.
+int rescore_window_merge(const CandList &cand, int nq, int n, const long long *best_slot,
+                         const double *best_score, const int32_t *n_valid, double *run_score,
+                         int32_t *run_row, int32_t *run_n, const int32_t *group = nullptr);
+// After the last tile and the n-candidate pass over the running lists (`rescored`: its best_score
+// [nq, n], the same order): best_score = the merged scores (0 for an empty rank), n_cand = the summed
+// counts; a filled rank whose rescored score differs from the merged one flags the status (an
+// internal error).
+int rescore_window_finish(int nq, int n, const double *run_score, const int32_t *run_row,
                           const int32_t *run_n, const double *rescored, double *best_score,
                           int32_t *n_cand, int *status);
-// The same fold and finish for the n best (asl_search_batch_topn): the tile's best_slot / best_score
-// and the running run_score / run_row are [nq, n], sorted by (score descending, row ascending),
-// run_row -1 beyond the filled ranks; `rescored` is [nq, n]. group (non-null: the distinct fold):
-// the library rows' group ids, both lists then hold one row per group and so does the result.
-int rescore_window_merge_topn(const WindowRows &window, const int32_t *cand_offsets, int nq, int n,
-                              const long long *best_slot, const double *best_score, const int32_t *n_valid,
-                              double *run_score, int32_t *run_row, int32_t *run_n,
-                              const int32_t *group = nullptr);
-int rescore_window_finish_topn(int nq, int n, const double *run_score, const int32_t *run_row,
-                               const int32_t *run_n, const double *rescored, double *best_score,
-                               int32_t *n_cand, int *status);
 int rescore_check_status(const int *status_dev);   // reads the flags back: synchronises
 int rescore_status_error(int status_bits);         // ASL_OK or the error the flags stand for
 

@@ -375,12 +375,11 @@ static int window_candidates_device(asl_library *L, int nq, const double *q_pmz_
 // place by the rescoring kernels (rescore.hpp: WindowRows) -- no candidate list. The batch's pairs,
 // counted in 64 bits, are cut into tiles of at most window_pair_budget() pairs; a tile is a run of
 // queries whose first and last may bring only part of their window. One tile (every batch whose
-// pairs fit): the rescoring as for any list. Several: each tile's argmax is folded into a running
-// best (rescore_window_merge), then one pass over a one-candidate list per query -- its winner --
-// emits the peak matches. Scratch: pair scores of one tile, 12 bytes per query.
-// n_best > 0 (asl_search_batch_topn): the same tiles with the n best per query -- outputs [nq, n_best],
-// each tile's top-n folded into a running top-n (rescore_window_merge_topn), the final pass over an
-// n-candidate list per query. n_best = 0 is the single-winner search, launch for launch.
+// pairs fit): the rescoring as for any list. Several: each tile's n best (n = 1: its argmax) are
+// folded into the running n best (rescore_window_merge), then one pass over an n-candidate list per
+// query -- its winners -- emits the peak matches. Scratch: pair scores of one tile, 12 bytes per winner.
+// n_best > 0 (asl_search_batch_topn): outputs [nq, n_best]. n_best = 0 is the single-winner search: the
+// same launches at n = 1 with the argmax as the selection.
 static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_search_params_t *P,
                                 int32_t *best_row, double *best_score, int32_t *n_cand,
                                 int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride, int n_best = 0,
@@ -389,7 +388,8 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
   // distinct (asl_search_batch_topn_distinct): every tile's ranks and the fold hold one row per group;
   // the final pass over the n-candidate lists, already distinct, is the plain one
   const int32_t *group = distinct ? L->group.p : nullptr;
-  const size_t nw = (size_t)nq * (size_t)std::max(n_best, 1);     // winners of the batch
+  const int n = std::max(n_best, 1);
+  const size_t nw = (size_t)nq * (size_t)n;     // winners of the batch
   std::vector<int32_t> h_lo((size_t)nq), h_cnt((size_t)nq);
   {
     ProfScope ps("filter");
@@ -434,10 +434,14 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
     for (int q = 0; q < nq; q++) h[(size_t)nq + 1 + q] = h_lo[(size_t)q];
     ASL_TRY(L->wtile.upload(h.data(), h.size()));
     win.begin = L->wtile.p + nq + 1;
-    return rescore_device(Q, L->dev, nullptr, nullptr, L->wtile.p, 0, total, P->fragment_mz_tolerance,
-                          P->allow_shift, 1, L->pair_score.p, L->best_slot.p, nullptr, best_row,
-                          best_score, n_cand, pm_count, pm_pairs, pm_stride, L->status.p, rows_only,
-                          true, &L->rs_scratch, nullptr, &win, true, n_best, group);
+    return rescore_device({.Q = Q, .L = L->dev,
+                           .cand = {.offsets = L->wtile.p, .total_slots = total, .window = &win},
+                           .tol = P->fragment_mz_tolerance, .allow_shift = P->allow_shift, .tie_by_row = 1,
+                           .filter = rows_only, .n_best = n_best, .group = group,
+                           .pair_score = L->pair_score.p, .best_slot = L->best_slot.p,
+                           .scratch = &L->rs_scratch, .status = L->status.p,
+                           .best_row = best_row, .best_score = best_score, .n_valid = n_cand,
+                           .pm_count = pm_count, .pm_pairs = pm_pairs, .pm_stride = pm_stride});
   }
   // tiles [t0, t1) of the global pair range; queries qa..qb (the query of pair t0 .. that of t1-1)
   struct Tile {
@@ -481,34 +485,28 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
     if (Qt.precursor_charge) Qt.precursor_charge += T.qa;
     const int32_t *off = L->wtile.p + T.idx;
     win.begin = off + T.nq + 1;
-    ASL_TRY(rescore_device(Qt, L->dev, nullptr, nullptr, off, 0, T.pairs, P->fragment_mz_tolerance,
-                           P->allow_shift, 1, L->pair_score.p, L->best_slot.p, nullptr, nullptr,
-                           L->tile_score.p, L->tile_n.p, nullptr, nullptr, pm_stride, L->status.p,
-                           rows_only, false, &L->rs_scratch, nullptr, &win, false, n_best, group));
-    if (n_best > 0)
-      ASL_TRY(rescore_window_merge_topn(win, off, T.nq, n_best, L->best_slot.p, L->tile_score.p, L->tile_n.p,
-                                        L->run_score.p + (size_t)T.qa * n_best,
-                                        L->run_row.p + (size_t)T.qa * n_best, L->run_n.p + T.qa, group));
-    else
-      ASL_TRY(rescore_window_merge(win, off, T.nq, L->best_slot.p, L->tile_score.p, L->tile_n.p,
-                                   L->run_score.p + T.qa, L->run_row.p + T.qa, L->run_n.p + T.qa));
+    const CandList tile{.offsets = off, .total_slots = T.pairs, .window = &win};
+    ASL_TRY(rescore_device({.Q = Qt, .L = L->dev, .cand = tile,
+                            .tol = P->fragment_mz_tolerance, .allow_shift = P->allow_shift, .tie_by_row = 1,
+                            .filter = rows_only, .n_best = n_best, .group = group,
+                            .pair_score = L->pair_score.p, .best_slot = L->best_slot.p,
+                            .scratch = &L->rs_scratch, .status = L->status.p, .clear_status = false,
+                            .best_score = L->tile_score.p, .n_valid = L->tile_n.p, .emit_matches = false}));
+    ASL_TRY(rescore_window_merge(tile, T.nq, n, L->best_slot.p, L->tile_score.p, L->tile_n.p,
+                                 L->run_score.p + (size_t)T.qa * n, L->run_row.p + (size_t)T.qa * n,
+                                 L->run_n.p + T.qa, group));
   }
-  if (n_best > 0) {
-    // the running lists once more, as an n-candidate list per query (-1: an empty rank): the same
-    // order comes out again, with rows and peak matches
-    ASL_TRY(rescore_device(Q, L->dev, nullptr, L->run_row.p, nullptr, n_best, (int64_t)nw,
-                           P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p, L->best_slot.p,
-                           nullptr, best_row, L->tile_score.p, nullptr, pm_count, pm_pairs, pm_stride,
-                           L->status.p, rows_only, false, &L->rs_scratch, nullptr, nullptr, true, n_best));
-    return rescore_window_finish_topn(nq, n_best, L->run_score.p, L->run_row.p, L->run_n.p, L->tile_score.p,
-                                      best_score, n_cand, L->status.p);
-  }
-  // the winners once more, as a one-candidate list per query (-1: none): rows and peak matches
-  ASL_TRY(rescore_device(Q, L->dev, nullptr, L->run_row.p, nullptr, 1, nq, P->fragment_mz_tolerance,
-                         P->allow_shift, 1, L->pair_score.p, L->best_slot.p, nullptr, best_row,
-                         L->tile_score.p, nullptr, pm_count, pm_pairs, pm_stride, L->status.p, rows_only,
-                         false, &L->rs_scratch));
-  return rescore_window_finish(nq, L->run_score.p, L->run_row.p, L->run_n.p, L->tile_score.p, best_score,
+  // the running lists once more, as an n-candidate list per query (-1: an empty rank): the same
+  // order comes out again, with rows and peak matches (n_best = 0: the one winner, by the argmax)
+  ASL_TRY(rescore_device({.Q = Q, .L = L->dev,
+                          .cand = {.rows32 = L->run_row.p, .stride = n, .total_slots = (int64_t)nw},
+                          .tol = P->fragment_mz_tolerance, .allow_shift = P->allow_shift, .tie_by_row = 1,
+                          .filter = rows_only, .n_best = n_best,
+                          .pair_score = L->pair_score.p, .best_slot = L->best_slot.p,
+                          .scratch = &L->rs_scratch, .status = L->status.p, .clear_status = false,
+                          .best_row = best_row, .best_score = L->tile_score.p,
+                          .pm_count = pm_count, .pm_pairs = pm_pairs, .pm_stride = pm_stride}));
+  return rescore_window_finish(nq, n, L->run_score.p, L->run_row.p, L->run_n.p, L->tile_score.p, best_score,
                                n_cand, L->status.p);
 }
 
@@ -577,11 +575,14 @@ static int rescore_knn_sync(asl_library_t *L, const asl_peaks_t *queries, const 
   // the precursor filter runs inside the rescoring kernel's compaction stage
   PrecFilter flt;
   batch_filter(L, P, flt);
-  ASL_TRY(rescore_device(Q.dev, L->dev, knn.d, nullptr, nullptr, k, (int64_t)nq * k,
-                         P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p,
-                         L->best_slot.p, nullptr, o_row.d, o_score.d, o_ncand.d, o_cnt.d,
-                         o_pairs.d, pm_stride, L->status.p, flt, true, &L->rs_scratch, nullptr, nullptr,
-                         true, n_best, distinct ? L->group.p : nullptr));
+  ASL_TRY(rescore_device({.Q = Q.dev, .L = L->dev,
+                          .cand = {.rows64 = knn.d, .stride = k, .total_slots = (int64_t)nq * k},
+                          .tol = P->fragment_mz_tolerance, .allow_shift = P->allow_shift, .tie_by_row = 1,
+                          .filter = flt, .n_best = n_best, .group = distinct ? L->group.p : nullptr,
+                          .pair_score = L->pair_score.p, .best_slot = L->best_slot.p,
+                          .scratch = &L->rs_scratch, .status = L->status.p,
+                          .best_row = o_row.d, .best_score = o_score.d, .n_valid = o_ncand.d,
+                          .pm_count = o_cnt.d, .pm_pairs = o_pairs.d, .pm_stride = pm_stride}));
   ASL_TRY(o_row.finish());
   ASL_TRY(o_score.finish());
   ASL_TRY(o_ncand.finish());
@@ -654,12 +655,15 @@ static int search_batch_sync(asl_library_t *L, asl_index_t *idx, const asl_peaks
     const bool rows_filtered = rq.rows_filtered;
     PrecFilter flt;
     batch_filter(L, P, flt);
-    ASL_TRY(rescore_device(Q.dev, L->dev, nullptr, L->knn.p, nullptr, k, (int64_t)nq * k,
-                           P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p,
-                           L->best_slot.p, nullptr, o_row.d, o_score.d, o_ncand.d, o_cnt.d,
-                           o_pairs.d, pm_stride, L->status.p, flt, true, &L->rs_scratch,
-                           rows_filtered ? L->rows_len.p : nullptr, nullptr, true, n_best,
-                           distinct ? L->group.p : nullptr));
+    ASL_TRY(rescore_device({.Q = Q.dev, .L = L->dev,
+                            .cand = {.rows32 = L->knn.p, .stride = k, .total_slots = (int64_t)nq * k,
+                                     .row_counts = rows_filtered ? L->rows_len.p : nullptr},
+                            .tol = P->fragment_mz_tolerance, .allow_shift = P->allow_shift, .tie_by_row = 1,
+                            .filter = flt, .n_best = n_best, .group = distinct ? L->group.p : nullptr,
+                            .pair_score = L->pair_score.p, .best_slot = L->best_slot.p,
+                            .scratch = &L->rs_scratch, .status = L->status.p,
+                            .best_row = o_row.d, .best_score = o_score.d, .n_valid = o_ncand.d,
+                            .pm_count = o_cnt.d, .pm_pairs = o_pairs.d, .pm_stride = pm_stride}));
   } else {
     ASL_TRY(window_search_device(L, Q.dev, P, o_row.d, o_score.d, o_ncand.d, o_cnt.d, o_pairs.d,
                                  pm_stride, n_best, distinct));
@@ -762,11 +766,15 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
     HIP_TRY(hipStreamWaitEvent(sc, pp.ev_scan[par], 0));
     PrecFilter flt;
     batch_filter(L, P, flt);
-    ASL_TRY(rescore_device(Q.dev, L->dev, nullptr, L->p_knn[par].p, nullptr, k, (int64_t)nq * k,
-                           P->fragment_mz_tolerance, P->allow_shift, 1, L->pair_score.p,
-                           L->best_slot.p, nullptr, best_row, best_score, n_cand, pm_count,
-                           pm_pairs, pm_stride, pp.status, flt, /*clear_status=*/false, &L->rs_scratch,
-                           rows_filtered ? L->p_rows[par].p : nullptr));
+    ASL_TRY(rescore_device({.Q = Q.dev, .L = L->dev,
+                            .cand = {.rows32 = L->p_knn[par].p, .stride = k, .total_slots = (int64_t)nq * k,
+                                     .row_counts = rows_filtered ? L->p_rows[par].p : nullptr},
+                            .tol = P->fragment_mz_tolerance, .allow_shift = P->allow_shift, .tie_by_row = 1,
+                            .filter = flt,
+                            .pair_score = L->pair_score.p, .best_slot = L->best_slot.p,
+                            .scratch = &L->rs_scratch, .status = pp.status, .clear_status = false,
+                            .best_row = best_row, .best_score = best_score, .n_valid = n_cand,
+                            .pm_count = pm_count, .pm_pairs = pm_pairs, .pm_stride = pm_stride}));
     HIP_TRY(hipEventRecord(pp.ev_resc[par], sc));
     pp.resc_recorded[par] = true;
   }

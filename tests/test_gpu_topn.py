@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_bf_stream import UNLIMITED, _set_budget, small          # noqa: F401 (small: a fixture)
+from test_gpu_bf_stream import UNLIMITED, _search, _set_budget, small          # noqa: F401 (small: a fixture)
 from test_gpu_window_scan import _queries, _tie_library, _window_mask
 
 pytestmark = pytest.mark.gpu
@@ -340,7 +340,12 @@ def test_window_only_topn_tiles_and_oracle(O, small, mode, tol, tmode):
     for n in NS:
         full = fulls[n] = _topn_budget(sl, q, mode, n, UNLIMITED)
         for budget in (1, 7, 1000):                 # 1: every pair a tile of its own
-            _same_results(_topn_budget(sl, q, mode, n, budget), full, (mode, n, budget))
+            tiled = _topn_budget(sl, q, mode, n, budget)
+            _same_results(tiled, full, (mode, n, budget))
+            if n == 1 and budget < 1000:
+                # the single-winner search at the same cuts: one fold and one matches kernel serve both,
+                # only the selection differs (argmax / ranked), so every output is the same
+                _consistent(tiled, _search(sl, q, mode, budget), 1, what=(mode, 'single', budget))
         sub = _topn_budget(sl, q.select(torch.as_tensor(special)), mode, n, 1)
         for f in FIELDS:
             assert _bytes_equal(getattr(sub, f), getattr(full, f)[special]), (mode, n, f)
@@ -351,6 +356,8 @@ def test_window_only_topn_tiles_and_oracle(O, small, mode, tol, tmode):
         _consistent(full, single, n, again=_topn_budget(sl, q, mode, n, 1000), what=(mode, n))
     _consistent(fulls[5], single, 5, fulls[2], fulls[5])
     if mode == 'open':
+        # n = ASL_MAX_BEST at budget 1 above filled the fold's result to its last entry, without groups
+        assert (fulls[16].best_row[:, 15] >= 0).any()
         # a library spectrum as query: the original and its copy tie, the lower row first
         tied = sum(fulls[2].best_score[i, 0] == fulls[2].best_score[i, 1] and
                    fulls[2].best_row[i, 0] < fulls[2].best_row[i, 1] for i in range(68, 88))
