@@ -79,6 +79,7 @@ EXPORTS = [
     'asl_index_set_window_key', 'asl_index_search_window', 'asl_index_set_window_scan',
     'asl_rescore_batch_topn', 'asl_search_batch_topn', 'asl_rescore_knn_topn',
     'asl_index_rank',
+    'asl_index_set_by_residual', 'asl_index_get_by_residual',
     'asl_library_set_groups', 'asl_rescore_batch_topn_distinct', 'asl_search_batch_topn_distinct',
     'asl_rescore_knn_topn_distinct',
 ]
@@ -260,6 +261,9 @@ def lib():
                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
             L.asl_search_batch_topn_distinct.argtypes = L.asl_search_batch_topn.argtypes
             L.asl_rescore_knn_topn_distinct.argtypes = L.asl_rescore_knn_topn.argtypes
+        if hasattr(L, 'asl_index_set_by_residual'):
+            L.asl_index_set_by_residual.argtypes = [C.c_void_p, C.c_int32]
+            L.asl_index_get_by_residual.argtypes = [C.c_void_p]
         L.asl_lpt_owner.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         L.asl_window_candidates.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                             C.c_double, C.c_int32, C.c_void_p, C.c_void_p]

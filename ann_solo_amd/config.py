@@ -3,7 +3,7 @@
 ``Config`` carries the reference's flags under the reference's names
 (/root/reference/src/ann_solo/config.py:62-216) plus the ADDITIVE flags of this implementation
 (``index``, ``pq_m``, ``pq_bits``, ``refine_k``, ``kmeans_niter``, ``ann_seed``, ``num_gpus``,
-``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``, ``pq_by_residual``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -87,6 +87,9 @@ class Config:
                                             # peptides (one rank per peptide; the score gap is the gap to the
                                             # next different identification), not other spectra of the winner's
 
+    pq_by_residual: bool = True             # IVF-PQ, FAISS' IndexIVFPQ.by_residual: True codes the residuals
+                                            # x - centroid[list]; False (opt-in) the hashed vectors themselves
+
     MAX_PEAKS = 256      # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
     MAX_CANDIDATES = 16384   # largest num_candidates: beyond MAX_TOPK in bounded passes (TK_MAX_K_PASSES)
@@ -114,6 +117,9 @@ class Config:
                 raise ValueError("ann_window = 'pre' does not run on a sharded index (num_gpus > 1)")
             if self.refine_k:
                 raise ValueError("ann_window = 'pre' does not combine with refine_k")
+        self.pq_by_residual = bool(self.pq_by_residual)      # (the flag parses to 0 / 1)
+        if not self.pq_by_residual and self.index != 'ivfpq':
+            raise ValueError("pq_by_residual = False needs index = 'ivfpq' (it is the product quantiser's mode)")
         if not 1 <= int(self.num_matches) <= self.MAX_MATCHES:
             raise ValueError(f'num_matches = {self.num_matches}: 1 .. {self.MAX_MATCHES}')
         if int(self.num_matches) > 1 and self.num_gpus and int(self.num_gpus) > 1:
@@ -208,6 +214,10 @@ def add_arguments(parser) -> None:
                              "probed lists, then those in the precursor window (the reference); 'pre' "
                              'keeps the k best vectors of the probed lists that are in the window '
                              '(IVF-PQ, m = 32, 8 bits; one GPU) (default: %(default)s)')
+    parser.add_argument('--pq_by_residual', default=int(d.pq_by_residual), type=int, choices=[0, 1],
+                        help="IVF-PQ: 1 quantises the residuals x - centroid (FAISS' IndexIVFPQ.by_residual); "
+                             '0 the hashed vectors themselves, whose sparsity the centroid does not destroy '
+                             '(needs --index ivfpq) (default: %(default)s)')
     parser.add_argument('--num_matches', default=d.num_matches, type=int,
                         help='library matches reported per query, best first (1 .. 16): above 1 every '
                              'SSM also carries its runners-up and the score gap to the second best; '

@@ -120,6 +120,20 @@ int asl_index_set_niter(asl_index_t *ix, int32_t niter) {
   return ASL_OK;
 }
 
+int asl_index_set_by_residual(asl_index_t *ix, int32_t on) {
+  clear_error();
+  if (!ix) return fail(ASL_ERR_INVALID, "set_by_residual: null index");
+  if (on != 0 && on != 1) return fail(ASL_ERR_INVALID, "set_by_residual: 0 (raw vectors) or 1 (residuals)");
+  if (ix->kind != ASL_INDEX_IVFPQ) return fail(ASL_ERR_STATE, "set_by_residual: an IVF-PQ index is required");
+  if (ix->trained)
+    return fail(ASL_ERR_STATE, "set_by_residual: set before train() / set_trained() (the codebooks belong to the "
+                               "mode they were trained or installed in)");
+  ix->by_residual = on != 0;
+  return ASL_OK;
+}
+
+int asl_index_get_by_residual(const asl_index_t *ix) { return ix && ix->kind == ASL_INDEX_IVFPQ ? ix->by_residual : 1; }
+
 int asl_index_set_trained(asl_index_t *ix, const float *centroids, const float *codebooks) {
   clear_error();
   if (!ix) return fail(ASL_ERR_INVALID, "set_trained: null index");
@@ -183,7 +197,7 @@ static int index_add_impl(asl_index_t *ix, int64_t n, const float *x, const int3
     DevBuf<uint8_t> codes;
     ASL_TRY(codes.reserve((size_t)n * ix->pq_m));
     ASL_TRY(pq_encode(dx.d, ix->ws_assign.p, ix->centroids.p, ix->codebooks.p, n, ix->d, ix->pq_m,
-                      ix->ksub, ix->dsub, codes.p));
+                      ix->ksub, ix->dsub, codes.p, ix->by_residual));
     ASL_TRY(dev_append(ix->codes_add, (size_t)ix->n_store * ix->pq_m, codes.p, (size_t)n * ix->pq_m));
     ASL_TRY(sync_stream());
     if (ix->refine_rows) {

@@ -54,6 +54,9 @@ struct asl_index {
   int d = 0, nlist = 0, kind = 0, pq_m = 0, pq_bits = 8, ksub = 0, dsub = 0;
   int niter = 25;
   bool trained = false;
+  // IVF-PQ, FAISS' IndexIVFPQ::by_residual (asl_index_set_by_residual): false = the quantiser is trained on and
+  // encodes the vectors themselves, and a score's coarse term dis0 is 0 -- the scans get zero_D for coarse_D
+  bool by_residual = true;
   int64_t ntotal = 0;   // global vectors added
   int64_t n_store = 0;  // vectors stored here
   int shard_rank = 0, shard_world = 1;
@@ -134,6 +137,7 @@ struct asl_index {
   // scratch
   asl::DevBuf<float> ws_scores, coarse_D, ws_x;
   asl::DevBuf<int32_t> coarse_I, ws_assign;
+  asl::DevBuf<float> zero_D;          // by_residual off: zeros for any coarse_D (index_zero_coarse); never written
   asl::DevBuf<uint32_t> bitmap;
   asl::DevBuf<uint64_t> ws_upper;     // k > TK_MAX_K: the bound of every row between the passes
   asl::ShardScratch shard;       // asl_index_search_sharded
@@ -170,5 +174,7 @@ int index_window_prepare(asl_index *ix, uint64_t serial, const float *key, int64
 int index_refine_k(const asl_index *ix);
 int coarse_scores_all(asl_index *ix, const float *xq, int m, float *scores, uint2 *ent = nullptr, int32_t *cnt = nullptr);
 int index_codebooks_transposed(asl_index *ix);
+// n zeros (grow-only, cleared when it grows): the coarse_D of an IVF-PQ index with by_residual off
+int index_zero_coarse(asl_index *ix, size_t n, const float **zeros);
 
 }  // namespace asl

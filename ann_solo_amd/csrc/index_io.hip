@@ -17,6 +17,9 @@ struct IdxHeader {
   int64_t ntotal, n_store;
   int32_t shard_rank, shard_world, has_vids, pad;
 };
+// IVF-PQ `pad`: bit 0 exact rows follow, bits 1.. refine_k (<= TK_MAX_K), and -- version 3 only -- this bit:
+// by_residual is off (raw-vector codes). Builds before version 3 refuse such a file rather than mis-score it.
+constexpr int32_t PAD_PQ_RAW = 1 << 30;
 
 int asl_index_save(const asl_index_t *ix, const char *path) {
   clear_error();
@@ -41,6 +44,10 @@ int asl_index_save(const asl_index_t *ix, const char *path) {
   h.has_vids = ix->has_vids;
   h.pad = ix->refine_rows ? (1 | (ix->refine_k << 1)) : 0;   // IVF-PQ: exact rows follow the payload
   if (ix->kind == ASL_INDEX_IVFFLAT) h.pad = ix->flat_storage;   // IVF-Flat: component storage mode
+  if (ix->kind == ASL_INDEX_IVFPQ && !ix->by_residual) {          // (a by-residual index: byte for byte version 2)
+    h.version = 3;
+    h.pad |= PAD_PQ_RAW;
+  }
   bool ok = fwrite(&h, sizeof h, 1, f) == 1;
   auto dump = [&](const void *dev, size_t bytes) {
     if (!ok || bytes == 0) return;
@@ -95,10 +102,13 @@ asl_index_t *asl_index_load(const char *path) {
     fclose(f);
     return nullptr;
   }
+  bool raw = false;      // IVF-PQ, version 3: codes of the raw vectors (by_residual off)
   {  // ... and every count below sizes a host vector or a device allocation
     const char *bad = nullptr;
     const bool ivf = h.kind == ASL_INDEX_IVFFLAT || h.kind == ASL_INDEX_IVFPQ;
-    if (h.version != 1 && h.version != 2) bad = "unsupported version";
+    raw = h.kind != ASL_INDEX_IVFFLAT && h.pad >= 0 && (h.pad & PAD_PQ_RAW);
+    if (raw) h.pad &= ~PAD_PQ_RAW;      // (the refine bits below it are checked and read as ever)
+    if (h.version < 1 || h.version > 3) bad = "unsupported version";
     else if (h.kind < ASL_INDEX_FLAT || h.kind > ASL_INDEX_IVFPQ) bad = "unknown index kind";
     else if (h.d <= 0 || h.d > (1 << 20)) bad = "bad dimension";
     else if (ivf && (h.nlist <= 0 || h.nlist > (1 << 24))) bad = "bad nlist";
@@ -109,6 +119,7 @@ asl_index_t *asl_index_load(const char *path) {
     else if (h.kind == ASL_INDEX_IVFFLAT ? (h.pad != ASL_FLAT_FX22 && h.pad != ASL_FLAT_F32)
                                          : (h.pad < 0 || ((h.pad & 1) && h.kind != ASL_INDEX_IVFPQ) || (h.pad >> 1) > TK_MAX_K))
       bad = "bad refine / storage fields";
+    else if (raw && (h.kind != ASL_INDEX_IVFPQ || h.version < 3)) bad = "bad refine / storage fields";
     if (!bad) {  // the payload must be exactly what the header announces
       const uint64_t ksub = h.kind == ASL_INDEX_IVFPQ ? (1ull << h.pq_bits) : 0;
       uint64_t want = sizeof h;
@@ -144,6 +155,7 @@ asl_index_t *asl_index_load(const char *path) {
   if (ix->kind == ASL_INDEX_IVFPQ) {
     ix->ksub = 1 << ix->pq_bits;
     ix->dsub = ix->d / ix->pq_m;
+    ix->by_residual = !raw;
   }
   bool ok = true;
   auto slurp = [&](auto &buf, size_t count) {

@@ -43,8 +43,12 @@ static int index_rank_device(asl_index *ix, int nq, const float *xq, const int64
   int rows = nq;
   if (pq && nprobe == 0) {
     rows = (int)std::min<int64_t>(nq, std::max<int64_t>(1, (int64_t)(SCORE_CHUNK_BYTES / ((size_t)nlist * 4))));
-    ASL_TRY(coarse_all.reserve((size_t)rows * nlist));
+    if (ix->by_residual) ASL_TRY(coarse_all.reserve((size_t)rows * nlist));
   }
+  // by_residual off: zeros for the probes' scores and for the coarse term of every list (index_zero_coarse)
+  const float *zeros = nullptr;
+  if (pq && !ix->by_residual)
+    ASL_TRY(index_zero_coarse(ix, nprobe ? (size_t)nq * nprobe : (size_t)rows * nlist, &zeros));
   ASL_TRY(tkey.reserve((size_t)nq));
   ASL_TRY(tscore.reserve((size_t)nq));
   ASL_TRY(counts.reserve((size_t)nq * 2));
@@ -52,12 +56,13 @@ static int index_rank_device(asl_index *ix, int nq, const float *xq, const int64
   for (int r0 = 0; r0 < nq; r0 += rows) {
     const int m = std::min(rows, nq - r0);
     const float *x = xq + (size_t)r0 * d;
-    const float *cD = nprobe ? ix->coarse_D.p + (size_t)r0 * nprobe : nullptr;
+    const float *cD = !nprobe ? nullptr : zeros ? zeros : ix->coarse_D.p + (size_t)r0 * nprobe;
     const int32_t *cI = nprobe ? ix->coarse_I.p + (size_t)r0 * nprobe : nullptr;
     win.q_pmz = key ? q_pmz + r0 : nullptr;
     if (pq) {
-      if (nprobe == 0) ASL_TRY(coarse_scores_all(ix, x, m, coarse_all.p));
-      ASL_TRY(rank_pq(x, m, d, ix->codebooks_t.p, ix->dsub, nlist, ix->ntotal, cD, cI, nprobe, coarse_all.p,
+      if (nprobe == 0 && !zeros) ASL_TRY(coarse_scores_all(ix, x, m, coarse_all.p));
+      ASL_TRY(rank_pq(x, m, d, ix->codebooks_t.p, ix->dsub, nlist, ix->ntotal, cD, cI, nprobe,
+                      zeros ? zeros : coarse_all.p,
                       ix->list_offsets.p, ix->tile_offsets.p, ix->codes_tiled.p, ix->ids_tiled.p, target + r0, inv.p,
                       win, tkey.p + r0, tscore.p + r0, counts.p + (size_t)r0 * 2, scope != nullptr));
     } else {

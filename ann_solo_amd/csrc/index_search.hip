@@ -312,6 +312,17 @@ int index_codebooks_transposed(asl_index *ix) {
   return ASL_OK;
 }
 
+// by_residual off: the coarse term of every score is FAISS' dis0 = 0, so the scans are handed zeros where they
+// would read coarse scores. One buffer on the index, cleared on the stream when it grows; nothing writes it.
+int index_zero_coarse(asl_index *ix, size_t n, const float **zeros) {
+  if (n > ix->zero_D.cap) {
+    ASL_TRY(ix->zero_D.reserve(n));
+    HIP_TRY(hipMemsetAsync(ix->zero_D.p, 0, n * sizeof(float), stream()));
+  }
+  *zeros = ix->zero_D.p;
+  return ASL_OK;
+}
+
 // IVF-PQ, tiled scan (pq_scan_v3.hip), over the default layout or -- rq.win -- over the in-window
 // run of every probed list in the window-ordered one
 static int scan_pq_tiled(asl_index *ix, IndexSearch &rq, const SearchPlan &pl, const float *cD, const int32_t *cI,
@@ -352,6 +363,8 @@ static int search_ivfpq(asl_index *ix, IndexSearch &rq, const SearchPlan &pl) {
   // search_preassigned: the caller's probe lists, read where they lie (see search_ivfflat)
   const float *cD = rq.pre_D ? rq.pre_D : ix->coarse_D.p;
   const int32_t *cI = rq.pre_D ? rq.pre_I : ix->coarse_I.p;
+  // by_residual off: the probes select the lists as ever, their scores add nothing (whoever computed them)
+  if (!ix->by_residual) ASL_TRY(index_zero_coarse(ix, (size_t)nq * nprobe, &cD));
   uint64_t *upper = nullptr;
   if (pl.tiled) {
     ASL_TRY(scan_pq_tiled(ix, rq, pl, cD, cI, own_ent));

@@ -172,10 +172,12 @@ static int pq_train_device(asl_index *ix, const float *x, int64_t n, uint64_t se
   }
   ASL_TRY(xt.reserve((size_t)nt * d));
   ASL_TRY(gather_rows_f32(x, d, nt < n ? rows_dev.p : nullptr, nt, d, xt.p, d));
-  DevBuf<int32_t> assign;
-  ASL_TRY(assign.reserve((size_t)nt));
-  ASL_TRY(assign_ip(ix, xt.p, d, nt, ix->centroids.p, ix->nlist, d, assign.p));
-  ASL_TRY(residual(xt.p, assign.p, ix->centroids.p, nt, d, xt.p));
+  if (ix->by_residual) {      // (off: the sub-space k-means runs on the gathered rows as they are)
+    DevBuf<int32_t> assign;
+    ASL_TRY(assign.reserve((size_t)nt));
+    ASL_TRY(assign_ip(ix, xt.p, d, nt, ix->centroids.p, ix->nlist, d, assign.p));
+    ASL_TRY(residual(xt.p, assign.p, ix->centroids.p, nt, d, xt.p));
+  }
   ASL_TRY(ix->codebooks.reserve((size_t)m * ksub * dsub));
   for (int mi = 0; mi < m; mi++)
     ASL_TRY(kmeans_device(ix, xt.p + (size_t)mi * dsub, nt, d, dsub, ksub, ix->niter,

@@ -663,15 +663,82 @@ __global__ __launch_bounds__(256) void pq_encode_rounds_kernel(
   }
   if (live) codes[(size_t)i * m + mi] = (uint8_t)best;
 }
+// by_residual off (FAISS' IndexIVFPQ::by_residual = false): code = argmin_c L2(x_sub, cb[m][c]) of the vector
+// itself -- no list assignment, no centroid row. The same three shapes, the same rule (ascending c, strict <,
+// the lowest code wins a tie) and the same fmaf chain as the pair above, in kernels of their own so that those
+// two stay as they are to the instruction (profiles/pq_by_residual_resource_usage.txt).
+__global__ __launch_bounds__(256) void pq_encode_raw_kernel(
+    const float *__restrict__ x, const float *__restrict__ codebooks, int64_t n, int d, int m, int ksub,
+    int dsub, uint8_t *__restrict__ codes) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float *s_cb = reinterpret_cast<float *>(smem);
+  const int mi = blockIdx.y;
+  const float *cb = codebooks + (size_t)mi * ksub * dsub;
+  for (int i = threadIdx.x; i < ksub * dsub; i += 256) s_cb[i] = cb[i];
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float *xi = x + (size_t)i * d + (size_t)mi * dsub;
+  float bs = INFINITY;
+  int best = 0;
+  if (dsub <= PQ_MAX_DSUB) {
+    float xv[PQ_MAX_DSUB];
+#pragma unroll
+    for (int t = 0; t < PQ_MAX_DSUB; ++t) xv[t] = t < dsub ? xi[t] : 0.0f;
+    for (int c = 0; c < ksub; ++c) {
+      float acc = 0.0f;
+#pragma unroll
+      for (int t = 0; t < PQ_MAX_DSUB; ++t)
+        if (t < dsub) {
+          const float df = xv[t] - s_cb[c * dsub + t];
+          acc = __builtin_fmaf(df, df, acc);
+        }
+      if (acc < bs) {
+        bs = acc;
+        best = c;
+      }
+    }
+  } else {
+    l2_argmin_wide<false>(xi, nullptr, dsub, s_cb, 0, ksub, bs, best);
+  }
+  codes[(size_t)i * m + mi] = (uint8_t)best;
+}
+__global__ __launch_bounds__(256) void pq_encode_raw_rounds_kernel(
+    const float *__restrict__ x, const float *__restrict__ codebooks, int64_t n, int d, int m, int ksub,
+    int dsub, uint8_t *__restrict__ codes) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float *s_cb = reinterpret_cast<float *>(smem);
+  const int mi = blockIdx.y;
+  const float *cb = codebooks + (size_t)mi * ksub * dsub;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = i < n;
+  const float *xi = x + (size_t)(live ? i : 0) * d + (size_t)mi * dsub;
+  const int chunk = pq_cb_chunk(ksub, dsub);
+  float bs = INFINITY;
+  int best = 0;
+  for (int c0 = 0; c0 < ksub; c0 += chunk) {
+    const int nc = min(chunk, ksub - c0);
+    if (c0) __syncthreads();      // every lane is done with the codes before
+    for (int j = threadIdx.x; j < nc * dsub; j += 256) s_cb[j] = cb[(size_t)c0 * dsub + j];
+    __syncthreads();
+    if (live) l2_argmin_wide<false>(xi, nullptr, dsub, s_cb, c0, nc, bs, best);
+  }
+  if (live) codes[(size_t)i * m + mi] = (uint8_t)best;
+}
 int pq_encode(const float *x, const int32_t *assign, const float *centroids,
               const float *codebooks, int64_t n, int d, int m, int ksub, int dsub,
-              uint8_t *codes) {
+              uint8_t *codes, bool by_residual) {
   if (n <= 0) return ASL_OK;
   const int chunk = pq_cb_chunk(ksub, dsub);
   if (chunk < 1) return fail(ASL_ERR_CAPACITY, "pq_encode: a sub-vector of %d floats does not fit LDS", dsub);
-  hipLaunchKernelGGL(chunk == ksub ? pq_encode_kernel : pq_encode_rounds_kernel,
-                     dim3((unsigned)cdiv(n, 256), m), dim3(256), (size_t)chunk * dsub * 4, stream(), x,
-                     assign, centroids, codebooks, n, d, m, ksub, dsub, codes);
+  if (!by_residual)
+    hipLaunchKernelGGL(chunk == ksub ? pq_encode_raw_kernel : pq_encode_raw_rounds_kernel,
+                       dim3((unsigned)cdiv(n, 256), m), dim3(256), (size_t)chunk * dsub * 4, stream(), x,
+                       codebooks, n, d, m, ksub, dsub, codes);
+  else
+    hipLaunchKernelGGL(chunk == ksub ? pq_encode_kernel : pq_encode_rounds_kernel,
+                       dim3((unsigned)cdiv(n, 256), m), dim3(256), (size_t)chunk * dsub * 4, stream(), x,
+                       assign, centroids, codebooks, n, d, m, ksub, dsub, codes);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }

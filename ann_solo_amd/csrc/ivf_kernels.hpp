@@ -50,7 +50,7 @@ int residual(const float *x, const int32_t *assign, const float *centroids, int6
              float *dst);
 int pq_encode(const float *x, const int32_t *assign, const float *centroids,
               const float *codebooks, int64_t n, int d, int m, int ksub, int dsub,
-              uint8_t *codes);
+              uint8_t *codes, bool by_residual = true);   // false: x itself is encoded (assign / centroids unread)
 int pq_lut(const float *xq, int nq, int d, const float *codebooks, int m, int ksub, int dsub,
            float *lut_out);
 int pq_scan(const float *xq, int nq, int d, const float *codebooks, int m, int ksub, int dsub,

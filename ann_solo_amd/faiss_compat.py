@@ -305,6 +305,20 @@ class Index:
         """k' of the exact re-rank (0: off) -- also for an index read from a file."""
         return int(_lib.lib().asl_index_get_refine(self._h))
 
+    @property
+    def by_residual(self) -> bool:
+        """FAISS' ``IndexIVFPQ.by_residual``: True (default) -- the product quantiser codes the residuals
+        ``x - centroid[list]`` and a score is ``q . centroid + sum LUT``; False -- it codes the vectors
+        themselves and a score is ``sum LUT`` alone (the centroids still define the lists and the probes).
+        Set it before ``train`` / ``set_trained`` (``AnnSoloMiError`` afterwards, and on any other index
+        kind); an index read from a file reports the file's mode. True for non-PQ kinds."""
+        return bool(_lib.lib().asl_index_get_by_residual(self._h))
+
+    @by_residual.setter
+    def by_residual(self, on: bool):
+        self.epoch += 1
+        _lib.check(_lib.lib().asl_index_set_by_residual(self._h, int(bool(on))))
+
     def refine(self, x, I_in, k):
         """Exact re-rank of a short-list obtained elsewhere: (D [nq,k], I [nq,k])."""
         x = _as_f32(x, self.d)

@@ -286,6 +286,8 @@ class SpectralLibrary:
             d.update(pq_m=cfg.pq_m, pq_bits=cfg.pq_bits)
             if cfg.refine_k:
                 d.update(refine_k=cfg.refine_k)
+            if not cfg.pq_by_residual:      # (on: every file name as before the option existed)
+                d.update(pq_by_residual=False)
         return hashlib.sha1(json.dumps(d).encode('utf-8')).hexdigest()
 
     def _encode(self, spectra: PackedSpectra) -> torch.Tensor:
@@ -311,6 +313,8 @@ class SpectralLibrary:
             ann_index.set_niter(cfg.kmeans_niter)
             if cfg.index == 'ivfpq' and cfg.refine_k:
                 ann_index.set_refine(cfg.refine_k)
+            if cfg.index == 'ivfpq' and not cfg.pq_by_residual:
+                ann_index.by_residual = False
             ann_index.train(vectors)
             ann_index.add(vectors)
             if self._index_dir is not None:
@@ -323,7 +327,8 @@ class SpectralLibrary:
         kind = 2 if cfg.index == 'ivfpq' else 1
         return (i.kind == kind and i.d == cfg.hash_len and i.nlist == cfg.num_list and
                 i.ntotal == len(part.ids) and bool(i.trained) and i.shard_world == 1 and
-                (kind != 2 or (i.pq_m == cfg.pq_m and i.pq_ksub == (1 << cfg.pq_bits))) and
+                (kind != 2 or (i.pq_m == cfg.pq_m and i.pq_ksub == (1 << cfg.pq_bits) and
+                               idx.by_residual == bool(cfg.pq_by_residual))) and
                 (kind != 1 or idx.storage == cfg.flat_storage))
 
     def _get_ann_index(self, charge: int) -> faiss.Index:

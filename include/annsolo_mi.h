@@ -142,6 +142,20 @@ asl_index_t *asl_index_load(const char *path);
 /* k-means iterations (FAISS ClusteringParameters.niter, default 25) */
 int asl_index_set_niter(asl_index_t *idx, int32_t niter);
 
+/* FAISS' IndexIVFPQ::by_residual. on = 1 (default): the product quantiser is trained on, and encodes,
+ * the residuals x - centroid[list]; on = 0: the vectors as they are (the centroids still define the
+ * inverted lists and the probes). The inner-product score of a stored vector is FAISS'
+ *   dis0 + sum_m LUT[m][code_m],   LUT = q . codebook,
+ * with dis0 = q . centroid[list] when by_residual is on and dis0 = 0 when it is off: the scans are the
+ * same kernels in both modes, handed the coarse scores or zeros. IVF-PQ only (ASL_ERR_STATE on Flat /
+ * IVF-Flat) and only while the index is untrained (ASL_ERR_STATE afterwards: the codebooks belong to
+ * the mode they were trained or installed in). With 0, asl_index_set_trained installs quantisers for
+ * raw codes. The mode is the handle's own: it survives asl_index_reset, asl_index_shard and
+ * asl_index_save / asl_index_load (a raw index is written as file version 3, which earlier builds refuse). */
+int asl_index_set_by_residual(asl_index_t *idx, int32_t on);
+/* 1 or 0 as set or loaded; 1 for Flat / IVF-Flat (and a null handle). */
+int asl_index_get_by_residual(const asl_index_t *idx);
+
 /* Exact re-rank of the IVF-PQ short-list (FAISS IndexRefineFlat's role). kprime > 0, set BEFORE
  * add(): the index also keeps every added vector as a sparse fp32 row (<= 64 non-zeros, 384 B),
  * and asl_index_search / asl_search_batch with k < kprime let the ADC scan return kprime
@@ -366,7 +380,10 @@ int asl_lpt_owner(int32_t nlist, const int64_t *sizes, int32_t world, int32_t *o
  * emits; -1 entries are skipped). Used by the sharded search: every rank quantises only
  * its own slice of the batch, the probe lists are all-gathered, and each rank scans its
  * own inverted lists for the whole batch. IVF-PQ and IVF-Flat (which ignores coarse_D: its
- * scores do not contain the coarse term). */
+ * scores do not contain the coarse term). An IVF-PQ index with by_residual off
+ * (asl_index_set_by_residual) reads coarse_I alone, here and in asl_index_search_gated /
+ * asl_index_search_entries: the caller's coarse_D selects nothing and adds nothing (dis0 = 0).
+ * asl_index_coarse returns the real q . centroid in either mode. */
 int asl_index_search_preassigned(asl_index_t *idx, int32_t nq, const float *xq, int32_t k,
                                  int32_t nprobe, const float *coarse_D,
                                  const int32_t *coarse_I, float *D, int64_t *I);
