@@ -82,6 +82,7 @@ EXPORTS = [
     'asl_index_set_by_residual', 'asl_index_get_by_residual',
     'asl_library_set_groups', 'asl_rescore_batch_topn_distinct', 'asl_search_batch_topn_distinct',
     'asl_rescore_knn_topn_distinct',
+    'asl_profile_rescore_counts',
 ]
 
 
@@ -272,6 +273,8 @@ def lib():
         L.asl_set_window_pair_budget.restype = C.c_int64
         L.asl_profile_get.argtypes = [C.c_char_p, c_f64p, c_i64p]
         L.asl_profile_scanned_vectors.restype = C.c_int64
+        if hasattr(L, 'asl_profile_rescore_counts'):
+            L.asl_profile_rescore_counts.argtypes = [c_i64p, c_i64p, c_i64p]
         _lib = L
     return _lib
 

@@ -162,6 +162,17 @@ unsigned long long *prof_scanned_dev() {
   return g_scanned_dev;
 }
 
+// device-side counters of the rescoring (deferred, pruned, work-list items), fed at level 1 only
+static unsigned long long *g_rescore_dev = nullptr;
+unsigned long long *prof_rescore_dev() {
+  if (!g_rescore_dev) {
+    if (hipMalloc((void **)&g_rescore_dev, 3 * sizeof(unsigned long long)) != hipSuccess) return nullptr;
+    // (on the null stream, and waited for: the counting launches may go to any stream)
+    if (hipMemset(g_rescore_dev, 0, 3 * sizeof(unsigned long long)) != hipSuccess) return nullptr;
+  }
+  return g_rescore_dev;
+}
+
 static void prof_collect(StageProf &sp) {
   for (auto &ev : sp.pending) {
     float ms = 0;
@@ -231,6 +242,10 @@ int asl_profile_reset(void) {
   }
   g_scanned = 0;
   if (g_scanned_dev) (void)hipMemsetAsync(g_scanned_dev, 0, sizeof(unsigned long long), g_stream);
+  if (g_rescore_dev) {      // (waited for: the counting launches may go to streams that do not wait for this one)
+    (void)hipMemsetAsync(g_rescore_dev, 0, 3 * sizeof(unsigned long long), g_stream);
+    (void)hipStreamSynchronize(g_stream);
+  }
   return ASL_OK;
 }
 
@@ -252,6 +267,20 @@ int64_t asl_profile_scanned_vectors(void) {
   if (g_scanned_dev && hipMemcpyAsync(&dev, g_scanned_dev, sizeof(dev), hipMemcpyDeviceToHost, g_stream) == hipSuccess)
     (void)hipStreamSynchronize(g_stream);
   return g_scanned + (int64_t)dev;
+}
+
+int asl_profile_rescore_counts(int64_t *deferred, int64_t *pruned, int64_t *work_items) {
+  clear_error();
+  unsigned long long h[3] = {0, 0, 0};
+  if (g_rescore_dev) {
+    ASL_TRY(ensure_device());   // batches of the pipeline still in flight count too
+    HIP_TRY(hipMemcpyAsync(h, g_rescore_dev, sizeof h, hipMemcpyDeviceToHost, g_stream));
+    HIP_TRY(hipStreamSynchronize(g_stream));
+  }
+  if (deferred) *deferred = (int64_t)h[0];
+  if (pruned) *pruned = (int64_t)h[1];
+  if (work_items) *work_items = (int64_t)h[2];
+  return ASL_OK;
 }
 
 }  // extern "C"

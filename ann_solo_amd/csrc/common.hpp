@@ -177,6 +177,9 @@ struct ProfScope {
 };
 void prof_add_scanned(int64_t vectors);
 unsigned long long *prof_scanned_dev();   // device accumulator (nullptr on allocation failure)
+// the rescoring's deferred / pruned candidates and work-list items since the last asl_profile_reset
+// (device accumulator, [3]; nullptr on allocation failure): kernels get it only where prof_counts()
+unsigned long long *prof_rescore_dev();
 bool prof_enabled();
 bool prof_counts();
 

@@ -9,7 +9,9 @@
 // testing the bitmap for every shift; the (peak, shift) items whose bin is marked are queued
 // and probed -- hash walk, exact window / cursor predicate -- a full row of lanes at a time;
 // a match is accumulated where it is found (LDS atomics: masks of matched peaks, exponent
-// range, exact fp64 sum). Candidates with a doubly matched peak are marked for
+// range, exact fp64 sum). Candidates with a doubly matched peak are marked -- unless, in a winner-only
+// request, the sum of all their matches already shows that they cannot reach the query's best score
+// (RS_PRUNED) -- and the queries that still have some are put on a work list for
 // Pass 1b (rescore_score_v2_kernel, the pair kernel): two candidates per wave, one per
 // half-wave, matches into per-half LDS lists keyed (product desc, generation order asc),
 // resolved by a conflict-free fast path or a bitonic sort + scalar greedy loop. What neither
@@ -27,6 +29,7 @@
 // Arithmetic mirrors the reference: window tests in double on float->double
 // promoted m/z (cpp:42,53); product = (float)(mult * (double)q_int * (double)c_int)
 // (cpp:81); score = double sum of those floats in sorted order (cpp:104).
+#include <atomic>
 #include <cstdlib>
 
 #include "common.hpp"
@@ -392,9 +395,26 @@ constexpr int RS_PF = 2;              // candidates staged per burst
 constexpr int RS_HC = 64;             // matches per candidate resolved in this kernel
 constexpr double RS_DEFER = -2.0;     // pair_score marker: left to the pair kernel (second launch)
 constexpr double RS_DEFER_BS = -3.0;  // pair_score marker: left to the binary-search kernel (third launch)
+// pair_score marker: a valid candidate whose score was not computed because it cannot reach the
+// query's best score (winner-only requests: rescore_flat_kernel's epilogue). Counts as scored.
+constexpr double RS_PRUNED = -4.0;
 enum { RS_QD_PAIR = 1, RS_QD_BS = 2 };   // q_defer bits: the query has slots marked RS_DEFER / RS_DEFER_BS;
                                          // bits 2.. count the RS_DEFER slots (work split of the second launch)
-constexpr int RS_DEF_Y = 8;             // blocks per query the second launch may use
+
+// blocks of the second launch a query with n_defer slots marked RS_DEFER gets: one pair step per wave
+__device__ __forceinline__ int rs_pair_blocks(int n_defer, int ymax) {
+  const int want = (n_defer + 2 * RS_WAVES - 1) / (2 * RS_WAVES);
+  return want < ymax ? want : ymax;
+}
+// appends a query's items to the second launch's work list (RescoreScratch: q_defer + nq is the count)
+__device__ __forceinline__ int rs_append_items(int *__restrict__ q_defer, int nq, int q, int n_defer, int ymax) {
+  const int ny = rs_pair_blocks(n_defer, ymax);
+  if (ny <= 0) return 0;
+  const int at = atomicAdd(&q_defer[nq], ny);
+  int2 *items = reinterpret_cast<int2 *>(q_defer + ((nq + 2) & ~1));
+  for (int y = 0; y < ny; ++y) items[at + y] = make_int2(q, y | (ny << 8));
+  return ny;
+}
 
 // The bin filter's numeric envelope. The fast kernels compute the bin of a shifted candidate peak
 // in fp32, b = floorf(fl(fl(cm + fl(md)) * fl(inv_w))) with inv_w = 1 / (2 tol), where the exact
@@ -660,55 +680,22 @@ __device__ __forceinline__ void score_two(int lane, const QueryLds2 &Q, const Ha
 // 3: the window-only modes' CSR runs of the precursor-sorted view (CandView::win_begin) --
 // are compiled with those facts folded in (each open "is this pointer null" question is a
 // wave-uniform predicate held in scalar registers across the hot loops); 0 = any shape but 3.
-// DEF: second-launch mode behind rescore_flat_kernel -- only the slots that kernel marked
-// RS_DEFER, only for queries whose q_defer has RS_QD_PAIR; what this kernel cannot resolve
-// either goes on to the binary-search kernel (RS_DEFER_BS / RS_QD_BS).
-template <int FORM, bool DEF = false>
-__global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel(
-    DevPeaks Qs, DevPeaks L, CandView cv, double tol, int allow_shift,
-    double *__restrict__ pair_score, int *__restrict__ q_defer, int *status) {
-  // DEF: a query's deferred slots are few (a handful) or nearly all of its candidates (two
-  // query peaks closer than the tolerance make every candidate with a peak there a conflict):
-  // as many of the launch's blocks per query take part as there is work for, the others leave
-  int ny = (int)gridDim.y;
-  if (DEF) {
-    const int qd = q_defer[blockIdx.x];
-    if (!(qd & RS_QD_PAIR)) return;
-    const int want = ((qd >> 2) + 2 * RS_WAVES - 1) / (2 * RS_WAVES);     // one pair step per wave
-    ny = want < ny ? want : ny;
-    if ((int)blockIdx.y >= ny) return;
-  }
-  cv.flt.wcol = nullptr;      // this kernel wants filter column and metadata from ONE gather
-  if (FORM != 3) cv.win_begin = nullptr;
-  if (FORM == 3) {            // window-only lists: a run of the precursor-sorted view per query
-    cv.rows64 = nullptr;
-    cv.rows32 = nullptr;
-    cv.counts = nullptr;
-    cv.flt.lib_pmz = nullptr;
-    cv.flt.valid = nullptr;
-    cv.flt.pass_all = true;
-    __builtin_assume(cv.offsets != nullptr);
-    __builtin_assume(cv.win_begin != nullptr);
-    __builtin_assume(cv.flt.meta != nullptr);
-    __builtin_assume(L.charge != nullptr);
-  } else if (FORM != 0) {
-    cv.offsets = nullptr;
-    cv.flt.lib_pmz = nullptr;
-    cv.flt.valid = nullptr;
-    __builtin_assume(cv.flt.meta != nullptr);
-    __builtin_assume(L.charge != nullptr);
-    if (FORM == 1) {
-      cv.rows64 = nullptr;
-    } else {
-      __builtin_assume(cv.rows64 != nullptr);
-    }
-  }
-  __shared__ QueryLds2 Q;
-  __shared__ HashLds H;
-  __shared__ PairLds W[RS_WAVES];
-  __shared__ uint16_t s_list[RS_SUPER];
-  __shared__ int s_nv, s_defer;
-  const int q = blockIdx.x;
+// The kernel is the SECOND LAUNCH behind rescore_flat_kernel: it scores only the slots that kernel
+// marked RS_DEFER; what it cannot resolve either goes on to the binary-search kernel (RS_DEFER_BS /
+// RS_QD_BS). Its work is the list the first launch left in q_defer (RescoreScratch): an item is
+// (query, y, ny) -- a query's deferred slots are few (a handful: one item) or nearly all of its
+// candidates (two query peaks closer than the tolerance make every candidate with a peak there a
+// conflict: up to RS_DEF_Y items, block y takes the slots of every ny-th group of 32). The grid is
+// as many blocks as the device holds at once; block b walks items b, b + gridDim.x, ...
+//
+// One item. The block's LDS structures are rebuilt per item (the caller puts a barrier in between).
+template <int FORM>
+__device__ __forceinline__ void pair_item(const int q, const int y, const int ny, const DevPeaks &Qs,
+                                          const DevPeaks &L, const CandView &cv, const double tol,
+                                          const int allow_shift, double *__restrict__ pair_score,
+                                          int *__restrict__ q_defer, int *status, QueryLds2 &Q, HashLds &H,
+                                          PairLds (&W)[RS_WAVES], uint16_t (&s_list)[RS_SUPER], int &s_nv,
+                                          int &s_defer) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   long long c0, c1;
   cv.range(q, c0, c1);
@@ -718,10 +705,11 @@ __global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel
   const double q_pmz = Qs.precursor_mz[q];
   // fp32 evaluation of a probe bin: its error bound in bin units (rs_bin_margin); the query
   // peaks are filed with that margin on both sides (still <= 3 bins per peak)
-  auto defer_query = [&]() {      // uniform: the whole query goes to the binary-search kernel
-    for (long long c = c0 + (long long)blockIdx.y * blockDim.x + tid; c < c1;
-         c += (long long)blockDim.x * gridDim.y) {
-      pair_score[c] = cv.cand(q, c, q_pmz, L.n) >= 0 ? RS_DEFER_BS : -1.0;
+  // (the first launch applies the same tests and sends such a query to the binary-search kernel
+  // whole, so none is on the work list; should one be, its deferred slots follow)
+  auto defer_query = [&]() {      // uniform
+    for (long long c = c0 + (long long)y * blockDim.x + tid; c < c1; c += (long long)blockDim.x * ny) {
+      if (pair_score[c] == RS_DEFER) pair_score[c] = RS_DEFER_BS;
     }
     if (tid == 0) atomicOr(&q_defer[q], RS_QD_BS);
   };
@@ -777,15 +765,10 @@ __global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel
       const int i = i0 + tid;
       bool ok = false;
       if (i < sn) {
-        if (DEF) {
-          ok = pair_score[sb + i] == RS_DEFER;     // a valid candidate: the first launch checked
-        } else {
-          ok = cv.cand(q, sb + i, q_pmz, L.n) >= 0;
-          if (!ok && blockIdx.y == 0) pair_score[sb + i] = -1.0;
-        }
+        ok = pair_score[sb + i] == RS_DEFER;     // a valid candidate: the first launch checked
         // several blocks per query: each takes the slots of every ny-th group of 32 (the order
         // inside s_list depends on the waves' timing, so blocks must not split it by position)
-        ok = ok && (ny == 1 || ((i >> 5) % ny) == (int)blockIdx.y);
+        ok = ok && (ny == 1 || ((i >> 5) % ny) == y);
       }
       const unsigned long long bal = __ballot(ok);
       int wbase = 0;
@@ -877,6 +860,53 @@ __global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel
   if (tid == 0 && s_defer) atomicOr(&q_defer[q], RS_QD_BS);
 }
 
+template <int FORM>
+__global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel(
+    DevPeaks Qs, DevPeaks L, CandView cv, double tol, int allow_shift,
+    double *__restrict__ pair_score, int *__restrict__ q_defer, int *status) {
+  cv.flt.wcol = nullptr;      // this kernel wants filter column and metadata from ONE gather
+  if (FORM != 3) cv.win_begin = nullptr;
+  if (FORM == 3) {            // window-only lists: a run of the precursor-sorted view per query
+    cv.rows64 = nullptr;
+    cv.rows32 = nullptr;
+    cv.counts = nullptr;
+    cv.flt.lib_pmz = nullptr;
+    cv.flt.valid = nullptr;
+    cv.flt.pass_all = true;
+    __builtin_assume(cv.offsets != nullptr);
+    __builtin_assume(cv.win_begin != nullptr);
+    __builtin_assume(cv.flt.meta != nullptr);
+    __builtin_assume(L.charge != nullptr);
+  } else if (FORM != 0) {
+    cv.offsets = nullptr;
+    cv.flt.lib_pmz = nullptr;
+    cv.flt.valid = nullptr;
+    __builtin_assume(cv.flt.meta != nullptr);
+    __builtin_assume(L.charge != nullptr);
+    if (FORM == 1) {
+      cv.rows64 = nullptr;
+    } else {
+      __builtin_assume(cv.rows64 != nullptr);
+    }
+  }
+  __shared__ QueryLds2 Q;
+  __shared__ HashLds H;
+  __shared__ PairLds W[RS_WAVES];
+  __shared__ uint16_t s_list[RS_SUPER];
+  __shared__ int s_nv, s_defer;
+  const int nq = Qs.n;
+  // (block-uniform values, said so: the query and all that follows from it stay in scalar registers)
+  const int n_items = __builtin_amdgcn_readfirstlane(q_defer[nq]);
+  const int2 *items = reinterpret_cast<const int2 *>(q_defer + ((nq + 2) & ~1));
+  for (int it = (int)blockIdx.x; it < n_items; it += (int)gridDim.x) {
+    if (it != (int)blockIdx.x) __syncthreads();      // the previous item's tables are no longer read
+    const int2 w = items[it];
+    const int wq = __builtin_amdgcn_readfirstlane(w.x), wy = __builtin_amdgcn_readfirstlane(w.y);
+    pair_item<FORM>(wq, wy & 0xff, wy >> 8, Qs, L, cv, tol, allow_shift, pair_score, q_defer, status, Q, H, W,
+                    s_list, s_nv, s_defer);
+  }
+}
+
 // ---------------------------------------------------------------------------------
 // Pass 1, FLAT formulation (the first launch of the search path). The pair kernel above spends
 // two thirds of its instructions outside the probing loop: per pair of candidates it stages
@@ -918,11 +948,24 @@ struct FlatLds {   // per wave
   uint16_t mq[RF_MQ];              // queued (peak | shift << 10) items whose bin is marked
 };
 
+// Winner-only requests (`prune`, one block per query): a candidate deferred for a doubly matched
+// peak or a wide exponent span still has, in sum[], the sum of ALL its generated matches -- an upper
+// bound of its score, which is the sum of a subset of the same non-negative products (DESIGN.md
+// section 3). Such candidates are listed in LDS with their bounds instead of being marked at once; the
+// block keeps the maximum of the exact scores it writes, and after the last chunk a listed candidate
+// whose bound lies below that maximum (by more than the rounding of the two sums: RS_PRUNE_REL /
+// _ABS) becomes RS_PRUNED, the others RS_DEFER. A candidate the list has no room for, one with a
+// negative or NaN product (emax bit 30: the subset argument needs products >= 0), and one deferred
+// before anything was accumulated (def_pair, def_bs) are never pruned.
+// The epilogue also puts the query's surviving deferred slots on the second launch's work list.
+constexpr int RF_DLIST = 256;    // deferred candidates per query that can be pruned
+constexpr double RS_PRUNE_REL = 1e-9, RS_PRUNE_ABS = 1e-12;
 constexpr int RF_OCC = 6;      // waves per SIMD: 80 VGPRs (7 / 8: 72 / 64 VGPRs and more spills: +2 % / +12 %, profiles/r03_rescore_ab.txt)
 template <int FORM>
 __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
     DevPeaks Qs, DevPeaks L, CandView cv, double tol, int allow_shift,
-    double *__restrict__ pair_score, int *__restrict__ q_defer, int *status) {
+    double *__restrict__ pair_score, int *__restrict__ q_defer, int *status, int prune, int ymax,
+    unsigned long long *__restrict__ counts) {
   if (FORM != 3) cv.win_begin = nullptr;
   if (FORM == 3) {            // window-only lists: a run of the precursor-sorted view per query
     cv.rows64 = nullptr;
@@ -955,7 +998,10 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
   __shared__ HashLds H;
   __shared__ FlatLds W[RS_WAVES];
   __shared__ uint16_t s_list[RS_SUPER];
-  __shared__ int s_nv, s_defer, s_ndef;
+  __shared__ int s_nv, s_defer, s_ndef, s_nlist, s_npruned;
+  __shared__ unsigned long long s_best;      // largest exact score written (>= 0: orders as u64)
+  __shared__ double s_dbound[RF_DLIST];
+  __shared__ uint32_t s_dslot[RF_DLIST];     // the listed candidate's slot - c0
   const int q = blockIdx.x;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   long long c0, c1;
@@ -991,7 +1037,10 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
   }
   for (int i = tid; i < RS_HT; i += blockDim.x) H.bin[i] = RS_EMPTY;
   for (int i = tid; i < RS_BM_BITS / 32; i += blockDim.x) H.bm[i] = 0u;
-  if (tid == 0) s_defer = s_ndef = 0;
+  if (tid == 0) {
+    s_defer = s_ndef = s_nlist = s_npruned = 0;
+    s_best = 0ull;
+  }
   __syncthreads();
   // the margin of this query's own m/z range, from the peaks just loaded (no extra trip to memory
   // in front of the load); beyond RS_MARGIN_MAX the query leaves the hash path (uniform)
@@ -1200,7 +1249,11 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
                     const uint32_t qb = 1u << (i & 31), cb = 1u << (j & 31);
                     const uint32_t oq = atomicOr(&Wv.qmask[tt][i >> 5], qb);
                     const uint32_t oc = atomicOr(&Wv.cmask[tt][j >> 5], cb);
-                    atomicMax(&Wv.emax[tt], ((oq & qb) || (oc & cb)) ? (0x80000000u | e) : e);
+                    // bit 31: a doubly matched peak; bits 31 + 30: a negative or NaN product (no
+                    // exact order-free sum AND no upper bound; both bits, so that the max keeps them)
+                    atomicMax(&Wv.emax[tt], !(prod >= 0.0f)               ? (0xC0000000u | e)
+                                            : ((oq & qb) || (oc & cb)) ? (0x80000000u | e)
+                                                                       : e);
                     atomicMin(&Wv.emin[tt], e);
                     atomicAdd(&Wv.sum[tt], (double)prod);
                   }
@@ -1246,10 +1299,27 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
       if (take && hi == 0) {
         const uint32_t em = Wv.emax[t], en = Wv.emin[t];
         double sc = Wv.sum[t];
-        if ((em >> 31) || ((em & 0xffu) > en + 23u)) sc = RS_DEFER;     // sort + greedy pass needed
+        bool listed = false;
+        if ((em >> 31) || ((em & 0xffu) > en + 23u)) {     // sort + greedy pass needed
+          if (prune && !(em & 0x40000000u) && !def_pair && !def_bs) {   // sum[t] bounds the score: the epilogue decides
+            const int k = atomicAdd(&s_nlist, 1);
+            if (k < RF_DLIST) {
+              s_dbound[k] = sc;
+              s_dslot[k] = (uint32_t)(sb - c0) + (uint32_t)slot;
+              listed = true;
+            }
+          }
+          sc = RS_DEFER;
+        }
         if (def_pair) sc = RS_DEFER;
         if (def_bs) sc = RS_DEFER_BS;
-        pair_score[sb + slot] = sc;
+        if (!listed) pair_score[sb + slot] = sc;
+        // (read first: after a query's first chunks hardly any score passes the maximum, and 32 lanes'
+        // atomics on one address are served one by one; a stale read only costs a needless atomic)
+        if (prune && sc >= 0.0) {
+          const unsigned long long bits = (unsigned long long)__double_as_longlong(sc);
+          if (bits > s_best) atomicMax(&s_best, bits);
+        }
         if (sc == RS_DEFER) {
           atomicOr(&s_defer, RS_QD_PAIR);
           atomicAdd(&s_ndef, 1);
@@ -1261,10 +1331,48 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
     }
     __syncthreads();   // s_list is rebuilt for the next super-chunk
   }
-  if (tid == 0 && s_defer) {      // (several blocks per query when gridDim.y > 1: or + add)
-    atomicOr(&q_defer[q], s_defer);
-    if (s_ndef) atomicAdd(&q_defer[q], s_ndef << 2);
+  // ---- the verdicts of the listed candidates, against the final best exact score (the loop's last
+  // barrier has made every wave's list entries and maximum visible)
+  const int nlist = s_nlist < RF_DLIST ? s_nlist : RF_DLIST;      // block-uniform; 0 unless `prune`
+  if (nlist) {
+    const double best = __longlong_as_double((long long)s_best);
+    for (int k0 = 0; k0 < nlist; k0 += blockDim.x) {
+      const int k = k0 + tid;
+      bool out = false;
+      if (k < nlist) {
+        out = s_dbound[k] * (1.0 + RS_PRUNE_REL) + RS_PRUNE_ABS < best;
+        pair_score[c0 + s_dslot[k]] = out ? RS_PRUNED : RS_DEFER;
+      }
+      const unsigned long long bal = __ballot(out);
+      if (lane == 0 && bal) atomicAdd(&s_npruned, __popcll(bal));
+    }
+    __syncthreads();
   }
+  if (tid == 0 && s_defer) {      // (several blocks per query when gridDim.y > 1: or + add)
+    const int left = s_ndef - s_npruned;
+    atomicOr(&q_defer[q], left ? s_defer : (s_defer & ~RS_QD_PAIR));
+    if (left) atomicAdd(&q_defer[q], left << 2);
+    // one block per query: its count is final, the query's items go on the work list here
+    // (gridDim.y > 1: rescore_worklist_kernel, once every block's count is in)
+    const int items = gridDim.y == 1 ? rs_append_items(q_defer, Qs.n, q, left, ymax) : 0;
+    if (counts) {
+      atomicAdd(&counts[0], (unsigned long long)s_ndef);
+      atomicAdd(&counts[1], (unsigned long long)s_npruned);
+      atomicAdd(&counts[2], (unsigned long long)items);
+    }
+  }
+}
+
+// The work list of the second launch where several blocks shared a query in the first (few queries
+// with long lists): one thread per query, after the first launch.
+__global__ void rescore_worklist_kernel(int *__restrict__ q_defer, int nq, int ymax,
+                                        unsigned long long *__restrict__ counts) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  const int qd = q_defer[q];
+  if (!(qd & RS_QD_PAIR)) return;
+  const int items = rs_append_items(q_defer, nq, q, qd >> 2, ymax);
+  if (counts) atomicAdd(&counts[2], (unsigned long long)items);
 }
 
 // tie_by_row = 0: first position wins ties (get_best_match on a caller-ordered list);
@@ -1283,7 +1391,10 @@ __global__ __launch_bounds__(64) void rescore_argmax_kernel(
   int cnt = 0;
   for (long long c = c0 + lane; c < c1; c += 64) {
     const double s = pair_score[c];
-    if (s < 0.0) continue;
+    if (s < 0.0) {
+      if (s == RS_PRUNED) ++cnt;      // a valid candidate below the best score: counted, never compared
+      continue;
+    }
     ++cnt;
     const long long key = tie_by_row ? cv.row(q, c) : c;
     if (s > bs || (s == bs && key < bkey)) {
@@ -1399,6 +1510,36 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_matches_kernel(
   }
 }
 
+// ASL_RESCORE_PRUNE=0 keeps every deferred candidate for the pair kernel (A/B runs of one build);
+// read once.
+static bool rescore_prune_enabled() {
+  static const bool on = [] {
+    const char *e = getenv("ASL_RESCORE_PRUNE");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
+
+// Grid of the second launch: the blocks of the pair kernel the device holds at once (they walk the
+// work list; more would only queue up to find it empty).
+static int pair_resident_blocks(int form, const void *kern, int *blocks) {
+  constexpr int MAX_DEV = 64;
+  static std::atomic<int> cached[MAX_DEV][4];      // per device and form; 0: not asked yet
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  const bool slot = dev >= 0 && dev < MAX_DEV;
+  int n = slot ? cached[dev][form].load(std::memory_order_relaxed) : 0;
+  if (!n) {
+    int cus = 0, per_cu = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * RS_WAVES, 0));
+    n = std::max(cus * per_cu, 1);
+    if (slot) cached[dev][form].store(n, std::memory_order_relaxed);   // (every thread computes the same value)
+  }
+  *blocks = n;
+  return ASL_OK;
+}
+
 // Host driver shared by asl_rescore_batch and asl_search_batch (rescore.hpp: RescoreRequest).
 int rescore_device(const RescoreRequest &rq) {
   const DevPeaks &Q = rq.Q, &L = rq.L;
@@ -1424,24 +1565,38 @@ int rescore_device(const RescoreRequest &rq) {
     {
       // hash kernel, then the binary-search kernel on whatever it deferred (its blocks
       // return at once for queries with nothing deferred)
-      ASL_TRY(q_defer.reserve((size_t)nq));
-      HIP_TRY(hipMemsetAsync(q_defer.p, 0, sizeof(int) * (size_t)nq, stream()));
+      // the second launch may use more blocks per query where the first one splits the lists
+      const int ymax = std::max(ysplit, RS_DEF_Y);
+      ASL_TRY(q_defer.reserve(RescoreScratch::defer_ints((size_t)nq, ymax)));
+      HIP_TRY(hipMemsetAsync(q_defer.p, 0, sizeof(int) * ((size_t)nq + 1), stream()));   // flags + item count
       const bool shaped = !cand.offsets && filter.meta && filter.wcol && L.charge && L.records &&
                           (cand.rows64 || cand.rows32);
-      // 1. flat kernel; 2. pair kernel on what it marked RS_DEFER; 3. binary-search kernel on
-      // RS_DEFER_BS (blocks of 2 / 3 return at once for queries without such slots)
-      auto flat = cand.window ? rescore_flat_kernel<3>
-                  : !shaped   ? rescore_flat_kernel<0>
-                  : cand.rows64 ? rescore_flat_kernel<2> : rescore_flat_kernel<1>;
+      const int form = cand.window ? 3 : !shaped ? 0 : cand.rows64 ? 2 : 1;
+      // Pruning (rescore_flat_kernel) is for the single winner, decided by the one block that sees all
+      // of a query's candidates: ranked requests and split lists never meet RS_PRUNED
+      const int prune = (n_best == 0 && ysplit == 1 && rescore_prune_enabled()) ? 1 : 0;
+      unsigned long long *counts = prof_counts() ? prof_rescore_dev() : nullptr;
+      // 1. flat kernel; 2. pair kernel over the work list of what it marked RS_DEFER; 3. binary-search
+      // kernel on RS_DEFER_BS (its blocks return at once for queries without such slots)
+      auto flat = form == 3 ? rescore_flat_kernel<3>
+                  : form == 0 ? rescore_flat_kernel<0>
+                  : form == 2 ? rescore_flat_kernel<2> : rescore_flat_kernel<1>;
       hipLaunchKernelGGL(flat, dim3(nq, ysplit), dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, rq.tol,
-                         rq.allow_shift, rq.pair_score, q_defer.p, rq.status);
+                         rq.allow_shift, rq.pair_score, q_defer.p, rq.status, prune, ymax, counts);
       ASL_CHECK_LAUNCH();
-      auto kern = cand.window ? rescore_score_v2_kernel<3, true>
-                  : !shaped   ? rescore_score_v2_kernel<0, true>
-                  : cand.rows64 ? rescore_score_v2_kernel<2, true>
-                                : rescore_score_v2_kernel<1, true>;
-      hipLaunchKernelGGL(kern, dim3(nq, std::max(ysplit, RS_DEF_Y)), dim3(64 * RS_WAVES), 0, stream(), Q,
-                         L, cv, rq.tol, rq.allow_shift, rq.pair_score, q_defer.p, rq.status);
+      if (ysplit > 1) {
+        hipLaunchKernelGGL(rescore_worklist_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(),
+                           q_defer.p, nq, ymax, counts);
+        ASL_CHECK_LAUNCH();
+      }
+      auto kern = form == 3 ? rescore_score_v2_kernel<3>
+                  : form == 0 ? rescore_score_v2_kernel<0>
+                  : form == 2 ? rescore_score_v2_kernel<2> : rescore_score_v2_kernel<1>;
+      int pair_grid = 0;
+      ASL_TRY(pair_resident_blocks(form, (const void *)kern, &pair_grid));
+      hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(pair_grid, (int64_t)nq * ymax)),
+                         dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, rq.tol, rq.allow_shift, rq.pair_score,
+                         q_defer.p, rq.status);
       ASL_CHECK_LAUNCH();
       // (small batches keep a workgroup per query: when every query is marked -- tol <= 0, queries
       // of more than 100 peaks -- they need all the parallelism there is)

@@ -61,8 +61,15 @@ __device__ __forceinline__ bool filter_pass(const PrecFilter &f, double q_pmz, l
 // one). Owned by whoever owns the stream the launches go to -- a library handle (its batches are
 // issued in order on its own stream) or a one-shot call -- so that two handles pipelined on
 // different streams never share, or re-allocate under each other, a buffer in flight.
+//
+// q_defer also carries the work list of the second launch (the pair kernel), so that one memset
+// clears both: [nq] per-query flags, [1] the number of items on the list, then (from the next even
+// index) the items, two ints each -- (query, y | ny << 8): block y of the ny blocks that share the
+// query's deferred slots.
+constexpr int RS_DEF_Y = 8;             // blocks per query the second launch may use
 struct RescoreScratch {
   DevBuf<int> q_defer, m_defer;
+  static size_t defer_ints(size_t nq, int ymax = RS_DEF_Y) { return nq + 2 + 2 * nq * (size_t)ymax; }
 };
 
 // Window-only candidate lists (asl_search_batch with use_ann = 0): no list of row ids, a query's

@@ -426,7 +426,7 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
   // every buffer before the first launch (growing one synchronises the device)
   // (the winners' pass after several tiles scores one slot per winner)
   ASL_TRY(L->pair_score.reserve((size_t)(total <= B ? total : std::max<int64_t>(B, (int64_t)nw))));
-  ASL_TRY(L->rs_scratch.q_defer.reserve((size_t)nq));
+  ASL_TRY(L->rs_scratch.q_defer.reserve(RescoreScratch::defer_ints((size_t)nq)));
   ASL_TRY(L->rs_scratch.m_defer.reserve(nw));
   if (total <= B) {   // one tile: the whole batch
     std::vector<int32_t> h((size_t)2 * nq + 1);

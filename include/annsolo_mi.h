@@ -645,6 +645,12 @@ int asl_profile_get(const char *stage, double *total_ms, int64_t *launches);
 /* Algorithmic work of the scan kernels since the last reset: sum over queries of
  * probed-list lengths (vectors scored). */
 int64_t asl_profile_scanned_vectors(void);
+/* The rescoring's second launch since the last reset, counted at level 1 only (all three stay 0
+ * otherwise; any pointer may be null): candidates the first kernel could not score itself
+ * (a doubly matched peak, ...), those of them it dropped because their upper bound lies below the
+ * query's best exact score (winner-only calls; ASL_RESCORE_PRUNE=0 in the environment keeps them
+ * all), and the items of the second launch's work list. */
+int asl_profile_rescore_counts(int64_t *deferred, int64_t *pruned, int64_t *work_items);
 
 #ifdef __cplusplus
 }
