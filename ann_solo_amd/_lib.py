@@ -83,6 +83,7 @@ EXPORTS = [
     'asl_library_set_groups', 'asl_rescore_batch_topn_distinct', 'asl_search_batch_topn_distinct',
     'asl_rescore_knn_topn_distinct',
     'asl_profile_rescore_counts',
+    'asl_library_set_selection', 'asl_index_set_selector', 'asl_index_search_selected',
 ]
 
 
@@ -262,6 +263,12 @@ def lib():
                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
             L.asl_search_batch_topn_distinct.argtypes = L.asl_search_batch_topn.argtypes
             L.asl_rescore_knn_topn_distinct.argtypes = L.asl_rescore_knn_topn.argtypes
+        if hasattr(L, 'asl_library_set_selection'):
+            L.asl_library_set_selection.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+            L.asl_index_set_selector.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+            L.asl_index_search_selected.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                                    C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                    C.c_void_p]
         if hasattr(L, 'asl_index_set_by_residual'):
             L.asl_index_set_by_residual.argtypes = [C.c_void_p, C.c_int32]
             L.asl_index_get_by_residual.argtypes = [C.c_void_p]

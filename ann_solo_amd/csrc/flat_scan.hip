@@ -124,7 +124,13 @@ struct FiUnit {
 // query value: a power of two, exact) -- so ids and score bits equal the oracle's over the same
 // stored vectors. Measured on the bench library (scripts/flat_layout_model.py): 13 135 -> 8 980
 // lines per query at nprobe 112, and the row loop loses one of its two loads.
-template <int FI_CAP, bool FX, bool WIDE>
+//
+// SEL (asl_index_search_selected, a library's selection; the 2048-key instantiations only): sel holds
+// FI_ROWS 64-bit words per block, bit v of word r = the vector at position r * 64 + v of the block is
+// selected. The wave loads a block's words once (lanes 0 .. FI_ROWS - 1, one word each) and every lane
+// keeps the FI_ROWS bits of its own positions; an unselected vector is accumulated like any other and
+// never counted or offered: wherever a position is tested with v < nb, its bit is tested too.
+template <int FI_CAP, bool FX, bool WIDE, bool SEL = false>
 __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_kernel(
     const float *__restrict__ xq, int d, const int32_t *__restrict__ coarse_I, int nprobe,
     const int32_t *__restrict__ list_offsets, const int32_t *__restrict__ blk_offsets,
@@ -132,7 +138,8 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
     const char *__restrict__ seg_bytes, const int32_t *__restrict__ ids, int k,
     float *__restrict__ D, int64_t *__restrict__ I64, int32_t *__restrict__ I32, int set_mode,
     const uint2 *__restrict__ ent, const int32_t *__restrict__ ent_cnt, int tab_stride,
-    const int *__restrict__ gate, const ScanPostFilter pf) {
+    const int *__restrict__ gate, const ScanPostFilter pf, const unsigned long long *__restrict__ sel) {
+  static_assert(!SEL || FI_CAP <= 2048, "the selector is built into the 2048-key instantiations only");
   if (gate && (int)blockIdx.x >= *gate) return;      // device-side row count (see pq_scan_v3_kernel)
   constexpr float FX_SCALE = FX ? 1.0f / 4194304.0f : 1.0f;      // 2^-22, folded into the query values
   using TopK = HistTopK<FI_CAP, FI_NT, FI_NT>;
@@ -250,6 +257,8 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
     bool first = true;
     for (int i = wave;; first = false) {
       int nb = 0, pos0 = 0;
+      uint32_t selbits = 0;    // SEL: bit r = my position of row r (r * 64 + lane) is selected
+      auto sel_ok = [&](int r) -> bool { return !SEL || ((selbits >> r) & 1u) != 0; };
       if (i < nent) {          // wave-uniform
         const FiUnit u = table[i];
         nb = __builtin_amdgcn_readfirstlane((int)s_nbv[i]);
@@ -257,6 +266,11 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
         const uint32_t blk = (uint32_t)__builtin_amdgcn_readfirstlane((int)u.blk);
         const char *bptr = seg_bytes + (size_t)blk_base[blk] * (FX ? 128 : 64);     // (a scalar load: blk is wave-uniform)
         for (int o = lane; o < nb; o += 64) acc[o] = 0.0f;
+        // SEL: the block's words are requested here and used behind the row loop, which hides their latency
+        // (requested there, the scan at nprobe 112 ran 2 % slower: DESIGN.md 5 "Subset search")
+        unsigned long long w = 0ull;
+        if constexpr (SEL)
+          if (lane < FI_ROWS) w = sel[(size_t)blk * FI_ROWS + lane];
         const uint32_t *erow = seg_tab + (size_t)blk * d;
         // FX: the block's byte table (lines per dimension), 16 dimensions per lane, and the
         // lines in front of each group of 16
@@ -391,6 +405,15 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
 #undef FI_APPLY
           }
         }
+        if constexpr (SEL) {      // (the transposition behind the row loop: its registers are free again)
+#pragma unroll
+          for (int r = 0; r < FI_ROWS; ++r) {
+            const unsigned long long wr =
+                ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(w >> 32), r) << 32) |
+                (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)w, r);
+            selbits |= (uint32_t)((wr >> lane) & 1ull) << r;
+          }
+        }
       }
       // the first blocks of a query: every accumulator of eight blocks would pass (4 k candidates
       // against a buffer of 2 k) -- the threshold is fixed from a histogram of all of them first
@@ -398,7 +421,7 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
       if (cold) {
         for (int r = 0; r * 64 < nb; ++r) {
           const int v = r * 64 + lane;
-          top.cold_count(v < nb, v < nb ? acc[v] : 0.0f);
+          top.cold_count(v < nb && sel_ok(r), v < nb ? acc[v] : 0.0f);
         }
         top.cold_threshold();
       }
@@ -422,7 +445,7 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
         int c = 0;
 #pragma unroll
         for (int r = 0; r < FI_ROWS; ++r)
-          c += __popcll(__ballot(r * 64 + lane < nb && top.passes(sc[r])));
+          c += __popcll(__ballot(r * 64 + lane < nb && sel_ok(r) && top.passes(sc[r])));
         if (c == 0) {
           offered = true;
         } else if (c <= 64) {
@@ -431,7 +454,7 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
 #pragma unroll
             for (int r = 0; r < FI_ROWS; ++r) {
               const int v = r * 64 + lane;
-              const bool p = v < nb && top.passes(sc[r]);
+              const bool p = v < nb && sel_ok(r) && top.passes(sc[r]);
               const unsigned long long m = __ballot(p);
               if (m) {                                                     // wave-uniform
                 top.free_write(p, m, sc[r], (uint32_t)(pos0 + v), base);
@@ -446,7 +469,7 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
         const int v = r * 64 + lane;
         const float score = v < nb ? acc[v] : 0.0f;
         for (;;) {
-          const bool p = v < nb && top.passes(score);
+          const bool p = v < nb && sel_ok(r) && top.passes(score);
           if (!__ballot(p)) break;                                        // wave-uniform
           if (top.free_append(p, score, (uint32_t)(pos0 + v), cold)) break;
           sync();
@@ -489,23 +512,24 @@ bool flat_inv_supported(int d, int k, int nprobe) {
   return d <= 4096 && nprobe <= 2 * FI_NT && k >= 1 && k + FI_NT + 256 <= 4096;
 }
 
-template <int FI_CAP, bool FX, bool WIDE>
+template <int FI_CAP, bool FX, bool WIDE, bool SEL = false>
 static int launch_flat_inv(const float *xq, int nq, int d, const int32_t *coarse_I, int nprobe,
                            const int32_t *list_offsets, const int32_t *blk_offsets,
                            const uint32_t *blk_base, const uint32_t *seg_tab,
                            const char *seg_bytes, const int32_t *ids, int k, float *D,
                            int64_t *I64, int32_t *I32, int set_mode, const uint2 *ent,
-                           const int32_t *ent_cnt, int tab_stride, const int *gate, const ScanPostFilter &pf) {
+                           const int32_t *ent_cnt, int tab_stride, const int *gate, const ScanPostFilter &pf,
+                           const unsigned long long *sel = nullptr) {
   using TopK = HistTopK<FI_CAP, FI_NT, FI_NT>;
   const size_t lds = TopK::lds_bytes() + (size_t)FI_NW * FI_BLK * 4 + (size_t)((d + 3) & ~3) * 4 +
                      (size_t)FI_CHUNK * (sizeof(FiUnit) + 2) + 64 + (size_t)((d + 7) & ~7) * 2;
   if (lds > 160 * 1024) return fail(ASL_ERR_CAPACITY, "flat scan: d=%d does not fit LDS", d);
   if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute((const void *)flat_inv_scan_kernel<FI_CAP, FX, WIDE>,
+    HIP_TRY(hipFuncSetAttribute((const void *)flat_inv_scan_kernel<FI_CAP, FX, WIDE, SEL>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((flat_inv_scan_kernel<FI_CAP, FX, WIDE>), dim3(nq), dim3(FI_NT), lds, stream(), xq, d,
+  hipLaunchKernelGGL((flat_inv_scan_kernel<FI_CAP, FX, WIDE, SEL>), dim3(nq), dim3(FI_NT), lds, stream(), xq, d,
                      coarse_I, nprobe, list_offsets, blk_offsets, blk_base, seg_tab, seg_bytes, ids,
-                     k, D, I64, I32, set_mode, ent, ent_cnt, tab_stride, gate, pf);
+                     k, D, I64, I32, set_mode, ent, ent_cnt, tab_stride, gate, pf, sel);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }
@@ -517,7 +541,8 @@ int flat_inv_scan(int layout, const float *xq, int nq, int d, const int32_t *coa
                   const int32_t *list_offsets, const int32_t *blk_offsets,
                   const uint32_t *blk_base, const void *seg_tab, int tab_stride, const char *seg_bytes,
                   const int32_t *ids, int k, float *D, int64_t *I64, int32_t *I32, int set_mode,
-                  const uint2 *ent, const int32_t *ent_cnt, const int *gate, const ScanPostFilter *post) {
+                  const uint2 *ent, const int32_t *ent_cnt, const int *gate, const ScanPostFilter *post,
+                  const unsigned long long *sel) {
   if (nq <= 0) return ASL_OK;
   const uint32_t *tab = reinterpret_cast<const uint32_t *>(seg_tab);
   const bool small = k + FI_NT + 256 <= 2048;
@@ -526,6 +551,20 @@ int flat_inv_scan(int layout, const float *xq, int nq, int d, const int32_t *coa
     if (!(set_mode == 1 && I32 && small))
       return fail(ASL_ERR_STATE, "postings scan: a post-filter needs set-mode int32 rows and k <= 1280");
     pf = *post;
+  }
+  if (sel) {      // one word per 64 positions of every block (flat_selector)
+    if (!small || set_mode == 2) return fail(ASL_ERR_STATE, "postings scan: a selector needs k <= 1280 and rows of ids");
+#define FI_SEL_LAUNCH(FX, WIDE)                                                                                  \
+  return launch_flat_inv<2048, FX, WIDE, true>(xq, nq, d, coarse_I, nprobe, list_offsets, blk_offsets, blk_base, \
+                                               tab, seg_bytes, ids, k, D, I64, I32, set_mode, ent, ent_cnt,      \
+                                               tab_stride, gate, pf, sel)
+    if (layout == 2) {
+      if (nprobe > FI_NT) FI_SEL_LAUNCH(true, true);
+      FI_SEL_LAUNCH(true, false);
+    }
+    if (nprobe > FI_NT) FI_SEL_LAUNCH(false, true);
+    FI_SEL_LAUNCH(false, false);
+#undef FI_SEL_LAUNCH
   }
 #define FI_LAUNCH(CAP, FX)                                                                                 \
   do {                                                                                                     \
@@ -545,6 +584,43 @@ int flat_inv_scan(int layout, const float *xq, int nq, int d, const int32_t *coa
   FI_LAUNCH(4096, false);
 #undef FI_LAUNCH
 }
+
+// ---- selector words of the postings layout (SEL above): FI_ROWS words per block, one wave per word. The
+// block's list comes from a binary search of blk_offsets; a position behind the list's end is unselected.
+__global__ __launch_bounds__(256) void flat_selector_kernel(const int32_t *__restrict__ list_offsets,
+                                                            const int32_t *__restrict__ blk_offsets, int nlist,
+                                                            const int32_t *__restrict__ ids,
+                                                            const uint8_t *__restrict__ keep, int64_t n,
+                                                            int64_t nwords, unsigned long long *__restrict__ words) {
+  const int64_t w = block_linear() * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (w >= nwords) return;             // (wave-uniform)
+  const int blk = (int)(w / FI_ROWS), r = (int)(w % FI_ROWS);
+  int a = 0, b = nlist;                // the last list with blk_offsets[l] <= blk
+  while (b - a > 1) {
+    const int mid = (a + b) >> 1;
+    if (blk_offsets[mid] <= blk) a = mid; else b = mid;
+  }
+  const int64_t pos = (int64_t)list_offsets[a] + (int64_t)(blk - blk_offsets[a]) * FI_BLK + r * 64 + lane;
+  bool on = false;
+  if (blk < blk_offsets[a + 1] && pos < list_offsets[a + 1]) {
+    const int32_t id = ids[pos];
+    on = id >= 0 && id < n && keep[id] != 0;
+  }
+  const unsigned long long m = __ballot(on);
+  if (lane == 0) words[w] = m;
+}
+
+int flat_selector(const int32_t *list_offsets, const int32_t *blk_offsets, int nlist, int64_t nblocks,
+                  const int32_t *ids, const uint8_t *keep, int64_t n, unsigned long long *words) {
+  const int64_t nwords = nblocks * FI_ROWS;
+  if (nwords <= 0 || nlist <= 0) return ASL_OK;
+  hipLaunchKernelGGL(flat_selector_kernel, grid_2d(cdiv(nwords, 4)), dim3(256), 0, stream(), list_offsets,
+                     blk_offsets, nlist, ids, keep, n, nwords, words);
+  ASL_CHECK_LAUNCH();
+  return ASL_OK;
+}
+int flat_selector_words_per_block() { return FI_ROWS; }
 
 // ---- algorithmic work of a postings scan (bench.py: the roofline of this kernel). Per (query,
 // probed block, non-zero query dimension) the scan needs the 4-byte table word and the

@@ -43,8 +43,15 @@ struct IndexSearch {
   const int *gate = nullptr;        // device-side count: only the first *gate rows are searched
   int rows = ROWS_ORDERED;          // IndexRows; a mode set with asl_index_set_unordered goes before ORDERED / SET
   const IndexPostFilter *post = nullptr;   // precursor window applied in the scan's finish where the scan can
-  uint64_t serial = 0;              // ... of the library (asl_library serial) that owns post->payload
+  // what state of which library this request speaks for: the asl_library serial and the generation of its
+  // selection (0, generation of asl_index_set_selector: the handle's own selector). It names post->payload and
+  // sel_keep alike; the index rebuilds what it derived from either exactly when the pair or the lists change.
+  uint64_t serial = 0, gen = 0;
   const IndexWindow *win = nullptr; // scan the in-window run of every probed list only (window-ordered layout)
+  // selector (asl_index_search_selected): keep[id] != 0 = selected, [sel_n] with sel_n == ntotal; the scans
+  // choose their k among the selected vectors of the probed lists. (serial, gen) above name its content.
+  const uint8_t *sel_keep = nullptr;
+  int64_t sel_n = 0;
   bool rows_filtered = false;       // OUT: the rows hold in-window hits only, their lengths in count / row_len
 };
 
@@ -91,6 +98,7 @@ struct asl_index {
   asl::DevBuf<int2> idpay;
   int64_t n_tile_slots = 0;
   uint64_t pay_serial = 0;       // serial of the library whose window column the pairs hold
+  uint64_t pay_gen = 0;          // ... and the generation of its selection (the column is the effective one)
   int64_t pay_n = 0;
   bool idpay_ready = false;
   bool has_tiles = false;
@@ -102,8 +110,21 @@ struct asl_index {
   asl::DevBuf<float> wkey_tiled;      // the key per tile slot (NaN in a list's last tile behind its end)
   bool win_ready = false;
   uint64_t win_serial = 0;       // serial of the library whose window column is the key; 0: a caller's key
+  uint64_t win_gen = 0;          // ... and the generation of its selection
   int window_scan = 0;           // asl_index_set_window_scan: asl_search_batch scans each query's window only
   asl::DevBuf<int2> win_ranges;       // [nq, nprobe] in-window run of each probed list
+  // selector words of the scans (ivf_kernels.hpp: tile_selector / flat_selector), derived like idpay: never
+  // saved, dropped by build_lists, rebuilt when (serial, generation) of the selector or the lists change.
+  // sel_words: per tile of the default layout (IVF-PQ) or per 64 positions of a block (IVF-Flat);
+  // wsel_words: per tile of the window-ordered copy (dropped with it)
+  asl::DevBuf<unsigned long long> sel_words, wsel_words;
+  bool sel_ready = false, wsel_ready = false;
+  uint64_t sel_serial = 0, sel_gen = 0, wsel_serial = 0, wsel_gen = 0;
+  // the handle's own selector (asl_index_set_selector): one byte per vector id; dropped when the lists change
+  asl::DevBuf<uint8_t> selector;
+  bool has_selector = false;
+  uint64_t selector_gen = 0;
+  int64_t n_blocks = 0;               // blocks of the postings layout
   // dimension-major postings for flat_inv_scan (IVF-Flat): blocks of FI_BLK vectors
   asl::DevBuf<int32_t> blk_offsets;   // [nlist + 1] first block of each list
   asl::DevBuf<uint32_t> blk_base;     // [nblocks] start of the block's postings, 64-byte units
@@ -161,16 +182,19 @@ int assign_ip(asl_index *ix, const float *x, int64_t ld, int64_t n, const float 
 // index_lists.hip
 int build_lists(asl_index *ix);
 const char *window_unsupported(const asl_index *ix);
-int window_install(asl_index *ix, int64_t n, const float *key, uint64_t serial);
-int post_filter_pairs(asl_index *ix, const IndexPostFilter &p, uint64_t serial, const int32_t *slot_ids,
-                      int64_t nslots);
+int window_install(asl_index *ix, int64_t n, const float *key, uint64_t serial, uint64_t gen = 0);
+int post_filter_pairs(asl_index *ix, const IndexPostFilter &p, uint64_t serial, uint64_t gen,
+                      const int32_t *slot_ids, int64_t nslots);
+// the selector words of rq's selector for the layout its scan reads (window: the window-ordered copy) -> *words
+int selector_words(asl_index *ix, const IndexSearch &rq, bool window, const unsigned long long **words);
 // index_search.hip
 int index_search_device(asl_index *ix, IndexSearch &rq);
 int index_nprobe(const asl_index *ix, int nprobe);
 int index_prepare(asl_index *ix);
 int coarse_search(asl_index *ix, const float *xq, int nq, int nprobe, float *out_D, int32_t *out_I, uint2 *ent_out,
                   int32_t *cnt_out, bool *have_ent);
-int index_window_prepare(asl_index *ix, uint64_t serial, const float *key, int64_t n, int nq, int nprobe);
+int index_window_prepare(asl_index *ix, uint64_t serial, uint64_t gen, const float *key, int64_t n, int nq,
+                         int nprobe);
 int index_refine_k(const asl_index *ix);
 int coarse_scores_all(asl_index *ix, const float *xq, int m, float *scores, uint2 *ent = nullptr, int32_t *cnt = nullptr);
 int index_codebooks_transposed(asl_index *ix);

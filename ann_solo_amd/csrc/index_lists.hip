@@ -15,6 +15,8 @@ int build_lists(asl_index *ix) {
   ix->idpay_ready = false;
   ix->win_ready = false;
   ix->win_serial = 0;
+  ix->sel_ready = ix->wsel_ready = false;
+  ix->has_selector = false;       // (one byte per vector of the lists as they were)
   const int64_t n = ix->n_store;
   std::vector<int32_t> h_vlist((size_t)n), h_order((size_t)n), h_ids;
   ix->h_list_offsets.assign((size_t)ix->nlist + 1, 0);
@@ -93,6 +95,7 @@ int build_lists(asl_index *ix) {
           pos_loc[(size_t)i] = (uint16_t)(r % FI_BLK);
         }
       const size_t nblk = (size_t)std::max<int32_t>(blk_off[(size_t)ix->nlist], 1);
+      ix->n_blocks = blk_off[(size_t)ix->nlist];
       const size_t ncell = nblk * (size_t)ix->d;
       DevBuf<int32_t> pos_blk_dev;
       DevBuf<uint16_t> pos_loc_dev;
@@ -191,9 +194,9 @@ __global__ void make_idpay_kernel(const int32_t *__restrict__ slot_ids, int64_t 
 // the scans index_search_device launches behind this call on that stream (the pipeline keeps every scan on its stream
 // B, every other entry point drains it first), so the rewrite is ordered after every scan that read the old pairs. A
 // host that changes asl_set_stream between two libraries on one index synchronises the old stream first (as before).
-int post_filter_pairs(asl_index *ix, const IndexPostFilter &p, uint64_t serial, const int32_t *slot_ids,
-                      int64_t nslots) {
-  if (ix->idpay_ready && ix->pay_serial == serial && ix->pay_n == p.n) return ASL_OK;
+int post_filter_pairs(asl_index *ix, const IndexPostFilter &p, uint64_t serial, uint64_t gen,
+                      const int32_t *slot_ids, int64_t nslots) {
+  if (ix->idpay_ready && ix->pay_serial == serial && ix->pay_gen == gen && ix->pay_n == p.n) return ASL_OK;
   ASL_TRY(ix->idpay.reserve((size_t)std::max<int64_t>(nslots, 1)));
   if (nslots > 0) {
     hipLaunchKernelGGL(make_idpay_kernel, grid_2d(cdiv(nslots, 256)), dim3(256), 0, stream(), slot_ids, nslots,
@@ -201,8 +204,36 @@ int post_filter_pairs(asl_index *ix, const IndexPostFilter &p, uint64_t serial, 
     ASL_CHECK_LAUNCH();
   }
   ix->pay_serial = serial;
+  ix->pay_gen = gen;
   ix->pay_n = p.n;
   ix->idpay_ready = true;
+  return ASL_OK;
+}
+
+// ix->sel_words / wsel_words for the selector of rq, rewritten on the CURRENT stream when they hold another
+// selector's bits (post_filter_pairs says why that orders the rewrite behind every scan that read the old
+// words). window: the words of the window-ordered copy (which is installed by then).
+int selector_words(asl_index *ix, const IndexSearch &rq, bool window, const unsigned long long **words) {
+  DevBuf<unsigned long long> &buf = window ? ix->wsel_words : ix->sel_words;
+  bool &ready = window ? ix->wsel_ready : ix->sel_ready;
+  uint64_t &serial = window ? ix->wsel_serial : ix->sel_serial, &gen = window ? ix->wsel_gen : ix->sel_gen;
+  *words = nullptr;
+  if (!(ready && serial == rq.serial && gen == rq.gen)) {
+    ready = false;
+    if (ix->kind == ASL_INDEX_IVFPQ) {
+      const int64_t ntiles = ix->n_tile_slots / 64;
+      ASL_TRY(buf.reserve((size_t)std::max<int64_t>(ntiles, 1)));
+      ASL_TRY(tile_selector(window ? ix->wids_tiled.p : ix->ids_tiled.p, ntiles, rq.sel_keep, rq.sel_n, buf.p));
+    } else {
+      ASL_TRY(buf.reserve((size_t)std::max<int64_t>(ix->n_blocks, 1) * flat_selector_words_per_block()));
+      ASL_TRY(flat_selector(ix->list_offsets.p, ix->blk_offsets.p, ix->nlist, ix->n_blocks, ix->ids.p, rq.sel_keep,
+                            rq.sel_n, buf.p));
+    }
+    serial = rq.serial;
+    gen = rq.gen;
+    ready = true;
+  }
+  *words = buf.p;
   return ASL_OK;
 }
 
@@ -217,8 +248,9 @@ const char *window_unsupported(const asl_index *ix) {
 
 // The window-ordered layout from key[id] (n == ntotal; host or device): every list's vectors sorted by
 // (key ascending, NaN last, id ascending) and tiled by tile_codes_kernel into that slot order, plus the
-// key per slot. `serial` records where the key came from (asl_library serial; 0: the caller's).
-int window_install(asl_index *ix, int64_t n, const float *key, uint64_t serial) {
+// key per slot. (serial, gen) record where the key came from (asl_library serial and the generation of its
+// selection; 0: the caller's).
+int window_install(asl_index *ix, int64_t n, const float *key, uint64_t serial, uint64_t gen) {
   if (const char *why = window_unsupported(ix)) return fail(ASL_ERR_STATE, "%s", why);
   if (!ix->trained) return fail(ASL_ERR_STATE, "window key: index is not trained");
   if (n != ix->ntotal) return fail(ASL_ERR_INVALID, "window key: %lld keys for %lld vectors", (long long)n,
@@ -227,6 +259,7 @@ int window_install(asl_index *ix, int64_t n, const float *key, uint64_t serial) 
   ASL_TRY(build_lists(ix));
   if (!ix->has_tiles) return fail(ASL_ERR_STATE, "window key: the index has no tiled layout");
   ix->win_ready = false;
+  ix->wsel_ready = false;         // (the words follow the slot order about to change)
   std::vector<float> h_key((size_t)n);
   std::vector<int32_t> h_ids((size_t)n);
   if (n) {
@@ -267,6 +300,7 @@ int window_install(asl_index *ix, int64_t n, const float *key, uint64_t serial) 
   ASL_TRY(sync_stream());
   ix->win_ready = true;
   ix->win_serial = serial;
+  ix->win_gen = gen;
   return ASL_OK;
 }
 

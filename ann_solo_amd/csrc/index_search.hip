@@ -119,6 +119,20 @@ static int validate(asl_index *ix, const IndexSearch &rq, SearchPlan &pl) {
       return fail(ASL_ERR_STATE, "the window scan takes no gate, packed keys or exact re-rank");
     if (!rq.win->q_pmz) return fail(ASL_ERR_INVALID, "window scan: null precursor m/z");
   }
+  // a selector (rq.sel_keep): the scans choose their k among the selected vectors; whatever cannot do that
+  // is an error, never a filter behind the top-k
+  if (rq.sel_keep) {
+    if (ix->kind == ASL_INDEX_FLAT) return fail(ASL_ERR_STATE, "a selector needs an IVF index (not a Flat index)");
+    if (ix->shard_world > 1 || ix->has_vids) return fail(ASL_ERR_STATE, "a selector does not run on a sharded index");
+    if (ix->scan_variant != 0)
+      return fail(ASL_ERR_STATE, "a selector needs the layout-specific scan (scan_variant 0), not the generic kernels");
+    if (!keys_fit(k)) return fail(ASL_ERR_STATE, "a selected search holds k <= %d (k=%d)", TK_MAX_K - FLAT_KEYS_SLACK, k);
+    if (rq.gate || pl.unordered == 2 || (rq.pre_ent && !rq.xq))
+      return fail(ASL_ERR_STATE, "a selected search takes no gate, packed keys or entry-list-only queries");
+    if (pl.refine) return fail(ASL_ERR_STATE, "a selected search does not run with the exact re-rank");
+    if (rq.sel_n != ix->ntotal)
+      return fail(ASL_ERR_INVALID, "selector: %lld flags for %lld vectors", (long long)rq.sel_n, (long long)ix->ntotal);
+  }
   if (rq.nq <= 0) return ASL_OK;
   // pre_ent / pre_cnt: the queries as ENTRY LISTS (list_nonzeros / encode_entries_device); xq may
   // then be null -- only the layout-specific scans read their queries in that form, and a row
@@ -157,6 +171,9 @@ static int validate(asl_index *ix, const IndexSearch &rq, SearchPlan &pl) {
       return fail(ASL_ERR_STATE, "packed-key rows need the postings scan of IVF-Flat (sparse vectors, k <= 1280) and an int64 output");
     if (rq.gate && !pl.use_inv) return fail(ASL_ERR_STATE, "gated search: needs the postings scan of IVF-Flat");
     if (ents_only && !pl.use_inv) return fail(ASL_ERR_STATE, "entry-list search: needs the postings scan of IVF-Flat");
+    if (rq.sel_keep && !pl.use_inv)
+      return fail(ASL_ERR_STATE, "a selector needs the postings scan of IVF-Flat (sparse vectors, nprobe <= 1024), "
+                                 "not dense rows");
     return ASL_OK;
   }
   // IVF-PQ. Exact re-rank: the ADC scan returns k' > k candidates as a set, refine.hip keeps the k best
@@ -176,6 +193,8 @@ static int validate(asl_index *ix, const IndexSearch &rq, SearchPlan &pl) {
     return fail(ASL_ERR_STATE, "packed-key rows need the tiled IVF-PQ scan (m = 32, 8 bits) and an int64 output");
   if (rq.gate && !pl.tiled) return fail(ASL_ERR_STATE, "gated search: needs the tiled IVF-PQ scan");
   if (ents_only && !pl.tiled) return fail(ASL_ERR_STATE, "entry-list search: needs the tiled IVF-PQ scan (m = 32, 8 bits)");
+  if (rq.sel_keep && !pl.tiled)
+    return fail(ASL_ERR_STATE, "a selector needs the tiled IVF-PQ scan (m = 32, 8 bits, nprobe <= 1024)");
   if (rq.win && !pl.tiled) return fail(ASL_ERR_STATE, "the window scan needs the tiled IVF-PQ scan (m = 32, 8 bits)");
   if (rq.win && !ix->win_ready)
     return fail(ASL_ERR_STATE, "window scan: no window key (asl_index_set_window_key), or the lists changed "
@@ -212,7 +231,7 @@ static int take_post_filter(asl_index *ix, IndexSearch &rq, int mode, const int3
   const IndexPostFilter &p = *rq.post;
   if (!(mode == 1 && rq.I32 && !rq.I64 && !rq.D && !rq.gate && keys_fit(rq.k)) || !p.payload || !p.q_pmz || !p.count ||
       p.n != ix->ntotal || ix->has_vids) return ASL_OK;
-  ASL_TRY(post_filter_pairs(ix, p, rq.serial, slot_ids, nslots));
+  ASL_TRY(post_filter_pairs(ix, p, rq.serial, rq.gen, slot_ids, nslots));
   pf = {.idpay = ix->idpay.p, .q_pmz = p.q_pmz, .count = p.count, .tol = p.tol, .mode = p.mode, .charge = p.charge};
   rq.rows_filtered = true;
   return ASL_OK;
@@ -283,6 +302,8 @@ static int search_ivfflat(asl_index *ix, IndexSearch &rq, const SearchPlan &pl) 
   const int mode_ = pl.unordered ? pl.unordered : (rq.rows != ROWS_ORDERED ? 1 : 0);
   ScanPostFilter pf;
   ASL_TRY(take_post_filter(ix, rq, mode_, ix->ids.p, ix->n_store, pf));
+  const unsigned long long *sel = nullptr;
+  if (rq.sel_keep) ASL_TRY(selector_words(ix, rq, false, &sel));
   {
     ProfScope ps("scan");     // the scan kernel itself
     const bool fx = ix->inv_layout == 2;
@@ -290,7 +311,7 @@ static int search_ivfflat(asl_index *ix, IndexSearch &rq, const SearchPlan &pl) 
                           ix->blk_offsets.p, ix->blk_base.p,
                           fx ? (const void *)ix->inv_tab8.p : (const void *)ix->inv_tab.p,
                           ix->tab_stride, ix->inv_data.p, ix->ids.p, rq.k, rq.D, rq.I64, rq.I32,
-                          mode_, q_ent, q_cnt, rq.gate, &pf));
+                          mode_, q_ent, q_cnt, rq.gate, &pf, sel));
   }
   return rq.gate ? ASL_OK : count_scanned(ix, cI, nq, nprobe);
 }
@@ -348,11 +369,13 @@ static int scan_pq_tiled(asl_index *ix, IndexSearch &rq, const SearchPlan &pl, c
   } else {
     ASL_TRY(take_post_filter(ix, rq, mode_, ix->ids_tiled.p, ix->n_tile_slots, pf));
   }
+  const unsigned long long *sel = nullptr;
+  if (rq.sel_keep) ASL_TRY(selector_words(ix, rq, rq.win != nullptr, &sel));
   ProfScope ps("scan");     // the scan kernel itself
   return pq_scan_v3(rq.xq, nq, ix->d, ix->codebooks_t.p, ix->dsub, cD, cI,
                     nprobe, ix->list_offsets.p, ix->tile_offsets.p,
                     rq.win ? ix->wcodes_tiled.p : ix->codes_tiled.p, rq.win ? ix->wids_tiled.p : ix->ids_tiled.p,
-                    rq.k, rq.D, rq.I64, rq.I32, mode_, q_ent, q_cnt, rq.gate, &pf, &rg);
+                    rq.k, rq.D, rq.I64, rq.I32, mode_, q_ent, q_cnt, rq.gate, &pf, &rg, sel);
 }
 
 // IVF-PQ: coarse stage, then the tiled scan or the generic kernel (which takes no post-filter)
@@ -415,12 +438,13 @@ int index_search_device(asl_index *ix, IndexSearch &rq) {
 // window scan of asl_search_batch: the index's mode, the key of library `serial` (installed when the
 // layout holds another key or the lists changed; synchronises -- call before the batch forks into
 // streams), the window of the next search
-int index_window_prepare(asl_index *ix, uint64_t serial, const float *key, int64_t n, int nq, int nprobe) {
+int index_window_prepare(asl_index *ix, uint64_t serial, uint64_t gen, const float *key, int64_t n, int nq,
+                         int nprobe) {
   if (!ix->trained) return fail(ASL_ERR_STATE, "search: index is not trained");
   ASL_TRY(build_lists(ix));
-  if (!ix->win_ready || ix->win_serial != serial) {
+  if (!ix->win_ready || ix->win_serial != serial || ix->win_gen != gen) {
     ASL_TRY(pipeline_drain());     // batches in flight may still scan the layout about to be rewritten
-    ASL_TRY(window_install(ix, n, key, serial));
+    ASL_TRY(window_install(ix, n, key, serial, gen));
   }
   return ix->win_ranges.reserve((size_t)std::max(nq, 1) * std::max(1, std::min(nprobe, ix->nlist)));
 }
@@ -576,6 +600,58 @@ int asl_index_search_window(asl_index_t *ix, int32_t nq, const float *xq, const 
   return with_staged_rows(D, I, (size_t)nq * k, dq.own.p || dp.own.p, [&](float *dD, int64_t *dI) {
     IndexWindow w{.q_pmz = dp.d, .tol = tol, .mode = mode, .charge = charge};
     IndexSearch rq{.nq = nq, .xq = dq.d, .k = k, .nprobe = nprobe, .D = dD, .I64 = dI, .win = &w};
+    return index_search_device(ix, rq);
+  });
+}
+
+int asl_index_set_selector(asl_index_t *ix, int64_t n, const uint8_t *keep) {
+  clear_error();
+  ASL_TRY(ensure_device());       // (waits for batches in flight: they may still read the words)
+  if (!ix) return fail(ASL_ERR_INVALID, "set_selector: null index");
+  if (n == 0 || !keep) {
+    ix->has_selector = false;
+    return ASL_OK;
+  }
+  if (n != ix->ntotal)
+    return fail(ASL_ERR_INVALID, "set_selector: %lld flags for %lld vectors", (long long)n, (long long)ix->ntotal);
+  if (ix->kind != ASL_INDEX_FLAT && ix->trained) ASL_TRY(build_lists(ix));   // (a rebuild later drops the selector)
+  ix->has_selector = false;
+  ASL_TRY(ix->selector.reserve((size_t)n));
+  HIP_TRY(hipMemcpyAsync(ix->selector.p, keep, (size_t)n, hipMemcpyDefault, stream()));
+  ASL_TRY(sync_stream());         // a host array is the caller's again on return
+  ix->has_selector = true;
+  ++ix->selector_gen;
+  return ASL_OK;
+}
+
+int asl_index_search_selected(asl_index_t *ix, int32_t nq, const float *xq, const double *q_pmz, int32_t charge,
+                              double tol, int32_t mode, int32_t k, int32_t nprobe, float *D, int64_t *I) {
+  clear_error();
+  ASL_TRY(ensure_device());
+  if (!ix) return fail(ASL_ERR_INVALID, "search_selected: null index");
+  if (nq <= 0) return ASL_OK;
+  if (!xq || !I) return fail(ASL_ERR_INVALID, "search_selected: null xq / I");
+  if (q_pmz && mode != ASL_TOL_DA && mode != ASL_TOL_PPM)
+    return fail(ASL_ERR_INVALID, "search_selected: mode must be Da or ppm");
+  if (ix->kind == ASL_INDEX_FLAT) return fail(ASL_ERR_STATE, "a selector needs an IVF index (not a Flat index)");
+  if (!ix->trained) return fail(ASL_ERR_STATE, "search: index is not trained");
+  ASL_TRY(build_lists(ix));
+  if (!ix->has_selector)
+    return fail(ASL_ERR_STATE, "search_selected: no selector (asl_index_set_selector), or the lists changed since "
+                               "it was set");
+  if (q_pmz) {
+    if (const char *why = window_unsupported(ix)) return fail(ASL_ERR_STATE, "%s", why);
+    if (!ix->win_ready)
+      return fail(ASL_ERR_STATE, "search_selected: no window key (asl_index_set_window_key), or the lists changed since");
+  }
+  In<float> dq;
+  In<double> dp;
+  ASL_TRY(dq.init(xq, (size_t)nq * ix->d));
+  if (q_pmz) ASL_TRY(dp.init(q_pmz, (size_t)nq));
+  return with_staged_rows(D, I, (size_t)nq * k, dq.own.p || dp.own.p, [&](float *dD, int64_t *dI) {
+    IndexWindow w{.q_pmz = dp.d, .tol = tol, .mode = mode, .charge = charge};
+    IndexSearch rq{.nq = nq, .xq = dq.d, .k = k, .nprobe = nprobe, .D = dD, .I64 = dI, .serial = 0,
+                   .gen = ix->selector_gen, .win = q_pmz ? &w : nullptr, .sel_keep = ix->selector.p, .sel_n = ix->ntotal};
     return index_search_device(ix, rq);
   });
 }

@@ -70,7 +70,11 @@ int pq_scan_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
                const int32_t *ent_cnt = nullptr,    // ent / ent_cnt: list_nonzeros (64 entries per query)
                const int *gate = nullptr,
                const ScanPostFilter *post = nullptr,   // (common.hpp) set-mode int32 rows, k <= 1280 only          // device-side row count: workgroups past it return at once
-               const ScanRanges *ranges = nullptr);   // (common.hpp) window scan of the window-ordered layout, k <= 1280
+               const ScanRanges *ranges = nullptr,   // (common.hpp) window scan of the window-ordered layout, k <= 1280
+               const unsigned long long *sel = nullptr);   // selector: a word per tile of the layout scanned, k <= 1280
+// selector words of a tiled layout: bit v of words[tile] = keep[slot_ids[tile * 64 + v]] (id -1: unselected)
+int tile_selector(const int32_t *slot_ids, int64_t ntiles, const uint8_t *keep, int64_t n,
+                  unsigned long long *words);
 // [lo, hi) of the in-window run of every (query, probe) in the window-ordered layout (pq_scan_v3.hip)
 int window_ranges(const double *q_pmz, int nq, const int32_t *coarse_I, int nprobe,
                   const int32_t *list_offsets, const int32_t *tile_offsets, const float *wkey, int charge,
@@ -88,7 +92,13 @@ int flat_inv_scan(int layout, const float *xq, int nq, int d, const int32_t *coa
                   const uint32_t *blk_base, const void *seg_tab, int tab_stride, const char *seg_bytes,
                   const int32_t *ids, int k, float *D, int64_t *I64, int32_t *I32, int set_mode,
                   const uint2 *ent, const int32_t *ent_cnt, const int *gate = nullptr,
-                  const ScanPostFilter *post = nullptr);   // set-mode int32 rows, k <= 1280 only
+                  const ScanPostFilter *post = nullptr,   // set-mode int32 rows, k <= 1280 only
+                  const unsigned long long *sel = nullptr);   // selector: flat_selector's words, k <= 1280
+// selector words of the postings layout: flat_selector_words_per_block() per block, bit v of word r of a
+// block = keep[id of the block's position r * 64 + v] (behind the list's end: unselected)
+int flat_selector(const int32_t *list_offsets, const int32_t *blk_offsets, int nlist, int64_t nblocks,
+                  const int32_t *ids, const uint8_t *keep, int64_t n, unsigned long long *words);
+int flat_selector_words_per_block();
 int flat_inv_work(const float *xq, int nq, int d, const int32_t *coarse_I, int nprobe,
                   const int32_t *blk_offsets, const uint32_t *seg_tab, unsigned long long *out_dev);
 uint32_t inv_place_block(const uint32_t *cnt, int d, uint32_t *tab, bool *ok);

@@ -89,7 +89,13 @@ static_assert(V3_CHUNK_RANGED * sizeof(TileEnt12) <= V3_CHUNK * sizeof(TileEnt8)
 // 157 -- measured 8.28 -> 7.46 ms at the bench config (with ONE round of prefetch: at this
 // occupancy the second prefetch stage only costs registers).
 // RANGED: the tile table comes from rg.range instead of the whole lists (see TileEnt12)
-template <int CAP, int T, int NW, int DEPTH, bool WIDE, bool RANGED = false>
+// SEL (asl_index_search_selected, a library's selection; the 2048-key instantiations only): sel holds one
+// 64-bit word per tile of the layout scanned, bit v = vector v of the tile is selected (padding slots are
+// not). The word comes in with the tile's table entry -- the tile index is wave-uniform, so it is a scalar
+// load into two scalar registers -- and is one more term of append()'s `in`: an unselected vector is scored
+// like any other and never offered, so the k best are chosen among the selected vectors alone. Reservation,
+// refused-tile retry, exact flushes and both finishes are those of the plain instantiations.
+template <int CAP, int T, int NW, int DEPTH, bool WIDE, bool RANGED = false, bool SEL = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIMD : 4) : (CAP <= 2048 ? 3 : 1))) void pq_scan_v3_kernel(
     const float *__restrict__ xq, int d, const float *__restrict__ codebooks, int dsub,
     const float *__restrict__ coarse_D, const int32_t *__restrict__ coarse_I, int nprobe,
@@ -97,7 +103,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     const uint8_t *__restrict__ codes_tiled, const int32_t *__restrict__ ids_tiled, int k,
     float *__restrict__ D, int64_t *__restrict__ I64, int32_t *__restrict__ I32, int set_mode,
     const uint2 *__restrict__ ent, const int32_t *__restrict__ ent_cnt, const int *__restrict__ gate,
-    const ScanPostFilter pf, const ScanRanges rg) {
+    const ScanPostFilter pf, const ScanRanges rg, const unsigned long long *__restrict__ sel) {
+  static_assert(!SEL || CAP <= 2048, "the selector is built into the 2048-key instantiations only");
   // gate: a device-side row count -- workgroups past it leave at once (a launch of fixed size over
   // a list whose length only the device knows: the shard-side rescans of exchange.hip)
   if (gate && (int)blockIdx.x >= *gate) return;
@@ -237,12 +244,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
       uint32_t tile_nv;   // tile | last lane << 26
       float coarse;
       uint32_t first;     // RANGED: first lane
+      unsigned long long sel;   // SEL: the tile's selector word
     } e[NS];
     auto fetch = [&](int i, uint4 &a, uint4 &b, Tile &en) {
       const Ent t = table[i];
       en.tile_nv = __builtin_amdgcn_readfirstlane(t.tile_nv);
       en.coarse = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t.coarse)));
       if constexpr (RANGED) en.first = __builtin_amdgcn_readfirstlane(t.first);
+      if constexpr (SEL) en.sel = sel[en.tile_nv & 0x3ffffffu];   // (a scalar load: the tile is wave-uniform)
       // the tile's address is a scalar and the lane's part a 32-bit offset of its own: the loads take
       // them as they are (scalar base + lane offset), no 64-bit lane addresses to keep or add up per tile
       // (the second chunk's offset is made here from the first: a lane constant less to keep)
@@ -256,12 +265,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     // the tile whose candidates wait to be appended: its scores and (scalar) its entry
     float p_score = 0.0f;
     uint32_t p_tile_nv = 0, p_first = 0;
+    unsigned long long p_sel = 0;
     bool pending = false;
     // A tile costs the ADC and one compare against the snapshot; the ordered key is only made for the
     // lanes that pass (free_write), under the branch a tile without a passer skips.
     auto append = [&]() {
       const int end = (int)(p_tile_nv >> 26);
-      const bool in = RANGED ? (lane <= end && lane >= (int)p_first) : lane <= end;
+      bool in = RANGED ? (lane <= end && lane >= (int)p_first) : lane <= end;
+      if constexpr (SEL) in = in && ((p_sel >> lane) & 1ull) != 0;
       bool p;
       if (thr_hi_u != 0) {        // wave-uniform; exact flushes are in use: the ordered-key test
         // (the score as a value of its own: keeps this a scalar branch and its ordered key in here,
@@ -290,6 +301,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
       p_score = e[s].coarse + tile_adc(lut_bytes, A[s], B[s], offA, offB);
       p_tile_nv = e[s].tile_nv;
       if constexpr (RANGED) p_first = e[s].first;
+      if constexpr (SEL) p_sel = e[s].sel;
       append();
     };
     int i = wave_u;               // my next entry; between syncs its codes are in set 0, the next tiles' behind
@@ -377,14 +389,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
                I32 ? I32 + (size_t)q * k : nullptr);
 }
 
-template <int CAP, int T, int NW, int DEPTH, bool WIDE, bool RANGED = false>
+template <int CAP, int T, int NW, int DEPTH, bool WIDE, bool RANGED = false, bool SEL = false>
 static int launch_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
                      const float *coarse_D, const int32_t *coarse_I, int nprobe,
                      const int32_t *list_offsets, const int32_t *tile_offsets,
                      const uint8_t *codes_tiled, const int32_t *ids_tiled, int k, float *D,
                      int64_t *I64, int32_t *I32, int set_mode, const uint2 *ent,
                      const int32_t *ent_cnt, const int *gate, const ScanPostFilter &pf,
-                     const ScanRanges &rg) {
+                     const ScanRanges &rg, const unsigned long long *sel = nullptr) {
   // (the ranged table -- V3_CHUNK_RANGED entries of TileEnt12 -- fits the same bytes)
   constexpr size_t TABLE = RANGED ? V3_CHUNK_RANGED * sizeof(TileEnt12) : V3_CHUNK * sizeof(TileEnt8);
   if ((size_t)d * 4 > (size_t)CAP * 8 || dsub > 64 || (size_t)d * 2 + 8 > TABLE || d != PQT_M * dsub)
@@ -393,11 +405,11 @@ static int launch_v3(const float *xq, int nq, int d, const float *codebooks, int
                      (size_t)V3_CHUNK * sizeof(TileEnt8);
   if (lds > 160 * 1024) return fail(ASL_ERR_CAPACITY, "pq scan: k=%d does not fit LDS", k);
   if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute((const void *)pq_scan_v3_kernel<CAP, T, NW, DEPTH, WIDE, RANGED>,
+    HIP_TRY(hipFuncSetAttribute((const void *)pq_scan_v3_kernel<CAP, T, NW, DEPTH, WIDE, RANGED, SEL>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((pq_scan_v3_kernel<CAP, T, NW, DEPTH, WIDE, RANGED>), dim3(nq), dim3(64 * NW), lds, stream(),
+  hipLaunchKernelGGL((pq_scan_v3_kernel<CAP, T, NW, DEPTH, WIDE, RANGED, SEL>), dim3(nq), dim3(64 * NW), lds, stream(),
                      xq, d, codebooks, dsub, coarse_D, coarse_I, nprobe, list_offsets, tile_offsets,
-                     codes_tiled, ids_tiled, k, D, I64, I32, set_mode, ent, ent_cnt, gate, pf, rg);
+                     codes_tiled, ids_tiled, k, D, I64, I32, set_mode, ent, ent_cnt, gate, pf, rg, sel);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }
@@ -412,7 +424,8 @@ int pq_scan_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
                const int32_t *list_offsets, const int32_t *tile_offsets,
                const uint8_t *codes_tiled, const int32_t *ids_tiled, int k, float *D,
                int64_t *I64, int32_t *I32, int set_mode, const uint2 *ent, const int32_t *ent_cnt,
-               const int *gate, const ScanPostFilter *post, const ScanRanges *ranges) {
+               const int *gate, const ScanPostFilter *post, const ScanRanges *ranges,
+               const unsigned long long *sel) {
   if (nq <= 0) return ASL_OK;
   // the post-filter needs the set-mode finish of the 2048-key instantiation (its scratch behind the keys)
   ScanPostFilter pf;
@@ -424,11 +437,21 @@ int pq_scan_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
   const ScanRanges none;
 #define V3_ARGS xq, nq, d, codebooks, dsub, coarse_D, coarse_I, nprobe, list_offsets, tile_offsets, \
                 codes_tiled, ids_tiled, k, D, I64, I32, set_mode, ent, ent_cnt, gate, pf
+  if (sel && (set_mode == 2 || k + 256 + 512 > 2048))
+    return fail(ASL_ERR_STATE, "pq scan: a selector needs k <= 1280 and rows of ids");
   if (ranges && ranges->range) {   // the window-ordered layout, one run per probed list
     if (pf.idpay || set_mode == 2 || k + 256 + 512 > 2048)
       return fail(ASL_ERR_STATE, "pq scan: the window scan needs k <= 1280, rows of ids and no post-filter");
+    if (sel) {                     // (sel: one word per tile of THAT layout)
+      if (nprobe > 512) return launch_v3<2048, 1, 8, V3_DEPTH, true, true, true>(V3_ARGS, *ranges, sel);
+      return launch_v3<2048, 1, 8, V3_DEPTH, false, true, true>(V3_ARGS, *ranges, sel);
+    }
     if (nprobe > 512) return launch_v3<2048, 1, 8, V3_DEPTH, true, true>(V3_ARGS, *ranges);
     return launch_v3<2048, 1, 8, V3_DEPTH, false, true>(V3_ARGS, *ranges);
+  }
+  if (sel) {
+    if (nprobe > 512) return launch_v3<2048, 1, 8, V3_DEPTH, true, false, true>(V3_ARGS, none, sel);
+    return launch_v3<2048, 1, 8, V3_DEPTH, false, false, true>(V3_ARGS, none, sel);
   }
   if (nprobe > 512) {         // two probes per thread (the one-probe form keeps its registers)
     if (k + 256 + 512 <= 2048) return launch_v3<2048, 1, 8, V3_DEPTH, true>(V3_ARGS, none);
@@ -526,6 +549,28 @@ int tile_codes(const uint8_t *codes, const int32_t *ids, const int32_t *dst_slot
   if (n <= 0) return ASL_OK;
   hipLaunchKernelGGL(tile_codes_kernel, grid_2d(cdiv(n * PQT_M, 256)), dim3(256), 0,
                      stream(), codes, ids, dst_slot, n, codes_tiled, ids_tiled);
+  ASL_CHECK_LAUNCH();
+  return ASL_OK;
+}
+
+// ---- selector words of a tiled layout (SEL above): one wave per tile gathers keep[id] through the layout's
+// slot ids and ballots; a padding slot (id -1) or an id outside [0, n) is unselected
+__global__ __launch_bounds__(256) void tile_selector_kernel(const int32_t *__restrict__ slot_ids, int64_t ntiles,
+                                                            const uint8_t *__restrict__ keep, int64_t n,
+                                                            unsigned long long *__restrict__ words) {
+  const int64_t tile = block_linear() * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (tile >= ntiles) return;          // (wave-uniform)
+  const int32_t id = slot_ids[tile * 64 + lane];
+  const unsigned long long m = __ballot(id >= 0 && id < n && keep[id] != 0);
+  if (lane == 0) words[tile] = m;
+}
+
+int tile_selector(const int32_t *slot_ids, int64_t ntiles, const uint8_t *keep, int64_t n,
+                  unsigned long long *words) {
+  if (ntiles <= 0) return ASL_OK;
+  hipLaunchKernelGGL(tile_selector_kernel, grid_2d(cdiv(ntiles, 4)), dim3(256), 0, stream(), slot_ids, ntiles,
+                     keep, n, words);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }

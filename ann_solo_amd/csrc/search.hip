@@ -60,6 +60,18 @@ __global__ void window_fill_kernel(const int32_t *__restrict__ lo, const int32_t
   }
 }
 
+// The effective columns of a library with a selection (asl_library_set_selection): the window column with
+// NaN where the row is unselected (or was NaN: invalid), the validity flags with 0 there.
+__global__ void selection_columns_kernel(const uint8_t *__restrict__ keep, const float *__restrict__ wcol,
+                                         const uint8_t *__restrict__ valid, int64_t n,
+                                         float *__restrict__ wcol_eff, uint8_t *__restrict__ valid_eff) {
+  const int64_t i = block_linear() * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool on = keep[i] != 0;
+  wcol_eff[i] = on ? wcol[i] : __builtin_nanf("");
+  valid_eff[i] = (on && (!valid || valid[i])) ? 1 : 0;
+}
+
 }  // namespace asl
 
 using namespace asl;
@@ -80,6 +92,15 @@ struct asl_library {
   uint32_t slot = 0;         // bytes per row (a multiple of 128)
   DevBuf<float> wcol;     // window column alone, NaN for invalid spectra
   bool has_valid = false;
+  // selection (asl_library_set_selection): keep[row] != 0 = selected, and the columns every search reads
+  // while it is installed -- wcol_eff: NaN where unselected or invalid, valid_eff: 0 there. sel_gen counts
+  // the changes (install, replace, drop): with `serial` it names what an index derived from these columns.
+  DevBuf<uint8_t> keep, valid_eff;
+  DevBuf<float> wcol_eff;
+  bool has_sel = false;
+  uint64_t sel_gen = 0;
+  const float *window_col() const { return has_sel ? wcol_eff.p : wcol.p; }
+  const uint8_t *valid_col() const { return has_sel ? valid_eff.p : has_valid ? valid.p : nullptr; }
   // group id per row (asl_library_set_groups; the *_topn_distinct calls rank one row per group)
   DevBuf<int32_t> group;
   bool has_group = false;
@@ -163,21 +184,30 @@ static void offer_window(IndexSearch &rq, IndexWindow &w, const DevPeaks &Q, con
 }
 static void offer_post_filter(IndexSearch &rq, IndexPostFilter &pf, const asl_library *L, const DevPeaks &Q,
                               const asl_search_params_t *P, int32_t *row_len) {
-  pf = {.payload = L->wcol.p, .n = L->n, .q_pmz = Q.precursor_mz, .count = row_len, .tol = P->precursor_tol,
+  pf = {.payload = L->window_col(), .n = L->n, .q_pmz = Q.precursor_mz, .count = row_len, .tol = P->precursor_tol,
         .mode = P->precursor_mode, .charge = P->charge};
   rq.post = &pf;
+}
+// what every ANN batch tells the index of its library: whose columns it may have derived a layout from
+// (serial, generation) and, with a selection installed, the selector
+static void offer_library(IndexSearch &rq, const asl_library *L) {
   rq.serial = L->serial;
+  rq.gen = L->sel_gen;
+  if (L->has_sel) {
+    rq.sel_keep = L->keep.p;
+    rq.sel_n = L->n;
+  }
 }
 
 // the precursor filter / row records of a library handle
 static void library_filter(const asl_library *L, PrecFilter &flt) {
   flt.meta = reinterpret_cast<const RowMeta *>(L->records.p);
   flt.meta_stride = L->slot;
-  flt.wcol = L->wcol.p;
+  flt.wcol = L->window_col();
 }
 static void batch_filter(const asl_library *L, const asl_search_params_t *P, PrecFilter &flt) {
   flt.lib_pmz = L->pmz32.p;
-  flt.valid = L->has_valid ? L->valid.p : nullptr;
+  flt.valid = L->valid_col();
   library_filter(L, flt);
   flt.tol = P->precursor_tol;
   flt.mode = P->precursor_mode;
@@ -340,6 +370,28 @@ int asl_library_set_groups(asl_library_t *L, int64_t n, const int32_t *group) {
   return ASL_OK;
 }
 
+int asl_library_set_selection(asl_library_t *L, int64_t n, const uint8_t *keep) {
+  clear_error();
+  if (!L) return fail(ASL_ERR_INVALID, "library_set_selection: null library");
+  if (n != 0 && keep && n != L->n)
+    return fail(ASL_ERR_INVALID, "library_set_selection: %lld flags for a library of %lld rows", (long long)n,
+                (long long)L->n);
+  ASL_TRY(ensure_device());       // (waits for the batches in flight: they read the columns about to change)
+  L->has_sel = false;
+  ++L->sel_gen;                   // whatever an index derived from the columns so far is out of date
+  if (n == 0 || !keep) return ASL_OK;
+  ASL_TRY(L->keep.reserve((size_t)n));
+  ASL_TRY(L->wcol_eff.reserve((size_t)n));
+  ASL_TRY(L->valid_eff.reserve((size_t)n));
+  HIP_TRY(hipMemcpyAsync(L->keep.p, keep, (size_t)n, hipMemcpyDefault, stream()));
+  hipLaunchKernelGGL(selection_columns_kernel, grid_2d(cdiv(n, 256)), dim3(256), 0, stream(), L->keep.p, L->wcol.p,
+                     L->has_valid ? L->valid.p : nullptr, n, L->wcol_eff.p, L->valid_eff.p);
+  ASL_CHECK_LAUNCH();
+  ASL_TRY(sync_stream());         // a host array is the caller's again on return
+  L->has_sel = true;
+  return ASL_OK;
+}
+
 // CSR window candidates on the device: fills L->woff ([nq+1]) and L->cand; total -> *total.
 static int window_candidates_device(asl_library *L, int nq, const double *q_pmz_dev, int charge,
                                     double tol, int mode, int64_t *total) {
@@ -365,7 +417,7 @@ static int window_candidates_device(asl_library *L, int nq, const double *q_pmz_
   ASL_TRY(L->woff.upload(h_off.data(), (size_t)nq + 1));
   ASL_TRY(L->cand.reserve((size_t)std::max<int64_t>(acc, 1)));
   hipLaunchKernelGGL(window_fill_kernel, dim3(nq), dim3(256), 0, stream(), L->lo.p, L->woff.p,
-                     L->sorted_row.p, L->has_valid ? L->valid.p : nullptr, L->cand.p);
+                     L->sorted_row.p, L->valid_col(), L->cand.p);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }
@@ -422,7 +474,7 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
   rows_only.pass_all = true;
   WindowRows win;
   win.sorted_row = L->sorted_row.p;
-  win.valid = L->has_valid ? L->valid.p : nullptr;
+  win.valid = L->valid_col();
   // every buffer before the first launch (growing one synchronises the device)
   // (the winners' pass after several tiles scores one slot per winner)
   ASL_TRY(L->pair_score.reserve((size_t)(total <= B ? total : std::max<int64_t>(B, (int64_t)nw))));
@@ -639,7 +691,7 @@ static int search_batch_sync(asl_library_t *L, asl_index_t *idx, const asl_peaks
     ASL_TRY(L->knn.reserve((size_t)nq * k));
     ASL_TRY(L->pair_score.reserve((size_t)nq * k));
     const bool win = idx->window_scan != 0;
-    if (win) ASL_TRY(index_window_prepare(idx, L->serial, L->wcol.p, L->n, nq, P->nprobe));
+    if (win) ASL_TRY(index_window_prepare(idx, L->serial, L->sel_gen, L->window_col(), L->n, nq, P->nprobe));
     ASL_TRY(encode_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
                           d, P->hash_seed, 1, L->qvec.p));
     // the candidates are consumed as a set (filter + best match): no final sort unless the
@@ -649,6 +701,7 @@ static int search_batch_sync(asl_library_t *L, asl_index_t *idx, const asl_peaks
                    .rows = knn_I == nullptr ? ROWS_SET : ROWS_ORDERED};
     IndexWindow w;
     IndexPostFilter pf;
+    offer_library(rq, L);
     if (win) offer_window(rq, w, Q.dev, P, knn_I == nullptr ? L->rows_len.p : nullptr);
     else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(rq, pf, L, Q.dev, P, L->rows_len.p);
     ASL_TRY(index_search_device(idx, rq));
@@ -706,7 +759,7 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
   // allocations first (growing a buffer synchronises the device: only ever on the first batches)
   ASL_TRY(index_prepare(idx));
   const bool win = idx->window_scan != 0;      // (the window-ordered layout of THIS library, up front)
-  if (win) ASL_TRY(index_window_prepare(idx, L->serial, L->wcol.p, L->n, nq, nprobe));
+  if (win) ASL_TRY(index_window_prepare(idx, L->serial, L->sel_gen, L->window_col(), L->n, nq, nprobe));
   ASL_TRY(L->p_qvec[par].reserve((size_t)nq * d));
   ASL_TRY(L->p_cD[par].reserve((size_t)nq * nprobe));
   ASL_TRY(L->p_cI[par].reserve((size_t)nq * nprobe));
@@ -750,6 +803,7 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
                    .rows = knn_I == nullptr ? ROWS_SET : ROWS_ORDERED};
     IndexWindow w;
     IndexPostFilter pf;
+    offer_library(rq, L);
     if (win) offer_window(rq, w, Q.dev, P, knn_I == nullptr ? L->p_rows[par].p : nullptr);
     else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(rq, pf, L, Q.dev, P, L->p_rows[par].p);
     ASL_TRY(index_search_device(idx, rq));

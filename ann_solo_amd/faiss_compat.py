@@ -141,6 +141,51 @@ class Index:
                                                       int(self.nprobe), _lib.ptr(D), _lib.ptr(I)))
         return D, I
 
+    def set_selector(self, mask):
+        """Subset search: ``mask`` is one flag per vector id (True / non-zero: selected; len(mask) ==
+        ntotal), FAISS' ``IDSelectorBitmap``; ``None`` drops it. ``search_selected`` reads it, no other
+        search does. Derived state, never saved; add / reset / shard drop it."""
+        if mask is None:
+            _lib.check(_lib.lib().asl_index_set_selector(self._h, 0, None))
+            return
+        if hasattr(mask, 'data_ptr'):
+            import torch
+            mask = (mask != 0).to(dtype=torch.uint8).contiguous()
+        else:
+            mask = np.ascontiguousarray(np.asarray(mask).astype(bool), np.uint8)
+        if mask.ndim != 1:
+            raise ValueError('set_selector: one flag per vector id')
+        _lib.check(_lib.lib().asl_index_set_selector(self._h, int(mask.shape[0]), _lib.ptr(mask)))
+
+    def search_selected(self, x, k, window=None, D=None, I=None):
+        """``search`` among the selected vectors (``set_selector``) -- FAISS' ``search(x, k,
+        params=SearchParametersIVF(sel=IDSelectorBitmap(...)))``: (D, I), rows (score desc, id asc) of the
+        k best SELECTED vectors of the probed lists, -1 padded; what ``search`` would return from an index
+        that held only the selected vectors in the same lists. ``window``: None, or ``(precursor_mz,
+        charge, tol, mode)`` as in ``search_window`` -- then of the selected vectors only those whose key
+        (``set_window_key``) passes each query's precursor window. Tiled IVF-PQ and IVF-Flat postings,
+        k <= 1280; anything else raises."""
+        x = _as_f32(x, self.d)
+        nq = x.shape[0]
+        pmz, charge, tol, mode = None, 0, 0.0, 'Da'
+        if window is not None:
+            pmz, charge, tol, mode = window
+            pmz = pmz.double().contiguous() if hasattr(pmz, 'data_ptr') else np.ascontiguousarray(pmz, np.float64)
+            if tuple(pmz.shape) != (nq,):
+                raise ValueError('search_selected: the window needs one precursor m/z per query')
+        if D is None and I is None:
+            if isinstance(x, np.ndarray):
+                D = np.empty((nq, k), np.float32)
+                I = np.empty((nq, k), np.int64)
+            else:
+                import torch
+                D = torch.empty((nq, k), dtype=torch.float32, device=x.device)
+                I = torch.empty((nq, k), dtype=torch.int64, device=x.device)
+        _lib.check(_lib.lib().asl_index_search_selected(self._h, nq, _lib.ptr(x), _lib.ptr(pmz), int(charge),
+                                                        float(tol), {'Da': 0, 'ppm': 1}[mode], int(k),
+                                                        int(self.nprobe), _lib.ptr(D), _lib.ptr(I)))
+        return D, I
+
     def rank_of(self, x, target, nprobe=None, window=None):
         """Where library vector ``target[i]`` stands in the neighbour order of query ``x[i]``
         (``asl_index_rank``): ``(rank, score, scope)``, int64 / float32 / int64 [nq]. ``rank`` counts the

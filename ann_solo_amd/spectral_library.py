@@ -381,6 +381,8 @@ class SpectralLibrary:
         the results of the whole batch. Every rank must call ``search`` with the same queries."""
         if self.config.ann_window == 'pre':
             raise ValueError("enable_sharding: ann_window = 'pre' does not run on a sharded index")
+        if getattr(self, '_search_subset', False):
+            raise ValueError('enable_sharding: a search subset (set_search_subset) does not run on a sharded library')
         import torch.distributed as dist
         world = dist.get_world_size(group) if dist.is_initialized() else 1
         rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -529,6 +531,43 @@ class SpectralLibrary:
             if isinstance(g, (list, tuple, np.ndarray)):
                 g = np.ascontiguousarray(g, np.int32)
             _lib.check(L.asl_library_set_groups(part.handle, len(g), _lib.ptr(g)))
+
+    def set_search_subset(self, subset: Optional[Dict[int, np.ndarray]]) -> None:
+        """Search a subset of the library: ``{charge: bool array}``, one flag per row of that charge
+        partition (True: selected), copied to the partition's device handle
+        (``asl_library_set_selection``). Every partition must be named; ``None`` drops the subset.
+        Both cascade levels honour it: the standard search walks the selected rows of the window, the
+        open search's scan chooses its ``num_candidates`` among the selected vectors of the probed
+        lists (never a filter behind the top-k), and results are what a library of the selected rows
+        alone -- same row numbers, same index lists -- would return. Does not run on a sharded library."""
+        d = getattr(self, '_dist', None)
+        if d is not None and d.world > 1:
+            raise ValueError('set_search_subset does not run on a sharded library')
+        if subset is None:
+            L = _lib.lib()
+            for part in self.partitions.values():
+                if part.handle is not None:
+                    _lib.check(L.asl_library_set_selection(part.handle, 0, None))
+            self._search_subset = False
+            return
+        missing = sorted(set(self.partitions) - set(subset))
+        if missing:
+            raise ValueError(f'set_search_subset: no flags for charge(s) {missing}')
+        keep = {}
+        for z, part in self.partitions.items():
+            k = subset[z]
+            if isinstance(k, (list, tuple, np.ndarray)):
+                k = np.ascontiguousarray(np.asarray(k).astype(bool), np.uint8)
+            else:                                   # a torch tensor, host or device
+                k = (k != 0).to(dtype=torch.uint8).contiguous()
+            if tuple(k.shape) != (len(part.ids),):
+                raise ValueError(f'set_search_subset: {tuple(k.shape)} flags for the {len(part.ids)} rows of '
+                                 f'charge {z}')
+            keep[z] = k
+        L = _lib.lib()
+        for z, part in self.partitions.items():
+            _lib.check(L.asl_library_set_selection(part.handle, len(part.ids), _lib.ptr(keep[z])))
+        self._search_subset = True
 
     def _match_groups_from_peptides(self, library_meta) -> None:
         """``distinct_matches``: the group of a library row is its peptide (``library_meta[charge]

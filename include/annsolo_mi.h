@@ -195,6 +195,32 @@ int asl_index_search_window(asl_index_t *idx, int32_t nq, const float *xq, const
  * whenever the layout holds another library's key or the lists changed). Per handle. */
 int asl_index_set_window_scan(asl_index_t *idx, int32_t on);
 
+/* Subset search (FAISS: search(..., params=SearchParametersIVF(sel=IDSelectorBitmap(...)))). A selector is one
+ * byte per vector id, keep[id] != 0 = selected. A selected search returns what asl_index_search (or, with a
+ * window, asl_index_search_window) would return if the index held, in the same lists with the same centroids,
+ * codebooks and codes, only the selected vectors: the scans choose their k among the selected vectors of the
+ * probed lists -- select first, then top-k. Ids and score bits are those of the plain search; nothing is
+ * renumbered. The scans read the selector as bits in storage order (a 64-bit word per 64-vector tile of the
+ * IVF-PQ layouts, 13 words per block of IVF-Flat postings), derived like the window-ordered layout: never
+ * saved, rebuilt when the selector or the lists change. Unselected codes and postings are still read.
+ * asl_index_set_selector: n == ntotal (else ASL_ERR_INVALID): copied (keep: host or device memory); n == 0 or
+ * keep == NULL drops it. add, add_preassigned, reset and shard drop it too. Waits for pipelined batches in
+ * flight. asl_index_search, asl_index_search_window and every other search ignore it. */
+int asl_index_set_selector(asl_index_t *idx, int64_t n, const uint8_t *keep);
+/* The ordered top-k (score desc, id asc; -1 / -FLT_MAX padded) among the selected vectors of the probed
+ * lists; same coarse quantiser and nprobe as asl_index_search. q_pmz == NULL: no window (charge, tol, mode
+ * unread). With q_pmz, of the selected vectors only those whose window key passes precursor_ok(q_pmz[i], key,
+ * charge, tol, mode): the window-ordered layout, which needs asl_index_set_window_key (and, like it, IVF-PQ).
+ * Served by the tiled IVF-PQ scan (m = 32, 8 bits, by_residual on or off) and the IVF-Flat postings scan
+ * (float and fixed-point postings), k <= 1280, nprobe <= 1024. Everything else is ASL_ERR_STATE with a message
+ * that names the reason, never a filter behind the top-k: no selector (or the lists changed since it was set),
+ * scan_variant 1, other PQ shapes, dense-row IVF-Flat, a Flat index, k > 1280, an index with the exact
+ * re-rank on (asl_index_set_refine, k < kprime), packed-key rows (asl_index_set_unordered 2), a sharded index;
+ * and, for requests that reach the index from inside the library, a gate or entry-list-only queries. */
+int asl_index_search_selected(asl_index_t *idx, int32_t nq, const float *xq, const double *q_pmz /* NULL: no window */,
+                              int32_t charge, double tol, int32_t mode, int32_t k, int32_t nprobe, float *D,
+                              int64_t *I);
+
 /* Rank of a given vector in the index's neighbour order (replaces the measurement of the reference's
  * notebooks/iprg2012_num_candidates.ipynb, the cell that searches IndexFlatIP with num_neighbors =
  * 1000000 and looks up where the brute-force match stands): rank[i] = the number of vectors v of the
@@ -209,7 +235,8 @@ int asl_index_set_window_scan(asl_index_t *idx, int32_t on);
  * where rank is -1; scope (optional): the number of vectors in the scope. Nothing is kept on the
  * handle. IVF-Flat with float postings and the tiled IVF-PQ (m = 32, 8 bits) only; ASL_ERR_STATE for
  * fixed-point postings, dense-row IVF-Flat, the generic kernels (scan_variant 1, other PQ shapes), a
- * Flat index and a sharded one. */
+ * Flat index and a sharded one. A selector (asl_index_set_selector, asl_library_set_selection) is ignored: the scope is
+ * every vector of the probed lists. */
 int asl_index_rank(asl_index_t *idx, int32_t nq, const float *xq, const int64_t *target /* [nq] */,
                    int32_t nprobe /* 0: all lists */, const float *key /* [ntotal] or NULL: no window */,
                    const double *q_pmz, int32_t charge, double tol, int32_t mode, int64_t *rank /* [nq] */,
@@ -550,6 +577,22 @@ int64_t asl_library_size(const asl_library_t *lib);
  * to the device; the array is the caller's again on return. group == NULL drops the column (n is
  * ignored). Setting it again replaces it. No other entry point reads it. */
 int asl_library_set_groups(asl_library_t *lib, int64_t n, const int32_t *group);
+/* Search a subset of the library: keep[n], keep[row] != 0 = selected, host or device memory, n ==
+ * asl_library_size(lib) (anything else: ASL_ERR_INVALID); copied, the array is the caller's again on return.
+ * n == 0 or keep == NULL drops the selection. Waits for pipelined batches in flight. While a selection is
+ * installed every result of asl_search_batch / _topn / _topn_distinct, synchronous or pipelined, is what the
+ * same call would return if the unselected rows were invalid library rows (never a candidate) AND the ANN index
+ * held, in the same lists with the same centroids, codebooks and codes, only the selected vectors: the scans
+ * choose their k among the selected vectors of the probed lists (as asl_index_search_selected), then the
+ * precursor window applies as configured (asl_set_scan_postfilter, asl_index_set_window_scan); use_ann = 0
+ * walks the selected rows of the window at any pair budget; asl_rescore_knn* drop an unselected row among the
+ * caller's ids. Row numbers and score bits do not change. The selection has a generation number beside the
+ * library's serial: an index notices a replaced or dropped selection as it notices another library, and
+ * rebuilds what it derived (selector words, post-filter pairs, window-ordered layout). Where the index cannot
+ * select inside its scan (the cases asl_index_search_selected lists) the fused calls return its
+ * ASL_ERR_STATE. Without a selection every call runs the kernels and launches it ran before; dropping one
+ * restores those results bit for bit. The selector of asl_index_set_selector plays no part in the fused calls. */
+int asl_library_set_selection(asl_library_t *lib, int64_t n, const uint8_t *keep);
 
 typedef struct {
   double min_bound, bin_size; /* encoder grid (get_dim) */
