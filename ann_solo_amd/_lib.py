@@ -70,7 +70,7 @@ EXPORTS = [
     'asl_index_pq_lut', 'asl_rescore_batch', 'asl_library_create', 'asl_library_free',
     'asl_library_size', 'asl_search_batch', 'asl_window_candidates', 'asl_profile_enable',
     'asl_profile_reset', 'asl_profile_get', 'asl_profile_scanned_vectors',
-    'asl_rescore_knn', 'asl_lpt_owner', 'asl_index_supports_keys', 'asl_index_search_sharded', 'asl_index_postings_work', 'asl_index_set_refine', 'asl_index_get_refine', 'asl_index_refine', 'asl_index_set_scan_variant', 'asl_index_search_preassigned', 'asl_process_batch',
+    'asl_rescore_knn', 'asl_lpt_owner', 'asl_index_supports_keys', 'asl_index_search_sharded', 'asl_index_postings_work', 'asl_index_set_refine', 'asl_index_get_refine', 'asl_index_refine', 'asl_index_set_scan_variant', 'asl_index_codes_mmajor', 'asl_index_search_preassigned', 'asl_process_batch',
     'asl_ssm_features_batch', 'asl_ssm_cosine_batch', 'asl_index_set_unordered', 'asl_topk_merge_keys',
     'asl_index_set_flat_storage', 'asl_index_get_flat_storage', 'asl_index_flat_layout',
     'asl_keys_split', 'asl_keys_merge_heads', 'asl_keys_extras', 'asl_keys_merge_final',
@@ -179,6 +179,8 @@ def lib():
         L.asl_index_load.restype = C.c_void_p
         L.asl_index_set_niter.argtypes = [C.c_void_p, C.c_int32]
         L.asl_index_set_scan_variant.argtypes = [C.c_void_p, C.c_int32]
+        if hasattr(L, 'asl_index_codes_mmajor'):      # (an older library given by ASL_LIB_PATH has none)
+            L.asl_index_codes_mmajor.argtypes = [C.c_void_p]
         L.asl_index_set_window_key.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.asl_index_search_window.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                               C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,

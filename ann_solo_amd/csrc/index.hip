@@ -97,12 +97,17 @@ int asl_index_get_flat_storage(const asl_index_t *ix) { return ix ? ix->flat_sto
 
 int asl_index_set_scan_variant(asl_index_t *ix, int32_t variant) {
   clear_error();
-  if (!ix || variant < 0 || variant > 1)
-    return fail(ASL_ERR_INVALID, "set_scan_variant: 0 (layout-specific scan) or 1 (generic kernels)");
-  ix->scan_variant = variant;
+  if (!ix || variant < 0 || variant > 2)
+    return fail(ASL_ERR_INVALID, "set_scan_variant: 0 (layout-specific scan), 1 (generic kernels) or 2 (as 0, the tiled "
+                                 "IVF-PQ scan reading its tile-major codes only)");
+  // 2: every layout-specific kernel as under 0, but no scan of the sub-quantiser-major copy (both in one process)
+  ix->scan_variant = variant == 1 ? 1 : 0;
+  ix->scan_mmajor = variant == 0;
   ix->agreed_val = -1;      // asl_index_supports_keys depends on the variant: the ranks agree again
   return ASL_OK;
 }
+
+int asl_index_codes_mmajor(const asl_index_t *ix) { return ix && ix->mm_ready && !ix->lists_dirty ? 1 : 0; }
 
 int asl_index_set_window_scan(asl_index_t *ix, int32_t on) {
   clear_error();

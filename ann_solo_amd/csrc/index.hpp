@@ -113,6 +113,14 @@ struct asl_index {
   uint64_t win_gen = 0;          // ... and the generation of its selection
   int window_scan = 0;           // asl_index_set_window_scan: asl_search_batch scans each query's window only
   asl::DevBuf<int2> win_ranges;       // [nq, nprobe] in-window run of each probed list
+  // sub-quantiser-major copy of codes_tiled (index_codes_mmajor; pq_scan_v3.hip, MM): 32 planes of mm_plane bytes,
+  // plane m = sub-quantiser m's 64 bytes of every tile of the default layout, in tile order. The plain tiled scan
+  // reads it instead of codes_tiled and skips the planes of a query's all-zero sub-vectors. Derived on the device,
+  // never saved, dropped by build_lists, rebuilt by the next plain scan; one more copy of the codes in memory.
+  asl::DevBuf<uint8_t> codes_mm;
+  uint32_t mm_plane = 0;
+  bool mm_ready = false;
+  bool scan_mmajor = true;       // asl_index_set_scan_variant(2) clears it: variant 0 with the tile-major codes only
   // selector words of the scans (ivf_kernels.hpp: tile_selector / flat_selector), derived like idpay: never
   // saved, dropped by build_lists, rebuilt when (serial, generation) of the selector or the lists change.
   // sel_words: per tile of the default layout (IVF-PQ) or per 64 positions of a block (IVF-Flat);
@@ -198,6 +206,7 @@ int index_window_prepare(asl_index *ix, uint64_t serial, uint64_t gen, const flo
 int index_refine_k(const asl_index *ix);
 int coarse_scores_all(asl_index *ix, const float *xq, int m, float *scores, uint2 *ent = nullptr, int32_t *cnt = nullptr);
 int index_codebooks_transposed(asl_index *ix);
+int index_codes_mmajor(asl_index *ix);   // index_search.hip: the sub-quantiser-major copy, built when missing (mm_ready)
 // n zeros (grow-only, cleared when it grows): the coarse_D of an IVF-PQ index with by_residual off
 int index_zero_coarse(asl_index *ix, size_t n, const float **zeros);
 

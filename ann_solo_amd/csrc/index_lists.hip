@@ -14,6 +14,7 @@ int build_lists(asl_index *ix) {
   ix->agreed_val = -1;
   ix->idpay_ready = false;
   ix->win_ready = false;
+  ix->mm_ready = false;
   ix->win_serial = 0;
   ix->sel_ready = ix->wsel_ready = false;
   ix->has_selector = false;       // (one byte per vector of the lists as they were)

@@ -344,6 +344,22 @@ int index_zero_coarse(asl_index *ix, size_t n, const float **zeros) {
   return ASL_OK;
 }
 
+// The sub-quantiser-major copy of the default layout's codes (pq_scan_v3.hip, MM), built from codes_tiled when a
+// plain scan finds none: after the lists changed, build_lists dropped it. The plane size is a whole number of
+// 128-byte lines, and an odd one, so that the 32 planes of a tile do not start a power of two apart.
+int index_codes_mmajor(asl_index *ix) {
+  if (ix->mm_ready) return ASL_OK;
+  const int64_t ntiles = ix->n_tile_slots / 64;
+  const uint64_t plane = ((((uint64_t)ntiles * 64 + 127) / 128) | 1u) * 128;
+  if (plane * (uint64_t)ix->pq_m >= (1ull << 32)) return ASL_OK;     // lane offsets are 32 bits: such an index stays tile-major
+  ASL_TRY(ix->codes_mm.reserve((size_t)plane * (size_t)ix->pq_m));
+  ASL_TRY(mmajor_codes(ix->codes_tiled.p, ntiles, (uint32_t)plane, ix->codes_mm.p));
+  ASL_TRY(sync_stream());      // (as build_lists after tile_codes: later scans may run on the pipeline's other stream)
+  ix->mm_plane = (uint32_t)plane;
+  ix->mm_ready = true;
+  return ASL_OK;
+}
+
 // IVF-PQ, tiled scan (pq_scan_v3.hip), over the default layout or -- rq.win -- over the in-window
 // run of every probed list in the window-ordered one
 static int scan_pq_tiled(asl_index *ix, IndexSearch &rq, const SearchPlan &pl, const float *cD, const int32_t *cI,
@@ -371,11 +387,17 @@ static int scan_pq_tiled(asl_index *ix, IndexSearch &rq, const SearchPlan &pl, c
   }
   const unsigned long long *sel = nullptr;
   if (rq.sel_keep) ASL_TRY(selector_words(ix, rq, rq.win != nullptr, &sel));
+  // a plain request (no window, selector or gate, the whole index here) is scanned from the sub-quantiser-major
+  // copy: same tiles, same slots, same results; the bytes of a query's all-zero sub-vectors are not fetched
+  const bool mm = ix->scan_mmajor && !rq.win && !rq.sel_keep && !rq.gate && ix->shard_world == 1 && !ix->has_vids;
+  if (mm) ASL_TRY(index_codes_mmajor(ix));
+  const bool use_mm = mm && ix->mm_ready;
   ProfScope ps("scan");     // the scan kernel itself
   return pq_scan_v3(rq.xq, nq, ix->d, ix->codebooks_t.p, ix->dsub, cD, cI,
                     nprobe, ix->list_offsets.p, ix->tile_offsets.p,
                     rq.win ? ix->wcodes_tiled.p : ix->codes_tiled.p, rq.win ? ix->wids_tiled.p : ix->ids_tiled.p,
-                    rq.k, rq.D, rq.I64, rq.I32, mode_, q_ent, q_cnt, rq.gate, &pf, &rg, sel);
+                    rq.k, rq.D, rq.I64, rq.I32, mode_, q_ent, q_cnt, rq.gate, &pf, &rg, sel,
+                    use_mm ? ix->codes_mm.p : nullptr, use_mm ? ix->mm_plane : 0u);
 }
 
 // IVF-PQ: coarse stage, then the tiled scan or the generic kernel (which takes no post-filter)

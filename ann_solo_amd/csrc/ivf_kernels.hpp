@@ -71,7 +71,12 @@ int pq_scan_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
                const int *gate = nullptr,
                const ScanPostFilter *post = nullptr,   // (common.hpp) set-mode int32 rows, k <= 1280 only          // device-side row count: workgroups past it return at once
                const ScanRanges *ranges = nullptr,   // (common.hpp) window scan of the window-ordered layout, k <= 1280
-               const unsigned long long *sel = nullptr);   // selector: a word per tile of the layout scanned, k <= 1280
+               const unsigned long long *sel = nullptr,    // selector: a word per tile of the layout scanned, k <= 1280
+               const uint8_t *codes_mm = nullptr,          // the sub-quantiser-major copy of codes_tiled and its plane
+               uint32_t mm_plane = 0);                     // size (mmajor_codes): plain requests are scanned from it
+// sub-quantiser-major copy of tile-major codes: plane m (plane bytes, a multiple of 128 and >= ntiles * 64) holds
+// sub-quantiser m's 64 bytes of every tile in tile order; codes_mm: 32 * plane bytes
+int mmajor_codes(const uint8_t *codes_tiled, int64_t ntiles, uint32_t plane, uint8_t *codes_mm);
 // selector words of a tiled layout: bit v of words[tile] = keep[slot_ids[tile * 64 + v]] (id -1: unselected)
 int tile_selector(const int32_t *slot_ids, int64_t ntiles, const uint8_t *keep, int64_t n,
                   unsigned long long *words);

@@ -95,7 +95,12 @@ static_assert(V3_CHUNK_RANGED * sizeof(TileEnt12) <= V3_CHUNK * sizeof(TileEnt8)
 // load into two scalar registers -- and is one more term of append()'s `in`: an unselected vector is scored
 // like any other and never offered, so the k best are chosen among the selected vectors alone. Reservation,
 // refused-tile retry, exact flushes and both finishes are those of the plain instantiations.
-template <int CAP, int T, int NW, int DEPTH, bool WIDE, bool RANGED = false, bool SEL = false>
+// MM (the plain instantiations only; index_codes_mmajor): codes_tiled is the SUB-QUANTISER-MAJOR copy --
+// plane m, mm_plane bytes each, holds sub-quantiser m's 64 bytes of every tile, tile after tile, in the tile's
+// own row order and byte permutation -- so a 128-byte line holds one sub-quantiser only, and a lane whose
+// sub-quantiser has no non-zero query component (its LUT column is +0.0 whatever the code) does not load: its
+// register keeps whatever bytes it holds, and the sums are those of the tile-major scan bit for bit.
+template <int CAP, int T, int NW, int DEPTH, bool WIDE, bool RANGED = false, bool SEL = false, bool MM = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIMD : 4) : (CAP <= 2048 ? 3 : 1))) void pq_scan_v3_kernel(
     const float *__restrict__ xq, int d, const float *__restrict__ codebooks, int dsub,
     const float *__restrict__ coarse_D, const int32_t *__restrict__ coarse_I, int nprobe,
@@ -103,8 +108,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     const uint8_t *__restrict__ codes_tiled, const int32_t *__restrict__ ids_tiled, int k,
     float *__restrict__ D, int64_t *__restrict__ I64, int32_t *__restrict__ I32, int set_mode,
     const uint2 *__restrict__ ent, const int32_t *__restrict__ ent_cnt, const int *__restrict__ gate,
-    const ScanPostFilter pf, const ScanRanges rg, const unsigned long long *__restrict__ sel) {
+    const ScanPostFilter pf, const ScanRanges rg, const unsigned long long *__restrict__ sel, const uint32_t mm_plane) {
   static_assert(!SEL || CAP <= 2048, "the selector is built into the 2048-key instantiations only");
+  static_assert(!MM || (!RANGED && !SEL), "the sub-quantiser-major copy exists of the default layout only");
   // gate: a device-side row count -- workgroups past it leave at once (a launch of fixed size over
   // a list whose length only the device knows: the shard-side rescans of exchange.hip)
   if (gate && (int)blockIdx.x >= *gate) return;
@@ -155,6 +161,20 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
                                                                         // not live yet; entry lists only: a row with
                                                                         // more than 64 non-zeros is searched as all-zero
 
+  // MM: the sub-quantisers that have a non-zero query component, from the list the table build walked
+  // (K entries, nz_m at +8 of its scratch, which is the tile table's memory and dies with the scan below)
+  uint32_t live_u = 0;
+  if constexpr (MM) {
+    const uint8_t *s_nz = reinterpret_cast<const uint8_t *>(table);
+    const int K = reinterpret_cast<const int *>(s_nz)[0];
+    uint32_t mine = 0;
+    for (int i = tid & 63; i < K; i += 64) mine |= 1u << (s_nz[8 + i] & 31);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine |= (uint32_t)__shfl_xor((int)mine, o);
+    live_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)mine);
+    __syncthreads();
+  }
+
   // ---- exclusive scan of the probes' tile counts (probe order: p, then p + NT)
   int total = 0;
   int *scan_part = reinterpret_cast<int *>(table);   // table is not live yet
@@ -176,7 +196,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
   const int rho = lane >> 4, j = lane & 15;
   const int ma = (rho & 1) ? j + 16 : j, mb = ma ^ 16;
   const uint32_t offA = (uint32_t)ma * 4u, offB = (uint32_t)mb * 4u;
-  const uint32_t chunkA = (uint32_t)(rho * 512 + ma * 16);
+  // lane part of a tile's two code loads: tile-major rho * 512 + m * 16; MM: plane m, row rho
+  const uint32_t chunkA = MM ? (uint32_t)ma * mm_plane + (uint32_t)(rho * 16) : (uint32_t)(rho * 512 + ma * 16);
+  const uint32_t chunkB = (uint32_t)mb * mm_plane + (uint32_t)(rho * 16);   // (MM only)
+  const bool liveA = (live_u >> ma) & 1u, liveB = (live_u >> mb) & 1u;      // (MM only)
 
   // ---- free-running appends (HistTopK's free_* protocol, as in flat_scan.hip) -------------------
   // A wave walks its own share of a table chunk (entries wave, wave + NW, ...) with its own register
@@ -240,6 +263,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     // score, and the step is instantiated per set, so every register index is a compile-time constant.
     constexpr int NS = DEPTH + 1;
     uint4 A[NS], B[NS];
+    if constexpr (MM) {   // a lane that never loads still indexes the table: any bytes, but defined ones
+#pragma unroll
+      for (int s = 0; s < NS; ++s) A[s] = B[s] = make_uint4(0u, 0u, 0u, 0u);
+    }
     struct Tile {         // the entry is the same for the whole wave: scalar registers
       uint32_t tile_nv;   // tile | last lane << 26
       float coarse;
@@ -255,12 +282,20 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
       // the tile's address is a scalar and the lane's part a 32-bit offset of its own: the loads take
       // them as they are (scalar base + lane offset), no 64-bit lane addresses to keep or add up per tile
       // (the second chunk's offset is made here from the first: a lane constant less to keep)
-      const uint8_t *base = codes_tiled + (size_t)(en.tile_nv & 0x3ffffffu) * 2048;
-      uint32_t offa = chunkA;
-      asm volatile("" : "+v"(offa));
-      const uint32_t offb = offa ^ 256u;       // mb = ma ^ 16
-      a = load_codes16<V3_NT>(base + offa);
-      b = load_codes16<V3_NT>(base + offb);
+      if constexpr (MM) {
+        const uint8_t *base = codes_tiled + (size_t)(en.tile_nv & 0x3ffffffu) * 64;
+        uint32_t offa = chunkA, offb = chunkB;   // (values of their own, as below: scalar base + 32-bit lane offset)
+        asm volatile("" : "+v"(offa), "+v"(offb));
+        if (liveA) a = load_codes16<V3_NT>(base + offa);
+        if (liveB) b = load_codes16<V3_NT>(base + offb);
+      } else {
+        const uint8_t *base = codes_tiled + (size_t)(en.tile_nv & 0x3ffffffu) * 2048;
+        uint32_t offa = chunkA;
+        asm volatile("" : "+v"(offa));
+        const uint32_t offb = offa ^ 256u;       // mb = ma ^ 16
+        a = load_codes16<V3_NT>(base + offa);
+        b = load_codes16<V3_NT>(base + offb);
+      }
     };
     // the tile whose candidates wait to be appended: its scores and (scalar) its entry
     float p_score = 0.0f;
@@ -389,14 +424,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
                I32 ? I32 + (size_t)q * k : nullptr);
 }
 
-template <int CAP, int T, int NW, int DEPTH, bool WIDE, bool RANGED = false, bool SEL = false>
+template <int CAP, int T, int NW, int DEPTH, bool WIDE, bool RANGED = false, bool SEL = false, bool MM = false>
 static int launch_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
                      const float *coarse_D, const int32_t *coarse_I, int nprobe,
                      const int32_t *list_offsets, const int32_t *tile_offsets,
                      const uint8_t *codes_tiled, const int32_t *ids_tiled, int k, float *D,
                      int64_t *I64, int32_t *I32, int set_mode, const uint2 *ent,
                      const int32_t *ent_cnt, const int *gate, const ScanPostFilter &pf,
-                     const ScanRanges &rg, const unsigned long long *sel = nullptr) {
+                     const ScanRanges &rg, const unsigned long long *sel = nullptr, uint32_t mm_plane = 0) {
   // (the ranged table -- V3_CHUNK_RANGED entries of TileEnt12 -- fits the same bytes)
   constexpr size_t TABLE = RANGED ? V3_CHUNK_RANGED * sizeof(TileEnt12) : V3_CHUNK * sizeof(TileEnt8);
   if ((size_t)d * 4 > (size_t)CAP * 8 || dsub > 64 || (size_t)d * 2 + 8 > TABLE || d != PQT_M * dsub)
@@ -405,11 +440,11 @@ static int launch_v3(const float *xq, int nq, int d, const float *codebooks, int
                      (size_t)V3_CHUNK * sizeof(TileEnt8);
   if (lds > 160 * 1024) return fail(ASL_ERR_CAPACITY, "pq scan: k=%d does not fit LDS", k);
   if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute((const void *)pq_scan_v3_kernel<CAP, T, NW, DEPTH, WIDE, RANGED, SEL>,
+    HIP_TRY(hipFuncSetAttribute((const void *)pq_scan_v3_kernel<CAP, T, NW, DEPTH, WIDE, RANGED, SEL, MM>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((pq_scan_v3_kernel<CAP, T, NW, DEPTH, WIDE, RANGED, SEL>), dim3(nq), dim3(64 * NW), lds, stream(),
+  hipLaunchKernelGGL((pq_scan_v3_kernel<CAP, T, NW, DEPTH, WIDE, RANGED, SEL, MM>), dim3(nq), dim3(64 * NW), lds, stream(),
                      xq, d, codebooks, dsub, coarse_D, coarse_I, nprobe, list_offsets, tile_offsets,
-                     codes_tiled, ids_tiled, k, D, I64, I32, set_mode, ent, ent_cnt, gate, pf, rg, sel);
+                     codes_tiled, ids_tiled, k, D, I64, I32, set_mode, ent, ent_cnt, gate, pf, rg, sel, mm_plane);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }
@@ -425,7 +460,7 @@ int pq_scan_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
                const uint8_t *codes_tiled, const int32_t *ids_tiled, int k, float *D,
                int64_t *I64, int32_t *I32, int set_mode, const uint2 *ent, const int32_t *ent_cnt,
                const int *gate, const ScanPostFilter *post, const ScanRanges *ranges,
-               const unsigned long long *sel) {
+               const unsigned long long *sel, const uint8_t *codes_mm, uint32_t mm_plane) {
   if (nq <= 0) return ASL_OK;
   // the post-filter needs the set-mode finish of the 2048-key instantiation (its scratch behind the keys)
   ScanPostFilter pf;
@@ -452,6 +487,17 @@ int pq_scan_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
   if (sel) {
     if (nprobe > 512) return launch_v3<2048, 1, 8, V3_DEPTH, true, false, true>(V3_ARGS, none, sel);
     return launch_v3<2048, 1, 8, V3_DEPTH, false, false, true>(V3_ARGS, none, sel);
+  }
+  if (codes_mm && !gate) {    // the sub-quantiser-major copy: plain requests (the caller gives it to no other)
+#define V3_MM_ARGS xq, nq, d, codebooks, dsub, coarse_D, coarse_I, nprobe, list_offsets, tile_offsets, \
+                   codes_mm, ids_tiled, k, D, I64, I32, set_mode, ent, ent_cnt, gate, pf, none, nullptr, mm_plane
+    if (nprobe > 512) {
+      if (k + 256 + 512 <= 2048) return launch_v3<2048, 1, 8, V3_DEPTH, true, false, false, true>(V3_MM_ARGS);
+      return launch_v3<4096, 1, 8, V3_DEPTH, true, false, false, true>(V3_MM_ARGS);
+    }
+    if (k + 256 + 512 <= 2048) return launch_v3<2048, 1, 8, V3_DEPTH, false, false, false, true>(V3_MM_ARGS);
+    return launch_v3<4096, 1, 8, V3_DEPTH, false, false, false, true>(V3_MM_ARGS);
+#undef V3_MM_ARGS
   }
   if (nprobe > 512) {         // two probes per thread (the one-probe form keeps its registers)
     if (k + 256 + 512 <= 2048) return launch_v3<2048, 1, 8, V3_DEPTH, true>(V3_ARGS, none);
@@ -549,6 +595,25 @@ int tile_codes(const uint8_t *codes, const int32_t *ids, const int32_t *dst_slot
   if (n <= 0) return ASL_OK;
   hipLaunchKernelGGL(tile_codes_kernel, grid_2d(cdiv(n * PQT_M, 256)), dim3(256), 0,
                      stream(), codes, ids, dst_slot, n, codes_tiled, ids_tiled);
+  ASL_CHECK_LAUNCH();
+  return ASL_OK;
+}
+
+// tile-major codes -> the sub-quantiser-major copy (MM above): one thread per 16-byte chunk (tile, rho, m)
+__global__ void mmajor_codes_kernel(const uint4 *__restrict__ codes_tiled, int64_t ntiles, uint32_t plane,
+                                    uint8_t *__restrict__ codes_mm) {
+  const int64_t t = block_linear() * blockDim.x + threadIdx.x;
+  if (t >= ntiles * 128) return;
+  const int64_t tile = t >> 7;
+  const int rho = (int)(t >> 5) & 3, m = (int)(t & 31);
+  *reinterpret_cast<uint4 *>(codes_mm + (size_t)m * plane + (size_t)tile * 64 + rho * 16) = codes_tiled[t];
+}
+
+int mmajor_codes(const uint8_t *codes_tiled, int64_t ntiles, uint32_t plane, uint8_t *codes_mm) {
+  HIP_TRY(hipMemsetAsync(codes_mm, 0, (size_t)plane * PQT_M, stream()));
+  if (ntiles <= 0) return ASL_OK;
+  hipLaunchKernelGGL(mmajor_codes_kernel, grid_2d(cdiv(ntiles * 128, 256)), dim3(256), 0, stream(),
+                     reinterpret_cast<const uint4 *>(codes_tiled), ntiles, plane, codes_mm);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }

@@ -85,6 +85,11 @@ class Index:
         self.epoch += 1
         _lib.check(_lib.lib().asl_index_set_scan_variant(self._h, int(variant)))
 
+    @property
+    def codes_mmajor(self) -> bool:
+        """True while the sub-quantiser-major copy of the IVF-PQ codes exists and matches the lists."""
+        return bool(_lib.lib().asl_index_codes_mmajor(self._h))
+
     def train(self, x):
         self.epoch += 1
         x = _as_f32(x, self.d)

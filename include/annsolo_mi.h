@@ -268,8 +268,15 @@ int asl_index_flat_layout(asl_index_t *idx);
  * and for the parity tests): 0 = the layout-specific kernels (IVF-PQ: the tiled
  * sub-quantiser-per-lane scan with the histogram top-k when m = 32, 8 bits, nprobe <= 256;
  * IVF-Flat: the per-dimension postings scan), 1 = the generic kernels (IVF-PQ: lane-per-vector
- * scan; IVF-Flat: dense GEMM + masked top-k). Any other value is ASL_ERR_INVALID. */
+ * scan; IVF-Flat: dense GEMM + masked top-k), 2 = as 0, except that the tiled IVF-PQ scan reads its
+ * tile-major codes only. Under 0 a plain IVF-PQ search (no window, selector or gate, unsharded) is scanned
+ * from a second, sub-quantiser-major copy of the codes, of which a query fetches only the lines of the
+ * sub-vectors in which it has a non-zero component; the copy is derived on the device by the first such
+ * search after the lists changed, is never saved, and takes as much memory as the codes themselves.
+ * asl_index_codes_mmajor: 1 while that copy exists and matches the lists, else 0.
+ * Any other value is ASL_ERR_INVALID. */
 int asl_index_set_scan_variant(asl_index_t *idx, int32_t variant);
+int asl_index_codes_mmajor(const asl_index_t *idx);
 
 /* Introspection, used by the parity tests and by multi-GPU sharding. Sizes via
  * asl_index_info; every pointer may be NULL to skip. Lists are stored in list

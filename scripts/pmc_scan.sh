@@ -14,7 +14,8 @@ pass() {  # name counters...
   rm -rf /tmp/pmc_${tag}_$name
   timeout -k 10 300 rocprofv3 --pmc "$@" --kernel-include-regex "pq_scan" --output-format csv \
      -d /tmp/pmc_${tag}_$name -o x -- python3 bench.py --steps 4 --warmup 1 "${BENCH_ARGS[@]}" \
-     > /tmp/pmc_${tag}_$name.log 2>&1 || return 1
+     > /tmp/pmc_${tag}_$name.log 2>&1 ||
+     { rc=$?; echo "[$name] pass failed, exit $rc" >> "$out/pmc_summary.txt"; return $rc; }
   python3 - "$name" /tmp/pmc_${tag}_$name <<'PY' >> "$out/pmc_summary.txt"
 import csv, sys, collections, glob
 name, root = sys.argv[1], sys.argv[2]
@@ -38,4 +39,5 @@ PY
 BENCH_ARGS=("$@")
 pass sq SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES &&
 pass tcc FETCH_SIZE &&
+pass busy VALUBusy GRBM_GUI_ACTIVE &&
 cat "$out/pmc_summary.txt"

@@ -1,0 +1,102 @@
+// Issue rate of wave64 vector instructions: what one SIMD sustains at W waves per SIMD, and what the profiler's
+// VALU counters say of a kernel that does nothing else (profiles/pq_mmajor_before.txt).
+//   hipcc -O3 --offload-arch=gfx950 -o valu_issue_rate scripts/valu_issue_rate.hip && ./valu_issue_rate
+//   rocprofv3 --pmc VALUBusy SQ_INSTS_VALU SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE -- ./valu_issue_rate
+// Workgroups of 4 waves (one per SIMD); the LDS size keeps exactly W of them on a CU. Per wave: s_memtime ticks
+// around 65 536 independent instructions; per kernel: wall time over instructions per SIMD.
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("hip error %s at %d\n", hipGetErrorString(e_), __LINE__); exit(2); } } while (0)
+
+constexpr int ITER = 4096, UNR = 16;   // 65536 instructions per wave
+
+template <int KIND>
+__global__ void k(float *out, long long *ticks, float seed) {
+  extern __shared__ char lds[];
+  float a[UNR];
+  for (int i = 0; i < UNR; i++) a[i] = seed + threadIdx.x * 0.001f + i;
+  const float b = seed * 0.5f, c = seed * 0.25f;
+  __syncthreads();
+  const long long t0 = __builtin_readcyclecounter();
+  for (int it = 0; it < ITER; it++) {
+#pragma unroll
+    for (int i = 0; i < UNR; i++) {
+      if (KIND == 0) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(a[i]) : "v"(b), "v"(c));
+      if (KIND == 1) asm volatile("v_add_f32 %0, %0, %1" : "+v"(a[i]) : "v"(b));
+      if (KIND == 2) asm volatile("v_add_f32_dpp %0, %1, %0 row_mirror row_mask:0xf bank_mask:0xf" : "+v"(a[i]) : "v"(a[(i + 1) % UNR]));
+      if (KIND == 3) asm volatile("v_lshl_add_u32 %0, %0, 7, %1" : "+v"(a[i]) : "v"(b));
+      if (KIND == 4) asm volatile("v_and_b32 %0, 0xff, %0" : "+v"(a[i]));
+      if (KIND == 5) asm volatile("v_bfe_u32 %0, %0, 8, 8" : "+v"(a[i]));
+    }
+  }
+  const long long t1 = __builtin_readcyclecounter();
+  float s = 0;
+  for (int i = 0; i < UNR; i++) s += a[i];
+  out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+  if ((threadIdx.x & 63) == 0) ticks[blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64] = t1 - t0;
+}
+
+template <int KIND>
+__global__ void kpk(float *out, long long *ticks, float seed) {   // v_pk_add_f32: two floats per lane
+  extern __shared__ char lds[];
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  f2 a[UNR];
+  for (int i = 0; i < UNR; i++) a[i] = f2{seed + threadIdx.x * 0.001f + i, seed};
+  const f2 b = {seed * 0.5f, seed * 0.25f};
+  __syncthreads();
+  const long long t0 = __builtin_readcyclecounter();
+  for (int it = 0; it < ITER; it++) {
+#pragma unroll
+    for (int i = 0; i < UNR; i++) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(a[i]) : "v"(b));
+  }
+  const long long t1 = __builtin_readcyclecounter();
+  float s = 0;
+  for (int i = 0; i < UNR; i++) s += a[i].x + a[i].y;
+  out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+  if ((threadIdx.x & 63) == 0) ticks[blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64] = t1 - t0;
+}
+
+template <typename F>
+static void run(const char *name, F kern, int W, float *out, long long *ticks) {
+  // workgroups of 4 waves (one per SIMD), exactly W of them fit a CU's 160 KB of LDS
+  const int nblk = 256 * W, nthr = 256;
+  const int lds = W == 1 ? 100 * 1024 : W == 2 ? 70 * 1024 : W == 4 ? 36 * 1024 : W == 6 ? 24 * 1024 : 19 * 1024;
+  CK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  hipEvent_t e0, e1;
+  CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+  hipLaunchKernelGGL(kern, dim3(nblk), dim3(nthr), lds, 0, out, ticks, 1.0f);   // warm-up
+  CK(hipDeviceSynchronize());
+  CK(hipEventRecord(e0));
+  hipLaunchKernelGGL(kern, dim3(nblk), dim3(nthr), lds, 0, out, ticks, 1.0f);
+  CK(hipEventRecord(e1));
+  CK(hipDeviceSynchronize());
+  float ms = 0;
+  CK(hipEventElapsedTime(&ms, e0, e1));
+  std::vector<long long> h((size_t)nblk * nthr / 64);
+  CK(hipMemcpy(h.data(), ticks, h.size() * 8, hipMemcpyDeviceToHost));
+  double sum = 0; long long mx = 0;
+  for (long long v : h) { sum += (double)v; if (v > mx) mx = v; }
+  const double n = (double)ITER * UNR;
+  printf("%-14s W=%d  ticks/wave avg %.0f max %lld  -> ticks per instruction per SIMD %.3f   kernel %.3f ms -> ns per instruction per SIMD %.3f\n",
+         name, W, sum / h.size(), mx, sum / h.size() / (n * W), ms, ms * 1e6 / (n * W));
+}
+
+int main() {
+  float *out; long long *ticks;
+  CK(hipMalloc(&out, 256 * 8 * 256 * 4)); CK(hipMalloc(&ticks, 256 * 8 * 4 * 8));
+  int clk = 0;
+  CK(hipDeviceGetAttribute(&clk, hipDeviceAttributeClockRate, 0));
+  printf("clock rate attribute %d kHz; readcyclecounter = s_memtime\n", clk);
+  for (int W : {1, 2, 4, 6, 8}) {
+    run("v_fma_f32", k<0>, W, out, ticks);
+    run("v_add_f32", k<1>, W, out, ticks);
+    run("v_add_f32_dpp", k<2>, W, out, ticks);
+    run("v_lshl_add_u32", k<3>, W, out, ticks);
+    run("v_and_b32", k<4>, W, out, ticks);
+    run("v_bfe_u32", k<5>, W, out, ticks);
+    run("v_pk_add_f32", kpk<0>, W, out, ticks);
+  }
+  return 0;
+}
