@@ -342,8 +342,15 @@ __global__ __launch_bounds__(64 * SIM_WAVES) void ssm_features_kernel(
     for (int f = lane; f < ASL_SSM_NFEAT; f += 64) o[f] = NAN;
     return;
   }
+  // counts (wave-uniform): clipped to the row's stride; negative = invalid; the matched lists
+  // hold MAXP entries, a longer pair list goes the way of a longer spectrum
   int npm = pm_count[q];
   if (npm > pm_stride) npm = pm_stride;
+  if (npm < 0 || npm > MAXP) {
+    if (lane == 0) atomicOr(status, npm < 0 ? 2 : 1);
+    for (int f = lane; f < ASL_SSM_NFEAT; f += 64) o[f] = NAN;
+    return;
+  }
   const uint32_t *pm = pm_pairs + (size_t)q * pm_stride * 2;
   for (int i = lane; i < MAXP; i += 64) {
     S.used_q[i] = 0;
@@ -409,6 +416,13 @@ __global__ __launch_bounds__(64 * SIM_WAVES) void ssm_features_kernel(
     return !S.used_l[i] && S.in_top[i];
   });
   if (n == 0) n_ul = n_tul = 0;
+  // a matching uses a library peak once, so n + n_ul = nl; a pair list that repeats peaks can
+  // exceed the MAXP entries of y / rx / ry (and, with n_uq <= nq, the 2 MAXP of x): capacity
+  if (n + n_ul > MAXP) {
+    if (lane == 0) atomicOr(status, 1);
+    for (int f = lane; f < ASL_SSM_NFEAT; f += 64) o[f] = NAN;
+    return;
+  }
   sim_sync();
   const SimView full{n, n_ul, S.mq, S.ml, S.mzq, S.mzl, S.ul};
   const SimView tv{nt, n_tul, S.tq, S.tl, S.tzq, S.tzl, S.tul};
@@ -566,7 +580,7 @@ __global__ __launch_bounds__(256) void ssm_cosine_kernel(
   if (n > pm_stride) n = pm_stride;
   const uint32_t *pm = pm_pairs + (size_t)q * pm_stride * 2;
   double d = 0.0;
-  bool bad = false;
+  bool bad = n < 0;   // a negative count is invalid here as in the feature kernel
   for (int i = lane; i < n; i += 64) {
     const uint32_t a = pm[2 * i], b = pm[2 * i + 1];
     if (a >= (uint32_t)nq || b >= (uint32_t)nl) {
@@ -623,7 +637,8 @@ extern "C" int asl_ssm_cosine_batch(const asl_peaks_t *queries, const asl_peaks_
   HIP_TRY(hipMemcpyAsync(&st, status.p, sizeof(int), hipMemcpyDeviceToHost, stream()));
   ASL_TRY(o.finish());
   ASL_TRY(sync_stream());
-  if (st & 2) return fail(ASL_ERR_INVALID, "ssm_cosine: a peak match index is out of range");
+  if (st & 2)
+    return fail(ASL_ERR_INVALID, "ssm_cosine: a peak match count is negative or an index is out of range");
   return ASL_OK;
 }
 
@@ -679,7 +694,11 @@ extern "C" int asl_ssm_features_batch(const asl_peaks_t *queries, const asl_peak
   }
   ASL_TRY(o.finish());
   ASL_TRY(sync_stream());
-  if (st & 1) return fail(ASL_ERR_CAPACITY, "ssm_features: a spectrum has more than %d peaks", SIM_MAXP);
-  if (st & 2) return fail(ASL_ERR_INVALID, "ssm_features: a peak match index is out of range");
+  if (st & 1)
+    return fail(ASL_ERR_CAPACITY,
+                "ssm_features: a spectrum has more than %d peaks, or a peak match list more than %d "
+                "pairs (or, repeating peaks, pairs plus unmatched library peaks)", SIM_MAXP, SIM_MAXP);
+  if (st & 2)
+    return fail(ASL_ERR_INVALID, "ssm_features: a peak match count is negative or an index is out of range");
   return ASL_OK;
 }

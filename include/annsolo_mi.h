@@ -547,7 +547,16 @@ int asl_process_batch(const asl_peaks_t *raw, const asl_process_params_t *params
  *   21 scribe_fragment_acc, 22 scribe_fragment_acc_top, 23 manhattan, 24 euclidean,
  *   25 chebyshev, 26 pearsonr, 27 pearsonr_top, 28 spearmanr, 29 spearmanr_top,
  *   30 braycurtis, 31 canberra, 32 ruzicka.
- * Rows with lib_rows[i] < 0 are NaN (the reference skips SSMs without a match). */
+ * Rows with lib_rows[i] < 0 are NaN (the reference skips SSMs without a match).
+ * pm_count[i], for rows with a library row (the others are not read):
+ *   - above pm_stride it is clipped to pm_stride (the row holds no more pairs);
+ *   - negative: ASL_ERR_INVALID, as for a pair index beyond its spectrum;
+ *   - the capacity is 256 peaks per spectrum and 256 pairs per SSM: more is ASL_ERR_CAPACITY.
+ *     A matching uses every peak at most once, so it never has more pairs than min(nq, nl)
+ *     peaks. A pair list that repeats peaks is evaluated as given (every pair counts, a peak
+ *     is unmatched if no pair names it) while pairs + unmatched library peaks <= 256, beyond
+ *     that it is ASL_ERR_CAPACITY too.
+ * On an error the feature rows of the batch are unspecified. */
 #define ASL_SSM_NFEAT 33
 int asl_ssm_features_batch(const asl_peaks_t *queries, const asl_peaks_t *library,
                            const int32_t *lib_rows /* [nq] */,
@@ -558,7 +567,9 @@ int asl_ssm_features_batch(const asl_peaks_t *queries, const asl_peaks_t *librar
 
 /* features[:, 0] alone -- the cosine over the peak matches (spectrum_similarity.py:81-106), the
  * cascade's default search-engine score (utils.py:407) -- with the same bits as column 0 of
- * asl_ssm_features_batch; rows with lib_rows[i] < 0 are NaN. */
+ * asl_ssm_features_batch; rows with lib_rows[i] < 0 are NaN. pm_count[i] follows the same rule:
+ * clipped to pm_stride, negative = ASL_ERR_INVALID; this entry stages nothing, so it has no
+ * capacity (neither peaks nor pairs). */
 int asl_ssm_cosine_batch(const asl_peaks_t *queries, const asl_peaks_t *library,
                          const int32_t *lib_rows /* [nq] */,
                          const uint32_t *pm_pairs /* [nq, pm_stride, 2] */,

@@ -258,7 +258,9 @@ static double corr_of(const sim_view_t *v, int spearman, double *x, double *y, d
 void orc_ssm_features(const float *q_mz, const float *q_int, int32_t nq, const float *l_mz,
                       const float *l_int, int32_t nl, const uint32_t *pm, int32_t npm,
                       double min_mz, double max_mz, double bin_size, int32_t top, double *out) {
-  const int cap = (nq > nl ? nq : nl) + 8;
+  /* every list fits: a pair list that repeats peaks has npm above min(nq, nl), and its merged
+   * spectrum up to npm + nq + nl entries */
+  const int cap = nq + nl + (npm > 0 ? npm : 0) + 8;
   double *buf = (double *)calloc((size_t)cap * 16, sizeof(double));
   double *mq = buf, *ml = mq + cap, *mzq = ml + cap, *mzl = mzq + cap, *ul = mzl + cap;
   double *uq = ul + cap, *tq = uq + cap, *tl = tq + cap, *tzq = tl + cap, *tzl = tzq + cap;

@@ -20,6 +20,8 @@ oracle/_ref (compiled from the sources where they lie).
   ssm_features_golden.npz   the 33 similarity features of utils._compute_ssm_features
                        (src/ann_solo/utils.py:276-457) evaluated by the reference's
                        SpectrumSimilarityCalculator (scipy of this container) on seeded SSMs
+  ssm_features_edges.npz    the same calculator on SSMs built one per branch of the kernel
+                       (`make_golden.py ssm_edges` writes this file alone, byte for byte)
 """
 import importlib.util
 import os
@@ -381,6 +383,228 @@ def gen_ssm_features(spectrum):
     print('ssm_features_golden.npz:', len(cases), 'SSMs x', len(SIM_FEATURES), 'features')
 
 
+def _load_similarity():
+    """The reference's spectrum_similarity module behind the shims (config and spectrum first)."""
+    import scipy.stats
+    _install_shims()
+    for name in ('config', 'spectrum', 'spectrum_similarity'):
+        if 'ann_solo.' + name not in sys.modules:
+            _load('ann_solo.' + name, os.path.join(REF, 'ann_solo', name + '.py'))
+    # scipy >= 1.11 renamed the two warning classes the reference names (stand-ins only)
+    for old in ('PearsonRConstantInputWarning', 'SpearmanRConstantInputWarning'):
+        if not hasattr(scipy.stats, old):
+            setattr(scipy.stats, old, scipy.stats.ConstantInputWarning)
+    return sys.modules['ann_solo.spectrum_similarity'], sys.modules['spectrum_utils.spectrum']
+
+
+def _savez_fixed(path, **arrays):
+    """np.savez_compressed with a fixed member timestamp: the same arrays give the same bytes."""
+    import zipfile
+    with zipfile.ZipFile(path, 'w', zipfile.ZIP_DEFLATED) as z:
+        for name, a in arrays.items():
+            info = zipfile.ZipInfo(name + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with z.open(info, 'w') as f:
+                np.lib.format.write_array(f, np.asanyarray(a), allow_pickle=False)
+
+
+# the columns of SIM_FEATURES that have a `top` variant
+SIM_TOP_COLUMNS = [i for i, (_, _, t) in enumerate(SIM_FEATURES) if t]
+SIM_EDGE_TOPS = [1, 3, 12]
+
+
+def gen_ssm_features_edges():
+    """ssm_features_edges.npz: the reference's SpectrumSimilarityCalculator on a few dozen SSMs
+    built to reach one branch each of the kernel and of Kendall's p-value (more than 64 and more
+    than 128 matched peaks, the exact/asymptotic switch at n = 33 / 34 and min(dis, tot - dis)
+    = 1 / 2, the closed forms, tie groups, zero intensities, ...). Every case is evaluated; the
+    most intense library peaks are distinct by construction (asserted), so argpartition's
+    choice is defined. Layout of ssm_features_golden.npz plus `names`, and `features_top`
+    [case, len(tops), len(top_columns)] = the `*_top` columns at top = 1, 3, 12 (NaN rows where
+    the library has fewer than 13 peaks)."""
+    import warnings
+    sim, sus = _load_similarity()
+    rng = np.random.default_rng(20250214)
+    unit = lambda v: (lambda w: w / np.linalg.norm(w))(np.asarray(v, np.float32))
+
+    def perm_with_inversions(n, k):
+        """A permutation of range(n) with exactly k inversions."""
+        p = rng.permutation(n)
+        inv = sum(int(p[i] > p[j]) for i in range(n) for j in range(i + 1, n))
+        while inv != k:
+            want_desc = inv > k
+            idx = [i for i in range(n - 1) if (p[i] > p[i + 1]) == want_desc]
+            i = idx[int(rng.integers(len(idx)))]
+            p[i], p[i + 1] = p[i + 1], p[i]
+            inv += -1 if want_desc else 1
+        return p
+
+    def discordant(x, y):
+        return sum(int(x[i] != x[j] and y[i] != y[j] and ((x[i] < x[j]) != (y[i] < y[j])))
+                   for i in range(len(x)) for j in range(i + 1, len(x)))
+
+    cases, names = [], []
+
+    def add(name, nq, nl, n, dis=None, ties=False, const_q=False, zeros=False, zero_tie=False,
+            shuffle_pairs=False):
+        """n matched pairs among nq / nl peaks. Intensities are ranks (query: value + 2,
+        library: value + 2.5), unit-normalised; `dis` = number of discordant matched pairs
+        (None: random). The low values of the matched library peaks lie outside its top 13."""
+        assert n <= min(nq, nl) and nl >= 6
+        qmz = np.sort(rng.uniform(100, 1900, nq)).astype(np.float32)
+        a = np.sort(rng.choice(nq, n, replace=False))
+        b = np.sort(rng.choice(nl, n, replace=False))
+        lmz = np.sort(rng.uniform(100, 1900, nl)).astype(np.float32)
+        lmz[b] = qmz[a] + rng.normal(0, 0.005, n).astype(np.float32)
+        order = np.argsort(lmz, kind='stable')
+        inv = np.empty(nl, np.int64)
+        inv[order] = np.arange(nl)
+        lmz, b = lmz[order], inv[b]
+        if shuffle_pairs:       # as shifted matches are: the library peaks not in m/z order
+            b = rng.permutation(b)
+            assert (np.diff(b) > 0).any() and (np.diff(b) < 0).any(), name
+        assert (np.diff(qmz) > 0).all() and (np.diff(lmz) > 0).all(), name
+        # rank values of the matched peaks: U (query) and V (library), ascending
+        U = np.sort(rng.choice(np.arange(1, nq + 1), n, replace=False))
+        low = min(6, n) if nl - 13 >= 6 else 0      # the tie groups go on V's lowest six
+        V = rng.choice(np.arange(1, nl - 13 + 1), low, replace=False) if low else np.zeros(0, np.int64)
+        rest = np.setdiff1d(np.arange(1, nl + 1), V)
+        V = np.sort(np.concatenate([V, rng.choice(rest, n - low, replace=False)])).astype(np.int64)
+        py = rng.permutation(n) if dis is None else perm_with_inversions(n, dis)
+        s = rng.permutation(n)                        # match order is not intensity order
+        x = U[s].astype(np.float64)
+        y = V[py[s]].astype(np.float64)
+        qi = np.empty(nq)
+        li = np.empty(nl)
+        qi[np.setdiff1d(np.arange(nq), a)] = rng.permutation(np.setdiff1d(np.arange(1, nq + 1), U))
+        li[np.setdiff1d(np.arange(nl), b)] = rng.permutation(np.setdiff1d(np.arange(1, nl + 1), V))
+        if ties:
+            # library: two groups of 2 and the pair tied on both sides, on the six lowest
+            # matched library values; query: two groups of 3 among the other positions
+            assert n >= 12 and low == 6
+            oy = np.argsort(y)
+            y[oy[1]], y[oy[3]], y[oy[5]] = y[oy[0]], y[oy[2]], y[oy[4]]
+            x[oy[5]] = x[oy[4]]
+            others = np.setdiff1d(np.arange(n), oy[:6])
+            ox = others[np.argsort(x[others])]
+            x[ox[1]] = x[ox[2]] = x[ox[0]]
+            x[ox[4]] = x[ox[5]] = x[ox[3]]
+        if const_q:
+            x[:] = x[0]
+        qi[a], li[b] = x, y
+        qi, li = qi + 2.0, li + 2.5
+        if zeros:
+            # two matched query peaks, the library peak of the first of them (the lowest
+            # matched library value) and one unmatched query peak
+            k0 = int(np.argmin(y))
+            k1 = (k0 + 1) % n
+            qi[a[k0]] = qi[a[k1]] = 0.0
+            li[b[k0]] = 0.0
+            qi[np.setdiff1d(np.arange(nq), a)[0]] = 0.0
+            if zero_tie:
+                k = [j for j in range(n) if j not in (k0, k1)][:3]
+                qi[a[k[1]]] = qi[a[k[2]]] = qi[a[k[0]]]
+        qi, li = unit(qi), unit(li)
+        if dis is not None:
+            assert discordant(qi[a], li[b]) == dis, name
+        top = np.sort(li)[-min(13, nl):]
+        assert len(np.unique(top)) == len(top) and len(np.unique(np.sort(li)[-6:])) == 6, name
+        if ties:
+            xs, ys = qi[a], li[b]
+            assert sorted(np.unique(xs, return_counts=True)[1])[-3:] == [2, 3, 3], name
+            assert sorted(np.unique(ys, return_counts=True)[1])[-3:] == [2, 2, 2], name
+        cases.append((qmz, qi, lmz, li, np.stack([a, b], 1).astype(np.int64)))
+        names.append(name)
+
+    tot = lambda n: n * (n - 1) // 2
+    add('switch_n33_random', 40, 45, 33)
+    add('switch_n34_random', 40, 45, 34)
+    add('mn_n34_monotone', 40, 45, 34, dis=0)
+    add('mn_n34_one_swap', 40, 45, 34, dis=1)
+    add('mn_n34_two_swaps', 40, 45, 34, dis=2)
+    add('mn_n34_reversed', 40, 45, 34, dis=tot(34))
+    add('mn_n34_reversed_one_swap', 40, 45, 34, dis=tot(34) - 1)
+    add('mn_n33_reversed_one_swap', 40, 45, 33, dis=tot(33) - 1)
+    add('half_n4_dis3', 10, 12, 4, dis=3)
+    add('half_n5_dis5', 10, 12, 5, dis=5)
+    add('recurrence_n33_dis263', 40, 45, 33, dis=263)
+    add('recurrence_n33_dis265', 40, 45, 33, dis=265)
+    add('recurrence_n12_dis30', 20, 25, 12, dis=30)
+    add('recurrence_n12_dis5', 20, 25, 12, dis=5)
+    add('ties_n12', 20, 25, 12, ties=True)
+    add('ties_n20', 30, 40, 20, ties=True)
+    add('ties_n40', 50, 60, 40, ties=True)
+    add('ties_n120', 128, 128, 120, ties=True)
+    add('constant_query_n6', 10, 6, 6, const_q=True)
+    add('n1', 10, 12, 1)
+    add('n2', 10, 12, 2)
+    add('n3', 10, 12, 3)
+    add('stride_64_of_64', 64, 64, 64)
+    add('stride_65_of_65', 65, 65, 65)
+    add('stride_65_of_70', 70, 70, 65)
+    add('stride_100_of_128_120', 128, 120, 100)
+    add('wide_100_of_129_140', 129, 140, 100)
+    add('wide_200_of_256', 256, 256, 200)
+    add('underflow_170_monotone', 200, 200, 170, dis=0)
+    add('underflow_171_monotone', 200, 200, 171, dis=0)
+    add('zeros_n12', 20, 20, 12, zeros=True)
+    add('zeros_n12_tie', 20, 20, 12, zeros=True, zero_tie=True)
+    add('all_matched_n20', 20, 20, 20)
+    add('permuted_pairs_n15', 30, 30, 15, shuffle_pairs=True)
+
+    class S:
+        pass
+    feats = np.full((len(cases), len(SIM_FEATURES)), np.nan)
+    feats_top = np.full((len(cases), len(SIM_EDGE_TOPS), len(SIM_TOP_COLUMNS)), np.nan)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        for ci, (qmz, qi, lmz, li, pm) in enumerate(cases):   # a case that raises ends the run
+            ssm = S()
+            ssm.query_spectrum = sus.MsmsSpectrum('q', 500.0, 2, qmz, qi)
+            ssm.library_spectrum = sus.MsmsSpectrum('l', 500.0, 2, lmz, li)
+            assert np.array_equal(ssm.library_spectrum.intensity, li)
+            ssm.peak_matches = pm
+            calc = {None: sim.SpectrumSimilarityCalculator(ssm),
+                    5: sim.SpectrumSimilarityCalculator(ssm, 5)}
+            for fi, (method, args, top) in enumerate(SIM_FEATURES):
+                if args == 'HG':
+                    v = calc[top].hypergeometric_score(min_mz=11, max_mz=2010, fragment_mz_tol=0.04)
+                else:
+                    v = getattr(calc[top], method)(*args)
+                feats[ci, fi] = float(v)
+            # top = 12 needs 13 distinct library peaks; shorter libraries keep their NaN rows
+            for ti, t in enumerate(SIM_EDGE_TOPS if len(li) >= 13 else []):
+                c = sim.SpectrumSimilarityCalculator(ssm, t)
+                for k, fi in enumerate(SIM_TOP_COLUMNS):
+                    # top = 1 with the top peak matched: the correlations get one point and
+                    # scipy's pearsonr / spearmanr raise ValueError for every such SSM, so the
+                    # reference defines no value (NaN here; the kernel and the oracle give 0)
+                    if t == 1 and c.matched_int_query is not None and \
+                            SIM_FEATURES[fi][0] in ('pearsonr', 'spearmanr'):
+                        assert len(c.matched_int_query) == 1 and len(c.unmatched_int_library) == 0
+                        continue
+                    feats_top[ci, ti, k] = float(getattr(c, SIM_FEATURES[fi][0])(*SIM_FEATURES[fi][1]))
+    assert not np.isnan(feats).any()
+    monotone = [bool((np.diff(c[4][:, 1]) > 0).all()) for c in cases]
+    assert [nm for nm, m in zip(names, monotone) if not m] == ['permuted_pairs_n15']
+    off = lambda xs: np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int64)
+    _savez_fixed(
+        os.path.join(HERE, 'ssm_features_edges.npz'),
+        q_offsets=off([c[0] for c in cases]), q_mz=np.concatenate([c[0] for c in cases]),
+        q_intensity=np.concatenate([c[1] for c in cases]),
+        l_offsets=off([c[2] for c in cases]), l_mz=np.concatenate([c[2] for c in cases]),
+        l_intensity=np.concatenate([c[3] for c in cases]),
+        pm_offsets=off([c[4] for c in cases]),
+        pm_pairs=np.concatenate([c[4].reshape(-1, 2) for c in cases]).astype(np.uint32),
+        features=feats, names=np.array(names), tops=np.array(SIM_EDGE_TOPS, np.int32),
+        top_columns=np.array(SIM_TOP_COLUMNS, np.int32), features_top=feats_top,
+        feature_names=np.array([m + ('_' + '_'.join(map(str, a)) if a and a != 'HG' else '') +
+                                ('_top5' if t else '') for m, a, t in SIM_FEATURES]))
+    print('ssm_features_edges.npz:', len(cases), 'SSMs x', len(SIM_FEATURES), 'features,',
+          int((~np.isnan(feats_top[:, 0, 0])).sum()), 'with top =', SIM_EDGE_TOPS)
+
+
 def gen_mztab(spectrum):
     """The reference's write_mztab (src/ann_solo/writer.py) on a fixed set of SSMs -> golden
     text + the inputs as JSON. reader.SpectralLibraryReader only types an argument there; a
@@ -642,10 +866,14 @@ if __name__ == '__main__':
         _load('ann_solo.spectrum_similarity', os.path.join(REF, 'ann_solo/spectrum_similarity.py'))
         gen_fdr()
         sys.exit(0)
+    if sys.argv[1:] == ['ssm_edges']:   # only ssm_features_edges.npz
+        gen_ssm_features_edges()
+        sys.exit(0)
     sp = gen_encoder()
     gen_similarity_kat(sp)
     gen_similarity_expected()
     gen_ssm_features(sp)
+    gen_ssm_features_edges()
     gen_mztab(sp)
     gen_rescoring()
     gen_fdr()
