@@ -42,7 +42,9 @@ class AslSearchParams(C.Structure):
                 ('hash_seed', C.c_uint32), ('k', C.c_int32), ('nprobe', C.c_int32),
                 ('charge', C.c_int32), ('precursor_tol', C.c_double),
                 ('precursor_mode', C.c_int32), ('fragment_mz_tolerance', C.c_double),
-                ('allow_shift', C.c_int32), ('use_ann', C.c_int32)]
+                ('allow_shift', C.c_int32), ('use_ann', C.c_int32),
+                # [nq, 2] float64 (lo, hi), host or device: read with precursor_mode 2 (ASL_TOL_INTERVAL) only
+                ('precursor_window', C.c_void_p)]
 
 
 class AslProcessParams(C.Structure):

@@ -3,7 +3,8 @@
 ``Config`` carries the reference's flags under the reference's names
 (/root/reference/src/ann_solo/config.py:62-216) plus the ADDITIVE flags of this implementation
 (``index``, ``pq_m``, ``pq_bits``, ``refine_k``, ``kmeans_niter``, ``ann_seed``, ``num_gpus``,
-``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``, ``pq_by_residual``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``, ``pq_by_residual``,
+``precursor_window_open``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -24,7 +25,7 @@ options with ``KeyError`` (config.py:285-291), not ``AttributeError`` -- so the 
 constructed exactly as ``ann_solo.py:78-79`` does. ``add_arguments(parser)`` is the additive
 patch for the reference's ``Config.__init__``."""
 from dataclasses import dataclass, fields
-from typing import Optional
+from typing import Optional, Tuple
 
 _MISSING = object()
 
@@ -89,6 +90,10 @@ class Config:
 
     pq_by_residual: bool = True             # IVF-PQ, FAISS' IndexIVFPQ.by_residual: True codes the residuals
                                             # x - centroid[list]; False (opt-in) the hashed vectors themselves
+    # open cascade level: the signed range (lo_da, hi_da) of the neutral mass difference (query - library) *
+    # charge a candidate may have, e.g. (-150, 500), instead of the symmetric +-precursor_tolerance_mass_open
+    # (flags --precursor_window_open_low / _high). None: the reference's symmetric window
+    precursor_window_open: Optional[Tuple[float, float]] = None
 
     MAX_PEAKS = 256      # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
@@ -126,6 +131,19 @@ class Config:
             raise ValueError('num_matches > 1 does not run on a sharded index (num_gpus > 1)')
         if self.distinct_matches and self.num_gpus and int(self.num_gpus) > 1:
             raise ValueError('distinct_matches does not run on a sharded index (num_gpus > 1)')
+        if self.precursor_window_open is not None:
+            try:
+                lo, hi = (float(v) for v in self.precursor_window_open)
+            except (TypeError, ValueError):
+                raise ValueError(f'precursor_window_open = {self.precursor_window_open!r}: a pair (lo_da, hi_da)')
+            if not lo <= hi:        # (a NaN bound fails too)
+                raise ValueError(f'precursor_window_open = ({lo}, {hi}): needs lo_da <= hi_da')
+            if self.precursor_tolerance_mass_open is None:
+                raise ValueError('precursor_window_open shapes the open cascade level: it needs '
+                                 'precursor_tolerance_mass_open (the switch of that level)')
+            if self.num_gpus and int(self.num_gpus) > 1:
+                raise ValueError('precursor_window_open does not run on a sharded index (num_gpus > 1)')
+            self.precursor_window_open = (lo, hi)
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -158,6 +176,13 @@ class Config:
                 v = _lookup(obj, 'seed')
             if v is not _MISSING:
                 kw[f.name] = v
+        if 'precursor_window_open' not in kw:      # the two flags of add_arguments: both or neither
+            lo, hi = (_lookup(obj, 'precursor_window_open_' + side) for side in ('low', 'high'))
+            lo, hi = (None if v is _MISSING else v for v in (lo, hi))
+            if (lo is None) != (hi is None):
+                raise ValueError('--precursor_window_open_low and --precursor_window_open_high go together')
+            if lo is not None:
+                kw['precursor_window_open'] = (lo, hi)
         kw.update(overrides)
         if kw.get('index') is None:
             kw.pop('index', None)
@@ -223,6 +248,14 @@ def add_arguments(parser) -> None:
                              'SSM also carries its runners-up and the score gap to the second best; '
                              'identifications, scores and FDR are those of the best match; one GPU '
                              '(default: %(default)s)')
+    parser.add_argument('--precursor_window_open_low', default=None, type=float,
+                        help='open search: lowest neutral mass difference (query - library, Da; may be '
+                             'negative) a candidate may have, instead of -precursor_tolerance_mass_open; '
+                             'needs --precursor_window_open_high; one GPU (default: the symmetric window)')
+    parser.add_argument('--precursor_window_open_high', default=None, type=float,
+                        help='open search: highest neutral mass difference (query - library, Da) a '
+                             'candidate may have; needs --precursor_window_open_low; one GPU '
+                             '(default: the symmetric window)')
     parser.add_argument('--distinct_matches', action='store_true', default=d.distinct_matches,
                         help='with --num_matches above 1: one rank per library peptide -- the '
                              "runners-up are the best matches of other peptides and the score gap is "

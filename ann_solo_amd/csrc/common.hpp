@@ -211,6 +211,25 @@ __device__ __forceinline__ bool precursor_ok(double q, float lib, int charge, do
   if (mode == ASL_TOL_DA) return fabs(q - l) * (double)charge <= tol;
   return fabs(q - l) / l * 1000000.0 <= tol;
 }
+// What a query brings to the window test: its precursor m/z (Da, ppm: q; hi unread) or, with
+// ASL_TOL_INTERVAL, its own closed interval [q, hi] on the window column (annsolo_mi.h). The queries'
+// array is [nq] doubles in the first two modes and [nq, 2] (lo, hi interleaved) in the third.
+struct QueryWindow {
+  double q, hi;
+};
+__device__ __forceinline__ QueryWindow query_window(const double *__restrict__ q_pmz, long long i, int mode) {
+  if (mode == ASL_TOL_INTERVAL) return {q_pmz[2 * i], q_pmz[2 * i + 1]};
+  return {q_pmz[i], 0.0};
+}
+// The interval form: lo <= lib <= hi in double. A NaN key or bound never passes, lo > hi is empty,
+// +-inf are legal bounds; charge and tol play no part.
+__device__ __forceinline__ bool precursor_ok(const QueryWindow &w, float lib, int charge, double tol, int mode) {
+  if (mode == ASL_TOL_INTERVAL) {
+    const double l = (double)lib;
+    return w.q <= l && l <= w.hi;
+  }
+  return precursor_ok(w.q, lib, charge, tol, mode);
+}
 
 // The precursor-window post-filter (spectral_library.py:441-446: AFTER the top-k) applied where the
 // top-k ends: a scan's set-mode finish that is given one writes only the hits that pass, compacted at
@@ -231,7 +250,7 @@ struct ScanRanges {
 
 struct ScanPostFilter {
   const int2 *idpay = nullptr;      // nullptr: no filter (every other field unused)
-  const double *q_pmz = nullptr;    // per query
+  const double *q_pmz = nullptr;    // per query ([nq, 2] with ASL_TOL_INTERVAL: QueryWindow)
   int32_t *count = nullptr;         // per query, out
   double tol = 0.0;
   int mode = ASL_TOL_DA;
@@ -241,8 +260,8 @@ struct ScanPostFilter {
 // What search.hip hands an index for its NEXT search (index_set_post_filter): the library's window
 // column by vector id (device, float32, NaN = never a candidate; the index keeps (id, value) pairs
 // per storage slot, rebuilt when the column or the lists change), the queries' precursor m/z and the
-// window; count[nq] receives the rows' lengths. index_post_filter_applied() says whether the scan
-// that ran could take it (set-mode int32 rows of the layout-specific scans, k <= 1280); if not, the
+// window (q_pmz: [nq, 2] intervals with ASL_TOL_INTERVAL); count[nq] receives the rows' lengths.
+// index_post_filter_applied() says whether the scan that ran could take it (set-mode int32 rows of the layout-specific scans, k <= 1280); if not, the
 // rows are the k unfiltered hits as ever.
 struct IndexPostFilter {
   const float *payload = nullptr;
@@ -255,7 +274,8 @@ struct IndexPostFilter {
 };
 
 // What an index in window-scan mode needs for its NEXT search (index_set_window): the queries'
-// precursor m/z (device), the window, and (set mode) where the rows' lengths go.
+// precursor m/z (device; [nq, 2] intervals with ASL_TOL_INTERVAL), the window, and (set mode) where the
+// rows' lengths go.
 struct IndexWindow {
   const double *q_pmz = nullptr;
   int32_t *row_len = nullptr;

@@ -350,10 +350,10 @@ struct HistTopK {
       if (filt && tid == 0) pf->count[q] = -1;       // the k unfiltered hits: the rescoring filters this row
       return -1;
     }
-    double f_q = 0.0;
+    QueryWindow f_q = {0.0, 0.0};
     uint8_t *sflag = reinterpret_cast<uint8_t *>(scratch + CAP);
     if (filt) {
-      f_q = pf->q_pmz[q];
+      f_q = query_window(pf->q_pmz, q, pf->mode);
       if (tid == 0) ctl[C_USER] = 0;                 // (update_bstar's barriers order it before the first append)
     }
     // the last compaction, fused: keys below the threshold bucket are dropped in registers (no

@@ -58,7 +58,7 @@ static int index_rank_device(asl_index *ix, int nq, const float *xq, const int64
     const float *x = xq + (size_t)r0 * d;
     const float *cD = !nprobe ? nullptr : zeros ? zeros : ix->coarse_D.p + (size_t)r0 * nprobe;
     const int32_t *cI = nprobe ? ix->coarse_I.p + (size_t)r0 * nprobe : nullptr;
-    win.q_pmz = key ? q_pmz + r0 : nullptr;
+    win.q_pmz = key ? q_pmz + (size_t)r0 * (mode == ASL_TOL_INTERVAL ? 2 : 1) : nullptr;
     if (pq) {
       if (nprobe == 0 && !zeros) ASL_TRY(coarse_scores_all(ix, x, m, coarse_all.p));
       ASL_TRY(rank_pq(x, m, d, ix->codebooks_t.p, ix->dsub, nlist, ix->ntotal, cD, cI, nprobe,
@@ -91,7 +91,8 @@ int asl_index_rank(asl_index_t *ix, int32_t nq, const float *xq, const int64_t *
   if (!xq || !target || !rank) return fail(ASL_ERR_INVALID, "rank: null xq / target / rank");
   if (nprobe < 0) return fail(ASL_ERR_INVALID, "rank: nprobe must be 0 (every list) or positive");
   if (key && !q_pmz) return fail(ASL_ERR_INVALID, "rank: a window key needs the queries' precursor m/z");
-  if (key && mode != ASL_TOL_DA && mode != ASL_TOL_PPM) return fail(ASL_ERR_INVALID, "rank: mode must be Da or ppm");
+  if (key && mode != ASL_TOL_DA && mode != ASL_TOL_PPM && mode != ASL_TOL_INTERVAL)
+    return fail(ASL_ERR_INVALID, "rank: mode must be Da, ppm or interval");
   if (const char *why = rank_unsupported(ix)) return fail(ASL_ERR_STATE, "%s", why);
   if (!ix->trained) return fail(ASL_ERR_STATE, "rank: index is not trained");
   ASL_TRY(build_lists(ix));
@@ -116,7 +117,7 @@ int asl_index_rank(asl_index_t *ix, int32_t nq, const float *xq, const int64_t *
   ASL_TRY(dt.init(target, (size_t)nq));
   if (key) {
     ASL_TRY(dkey.init(key, (size_t)ix->ntotal));
-    ASL_TRY(dp.init(q_pmz, (size_t)nq));
+    ASL_TRY(dp.init(q_pmz, (size_t)nq * (mode == ASL_TOL_INTERVAL ? 2 : 1)));
   }
   ASL_TRY(drank.init(rank, (size_t)nq));
   ASL_TRY(dscore.init(score, (size_t)nq));

@@ -609,7 +609,8 @@ int asl_index_search_window(asl_index_t *ix, int32_t nq, const float *xq, const 
   if (!ix) return fail(ASL_ERR_INVALID, "search_window: null index");
   if (nq <= 0) return ASL_OK;
   if (!xq || !q_pmz || !I) return fail(ASL_ERR_INVALID, "search_window: null xq / q_pmz / I");
-  if (mode != ASL_TOL_DA && mode != ASL_TOL_PPM) return fail(ASL_ERR_INVALID, "search_window: mode must be Da or ppm");
+  if (mode != ASL_TOL_DA && mode != ASL_TOL_PPM && mode != ASL_TOL_INTERVAL)
+    return fail(ASL_ERR_INVALID, "search_window: mode must be Da, ppm or interval");
   if (const char *why = window_unsupported(ix)) return fail(ASL_ERR_STATE, "%s", why);
   if (!ix->trained) return fail(ASL_ERR_STATE, "search: index is not trained");
   ASL_TRY(build_lists(ix));
@@ -618,7 +619,7 @@ int asl_index_search_window(asl_index_t *ix, int32_t nq, const float *xq, const 
   In<float> dq;
   In<double> dp;
   ASL_TRY(dq.init(xq, (size_t)nq * ix->d));
-  ASL_TRY(dp.init(q_pmz, (size_t)nq));
+  ASL_TRY(dp.init(q_pmz, (size_t)nq * (mode == ASL_TOL_INTERVAL ? 2 : 1)));
   return with_staged_rows(D, I, (size_t)nq * k, dq.own.p || dp.own.p, [&](float *dD, int64_t *dI) {
     IndexWindow w{.q_pmz = dp.d, .tol = tol, .mode = mode, .charge = charge};
     IndexSearch rq{.nq = nq, .xq = dq.d, .k = k, .nprobe = nprobe, .D = dD, .I64 = dI, .win = &w};
@@ -653,8 +654,8 @@ int asl_index_search_selected(asl_index_t *ix, int32_t nq, const float *xq, cons
   if (!ix) return fail(ASL_ERR_INVALID, "search_selected: null index");
   if (nq <= 0) return ASL_OK;
   if (!xq || !I) return fail(ASL_ERR_INVALID, "search_selected: null xq / I");
-  if (q_pmz && mode != ASL_TOL_DA && mode != ASL_TOL_PPM)
-    return fail(ASL_ERR_INVALID, "search_selected: mode must be Da or ppm");
+  if (q_pmz && mode != ASL_TOL_DA && mode != ASL_TOL_PPM && mode != ASL_TOL_INTERVAL)
+    return fail(ASL_ERR_INVALID, "search_selected: mode must be Da, ppm or interval");
   if (ix->kind == ASL_INDEX_FLAT) return fail(ASL_ERR_STATE, "a selector needs an IVF index (not a Flat index)");
   if (!ix->trained) return fail(ASL_ERR_STATE, "search: index is not trained");
   ASL_TRY(build_lists(ix));
@@ -669,7 +670,7 @@ int asl_index_search_selected(asl_index_t *ix, int32_t nq, const float *xq, cons
   In<float> dq;
   In<double> dp;
   ASL_TRY(dq.init(xq, (size_t)nq * ix->d));
-  if (q_pmz) ASL_TRY(dp.init(q_pmz, (size_t)nq));
+  if (q_pmz) ASL_TRY(dp.init(q_pmz, (size_t)nq * (mode == ASL_TOL_INTERVAL ? 2 : 1)));
   return with_staged_rows(D, I, (size_t)nq * k, dq.own.p || dp.own.p, [&](float *dD, int64_t *dI) {
     IndexWindow w{.q_pmz = dp.d, .tol = tol, .mode = mode, .charge = charge};
     IndexSearch rq{.nq = nq, .xq = dq.d, .k = k, .nprobe = nprobe, .D = dD, .I64 = dI, .serial = 0,

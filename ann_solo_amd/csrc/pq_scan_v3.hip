@@ -517,6 +517,8 @@ int pq_scan_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
 // same terms are non-decreasing (l - q is exact up to l = 2q, Sterbenz; beyond that a float32 step
 // of l is still far above the double rounding of l - q). Correctly rounded operations are monotone,
 // so on either side the predicate changes value once. NaN keys (sorted last) never pass.
+// ASL_TOL_INTERVAL (q_pmz: [nq, 2]): the same walk is lower_bound(lo) and upper_bound(hi) -- the first
+// search ends at the first key >= lo, the right-hand one at the first key from there that is not <= hi.
 // acc (optional): += sum of hi - lo (asl_profile_scanned_vectors).
 __global__ void window_ranges_kernel(const double *__restrict__ q_pmz, int nq,
                                      const int32_t *__restrict__ coarse_I, int nprobe,
@@ -532,23 +534,25 @@ __global__ void window_ranges_kernel(const double *__restrict__ q_pmz, int nq,
     if (l >= 0) {
       const float *key = wkey + (size_t)tile_offsets[l] * 64;
       const int n = list_offsets[l + 1] - list_offsets[l];
-      const double qm = q_pmz[i / nprobe];
+      const QueryWindow w = query_window(q_pmz, i / nprobe, mode);
+      const double qm = w.q;
       int a = 0, b = n;   // p0 = first key with (double)key >= qm (NaN: not below)
       while (a < b) {
         const int mid = (a + b) >> 1;
         if ((double)key[mid] < qm) a = mid + 1; else b = mid;
       }
       const int p0 = a;
-      a = 0, b = p0;      // left side: first key that passes
+      // (interval: p0 is lower_bound(lo) and nothing left of it passes; a NaN bound or lo > hi: no run)
+      a = mode == ASL_TOL_INTERVAL ? p0 : 0, b = p0;      // left side: first key that passes
       while (a < b) {
         const int mid = (a + b) >> 1;
         if (precursor_ok(qm, key[mid], charge, tol, mode)) b = mid; else a = mid + 1;
       }
       const int lo = a;
-      a = p0, b = n;      // right side: first key that fails
+      a = p0, b = (mode == ASL_TOL_INTERVAL && !(w.q <= w.hi)) ? p0 : n;      // right side: first key that fails
       while (a < b) {
         const int mid = (a + b) >> 1;
-        if (precursor_ok(qm, key[mid], charge, tol, mode)) a = mid + 1; else b = mid;
+        if (precursor_ok(w, key[mid], charge, tol, mode)) a = mid + 1; else b = mid;
       }
       r = make_int2(lo, a);
       cnt = (unsigned long long)(a - lo);

@@ -179,7 +179,7 @@ __global__ __launch_bounds__(64 * NW) void rank_flat_kernel(
   __syncthreads();
   const int K = (int)s_cnt[2];
   float *acc = s_acc + wave * FI_BLK;
-  const double qm = win.key_slot ? win.q_pmz[q] : 0.0;
+  const QueryWindow qm = win.key_slot ? query_window(win.q_pmz, q, win.mode) : QueryWindow{0.0, 0.0};
   if constexpr (TARGET) {
     // the target: its position in list order, its list, whether that list is probed and its key in the window
     const int64_t t = target[q];
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(64 * RK_PQ_NW) void rank_pq_kernel(
   const int ma = (rho & 1) ? j + 16 : j, mb = ma ^ 16;
   const uint32_t offA = (uint32_t)ma * 4u, offB = (uint32_t)mb * 4u;
   const uint32_t chunkA = (uint32_t)(rho * 512 + ma * 16), chunkB = chunkA ^ 256u;
-  const double qm = win.key_slot ? win.q_pmz[q] : 0.0;
+  const QueryWindow qm = win.key_slot ? query_window(win.q_pmz, q, win.mode) : QueryWindow{0.0, 0.0};
   auto tile_scores = [&](int tile, float coarse) -> float {        // lane l: the score of the tile's vector l
     const uint8_t *base = codes_tiled + (size_t)tile * 2048;
     const uint4 A = *reinterpret_cast<const uint4 *>(base + chunkA);

@@ -25,7 +25,13 @@ struct __attribute__((aligned(32))) RowMeta {
 struct PrecFilter {
   const float *lib_pmz = nullptr;   // spec_info's float32 precursor m/z column
   const uint8_t *valid = nullptr;   // is_valid flags (nullptr: all valid)
-  double tol = 0.0;
+  // Da / ppm: the tolerance. ASL_TOL_INTERVAL, which reads no tolerance: the queries' intervals on the
+  // window column, [nq, 2] (lo, hi) -- the window test reads these, never the query's precursor m/z
+  // (which the shifted dot product still uses). One slot, so the kernels' arguments keep their size.
+  union {
+    double tol = 0.0;
+    const double *interval;
+  };
   int mode = ASL_TOL_DA;
   int charge = 0;
   const RowMeta *meta = nullptr;    // packed rows (asl_library): replaces lib_pmz / valid
@@ -47,13 +53,19 @@ __device__ __forceinline__ const RowMeta *meta_row(const PrecFilter &f, long lon
 
 // precursor_ok (spectral_library.py:421-427): common.hpp -- the scans' finish applies it too
 
-__device__ __forceinline__ bool filter_pass(const PrecFilter &f, double q_pmz, long long row) {
+// the window test of query q on a row's window value
+__device__ __forceinline__ bool window_pass(const PrecFilter &f, int q, double q_pmz, float key) {
+  if (f.mode == ASL_TOL_INTERVAL) return precursor_ok(query_window(f.interval, q, f.mode), key, f.charge, 0.0, f.mode);
+  return precursor_ok(q_pmz, key, f.charge, f.tol, f.mode);
+}
+
+__device__ __forceinline__ bool filter_pass(const PrecFilter &f, int q, double q_pmz, long long row) {
   if (f.pass_all) return true;
-  if (f.wcol) return precursor_ok(q_pmz, f.wcol[row], f.charge, f.tol, f.mode);
-  if (f.meta) return precursor_ok(q_pmz, meta_row(f, row)->pmz32, f.charge, f.tol, f.mode);
+  if (f.wcol) return window_pass(f, q, q_pmz, f.wcol[row]);
+  if (f.meta) return window_pass(f, q, q_pmz, meta_row(f, row)->pmz32);
   if (!f.lib_pmz) return true;
   if (f.valid && !f.valid[row]) return false;
-  return precursor_ok(q_pmz, f.lib_pmz[row], f.charge, f.tol, f.mode);
+  return window_pass(f, q, q_pmz, f.lib_pmz[row]);
 }
 
 // Per-query flags that pass from one rescoring launch to the next (which queries the flat kernel

@@ -33,7 +33,7 @@ struct CandView {
   // row of query q's slot c if it is a candidate of the query (in range, passes the filter), else -1
   __device__ __forceinline__ long long cand(int q, long long c, double q_pmz, int n_lib) const {
     const long long r = row(q, c);
-    return (r >= 0 && r < n_lib && filter_pass(flt, q_pmz, r)) ? r : -1;
+    return (r >= 0 && r < n_lib && filter_pass(flt, q, q_pmz, r)) ? r : -1;
   }
   __device__ __forceinline__ void range(int q, long long &c0, long long &c1) const {
     if (offsets) {

@@ -20,30 +20,33 @@ namespace asl {
 int encode_device(const float *mz, const float *inten, const int32_t *offsets, int32_t n,
                   double min_bound, double bin_size, int32_t hash_len, uint32_t seed,
                   int norm, float *out);
-// Window [lo,hi) of each query inside the precursor-sorted library.
+// Window [lo,hi) of each query inside the precursor-sorted library (q_pmz: [nq, 2] with ASL_TOL_INTERVAL,
+// where the walk is lower_bound(lo), upper_bound(hi)).
 __global__ void window_range_kernel(const double *__restrict__ q_pmz, int nq,
                                     const float *__restrict__ sorted_pmz, int n, int charge,
                                     double tol, int mode, int32_t *__restrict__ lo_out,
                                     int32_t *__restrict__ cnt_out) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= nq) return;
-  const double qm = q_pmz[q];
+  const QueryWindow w = query_window(q_pmz, q, mode);
+  const double qm = w.q;
   int a = 0, b = n;  // p0 = first element with (double)l >= qm
   while (a < b) {
     const int mid = (a + b) >> 1;
     if ((double)sorted_pmz[mid] < qm) a = mid + 1; else b = mid;
   }
   const int p0 = a;
-  a = 0; b = p0;     // left side: first index whose value passes
+  // (interval: p0 is lower_bound(lo) and nothing left of it passes; a NaN bound or lo > hi: no run)
+  a = mode == ASL_TOL_INTERVAL ? p0 : 0; b = p0;     // left side: first index whose value passes
   while (a < b) {
     const int mid = (a + b) >> 1;
     if (precursor_ok(qm, sorted_pmz[mid], charge, tol, mode)) b = mid; else a = mid + 1;
   }
   const int lo = a;
-  a = p0; b = n;     // right side: first index whose value fails
+  a = p0; b = (mode == ASL_TOL_INTERVAL && !(w.q <= w.hi)) ? p0 : n;     // right side: first index whose value fails
   while (a < b) {
     const int mid = (a + b) >> 1;
-    if (precursor_ok(qm, sorted_pmz[mid], charge, tol, mode)) a = mid + 1; else b = mid;
+    if (precursor_ok(w, sorted_pmz[mid], charge, tol, mode)) a = mid + 1; else b = mid;
   }
   lo_out[q] = lo;
   cnt_out[q] = a - lo;
@@ -115,6 +118,7 @@ struct asl_library {
   DevBuf<float> p_qvec[2], p_cD[2];
   DevBuf<int32_t> p_cI[2], p_knn[2], p_cnt[2];
   DevBuf<int32_t> p_rows[2], rows_len;   // lengths of the neighbour rows when the scan applied the precursor filter
+  DevBuf<double> p_win[2];         // ASL_TOL_INTERVAL: the batch's intervals when the caller's array is on the host
   DevBuf<uint2> p_ent[2];          // the batch's entry lists: listed by the coarse stage, read by the scan
   bool p_have_ent[2] = {false, false};
   DevBuf<double> pair_score;
@@ -173,18 +177,28 @@ static int64_t &window_pair_budget() {
   static int64_t b = 1ll << 28;
   return b;
 }
+// What the window test of a batch reads per query: the queries' precursor m/z or, with ASL_TOL_INTERVAL, the
+// intervals of asl_search_params_t::precursor_window on the device (`win`: [nq, 2])
+static const double *window_operand(const DevPeaks &Q, const asl_search_params_t *P, const double *win) {
+  return P->precursor_mode == ASL_TOL_INTERVAL ? win : Q.precursor_mz;
+}
+static int check_window_arg(const asl_search_params_t *P, const char *who) {
+  if (P->precursor_mode == ASL_TOL_INTERVAL && !P->precursor_window)
+    return fail(ASL_ERR_INVALID, "%s: precursor_mode ASL_TOL_INTERVAL needs precursor_window ([nq, 2] doubles)", who);
+  return ASL_OK;
+}
 // The precursor window of a batch's scan, into its request: the window scan (asl_index_set_window_scan)
 // when the index is in that mode, else -- no ordered neighbour list asked for -- the scan-side
 // post-filter of THIS library's window column. row_len: the lengths of the set-mode rows.
 static void offer_window(IndexSearch &rq, IndexWindow &w, const DevPeaks &Q, const asl_search_params_t *P,
-                         int32_t *row_len) {
-  w = {.q_pmz = Q.precursor_mz, .row_len = row_len, .tol = P->precursor_tol, .mode = P->precursor_mode,
+                         const double *win, int32_t *row_len) {
+  w = {.q_pmz = window_operand(Q, P, win), .row_len = row_len, .tol = P->precursor_tol, .mode = P->precursor_mode,
        .charge = P->charge};
   rq.win = &w;
 }
 static void offer_post_filter(IndexSearch &rq, IndexPostFilter &pf, const asl_library *L, const DevPeaks &Q,
-                              const asl_search_params_t *P, int32_t *row_len) {
-  pf = {.payload = L->window_col(), .n = L->n, .q_pmz = Q.precursor_mz, .count = row_len, .tol = P->precursor_tol,
+                              const asl_search_params_t *P, const double *win, int32_t *row_len) {
+  pf = {.payload = L->window_col(), .n = L->n, .q_pmz = window_operand(Q, P, win), .count = row_len, .tol = P->precursor_tol,
         .mode = P->precursor_mode, .charge = P->charge};
   rq.post = &pf;
 }
@@ -205,13 +219,14 @@ static void library_filter(const asl_library *L, PrecFilter &flt) {
   flt.meta_stride = L->slot;
   flt.wcol = L->window_col();
 }
-static void batch_filter(const asl_library *L, const asl_search_params_t *P, PrecFilter &flt) {
+static void batch_filter(const asl_library *L, const asl_search_params_t *P, const double *win, PrecFilter &flt) {
   flt.lib_pmz = L->pmz32.p;
   flt.valid = L->valid_col();
   library_filter(L, flt);
   flt.tol = P->precursor_tol;
   flt.mode = P->precursor_mode;
   flt.charge = P->charge;
+  if (P->precursor_mode == ASL_TOL_INTERVAL) flt.interval = win;     // (shares the tolerance's slot)
 }
 
 extern "C" {
@@ -433,7 +448,7 @@ static int window_candidates_device(asl_library *L, int nq, const double *q_pmz_
 // n_best > 0 (asl_search_batch_topn): outputs [nq, n_best]. n_best = 0 is the single-winner search: the
 // same launches at n = 1 with the argmax as the selection.
 static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_search_params_t *P,
-                                int32_t *best_row, double *best_score, int32_t *n_cand,
+                                const double *intervals, int32_t *best_row, double *best_score, int32_t *n_cand,
                                 int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride, int n_best = 0,
                                 bool distinct = false) {
   const int nq = Q.n;
@@ -448,7 +463,7 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
     ASL_TRY(L->lo.reserve((size_t)nq));
     ASL_TRY(L->cnt.reserve((size_t)nq));
     hipLaunchKernelGGL(window_range_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(),
-                       Q.precursor_mz, nq, L->sorted_pmz.p, (int)L->n, P->charge, P->precursor_tol,
+                       window_operand(Q, P, intervals), nq, L->sorted_pmz.p, (int)L->n, P->charge, P->precursor_tol,
                        P->precursor_mode, L->lo.p, L->cnt.p);
     ASL_CHECK_LAUNCH();
     ASL_TRY(L->lo.download(h_lo.data(), (size_t)nq));
@@ -571,7 +586,7 @@ int asl_window_candidates(asl_library_t *L, int32_t nq, const double *query_pmz,
     return ASL_OK;
   }
   In<double> dq;
-  ASL_TRY(dq.init(query_pmz, (size_t)nq));
+  ASL_TRY(dq.init(query_pmz, (size_t)nq * (mode == ASL_TOL_INTERVAL ? 2 : 1)));
   int64_t total = 0;
   ASL_TRY(window_candidates_device(L, nq, dq.d, charge, tol, mode, &total));
   std::vector<int32_t> h_off((size_t)nq + 1), h_cand((size_t)total);
@@ -608,9 +623,12 @@ static int rescore_knn_sync(asl_library_t *L, const asl_peaks_t *queries, const 
   if (nq == 0) return ASL_OK;
   if (k <= 0) return fail(ASL_ERR_INVALID, "rescore_knn: k must be positive");
   if (pm_pairs && pm_stride <= 0) return fail(ASL_ERR_INVALID, "rescore_knn: pm_stride");
+  ASL_TRY(check_window_arg(P, "rescore_knn"));
   ASL_TRY(ensure_device());
   PeaksStage Q;
   ASL_TRY(Q.init(queries));
+  In<double> dwin;
+  if (P->precursor_mode == ASL_TOL_INTERVAL) ASL_TRY(dwin.init(P->precursor_window, (size_t)nq * 2));
   In<int64_t> knn;
   ASL_TRY(knn.init(knn_I, (size_t)nq * k));
   Out<int32_t> o_row, o_ncand, o_cnt;
@@ -626,7 +644,7 @@ static int rescore_knn_sync(asl_library_t *L, const asl_peaks_t *queries, const 
   ASL_TRY(L->pair_score.reserve((size_t)nq * k));
   // the precursor filter runs inside the rescoring kernel's compaction stage
   PrecFilter flt;
-  batch_filter(L, P, flt);
+  batch_filter(L, P, dwin.d, flt);
   ASL_TRY(rescore_device({.Q = Q.dev, .L = L->dev,
                           .cand = {.rows64 = knn.d, .stride = k, .total_slots = (int64_t)nq * k},
                           .tol = P->fragment_mz_tolerance, .allow_shift = P->allow_shift, .tie_by_row = 1,
@@ -669,9 +687,12 @@ static int search_batch_sync(asl_library_t *L, asl_index_t *idx, const asl_peaks
                              int64_t *knn_I, bool distinct = false) {
   const int nq = queries->n;
   const size_t nw = (size_t)nq * (size_t)std::max(n_best, 1);
+  ASL_TRY(check_window_arg(P, "search_batch"));
   ASL_TRY(ensure_device());
   PeaksStage Q;
   ASL_TRY(Q.init(queries));
+  In<double> dwin;
+  if (P->precursor_mode == ASL_TOL_INTERVAL) ASL_TRY(dwin.init(P->precursor_window, (size_t)nq * 2));
   Out<int32_t> o_row, o_ncand, o_cnt;
   Out<double> o_score;
   Out<uint32_t> o_pairs;
@@ -702,12 +723,12 @@ static int search_batch_sync(asl_library_t *L, asl_index_t *idx, const asl_peaks
     IndexWindow w;
     IndexPostFilter pf;
     offer_library(rq, L);
-    if (win) offer_window(rq, w, Q.dev, P, knn_I == nullptr ? L->rows_len.p : nullptr);
-    else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(rq, pf, L, Q.dev, P, L->rows_len.p);
+    if (win) offer_window(rq, w, Q.dev, P, dwin.d, knn_I == nullptr ? L->rows_len.p : nullptr);
+    else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(rq, pf, L, Q.dev, P, dwin.d, L->rows_len.p);
     ASL_TRY(index_search_device(idx, rq));
     const bool rows_filtered = rq.rows_filtered;
     PrecFilter flt;
-    batch_filter(L, P, flt);
+    batch_filter(L, P, dwin.d, flt);
     ASL_TRY(rescore_device({.Q = Q.dev, .L = L->dev,
                             .cand = {.rows32 = L->knn.p, .stride = k, .total_slots = (int64_t)nq * k,
                                      .row_counts = rows_filtered ? L->rows_len.p : nullptr},
@@ -718,7 +739,7 @@ static int search_batch_sync(asl_library_t *L, asl_index_t *idx, const asl_peaks
                             .best_row = o_row.d, .best_score = o_score.d, .n_valid = o_ncand.d,
                             .pm_count = o_cnt.d, .pm_pairs = o_pairs.d, .pm_stride = pm_stride}));
   } else {
-    ASL_TRY(window_search_device(L, Q.dev, P, o_row.d, o_score.d, o_ncand.d, o_cnt.d, o_pairs.d,
+    ASL_TRY(window_search_device(L, Q.dev, P, dwin.d, o_row.d, o_score.d, o_ncand.d, o_cnt.d, o_pairs.d,
                                  pm_stride, n_best, distinct));
   }
   ASL_TRY(o_row.finish());
@@ -769,6 +790,19 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
   ASL_TRY(L->p_rows[par].reserve((size_t)nq));
   ASL_TRY(L->pair_score.reserve((size_t)nq * k));
   ASL_TRY(L->best_slot.reserve((size_t)nq));
+  // ASL_TOL_INTERVAL: the intervals where they are, or -- a host array -- copied into this parity's buffer
+  // before the call returns. Its last readers were the scan and the rescoring of batch i-2.
+  const double *dwin = nullptr;
+  if (P->precursor_mode == ASL_TOL_INTERVAL) {
+    dwin = P->precursor_window;
+    if (!is_device_ptr(dwin)) {
+      ASL_TRY(L->p_win[par].reserve((size_t)nq * 2));
+      if (pp.resc_recorded[par]) HIP_TRY(hipStreamWaitEvent(stream(), pp.ev_resc[par], 0));
+      HIP_TRY(hipMemcpyAsync(L->p_win[par].p, dwin, (size_t)nq * 16, hipMemcpyHostToDevice, stream()));
+      HIP_TRY(hipStreamSynchronize(stream()));     // the array is the caller's again on return
+      dwin = L->p_win[par].p;
+    }
+  }
   pp.parity ^= 1;
   // the caller's stream produced the inputs (and owns the output memory) up to here
   HIP_TRY(hipEventRecord(pp.ev_in, stream()));
@@ -804,8 +838,8 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
     IndexWindow w;
     IndexPostFilter pf;
     offer_library(rq, L);
-    if (win) offer_window(rq, w, Q.dev, P, knn_I == nullptr ? L->p_rows[par].p : nullptr);
-    else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(rq, pf, L, Q.dev, P, L->p_rows[par].p);
+    if (win) offer_window(rq, w, Q.dev, P, dwin, knn_I == nullptr ? L->p_rows[par].p : nullptr);
+    else if (knn_I == nullptr && scan_postfilter_on()) offer_post_filter(rq, pf, L, Q.dev, P, dwin, L->p_rows[par].p);
     ASL_TRY(index_search_device(idx, rq));
     // (window scan: set-mode rows hold in-window hits only, and their lengths)
     rows_filtered = rq.rows_filtered;
@@ -819,7 +853,7 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
     StreamScope on_c(sc);
     HIP_TRY(hipStreamWaitEvent(sc, pp.ev_scan[par], 0));
     PrecFilter flt;
-    batch_filter(L, P, flt);
+    batch_filter(L, P, dwin, flt);
     ASL_TRY(rescore_device({.Q = Q.dev, .L = L->dev,
                             .cand = {.rows32 = L->p_knn[par].p, .stride = k, .total_slots = (int64_t)nq * k,
                                      .row_counts = rows_filtered ? L->p_rows[par].p : nullptr},
@@ -846,6 +880,7 @@ int asl_search_batch(asl_library_t *L, asl_index_t *idx, const asl_peaks_t *quer
   if (pm_pairs && pm_stride <= 0) return fail(ASL_ERR_INVALID, "search_batch: pm_stride");
   if (P->use_ann && !idx) return fail(ASL_ERR_INVALID, "search_batch: use_ann needs an index");
   if (P->use_ann && P->k <= 0) return fail(ASL_ERR_INVALID, "search_batch: k must be positive");
+  ASL_TRY(check_window_arg(P, "search_batch"));
   {
     // pipeline mode applies to ANN batches whose arguments all live on the device (nothing to
     // stage, nothing to copy back) and whose peak count the caller supplied; anything else takes

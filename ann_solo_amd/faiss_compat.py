@@ -44,6 +44,21 @@ def _as_f32(x, d):
     return x if isinstance(x, np.ndarray) else x.contiguous()
 
 
+TOL_MODES = {'Da': 0, 'ppm': 1, 'interval': 2}     # ASL_TOL_DA / ASL_TOL_PPM / ASL_TOL_INTERVAL
+
+
+def _window_operand(pmz, nq, mode, who):
+    """The queries' side of a window test as float64: one precursor m/z per query ('Da', 'ppm') or, with
+    ``mode='interval'``, an [nq, 2] array of closed intervals (lo, hi) on the key -- whose shape is checked
+    here, before the library reads 2 * nq doubles. The 'Da' / 'ppm' operand is the caller's to check, where
+    it did so before the third mode existed."""
+    TOL_MODES[mode]       # (KeyError for anything else, as ever)
+    pmz = pmz.double().contiguous() if hasattr(pmz, 'data_ptr') else np.ascontiguousarray(pmz, np.float64)
+    if mode == 'interval' and tuple(pmz.shape) != (nq, 2):
+        raise ValueError(f'{who}: the window needs an [nq, 2] array of intervals (lo, hi)')
+    return pmz
+
+
 class Index:
     def __init__(self, handle, d):
         if not handle:
@@ -128,11 +143,12 @@ class Index:
         """``search`` restricted to the vectors whose key (``set_window_key``) passes each query's
         precursor window -- FAISS' ``search(x, k, params=SearchParametersIVF(sel=IDSelectorRange(...)))``
         over a key-sorted id range: (D, I), rows (score desc, id asc) of the k best in-window vectors of
-        the probed lists, -1 padded. ``mode``: 'Da' or 'ppm' (the reference's window test)."""
+        the probed lists, -1 padded. ``mode``: 'Da' or 'ppm' (the reference's window test), or 'interval':
+        ``precursor_mz`` is then an [nq, 2] float64 array of closed intervals (lo, hi), a vector passes iff
+        lo <= key <= hi (NaN never passes, lo > hi is empty), and ``charge`` and ``tol`` are unread."""
         x = _as_f32(x, self.d)
         nq = x.shape[0]
-        pmz = (precursor_mz.double().contiguous() if hasattr(precursor_mz, 'data_ptr')
-               else np.ascontiguousarray(precursor_mz, np.float64))
+        pmz = _window_operand(precursor_mz, nq, mode, 'search_window')
         if D is None and I is None:
             if isinstance(x, np.ndarray):
                 D = np.empty((nq, k), np.float32)
@@ -142,7 +158,7 @@ class Index:
                 D = torch.empty((nq, k), dtype=torch.float32, device=x.device)
                 I = torch.empty((nq, k), dtype=torch.int64, device=x.device)
         _lib.check(_lib.lib().asl_index_search_window(self._h, nq, _lib.ptr(x), _lib.ptr(pmz), int(charge),
-                                                      float(tol), {'Da': 0, 'ppm': 1}[mode], int(k),
+                                                      float(tol), TOL_MODES[mode], int(k),
                                                       int(self.nprobe), _lib.ptr(D), _lib.ptr(I)))
         return D, I
 
@@ -175,8 +191,8 @@ class Index:
         pmz, charge, tol, mode = None, 0, 0.0, 'Da'
         if window is not None:
             pmz, charge, tol, mode = window
-            pmz = pmz.double().contiguous() if hasattr(pmz, 'data_ptr') else np.ascontiguousarray(pmz, np.float64)
-            if tuple(pmz.shape) != (nq,):
+            pmz = _window_operand(pmz, nq, mode, 'search_selected')
+            if mode != 'interval' and tuple(pmz.shape) != (nq,):
                 raise ValueError('search_selected: the window needs one precursor m/z per query')
         if D is None and I is None:
             if isinstance(x, np.ndarray):
@@ -187,7 +203,7 @@ class Index:
                 D = torch.empty((nq, k), dtype=torch.float32, device=x.device)
                 I = torch.empty((nq, k), dtype=torch.int64, device=x.device)
         _lib.check(_lib.lib().asl_index_search_selected(self._h, nq, _lib.ptr(x), _lib.ptr(pmz), int(charge),
-                                                        float(tol), {'Da': 0, 'ppm': 1}[mode], int(k),
+                                                        float(tol), TOL_MODES[mode], int(k),
                                                         int(self.nprobe), _lib.ptr(D), _lib.ptr(I)))
         return D, I
 
@@ -222,12 +238,12 @@ class Index:
         if window is not None:
             key, pmz, charge, tol, mode = window
             key = key.float().contiguous() if hasattr(key, 'data_ptr') else np.ascontiguousarray(key, np.float32)
-            pmz = pmz.double().contiguous() if hasattr(pmz, 'data_ptr') else np.ascontiguousarray(pmz, np.float64)
-            if key.shape != (self.ntotal,) or pmz.shape != (nq,):
+            pmz = _window_operand(pmz, nq, mode, 'rank_of')
+            if key.shape != (self.ntotal,) or (mode != 'interval' and pmz.shape != (nq,)):
                 raise ValueError('rank_of: the window needs one key per vector id and one precursor m/z per query')
         nprobe = self.nprobe if nprobe is None else nprobe
         _lib.check(_lib.lib().asl_index_rank(self._h, nq, _lib.ptr(x), _lib.ptr(target), int(nprobe), _lib.ptr(key),
-                                             _lib.ptr(pmz), int(charge), float(tol), {'Da': 0, 'ppm': 1}[mode],
+                                             _lib.ptr(pmz), int(charge), float(tol), TOL_MODES[mode],
                                              _lib.ptr(rank), _lib.ptr(score), _lib.ptr(scope)))
         return rank, score, scope
 

@@ -452,14 +452,21 @@ class SpectralLibrary:
         return self.config.mode == 'ann' and mode == 'open' and charge in self._ann_filenames
 
     def _search_batch(self, queries: PackedSpectra, charge: int, mode: str,
-                      want_knn: bool = False, device_out: bool = False) -> Optional[BatchResult]:
+                      want_knn: bool = False, device_out: bool = False, windows=None) -> Optional[BatchResult]:
         """One batch of same-charge, processed query spectra (spectral_library.py:328-370):
         through the device hot path of this GPU, or -- after ``enable_sharding`` on more than
         one rank -- over all ranks. Returns None when the library has no spectra of that charge
-        (:411-412)."""
+        (:411-412). ``windows``: None, or one closed interval (lo, hi) of library precursor m/z per query
+        ([nq, 2] float64, numpy or a device tensor) -- the candidates are then the rows whose float32
+        precursor m/z lies inside it (``ASL_TOL_INTERVAL``), whatever the level's tolerance is; scores
+        still use the query's own precursor m/z. One GPU."""
         d = getattr(self, '_dist', None)
         if d is None or d.world == 1:
-            return self._search_batch_local(queries, charge, mode, want_knn, device_out)
+            if windows is None:     # (engines that override _search_batch_local with its older signature)
+                return self._search_batch_local(queries, charge, mode, want_knn, device_out)
+            return self._search_batch_local(queries, charge, mode, want_knn, device_out, windows=windows)
+        if windows is not None:
+            raise ValueError('windows= does not run on a sharded index')
         tol_val, tol_mode = self._tolerance(mode)
         if tol_mode not in ('Da', 'ppm'):
             raise ValueError('Unknown precursor tolerance mode')
@@ -472,7 +479,7 @@ class SpectralLibrary:
 
     def _search_batch_local(self, queries: PackedSpectra, charge: int, mode: str,
                             want_knn: bool = False, device_out: bool = False,
-                            pm_stride: Optional[int] = None) -> Optional[BatchResult]:
+                            pm_stride: Optional[int] = None, windows=None) -> Optional[BatchResult]:
         """One batch on this GPU alone (the index must not be sharded for open searches)."""
         tol_val, tol_mode = self._tolerance(mode)
         if tol_mode not in ('Da', 'ppm'):
@@ -504,13 +511,28 @@ class SpectralLibrary:
                                  float(tol_val), 0 if tol_mode == 'Da' else 1,
                                  cfg.fragment_mz_tolerance, int(cfg.allow_peak_shifts),
                                  int(use_ann))
+        windows = self._interval_windows(P, windows, nq)
         _lib.check(_lib.lib().asl_search_batch(
             part.handle, idx._h if idx is not None else None, C.byref(_lib.peaks_struct(q)),
             C.byref(P), _lib.ptr(best_row), _lib.ptr(best_score), _lib.ptr(n_cand),
             _lib.ptr(pm_count), _lib.ptr(pm_pairs), stride, _lib.ptr(knn)))
         if device_out and use_ann and getattr(self, '_pipeline_on', False):
-            self._hold(q, best_row, best_score, n_cand, pm_count, pm_pairs, knn)
+            self._hold(q, best_row, best_score, n_cand, pm_count, pm_pairs, knn, windows)
         return BatchResult(best_row, best_score, n_cand, pm_count, pm_pairs, knn)
+
+    def _interval_windows(self, P, windows, nq: int):
+        """``windows=`` of a search call into its parameter block: [nq, 2] float64 on the device,
+        ``precursor_mode`` 2 (``ASL_TOL_INTERVAL``). Returns the tensor (the caller keeps it alive)."""
+        if windows is None:
+            return None
+        if not hasattr(windows, 'data_ptr'):
+            windows = torch.from_numpy(np.ascontiguousarray(windows, np.float64))
+        windows = windows.to(device=self.device, dtype=torch.float64).contiguous()
+        if tuple(windows.shape) != (nq, 2):
+            raise ValueError(f'windows: {tuple(windows.shape)} for {nq} queries; one interval (lo, hi) per query')
+        P.precursor_mode = faiss.TOL_MODES['interval']
+        P.precursor_window = _lib.ptr(windows)
+        return windows
 
     def set_match_groups(self, groups: Optional[Dict[int, np.ndarray]]) -> None:
         """Group ids of the library rows for distinct ranked matches: ``{charge: int32 array}``, one
@@ -590,12 +612,14 @@ class SpectralLibrary:
 
     def search_batch_topn(self, queries: PackedSpectra, charge: int, mode: str, n_best: int,
                           want_knn: bool = False, device_out: bool = False,
-                          pm_stride: Optional[int] = None, distinct: bool = False) -> Optional[TopnBatchResult]:
+                          pm_stride: Optional[int] = None, distinct: bool = False,
+                          windows=None) -> Optional[TopnBatchResult]:
         """``_search_batch_local`` for the ``n_best`` (1 .. 16) best library matches of every query
         (``asl_search_batch_topn``): every cascade level and index mode, on this GPU alone.
         Synchronous -- the call never joins the two-stream pipeline. Rank 0 (and ``n_candidates``,
         ``knn``) is what ``_search_batch_local`` returns, bit for bit. ``distinct``: one rank per
-        group of ``set_match_groups`` (``asl_search_batch_topn_distinct``; an error without groups)."""
+        group of ``set_match_groups`` (``asl_search_batch_topn_distinct``; an error without groups).
+        ``windows``: as in ``_search_batch``."""
         d = getattr(self, '_dist', None)
         if d is not None and d.world > 1:
             raise ValueError('search_batch_topn does not run on a sharded index')
@@ -627,6 +651,7 @@ class SpectralLibrary:
                                  float(tol_val), 0 if tol_mode == 'Da' else 1,
                                  cfg.fragment_mz_tolerance, int(cfg.allow_peak_shifts),
                                  int(use_ann))
+        windows = self._interval_windows(P, windows, nq)
         call = _lib.lib().asl_search_batch_topn_distinct if distinct else _lib.lib().asl_search_batch_topn
         _lib.check(call(
             part.handle, idx._h if idx is not None else None, C.byref(_lib.peaks_struct(q)),
@@ -634,23 +659,30 @@ class SpectralLibrary:
             _lib.ptr(pm_count), _lib.ptr(pm_pairs), stride, _lib.ptr(knn)))
         return TopnBatchResult(best_row, best_score, n_cand, pm_count, pm_pairs, knn)
 
-    def _get_library_candidates(self, queries: PackedSpectra, charge: int, mode: str):
+    def _get_library_candidates(self, queries: PackedSpectra, charge: int, mode: str, windows=None):
         """CSR candidate lists (library rows of the charge partition, ascending) after the
         precursor filter -- and, in open+ann mode, after the ANN filter. Diagnostic
-        mirror of spectral_library.py:372-455; ``_search_batch`` never materialises it."""
+        mirror of spectral_library.py:372-455; ``_search_batch`` never materialises it.
+        ``windows``: as in ``_search_batch`` (the precursor filter is then the interval test)."""
         tol_val, tol_mode = self._tolerance(mode)
         if charge not in self.partitions:
             return None
         part = self.partitions[charge]
         nq = queries.n
         qp = np.ascontiguousarray(queries.precursor_mz.cpu().numpy(), np.float64)
+        tol_code = 0 if tol_mode == 'Da' else 1
+        if windows is not None:
+            qp = np.ascontiguousarray(_to_np(windows), np.float64)
+            if qp.shape != (nq, 2):
+                raise ValueError(f'windows: {qp.shape} for {nq} queries; one interval (lo, hi) per query')
+            tol_code = faiss.TOL_MODES['interval']
         off = np.empty(nq + 1, np.int32)
         _lib.check(_lib.lib().asl_window_candidates(part.handle, nq, _lib.ptr(qp), charge,
-                                                    float(tol_val), 0 if tol_mode == 'Da' else 1,
+                                                    float(tol_val), tol_code,
                                                     _lib.ptr(off), None))
         rows = np.empty(int(off[-1]), np.int64)
         _lib.check(_lib.lib().asl_window_candidates(part.handle, nq, _lib.ptr(qp), charge,
-                                                    float(tol_val), 0 if tol_mode == 'Da' else 1,
+                                                    float(tol_val), tol_code,
                                                     _lib.ptr(off), _lib.ptr(rows)))
         lists = [rows[off[i]:off[i + 1]] for i in range(nq)]
         if self.config.mode == 'ann' and mode == 'open' and charge in self._ann_filenames:
@@ -741,7 +773,13 @@ class SpectralLibrary:
         identifiers are unique).
 
         ``query_meta[charge][i]`` / ``library_meta[charge][row]``: mappings with the reference's
-        attribute names (see ``spectrum.ssms_from_batch``). ``score_ssms`` stands for
+        attribute names (see ``spectrum.ssms_from_batch``). A query record may also carry
+        ``isolation_window = (lo, hi)``, the m/z interval its precursor is known to lie in (wide-window
+        DDA, DIA pseudo-spectra; lo <= hi, else ``ValueError``): when EVERY query of a charge has one, the
+        open level takes its candidates from the library rows whose precursor m/z lies inside that
+        interval, instead of the window around ``precursor_mz`` (``precursor_tolerance_mass_open`` or
+        ``Config.precursor_window_open``); scores still use ``precursor_mz``. One GPU: ``ValueError`` on
+        a sharded library. ``score_ssms`` stands for
         ``utils.score_ssms`` (:319-326, mokapot -- out of scope): called as ``score_ssms(ssms,
         mode)`` with a list of SSM records it assigns ``search_engine_score`` / ``q`` and
         returns the SSMs to keep; a callable with the attribute ``columnar = True`` receives the
@@ -786,6 +824,23 @@ class SpectralLibrary:
         logging.info('%d spectra identified after the open search', n_identified)   # :257
         return SSMTable.concat([t1, t2])
 
+    def _open_level_windows(self, qs: PackedSpectra, query_meta, charge: int) -> Optional[np.ndarray]:
+        """The open level's per-query intervals for one charge set ([qs.n, 2] float64), or None for the
+        symmetric window of ``precursor_tolerance_mass_open``: the queries' isolation windows when every
+        query of the set has one, else the range of ``Config.precursor_window_open`` around each query."""
+        d = getattr(self, '_dist', None)
+        sharded = d is not None and d.world > 1
+        meta = query_meta.get(charge) if hasattr(query_meta, 'get') else None
+        iso = isolation_windows(meta, qs.n)
+        if iso is None and self.config.precursor_window_open is None:
+            return None
+        if sharded:     # like every other opt-in: an error, never another window than the one asked for
+            raise ValueError(('isolation windows in the query metadata do' if iso is not None else
+                              'precursor_window_open does') + ' not run on a sharded index')
+        if iso is not None:
+            return iso
+        return open_window_intervals(_to_np(qs.precursor_mz), charge, self.config.precursor_window_open)
+
     def _search_cascade(self, query_spectra, query_meta, library_meta, rows_by_charge, mode,
                         score_ssms=None, uid=None) -> 'SSMTable':
         """One cascade level (:264-326): batches of ``batch_size`` same-charge queries through
@@ -815,20 +870,27 @@ class SpectralLibrary:
             for charge, rows in rows_by_charge.items():
                 rows = np.asarray(rows, np.int64)
                 qs = query_spectra[charge]
+                # open level: per-query intervals instead of the symmetric window (isolation windows of the
+                # queries' metadata, else Config.precursor_window_open); None: the level's tolerance
+                level_win = self._open_level_windows(qs, query_meta, charge) if mode == 'open' else None
                 for b0 in range(0, len(rows), bs):
                     sel = rows[b0:b0 + bs]
                     if len(sel) == 0:
                         continue
                     whole = len(sel) == qs.n and sel[0] == 0 and sel[-1] == qs.n - 1
                     q = (qs if whole else qs.select(torch.as_tensor(sel))).to(self.device)
+                    win = None if level_win is None else level_win[sel]
                     if n_best > 1:      # rank 0 goes the single winner's way, the rest rides along
                         top = self.search_batch_topn(q, charge, mode, n_best, device_out=True,
-                                                     distinct=distinct)
+                                                     distinct=distinct, windows=win)
                         res = None if top is None else top.rank0()
                         if res is not None:
                             res.topn = top
                     else:
-                        res = self._search_batch(q, charge, mode, device_out=True)
+                        # (no keyword without windows: engines that override _search_batch with its older
+                        # signature, as the oracle-backed ones of the tests do, keep working)
+                        res = (self._search_batch(q, charge, mode, device_out=True) if win is None else
+                               self._search_batch(q, charge, mode, device_out=True, windows=win))
                     if res is not None:
                         pending.append((charge, sel, q, res))
         finally:
@@ -878,6 +940,35 @@ class SpectralLibrary:
 
 def _to_np(a):
     return a.detach().cpu().numpy() if hasattr(a, 'detach') else np.asarray(a)
+
+
+def open_window_intervals(precursor_mz, charge: int, window_da) -> np.ndarray:
+    """``Config.precursor_window_open`` as intervals of library precursor m/z, [n, 2] float64: the neutral
+    mass difference (query - library) * charge lies in [lo_da, hi_da] iff the library's m/z lies in
+    [q - hi_da / charge, q - lo_da / charge] (computed in float64; the bounds are inclusive)."""
+    lo_da, hi_da = (float(v) for v in window_da)
+    q = np.asarray(precursor_mz, np.float64)
+    return np.stack([q - hi_da / charge, q - lo_da / charge], axis=1)
+
+
+def isolation_windows(meta, n: int) -> Optional[np.ndarray]:
+    """The queries' isolation windows, [n, 2] float64 (lo, hi) in m/z, from the optional ``isolation_window``
+    entry of their metadata records -- None unless every one of the n queries has one. An entry that is no
+    pair lo <= hi is a ValueError."""
+    if meta is None or n == 0 or len(meta) < n:
+        return None
+    out = np.empty((n, 2), np.float64)
+    for i in range(n):
+        m = meta[i]
+        w = m.get('isolation_window') if hasattr(m, 'get') else None
+        if w is None:
+            return None
+        w = np.asarray(w, np.float64)
+        if w.shape != (2,) or not w[0] <= w[1]:       # (a NaN bound fails too)
+            raise ValueError(f'query {i}: isolation_window = {m.get("isolation_window")!r}; a pair (lo, hi) of m/z '
+                             'with lo <= hi')
+        out[i] = w
+    return out
 
 
 def _query_uids(query_meta, charges) -> Optional[Dict[int, np.ndarray]]:

@@ -42,8 +42,23 @@ extern "C" {
 #define ASL_INDEX_IVFFLAT 1   /* IndexIVFFlat(IndexFlatIP, d, nlist, IP)     */
 #define ASL_INDEX_IVFPQ 2     /* IVF + product quantiser, by-residual IP ADC */
 
+/* The precursor window of a query: which library rows are its candidates, by the float32 window column
+ * `key` (lib_pmz_f32; NaN, or unselected under a selection: never a candidate).
+ * ASL_TOL_DA / ASL_TOL_PPM: one tolerance for the batch, symmetric around the query's own precursor m/z q
+ * (spectral_library.py:417-429, in double): |q - key| * charge <= tol, or |q - key| / key * 1e6 <= tol.
+ * ASL_TOL_INTERVAL: a closed interval per query. Wherever a call takes the queries' precursor m/z for the
+ * window test (q_pmz, query_pmz; asl_search_params_t::precursor_window for the fused calls) it then takes
+ * [nq, 2] doubles, (lo_i, hi_i) interleaved, and row r passes iff lo_i <= (double)key[r] && (double)key[r]
+ * <= hi_i. A NaN key or a NaN bound never passes, lo > hi is an empty window and no error, +-inf are legal
+ * bounds; charge and tol are unread. Only the candidates change: the shifted dot product still takes its
+ * precursor mass difference from the query's and the row's own precursor m/z, and the window is applied
+ * before or after the top-k as configured. (FAISS: IDSelectorRange per query.) asl_index_search_window,
+ * asl_index_search_selected and asl_index_rank answer any other value of their mode argument with
+ * ASL_ERR_INVALID; asl_window_candidates and precursor_mode of the fused calls are not checked (as before the
+ * third mode existed, a value other than these three is read as ASL_TOL_PPM). */
 #define ASL_TOL_DA 0
 #define ASL_TOL_PPM 1
+#define ASL_TOL_INTERVAL 2
 
 const char *asl_last_error(void);
 const char *asl_version(void);
@@ -185,7 +200,8 @@ int asl_index_refine(asl_index_t *idx, int32_t nq, const float *xq, int32_t kpri
 int asl_index_set_window_key(asl_index_t *idx, int64_t n, const float *key);
 /* top-k (score desc, id asc) among the probed lists' vectors whose key passes
  * precursor_ok(q_pmz[i], key, charge, tol, mode) -- the window test of asl_search_batch, same double
- * arithmetic; -1 / -FLT_MAX padded. Same coarse quantiser and nprobe as asl_index_search. */
+ * arithmetic; -1 / -FLT_MAX padded. Same coarse quantiser and nprobe as asl_index_search.
+ * mode == ASL_TOL_INTERVAL: q_pmz is [nq, 2]. */
 int asl_index_search_window(asl_index_t *idx, int32_t nq, const float *xq, const double *q_pmz,
                             int32_t charge, double tol, int32_t mode, int32_t k, int32_t nprobe,
                             float *D, int64_t *I);
@@ -210,7 +226,8 @@ int asl_index_set_selector(asl_index_t *idx, int64_t n, const uint8_t *keep);
 /* The ordered top-k (score desc, id asc; -1 / -FLT_MAX padded) among the selected vectors of the probed
  * lists; same coarse quantiser and nprobe as asl_index_search. q_pmz == NULL: no window (charge, tol, mode
  * unread). With q_pmz, of the selected vectors only those whose window key passes precursor_ok(q_pmz[i], key,
- * charge, tol, mode): the window-ordered layout, which needs asl_index_set_window_key (and, like it, IVF-PQ).
+ * charge, tol, mode; ASL_TOL_INTERVAL: q_pmz is [nq, 2]): the window-ordered layout, which needs
+ * asl_index_set_window_key (and, like it, IVF-PQ).
  * Served by the tiled IVF-PQ scan (m = 32, 8 bits, by_residual on or off) and the IVF-Flat postings scan
  * (float and fixed-point postings), k <= 1280, nprobe <= 1024. Everything else is ASL_ERR_STATE with a message
  * that names the reason, never a filter behind the top-k: no selector (or the lists changed since it was set),
@@ -229,7 +246,7 @@ int asl_index_search_selected(asl_index_t *idx, int32_t nq, const float *xq, con
  * -- nprobe = 0: of every list (exhaustive), else of the coarse quantiser's top-nprobe, the lists
  * asl_index_search scans -- and, with key != NULL (float32 per vector id, [ntotal]), of those only the
  * ones that pass precursor_ok(q_pmz[i], key[v], charge, tol, mode), as asl_index_search_window keeps
- * them. rank[i] = -1 when the target is not in the scope (target < 0 or >= ntotal, its list not
+ * them (ASL_TOL_INTERVAL: q_pmz is [nq, 2]). rank[i] = -1 when the target is not in the scope (target < 0 or >= ntotal, its list not
  * probed, its key NaN or outside the window). So with the same probes and window the target is in the
  * rows of a search for every k > rank and for no k <= rank. score (optional): the target's score, NaN
  * where rank is -1; scope (optional): the number of vectors in the scope. Nothing is kept on the
@@ -619,10 +636,19 @@ typedef struct {
   int32_t nprobe;             /* config.num_probe */
   int32_t charge;             /* precursor charge of this batch */
   double precursor_tol;       /* config.precursor_tolerance_mass(_open) */
-  int32_t precursor_mode;     /* ASL_TOL_DA / ASL_TOL_PPM */
+  int32_t precursor_mode;     /* ASL_TOL_DA / ASL_TOL_PPM / ASL_TOL_INTERVAL */
   double fragment_mz_tolerance;
   int32_t allow_shift;        /* config.allow_peak_shifts */
   int32_t use_ann;            /* 1: ANN top-k AND window (open+ann); 0: window only (std / bf) */
+  /* The queries' intervals, [nq, 2] (lo, hi), host or device memory: read only when precursor_mode ==
+   * ASL_TOL_INTERVAL (NULL is then ASL_ERR_INVALID; precursor_tol is unread). A host array is copied before
+   * the call returns, by a pipelined asl_search_batch too -- which for that copy waits on the host until the
+   * batch before the previous one has been rescored (the copy goes into that batch's buffer), so part of
+   * the pipeline's overlap is lost: pass device arrays to pipelined calls. A device array must stay as it
+   * is for as long as the queries' arrays. The member was added behind the older ones: a caller compiled against the struct
+   * without it never sets ASL_TOL_INTERVAL, so it is never read for that caller. Honoured by
+   * asl_search_batch / _topn / _topn_distinct and asl_rescore_knn*, in every mode they have. */
+  const double *precursor_window;
 } asl_search_params_t;
 
 /* Outputs, each [nq] (NULL to skip): best_row = library row of the best match
@@ -686,7 +712,7 @@ int asl_rescore_knn_topn_distinct(asl_library_t *lib, const asl_peaks_t *queries
 /* Precursor-window candidate generation alone (spectral_library.py:417-429):
  * CSR lists of library rows (ascending) whose precursor passes the window. Two-call
  * protocol: first with cand_rows == NULL to get cand_offsets[nq+1], then with a
- * buffer of cand_offsets[nq] entries. */
+ * buffer of cand_offsets[nq] entries. mode == ASL_TOL_INTERVAL: query_pmz is [nq, 2]. */
 int asl_window_candidates(asl_library_t *lib, int32_t nq, const double *query_pmz,
                           int32_t charge, double tol, int32_t mode, int32_t *cand_offsets,
                           int64_t *cand_rows);
