@@ -4,7 +4,7 @@
 (/root/reference/src/ann_solo/config.py:62-216) plus the ADDITIVE flags of this implementation
 (``index``, ``pq_m``, ``pq_bits``, ``refine_k``, ``kmeans_niter``, ``ann_seed``, ``num_gpus``,
 ``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``, ``pq_by_residual``,
-``precursor_window_open``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``precursor_window_open``, ``fragment_tolerance_unit``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -94,6 +94,12 @@ class Config:
     # charge a candidate may have, e.g. (-150, 500), instead of the symmetric +-precursor_tolerance_mass_open
     # (flags --precursor_window_open_low / _high). None: the reference's symmetric window
     precursor_window_open: Optional[Tuple[float, float]] = None
+    # unit of fragment_mz_tolerance in the (shifted) dot product: 'Da' (the reference: one window width for
+    # every peak) | 'ppm' (opt-in: of the QUERY peak's m/z, tol_i = tolerance * 1e-6 * q_mz[i]).
+    # Deliberately NOT the reference's ``fragment_tol_mode``: that flag defaults to 'ppm' but reaches only the
+    # decoy annotation -- the reference's dot product reads the tolerance as Da whatever it says -- so
+    # ``from_reference`` would pick its default up and change the results of every existing configuration.
+    fragment_tolerance_unit: str = 'Da'
 
     MAX_PEAKS = 256      # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
@@ -131,6 +137,10 @@ class Config:
             raise ValueError('num_matches > 1 does not run on a sharded index (num_gpus > 1)')
         if self.distinct_matches and self.num_gpus and int(self.num_gpus) > 1:
             raise ValueError('distinct_matches does not run on a sharded index (num_gpus > 1)')
+        if self.fragment_tolerance_unit not in ('Da', 'ppm'):
+            raise ValueError(f"fragment_tolerance_unit = {self.fragment_tolerance_unit!r}: 'Da' or 'ppm'")
+        if self.fragment_tolerance_unit == 'ppm' and self.num_gpus and int(self.num_gpus) > 1:
+            raise ValueError("fragment_tolerance_unit = 'ppm' does not run on a sharded index (num_gpus > 1)")
         if self.precursor_window_open is not None:
             try:
                 lo, hi = (float(v) for v in self.precursor_window_open)
@@ -256,6 +266,12 @@ def add_arguments(parser) -> None:
                         help='open search: highest neutral mass difference (query - library, Da) a '
                              'candidate may have; needs --precursor_window_open_low; one GPU '
                              '(default: the symmetric window)')
+    parser.add_argument('--fragment_tolerance_unit', default=d.fragment_tolerance_unit, type=str,
+                        choices=['Da', 'ppm'],
+                        help="unit of --fragment_mz_tolerance in the (shifted) dot product: 'Da', one window "
+                             "width for every peak (the reference), or 'ppm' of the query peak's m/z; not "
+                             "the reference's --fragment_tol_mode, which only reaches its decoy annotation; "
+                             'one GPU (default: %(default)s)')
     parser.add_argument('--distinct_matches', action='store_true', default=d.distinct_matches,
                         help='with --num_matches above 1: one rank per library peptide -- the '
                              "runners-up are the best matches of other peptides and the score gap is "

@@ -232,9 +232,15 @@ __device__ double resolve_matches(int lane, WL &W, uint32_t *out_pairs, int out_
 // DEFER (the small-LDS instantiation of the matches kernel): a pair that does not fit the
 // structures -- more candidate peaks or generated matches than they hold -- is not an error, the
 // call returns -1 and the pair is left to the full-size instantiation.
+// The fragment window of query peak qm. Da: `tol` itself. ppm (`ppm` != 0, wave-uniform): `tol` holds
+// rel = fragment_mz_tolerance * 1e-6 and the window is relative to the QUERY peak, tol_i = rel * qm --
+// one fp64 multiply (the build has -ffp-contract=off). qm - tol_i = qm (1 - rel) ascends with qm, so the
+// reference's cursors still only advance. The shift gate (cpp:20) reads rs_frag_tol(tol, ppm, q_pmz).
+__device__ __forceinline__ double rs_frag_tol(double tol, int ppm, double qm) { return ppm ? tol * qm : tol; }
+
 template <bool EMIT, bool DEFER = false, class QL = QueryLds, class WL = WaveLds>
 __device__ double dot_pair_wave(int lane, const QL &Q, int qn, double q_pmz,
-                                const DevPeaks &L, int row, double tol, int allow_shift,
+                                const DevPeaks &L, int row, double tol, int ppm, int allow_shift,
                                 WL &W, uint32_t *out_pairs, int out_cap, int *out_count,
                                 int *status) {
   const int co = L.offsets[row];
@@ -254,7 +260,7 @@ __device__ double dot_pair_wave(int lane, const QL &Q, int qn, double q_pmz,
   if (lane == 0) W.counter = 0;
   const int c_charge = L.precursor_charge[row];
   const double pmd = (q_pmz - L.precursor_mz[row]) * (double)(unsigned)c_charge;  // cpp:18
-  const int S = (allow_shift && fabs(pmd) >= tol) ? c_charge + 1 : 1;            // cpp:20
+  const int S = (allow_shift && fabs(pmd) >= rs_frag_tol(tol, ppm, q_pmz)) ? c_charge + 1 : 1;   // cpp:20
   wave_sync();
 
   for (int qb = 0; qb < qn; qb += 64) {
@@ -262,11 +268,12 @@ __device__ double dot_pair_wave(int lane, const QL &Q, int qn, double q_pmz,
     if (qi < qn) {
       const double qm = (double)Q.mz[qi];
       const float q_int = Q.inten[qi];
+      const double tl = rs_frag_tol(tol, ppm, qm);
       for (int s = 0; s < S; ++s) {
         const double md = s ? pmd / (double)s : 0.0;  // cpp:26-31
         // cursor = first j where NOT (qm - tol > c_mz[j] + md), capped at cn-1 (cpp:39-46)
         int lo = 0, hi = cn;
-        const double lim = qm - tol;
+        const double lim = qm - tl;
         while (lo < hi) {
           int mid = (lo + hi) >> 1;
           if (lim > (double)W.c_mz[mid] + md)
@@ -276,7 +283,7 @@ __device__ double dot_pair_wave(int lane, const QL &Q, int qn, double q_pmz,
         }
         int j = min(lo, cn - 1);
         // cpp:49-55
-        while (j < cn && fabs(qm - ((double)W.c_mz[j] + md)) <= tol) {
+        while (j < cn && fabs(qm - ((double)W.c_mz[j] + md)) <= tl) {
           const int chg = W.c_chg[j];
           double mult = 0.0;
           if (s == 0 || chg == s)
@@ -320,7 +327,7 @@ __device__ __forceinline__ void load_query(int tid, int nthreads, const DevPeaks
 
 constexpr int RS_BS_GROUP = 16;      // queries per workgroup of the binary-search kernel
 __global__ __launch_bounds__(64 * RS_WAVES) void rescore_score_kernel(
-    DevPeaks Qs, DevPeaks L, CandView cv, double tol, int allow_shift,
+    DevPeaks Qs, DevPeaks L, CandView cv, double tol, int ppm, int allow_shift,
     double *__restrict__ pair_score, const int *__restrict__ q_defer, int *status, int group) {
   __shared__ QueryLds Q;
   __shared__ WaveLds W[RS_WAVES];
@@ -357,7 +364,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_score_kernel(
       const long long row = cv.cand(q, c, q_pmz, L.n);
       double s = -1.0;
       if (row >= 0)
-        s = dot_pair_wave<false>(lane, Q, qn, q_pmz, L, (int)row, tol, allow_shift, W[wave],
+        s = dot_pair_wave<false>(lane, Q, qn, q_pmz, L, (int)row, tol, ppm, allow_shift, W[wave],
                                  nullptr, 0, nullptr, status);
       if (lane == 0) pair_score[c] = s;
     }
@@ -437,11 +444,25 @@ __device__ __forceinline__ int rs_append_items(int *__restrict__ q_defer, int nq
 //     tol >= 6.8e-4, at 20 000 tol >= 4.3e-3, at 100 000 tol >= 2.04e-2.
 // Nothing is scored through a filter whose margin does not cover it; inside the envelope the
 // bins, and so the exact test's inputs, are the same whatever the margin.
+// ppm windows (rs_frag_tol: tol_i = rel * qm_i per query peak) keep LINEAR bins, of width 2 tol_max with
+// tol_max = rel * (the query's largest m/z), the widest window of the query (rs_tol_max). A peak is
+// filed under the bins of its own window [qm - tol_i, qm + tol_i] widened by the margin at tol_max.
+// The argument above holds with tol := tol_max: a candidate peak that matches query peak i has
+// |x| <= |qm_i| + tol_i <= max|qm| + tol_max, inv_w is 1 / (2 tol_max), so its fp32 bin lies within
+// `margin` bins of x inv_w, which lies inside the filed interval; and since tol_i <= tol_max that
+// interval spans (2 tol_i) / (2 tol_max) + 2 margin <= 1 + 0.9 < 2 bin widths: still <= 3 bins per peak
+// (RS_HT holds them). Low-mass peaks, whose windows are narrower than a bin, share bins with
+// non-matching positions more often: extra hits, which the exact test rejects. !(tol_max > 0) or a
+// margin above RS_MARGIN_MAX defers the query as in Da mode (at m/z 2000 that is below 0.34 ppm).
 // (The kernels take the margin from the query's peaks once they are in LDS: two loads from memory
 // in front of the peak load, to decide first, were a dependent round trip per workgroup and cost the
 // rescoring stage 0.08 ms of 2.1 at 32 768 queries -- profiles/rescore_envelope_ab.txt.)
 constexpr double RS_MD_ENV = 4096.0;
 constexpr double RS_MARGIN_MAX = 0.45;
+// the widest fragment window of a query whose peaks ascend (Da: the tolerance itself)
+__device__ __forceinline__ double rs_tol_max(float q_first, float q_last, double tol, int ppm) {
+  return ppm ? tol * (double)fmaxf(q_first, q_last) : tol;
+}
 __device__ __forceinline__ double rs_bin_margin(float q_first, float q_last, double tol) {
   if (!(tol > 0.0)) return 1.0;
   const double q_abs = (double)fmaxf(fabsf(q_first), fabsf(q_last));
@@ -564,7 +585,7 @@ __device__ __attribute__((noinline)) double resolve_half_slow(int lane, PairLds 
 __device__ __forceinline__ void score_two(int lane, const QueryLds2 &Q, const HashLds &H,
                                           PairLds &Wv, int slotA, int slotB, int cnA, int cnB,
                                           int chgA, int chgB, double pmzA, double pmzB,
-                                          double q_pmz, double tol, double inv_w, int allow_shift,
+                                          double q_pmz, double tol, int ppm, double inv_w, int allow_shift,
                                           int *status, double &scoreA, double &scoreB) {
   const int half = lane >> 5, hl = lane & 31;
   if (lane == 0) {
@@ -573,8 +594,9 @@ __device__ __forceinline__ void score_two(int lane, const QueryLds2 &Q, const Ha
   }
   const double pmdA = (q_pmz - pmzA) * (double)(unsigned)chgA;          // cpp:18
   const double pmdB = (q_pmz - pmzB) * (double)(unsigned)chgB;
-  const int SA = (allow_shift && fabs(pmdA) >= tol) ? chgA + 1 : 1;      // cpp:20
-  const int SB = (allow_shift && fabs(pmdB) >= tol) ? chgB + 1 : 1;
+  const double gate = rs_frag_tol(tol, ppm, q_pmz);
+  const int SA = (allow_shift && fabs(pmdA) >= gate) ? chgA + 1 : 1;     // cpp:20
+  const int SB = (allow_shift && fabs(pmdB) >= gate) ? chgB + 1 : 1;
   const int slot = half ? slotB : slotA, cn = half ? cnB : cnA, S = half ? SB : SA;
   const double pmd = half ? pmdB : pmdA;
   const float *s_mz = Wv.c_mz + slot * 64;
@@ -626,15 +648,16 @@ __device__ __forceinline__ void score_two(int lane, const QueryLds2 &Q, const Ha
             const int i = H.peak[h];
             const double x = (double)cm + md;
             const double qm = (double)Q.mz[i];
-            const double lim = qm - tol;
-            if (fabs(qm - x) <= tol && (!(lim > x) || j == cn - 1)) {
+            const double tl = rs_frag_tol(tol, ppm, qm);
+            const double lim = qm - tl;
+            if (fabs(qm - x) <= tl && (!(lim > x) || j == cn - 1)) {
               // the reference walks from its cursor: every peak between the cursor and j
               // must pass the window test too (differs only on fp boundaries)
               bool run = true;
               for (int jj = j; jj > 0; --jj) {
                 const double xp = (double)s_mz[jj - 1] + md;
                 if (lim > xp) break;
-                if (!(fabs(qm - xp) <= tol)) {
+                if (!(fabs(qm - xp) <= tl)) {
                   run = false;
                   break;
                 }
@@ -691,7 +714,7 @@ __device__ __forceinline__ void score_two(int lane, const QueryLds2 &Q, const Ha
 // One item. The block's LDS structures are rebuilt per item (the caller puts a barrier in between).
 template <int FORM>
 __device__ __forceinline__ void pair_item(const int q, const int y, const int ny, const DevPeaks &Qs,
-                                          const DevPeaks &L, const CandView &cv, const double tol,
+                                          const DevPeaks &L, const CandView &cv, const double tol, const int ppm,
                                           const int allow_shift, double *__restrict__ pair_score,
                                           int *__restrict__ q_defer, int *status, QueryLds2 &Q, HashLds &H,
                                           PairLds (&W)[RS_WAVES], uint16_t (&s_list)[RS_SUPER], int &s_nv,
@@ -727,16 +750,22 @@ __device__ __forceinline__ void pair_item(const int q, const int y, const int ny
   __syncthreads();
   // the margin of this query's own m/z range, from the peaks just loaded (no extra trip to memory
   // in front of the load); beyond RS_MARGIN_MAX the query leaves the hash path (uniform)
-  const double margin = qn > 0 ? rs_bin_margin(Q.mz[0], Q.mz[qn - 1], tol) : 0.0;
+  // (ppm: linear bins of the query's widest window, tol_max -- see rs_bin_margin)
+  const double tol_max = qn > 0 ? rs_tol_max(Q.mz[0], Q.mz[qn - 1], tol, ppm) : tol;
+  const double margin = qn > 0 ? rs_bin_margin(Q.mz[0], Q.mz[qn - 1], tol_max) : 0.0;
   if (!(margin <= RS_MARGIN_MAX)) {
     defer_query();
     return;
   }
-  const double inv_w = 1.0 / (2.0 * tol);
+  const double inv_w = 1.0 / (2.0 * tol_max);
   if (tid < qn) {
     const double qm = (double)Q.mz[tid];
-    const int blo = (int)floor((qm - tol) * inv_w - margin);
-    const int bhi = (int)floor((qm + tol) * inv_w + margin);
+    const double tl = rs_frag_tol(tol, ppm, qm);
+    // (tol_i <= tol_max for ascending peaks; the clamp keeps a spectrum that breaks that rule at <= 3
+    // bins per peak, which is what the table is sized for)
+    const double tf = fmin(tl, tol_max);
+    const int blo = (int)floor((qm - tf) * inv_w - margin);
+    const int bhi = (int)floor((qm + tf) * inv_w + margin);
     for (int b = blo; b <= bhi; ++b) {
       const uint32_t bit = hbit(b);
       atomicOr(&H.bm[bit >> 5], 1u << (bit & 31));
@@ -842,7 +871,7 @@ __device__ __forceinline__ void pair_item(const int q, const int y, const int ny
           double sA = 0.0, sB = 0.0;
           if (runA || runB) {
             score_two(lane, Q, H, Wv, u, u + 1, runA ? cnA : 0, runB ? cnB : 0, chA, chB,
-                      rl_d(m_pmz, vA ? lA : 0), rl_d(m_pmz, vB ? lB : 0), q_pmz, tol, inv_w,
+                      rl_d(m_pmz, vA ? lA : 0), rl_d(m_pmz, vB ? lB : 0), q_pmz, tol, ppm, inv_w,
                       allow_shift, status, sA, sB);
           }
           if (defA || sA == RS_DEFER) sA = RS_DEFER_BS;
@@ -862,7 +891,7 @@ __device__ __forceinline__ void pair_item(const int q, const int y, const int ny
 
 template <int FORM>
 __global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel(
-    DevPeaks Qs, DevPeaks L, CandView cv, double tol, int allow_shift,
+    DevPeaks Qs, DevPeaks L, CandView cv, double tol, int ppm, int allow_shift,
     double *__restrict__ pair_score, int *__restrict__ q_defer, int *status) {
   cv.flt.wcol = nullptr;      // this kernel wants filter column and metadata from ONE gather
   if (FORM != 3) cv.win_begin = nullptr;
@@ -902,7 +931,7 @@ __global__ __launch_bounds__(64 * RS_WAVES, RS_OCC) void rescore_score_v2_kernel
     if (it != (int)blockIdx.x) __syncthreads();      // the previous item's tables are no longer read
     const int2 w = items[it];
     const int wq = __builtin_amdgcn_readfirstlane(w.x), wy = __builtin_amdgcn_readfirstlane(w.y);
-    pair_item<FORM>(wq, wy & 0xff, wy >> 8, Qs, L, cv, tol, allow_shift, pair_score, q_defer, status, Q, H, W,
+    pair_item<FORM>(wq, wy & 0xff, wy >> 8, Qs, L, cv, tol, ppm, allow_shift, pair_score, q_defer, status, Q, H, W,
                     s_list, s_nv, s_defer);
   }
 }
@@ -963,7 +992,7 @@ constexpr double RS_PRUNE_REL = 1e-9, RS_PRUNE_ABS = 1e-12;
 constexpr int RF_OCC = 6;      // waves per SIMD: 80 VGPRs (7 / 8: 72 / 64 VGPRs and more spills: +2 % / +12 %, profiles/r03_rescore_ab.txt)
 template <int FORM>
 __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
-    DevPeaks Qs, DevPeaks L, CandView cv, double tol, int allow_shift,
+    DevPeaks Qs, DevPeaks L, CandView cv, double tol, int ppm, int allow_shift,
     double *__restrict__ pair_score, int *__restrict__ q_defer, int *status, int prune, int ymax,
     unsigned long long *__restrict__ counts) {
   if (FORM != 3) cv.win_begin = nullptr;
@@ -1002,6 +1031,10 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
   __shared__ unsigned long long s_best;      // largest exact score written (>= 0: orders as u64)
   __shared__ double s_dbound[RF_DLIST];
   __shared__ uint32_t s_dslot[RF_DLIST];     // the listed candidate's slot - c0
+  // the window of every query peak (rs_frag_tol; Da: the one tolerance), worked out once at the filing:
+  // the drain reads it beside the peak, and neither the tolerance nor the mode stays in registers
+  // across the stream loop
+  __shared__ double s_qtol[RS_HQ_MAX];
   const int q = blockIdx.x;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   long long c0, c1;
@@ -1010,6 +1043,7 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
   const int qo = Qs.offsets[q];
   const int qn = Qs.offsets[q + 1] - qo;
   const double q_pmz = Qs.precursor_mz[q];
+  const double gate = rs_frag_tol(tol, ppm, q_pmz);      // the shift gate's threshold (cpp:20)
   // the row was filtered where it was made (block-uniform): every slot in range is a candidate
   const bool pre = cv.prefiltered(q);
   auto is_cand = [&](long long c) -> bool {
@@ -1044,16 +1078,23 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
   __syncthreads();
   // the margin of this query's own m/z range, from the peaks just loaded (no extra trip to memory
   // in front of the load); beyond RS_MARGIN_MAX the query leaves the hash path (uniform)
-  const double margin = qn > 0 ? rs_bin_margin(Q.mz[0], Q.mz[qn - 1], tol) : 0.0;
+  // (ppm: linear bins of the query's widest window, tol_max -- see rs_bin_margin)
+  const double tol_max = qn > 0 ? rs_tol_max(Q.mz[0], Q.mz[qn - 1], tol, ppm) : tol;
+  const double margin = qn > 0 ? rs_bin_margin(Q.mz[0], Q.mz[qn - 1], tol_max) : 0.0;
   if (!(margin <= RS_MARGIN_MAX)) {
     defer_query();
     return;
   }
-  const double inv_w = 1.0 / (2.0 * tol);
+  const double inv_w = 1.0 / (2.0 * tol_max);
   if (tid < qn) {
     const double qm = (double)Q.mz[tid];
-    const int blo = (int)floor((qm - tol) * inv_w - margin);
-    const int bhi = (int)floor((qm + tol) * inv_w + margin);
+    const double tl = rs_frag_tol(tol, ppm, qm);
+    s_qtol[tid] = tl;
+    // (tol_i <= tol_max for ascending peaks; the clamp keeps a spectrum that breaks that rule at <= 3
+    // bins per peak, which is what the table is sized for)
+    const double tf = fmin(tl, tol_max);
+    const int blo = (int)floor((qm - tf) * inv_w - margin);
+    const int bhi = (int)floor((qm + tf) * inv_w + margin);
     for (int b = blo; b <= bhi; ++b) {
       const uint32_t bit = hbit(b);
       atomicOr(&H.bm[bit >> 5], 1u << (bit & 31));
@@ -1123,7 +1164,7 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
         }
       }
       const double pmd = (q_pmz - m_pmz) * (double)(unsigned)m_chg;            // cpp:18
-      const int S = (allow_shift && fabs(pmd) >= tol) ? m_chg + 1 : 1;          // cpp:20
+      const int S = (allow_shift && fabs(pmd) >= gate) ? m_chg + 1 : 1;         // cpp:20
       // (a shift beyond the bin filter's envelope: RS_MD_ENV)
       const bool def_bs = okr && (m_cn > 64 || m_chg >= 31 || (S > 1 && !(fabs(pmd) <= RS_MD_ENV)));
       const bool def_pair = okr && !def_bs && S > RF_SMAX;
@@ -1227,8 +1268,9 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
                 const int i = H.peak[h];
                 const double x = (double)cm + md;
                 const double qm = (double)Q.mz[i];
-                const double lim = qm - tol;
-                if (fabs(qm - x) <= tol && (!(lim > x) || j == cn - 1)) {
+                const double tl = s_qtol[i];
+                const double lim = qm - tl;
+                if (fabs(qm - x) <= tl && (!(lim > x) || j == cn - 1)) {
                   // the reference walks from its cursor: every peak between the cursor and j
                   // must pass the window test too (differs only on fp boundaries)
                   bool run = true;
@@ -1238,7 +1280,7 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
                                            : L.mz + co;
                     const double xp = (double)pm_[jj - 1] + md;
                     if (lim > xp) break;
-                    if (!(fabs(qm - xp) <= tol)) {
+                    if (!(fabs(qm - xp) <= tl)) {
                       run = false;
                       break;
                     }
@@ -1434,8 +1476,8 @@ constexpr int RS_SMALL_P = 128, RS_SMALL_M = 128;
 template <bool SMALL, class QL, class WL>
 __device__ __forceinline__ void matches_one(int q, int w, int lane, QL &Qw, WL &Ww, int *s_cnt_w, const DevPeaks &Qs,
                                             const DevPeaks &L, const CandView &cv,
-                                            const long long *__restrict__ best_slot, double tol, int allow_shift,
-                                            int32_t *__restrict__ pm_count, uint32_t *__restrict__ pm_pairs,
+                                            const long long *__restrict__ best_slot, double tol, int ppm,
+                                            int allow_shift, int32_t *__restrict__ pm_count, uint32_t *__restrict__ pm_pairs,
                                             int pm_stride, int32_t *__restrict__ best_row, int *status,
                                             int *__restrict__ m_defer) {
   const long long slot = best_slot[w];
@@ -1456,7 +1498,7 @@ __device__ __forceinline__ void matches_one(int q, int w, int lane, QL &Qw, WL &
   load_query(lane, 64, Qs, q, Qw, qn, status);
   wave_sync();
   int cnt_tmp = 0;
-  const double sc = dot_pair_wave<true, SMALL>(lane, Qw, qn, Qs.precursor_mz[q], L, (int)row, tol, allow_shift,
+  const double sc = dot_pair_wave<true, SMALL>(lane, Qw, qn, Qs.precursor_mz[q], L, (int)row, tol, ppm, allow_shift,
                                                Ww, pm_pairs ? pm_pairs + (size_t)w * pm_stride * 2 : nullptr,
                                                pm_pairs ? pm_stride : 0, s_cnt_w, status);
   if (SMALL && sc < 0.0) {        // (wave-uniform) does not fit: the second launch does this query
@@ -1478,7 +1520,7 @@ constexpr int RS_MF_GROUP = 16;
 template <bool SMALL>
 __global__ __launch_bounds__(64 * RS_WAVES) void rescore_matches_kernel(
     DevPeaks Qs, DevPeaks L, CandView cv, int nq, int n, const long long *__restrict__ best_slot,
-    double tol, int allow_shift, int32_t *__restrict__ pm_count,
+    double tol, int ppm, int allow_shift, int32_t *__restrict__ pm_count,
     uint32_t *__restrict__ pm_pairs, int pm_stride, int32_t *__restrict__ best_row,
     int *status, int *__restrict__ m_defer) {
   typedef QueryLdsT<SMALL ? RS_SMALL_P : RS_MAXP> QL;
@@ -1493,7 +1535,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_matches_kernel(
     if (w >= nw) return;
     if (lane == 0) m_defer[w] = 0;
     matches_one<true>((int)(w / n), (int)w, lane, Q[wave], W[wave], &s_cnt[wave], Qs, L, cv, best_slot, tol,
-                      allow_shift, pm_count, pm_pairs, pm_stride, best_row, status, m_defer);
+                      ppm, allow_shift, pm_count, pm_pairs, pm_stride, best_row, status, m_defer);
     return;
   }
   // a wave takes RS_MF_GROUP consecutive winners: one read of their flags; if every one is marked
@@ -1505,7 +1547,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_matches_kernel(
     todo &= todo - 1ull;
     const long long w = base + l;
     matches_one<false>((int)(w / n), (int)w, lane, Q[wave], W[wave], &s_cnt[wave], Qs, L, cv, best_slot, tol,
-                       allow_shift, pm_count, pm_pairs, pm_stride, best_row, status, m_defer);
+                       ppm, allow_shift, pm_count, pm_pairs, pm_stride, best_row, status, m_defer);
     wave_sync();
   }
 }
@@ -1555,6 +1597,10 @@ int rescore_device(const RescoreRequest &rq) {
     return fail(ASL_ERR_INVALID, "rescore: window lists need CSR offsets and packed rows (internal)");
   DevBuf<int> &q_defer = rq.scratch->q_defer, &m_defer = rq.scratch->m_defer;
   const CandView cv = make_cand_view(cand, filter);
+  // what the kernels read as `tol`: the tolerance in Da, or (tol_ppm) the relative tolerance, one fp64
+  // multiply done here once
+  const int ppm = rq.tol_ppm ? 1 : 0;
+  const double tol = ppm ? rq.tol * 1e-6 : rq.tol;
   if (rq.clear_status) HIP_TRY(hipMemsetAsync(rq.status, 0, sizeof(int), stream()));
   {
     ProfScope ps("rescore");
@@ -1581,8 +1627,8 @@ int rescore_device(const RescoreRequest &rq) {
       auto flat = form == 3 ? rescore_flat_kernel<3>
                   : form == 0 ? rescore_flat_kernel<0>
                   : form == 2 ? rescore_flat_kernel<2> : rescore_flat_kernel<1>;
-      hipLaunchKernelGGL(flat, dim3(nq, ysplit), dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, rq.tol,
-                         rq.allow_shift, rq.pair_score, q_defer.p, rq.status, prune, ymax, counts);
+      hipLaunchKernelGGL(flat, dim3(nq, ysplit), dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, tol,
+                         ppm, rq.allow_shift, rq.pair_score, q_defer.p, rq.status, prune, ymax, counts);
       ASL_CHECK_LAUNCH();
       if (ysplit > 1) {
         hipLaunchKernelGGL(rescore_worklist_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, stream(),
@@ -1595,14 +1641,14 @@ int rescore_device(const RescoreRequest &rq) {
       int pair_grid = 0;
       ASL_TRY(pair_resident_blocks(form, (const void *)kern, &pair_grid));
       hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(pair_grid, (int64_t)nq * ymax)),
-                         dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, rq.tol, rq.allow_shift, rq.pair_score,
+                         dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, tol, ppm, rq.allow_shift, rq.pair_score,
                          q_defer.p, rq.status);
       ASL_CHECK_LAUNCH();
       // (small batches keep a workgroup per query: when every query is marked -- tol <= 0, queries
       // of more than 100 peaks -- they need all the parallelism there is)
       const int bs_group = nq >= 4096 ? RS_BS_GROUP : 1;
       hipLaunchKernelGGL(rescore_score_kernel, dim3((unsigned)cdiv(nq, bs_group), ysplit), dim3(64 * RS_WAVES), 0,
-                         stream(), Q, L, cv, rq.tol, rq.allow_shift, rq.pair_score,
+                         stream(), Q, L, cv, tol, ppm, rq.allow_shift, rq.pair_score,
                          (const int *)q_defer.p, rq.status, bs_group);
     }
     ASL_CHECK_LAUNCH();
@@ -1621,14 +1667,22 @@ int rescore_device(const RescoreRequest &rq) {
     const long long nw = (long long)nq * n;
     ASL_TRY(m_defer.reserve((size_t)nw));
     hipLaunchKernelGGL(rescore_matches_kernel<true>, dim3((unsigned)cdiv(nw, RS_WAVES)),
-                       dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, n, rq.best_slot, rq.tol,
-                       rq.allow_shift, rq.pm_count, rq.pm_pairs, rq.pm_stride, rq.best_row, rq.status, m_defer.p);
+                       dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, n, rq.best_slot, tol,
+                       ppm, rq.allow_shift, rq.pm_count, rq.pm_pairs, rq.pm_stride, rq.best_row, rq.status, m_defer.p);
     ASL_CHECK_LAUNCH();
     hipLaunchKernelGGL(rescore_matches_kernel<false>, dim3((unsigned)cdiv(nw, RS_MF_GROUP * RS_WAVES)),
-                       dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, n, rq.best_slot, rq.tol,
-                       rq.allow_shift, rq.pm_count, rq.pm_pairs, rq.pm_stride, rq.best_row, rq.status, m_defer.p);
+                       dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, n, rq.best_slot, tol,
+                       ppm, rq.allow_shift, rq.pm_count, rq.pm_pairs, rq.pm_stride, rq.best_row, rq.status, m_defer.p);
     ASL_CHECK_LAUNCH();
   }
+  return ASL_OK;
+}
+
+int decode_score_flags(int word, const char *who, ScoreFlags &out) {
+  if (word & ~(ASL_SCORE_SHIFT | ASL_SCORE_FRAGMENT_PPM))
+    return fail(ASL_ERR_INVALID, "%s: allow_shift holds bits other than ASL_SCORE_SHIFT | ASL_SCORE_FRAGMENT_PPM", who);
+  out.allow_shift = (word & ASL_SCORE_SHIFT) ? 1 : 0;
+  out.tol_ppm = (word & ASL_SCORE_FRAGMENT_PPM) ? 1 : 0;
   return ASL_OK;
 }
 
@@ -1657,10 +1711,12 @@ using namespace asl;
 // asl_rescore_batch_topn_distinct (lib_group: [library->n] group ids, host or device; null: plain)
 static int rescore_batch_sync(const asl_peaks_t *queries, const asl_peaks_t *library,
                               const int64_t *cand_rows, const int32_t *cand_offsets, double tol,
-                              int allow_shift, int n_best, int32_t *best_cand, double *best_score,
+                              int score_flags, int n_best, int32_t *best_cand, double *best_score,
                               int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride,
                               const int32_t *lib_group = nullptr) {
   if (!queries || !library) return fail(ASL_ERR_INVALID, "rescore_batch: null spectra");
+  ScoreFlags sf;
+  ASL_TRY(decode_score_flags(score_flags, "rescore_batch", sf));
   const int nq = queries->n;
   const size_t nw = (size_t)nq * (size_t)std::max(n_best, 1);
   if (nq == 0) return ASL_OK;
@@ -1702,7 +1758,7 @@ static int rescore_batch_sync(const asl_peaks_t *queries, const asl_peaks_t *lib
   RescoreScratch scratch;      // lives until rescore_check_status below has synchronised
   ASL_TRY(rescore_device({.Q = Q.dev, .L = L.dev,
                           .cand = {.rows64 = rows.d, .offsets = off.d, .total_slots = total},
-                          .tol = tol, .allow_shift = allow_shift, .n_best = n_best,
+                          .tol = tol, .tol_ppm = sf.tol_ppm, .allow_shift = sf.allow_shift, .n_best = n_best,
                           .group = lib_group ? grp.d : nullptr,
                           .pair_score = pair_score.p, .best_slot = best_slot.p, .scratch = &scratch,
                           .status = status.p,

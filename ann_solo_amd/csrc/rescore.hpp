@@ -116,7 +116,8 @@ struct RescoreRequest {
   // -- candidate list
   CandList cand;
   // -- scoring
-  double tol = 0.0;                     // fragment m/z tolerance
+  double tol = 0.0;                     // fragment m/z tolerance: Da, or
+  int tol_ppm = 0;                      // 1: ppm of the QUERY peak's m/z (rescore.hip: rs_frag_tol)
   int allow_shift = 0;
   int tie_by_row = 0;                   // equal scores: 0 the first slot wins, 1 the lowest library row
   PrecFilter filter;                    // precursor window applied to the slots (default: none)
@@ -145,6 +146,13 @@ struct RescoreRequest {
   int32_t pm_stride = 0;
   bool emit_matches = true;             // false: stop after the selection (no best_row, pm_count, pm_pairs written)
 };
+
+// The ABI's score flag word (annsolo_mi.h: ASL_SCORE_*, the `allow_shift` argument / member), decoded
+// where a call enters: bits other than the two flags are ASL_ERR_INVALID.
+struct ScoreFlags {
+  int allow_shift = 0, tol_ppm = 0;
+};
+int decode_score_flags(int word, const char *who, ScoreFlags &out);
 
 // Host driver shared by asl_rescore_batch, asl_search_batch and asl_rescore_knn.
 int rescore_device(const RescoreRequest &rq);

@@ -185,8 +185,12 @@ static const double *window_operand(const DevPeaks &Q, const asl_search_params_t
 static int check_window_arg(const asl_search_params_t *P, const char *who) {
   if (P->precursor_mode == ASL_TOL_INTERVAL && !P->precursor_window)
     return fail(ASL_ERR_INVALID, "%s: precursor_mode ASL_TOL_INTERVAL needs precursor_window ([nq, 2] doubles)", who);
-  return ASL_OK;
+  ScoreFlags sf;      // params->allow_shift is the score flag word: checked here, where every call enters
+  return decode_score_flags(P->allow_shift, who, sf);
 }
+// (the checked word's two flags, for the rescoring requests)
+static inline int score_shift(const asl_search_params_t *P) { return (P->allow_shift & ASL_SCORE_SHIFT) ? 1 : 0; }
+static inline int score_ppm(const asl_search_params_t *P) { return (P->allow_shift & ASL_SCORE_FRAGMENT_PPM) ? 1 : 0; }
 // The precursor window of a batch's scan, into its request: the window scan (asl_index_set_window_scan)
 // when the index is in that mode, else -- no ordered neighbour list asked for -- the scan-side
 // post-filter of THIS library's window column. row_len: the lengths of the set-mode rows.
@@ -503,7 +507,8 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
     win.begin = L->wtile.p + nq + 1;
     return rescore_device({.Q = Q, .L = L->dev,
                            .cand = {.offsets = L->wtile.p, .total_slots = total, .window = &win},
-                           .tol = P->fragment_mz_tolerance, .allow_shift = P->allow_shift, .tie_by_row = 1,
+                           .tol = P->fragment_mz_tolerance, .tol_ppm = score_ppm(P), .allow_shift = score_shift(P),
+                            .tie_by_row = 1,
                            .filter = rows_only, .n_best = n_best, .group = group,
                            .pair_score = L->pair_score.p, .best_slot = L->best_slot.p,
                            .scratch = &L->rs_scratch, .status = L->status.p,
@@ -554,7 +559,8 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
     win.begin = off + T.nq + 1;
     const CandList tile{.offsets = off, .total_slots = T.pairs, .window = &win};
     ASL_TRY(rescore_device({.Q = Qt, .L = L->dev, .cand = tile,
-                            .tol = P->fragment_mz_tolerance, .allow_shift = P->allow_shift, .tie_by_row = 1,
+                            .tol = P->fragment_mz_tolerance, .tol_ppm = score_ppm(P), .allow_shift = score_shift(P),
+                            .tie_by_row = 1,
                             .filter = rows_only, .n_best = n_best, .group = group,
                             .pair_score = L->pair_score.p, .best_slot = L->best_slot.p,
                             .scratch = &L->rs_scratch, .status = L->status.p, .clear_status = false,
@@ -567,7 +573,8 @@ static int window_search_device(asl_library *L, const DevPeaks &Q, const asl_sea
   // order comes out again, with rows and peak matches (n_best = 0: the one winner, by the argmax)
   ASL_TRY(rescore_device({.Q = Q, .L = L->dev,
                           .cand = {.rows32 = L->run_row.p, .stride = n, .total_slots = (int64_t)nw},
-                          .tol = P->fragment_mz_tolerance, .allow_shift = P->allow_shift, .tie_by_row = 1,
+                          .tol = P->fragment_mz_tolerance, .tol_ppm = score_ppm(P), .allow_shift = score_shift(P),
+                            .tie_by_row = 1,
                           .filter = rows_only, .n_best = n_best,
                           .pair_score = L->pair_score.p, .best_slot = L->best_slot.p,
                           .scratch = &L->rs_scratch, .status = L->status.p, .clear_status = false,
@@ -647,7 +654,8 @@ static int rescore_knn_sync(asl_library_t *L, const asl_peaks_t *queries, const 
   batch_filter(L, P, dwin.d, flt);
   ASL_TRY(rescore_device({.Q = Q.dev, .L = L->dev,
                           .cand = {.rows64 = knn.d, .stride = k, .total_slots = (int64_t)nq * k},
-                          .tol = P->fragment_mz_tolerance, .allow_shift = P->allow_shift, .tie_by_row = 1,
+                          .tol = P->fragment_mz_tolerance, .tol_ppm = score_ppm(P), .allow_shift = score_shift(P),
+                            .tie_by_row = 1,
                           .filter = flt, .n_best = n_best, .group = distinct ? L->group.p : nullptr,
                           .pair_score = L->pair_score.p, .best_slot = L->best_slot.p,
                           .scratch = &L->rs_scratch, .status = L->status.p,
@@ -732,7 +740,8 @@ static int search_batch_sync(asl_library_t *L, asl_index_t *idx, const asl_peaks
     ASL_TRY(rescore_device({.Q = Q.dev, .L = L->dev,
                             .cand = {.rows32 = L->knn.p, .stride = k, .total_slots = (int64_t)nq * k,
                                      .row_counts = rows_filtered ? L->rows_len.p : nullptr},
-                            .tol = P->fragment_mz_tolerance, .allow_shift = P->allow_shift, .tie_by_row = 1,
+                            .tol = P->fragment_mz_tolerance, .tol_ppm = score_ppm(P), .allow_shift = score_shift(P),
+                            .tie_by_row = 1,
                             .filter = flt, .n_best = n_best, .group = distinct ? L->group.p : nullptr,
                             .pair_score = L->pair_score.p, .best_slot = L->best_slot.p,
                             .scratch = &L->rs_scratch, .status = L->status.p,
@@ -857,7 +866,8 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
     ASL_TRY(rescore_device({.Q = Q.dev, .L = L->dev,
                             .cand = {.rows32 = L->p_knn[par].p, .stride = k, .total_slots = (int64_t)nq * k,
                                      .row_counts = rows_filtered ? L->p_rows[par].p : nullptr},
-                            .tol = P->fragment_mz_tolerance, .allow_shift = P->allow_shift, .tie_by_row = 1,
+                            .tol = P->fragment_mz_tolerance, .tol_ppm = score_ppm(P), .allow_shift = score_shift(P),
+                            .tie_by_row = 1,
                             .filter = flt,
                             .pair_score = L->pair_score.p, .best_slot = L->best_slot.p,
                             .scratch = &L->rs_scratch, .status = pp.status, .clear_status = false,

@@ -59,6 +59,7 @@ import torch.distributed as dist
 
 from . import _lib
 from .packed import PackedSpectra
+from .spectrum_match import score_flags
 
 
 def lpt_owner(list_sizes, world: int) -> np.ndarray:
@@ -337,7 +338,8 @@ class HipShardBackend:
         _, min_bound, _ = get_dim(cfg.min_mz, cfg.max_mz, cfg.bin_size)
         P = _lib.AslSearchParams(min_bound, cfg.bin_size, HASH_SEED, self.k, sl._num_probe,
                                  self.charge, float(tol_val), 0 if tol_mode == 'Da' else 1,
-                                 cfg.fragment_mz_tolerance, int(cfg.allow_peak_shifts), 1)
+                                 cfg.fragment_mz_tolerance,
+                                 score_flags(cfg.allow_peak_shifts, cfg.fragment_tolerance_unit), 1)
         knn = knn.contiguous()
         _lib.check(_lib.lib().asl_rescore_knn(
             self.part.handle, C.byref(_lib.peaks_struct(q)), C.byref(P), _lib.ptr(knn),

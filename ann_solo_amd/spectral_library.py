@@ -33,6 +33,7 @@ from . import faiss_compat as faiss
 from .config import Config
 from .packed import PackedSpectra
 from .spectrum import get_dim, spectra_to_vectors, HASH_SEED
+from .spectrum_match import score_flags
 
 
 @dataclass
@@ -509,7 +510,8 @@ class SpectralLibrary:
         _, min_bound, _ = get_dim(cfg.min_mz, cfg.max_mz, cfg.bin_size)
         P = _lib.AslSearchParams(min_bound, cfg.bin_size, HASH_SEED, k, self._num_probe, charge,
                                  float(tol_val), 0 if tol_mode == 'Da' else 1,
-                                 cfg.fragment_mz_tolerance, int(cfg.allow_peak_shifts),
+                                 cfg.fragment_mz_tolerance,
+                                 score_flags(cfg.allow_peak_shifts, cfg.fragment_tolerance_unit),
                                  int(use_ann))
         windows = self._interval_windows(P, windows, nq)
         _lib.check(_lib.lib().asl_search_batch(
@@ -649,7 +651,8 @@ class SpectralLibrary:
         _, min_bound, _ = get_dim(cfg.min_mz, cfg.max_mz, cfg.bin_size)
         P = _lib.AslSearchParams(min_bound, cfg.bin_size, HASH_SEED, k, self._num_probe, charge,
                                  float(tol_val), 0 if tol_mode == 'Da' else 1,
-                                 cfg.fragment_mz_tolerance, int(cfg.allow_peak_shifts),
+                                 cfg.fragment_mz_tolerance,
+                                 score_flags(cfg.allow_peak_shifts, cfg.fragment_tolerance_unit),
                                  int(use_ann))
         windows = self._interval_windows(P, windows, nq)
         call = _lib.lib().asl_search_batch_topn_distinct if distinct else _lib.lib().asl_search_batch_topn

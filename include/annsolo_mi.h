@@ -482,7 +482,24 @@ typedef struct {
  *   best_score[q] SpectrumMatcher::dot score (double)
  *   pm_count[q]   number of matched peak pairs of the winner
  *   pm_pairs      [nq, pm_stride, 2] (query_peak, candidate_peak) in greedy order, zero beyond
- *                 pm_count[q] (asl_search_batch / asl_rescore_knn write every slot) */
+ *                 pm_count[q] (asl_search_batch / asl_rescore_knn write every slot)
+ *
+ * `allow_shift` -- here, in the _topn entries below and as asl_search_params_t.allow_shift -- is a FLAG
+ * WORD. 0 and 1 mean what they always meant; any bit other than the two below is ASL_ERR_INVALID.
+ *   ASL_SCORE_SHIFT         the shifted dot product (config.allow_peak_shifts)
+ *   ASL_SCORE_FRAGMENT_PPM  fragment_mz_tolerance t is in ppm of the QUERY peak's m/z, not in Da:
+ *       rel   = t * 1e-6                      (fp64, once)
+ *       tol_i = rel * (double)q_mz[i]         (fp64, one multiply) is the window of query peak i,
+ *     read wherever SpectrumMatcher::dot reads its tolerance for that peak: the cursor test
+ *     (double)q_mz[i] - tol_i > x and the window test fabs((double)q_mz[i] - x) <= tol_i, with
+ *     x = (double)c_mz[j] + mass_diff[s] as before; and the shift gate (SpectrumMatch.cpp:20) becomes
+ *     num_shifts = (shift && fabs(pmd) >= rel * q_precursor_mz) ? charge + 1 : 1. Products, their
+ *     order, the greedy assignment, the fp64 sum and the tie rules between candidates do not change;
+ *     with the flag clear every output is what it was, bit for bit. (The reference's
+ *     --fragment_tol_mode never reaches its dot product, which reads the number as Da whatever the
+ *     flag says: this mode has no counterpart there.) */
+#define ASL_SCORE_SHIFT 1
+#define ASL_SCORE_FRAGMENT_PPM 2
 int asl_rescore_batch(const asl_peaks_t *queries, const asl_peaks_t *library,
                       const int64_t *cand_rows, const int32_t *cand_offsets,
                       double fragment_mz_tolerance, int allow_shift, int32_t *best_cand,
@@ -637,8 +654,8 @@ typedef struct {
   int32_t charge;             /* precursor charge of this batch */
   double precursor_tol;       /* config.precursor_tolerance_mass(_open) */
   int32_t precursor_mode;     /* ASL_TOL_DA / ASL_TOL_PPM / ASL_TOL_INTERVAL */
-  double fragment_mz_tolerance;
-  int32_t allow_shift;        /* config.allow_peak_shifts */
+  double fragment_mz_tolerance; /* Da, or ppm of the query peak with ASL_SCORE_FRAGMENT_PPM */
+  int32_t allow_shift;        /* flag word: ASL_SCORE_SHIFT (config.allow_peak_shifts) | ASL_SCORE_FRAGMENT_PPM */
   int32_t use_ann;            /* 1: ANN top-k AND window (open+ann); 0: window only (std / bf) */
   /* The queries' intervals, [nq, 2] (lo, hi), host or device memory: read only when precursor_mode ==
    * ASL_TOL_INTERVAL (NULL is then ASL_ERR_INVALID; precursor_tol is unread). A host array is copied before
