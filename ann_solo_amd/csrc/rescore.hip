@@ -1587,6 +1587,7 @@ int rescore_device(const RescoreRequest &rq) {
   const DevPeaks &Q = rq.Q, &L = rq.L;
   const CandList &cand = rq.cand;
   const PrecFilter &filter = rq.filter;
+  const BatchOut &out = rq.out;
   const int nq = Q.n, n_best = rq.n_best;
   if (nq == 0) return ASL_OK;
   if (!rq.scratch) return fail(ASL_ERR_INVALID, "rescore: no scratch (internal)");
@@ -1653,11 +1654,11 @@ int rescore_device(const RescoreRequest &rq) {
     }
     ASL_CHECK_LAUNCH();
     if (n_best > 0) {
-      ASL_TRY(rescore_select_ranked(cv, nq, n_best, rq.pair_score, rq.tie_by_row, rq.group, (int)L.n, rq.best_cand,
-                                    rq.best_slot, rq.best_score, rq.n_valid));
+      ASL_TRY(rescore_select_ranked(cv, nq, n_best, rq.pair_score, rq.tie_by_row, rq.group, (int)L.n, out.best_cand,
+                                    rq.best_slot, out.best_score, out.n_cand));
     } else {
       hipLaunchKernelGGL(rescore_argmax_kernel, dim3(nq), dim3(64), 0, stream(), cv, nq,
-                         rq.pair_score, rq.tie_by_row, rq.best_cand, rq.best_slot, rq.best_score, rq.n_valid);
+                         rq.pair_score, rq.tie_by_row, out.best_cand, rq.best_slot, out.best_score, out.n_cand);
       ASL_CHECK_LAUNCH();
     }
   }
@@ -1668,11 +1669,11 @@ int rescore_device(const RescoreRequest &rq) {
     ASL_TRY(m_defer.reserve((size_t)nw));
     hipLaunchKernelGGL(rescore_matches_kernel<true>, dim3((unsigned)cdiv(nw, RS_WAVES)),
                        dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, n, rq.best_slot, tol,
-                       ppm, rq.allow_shift, rq.pm_count, rq.pm_pairs, rq.pm_stride, rq.best_row, rq.status, m_defer.p);
+                       ppm, rq.allow_shift, out.pm_count, out.pm_pairs, out.pm_stride, out.best_row, rq.status, m_defer.p);
     ASL_CHECK_LAUNCH();
     hipLaunchKernelGGL(rescore_matches_kernel<false>, dim3((unsigned)cdiv(nw, RS_MF_GROUP * RS_WAVES)),
                        dim3(64 * RS_WAVES), 0, stream(), Q, L, cv, nq, n, rq.best_slot, tol,
-                       ppm, rq.allow_shift, rq.pm_count, rq.pm_pairs, rq.pm_stride, rq.best_row, rq.status, m_defer.p);
+                       ppm, rq.allow_shift, out.pm_count, out.pm_pairs, out.pm_stride, out.best_row, rq.status, m_defer.p);
     ASL_CHECK_LAUNCH();
   }
   return ASL_OK;
@@ -1742,13 +1743,9 @@ static int rescore_batch_sync(const asl_peaks_t *queries, const asl_peaks_t *lib
   ASL_TRY(rows.init(cand_rows, (size_t)total));
   In<int32_t> grp;
   if (lib_group) ASL_TRY(grp.init(lib_group, (size_t)library->n));
-  Out<int32_t> o_best, o_cnt;
-  Out<double> o_score;
-  Out<uint32_t> o_pairs;
-  ASL_TRY(o_best.init(best_cand, nw));
-  ASL_TRY(o_score.init(best_score, nw));
-  ASL_TRY(o_cnt.init(pm_count, nw));
-  ASL_TRY(o_pairs.init(pm_pairs, nw * (pm_pairs ? pm_stride : 0) * 2));
+  BatchOutStage o;
+  ASL_TRY(o.init({.best_cand = best_cand, .best_score = best_score, .pm_count = pm_count, .pm_pairs = pm_pairs,
+                  .pm_stride = pm_stride}, (size_t)nq, nw));
   DevBuf<double> pair_score;
   DevBuf<long long> best_slot;
   DevBuf<int> status;
@@ -1761,13 +1758,8 @@ static int rescore_batch_sync(const asl_peaks_t *queries, const asl_peaks_t *lib
                           .tol = tol, .tol_ppm = sf.tol_ppm, .allow_shift = sf.allow_shift, .n_best = n_best,
                           .group = lib_group ? grp.d : nullptr,
                           .pair_score = pair_score.p, .best_slot = best_slot.p, .scratch = &scratch,
-                          .status = status.p,
-                          .best_cand = o_best.d, .best_score = o_score.d,
-                          .pm_count = o_cnt.d, .pm_pairs = o_pairs.d, .pm_stride = pm_stride}));
-  ASL_TRY(o_best.finish());
-  ASL_TRY(o_score.finish());
-  ASL_TRY(o_cnt.finish());
-  ASL_TRY(o_pairs.finish());
+                          .status = status.p, .out = o.dev}));
+  ASL_TRY(o.finish());
   return rescore_check_status(status.p);  // synchronises
 }
 

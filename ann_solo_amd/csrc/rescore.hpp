@@ -1,4 +1,5 @@
-// rescore.hpp -- interface of the rescoring driver (rescore.hip) shared with search.hip.
+// rescore.hpp -- interface of the rescoring driver (rescore.hip): the request, the kernel-argument
+// structs and the output staging that window_search.hip and search.hip (through library.hpp) share with it.
 #pragma once
 #include "common.hpp"
 
@@ -109,6 +110,45 @@ struct CandList {
   const WindowRows *window = nullptr;
 };
 
+// Where the results go, one entry per winner (any may be null). The caller's pointers, host or device, at
+// an entry point; device pointers from BatchOutStage on and in a RescoreRequest.
+struct BatchOut {
+  int32_t *best_row = nullptr;          // the winner's library row (-1: none)
+  int32_t *best_cand = nullptr;         // its position in its query's list (-1: none)
+  double *best_score = nullptr;
+  int32_t *n_cand = nullptr;            // [nq] candidates of the query that were scored
+  int32_t *pm_count = nullptr;          // the winner's peak matches in greedy order: their number,
+  uint32_t *pm_pairs = nullptr;         // (query peak, library peak) pairs [pm_stride, 2]
+  int32_t pm_stride = 0;
+};
+
+// Stages a caller's BatchOut for nq queries and nw winners: kernels write to `dev`, finish() enqueues the
+// copies back to whatever lives on the host (the caller synchronises once at the end).
+struct BatchOutStage {
+  Out<int32_t> row, cand, n_cand, count;
+  Out<double> score;
+  Out<uint32_t> pairs;
+  BatchOut dev;
+  int init(const BatchOut &o, size_t nq, size_t nw) {
+    ASL_TRY(row.init(o.best_row, nw));
+    ASL_TRY(cand.init(o.best_cand, nw));
+    ASL_TRY(score.init(o.best_score, nw));
+    ASL_TRY(n_cand.init(o.n_cand, nq));
+    ASL_TRY(count.init(o.pm_count, nw));
+    ASL_TRY(pairs.init(o.pm_pairs, nw * (o.pm_pairs ? o.pm_stride : 0) * 2));
+    dev = {row.d, cand.d, score.d, n_cand.d, count.d, pairs.d, o.pm_stride};
+    return ASL_OK;
+  }
+  int finish() {
+    ASL_TRY(row.finish());
+    ASL_TRY(cand.finish());
+    ASL_TRY(score.finish());
+    ASL_TRY(n_cand.finish());
+    ASL_TRY(count.finish());
+    return pairs.finish();
+  }
+};
+
 // One call of the rescoring driver (rescore_device). All pointers are device pointers.
 struct RescoreRequest {
   // -- spectra
@@ -123,9 +163,9 @@ struct RescoreRequest {
   PrecFilter filter;                    // precursor window applied to the slots (default: none)
   // -- selection
   // 0: the single winner (rescore_argmax_kernel). 1..ASL_MAX_BEST (asl_*_topn): the n best slots per
-  // query (rescore_topn_kernel, the matches kernel over nq * n winners); best_slot / best_cand /
+  // query (rescore_topn_kernel, the matches kernel over nq * n winners); best_slot and out's best_cand /
   // best_row / best_score / pm_count are then [nq, n_best], pm_pairs [nq, n_best, pm_stride, 2],
-  // n_valid stays [nq]
+  // n_cand stays [nq]
   int n_best = 0;
   // n_best > 0, non-null (asl_*_topn_distinct): group id of every library row, [L.n]; the ranks then
   // hold distinct groups. nullptr: plain ranks
@@ -136,14 +176,8 @@ struct RescoreRequest {
   RescoreScratch *scratch = nullptr;    // required
   int *status = nullptr;                // RS_STATUS_* flags, or-ed in (rescore_check_status)
   bool clear_status = true;             // zero the flags first
-  // -- outputs (one per winner; any may be null)
-  int32_t *best_cand = nullptr;         // the winner's position in its query's list (-1: none)
-  int32_t *best_row = nullptr;          // its library row (-1: none)
-  double *best_score = nullptr;
-  int32_t *n_valid = nullptr;           // [nq] candidates of the query that were scored
-  int32_t *pm_count = nullptr;          // the winner's peak matches in greedy order: their number,
-  uint32_t *pm_pairs = nullptr;         // (query peak, library peak) pairs [pm_stride, 2]
-  int32_t pm_stride = 0;
+  // -- outputs
+  BatchOut out;
   bool emit_matches = true;             // false: stop after the selection (no best_row, pm_count, pm_pairs written)
 };
 

@@ -1,5 +1,5 @@
 // rescore_cand.hpp -- what the two rescoring units share (rescore.hip: scoring, single winner, peak
-// matches; rescore_rank.hip: ranked selection, window fold). Internal: search.hip sees rescore.hpp only.
+// matches; rescore_rank.hip: ranked selection, window fold). Internal: the search units see rescore.hpp only.
 #pragma once
 #include "rescore.hpp"
 

@@ -1,6 +1,6 @@
 // rescore_rank.hip -- the ranked side of the rescoring: selection of the n best slots per query
 // (asl_*_topn, asl_*_topn_distinct; rescore_device's pass 2 when n_best > 0) and the fold of a tiled
-// window search's per-tile winners into the running ones (search.hip: window_search_device).
+// window search's per-tile winners into the running ones (window_search.hip: window_search_device).
 // Scoring, the single-winner argmax and the peak matches are in rescore.hip.
 #include "common.hpp"
 #include "rescore_cand.hpp"
@@ -175,7 +175,7 @@ int rescore_select_ranked(const CandView &cv, int nq, int n, const double *pair_
   return ASL_OK;
 }
 
-// Tiled window search (search.hip): the fold of one tile, one thread per query of the tile. Each
+// Tiled window search (window_search.hip): the fold of one tile, one thread per query of the tile. Each
 // query's tiles are folded in stream order, so the running list needs no atomics. The tile's n best
 // (slots, scores: the selection above or the argmax, sorted) and the running n best of the query
 // (rows, scores, sorted, row -1 beyond the filled ranks) are two sorted lists of at most n over
