@@ -47,6 +47,7 @@ constexpr int V3_CHUNK = 256;   // tile-table entries per chunk
 // they come from DRAM).
 constexpr int V3_DEPTH = 1;     // rounds of tiles in flight ahead of the one being scored
 constexpr int V3_NT = 0;        // 1: non-temporal loads of the codes (streamed once per query)
+constexpr int V3_AHEAD = 8;     // tile_adc: LUT reads in flight ahead of the first-level adds (8: all 32; pq_tile.hpp)
 constexpr int V3_WAVES_PER_SIMD = 6;   // occupancy the 2048-key instantiation is compiled for (3 workgroups per CU)
 
 template <int NT_>
@@ -333,7 +334,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
       if (i + DEPTH * NW < nent)
         fetch(i + DEPTH * NW, A[(s + DEPTH) % NS], B[(s + DEPTH) % NS], e[(s + DEPTH) % NS]);
       flag_u = __builtin_amdgcn_readfirstlane(fl);
-      p_score = e[s].coarse + tile_adc(lut_bytes, A[s], B[s], offA, offB);
+      p_score = e[s].coarse + tile_adc<V3_AHEAD>(lut_bytes, A[s], B[s], offA, offB);
       p_tile_nv = e[s].tile_nv;
       if constexpr (RANGED) p_first = e[s].first;
       if constexpr (SEL) p_sel = e[s].sel;

@@ -22,35 +22,62 @@ __device__ __forceinline__ float dpp_mov(float x) {
       float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
 }
 
-__device__ __forceinline__ float lut_at(const char *lut_bytes, uint32_t word, int byte_idx,
-                                        uint32_t lane_off) {
-  uint32_t c = (word >> (8 * byte_idx)) & 0xffu;
-  // keep the byte a value of its own: otherwise byte 0 is rewritten to (word << 7) & 0x7f80 and
-  // costs three VALU instructions (shift, and, add) instead of two (and / bfe, lshl_add)
-  asm volatile("" : "+v"(c));
-  return *reinterpret_cast<const float *>(lut_bytes + ((c << 7) + lane_off));
-}
-
 typedef float pqt_f2 __attribute__((ext_vector_type(2)));
 
+// The table entries lut[c * 32 + m] of two neighbouring code bytes of word (bytes 2 * half and 2 * half + 1).
+// lane_at: the LDS address of lut[m], as the bits of a float.
+// The address c * 128 + lane_at is made by the FLOAT unit, from two full-rate instructions per look-up: a mask
+// (byte 3: a shift) and one v_fma_f32. By profiles/pq_adc_addr_issue_rate.txt v_lshl_add_u32, v_bfe_u32,
+// v_and_or_b32, v_bfi_b32, v_mad_u32_u24, the SDWA shifts and v_cvt_f32_ubyteN all issue at about half the rate
+// of v_and_b32, v_lshrrev_b32 and v_fma_f32. A bit pattern p below 2^24 is, read as a float, exactly
+// p * 2^-149 (a denormal, or a normal of the first binade, which has the same spacing). So with the byte left
+// where it stands, p = c << (8 * i), fma(p, 2^(7 - 8 * i), lane_at) is (c * 128 + lane_at) * 2^-149 without
+// rounding -- product and sum are integers below 2^23 in that unit -- and its bit pattern is the address.
+// This needs fp32 denormals on (FP_DENORM mode 3, what hipcc compiles kernels for unless asked to flush them);
+// v_fma_f32 handles them at full rate. With denormals flushed every look-up would read lut[0], inside the table
+// but wrong: tests/test_gpu_pq_adc_address.py compares every byte value at every position.
+__device__ __forceinline__ pqt_f2 lut_at2(uint32_t word, int half, float lane_at) {
+  typedef const __attribute__((address_space(3))) float *lds_f;
+  const uint32_t p0 = half == 0 ? word & 0xffu : word & 0xff0000u;
+  const uint32_t p1 = half == 0 ? word & 0xff00u : word >> 24;
+  const float a0 = __builtin_fmaf(__builtin_bit_cast(float, p0), half == 0 ? 128.0f : 0x1p-9f, lane_at);
+  const float a1 = __builtin_fmaf(__builtin_bit_cast(float, p1), half == 0 ? 0.5f : 128.0f, lane_at);
+  pqt_f2 r;
+  r.x = *(lds_f)(uintptr_t)__builtin_bit_cast(uint32_t, a0);
+  r.y = *(lds_f)(uintptr_t)__builtin_bit_cast(uint32_t, a1);
+  return r;
+}
+
 // 64 ADC sums of one tile: lane l returns the sum of vector l (without the coarse term).
+// AHEAD: groups of four look-ups whose reads are issued ahead of a group's add. 0: read, wait, add, group by
+// group, the fewest registers (rank_scan.hip: 55 VGPRs, eight waves per SIMD). From 1 on the compiler issues all
+// 32 reads before the first wait and adds as they arrive (pq_scan_v3.hip: 3 to 8 more VGPRs, all within the six
+// waves per SIMD its LDS allows; profiles/pq_adc_addr_ab.txt).
+template <int AHEAD = 0>
 __device__ __forceinline__ float tile_adc(const char *lut_bytes, const uint4 A, const uint4 B,
-                                          uint32_t offA, uint32_t offB) {
+                                          uint32_t offA_u, uint32_t offB_u) {
+  // the table's LDS address goes into the lane constant: the address register is all a read needs
+  const uint32_t lut0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)lut_bytes;
+  const float offA = __builtin_bit_cast(float, lut0 + offA_u), offB = __builtin_bit_cast(float, lut0 + offB_u);
   float v[16];
   const uint32_t a[4] = {A.x, A.y, A.z, A.w};
   const uint32_t b[4] = {B.x, B.y, B.z, B.w};
   // the 16 first-level sums as 8 packed fp32 adds (v_pk_add_f32: two IEEE adds per instruction,
   // same bits); the DPP butterflies below have no packed form
+  pqt_f2 x[8], y[8];
+  auto issue = [&](int g) {
+    x[g] = lut_at2(a[g >> 1], g & 1, offA);   // v[2 g], v[2 g + 1]: bytes 2 g and 2 g + 1 of the 16
+    y[g] = lut_at2(b[g >> 1], g & 1, offB);
+  };
 #pragma unroll
-  for (int r = 0; r < 16; r += 2) {
-    pqt_f2 x, y;
-    x.x = lut_at(lut_bytes, a[r >> 2], r & 3, offA);
-    x.y = lut_at(lut_bytes, a[(r + 1) >> 2], (r + 1) & 3, offA);
-    y.x = lut_at(lut_bytes, b[r >> 2], r & 3, offB);
-    y.y = lut_at(lut_bytes, b[(r + 1) >> 2], (r + 1) & 3, offB);
-    const pqt_f2 z = x + y;
-    v[r] = z.x;
-    v[r + 1] = z.y;
+  for (int g = 0; g < AHEAD && g < 8; ++g) issue(g);
+#pragma unroll
+  for (int g = 0; g < 8; ++g) {
+    if (g + AHEAD < 8) issue(g + AHEAD);
+    const pqt_f2 z = x[g] + y[g];
+    v[2 * g] = z.x;
+    v[2 * g + 1] = z.y;
+    if (AHEAD == 0) __builtin_amdgcn_sched_barrier(0);   // keeps the groups apart: short live ranges
   }
 #pragma unroll
   for (int r = 0; r < 8; ++r) v[r] = v[r] + dpp_mov<0x140>(v[r ^ 15]);   // row_mirror

@@ -1,5 +1,6 @@
 // Issue rate of wave64 vector instructions: what one SIMD sustains at W waves per SIMD, and what the profiler's
-// VALU counters say of a kernel that does nothing else (profiles/pq_mmajor_before.txt).
+// VALU counters say of a kernel that does nothing else (profiles/pq_mmajor_before.txt); and the prices of what a look-up
+// address of the PQ scan can be made of (profiles/pq_adc_addr_issue_rate.txt).
 //   hipcc -O3 --offload-arch=gfx950 -o valu_issue_rate scripts/valu_issue_rate.hip && ./valu_issue_rate
 //   rocprofv3 --pmc VALUBusy SQ_INSTS_VALU SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE -- ./valu_issue_rate
 // Workgroups of 4 waves (one per SIMD); the LDS size keeps exactly W of them on a CU. Per wave: s_memtime ticks
@@ -18,6 +19,13 @@ __global__ void k(float *out, long long *ticks, float seed) {
   float a[UNR];
   for (int i = 0; i < UNR; i++) a[i] = seed + threadIdx.x * 0.001f + i;
   const float b = seed * 0.5f, c = seed * 0.25f;
+  float one = seed, tiny = seed * 0x1p-142f;
+  asm volatile("" : "+v"(one), "+v"(tiny));
+  if (KIND == 23 || KIND == 26)   // denormal accumulators: they stay below 2^23 ulps over the whole loop
+    for (int i = 0; i < UNR; i++) a[i] = __int_as_float((int)(threadIdx.x & 127) + i);
+  int v7 = 7;
+  asm volatile("" : "+v"(v7));
+  int smask = __builtin_amdgcn_readfirstlane(0x7f80 + (int)seed - 1);   // a mask in a scalar register
   __syncthreads();
   const long long t0 = __builtin_readcyclecounter();
   for (int it = 0; it < ITER; it++) {
@@ -29,6 +37,29 @@ __global__ void k(float *out, long long *ticks, float seed) {
       if (KIND == 3) asm volatile("v_lshl_add_u32 %0, %0, 7, %1" : "+v"(a[i]) : "v"(b));
       if (KIND == 4) asm volatile("v_and_b32 %0, 0xff, %0" : "+v"(a[i]));
       if (KIND == 5) asm volatile("v_bfe_u32 %0, %0, 8, 8" : "+v"(a[i]));
+      // what a cheaper look-up address could be made of (profiles/pq_adc_addr_issue_rate.txt); v7 holds 7
+      if (KIND == 6) asm volatile("v_lshlrev_b32_sdwa %0, %1, %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "+v"(a[i]) : "v"(v7));
+      if (KIND == 7) asm volatile("v_lshlrev_b32_sdwa %0, %1, %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "+v"(a[i]) : "v"(v7));
+      if (KIND == 8) asm volatile("v_lshlrev_b32_sdwa %0, %1, %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "+v"(a[i]) : "v"(v7));
+      if (KIND == 9) asm volatile("v_lshlrev_b32_sdwa %0, %1, %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "+v"(a[i]) : "v"(v7));
+      if (KIND == 10) asm volatile("v_or_b32 %0, %0, %1" : "+v"(a[i]) : "v"(b));
+      if (KIND == 11) asm volatile("v_add_u32 %0, %0, %1" : "+v"(a[i]) : "v"(b));
+      if (KIND == 12) asm volatile("v_lshrrev_b32 %0, 1, %0" : "+v"(a[i]));
+      if (KIND == 13) asm volatile("v_and_or_b32 %0, %0, %1, %2" : "+v"(a[i]) : "v"(b), "v"(c));
+      if (KIND == 14) asm volatile("v_bfi_b32 %0, %1, %0, %2" : "+v"(a[i]) : "v"(b), "v"(c));
+      if (KIND == 15) asm volatile("v_perm_b32 %0, %0, %1, %2" : "+v"(a[i]) : "v"(b), "v"(c));
+      if (KIND == 16) asm volatile("v_mad_u32_u24 %0, %0, %1, %2" : "+v"(a[i]) : "v"(b), "v"(c));
+      if (KIND == 17) asm volatile("v_lshl_or_b32 %0, %0, 7, %1" : "+v"(a[i]) : "v"(b));
+      if (KIND == 18) asm volatile("v_and_or_b32 %0, %0, %1, %2" : "+v"(a[i]) : "s"(smask), "v"(c));
+      // the address as a denormal float: byte -> float, then fma(c, 2^-142, lane offset's bits) = bits c * 128 + offset
+      if (KIND == 20) asm volatile("v_cvt_f32_ubyte0 %0, %0" : "+v"(a[i]));
+      if (KIND == 21) asm volatile("v_cvt_f32_ubyte1 %0, %0" : "+v"(a[i]));
+      if (KIND == 22) asm volatile("v_cvt_f32_ubyte3 %0, %0" : "+v"(a[i]));
+      if (KIND == 23) asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(a[i]) : "v"(one), "v"(tiny));
+      if (KIND == 26) asm volatile("v_fmamk_f32 %0, %1, 0x80, %0" : "+v"(a[i]) : "v"(one));   // the same with 2^-142 as a literal
+      if (KIND == 24) asm volatile("v_lshlrev_b32 %0, 7, %0" : "+v"(a[i]));
+      if (KIND == 25) asm volatile("v_and_b32 %0, %1, %0" : "+v"(a[i]) : "s"(smask));
+      if (KIND == 19) asm volatile("v_mul_u32_u24_sdwa %0, %1, %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "+v"(a[i]) : "v"(v7));
     }
   }
   const long long t1 = __builtin_readcyclecounter();
@@ -79,7 +110,7 @@ static void run(const char *name, F kern, int W, float *out, long long *ticks) {
   double sum = 0; long long mx = 0;
   for (long long v : h) { sum += (double)v; if (v > mx) mx = v; }
   const double n = (double)ITER * UNR;
-  printf("%-14s W=%d  ticks/wave avg %.0f max %lld  -> ticks per instruction per SIMD %.3f   kernel %.3f ms -> ns per instruction per SIMD %.3f\n",
+  printf("%-16s W=%d  ticks/wave avg %.0f max %lld  -> ticks per instruction per SIMD %.3f   kernel %.3f ms -> ns per instruction per SIMD %.3f\n",
          name, W, sum / h.size(), mx, sum / h.size() / (n * W), ms, ms * 1e6 / (n * W));
 }
 
@@ -97,6 +128,27 @@ int main() {
     run("v_and_b32", k<4>, W, out, ticks);
     run("v_bfe_u32", k<5>, W, out, ticks);
     run("v_pk_add_f32", kpk<0>, W, out, ticks);
+    run("lshlrev_sdwa_b0", k<6>, W, out, ticks);
+    run("lshlrev_sdwa_b1", k<7>, W, out, ticks);
+    run("lshlrev_sdwa_b2", k<8>, W, out, ticks);
+    run("lshlrev_sdwa_b3", k<9>, W, out, ticks);
+    run("v_or_b32", k<10>, W, out, ticks);
+    run("v_add_u32", k<11>, W, out, ticks);
+    run("v_lshrrev_b32", k<12>, W, out, ticks);
+    run("v_and_or_b32", k<13>, W, out, ticks);
+    run("v_bfi_b32", k<14>, W, out, ticks);
+    run("v_perm_b32", k<15>, W, out, ticks);
+    run("v_mad_u32_u24", k<16>, W, out, ticks);
+    run("v_lshl_or_b32", k<17>, W, out, ticks);
+    run("and_or_sgpr", k<18>, W, out, ticks);
+    run("mul_u24_sdwa_b1", k<19>, W, out, ticks);
+    run("cvt_f32_ubyte0", k<20>, W, out, ticks);
+    run("cvt_f32_ubyte1", k<21>, W, out, ticks);
+    run("cvt_f32_ubyte3", k<22>, W, out, ticks);
+    run("fma_f32_denorm", k<23>, W, out, ticks);
+    run("fmamk_f32_denorm", k<26>, W, out, ticks);
+    run("v_lshlrev_b32", k<24>, W, out, ticks);
+    run("and_b32_sgpr", k<25>, W, out, ticks);
   }
   return 0;
 }
