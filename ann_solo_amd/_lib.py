@@ -24,6 +24,7 @@ c_u32p = C.POINTER(C.c_uint32)
 
 TK_MAX_K = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp)
 TK_MAX_K_PASSES = 16384   # largest k of a search (bounded passes beyond TK_MAX_K)
+SCORE_HIST_BINS = 128     # include/annsolo_mi.h: ASL_SCORE_HIST_BINS
 
 
 class AnnSoloMiError(RuntimeError):
@@ -86,6 +87,7 @@ EXPORTS = [
     'asl_rescore_knn_topn_distinct',
     'asl_profile_rescore_counts',
     'asl_library_set_selection', 'asl_index_set_selector', 'asl_index_search_selected',
+    'asl_rescore_batch_topn_hist', 'asl_search_batch_topn_hist', 'asl_rescore_knn_topn_hist',
 ]
 
 
@@ -273,6 +275,19 @@ def lib():
             L.asl_index_search_selected.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                                     C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                                     C.c_void_p]
+        if hasattr(L, 'asl_search_batch_topn_hist'):
+            L.asl_rescore_batch_topn_hist.argtypes = [C.POINTER(AslPeaks), C.POINTER(AslPeaks), C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int32,
+                                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_int32, C.c_void_p]
+            L.asl_search_batch_topn_hist.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(AslPeaks),
+                                                     C.POINTER(AslSearchParams), C.c_int32, C.c_int32, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                     C.c_void_p, C.c_void_p]
+            L.asl_rescore_knn_topn_hist.argtypes = [C.c_void_p, C.POINTER(AslPeaks),
+                                                    C.POINTER(AslSearchParams), C.c_void_p, C.c_int32, C.c_int32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_int32, C.c_void_p]
         if hasattr(L, 'asl_index_set_by_residual'):
             L.asl_index_set_by_residual.argtypes = [C.c_void_p, C.c_int32]
             L.asl_index_get_by_residual.argtypes = [C.c_void_p]

@@ -4,7 +4,7 @@
 (/root/reference/src/ann_solo/config.py:62-216) plus the ADDITIVE flags of this implementation
 (``index``, ``pq_m``, ``pq_bits``, ``refine_k``, ``kmeans_niter``, ``ann_seed``, ``num_gpus``,
 ``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``, ``pq_by_residual``,
-``precursor_window_open``, ``fragment_tolerance_unit``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``precursor_window_open``, ``fragment_tolerance_unit``, ``score_stats``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -100,6 +100,10 @@ class Config:
     # decoy annotation -- the reference's dot product reads the tolerance as Da whatever it says -- so
     # ``from_reference`` would pick its default up and change the results of every existing configuration.
     fragment_tolerance_unit: str = 'Da'
+    # every SSM also says how many candidates its query scored (n_scored) and how many of them were expected
+    # to score as high as the winner by chance (expect: a log-linear fit to the tail of the losers' score
+    # histogram, which the device counts; score_stats.py). Identifications, scores and files do not change
+    score_stats: bool = False
 
     MAX_PEAKS = 256      # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
@@ -141,6 +145,9 @@ class Config:
             raise ValueError(f"fragment_tolerance_unit = {self.fragment_tolerance_unit!r}: 'Da' or 'ppm'")
         if self.fragment_tolerance_unit == 'ppm' and self.num_gpus and int(self.num_gpus) > 1:
             raise ValueError("fragment_tolerance_unit = 'ppm' does not run on a sharded index (num_gpus > 1)")
+        self.score_stats = bool(self.score_stats)
+        if self.score_stats and self.num_gpus and int(self.num_gpus) > 1:
+            raise ValueError('score_stats does not run on a sharded index (num_gpus > 1)')
         if self.precursor_window_open is not None:
             try:
                 lo, hi = (float(v) for v in self.precursor_window_open)
@@ -277,3 +284,9 @@ def add_arguments(parser) -> None:
                              "runners-up are the best matches of other peptides and the score gap is "
                              'the gap to the next different identification; one GPU '
                              '(default: every library spectrum is a rank of its own)')
+    parser.add_argument('--score_stats', action='store_true', default=d.score_stats,
+                        help='every SSM also carries n_scored, the candidates its query scored, and expect, '
+                             "the number of them expected to reach the best match's score by chance (a "
+                             "log-linear fit to the tail of the query's score histogram; a descriptive "
+                             'statistic, not a calibrated p-value); identifications and scores do not change; '
+                             'the batches run synchronously; one GPU (default: off)')

@@ -1620,8 +1620,9 @@ int rescore_device(const RescoreRequest &rq) {
                           (cand.rows64 || cand.rows32);
       const int form = cand.window ? 3 : !shaped ? 0 : cand.rows64 ? 2 : 1;
       // Pruning (rescore_flat_kernel) is for the single winner, decided by the one block that sees all
-      // of a query's candidates: ranked requests and split lists never meet RS_PRUNED
-      const int prune = (n_best == 0 && ysplit == 1 && rescore_prune_enabled()) ? 1 : 0;
+      // of a query's candidates: ranked requests and split lists never meet RS_PRUNED. Nor does a request
+      // with a score histogram, whatever its selection: a pruned slot holds no score to count
+      const int prune = (n_best == 0 && ysplit == 1 && !out.score_hist && rescore_prune_enabled()) ? 1 : 0;
       unsigned long long *counts = prof_counts() ? prof_rescore_dev() : nullptr;
       // 1. flat kernel; 2. pair kernel over the work list of what it marked RS_DEFER; 3. binary-search
       // kernel on RS_DEFER_BS (its blocks return at once for queries without such slots)
@@ -1653,6 +1654,7 @@ int rescore_device(const RescoreRequest &rq) {
                          (const int *)q_defer.p, rq.status, bs_group);
     }
     ASL_CHECK_LAUNCH();
+    if (out.score_hist) ASL_TRY(rescore_hist(cv, nq, cand.total_slots, rq.pair_score, out.score_hist));
     if (n_best > 0) {
       ASL_TRY(rescore_select_ranked(cv, nq, n_best, rq.pair_score, rq.tie_by_row, rq.group, (int)L.n, out.best_cand,
                                     rq.best_slot, out.best_score, out.n_cand));
@@ -1714,7 +1716,7 @@ static int rescore_batch_sync(const asl_peaks_t *queries, const asl_peaks_t *lib
                               const int64_t *cand_rows, const int32_t *cand_offsets, double tol,
                               int score_flags, int n_best, int32_t *best_cand, double *best_score,
                               int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride,
-                              const int32_t *lib_group = nullptr) {
+                              const int32_t *lib_group = nullptr, int32_t *score_hist = nullptr) {
   if (!queries || !library) return fail(ASL_ERR_INVALID, "rescore_batch: null spectra");
   ScoreFlags sf;
   ASL_TRY(decode_score_flags(score_flags, "rescore_batch", sf));
@@ -1745,7 +1747,7 @@ static int rescore_batch_sync(const asl_peaks_t *queries, const asl_peaks_t *lib
   if (lib_group) ASL_TRY(grp.init(lib_group, (size_t)library->n));
   BatchOutStage o;
   ASL_TRY(o.init({.best_cand = best_cand, .best_score = best_score, .pm_count = pm_count, .pm_pairs = pm_pairs,
-                  .pm_stride = pm_stride}, (size_t)nq, nw));
+                  .pm_stride = pm_stride, .score_hist = score_hist}, (size_t)nq, nw));
   DevBuf<double> pair_score;
   DevBuf<long long> best_slot;
   DevBuf<int> status;
@@ -1798,4 +1800,19 @@ extern "C" int asl_rescore_batch_topn_distinct(const asl_peaks_t *queries, const
   if (!lib_group) return fail(ASL_ERR_INVALID, "rescore_batch_topn_distinct: null lib_group");
   return rescore_batch_sync(queries, library, cand_rows, cand_offsets, tol, allow_shift, n_best, best_cand,
                             best_score, pm_count, pm_pairs, pm_stride, lib_group);
+}
+
+extern "C" int asl_rescore_batch_topn_hist(const asl_peaks_t *queries, const asl_peaks_t *library,
+                                           const int64_t *cand_rows, const int32_t *cand_offsets,
+                                           const int32_t *lib_group, double tol, int allow_shift, int32_t n_best,
+                                           int32_t distinct, int32_t *best_cand, double *best_score,
+                                           int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride,
+                                           int32_t *score_hist) {
+  clear_error();
+  if (n_best < 1 || n_best > ASL_MAX_BEST)
+    return fail(ASL_ERR_INVALID, "rescore_batch_topn_hist: n_best must be in [1, %d]", ASL_MAX_BEST);
+  ASL_TRY(ensure_device());     // (no device: ASL_ERR_NO_DEVICE whatever else was passed)
+  if (distinct && !lib_group) return fail(ASL_ERR_STATE, "rescore_batch_topn_hist: distinct ranks without lib_group");
+  return rescore_batch_sync(queries, library, cand_rows, cand_offsets, tol, allow_shift, n_best, best_cand,
+                            best_score, pm_count, pm_pairs, pm_stride, distinct ? lib_group : nullptr, score_hist);
 }

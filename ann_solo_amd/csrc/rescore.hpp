@@ -120,6 +120,9 @@ struct BatchOut {
   int32_t *pm_count = nullptr;          // the winner's peak matches in greedy order: their number,
   uint32_t *pm_pairs = nullptr;         // (query peak, library peak) pairs [pm_stride, 2]
   int32_t pm_stride = 0;
+  // [nq, ASL_SCORE_HIST_BINS] histogram of the scores of the slots n_cand counts (asl_*_topn_hist). A rescoring
+  // pass ADDS into the rows (a tiled window search: one pass per tile); the entry point zeroes them once per batch
+  int32_t *score_hist = nullptr;
 };
 
 // Stages a caller's BatchOut for nq queries and nw winners: kernels write to `dev`, finish() enqueues the
@@ -128,6 +131,7 @@ struct BatchOutStage {
   Out<int32_t> row, cand, n_cand, count;
   Out<double> score;
   Out<uint32_t> pairs;
+  Out<int32_t> hist;
   BatchOut dev;
   int init(const BatchOut &o, size_t nq, size_t nw) {
     ASL_TRY(row.init(o.best_row, nw));
@@ -136,7 +140,10 @@ struct BatchOutStage {
     ASL_TRY(n_cand.init(o.n_cand, nq));
     ASL_TRY(count.init(o.pm_count, nw));
     ASL_TRY(pairs.init(o.pm_pairs, nw * (o.pm_pairs ? o.pm_stride : 0) * 2));
-    dev = {row.d, cand.d, score.d, n_cand.d, count.d, pairs.d, o.pm_stride};
+    ASL_TRY(hist.init(o.score_hist, nq * (size_t)ASL_SCORE_HIST_BINS));
+    dev = {row.d, cand.d, score.d, n_cand.d, count.d, pairs.d, o.pm_stride, hist.d};
+    // the rows are summed into: zeroed here, once per batch, so that queries without candidates read zero
+    if (hist.d) HIP_TRY(hipMemsetAsync(hist.d, 0, nq * (size_t)ASL_SCORE_HIST_BINS * sizeof(int32_t), stream()));
     return ASL_OK;
   }
   int finish() {
@@ -145,6 +152,7 @@ struct BatchOutStage {
     ASL_TRY(score.finish());
     ASL_TRY(n_cand.finish());
     ASL_TRY(count.finish());
+    ASL_TRY(hist.finish());
     return pairs.finish();
   }
 };

@@ -78,4 +78,8 @@ int rescore_select_ranked(const CandView &cv, int nq, int n, const double *pair_
                           const int32_t *group, int n_lib, int32_t *best_cand, long long *best_slot,
                           double *best_score, int32_t *n_valid);
 
+// The score histogram (rescore_hist.hip): rescore_device's pass after the scoring launches when the request
+// carries BatchOut::score_hist. Launches rescore_hist_kernel on the stream; ADDS into hist [nq, ASL_SCORE_HIST_BINS].
+int rescore_hist(const CandView &cv, int nq, int64_t total_slots, const double *pair_score, int32_t *hist);
+
 }  // namespace asl

@@ -113,8 +113,10 @@ static RescoreRequest rows_request(const SearchBatch &b, CandList cand) {
 }
 
 // the caller's outputs of the six entry points (library rows, no list positions)
-static BatchOut row_outputs(int32_t *row, double *score, int32_t *n_cand, int32_t *count, uint32_t *pairs, int32_t stride) {
-  return {.best_row = row, .best_score = score, .n_cand = n_cand, .pm_count = count, .pm_pairs = pairs, .pm_stride = stride};
+static BatchOut row_outputs(int32_t *row, double *score, int32_t *n_cand, int32_t *count, uint32_t *pairs, int32_t stride,
+                            int32_t *hist = nullptr) {
+  return {.best_row = row, .best_score = score, .n_cand = n_cand, .pm_count = count, .pm_pairs = pairs, .pm_stride = stride,
+          .score_hist = hist};
 }
 
 // The synchronous batch: every checked call but asl_search_batch in pipeline mode. The candidates are the
@@ -353,6 +355,26 @@ int asl_rescore_knn_topn_distinct(asl_library_t *L, const asl_peaks_t *queries, 
                                   int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride) {
   return checked_batch_sync("rescore_knn_topn_distinct", ENTRY_KNN | ENTRY_TOPN | ENTRY_DISTINCT, L, nullptr, queries, P,
                             n_best, row_outputs(best_row, best_score, n_cand, pm_count, pm_pairs, pm_stride), knn_I,
+                            nullptr);
+}
+
+// The ranked calls with the score histogram of every query's candidates (NULL: the plain calls, launch for launch).
+int asl_search_batch_topn_hist(asl_library_t *L, asl_index_t *idx, const asl_peaks_t *queries,
+                               const asl_search_params_t *P, int32_t n_best, int32_t distinct, int32_t *best_row,
+                               double *best_score, int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs,
+                               int32_t pm_stride, int64_t *knn_I, int32_t *score_hist) {
+  return checked_batch_sync("search_batch_topn_hist", ENTRY_TOPN | (distinct ? ENTRY_DISTINCT : 0), L, idx, queries, P,
+                            n_best, row_outputs(best_row, best_score, n_cand, pm_count, pm_pairs, pm_stride, score_hist),
+                            nullptr, knn_I);
+}
+
+int asl_rescore_knn_topn_hist(asl_library_t *L, const asl_peaks_t *queries, const asl_search_params_t *P,
+                              const int64_t *knn_I, int32_t n_best, int32_t distinct, int32_t *best_row,
+                              double *best_score, int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs,
+                              int32_t pm_stride, int32_t *score_hist) {
+  return checked_batch_sync("rescore_knn_topn_hist", ENTRY_KNN | ENTRY_TOPN | (distinct ? ENTRY_DISTINCT : 0), L, nullptr,
+                            queries, P, n_best,
+                            row_outputs(best_row, best_score, n_cand, pm_count, pm_pairs, pm_stride, score_hist), knn_I,
                             nullptr);
 }
 

@@ -195,7 +195,9 @@ int asl::window_search_device(const SearchBatch &b) {
     const int32_t *off = L->wtile.p + T.idx;
     win.begin = off + T.nq + 1;
     rt.cand = {.offsets = off, .total_slots = T.pairs, .window = &win};
-    rt.out = {.best_score = L->tile_score.p, .n_cand = L->tile_n.p};
+    // (the histogram: every tile's pass adds its part of the window into the rows of its queries)
+    rt.out = {.best_score = L->tile_score.p, .n_cand = L->tile_n.p,
+              .score_hist = out.score_hist ? out.score_hist + (size_t)T.qa * ASL_SCORE_HIST_BINS : nullptr};
     rt.emit_matches = false;
     ASL_TRY(rescore_device(rt));
     ASL_TRY(rescore_window_merge(rt.cand, T.nq, n, L->best_slot.p, L->tile_score.p, L->tile_n.p,
@@ -205,7 +207,7 @@ int asl::window_search_device(const SearchBatch &b) {
   // the running lists once more, as an n-candidate list per query (-1: an empty rank): the same
   // order comes out again, with rows and peak matches (n_best = 0: the one winner, by the argmax)
   // (distinct: every tile's ranks and the fold hold one row per group; these lists, already distinct, are
-  // ranked as they are)
+  // ranked as they are; the winners were counted with their tiles: no histogram here)
   rq.cand = {.rows32 = L->run_row.p, .stride = n, .total_slots = (int64_t)nw};
   rq.group = nullptr;
   rq.out = {.best_row = out.best_row, .best_score = L->tile_score.p, .pm_count = out.pm_count,

@@ -72,6 +72,9 @@ class TopnBatchResult:
     pm_count: np.ndarray            # [nq, n_best]
     pm_pairs: np.ndarray            # [nq, n_best, stride, 2]
     knn: Optional[np.ndarray] = None
+    # [nq, 128] int32: the histogram of every query's candidate scores (``score_hist=True``); its rows sum
+    # to n_candidates
+    score_hist: Optional[np.ndarray] = None
 
     def peak_matches(self, i, r=0) -> np.ndarray:
         return _to_np(self.pm_pairs[i, r, :int(self.pm_count[i, r])]).astype(np.int64)
@@ -615,13 +618,15 @@ class SpectralLibrary:
     def search_batch_topn(self, queries: PackedSpectra, charge: int, mode: str, n_best: int,
                           want_knn: bool = False, device_out: bool = False,
                           pm_stride: Optional[int] = None, distinct: bool = False,
-                          windows=None) -> Optional[TopnBatchResult]:
+                          windows=None, score_hist: bool = False) -> Optional[TopnBatchResult]:
         """``_search_batch_local`` for the ``n_best`` (1 .. 16) best library matches of every query
         (``asl_search_batch_topn``): every cascade level and index mode, on this GPU alone.
         Synchronous -- the call never joins the two-stream pipeline. Rank 0 (and ``n_candidates``,
         ``knn``) is what ``_search_batch_local`` returns, bit for bit. ``distinct``: one rank per
         group of ``set_match_groups`` (``asl_search_batch_topn_distinct``; an error without groups).
-        ``windows``: as in ``_search_batch``."""
+        ``windows``: as in ``_search_batch``. ``score_hist``: the result also carries the histogram of
+        every query's candidate scores, ``[nq, 128]`` int32 (``asl_search_batch_topn_hist``; 128 bins of
+        width 1/128, ``score_stats.bin_of``), whose rows sum to ``n_candidates``; nothing else changes."""
         d = getattr(self, '_dist', None)
         if d is not None and d.world > 1:
             raise ValueError('search_batch_topn does not run on a sharded index')
@@ -655,6 +660,13 @@ class SpectralLibrary:
                                  score_flags(cfg.allow_peak_shifts, cfg.fragment_tolerance_unit),
                                  int(use_ann))
         windows = self._interval_windows(P, windows, nq)
+        if score_hist:
+            hist = mk((nq, _lib.SCORE_HIST_BINS), xp.int32)
+            _lib.check(_lib.lib().asl_search_batch_topn_hist(
+                part.handle, idx._h if idx is not None else None, C.byref(_lib.peaks_struct(q)),
+                C.byref(P), n, int(bool(distinct)), _lib.ptr(best_row), _lib.ptr(best_score), _lib.ptr(n_cand),
+                _lib.ptr(pm_count), _lib.ptr(pm_pairs), stride, _lib.ptr(knn), _lib.ptr(hist)))
+            return TopnBatchResult(best_row, best_score, n_cand, pm_count, pm_pairs, knn, hist)
         call = _lib.lib().asl_search_batch_topn_distinct if distinct else _lib.lib().asl_search_batch_topn
         _lib.check(call(
             part.handle, idx._h if idx is not None else None, C.byref(_lib.peaks_struct(q)),
@@ -856,14 +868,15 @@ class SpectralLibrary:
         t_level = time.perf_counter()
         n_in = sum(len(r) for r in rows_by_charge.values())
         n_best = int(self.config.num_matches)
-        distinct = bool(self.config.distinct_matches)
+        distinct = bool(self.config.distinct_matches) and n_best > 1
+        stats = bool(getattr(self.config, 'score_stats', False))
         table = SSMTable(query_meta, library_meta, n_best - 1)
         # Phase 1 issues every batch of the level; on one GPU the open-search batches go through
         # the two-stream pipeline (front of batch i+1 under the scan of batch i, no host wait
         # between batches). Phase 2, after one synchronisation, scores the winners and files them.
         d = getattr(self, '_dist', None)
-        # (num_matches > 1: the top-n entry point is synchronous, the batches are not pipelined)
-        piped = (self.device.type == 'cuda' and (d is None or d.world == 1) and n_best == 1 and
+        # (num_matches > 1, score_stats: the top-n entry points are synchronous, the batches are not pipelined)
+        piped = (self.device.type == 'cuda' and (d is None or d.world == 1) and n_best == 1 and not stats and
                  not getattr(self, '_pipeline_on', False) and getattr(self, 'pipeline_cascade', True) and
                  any(self._uses_ann(z, mode) for z in rows_by_charge))
         if piped:
@@ -883,7 +896,13 @@ class SpectralLibrary:
                     whole = len(sel) == qs.n and sel[0] == 0 and sel[-1] == qs.n - 1
                     q = (qs if whole else qs.select(torch.as_tensor(sel))).to(self.device)
                     win = None if level_win is None else level_win[sel]
-                    if n_best > 1:      # rank 0 goes the single winner's way, the rest rides along
+                    if stats:           # the histogram call, at num_matches = 1 too
+                        top = self.search_batch_topn(q, charge, mode, n_best, device_out=True,
+                                                     distinct=distinct, windows=win, score_hist=True)
+                        res = None if top is None else top.rank0()
+                        if res is not None:
+                            res.topn = top
+                    elif n_best > 1:    # rank 0 goes the single winner's way, the rest rides along
                         top = self.search_batch_topn(q, charge, mode, n_best, device_out=True,
                                                      distinct=distinct, windows=win)
                         res = None if top is None else top.rank0()
@@ -1002,7 +1021,13 @@ class SSMTable:
     With ``distinct_matches`` the ranks are distinct identifications: ``alt_lib_row`` / ``alt_score``
     / ``alt_peak_matches`` name the best library spectrum of each of the next ``n_alt`` OTHER
     peptides (never another spectrum of the winner's or of an earlier runner-up's peptide), and
-    ``delta_score`` is the gap to the best match of a different peptide."""
+    ``delta_score`` is the gap to the best match of a different peptide.
+
+    With ``score_stats`` every match carries ``n_scored[len]``, the candidates its query scored, and
+    ``expect[len]``, how many of them were expected to score at least as high as the match by chance
+    (``score_stats.expect_value`` over the batch's score histograms; NaN where no tail could be fitted:
+    fewer than 10 losers, fewer than 3 fit points, a slope that is not negative). Without the option
+    the columns hold 0 and NaN."""
 
     def __init__(self, query_meta, library_meta, n_alt: int = 0):
         self.query_meta, self.library_meta = query_meta, library_meta
@@ -1010,6 +1035,8 @@ class SSMTable:
         self.alt_lib_row = np.zeros((0, self.n_alt), np.int32)
         self.alt_score = np.zeros((0, self.n_alt), np.float64)
         self.delta_score = np.zeros(0, np.float64)
+        self.n_scored = np.zeros(0, np.int32)
+        self.expect = np.zeros(0, np.float64)
         self._alt_batches: list = []             # per batch: its TopnBatchResult (None: single winner)
         self.charge = np.zeros(0, np.int32)
         self.qrow = np.zeros(0, np.int64)
@@ -1037,6 +1064,14 @@ class SSMTable:
         self.alt_lib_row = np.concatenate([self.alt_lib_row, alt_row])
         self.alt_score = np.concatenate([self.alt_score, alt_score])
         self.delta_score = np.concatenate([self.delta_score, delta])
+        n_scored, expect = np.zeros(len(hit), np.int32), np.full(len(hit), np.nan)
+        if top is not None and getattr(top, 'score_hist', None) is not None:
+            from . import score_stats
+            best = _to_np(top.best_score)[hit, 0]
+            n_scored = _to_np(top.n_candidates)[hit].astype(np.int32)
+            expect = score_stats.expect_value(score_stats.loser_hist(_to_np(top.score_hist)[hit], best), best)
+        self.n_scored = np.concatenate([self.n_scored, n_scored])
+        self.expect = np.concatenate([self.expect, expect])
         self._pending.append((np.full(len(hit), charge, np.int32), np.asarray(qrows, np.int64)[hit],
                               best_row[hit].astype(np.int32), np.asarray(score, np.float64)[hit],
                               np.full(len(hit), b, np.int32), hit.astype(np.int32)))
@@ -1063,7 +1098,7 @@ class SSMTable:
         out = SSMTable(self.query_meta, self.library_meta, self.n_alt)
         out._batches, out._alt_batches = self._batches, self._alt_batches
         for name in ('charge', 'qrow', 'lib_row', 'score', 'q', 'batch', 'pos', 'alt_lib_row', 'alt_score',
-                     'delta_score'):
+                     'delta_score', 'n_scored', 'expect'):
             setattr(out, name, getattr(self, name)[idx])
         return out
 
@@ -1077,7 +1112,7 @@ class SSMTable:
             pad = ((0, 0), (0, out.n_alt - t.n_alt))
             out.alt_lib_row = np.concatenate([out.alt_lib_row, np.pad(t.alt_lib_row, pad, constant_values=-1)])
             out.alt_score = np.concatenate([out.alt_score, np.pad(t.alt_score, pad)])
-            for name in ('charge', 'qrow', 'lib_row', 'score', 'q', 'pos', 'delta_score'):
+            for name in ('charge', 'qrow', 'lib_row', 'score', 'q', 'pos', 'delta_score', 'n_scored', 'expect'):
                 setattr(out, name, np.concatenate([getattr(out, name), getattr(t, name)]))
             out.batch = np.concatenate([out.batch, t.batch + shift])
             shift += len(t._batches)
@@ -1171,7 +1206,8 @@ class SSMTable:
             lm['peptide'], qm['identifier'], qm['index'], lm['identifier'],
             qm.get('retention_time'), qm['precursor_charge'], qm['precursor_mz'],
             lm['precursor_mz'], lm.get('is_decoy', False), float(self.score[i]), float(self.q[i]),
-            self._peak_matches(i), float(self.delta_score[i]), self._alternatives(i))
+            self._peak_matches(i), float(self.delta_score[i]), self._alternatives(i),
+            int(self.n_scored[i]), float(self.expect[i]))
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))

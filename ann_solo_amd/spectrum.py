@@ -144,6 +144,11 @@ class SpectrumSpectrumMatch:
     # (library_identifier, shifted-dot score, peak_matches[n, 2])
     delta_score: float = float('nan')
     alternatives: tuple = ()
+    # score_stats: the candidates the query scored and how many of them were expected to score at least as
+    # high as this match by chance (score_stats.expect_value; NaN where no tail could be fitted); 0 / NaN
+    # without the option
+    n_scored: int = 0
+    expect: float = float('nan')
 
 
 def ssms_from_batch(result, query_meta, library_meta, scores=None, q_values=None

@@ -540,6 +540,33 @@ int asl_rescore_batch_topn_distinct(const asl_peaks_t *queries, const asl_peaks_
                                     int32_t *best_cand, double *best_score, int32_t *pm_count,
                                     uint32_t *pm_pairs, int32_t pm_stride);
 
+/* SCORE HISTOGRAM: the ranked calls keep the n best scores of a query and drop the rest; the *_hist
+ * calls also say how ALL of the query's scored candidates are distributed, which is what tells a
+ * winner among 160 candidates from one among 350 000 (ann_solo_amd/score_stats.py fits an expectation
+ * value to it). score_hist is [nq, ASL_SCORE_HIST_BINS] int32, host or device memory, every element
+ * written: ASL_SCORE_HIST_BINS bins of width 1/128 over [0, 1], lower edges inclusive; a candidate
+ * with exact score s (the double the ranks report, s >= 0) is counted in bin
+ *   !(s < 1.0) ? ASL_SCORE_HIST_BINS - 1 : (int)(s * 128.0)
+ * (the product is exact, so this is floor(128 s); everything at or above 1 is in the top bin).
+ * Counted are exactly the slots n_cand counts -- valid entries that pass the filter and the
+ * selection; a row listed twice counts twice, an entry below 0 never -- so sum(score_hist[q]) ==
+ * n_cand[q] for every query, on every path, at any pair budget; a query without candidates reads all
+ * zero. The histogram does not depend on n_best or distinct. Counts are integers summed with integer
+ * adds: the result does not depend on any order.
+ * asl_rescore_batch_topn_hist is asl_rescore_batch_topn (distinct == 0; lib_group is not read) or
+ * asl_rescore_batch_topn_distinct (distinct != 0; lib_group == NULL is then ASL_ERR_STATE) with the
+ * histogram added. score_hist == NULL: exactly those calls, launch for launch and bit for bit; with the
+ * pointer set every other output is unchanged. n_best as in asl_rescore_batch_topn (n_best = 1: the
+ * single winner); synchronous. */
+#define ASL_SCORE_HIST_BINS 128
+int asl_rescore_batch_topn_hist(const asl_peaks_t *queries, const asl_peaks_t *library,
+                                const int64_t *cand_rows, const int32_t *cand_offsets,
+                                const int32_t *lib_group /* [library->n], read when distinct */,
+                                double fragment_mz_tolerance, int allow_shift, int32_t n_best,
+                                int32_t distinct, int32_t *best_cand, double *best_score,
+                                int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride,
+                                int32_t *score_hist /* [nq, ASL_SCORE_HIST_BINS] or NULL */);
+
 /* ------------------------------------------------------------------ peak preprocessing
  * Replaces process_spectrum (src/ann_solo/spectrum.py:57-119: spectrum_utils set_mz_range,
  * round(resolution,'sum'), remove_precursor_peak(tol,'Da',2), filter_intensity,
@@ -725,6 +752,26 @@ int asl_rescore_knn_topn_distinct(asl_library_t *lib, const asl_peaks_t *queries
                                   int32_t n_best, int32_t *best_row, double *best_score,
                                   int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs,
                                   int32_t pm_stride);
+
+/* asl_search_batch_topn / asl_rescore_knn_topn (distinct == 0) or their _distinct forms (distinct != 0;
+ * without a group column: ASL_ERR_STATE) with the score histogram of asl_rescore_batch_topn_hist:
+ * score_hist [nq, ASL_SCORE_HIST_BINS], host or device, sum(score_hist[q]) == n_cand[q]. NULL: exactly
+ * the plain calls, launch for launch; with the pointer set every other output is unchanged. Every mode
+ * of asl_search_batch_topn is covered: any index kind, the scan-side post-filter on or off, the window
+ * scan, use_ann = 0 at any pair budget (every tile's pass adds its part of a query's window into the
+ * query's row; the final pass over the running winners counts nothing), a library selection,
+ * ASL_TOL_INTERVAL and ASL_SCORE_FRAGMENT_PPM. n_best = 1 is the single winner (column 0 equals
+ * asl_search_batch's outputs). Synchronous and not pipelined, same argument contract as the plain calls. */
+int asl_search_batch_topn_hist(asl_library_t *lib, asl_index_t *idx, const asl_peaks_t *queries,
+                               const asl_search_params_t *params, int32_t n_best, int32_t distinct,
+                               int32_t *best_row, double *best_score, int32_t *n_cand,
+                               int32_t *pm_count, uint32_t *pm_pairs, int32_t pm_stride,
+                               int64_t *knn_I, int32_t *score_hist);
+int asl_rescore_knn_topn_hist(asl_library_t *lib, const asl_peaks_t *queries,
+                              const asl_search_params_t *params, const int64_t *knn_I,
+                              int32_t n_best, int32_t distinct, int32_t *best_row, double *best_score,
+                              int32_t *n_cand, int32_t *pm_count, uint32_t *pm_pairs,
+                              int32_t pm_stride, int32_t *score_hist);
 
 /* Precursor-window candidate generation alone (spectral_library.py:417-429):
  * CSR lists of library rows (ascending) whose precursor passes the window. Two-call
