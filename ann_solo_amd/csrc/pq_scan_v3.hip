@@ -46,8 +46,14 @@ constexpr int V3_CHUNK = 256;   // tile-table entries per chunk
 // profiles/r06_pq_beyond_llc_*: measured both where the codes sit in the Infinity Cache and where
 // they come from DRAM).
 constexpr int V3_DEPTH = 1;     // rounds of tiles in flight ahead of the one being scored
-constexpr int V3_NT = 0;        // 1: non-temporal loads of the codes (streamed once per query)
+constexpr int V3_NT = 0;        // 1: non-temporal loads of the codes (streamed once per query; MM: the buffer loads' nt bit)
 constexpr int V3_AHEAD = 8;     // tile_adc: LUT reads in flight ahead of the first-level adds (8: all 32; pq_tile.hpp)
+// MM: buffer offset of a lane whose sub-quantiser is dead. A raw buffer (no stride, no index) returns 0 for every
+// dword whose byte offset is not below the resource's num_records - 3 and sends no request for it; the resource of a
+// tile is smaller than 2^32 - 4096 bytes (32 * mm_plane < 2^32, a multiple of 4096), so the four dwords of a 16-byte
+// load at this offset -- 16-byte aligned, ...f0 to ...fc, no 32-bit wrap -- are all out of range, and with
+// num_records = 0 (a fetch past the end of a wave's share) so is every offset.
+constexpr uint32_t V3_MM_DEAD = 0xfffffff0u;
 constexpr int V3_WAVES_PER_SIMD = 6;   // occupancy the 2048-key instantiation is compiled for (3 workgroups per CU)
 
 template <int NT_>
@@ -99,8 +105,8 @@ static_assert(V3_CHUNK_RANGED * sizeof(TileEnt12) <= V3_CHUNK * sizeof(TileEnt8)
 // MM (the plain instantiations only; index_codes_mmajor): codes_tiled is the SUB-QUANTISER-MAJOR copy --
 // plane m, mm_plane bytes each, holds sub-quantiser m's 64 bytes of every tile, tile after tile, in the tile's
 // own row order and byte permutation -- so a 128-byte line holds one sub-quantiser only, and a lane whose
-// sub-quantiser has no non-zero query component (its LUT column is +0.0 whatever the code) does not load: its
-// register keeps whatever bytes it holds, and the sums are those of the tile-major scan bit for bit.
+// sub-quantiser has no non-zero query component (its LUT column is +0.0 whatever the code) fetches nothing: its
+// buffer load is out of range and returns zeros, and the sums are those of the tile-major scan bit for bit.
 template <int CAP, int T, int NW, int DEPTH, bool WIDE, bool RANGED = false, bool SEL = false, bool MM = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIMD : 4) : (CAP <= 2048 ? 3 : 1))) void pq_scan_v3_kernel(
     const float *__restrict__ xq, int d, const float *__restrict__ codebooks, int dsub,
@@ -198,9 +204,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
   const int ma = (rho & 1) ? j + 16 : j, mb = ma ^ 16;
   const uint32_t offA = (uint32_t)ma * 4u, offB = (uint32_t)mb * 4u;
   // lane part of a tile's two code loads: tile-major rho * 512 + m * 16; MM: plane m, row rho
-  const uint32_t chunkA = MM ? (uint32_t)ma * mm_plane + (uint32_t)(rho * 16) : (uint32_t)(rho * 512 + ma * 16);
-  const uint32_t chunkB = (uint32_t)mb * mm_plane + (uint32_t)(rho * 16);   // (MM only)
+  // MM: every lane issues both loads of a tile -- a load under `if (live)` leaves the number of loads in flight
+  // unknown to the compiler, which then waits for all of them right behind their issue, see the tile loop -- as
+  // buffer loads whose resource ends with the copy: a dead lane's offset lies beyond it, so the hardware returns
+  // zeros and fetches nothing. Its LUT column is +0.0 whatever the bytes. (32 * mm_plane < 2^32, index_codes_mmajor,
+  // a multiple of 4096: every live offset and the remaining size fit 32 bits, and V3_MM_DEAD is beyond any size.)
   const bool liveA = (live_u >> ma) & 1u, liveB = (live_u >> mb) & 1u;      // (MM only)
+  const uint32_t chunkA = MM ? (liveA ? (uint32_t)ma * mm_plane + (uint32_t)(rho * 16) : V3_MM_DEAD) : (uint32_t)(rho * 512 + ma * 16);
+  const uint32_t chunkB = liveB ? (uint32_t)mb * mm_plane + (uint32_t)(rho * 16) : V3_MM_DEAD;   // (MM only)
 
   // ---- free-running appends (HistTopK's free_* protocol, as in flat_scan.hip) -------------------
   // A wave walks its own share of a table chunk (entries wave, wave + NW, ...) with its own register
@@ -264,7 +275,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     // score, and the step is instantiated per set, so every register index is a compile-time constant.
     constexpr int NS = DEPTH + 1;
     uint4 A[NS], B[NS];
-    if constexpr (MM) {   // a lane that never loads still indexes the table: any bytes, but defined ones
+    if constexpr (MM) {   // (defined bytes in the sets of a wave that has no entry in this chunk)
 #pragma unroll
       for (int s = 0; s < NS; ++s) A[s] = B[s] = make_uint4(0u, 0u, 0u, 0u);
     }
@@ -274,7 +285,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
       uint32_t first;     // RANGED: first lane
       unsigned long long sel;   // SEL: the tile's selector word
     } e[NS];
-    auto fetch = [&](int i, uint4 &a, uint4 &b, Tile &en) {
+    // (real: false past the end of the wave's share, MM only -- the loads are issued all the same, of an empty
+    // resource: every lane out of range, nothing fetched)
+    auto fetch = [&](int i, uint4 &a, uint4 &b, Tile &en, bool real = true) {
       const Ent t = table[i];
       en.tile_nv = __builtin_amdgcn_readfirstlane(t.tile_nv);
       en.coarse = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t.coarse)));
@@ -284,11 +297,18 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
       // them as they are (scalar base + lane offset), no 64-bit lane addresses to keep or add up per tile
       // (the second chunk's offset is made here from the first: a lane constant less to keep)
       if constexpr (MM) {
-        const uint8_t *base = codes_tiled + (size_t)(en.tile_nv & 0x3ffffffu) * 64;
+        const uint32_t toff = (en.tile_nv & 0x3ffffffu) * 64u;
+        const uint8_t *base = codes_tiled + (size_t)toff;
         uint32_t offa = chunkA, offb = chunkB;   // (values of their own, as below: scalar base + 32-bit lane offset)
         asm volatile("" : "+v"(offa), "+v"(offb));
-        if (liveA) a = load_codes16<V3_NT>(base + offa);
-        if (liveB) b = load_codes16<V3_NT>(base + offb);
+        // (the resource: from the tile's first plane-0 byte to the end of the copy, raw, no stride)
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<uint8_t *>(base), 0, (int)(real ? (uint32_t)PQT_M * mm_plane - toff : 0u), 0x00020000);
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 va = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)offa, 0, V3_NT ? 2 : 0);   // (aux bit 1: nt)
+        const u32x4 vb = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)offb, 0, V3_NT ? 2 : 0);
+        a = make_uint4(va.x, va.y, va.z, va.w);
+        b = make_uint4(vb.x, vb.y, vb.z, vb.w);
       } else {
         const uint8_t *base = codes_tiled + (size_t)(en.tile_nv & 0x3ffffffu) * 2048;
         uint32_t offa = chunkA;
@@ -331,7 +351,16 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     // fetch (one LDS wait for both)
     auto step = [&](int i, int s) {
       const int fl = flag_up();
-      if (i + DEPTH * NW < nent)
+      // MM: the fetch is unconditional -- past the end of my share the chunk's last entry again, with an empty
+      // resource, never scored -- so the loads issued per step are a compile-time count and the wait in front of
+      // the ADC leaves this step's two in flight under it (vmcnt(3) / vmcnt(2); the older pair is waited for
+      // before the issue).
+      // The other instantiations keep the conditional fetch and with it the full wait behind their loads: the
+      // counted form measured slower there (profiles/HISTORY.md, "PQ scan: counted prefetch").
+      if constexpr (MM)
+        fetch(min(i + DEPTH * NW, nent - 1), A[(s + DEPTH) % NS], B[(s + DEPTH) % NS], e[(s + DEPTH) % NS],
+              i + DEPTH * NW < nent);
+      else if (i + DEPTH * NW < nent)
         fetch(i + DEPTH * NW, A[(s + DEPTH) % NS], B[(s + DEPTH) % NS], e[(s + DEPTH) % NS]);
       flag_u = __builtin_amdgcn_readfirstlane(fl);
       p_score = e[s].coarse + tile_adc<V3_AHEAD>(lut_bytes, A[s], B[s], offA, offB);
