@@ -54,6 +54,30 @@ constexpr int V3_AHEAD = 8;     // tile_adc: LUT reads in flight ahead of the fi
 // load at this offset -- 16-byte aligned, ...f0 to ...fc, no 32-bit wrap -- are all out of range, and with
 // num_records = 0 (a fetch past the end of a wave's share) so is every offset.
 constexpr uint32_t V3_MM_DEAD = 0xfffffff0u;
+// Measurement builds only (scripts/build_variant.sh V3_PAD_SALU=16 ...; profiles/pq_tile_step_sensitivity.txt): N
+// independent scalar / full-rate vector instructions more per tile step, on registers of their own, behind the
+// ADC. What a step's time gains per added instruction is what removing one of that kind is worth. 0: nothing.
+constexpr int V3_PAD_SALU = 0;
+constexpr int V3_PAD_VALU = 0;
+#define V3_PAD4(op) op " %0, 0\n\t" op " %1, 1\n\t" op " %2, 2\n\t" op " %3, 3\n\t"
+#define V3_PAD16(op) V3_PAD4(op) V3_PAD4(op) V3_PAD4(op) V3_PAD4(op)
+template <int NS_, int NV_>
+__device__ __forceinline__ void v3_pad() {
+  // (16 instructions per statement: the compiler puts an s_nop behind every asm statement)
+  static_assert(NS_ % 16 == 0 && NV_ % 16 == 0, "the padding comes in blocks of 16 instructions");
+#pragma unroll
+  for (int n = 0; n < NS_ / 16; ++n) {
+    uint32_t a, b, c, d;
+    asm volatile(V3_PAD16("s_mov_b32") : "=s"(a), "=s"(b), "=s"(c), "=s"(d));
+  }
+#pragma unroll
+  for (int n = 0; n < NV_ / 16; ++n) {
+    uint32_t a, b, c, d;
+    asm volatile(V3_PAD16("v_mov_b32") : "=v"(a), "=v"(b), "=v"(c), "=v"(d));
+  }
+}
+#undef V3_PAD16
+#undef V3_PAD4
 constexpr int V3_WAVES_PER_SIMD = 6;   // occupancy the 2048-key instantiation is compiled for (3 workgroups per CU)
 
 template <int NT_>
@@ -137,11 +161,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
   // table build and complete under it
   constexpr int PP = WIDE ? 2 : 1;
   int my_len[PP], my_tile0[PP], my_nt[PP], my_pre[PP];
-  int my_first[PP];      // RANGED: first lane of the run's first tile
   float my_coarse[PP];
 #pragma unroll
   for (int pp = 0; pp < PP; ++pp) {
-    my_len[pp] = 0, my_tile0[pp] = 0, my_nt[pp] = 0, my_coarse[pp] = 0.0f, my_first[pp] = 0;
+    my_len[pp] = 0, my_tile0[pp] = 0, my_nt[pp] = 0, my_coarse[pp] = 0.0f;
     const int p = tid + pp * NT;
     if (p < nprobe) {
       const int l = coarse_I[(size_t)q * nprobe + p];
@@ -150,9 +173,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
           // the run [lo, hi) of the list, counted from lane 0 of the tile that holds lo: the tile
           // count and the end lane of every tile follow from my_len as for a whole list
           const int2 r = rg.range[(size_t)q * nprobe + p];
-          my_first[pp] = r.x & 63;
+          // (the first lane of the run's first tile rides in the six bits a tile index leaves free: a register less)
           my_len[pp] = r.y > r.x ? r.y - (r.x & ~63) : 0;
-          my_tile0[pp] = tile_offsets[l] + (r.x >> 6);
+          my_tile0[pp] = (int)((uint32_t)(tile_offsets[l] + (r.x >> 6)) | ((uint32_t)(r.x & 63) << 26));
         } else {
           my_len[pp] = list_offsets[l + 1] - list_offsets[l];
           my_tile0[pp] = tile_offsets[l];
@@ -219,24 +242,32 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
   // meet only when the key buffer is full (a sync) and at the end of a chunk. The histogram is not
   // touched per tile: the sync counts what was appended since the last one (lazy counts).
   //
-  // The tile loop rotates the register sets of the prefetch pipeline by unrolling; the sync has ONE
-  // place, behind that loop (free_sync inlines a compaction and a sort: a copy per register set cost
-  // the instantiations their registers). A wave that has to meet the others -- its reservation was
-  // refused, or the flag is up -- leaves the rotation with the tile in flight moved to set 0, joins the
-  // sync, offers a refused tile again (its scores wait in a register) against the new threshold, and
-  // starts the rotation over.
+  // The tile loop rotates the register sets of the prefetch pipeline by unrolling, in TWO places. The hot
+  // loop holds the steps and the usual append: per tile the flag and table entry, the fetch, the ADC, one
+  // compare, one ballot and one scalar test "anything to do?" (a passer, the flag, exact flushes in use), which
+  // falls through; a tile with passers and nothing else reserves and writes its keys right there (with the
+  // threshold moving only in a sync, about one vector of a 64-vector tile still passes at the end of a scan:
+  // such a tile is the rule, profiles/HISTORY.md). A wave leaves the hot loop when the flag is up, exact flushes
+  // are in use or its reservation was refused, deals with that tile off the loop, and walks the rest of
+  // the rotation there, a step at a time with the append behind each, so that the hot loop always starts at
+  // set 0. The sync has ONE place, behind both (free_sync inlines a compaction and a sort: a copy per register
+  // set cost the instantiations their registers). A wave that has to meet the others -- its reservation was
+  // refused, or the flag is up -- moves the tile in flight to set 0, joins the sync, offers a refused tile
+  // again (its scores wait in a register) against the new threshold, and starts the rotation over.
   //
   // No deadlock, whatever the data: the workgroup's barriers are (a) the fixed sequence of one
   // sync and (b) the one barrier that ends a chunk. A wave enters (a) only with the flag raised --
   // by itself, right before its first barrier, or seen raised by another wave, which is then on its
   // way to that barrier and waits there -- and the flag is lowered behind the first barrier of the
   // sequence, before the barriers of free_sync, so no wave sees it raised once the sync is over
-  // (a value read ahead of the sync is dropped in it). Every wave looks at the flag with every tile
-  // and in the wait at the end of its share, so every wave joins every sync. A wave enters (b) only
-  // after s_done says that all NW waves have finished their share of this chunk; a finished wave
-  // raises the flag only to join, and each request of an unfinished wave was answered by a complete
-  // sync before that wave could finish, so at that point no sync is open or can open. The retry of
-  // a refused tile ends: a sync leaves at least ROUND_VECS = NW * 64 free slots.
+  // (a value read ahead of the sync is dropped in it). Every wave looks at the flag with every tile --
+  // every step reads it, in the hot loop and off it, and the value read is part of the hot loop's one test,
+  // ahead of the append there, and of the test behind every append off it -- and in the wait at the end of its share, so every wave joins
+  // every sync. A wave enters (b) only after s_done says that all NW waves have finished their share of
+  // this chunk; a wave counts itself finished once, when the hot loop ends with no entry left and no
+  // reservation pending; a finished wave raises the flag only to join, and each request of an unfinished
+  // wave was answered by a complete sync before that wave could finish, so at that point no sync is open or
+  // can open. The retry of a refused tile ends: a sync leaves at least ROUND_VECS = NW * 64 free slots.
   int *s_flag = top.ctl + TopK::C_USER;            // a wave asks for a sync (C_USER is free until finish_set)
   int *s_done = top.ctl + TopK::C_USER + 1;        // waves that finished their share, summed over the chunks
   if (tid == 0) {
@@ -257,14 +288,16 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     for (int pp = 0; pp < PP; ++pp) {
       // (my probe as values of their own: what the fill derives from them is made here, once per chunk,
       // not kept in registers across the tile loop)
-      asm volatile("" : "+v"(my_pre[pp]), "+v"(my_nt[pp]), "+v"(my_tile0[pp]), "+v"(my_len[pp]));
-      const int lo = max(my_pre[pp], c0), hi = min(my_pre[pp] + my_nt[pp], c0 + CHUNK);
+      // (the probe's tile count is made again from its length here: a register less across the tile loop)
+      asm volatile("" : "+v"(my_pre[pp]), "+v"(my_tile0[pp]), "+v"(my_len[pp]));
+      const int lo = max(my_pre[pp], c0), hi = min(my_pre[pp] + ((my_len[pp] + 63) >> 6), c0 + CHUNK);
       for (int t = lo; t < hi; ++t) {
         const int local = t - my_pre[pp];
         Ent e;
-        e.tile_nv = (uint32_t)(my_tile0[pp] + local) | ((uint32_t)(min(64, my_len[pp] - local * 64) - 1) << 26);
+        const uint32_t tile0 = RANGED ? (uint32_t)my_tile0[pp] & 0x3ffffffu : (uint32_t)my_tile0[pp];
+        e.tile_nv = (tile0 + (uint32_t)local) | ((uint32_t)(min(64, my_len[pp] - local * 64) - 1) << 26);
         e.coarse = my_coarse[pp];
-        if constexpr (RANGED) e.first = local == 0 ? (uint32_t)my_first[pp] : 0u;
+        if constexpr (RANGED) e.first = local == 0 ? (uint32_t)my_tile0[pp] >> 26 : 0u;
         table[t - c0] = e;
       }
     }
@@ -287,11 +320,18 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     } e[NS];
     // (real: false past the end of the wave's share, MM only -- the loads are issued all the same, of an empty
     // resource: every lane out of range, nothing fetched)
-    auto fetch = [&](int i, uint4 &a, uint4 &b, Tile &en, bool real = true) {
-      const Ent t = table[i];
-      en.tile_nv = __builtin_amdgcn_readfirstlane(t.tile_nv);
-      en.coarse = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t.coarse)));
-      if constexpr (RANGED) en.first = __builtin_amdgcn_readfirstlane(t.first);
+    // The entry to fetch is read at a running LDS address (a lane register that a step advances by its
+    // wave's stride), not at an index turned into an address per tile. num_records: the resource's size,
+    // 0 for a fetch past the end of the wave's share (MM only -- the loads are issued all the same, of
+    // an empty resource: every lane out of range, nothing fetched).
+    auto fetch = [&](uint32_t taddr, uint4 &a, uint4 &b, Tile &en, uint32_t num_records = 0) {
+      // (tile_nv, coarse: one 8-byte read -- the table is 16-byte aligned, an entry 8 or 12 bytes long)
+      typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+      const u32x2 t = *(const __attribute__((address_space(3))) u32x2 *)(uintptr_t)taddr;
+      en.tile_nv = __builtin_amdgcn_readfirstlane(t.x);
+      en.coarse = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane((int)t.y));
+      if constexpr (RANGED)
+        en.first = __builtin_amdgcn_readfirstlane(*(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)(taddr + 8u));
       if constexpr (SEL) en.sel = sel[en.tile_nv & 0x3ffffffu];   // (a scalar load: the tile is wave-uniform)
       // the tile's address is a scalar and the lane's part a 32-bit offset of its own: the loads take
       // them as they are (scalar base + lane offset), no 64-bit lane addresses to keep or add up per tile
@@ -299,14 +339,15 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
       if constexpr (MM) {
         const uint32_t toff = (en.tile_nv & 0x3ffffffu) * 64u;
         const uint8_t *base = codes_tiled + (size_t)toff;
-        uint32_t offa = chunkA, offb = chunkB;   // (values of their own, as below: scalar base + 32-bit lane offset)
-        asm volatile("" : "+v"(offa), "+v"(offb));
-        // (the resource: from the tile's first plane-0 byte to the end of the copy, raw, no stride)
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint8_t *>(base), 0, (int)(real ? (uint32_t)PQT_M * mm_plane - toff : 0u), 0x00020000);
+        // (the resource: from the tile's first plane-0 byte on, raw, no stride. Its size is the whole copy's,
+        // 32 * mm_plane, for every tile -- not the bytes left behind this tile, a subtraction per tile: a live
+        // lane's offset is below 31 * mm_plane + 64, so what it reads lies inside the copy, tile + 64 <= mm_plane,
+        // and V3_MM_DEAD is beyond 32 * mm_plane all the same)
+        const __amdgpu_buffer_rsrc_t rs =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(base), 0, (int)num_records, 0x00020000);
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        const u32x4 va = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)offa, 0, V3_NT ? 2 : 0);   // (aux bit 1: nt)
-        const u32x4 vb = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)offb, 0, V3_NT ? 2 : 0);
+        const u32x4 va = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)chunkA, 0, V3_NT ? 2 : 0);   // (aux bit 1: nt)
+        const u32x4 vb = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)chunkB, 0, V3_NT ? 2 : 0);
         a = make_uint4(va.x, va.y, va.z, va.w);
         b = make_uint4(vb.x, vb.y, vb.z, vb.w);
       } else {
@@ -318,86 +359,132 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
         b = load_codes16<V3_NT>(base + offb);
       }
     };
-    // the tile whose candidates wait to be appended: its scores and (scalar) its entry
+    constexpr uint32_t ENT_STRIDE = NW * sizeof(Ent);   // from one entry of a wave to its next
+    const uint32_t mm_size = (uint32_t)PQT_M * mm_plane;
+    // the tile whose candidates are offered: its scores and (scalar) its entry
     float p_score = 0.0f;
     uint32_t p_tile_nv = 0, p_first = 0;
     unsigned long long p_sel = 0;
     bool pending = false;
-    // A tile costs the ADC and one compare against the snapshot; the ordered key is only made for the
-    // lanes that pass (free_write), under the branch a tile without a passer skips.
-    auto append = [&]() {
-      const int end = (int)(p_tile_nv >> 26);
-      bool in = RANGED ? (lane <= end && lane >= (int)p_first) : lane <= end;
-      if constexpr (SEL) in = in && ((p_sel >> lane) & 1ull) != 0;
-      bool p;
-      if (thr_hi_u != 0) {        // wave-uniform; exact flushes are in use: the ordered-key test
-        // (the score as a value of its own: keeps this a scalar branch and its ordered key in here,
-        // not three selects and a key per tile)
+    // The lanes that hold a vector to offer, as a scalar mask: lane <= end (RANGED: and lane >= first; SEL: and
+    // selected). (A 64-bit shift takes the low six bits of its count: ~end is 63 - end there.)
+    auto in_mask = [&]() -> unsigned long long {
+      unsigned long long in = ~0ull >> (~(p_tile_nv >> 26) & 63u);
+      if constexpr (RANGED) in &= ~0ull << (p_first & 63u);
+      if constexpr (SEL) in &= p_sel;
+      return in;
+    };
+    // A tile costs the ADC, one compare against the snapshot and the scalar AND with in_mask; everything
+    // else is on the path a tile without a passer never enters.
+    auto passers = [&]() -> unsigned long long { return __ballot(p_score >= thr_u) & in_mask(); };
+    // The rare path: m = passers(). While exact flushes are in use (thr_hi_u != 0, wave-uniform) the
+    // test is the ordered key's and m is made again; the ordered key of the lanes that pass is made in
+    // free_write. The reservation's verdict is settled before the lanes part to write their keys:
+    // `pending` stays a scalar, and with it every branch of the wave's loop.
+    auto append = [&](unsigned long long m, bool thresholded = false) {
+      if (!thresholded && thr_hi_u != 0) {
         float sc = p_score;
         asm volatile("; exact flushes" : "+v"(sc));
-        p = in && f2ord(sc) >= thr_hi_u;
-      } else {
-        p = in && p_score >= thr_u;
+        m = __ballot(f2ord(sc) >= thr_hi_u) & in_mask();
       }
-      const unsigned long long m = __ballot(p);
-      // (the reservation's verdict is settled before the lanes part to write their keys: `pending`
-      // stays a scalar, and with it every branch of the wave's loop)
-      int base = -2;              // nothing passes
-      if (m) base = top.free_reserve(__popcll(m));   // wave-uniform; -1: the buffer is full
-      pending = base == -1;
-      if (base >= 0) top.free_write(p, m, p_score, (p_tile_nv << 6) + (uint32_t)lane, base, false);
+      pending = false;
+      if (m) {
+        const int base = top.free_reserve(__builtin_amdgcn_readfirstlane(__popcll(m)));   // wave-uniform; -1: the buffer is full
+        pending = base < 0;
+        if (!pending) top.free_write(__builtin_amdgcn_inverse_ballot_w64(m), m, p_score, (p_tile_nv << 6) + (uint32_t)lane, base, false);
+      }
     };
-    // one tile: the codes of tile i are in set s; the flag is read ahead, with the table entry of the
-    // fetch (one LDS wait for both)
-    auto step = [&](int i, int s) {
+    const uint32_t table_lds = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)reinterpret_cast<const char *>(table);
+    int i = wave_u;               // my next entry; between syncs its codes are in set 0, the next tiles' behind
+    if (i < nent) {
+      uint32_t t0 = table_lds + (uint32_t)i * (uint32_t)sizeof(Ent);
+      asm volatile("" : "+v"(t0));
+#pragma unroll
+      for (int s = 0; s < DEPTH; ++s)
+        if (i + s * NW < nent) fetch(t0 + s * ENT_STRIDE, A[s], B[s], e[s], mm_size);
+    }
+    // One step: the flag and the next table entry are read (one LDS wait for both), the next tile's codes
+    // fetched, the tile in set s scored. taddr: the LDS address of the entry fetched last.
+    // MM: the fetch is unconditional -- past the end of my share the last entry fetched again, with an empty
+    // resource, never scored -- so the loads issued per step are a compile-time count and the wait in front of
+    // the ADC leaves this step's two in flight under it (vmcnt(3) / vmcnt(2); the older pair is waited for
+    // before the issue). The other instantiations keep the conditional fetch and with it the full wait behind
+    // their loads: the counted form measured slower there (profiles/HISTORY.md, "PQ scan: counted prefetch").
+    uint32_t taddr = 0;
+    auto step = [&](int s) {
+      const int f = (s + DEPTH) % NS;
       const int fl = flag_up();
-      // MM: the fetch is unconditional -- past the end of my share the chunk's last entry again, with an empty
-      // resource, never scored -- so the loads issued per step are a compile-time count and the wait in front of
-      // the ADC leaves this step's two in flight under it (vmcnt(3) / vmcnt(2); the older pair is waited for
-      // before the issue).
-      // The other instantiations keep the conditional fetch and with it the full wait behind their loads: the
-      // counted form measured slower there (profiles/HISTORY.md, "PQ scan: counted prefetch").
-      if constexpr (MM)
-        fetch(min(i + DEPTH * NW, nent - 1), A[(s + DEPTH) % NS], B[(s + DEPTH) % NS], e[(s + DEPTH) % NS],
-              i + DEPTH * NW < nent);
-      else if (i + DEPTH * NW < nent)
-        fetch(i + DEPTH * NW, A[(s + DEPTH) % NS], B[(s + DEPTH) % NS], e[(s + DEPTH) % NS]);
+      const bool real = i + DEPTH * NW < nent;
+      if constexpr (MM) {
+        taddr += real ? ENT_STRIDE : 0u;
+        fetch(taddr, A[f], B[f], e[f], real ? mm_size : 0u);
+      } else if (real) {
+        taddr += ENT_STRIDE;
+        fetch(taddr, A[f], B[f], e[f]);
+      }
       flag_u = __builtin_amdgcn_readfirstlane(fl);
       p_score = e[s].coarse + tile_adc<V3_AHEAD>(lut_bytes, A[s], B[s], offA, offB);
       p_tile_nv = e[s].tile_nv;
       if constexpr (RANGED) p_first = e[s].first;
       if constexpr (SEL) p_sel = e[s].sel;
-      append();
+      i += NW;
     };
-    int i = wave_u;               // my next entry; between syncs its codes are in set 0, the next tiles' behind
-#pragma unroll
-    for (int s = 0; s < DEPTH; ++s)
-      if (i + s * NW < nent) fetch(i + s * NW, A[s], B[s], e[s]);
-    bool finished = false;
-    for (;;) {                    // every condition below is wave-uniform
-      bool meet = false;
-      while (i < nent && !meet) {
+    // The hot loop: the rotation of the register sets from set 0 on. Per step ONE scalar test -- a passer, the
+    // flag, exact flushes in use: anything to do? -- which falls through for a tile without a passer, and the
+    // test for the end of the share, which is the back edge. A tile with passers and nothing else is appended
+    // here, by the thresholded test alone. Returns -1 at the end of the share; s if the tile of set s (it is
+    // scored: p_score) is still to be offered -- the flag is up or exact flushes are in use --; s + NS if it
+    // was offered here and refused (`pending`).
+    auto hot = [&]() -> int {
+      for (;;) {
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          if (i < nent && !meet) {
-            step(i, s);
-            i += NW;
-            if (pending || flag_u) {
-              // to the sync, from wherever in the rotation: the tiles in flight move to the front
-              // sets (register moves, once per sync), so that the loop starts over at set 0
-              meet = true;
-              if (s + 1 < NS) {
+          if (i >= nent) return -1;
+          step(s);
+          v3_pad<V3_PAD_SALU, V3_PAD_VALU>();
+          const unsigned long long m = passers();
+          if (__builtin_expect(((uint32_t)m | (uint32_t)(m >> 32) | (uint32_t)flag_u | thr_hi_u) != 0u, 0)) {
+            if (((uint32_t)flag_u | thr_hi_u) != 0u) return s;
+            append(m, true);              // the usual case: a passer, nothing else
+            if (pending) return s + NS;   // refused: offered already, to the sync
+          }
+        }
+      }
+    };
+    bool finished = false;
+    for (;;) {                    // every condition below is wave-uniform
+      // (the entry fetched last is DEPTH - 1 strides ahead of i; where that is past the share, no entry is
+      // fetched any more and the address only has to be one of the table)
+      taddr = table_lds + (uint32_t)(DEPTH == 1 ? min(i, CHUNK - 1) : min(i + (DEPTH - 1) * NW, nent - 1)) * (uint32_t)sizeof(Ent);
+      asm volatile("" : "+v"(taddr));
+      int ev = hot();
+      asm volatile("" : "+s"(ev));          // (one way out of the hot loop, whatever is made of ev below)
+      bool meet = false;
+      // Off the hot loop: the tile of set ev % NS is appended (unless it was, and was refused), then the rest of
+      // the rotation is walked here, a step at a time, so that the hot loop always starts at set 0. A wave that has to meet the others --
+      // its reservation was refused, or the flag is up -- moves the tiles in flight to the front sets
+      // (register moves, once per sync) and goes to the sync.
 #pragma unroll
-                for (int u = 0; u < DEPTH; ++u) {
-                  A[u] = A[(s + 1 + u) % NS];
-                  B[u] = B[(s + 1 + u) % NS];
-                  e[u] = e[(s + 1 + u) % NS];
-                }
-              }
+      for (int s = 0; s < NS; ++s) {
+        if (ev < 0 || s < ev % NS || meet) continue;
+        if (s > ev % NS) {
+          if (i >= nent) continue;
+          step(s);
+        }
+        if (!(ev >= NS && s == ev % NS)) append(passers());   // (ev >= NS: offered in the hot loop and refused)
+        if (pending || flag_u) {
+          meet = true;
+          if (s + 1 < NS) {
+#pragma unroll
+            for (int u = 0; u < DEPTH; ++u) {
+              A[u] = A[(s + 1 + u) % NS];
+              B[u] = B[(s + 1 + u) % NS];
+              e[u] = e[(s + 1 + u) % NS];
             }
           }
         }
       }
+      if (ev >= 0 && !meet) continue;
       if (!meet) {
         // my share is done: wait for the other waves, joining the syncs they ask for
         if (!finished) {
@@ -425,7 +512,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
         thr_u = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, top.thr_f)));
         thr_hi_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)top.thr_hi);
         flag_u = 0;               // read before this sync
-        if (pending) append();
+        if (pending) append(passers());
       } while (pending);
     }
     __syncthreads();
