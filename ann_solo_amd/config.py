@@ -68,7 +68,9 @@ class Config:
     # accepted with its cosine as the score and q = 0.
     model: Optional[str] = None
     # --- additive flags of this implementation
-    index: str = 'ivfflat'                  # 'ivfflat' (the reference's index type) | 'ivfpq'
+    index: str = 'ivfflat'                  # 'ivfflat' (the reference's index type) | 'ivfpq' | 'winflat' (exact
+                                            # inner products over every library vector of the query's precursor
+                                            # window: no coarse quantiser; num_list / num_probe are ignored)
     pq_m: int = 32
     pq_bits: int = 8
     refine_k: Optional[int] = None          # IVF-PQ: exact re-rank of the refine_k best ADC candidates
@@ -133,6 +135,14 @@ class Config:
             if self.refine_k:
                 raise ValueError("ann_window = 'pre' does not combine with refine_k")
         self.pq_by_residual = bool(self.pq_by_residual)      # (the flag parses to 0 / 1)
+        if self.index == 'winflat':
+            if self.num_gpus and int(self.num_gpus) > 1:
+                raise ValueError("index = 'winflat' does not run on a sharded index (num_gpus > 1)")
+            if self.refine_k:
+                raise ValueError("index = 'winflat' scores exactly already: it does not combine with refine_k")
+            if self.num_candidates is not None and int(self.num_candidates) > 1280:
+                raise ValueError(f"index = 'winflat' holds num_candidates <= 1280 (num_candidates = "
+                                 f'{self.num_candidates})')
         if not self.pq_by_residual and self.index != 'ivfpq':
             raise ValueError("pq_by_residual = False needs index = 'ivfpq' (it is the product quantiser's mode)")
         if not 1 <= int(self.num_matches) <= self.MAX_MATCHES:
@@ -225,9 +235,11 @@ def add_arguments(parser) -> None:
 
     No existing flag changes name, default or meaning."""
     d = Config()
-    parser.add_argument('--index', default=d.index, type=str, choices=['ivfflat', 'ivfpq'],
+    parser.add_argument('--index', default=d.index, type=str, choices=['ivfflat', 'ivfpq', 'winflat'],
                         help='ANN index type: inverted file with exact inner products (the '
-                             "reference's index) or with product-quantised codes "
+                             "reference's index) or with product-quantised codes, or 'winflat': exact inner "
+                             "products over every library vector in the query's precursor window, no coarse "
+                             'quantiser (--num_list and --num_probe are ignored; one GPU) '
                              '(default: %(default)s)')
     parser.add_argument('--pq_m', default=d.pq_m, type=int,
                         help='IVF-PQ: number of sub-quantisers; must divide hash_len '

@@ -231,6 +231,34 @@ __device__ __forceinline__ bool precursor_ok(const QueryWindow &w, float lib, in
   return precursor_ok(w.q, lib, charge, tol, mode);
 }
 
+// The run [lo, hi) of the positions of key[0 .. n) -- ascending, NaN last -- that pass the window w: two binary
+// searches with precursor_ok itself as the predicate, so the run holds exactly the vectors the reference's
+// filter keeps (window_ranges_kernel, pq_scan_v3.hip, says why the run is contiguous). ASL_TOL_INTERVAL: the same
+// walk is lower_bound(lo) and upper_bound(hi); a NaN bound or lo > hi: no run. NaN keys never pass.
+__device__ __forceinline__ int2 window_run(const float *__restrict__ key, int n, const QueryWindow &w, int charge,
+                                           double tol, int mode) {
+  const double qm = w.q;
+  int a = 0, b = n;   // p0 = first key with (double)key >= qm (NaN: not below)
+  while (a < b) {
+    const int mid = (a + b) >> 1;
+    if ((double)key[mid] < qm) a = mid + 1; else b = mid;
+  }
+  const int p0 = a;
+  // (interval: p0 is lower_bound(lo) and nothing left of it passes)
+  a = mode == ASL_TOL_INTERVAL ? p0 : 0, b = p0;      // left side: first key that passes
+  while (a < b) {
+    const int mid = (a + b) >> 1;
+    if (precursor_ok(qm, key[mid], charge, tol, mode)) b = mid; else a = mid + 1;
+  }
+  const int lo = a;
+  a = p0, b = (mode == ASL_TOL_INTERVAL && !(w.q <= w.hi)) ? p0 : n;      // right side: first key that fails
+  while (a < b) {
+    const int mid = (a + b) >> 1;
+    if (precursor_ok(w, key[mid], charge, tol, mode)) a = mid + 1; else b = mid;
+  }
+  return make_int2(lo, a);
+}
+
 // The precursor-window post-filter (spectral_library.py:441-446: AFTER the top-k) applied where the
 // top-k ends: a scan's set-mode finish that is given one writes only the hits that pass, compacted at
 // the front of the row, and their number -- the rescoring then walks ~1/6 of a 1 024-wide row and

@@ -130,7 +130,16 @@ struct FiUnit {
 // selected. The wave loads a block's words once (lanes 0 .. FI_ROWS - 1, one word each) and every lane
 // keeps the FI_ROWS bits of its own positions; an unselected vector is accumulated like any other and
 // never counted or offered: wherever a position is tested with v < nb, its bit is tested too.
-template <int FI_CAP, bool FX, bool WIDE, bool SEL = false>
+//
+// RANGED (the window-exact index, ASL_INDEX_WINFLAT; the 2048-key instantiations only): the index is ONE list
+// in precursor order and rg.range[q] = [lo, hi) is the query's run of positions (winflat_runs_kernel below);
+// coarse_I, nprobe, list_offsets and blk_offsets are unread. The unit table lists the blocks lo / FI_BLK ..
+// (hi - 1) / FI_BLK -- a whole block outside the run is never listed and none of its lines are fetched -- and
+// a unit's first and one-past-last in-run position follow from its pos0 and the run. An out-of-run vector of a
+// boundary block is accumulated like any other and never counted or offered (the rule SEL follows): wherever
+// a position is tested with v < nb, it is tested with first <= v && v < last. Set-mode rows hold in-run hits
+// only and rg.row_len[q] their number, as in the ranged PQ scan.
+template <int FI_CAP, bool FX, bool WIDE, bool SEL = false, bool RANGED = false>
 __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_kernel(
     const float *__restrict__ xq, int d, const int32_t *__restrict__ coarse_I, int nprobe,
     const int32_t *__restrict__ list_offsets, const int32_t *__restrict__ blk_offsets,
@@ -138,8 +147,10 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
     const char *__restrict__ seg_bytes, const int32_t *__restrict__ ids, int k,
     float *__restrict__ D, int64_t *__restrict__ I64, int32_t *__restrict__ I32, int set_mode,
     const uint2 *__restrict__ ent, const int32_t *__restrict__ ent_cnt, int tab_stride,
-    const int *__restrict__ gate, const ScanPostFilter pf, const unsigned long long *__restrict__ sel) {
+    const int *__restrict__ gate, const ScanPostFilter pf, const unsigned long long *__restrict__ sel,
+    const ScanRanges rg) {
   static_assert(!SEL || FI_CAP <= 2048, "the selector is built into the 2048-key instantiations only");
+  static_assert(!RANGED || (FI_CAP <= 2048 && !WIDE && !SEL), "the ranged form: 2048 keys, no probes, no selector");
   if (gate && (int)blockIdx.x >= *gate) return;      // device-side row count (see pq_scan_v3_kernel)
   constexpr float FX_SCALE = FX ? 1.0f / 4194304.0f : 1.0f;      // 2^-22, folded into the query values
   using TopK = HistTopK<FI_CAP, FI_NT, FI_NT>;
@@ -167,11 +178,12 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
   // spectral_library.py:77-81)
   constexpr int PP = WIDE ? 2 : 1;
   int my_len[PP], my_pos[PP], my_b0[PP], my_nb[PP], my_pre[PP];
+  int run_lo = 0, run_hi = 0, run_b0 = 0;      // RANGED: the query's run of positions and its first block
 #pragma unroll
   for (int pp = 0; pp < PP; ++pp) {
     my_len[pp] = 0, my_pos[pp] = 0, my_b0[pp] = 0, my_nb[pp] = 0;
     const int p = tid + pp * FI_NT;
-    if (p < nprobe) {
+    if (!RANGED && p < nprobe) {
       const int l = coarse_I[(size_t)q * nprobe + p];
       if (l >= 0) {
         my_pos[pp] = list_offsets[l];
@@ -182,8 +194,15 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
     }
   }
   int total = 0;
+  if constexpr (RANGED) {
+    const int2 run = rg.range[q];              // block-uniform
+    run_lo = run.x, run_hi = run.y;
+    run_b0 = run_lo / FI_BLK;
+    if (run_hi > run_lo) total = (run_hi - 1) / FI_BLK - run_b0 + 1;
+    __syncthreads();                           // s_q complete
+  }
 #pragma unroll
-  for (int pp = 0; pp < PP; ++pp) {
+  for (int pp = 0; pp < (RANGED ? 0 : PP); ++pp) {
     int part_total;
     if (pp) __syncthreads();      // the partial sums of the first scan have been read
     my_pre[pp] = total + block_excl_scan<FI_NW>(my_nb[pp], s_misc, tid, part_total);   // barrier inside: s_q complete
@@ -235,8 +254,17 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
   };
   auto sync_wanted = [&]() -> bool { return __builtin_amdgcn_readfirstlane(*s_flag) != 0; };
   for (int c0 = 0; c0 < total; c0 += FI_CHUNK) {
+    if constexpr (RANGED) {
+      for (int t = c0 + tid; t < min(total, c0 + FI_CHUNK); t += FI_NT) {
+        FiUnit u;
+        u.blk = (uint32_t)(run_b0 + t);
+        u.pos0 = (run_b0 + t) * FI_BLK;
+        table[t - c0] = u;
+        s_nbv[t - c0] = (uint16_t)min(FI_BLK, run_hi - u.pos0);      // one past the block's last in-run position
+      }
+    }
 #pragma unroll
-    for (int pp = 0; pp < PP; ++pp) {
+    for (int pp = 0; pp < (RANGED ? 0 : PP); ++pp) {
       const int lo = max(my_pre[pp], c0), hi = min(my_pre[pp] + my_nb[pp], c0 + FI_CHUNK);
       for (int t = lo; t < hi; ++t) {
         const int j = t - my_pre[pp];
@@ -259,12 +287,17 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
       int nb = 0, pos0 = 0;
       uint32_t selbits = 0;    // SEL: bit r = my position of row r (r * 64 + lane) is selected
       auto sel_ok = [&](int r) -> bool { return !SEL || ((selbits >> r) & 1u) != 0; };
+      int first_in = 0;        // RANGED: the block's first in-run position (nb: one past its last)
+      auto in_run = [&](int v) -> bool { return !RANGED || v >= first_in; };
       if (i < nent) {          // wave-uniform
         const FiUnit u = table[i];
         nb = __builtin_amdgcn_readfirstlane((int)s_nbv[i]);
         pos0 = __builtin_amdgcn_readfirstlane(u.pos0);
+        if constexpr (RANGED) first_in = max(run_lo - pos0, 0);
         const uint32_t blk = (uint32_t)__builtin_amdgcn_readfirstlane((int)u.blk);
         const char *bptr = seg_bytes + (size_t)blk_base[blk] * (FX ? 128 : 64);     // (a scalar load: blk is wave-uniform)
+        // (RANGED: the run's last block is zeroed up to its last in-run position; the postings of the vectors
+        // behind it land on what the wave's previous block left there, and those positions are never read)
         for (int o = lane; o < nb; o += 64) acc[o] = 0.0f;
         // SEL: the block's words are requested here and used behind the row loop, which hides their latency
         // (requested there, the scan at nprobe 112 ran 2 % slower: DESIGN.md 5 "Subset search")
@@ -421,7 +454,7 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
       if (cold) {
         for (int r = 0; r * 64 < nb; ++r) {
           const int v = r * 64 + lane;
-          top.cold_count(v < nb && sel_ok(r), v < nb ? acc[v] : 0.0f);
+          top.cold_count(v < nb && in_run(v) && sel_ok(r), v < nb ? acc[v] : 0.0f);
         }
         top.cold_threshold();
       }
@@ -445,7 +478,7 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
         int c = 0;
 #pragma unroll
         for (int r = 0; r < FI_ROWS; ++r)
-          c += __popcll(__ballot(r * 64 + lane < nb && sel_ok(r) && top.passes(sc[r])));
+          c += __popcll(__ballot(r * 64 + lane < nb && in_run(r * 64 + lane) && sel_ok(r) && top.passes(sc[r])));
         if (c == 0) {
           offered = true;
         } else if (c <= 64) {
@@ -454,7 +487,7 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
 #pragma unroll
             for (int r = 0; r < FI_ROWS; ++r) {
               const int v = r * 64 + lane;
-              const bool p = v < nb && sel_ok(r) && top.passes(sc[r]);
+              const bool p = v < nb && in_run(v) && sel_ok(r) && top.passes(sc[r]);
               const unsigned long long m = __ballot(p);
               if (m) {                                                     // wave-uniform
                 top.free_write(p, m, sc[r], (uint32_t)(pos0 + v), base);
@@ -469,7 +502,7 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
         const int v = r * 64 + lane;
         const float score = v < nb ? acc[v] : 0.0f;
         for (;;) {
-          const bool p = v < nb && sel_ok(r) && top.passes(score);
+          const bool p = v < nb && in_run(v) && sel_ok(r) && top.passes(score);
           if (!__ballot(p)) break;                                        // wave-uniform
           if (top.free_append(p, score, (uint32_t)(pos0 + v), cold)) break;
           sync();
@@ -497,7 +530,19 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
     __syncthreads();
   }
   top.free_done();
-  if (set_mode && (size_t)FI_CAP * 9 <= (size_t)FI_NW * FI_BLK * 4)   // unordered exact top-k; the accumulators are dead: scratch
+  if constexpr (RANGED) {
+    // set mode: the row holds in-run hits only, so its length goes to the rescoring as it is (-1 after exact
+    // flushes: the row is -1 padded and the rescoring's own filter, which every hit passes, finds its end)
+    static_assert((size_t)FI_CAP * 8 <= (size_t)FI_NW * FI_BLK * 4, "the set finish's scratch is the accumulators");
+    if (set_mode) {
+      const int n = top.finish_set(D ? D + (size_t)q * k : nullptr, I64 ? I64 + (size_t)q * k : nullptr,
+                                   I32 ? I32 + (size_t)q * k : nullptr, reinterpret_cast<u64 *>(s_acc));
+      if (rg.row_len && tid == 0) rg.row_len[q] = n;
+    } else {
+      top.finish(D ? D + (size_t)q * k : nullptr, I64 ? I64 + (size_t)q * k : nullptr,
+                 I32 ? I32 + (size_t)q * k : nullptr);
+    }
+  } else if (set_mode && (size_t)FI_CAP * 9 <= (size_t)FI_NW * FI_BLK * 4)   // unordered exact top-k; the accumulators are dead: scratch
     top.finish_set(D ? D + (size_t)q * k : nullptr, I64 ? I64 + (size_t)q * k : nullptr,
                    I32 ? I32 + (size_t)q * k : nullptr, reinterpret_cast<u64 *>(s_acc), &pf, q);
   else if (set_mode && (size_t)FI_CAP * 8 <= (size_t)FI_NW * FI_BLK * 4)
@@ -512,24 +557,24 @@ bool flat_inv_supported(int d, int k, int nprobe) {
   return d <= 4096 && nprobe <= 2 * FI_NT && k >= 1 && k + FI_NT + 256 <= 4096;
 }
 
-template <int FI_CAP, bool FX, bool WIDE, bool SEL = false>
+template <int FI_CAP, bool FX, bool WIDE, bool SEL = false, bool RANGED = false>
 static int launch_flat_inv(const float *xq, int nq, int d, const int32_t *coarse_I, int nprobe,
                            const int32_t *list_offsets, const int32_t *blk_offsets,
                            const uint32_t *blk_base, const uint32_t *seg_tab,
                            const char *seg_bytes, const int32_t *ids, int k, float *D,
                            int64_t *I64, int32_t *I32, int set_mode, const uint2 *ent,
                            const int32_t *ent_cnt, int tab_stride, const int *gate, const ScanPostFilter &pf,
-                           const unsigned long long *sel = nullptr) {
+                           const unsigned long long *sel = nullptr, const ScanRanges &rg = ScanRanges()) {
   using TopK = HistTopK<FI_CAP, FI_NT, FI_NT>;
   const size_t lds = TopK::lds_bytes() + (size_t)FI_NW * FI_BLK * 4 + (size_t)((d + 3) & ~3) * 4 +
                      (size_t)FI_CHUNK * (sizeof(FiUnit) + 2) + 64 + (size_t)((d + 7) & ~7) * 2;
   if (lds > 160 * 1024) return fail(ASL_ERR_CAPACITY, "flat scan: d=%d does not fit LDS", d);
   if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute((const void *)flat_inv_scan_kernel<FI_CAP, FX, WIDE, SEL>,
+    HIP_TRY(hipFuncSetAttribute((const void *)flat_inv_scan_kernel<FI_CAP, FX, WIDE, SEL, RANGED>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((flat_inv_scan_kernel<FI_CAP, FX, WIDE, SEL>), dim3(nq), dim3(FI_NT), lds, stream(), xq, d,
+  hipLaunchKernelGGL((flat_inv_scan_kernel<FI_CAP, FX, WIDE, SEL, RANGED>), dim3(nq), dim3(FI_NT), lds, stream(), xq, d,
                      coarse_I, nprobe, list_offsets, blk_offsets, blk_base, seg_tab, seg_bytes, ids,
-                     k, D, I64, I32, set_mode, ent, ent_cnt, tab_stride, gate, pf, sel);
+                     k, D, I64, I32, set_mode, ent, ent_cnt, tab_stride, gate, pf, sel, rg);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }
@@ -542,10 +587,23 @@ int flat_inv_scan(int layout, const float *xq, int nq, int d, const int32_t *coa
                   const uint32_t *blk_base, const void *seg_tab, int tab_stride, const char *seg_bytes,
                   const int32_t *ids, int k, float *D, int64_t *I64, int32_t *I32, int set_mode,
                   const uint2 *ent, const int32_t *ent_cnt, const int *gate, const ScanPostFilter *post,
-                  const unsigned long long *sel) {
+                  const unsigned long long *sel, const ScanRanges *ranges) {
   if (nq <= 0) return ASL_OK;
   const uint32_t *tab = reinterpret_cast<const uint32_t *>(seg_tab);
   const bool small = k + FI_NT + 256 <= 2048;
+  if (ranges && ranges->range) {      // one precursor-ordered list, a run of positions per query (RANGED)
+    if (!small || set_mode == 2 || sel || gate || (post && post->idpay))
+      return fail(ASL_ERR_STATE, "postings scan: the ranged form needs k <= 1280 and rows of ids, and takes no "
+                                 "selector, gate or post-filter");
+    const ScanPostFilter none;
+    if (layout == 2)
+      return launch_flat_inv<2048, true, false, false, true>(xq, nq, d, nullptr, 0, nullptr, nullptr, blk_base, tab,
+                                                             seg_bytes, ids, k, D, I64, I32, set_mode, ent, ent_cnt,
+                                                             tab_stride, nullptr, none, nullptr, *ranges);
+    return launch_flat_inv<2048, false, false, false, true>(xq, nq, d, nullptr, 0, nullptr, nullptr, blk_base, tab,
+                                                            seg_bytes, ids, k, D, I64, I32, set_mode, ent, ent_cnt,
+                                                            tab_stride, nullptr, none, nullptr, *ranges);
+  }
   ScanPostFilter pf;       // the set-mode finish of the 2048-key instantiation only (scratch behind the keys)
   if (post && post->idpay) {
     if (!(set_mode == 1 && I32 && small))
@@ -583,6 +641,38 @@ int flat_inv_scan(int layout, const float *xq, int nq, int d, const int32_t *coa
   if (small) FI_LAUNCH(2048, false);
   FI_LAUNCH(4096, false);
 #undef FI_LAUNCH
+}
+
+// ---- the run [lo, hi) of every query in the one precursor-ordered list of the window-exact index (RANGED above):
+// window_run (common.hpp), the two binary searches window_ranges_kernel makes per (query, probe), once per
+// query over the whole key column (ascending, NaN last). q_pmz == nullptr: the
+// window that passes everything, NaN keys included: [0, n). acc (optional): += sum of hi - lo.
+__global__ void winflat_runs_kernel(const double *__restrict__ q_pmz, int nq, const float *__restrict__ key, int n,
+                                    int charge, double tol, int mode, int2 *__restrict__ runs,
+                                    unsigned long long *__restrict__ acc) {
+  const int64_t i = block_linear() * blockDim.x + threadIdx.x;
+  unsigned long long cnt = 0;
+  if (i < nq) {
+    int2 r = make_int2(0, n);
+    if (q_pmz) {
+      r = window_run(key, n, query_window(q_pmz, i, mode), charge, tol, mode);
+    }
+    runs[i] = r;
+    cnt = (unsigned long long)(r.y - r.x);
+  }
+  if (acc) {
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(acc, cnt);
+  }
+}
+
+int winflat_runs(const double *q_pmz, int nq, const float *key, int64_t n, int charge, double tol, int mode,
+                 int2 *runs, unsigned long long *acc) {
+  if (nq <= 0) return ASL_OK;
+  hipLaunchKernelGGL(winflat_runs_kernel, grid_2d(cdiv(nq, 256)), dim3(256), 0, stream(), q_pmz, nq, key, (int)n,
+                     charge, tol, mode, runs, acc);
+  ASL_CHECK_LAUNCH();
+  return ASL_OK;
 }
 
 // ---- selector words of the postings layout (SEL above): FI_ROWS words per block, one wave per word. The

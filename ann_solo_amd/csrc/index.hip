@@ -27,8 +27,8 @@ static int dev_append(DevBuf<T> &buf, size_t old_n, const T *src_dev, size_t n) 
 }
 
 int index_shape_check(const char *who, int d, int nlist, int kind, int pq_m, int pq_bits) {
-  if (d <= 0 || kind < ASL_INDEX_FLAT || kind > ASL_INDEX_IVFPQ) return fail(ASL_ERR_INVALID, "%s: bad d/kind", who);
-  if (kind != ASL_INDEX_FLAT && nlist <= 0) return fail(ASL_ERR_INVALID, "%s: nlist must be positive", who);
+  if (d <= 0 || kind < ASL_INDEX_FLAT || kind > ASL_INDEX_WINFLAT) return fail(ASL_ERR_INVALID, "%s: bad d/kind", who);
+  if (ivf_kind(kind) && nlist <= 0) return fail(ASL_ERR_INVALID, "%s: nlist must be positive", who);
   if (kind != ASL_INDEX_IVFPQ) return ASL_OK;
   if (pq_bits < 1 || pq_bits > 8) return fail(ASL_ERR_INVALID, "%s: pq_bits=%d outside 1..8", who, pq_bits);
   if (!(pq_m == 4 || pq_m == 8 || pq_m == 16 || pq_m == 32 || pq_m == 64))
@@ -60,7 +60,7 @@ asl_index_t *asl_index_create(int32_t d, int32_t nlist, int32_t kind, int32_t pq
   if (ensure_device() != ASL_OK) return nullptr;
   asl_index *ix = new asl_index();
   ix->d = d;
-  ix->nlist = kind == ASL_INDEX_FLAT ? 0 : nlist;
+  ix->nlist = ivf_kind(kind) ? nlist : 0;
   ix->kind = kind;
   if (kind == ASL_INDEX_IVFPQ) {
     ix->pq_m = pq_m;
@@ -68,7 +68,7 @@ asl_index_t *asl_index_create(int32_t d, int32_t nlist, int32_t kind, int32_t pq
     ix->ksub = 1 << pq_bits;
     ix->dsub = d / pq_m;
   }
-  ix->trained = kind == ASL_INDEX_FLAT;
+  ix->trained = !ivf_kind(kind);      // Flat and the window-exact index store the vectors as given
   return ix;
 }
 
@@ -84,7 +84,8 @@ int asl_index_set_unordered(asl_index_t *ix, int32_t unordered) {
 
 int asl_index_set_flat_storage(asl_index_t *ix, int32_t mode) {
   clear_error();
-  if (!ix || ix->kind != ASL_INDEX_IVFFLAT) return fail(ASL_ERR_INVALID, "set_flat_storage: an IVF-Flat index is required");
+  if (!ix || (ix->kind != ASL_INDEX_IVFFLAT && ix->kind != ASL_INDEX_WINFLAT))
+    return fail(ASL_ERR_INVALID, "set_flat_storage: an IVF-Flat or window-exact index is required");
   if (mode != ASL_FLAT_FX22 && mode != ASL_FLAT_F32) return fail(ASL_ERR_INVALID, "set_flat_storage: ASL_FLAT_FX22 or ASL_FLAT_F32");
   if (ix->ntotal > 0 && mode != ix->flat_storage)
     return fail(ASL_ERR_STATE, "set_flat_storage: set before add() (stored components are rounded as they arrive)");
@@ -113,6 +114,7 @@ int asl_index_set_window_scan(asl_index_t *ix, int32_t on) {
   clear_error();
   if (!ix) return fail(ASL_ERR_INVALID, "set_window_scan: null index");
   if (on != 0 && on != 1) return fail(ASL_ERR_INVALID, "set_window_scan: 0 (post-filter) or 1 (window scan)");
+  if (ix->kind == ASL_INDEX_WINFLAT) return ASL_OK;      // the window is always the scan's: there is no other mode
   if (on)
     if (const char *why = window_unsupported(ix)) return fail(ASL_ERR_STATE, "%s", why);
   ix->window_scan = on;
@@ -142,6 +144,8 @@ int asl_index_get_by_residual(const asl_index_t *ix) { return ix && ix->kind == 
 int asl_index_set_trained(asl_index_t *ix, const float *centroids, const float *codebooks) {
   clear_error();
   if (!ix) return fail(ASL_ERR_INVALID, "set_trained: null index");
+  if (ix->kind == ASL_INDEX_WINFLAT)
+    return fail(ASL_ERR_STATE, "set_trained: a window-exact index has no quantiser to install");
   ASL_TRY(ensure_device());
   if (ix->kind != ASL_INDEX_FLAT) {
     if (!centroids) return fail(ASL_ERR_INVALID, "set_trained: centroids required");
@@ -167,6 +171,8 @@ int asl_index_add(asl_index_t *ix, int64_t n, const float *x) { return index_add
 // FAISS file keeps FAISS' own assignments, bit for bit whatever its BLAS rounded).
 int asl_index_add_preassigned(asl_index_t *ix, int64_t n, const float *x, const int32_t *lists) {
   if (!lists) return fail(ASL_ERR_INVALID, "add_preassigned: null list assignment");
+  if (ix && ix->kind == ASL_INDEX_WINFLAT)
+    return fail(ASL_ERR_STATE, "add_preassigned: a window-exact index has one list, nothing to assign (use add)");
   if (!ix || ix->kind == ASL_INDEX_FLAT) return fail(ASL_ERR_INVALID, "add_preassigned: an IVF index is required");
   return index_add_impl(ix, n, x, lists);
 }
@@ -182,7 +188,7 @@ static int index_add_impl(asl_index_t *ix, int64_t n, const float *x, const int3
   ASL_TRY(ensure_device());
   In<float> dx;
   ASL_TRY(dx.init(x, (size_t)n * ix->d));
-  if (ix->kind != ASL_INDEX_FLAT) {
+  if (ivf_kind(ix->kind)) {
     ASL_TRY(ix->ws_assign.reserve((size_t)n));
     if (lists) {
       std::vector<int32_t> h((size_t)n);
@@ -232,7 +238,8 @@ static int index_add_impl(asl_index_t *ix, int64_t n, const float *x, const int3
     }
   } else {
     ASL_TRY(dev_append(ix->vecs, (size_t)ix->n_store * ix->d, dx.d, (size_t)n * ix->d));
-    if (ix->kind == ASL_INDEX_IVFFLAT && ix->flat_storage == ASL_FLAT_FX22)      // stored components: 22-bit fixed point
+    if ((ix->kind == ASL_INDEX_IVFFLAT || ix->kind == ASL_INDEX_WINFLAT) &&
+        ix->flat_storage == ASL_FLAT_FX22)                                       // stored components: 22-bit fixed point
       ASL_TRY(quantize_fx22(ix->vecs.p + (size_t)ix->n_store * ix->d, n * ix->d));
   }
   ASL_TRY(sync_stream());
@@ -246,6 +253,8 @@ static int index_add_impl(asl_index_t *ix, int64_t n, const float *x, const int3
 int asl_index_set_refine(asl_index_t *ix, int32_t kprime) {
   clear_error();
   if (!ix) return fail(ASL_ERR_INVALID, "set_refine: null index");
+  if (ix->kind == ASL_INDEX_WINFLAT)
+    return fail(ASL_ERR_STATE, "set_refine: a window-exact index scores exactly already, there is nothing to re-rank");
   if (ix->kind != ASL_INDEX_IVFPQ) return fail(ASL_ERR_INVALID, "set_refine: an IVF-PQ index is required");
   if (kprime < 0 || kprime > TK_MAX_K) return fail(ASL_ERR_INVALID, "set_refine: k' must be in 0..%d", TK_MAX_K);
   if (kprime > 0 && !ix->refine_rows) {
@@ -301,7 +310,7 @@ int asl_index_info(const asl_index_t *ix, asl_index_info_t *info) {
 
 int asl_index_get_centroids(const asl_index_t *ix, float *out) {
   clear_error();
-  if (!ix || !out || ix->kind == ASL_INDEX_FLAT || !ix->trained)
+  if (!ix || !out || !ivf_kind(ix->kind) || !ix->trained)
     return fail(ASL_ERR_STATE, "get_centroids: not available");
   HIP_TRY(hipMemcpyAsync(out, ix->centroids.p, (size_t)ix->nlist * ix->d * 4, hipMemcpyDefault, stream()));
   return sync_stream();

@@ -112,7 +112,13 @@ struct asl_index {
   uint64_t win_serial = 0;       // serial of the library whose window column is the key; 0: a caller's key
   uint64_t win_gen = 0;          // ... and the generation of its selection
   int window_scan = 0;           // asl_index_set_window_scan: asl_search_batch scans each query's window only
-  asl::DevBuf<int2> win_ranges;       // [nq, nprobe] in-window run of each probed list
+  asl::DevBuf<int2> win_ranges;       // [nq, nprobe] in-window run of each probed list (WINFLAT: [nq], one run per query)
+  // ASL_INDEX_WINFLAT (the window-exact index): ONE list of all vectors cut into postings blocks -- ids (the
+  // id per position), blk_base, inv_tab / inv_tab8, inv_data, has_inv, inv_layout below, as IVF-Flat with one
+  // list -- in id order, or, once a key is installed (win_ready; win_serial / win_gen as above), ordered by
+  // (key ascending, NaN last, id ascending) with the key per position here. Derived, never saved; dropped by
+  // add, reset and a new key.
+  asl::DevBuf<float> wf_key;          // [n_store] the key by position
   // sub-quantiser-major copy of codes_tiled (index_codes_mmajor; pq_scan_v3.hip, MM): 32 planes of mm_plane bytes,
   // plane m = sub-quantiser m's 64 bytes of every tile of the default layout, in tile order. The plain tiled scan
   // reads it instead of codes_tiled and skips the planes of a query's all-zero sub-vectors. Derived on the device,
@@ -144,6 +150,7 @@ struct asl_index {
   int flat_storage = ASL_FLAT_F32;   // ASL_FLAT_F32 (default): components as given; ASL_FLAT_FX22: add() rounds
                                      // components in [0, 1) to 22 fractional bits
   int inv_layout = 0;            // what build_lists found the data fit for: 0 none, 1 float postings, 2 fixed-point words
+  int nnz_max = 0;               // the most non-zeros of a stored vector, as build_postings counted them
   int tab_stride = 0;            // bytes per block of inv_tab8 (d rounded up to a 128-byte line)
   asl::DevBuf<uint8_t> inv_tab8;
   asl::DevBuf<uint16_t> inv_cnt16;    // postings per (block, dimension): work accounting only (asl_index_postings_work)
@@ -181,6 +188,10 @@ int index_shape_check(const char *who, int d, int nlist, int kind, int pq_m, int
 // 2-byte entries behind an 8-byte head in the 2 KB of its tile table: d * 2 + 8 <= 2048. A wider index
 // of that m and bits gets no tiles and is scanned by the generic kernel, like every other shape.
 constexpr int PQ_TILED_MAX_D = 1020;
+// the kinds with inverted lists, a coarse quantiser and training (not Flat, not the one-list window-exact index)
+inline bool ivf_kind(int kind) { return kind == ASL_INDEX_IVFFLAT || kind == ASL_INDEX_IVFPQ; }
+// asl_search_batch scans each query's window only: the index's mode, or the kind that has no other
+inline bool window_mode(const asl_index *ix) { return ix->window_scan || ix->kind == ASL_INDEX_WINFLAT; }
 inline bool tiled_index(const asl_index *ix) {
   return ix->kind == ASL_INDEX_IVFPQ && ix->pq_m == 32 && ix->ksub == 256 && ix->d <= PQ_TILED_MAX_D;
 }
@@ -189,6 +200,14 @@ int assign_ip(asl_index *ix, const float *x, int64_t ld, int64_t n, const float 
               int32_t *assign_dev);
 // index_lists.hip
 int build_lists(asl_index *ix);
+// the per-dimension postings of ix->vecs for a position order (order[i]: the add-order row at position i; blk_off:
+// [nlists + 1] first block of each list; pos_blk / pos_loc: block and local index per position): float postings,
+// or the fixed-point words when ix->flat_storage is fx22 and every non-zero is on the grid. Sets has_inv /
+// inv_layout; leaves them clear when the vectors are too dense or the layout does not fit its offsets.
+int build_postings(asl_index *ix, const int32_t *order_dev, int64_t n, const std::vector<int32_t> &blk_off,
+                   const std::vector<int32_t> &pos_blk, const std::vector<uint16_t> &pos_loc);
+// the one-list layout of a window-exact index: in id order, or (keyed) by (key, NaN last, id)
+int winflat_layout(asl_index *ix, bool keyed, const float *key, uint64_t serial, uint64_t gen);
 const char *window_unsupported(const asl_index *ix);
 int window_install(asl_index *ix, int64_t n, const float *key, uint64_t serial, uint64_t gen = 0);
 int post_filter_pairs(asl_index *ix, const IndexPostFilter &p, uint64_t serial, uint64_t gen,

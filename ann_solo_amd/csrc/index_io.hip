@@ -43,7 +43,7 @@ int asl_index_save(const asl_index_t *ix, const char *path) {
   h.shard_world = ix->shard_world;
   h.has_vids = ix->has_vids;
   h.pad = ix->refine_rows ? (1 | (ix->refine_k << 1)) : 0;   // IVF-PQ: exact rows follow the payload
-  if (ix->kind == ASL_INDEX_IVFFLAT) h.pad = ix->flat_storage;   // IVF-Flat: component storage mode
+  if (ix->kind == ASL_INDEX_IVFFLAT || ix->kind == ASL_INDEX_WINFLAT) h.pad = ix->flat_storage;   // component storage mode
   if (ix->kind == ASL_INDEX_IVFPQ && !ix->by_residual) {          // (a by-residual index: byte for byte version 2)
     h.version = 3;
     h.pad |= PAD_PQ_RAW;
@@ -59,10 +59,10 @@ int asl_index_save(const asl_index_t *ix, const char *path) {
     ok = fwrite(tmp.data(), 1, bytes, f) == bytes;
   };
   (void)hipStreamSynchronize(stream());
-  if (ix->trained && ix->kind != ASL_INDEX_FLAT) dump(ix->centroids.p, (size_t)ix->nlist * ix->d * 4);
+  if (ix->trained && ivf_kind(ix->kind)) dump(ix->centroids.p, (size_t)ix->nlist * ix->d * 4);
   if (ix->trained && ix->kind == ASL_INDEX_IVFPQ) dump(ix->codebooks.p, (size_t)ix->pq_m * ix->ksub * ix->dsub * 4);
   const size_t n = (size_t)ix->n_store;
-  if (ix->kind != ASL_INDEX_FLAT) dump(ix->vlist.p, n * 4);
+  if (ivf_kind(ix->kind)) dump(ix->vlist.p, n * 4);
   if (ix->has_vids) dump(ix->vids.p, n * 4);
   if (ix->kind == ASL_INDEX_IVFPQ)
     dump(ix->codes_add.p, n * ix->pq_m);
@@ -106,17 +106,19 @@ asl_index_t *asl_index_load(const char *path) {
   {  // ... and every count below sizes a host vector or a device allocation
     const char *bad = nullptr;
     const bool ivf = h.kind == ASL_INDEX_IVFFLAT || h.kind == ASL_INDEX_IVFPQ;
-    raw = h.kind != ASL_INDEX_IVFFLAT && h.pad >= 0 && (h.pad & PAD_PQ_RAW);
+    raw = h.kind != ASL_INDEX_IVFFLAT && h.kind != ASL_INDEX_WINFLAT && h.pad >= 0 && (h.pad & PAD_PQ_RAW);
     if (raw) h.pad &= ~PAD_PQ_RAW;      // (the refine bits below it are checked and read as ever)
     if (h.version < 1 || h.version > 3) bad = "unsupported version";
-    else if (h.kind < ASL_INDEX_FLAT || h.kind > ASL_INDEX_IVFPQ) bad = "unknown index kind";
+    else if (h.kind < ASL_INDEX_FLAT || h.kind > ASL_INDEX_WINFLAT) bad = "unknown index kind";
     else if (h.d <= 0 || h.d > (1 << 20)) bad = "bad dimension";
     else if (ivf && (h.nlist <= 0 || h.nlist > (1 << 24))) bad = "bad nlist";
     else if (h.n_store < 0 || h.ntotal < h.n_store || h.ntotal >= ((int64_t)1 << 31)) bad = "bad vector counts";
     else if (h.niter < 0 || (h.trained != 0 && h.trained != 1) || (h.has_vids != 0 && h.has_vids != 1)) bad = "bad flags";
     else if (h.shard_world < 1 || h.shard_rank < 0 || h.shard_rank >= h.shard_world) bad = "bad shard fields";
     else if (!h.trained && h.n_store > 0 && ivf) bad = "vectors in an untrained index";
-    else if (h.kind == ASL_INDEX_IVFFLAT ? (h.pad != ASL_FLAT_FX22 && h.pad != ASL_FLAT_F32)
+    else if (h.kind == ASL_INDEX_WINFLAT && (h.has_vids || h.shard_world != 1 || h.n_store != h.ntotal || !h.trained))
+      bad = "bad fields for a window-exact index";
+    else if (h.kind == ASL_INDEX_IVFFLAT || h.kind == ASL_INDEX_WINFLAT ? (h.pad != ASL_FLAT_FX22 && h.pad != ASL_FLAT_F32)
                                          : (h.pad < 0 || ((h.pad & 1) && h.kind != ASL_INDEX_IVFPQ) || (h.pad >> 1) > TK_MAX_K))
       bad = "bad refine / storage fields";
     else if (raw && (h.kind != ASL_INDEX_IVFPQ || h.version < 3)) bad = "bad refine / storage fields";
@@ -141,7 +143,7 @@ asl_index_t *asl_index_load(const char *path) {
   }
   asl_index *ix = new asl_index();
   ix->d = h.d;
-  ix->nlist = h.nlist;
+  ix->nlist = h.kind == ASL_INDEX_WINFLAT ? 0 : h.nlist;      // (unread by that kind)
   ix->kind = h.kind;
   ix->pq_m = h.pq_m;
   ix->pq_bits = h.pq_bits;
@@ -170,15 +172,16 @@ asl_index_t *asl_index_load(const char *path) {
         hipMemcpy(buf.p, tmp.data(), count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
       ok = false;
   };
-  if (ix->trained && ix->kind != ASL_INDEX_FLAT) slurp(ix->centroids, (size_t)ix->nlist * ix->d);
+  if (ix->trained && ivf_kind(ix->kind)) slurp(ix->centroids, (size_t)ix->nlist * ix->d);
   if (ix->trained && ix->kind == ASL_INDEX_IVFPQ) slurp(ix->codebooks, (size_t)ix->pq_m * ix->ksub * ix->dsub);
   const size_t n = (size_t)ix->n_store;
-  if (ix->kind != ASL_INDEX_FLAT) slurp(ix->vlist, n);
+  if (ivf_kind(ix->kind)) slurp(ix->vlist, n);
   if (ix->has_vids) slurp(ix->vids, n);
   if (ix->kind == ASL_INDEX_IVFPQ)
     slurp(ix->codes_add, n * ix->pq_m);
   else
     slurp(ix->vecs, n * ix->d);
+  if (ix->kind == ASL_INDEX_WINFLAT) ix->flat_storage = h.pad;
   if (ix->kind == ASL_INDEX_IVFFLAT) {
     ix->flat_storage = h.pad;
     // version 1: the field was 0 both for fixed-point files and for the unrounded float32 files
@@ -204,10 +207,10 @@ asl_index_t *asl_index_load(const char *path) {
     }
   }
   fclose(f);
-  if (ok && ix->n_store > 0 && (ix->kind != ASL_INDEX_FLAT || ix->has_vids)) {
+  if (ok && ix->n_store > 0 && (ivf_kind(ix->kind) || ix->has_vids)) {
     // list assignments / global ids index host and device arrays later: range-check them now
     std::vector<int32_t> tmp((size_t)ix->n_store);
-    if (ix->kind != ASL_INDEX_FLAT) {
+    if (ivf_kind(ix->kind)) {
       ok = hipMemcpy(tmp.data(), ix->vlist.p, tmp.size() * 4, hipMemcpyDeviceToHost) == hipSuccess;
       for (size_t i = 0; ok && i < tmp.size(); i++) ok = tmp[i] >= 0 && tmp[i] < ix->nlist;
     }

@@ -1,5 +1,6 @@
 // index_lists.hip -- the scan layouts derived from the add-order storage: inverted lists, IVF-PQ tiles,
-// IVF-Flat postings, the window-ordered tiles, the (id, window value) pairs of the scans' post-filter.
+// IVF-Flat postings, the window-ordered tiles, the one precursor-ordered list of the window-exact index, the
+// (id, window value) pairs of the scans' post-filter.
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -8,9 +9,112 @@
 
 namespace asl {
 
+// The per-dimension postings (flat_scan.hip) of ix->vecs in a position order: the builder of the IVF-Flat lists
+// and of the one list of the window-exact index (index.hpp says what the arguments are).
+int build_postings(asl_index *ix, const int32_t *order_dev, int64_t n, const std::vector<int32_t> &blk_off,
+                   const std::vector<int32_t> &pos_blk, const std::vector<uint16_t> &pos_loc) {
+  DevBuf<int32_t> nnz, nnz_max;
+  ASL_TRY(nnz.reserve((size_t)n));
+  ASL_TRY(nnz_max.reserve(2));
+  ASL_TRY(count_nnz(ix->vecs.p, ix->d, n, nnz.p, nnz_max.p));
+  int32_t h_nm[2] = {0, 0};
+  ASL_TRY(nnz_max.download(h_nm, 2));
+  ASL_TRY(sync_stream());
+  const int32_t h_max = h_nm[0];
+  ix->nnz_max = h_max;
+  // every non-zero on the 2^-22 grid inside (0, 1): posting words (flat_scan.hip, FX)
+  // (the window-exact index: only in fixed-point storage mode)
+  const bool fixed_point = h_nm[1] == 0 && ix->d <= 1024 && FI_BLK <= 1024 &&
+                           (ix->kind != ASL_INDEX_WINFLAT || ix->flat_storage == ASL_FLAT_FX22);
+  // dimension-major postings (the default IVF-Flat scan)
+  if (h_max > 0 && (size_t)h_max * 8 < (size_t)ix->d) {
+    const size_t nblk = (size_t)std::max<int32_t>(blk_off.back(), 1);
+    ix->n_blocks = blk_off.back();
+    const size_t ncell = nblk * (size_t)ix->d;
+    DevBuf<int32_t> pos_blk_dev;
+    DevBuf<uint16_t> pos_loc_dev;
+    DevBuf<uint32_t> cnt_dev;
+    ASL_TRY(pos_blk_dev.upload(pos_blk.data(), (size_t)n));
+    ASL_TRY(pos_loc_dev.upload(pos_loc.data(), (size_t)n));
+    ASL_TRY(cnt_dev.reserve(ncell));
+    HIP_TRY(hipMemsetAsync(cnt_dev.p, 0, ncell * 4, stream()));
+    ASL_TRY(inv_count(ix->vecs.p, ix->d, order_dev, pos_blk_dev.p, n, cnt_dev.p));
+    std::vector<uint32_t> h_cnt(ncell);
+    ASL_TRY(cnt_dev.download(h_cnt.data(), ncell));
+    ASL_TRY(sync_stream());
+    ix->inv_layout = 0;
+    if (fixed_point) {
+      // whole lines of 32 posting words per (block, dimension); the table byte is the line count
+      const int stride = (ix->d + 127) & ~127;
+      std::vector<uint8_t> h_tab8(nblk * (size_t)stride, 0);
+      std::vector<uint16_t> h_c16(ncell);
+      std::vector<uint32_t> h_line(ncell), h_base(nblk);
+      uint64_t run = 0;     // 128-byte lines
+      for (size_t b = 0; b < nblk; b++) {
+        h_base[b] = (uint32_t)run;
+        for (int j = 0; j < ix->d; j++) {
+          const uint32_t c = h_cnt[b * (size_t)ix->d + j];       // <= FI_BLK: at most 26 lines
+          h_line[b * (size_t)ix->d + j] = (uint32_t)run;
+          h_c16[b * (size_t)ix->d + j] = (uint16_t)c;
+          h_tab8[b * (size_t)stride + j] = (uint8_t)((c + 31) / 32);
+          run += (c + 31) / 32;
+        }
+      }
+      if (run < (1ull << 32)) {
+        const size_t bytes = (size_t)std::max<uint64_t>(run, 1) * 128 + 512;
+        DevBuf<uint32_t> line_dev;
+        ASL_TRY(line_dev.upload(h_line.data(), ncell));
+        ASL_TRY(ix->blk_offsets.upload(blk_off.data(), blk_off.size()));
+        ASL_TRY(ix->blk_base.upload(h_base.data(), nblk));
+        ASL_TRY(ix->inv_tab8.upload(h_tab8.data(), h_tab8.size()));
+        ASL_TRY(ix->inv_cnt16.upload(h_c16.data(), ncell));
+        ASL_TRY(ix->inv_data.reserve(bytes));
+        HIP_TRY(hipMemsetAsync(ix->inv_data.p, 0, bytes, stream()));
+        HIP_TRY(hipMemsetAsync(cnt_dev.p, 0, ncell * 4, stream()));
+        ASL_TRY(fx_fill(ix->vecs.p, ix->d, order_dev, pos_blk_dev.p, pos_loc_dev.p, n, line_dev.p,
+                        cnt_dev.p, reinterpret_cast<uint32_t *>(ix->inv_data.p)));
+        ASL_TRY(fx_order((int64_t)ncell, line_dev.p, cnt_dev.p, reinterpret_cast<uint32_t *>(ix->inv_data.p)));
+        ASL_TRY(sync_stream());
+        ix->tab_stride = stride;
+        ix->has_inv = true;
+        ix->inv_layout = 2;
+      }
+    }
+    if (!ix->has_inv) {
+    // segments placed block by block (flat_scan.hip: inv_place_block)
+    std::vector<uint32_t> h_tab(ncell), h_base(nblk);
+    uint64_t run = 0;     // 64-byte units
+    bool ok = true;
+    for (size_t b = 0; b < nblk && ok; b++) {
+      h_base[b] = (uint32_t)run;
+      run += inv_place_block(h_cnt.data() + b * (size_t)ix->d, ix->d, h_tab.data() + b * (size_t)ix->d, &ok);
+      run += run & 1ull;      // every block starts on a 128-byte line
+    }
+    if (ok && run < (1ull << 32)) {     // 32-bit unit offsets (256 GB of postings)
+      // (+ 512: the scan reads a full wave-width from the start of an empty segment)
+      const size_t bytes = (size_t)std::max<uint64_t>(run, 2) * 64 + 512;
+      ASL_TRY(ix->blk_offsets.upload(blk_off.data(), blk_off.size()));
+      ASL_TRY(ix->blk_base.upload(h_base.data(), nblk));
+      ASL_TRY(ix->inv_tab.upload(h_tab.data(), ncell));
+      ASL_TRY(ix->inv_data.reserve(bytes));
+      HIP_TRY(hipMemsetAsync(ix->inv_data.p, 0, bytes, stream()));
+      HIP_TRY(hipMemsetAsync(cnt_dev.p, 0, ncell * 4, stream()));
+      ASL_TRY(inv_fill(ix->vecs.p, ix->d, order_dev, pos_blk_dev.p, pos_loc_dev.p, n,
+                       ix->blk_base.p, ix->inv_tab.p, cnt_dev.p, ix->inv_data.p));
+      ASL_TRY(inv_order((int64_t)nblk, ix->d, ix->blk_base.p, ix->inv_tab.p, ix->inv_data.p));
+      ASL_TRY(sync_stream());
+      ix->has_inv = true;
+      ix->inv_layout = 1;
+    }
+    }
+  }
+  return ASL_OK;
+}
+
 // list-ordered copy of the PQ codes (the scan layout) from the add-order master
 int build_lists(asl_index *ix) {
   if (!ix->lists_dirty) return ASL_OK;
+  if (ix->kind == ASL_INDEX_WINFLAT) return winflat_layout(ix, false, nullptr, 0, 0);   // (no key: id order)
   ix->agreed_val = -1;
   ix->idpay_ready = false;
   ix->win_ready = false;
@@ -72,112 +176,68 @@ int build_lists(asl_index *ix) {
   }
   ix->has_inv = false;
   if (ix->kind == ASL_INDEX_IVFFLAT && n > 0 && ix->d <= 65535) {
-    DevBuf<int32_t> nnz, nnz_max;
-    ASL_TRY(nnz.reserve((size_t)n));
-    ASL_TRY(nnz_max.reserve(2));
-    ASL_TRY(count_nnz(ix->vecs.p, ix->d, n, nnz.p, nnz_max.p));
-    int32_t h_nm[2] = {0, 0};
-    ASL_TRY(nnz_max.download(h_nm, 2));
-    ASL_TRY(sync_stream());
-    const int32_t h_max = h_nm[0];
-    // every non-zero on the 2^-22 grid inside (0, 1): posting words (flat_scan.hip, FX)
-    const bool fixed_point = h_nm[1] == 0 && ix->d <= 1024 && FI_BLK <= 1024;
-    // dimension-major postings (the default IVF-Flat scan)
-    if (h_max > 0 && (size_t)h_max * 8 < (size_t)ix->d) {
-      std::vector<int32_t> blk_off((size_t)ix->nlist + 1, 0), pos_blk((size_t)n);
-      std::vector<uint16_t> pos_loc((size_t)n);
-      for (int l = 0; l < ix->nlist; l++)
-        blk_off[(size_t)l + 1] =
-            blk_off[(size_t)l] + (off[(size_t)l + 1] - off[(size_t)l] + FI_BLK - 1) / FI_BLK;
-      for (int l = 0; l < ix->nlist; l++)
-        for (int32_t i = off[(size_t)l]; i < off[(size_t)l + 1]; i++) {
-          const int32_t r = i - off[(size_t)l];
-          pos_blk[(size_t)i] = blk_off[(size_t)l] + r / FI_BLK;
-          pos_loc[(size_t)i] = (uint16_t)(r % FI_BLK);
-        }
-      const size_t nblk = (size_t)std::max<int32_t>(blk_off[(size_t)ix->nlist], 1);
-      ix->n_blocks = blk_off[(size_t)ix->nlist];
-      const size_t ncell = nblk * (size_t)ix->d;
-      DevBuf<int32_t> pos_blk_dev;
-      DevBuf<uint16_t> pos_loc_dev;
-      DevBuf<uint32_t> cnt_dev;
-      ASL_TRY(pos_blk_dev.upload(pos_blk.data(), (size_t)n));
-      ASL_TRY(pos_loc_dev.upload(pos_loc.data(), (size_t)n));
-      ASL_TRY(cnt_dev.reserve(ncell));
-      HIP_TRY(hipMemsetAsync(cnt_dev.p, 0, ncell * 4, stream()));
-      ASL_TRY(inv_count(ix->vecs.p, ix->d, order.p, pos_blk_dev.p, n, cnt_dev.p));
-      std::vector<uint32_t> h_cnt(ncell);
-      ASL_TRY(cnt_dev.download(h_cnt.data(), ncell));
-      ASL_TRY(sync_stream());
-      ix->inv_layout = 0;
-      if (fixed_point) {
-        // whole lines of 32 posting words per (block, dimension); the table byte is the line count
-        const int stride = (ix->d + 127) & ~127;
-        std::vector<uint8_t> h_tab8(nblk * (size_t)stride, 0);
-        std::vector<uint16_t> h_c16(ncell);
-        std::vector<uint32_t> h_line(ncell), h_base(nblk);
-        uint64_t run = 0;     // 128-byte lines
-        for (size_t b = 0; b < nblk; b++) {
-          h_base[b] = (uint32_t)run;
-          for (int j = 0; j < ix->d; j++) {
-            const uint32_t c = h_cnt[b * (size_t)ix->d + j];       // <= FI_BLK: at most 26 lines
-            h_line[b * (size_t)ix->d + j] = (uint32_t)run;
-            h_c16[b * (size_t)ix->d + j] = (uint16_t)c;
-            h_tab8[b * (size_t)stride + j] = (uint8_t)((c + 31) / 32);
-            run += (c + 31) / 32;
-          }
-        }
-        if (run < (1ull << 32)) {
-          const size_t bytes = (size_t)std::max<uint64_t>(run, 1) * 128 + 512;
-          DevBuf<uint32_t> line_dev;
-          ASL_TRY(line_dev.upload(h_line.data(), ncell));
-          ASL_TRY(ix->blk_offsets.upload(blk_off.data(), blk_off.size()));
-          ASL_TRY(ix->blk_base.upload(h_base.data(), nblk));
-          ASL_TRY(ix->inv_tab8.upload(h_tab8.data(), h_tab8.size()));
-          ASL_TRY(ix->inv_cnt16.upload(h_c16.data(), ncell));
-          ASL_TRY(ix->inv_data.reserve(bytes));
-          HIP_TRY(hipMemsetAsync(ix->inv_data.p, 0, bytes, stream()));
-          HIP_TRY(hipMemsetAsync(cnt_dev.p, 0, ncell * 4, stream()));
-          ASL_TRY(fx_fill(ix->vecs.p, ix->d, order.p, pos_blk_dev.p, pos_loc_dev.p, n, line_dev.p,
-                          cnt_dev.p, reinterpret_cast<uint32_t *>(ix->inv_data.p)));
-          ASL_TRY(fx_order((int64_t)ncell, line_dev.p, cnt_dev.p, reinterpret_cast<uint32_t *>(ix->inv_data.p)));
-          ASL_TRY(sync_stream());
-          ix->tab_stride = stride;
-          ix->has_inv = true;
-          ix->inv_layout = 2;
-        }
+    std::vector<int32_t> blk_off((size_t)ix->nlist + 1, 0), pos_blk((size_t)n);
+    std::vector<uint16_t> pos_loc((size_t)n);
+    for (int l = 0; l < ix->nlist; l++)
+      blk_off[(size_t)l + 1] =
+          blk_off[(size_t)l] + (off[(size_t)l + 1] - off[(size_t)l] + FI_BLK - 1) / FI_BLK;
+    for (int l = 0; l < ix->nlist; l++)
+      for (int32_t i = off[(size_t)l]; i < off[(size_t)l + 1]; i++) {
+        const int32_t r = i - off[(size_t)l];
+        pos_blk[(size_t)i] = blk_off[(size_t)l] + r / FI_BLK;
+        pos_loc[(size_t)i] = (uint16_t)(r % FI_BLK);
       }
-      if (!ix->has_inv) {
-      // segments placed block by block (flat_scan.hip: inv_place_block)
-      std::vector<uint32_t> h_tab(ncell), h_base(nblk);
-      uint64_t run = 0;     // 64-byte units
-      bool ok = true;
-      for (size_t b = 0; b < nblk && ok; b++) {
-        h_base[b] = (uint32_t)run;
-        run += inv_place_block(h_cnt.data() + b * (size_t)ix->d, ix->d, h_tab.data() + b * (size_t)ix->d, &ok);
-        run += run & 1ull;      // every block starts on a 128-byte line
-      }
-      if (ok && run < (1ull << 32)) {     // 32-bit unit offsets (256 GB of postings)
-        // (+ 512: the scan reads a full wave-width from the start of an empty segment)
-        const size_t bytes = (size_t)std::max<uint64_t>(run, 2) * 64 + 512;
-        ASL_TRY(ix->blk_offsets.upload(blk_off.data(), blk_off.size()));
-        ASL_TRY(ix->blk_base.upload(h_base.data(), nblk));
-        ASL_TRY(ix->inv_tab.upload(h_tab.data(), ncell));
-        ASL_TRY(ix->inv_data.reserve(bytes));
-        HIP_TRY(hipMemsetAsync(ix->inv_data.p, 0, bytes, stream()));
-        HIP_TRY(hipMemsetAsync(cnt_dev.p, 0, ncell * 4, stream()));
-        ASL_TRY(inv_fill(ix->vecs.p, ix->d, order.p, pos_blk_dev.p, pos_loc_dev.p, n,
-                         ix->blk_base.p, ix->inv_tab.p, cnt_dev.p, ix->inv_data.p));
-        ASL_TRY(inv_order((int64_t)nblk, ix->d, ix->blk_base.p, ix->inv_tab.p, ix->inv_data.p));
-        ASL_TRY(sync_stream());
-        ix->has_inv = true;
-        ix->inv_layout = 1;
-      }
-      }
-    }
+    ASL_TRY(build_postings(ix, order.p, n, blk_off, pos_blk, pos_loc));
   }
   ASL_TRY(sync_stream());
   ix->lists_dirty = false;
+  return ASL_OK;
+}
+
+// The derived layout of the window-exact index (ASL_INDEX_WINFLAT): all vectors as ONE list, in id
+// order (not keyed: what asl_index_search needs) or ordered by (key ascending, NaN last, id ascending) --
+// the order window_install uses inside a list -- cut into blocks of FI_BLK consecutive positions with the
+// postings of build_postings, plus the id and the key per position. key: [n_store], host or device.
+int winflat_layout(asl_index *ix, bool keyed, const float *key, uint64_t serial, uint64_t gen) {
+  const int64_t n = ix->n_store;
+  ix->win_ready = false;
+  ix->win_serial = ix->win_gen = 0;
+  ix->has_inv = false;
+  ix->inv_layout = 0;
+  ix->n_blocks = 0;
+  std::vector<int32_t> h_order((size_t)n);
+  std::iota(h_order.begin(), h_order.end(), 0);
+  if (keyed && n) {
+    std::vector<float> h_key((size_t)n), h_wkey((size_t)n);
+    HIP_TRY(hipMemcpy(h_key.data(), key, (size_t)n * 4, hipMemcpyDefault));
+    std::sort(h_order.begin(), h_order.end(), [&](int32_t x, int32_t y) {
+      const float kx = h_key[(size_t)x], ky = h_key[(size_t)y];
+      const bool nx = std::isnan(kx), ny = std::isnan(ky);
+      if (nx != ny) return ny;
+      if (!nx && kx != ky) return kx < ky;
+      return x < y;
+    });
+    for (int64_t i = 0; i < n; i++) h_wkey[(size_t)i] = h_key[(size_t)h_order[(size_t)i]];
+    ASL_TRY(ix->wf_key.upload(h_wkey.data(), (size_t)n));
+    ASL_TRY(sync_stream());
+  }
+  ASL_TRY(ix->ids.upload(h_order.data(), (size_t)n));
+  if (n > 0 && ix->d <= 65535) {
+    std::vector<int32_t> blk_off = {0, (int32_t)((n + FI_BLK - 1) / FI_BLK)}, pos_blk((size_t)n);
+    std::vector<uint16_t> pos_loc((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+      pos_blk[(size_t)i] = (int32_t)(i / FI_BLK);
+      pos_loc[(size_t)i] = (uint16_t)(i % FI_BLK);
+    }
+    ASL_TRY(build_postings(ix, ix->ids.p, n, blk_off, pos_blk, pos_loc));
+  }
+  ASL_TRY(sync_stream());
+  ix->lists_dirty = false;
+  if (keyed) {
+    ix->win_ready = true;
+    ix->win_serial = serial;
+    ix->win_gen = gen;
+  }
   return ASL_OK;
 }
 
@@ -252,6 +312,12 @@ const char *window_unsupported(const asl_index *ix) {
 // key per slot. (serial, gen) record where the key came from (asl_library serial and the generation of its
 // selection; 0: the caller's).
 int window_install(asl_index *ix, int64_t n, const float *key, uint64_t serial, uint64_t gen) {
+  if (ix->kind == ASL_INDEX_WINFLAT) {      // the one-list layout in key order
+    if (n != ix->ntotal) return fail(ASL_ERR_INVALID, "window key: %lld keys for %lld vectors", (long long)n,
+                                     (long long)ix->ntotal);
+    if (n > 0 && !key) return fail(ASL_ERR_INVALID, "window key: null key");
+    return winflat_layout(ix, true, key, serial, gen);
+  }
   if (const char *why = window_unsupported(ix)) return fail(ASL_ERR_STATE, "%s", why);
   if (!ix->trained) return fail(ASL_ERR_STATE, "window key: index is not trained");
   if (n != ix->ntotal) return fail(ASL_ERR_INVALID, "window key: %lld keys for %lld vectors", (long long)n,
@@ -313,7 +379,8 @@ extern "C" {
 
 int asl_index_flat_layout(asl_index_t *ix) {
   clear_error();
-  if (!ix || ix->kind != ASL_INDEX_IVFFLAT) return fail(ASL_ERR_INVALID, "flat_layout: an IVF-Flat index is required");
+  if (!ix || (ix->kind != ASL_INDEX_IVFFLAT && ix->kind != ASL_INDEX_WINFLAT))
+    return fail(ASL_ERR_INVALID, "flat_layout: an IVF-Flat or window-exact index is required");
   if (ix->trained && ix->n_store > 0) {
     ASL_TRY(ensure_device());
     ASL_TRY(build_lists(ix));
@@ -332,7 +399,7 @@ int asl_index_get_lists(const asl_index_t *cix, int32_t *list_offsets, int32_t *
                         uint8_t *codes, float *vecs) {
   clear_error();
   asl_index *ix = const_cast<asl_index *>(cix);
-  if (!ix || ix->kind == ASL_INDEX_FLAT) return fail(ASL_ERR_STATE, "get_lists: IVF index required");
+  if (!ix || !ivf_kind(ix->kind)) return fail(ASL_ERR_STATE, "get_lists: IVF index required");
   ASL_TRY(build_lists(ix));
   const int64_t n = ix->n_store;
   if (list_offsets)

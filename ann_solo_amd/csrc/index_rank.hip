@@ -10,6 +10,7 @@ namespace asl {
 
 // what the index must be for a rank query; nullptr when it is, else why not
 static const char *rank_unsupported(const asl_index *ix) {
+  if (ix->kind == ASL_INDEX_WINFLAT) return "rank: not served by a window-exact index (IVF-Flat postings or tiled IVF-PQ)";
   if (ix->kind == ASL_INDEX_FLAT) return "rank: needs an IVF index (IVF-Flat postings or tiled IVF-PQ), not Flat";
   if (ix->shard_world > 1 || ix->has_vids) return "rank: does not run on a sharded index";
   if (ix->scan_variant != 0) return "rank: needs the layout-specific scan (scan_variant 0), not the generic kernels";

@@ -103,10 +103,43 @@ struct SearchPlan {
   bool use_inv = false, tiled = false;   // the layout-specific scan: postings (IVF-Flat) / tiles (IVF-PQ)
 };
 
+// The window-exact index (ASL_INDEX_WINFLAT): one list, no probes. What it does not serve is an error that names
+// the reason, never a filter behind the top-k. A selector that comes WITH a window is the fused path's (the
+// library's selection): the key column it installed is the effective one, NaN where unselected, so the runs
+// leave the unselected out and the selector itself is unread.
+static int validate_winflat(asl_index *ix, const IndexSearch &rq, const SearchPlan &pl) {
+  if (rq.gate || rq.pre_I || rq.pre_D)
+    return fail(ASL_ERR_STATE, "a window-exact index has no probe lists: no preassigned or gated search");
+  if (rq.pre_ent && !rq.xq) return fail(ASL_ERR_STATE, "a window-exact index takes no entry-list-only queries");
+  if (pl.unordered == 2) return fail(ASL_ERR_STATE, "packed-key rows are not served by a window-exact index");
+  if (rq.sel_keep && !rq.win)
+    return fail(ASL_ERR_STATE, "a window-exact index takes a selection through its key column (NaN: unselected), "
+                               "not a selector");
+  if (rq.win && !rq.win->q_pmz) return fail(ASL_ERR_INVALID, "window scan: null precursor m/z");
+  if (rq.nq <= 0) return ASL_OK;
+  if (!rq.xq) return fail(ASL_ERR_INVALID, "search: null queries");
+  if (rq.k <= 0) return fail(ASL_ERR_CAPACITY, "search: k=%d outside 1..%d", rq.k, TK_MAX_K - FLAT_KEYS_SLACK);
+  if (!keys_fit(rq.k))
+    return fail(ASL_ERR_STATE, "a window-exact index holds k <= %d (k=%d)", TK_MAX_K - FLAT_KEYS_SLACK, rq.k);
+  if (!flat_inv_supported(ix->d, rq.k, 1))
+    return fail(ASL_ERR_STATE, "a window-exact index is searched by the postings scan, which holds d <= 4096 (d=%d)", ix->d);
+  ASL_TRY(build_lists(ix));      // (after add or reset: the layout in id order, no key)
+  if (ix->n_store > 0 && !ix->has_inv && ix->d <= 65535 && ix->nnz_max == 0)
+    return fail(ASL_ERR_STATE, "a window-exact index of all-zero vectors has no postings to scan");
+  if (ix->n_store > 0 && !ix->has_inv)
+    return fail(ASL_ERR_STATE, "a window-exact index needs sparse vectors: its postings are built when the most "
+                               "non-zeros of a vector (%d), times 8, stay below d=%d", ix->nnz_max, ix->d);
+  if (rq.win && !ix->win_ready)
+    return fail(ASL_ERR_STATE, "window scan: no window key (asl_index_set_window_key), or vectors were added "
+                               "since it was set");
+  return ASL_OK;
+}
+
 // Every request-versus-index check, in the order callers met them (a stale layout is rebuilt where one asks what the lists hold).
 static int validate(asl_index *ix, const IndexSearch &rq, SearchPlan &pl) {
   const int k = rq.k;
   pl.unordered = rq.rows == ROWS_KEYS ? 2 : rq.rows == ROWS_SET_RAW ? 1 : ix->unordered;
+  if (ix->kind == ASL_INDEX_WINFLAT) return validate_winflat(ix, rq, pl);
   pl.refine = ix->kind == ASL_INDEX_IVFPQ && ix->refine_k > k && ix->refine_rows && pl.unordered == 0;
   // a window (rq.win): only the in-window run of every probed list is scanned, in the window-ordered
   // layout; whatever cannot do that is an error, never the whole lists
@@ -316,6 +349,34 @@ static int search_ivfflat(asl_index *ix, IndexSearch &rq, const SearchPlan &pl) 
   return rq.gate ? ASL_OK : count_scanned(ix, cI, nq, nprobe);
 }
 
+// The window-exact index: every query's run of positions in the one precursor-ordered list (no window: all of
+// it), then the ranged form of the postings scan over the blocks of the run. Set-mode rows of a windowed request
+// hold in-window hits only; their lengths go to rq.win->row_len.
+static int search_winflat(asl_index *ix, IndexSearch &rq, const SearchPlan &pl) {
+  const int nq = rq.nq;
+  const uint2 *q_ent;
+  const int32_t *q_cnt;
+  ASL_TRY(query_entries(ix, rq, false, &q_ent, &q_cnt));
+  const int mode_ = (pl.unordered || rq.rows != ROWS_ORDERED) ? 1 : 0;
+  ASL_TRY(ix->win_ranges.reserve((size_t)nq));
+  {
+    ProfScope ps("window_ranges");
+    const IndexWindow *w = rq.win;
+    ASL_TRY(winflat_runs(w ? w->q_pmz : nullptr, nq, ix->wf_key.p, ix->n_store, w ? w->charge : 0, w ? w->tol : 0.0,
+                         w ? w->mode : ASL_TOL_DA, ix->win_ranges.p,
+                         prof_counts() ? prof_scanned_dev() : nullptr));      // work: sum of hi - lo
+  }
+  ScanRanges rg;
+  rg.range = ix->win_ranges.p;
+  rg.row_len = (rq.win && mode_ == 1) ? rq.win->row_len : nullptr;
+  rq.rows_filtered = rg.row_len != nullptr;
+  ProfScope ps("scan");
+  const bool fx = ix->has_inv && ix->inv_layout == 2;      // (an empty index: every run is empty, no layout is read)
+  return flat_inv_scan(fx ? 2 : 1, rq.xq, nq, ix->d, nullptr, 0, nullptr, nullptr, ix->blk_base.p,
+                       fx ? (const void *)ix->inv_tab8.p : (const void *)ix->inv_tab.p, ix->tab_stride, ix->inv_data.p,
+                       ix->ids.p, rq.k, rq.D, rq.I64, rq.I32, mode_, q_ent, q_cnt, nullptr, nullptr, nullptr, &rg);
+}
+
 // [m][dsub][ksub] copy of the codebooks for the tiled scan's LUT build (rebuilt after train / set_trained)
 int index_codebooks_transposed(asl_index *ix) {
   if (ix->cbt_ready) return ASL_OK;
@@ -453,6 +514,7 @@ int index_search_device(asl_index *ix, IndexSearch &rq) {
   ASL_TRY(validate(ix, rq, pl));
   if (rq.nq <= 0) return ASL_OK;
   if (ix->kind == ASL_INDEX_FLAT) return search_gemm_topk(ix, rq, nullptr, 0);
+  if (ix->kind == ASL_INDEX_WINFLAT) return search_winflat(ix, rq, pl);
   if (ix->kind == ASL_INDEX_IVFFLAT) return search_ivfflat(ix, rq, pl);
   return pl.refine ? search_ivfpq_refined(ix, rq, pl) : search_ivfpq(ix, rq, pl);
 }
@@ -463,8 +525,9 @@ int index_search_device(asl_index *ix, IndexSearch &rq) {
 int index_window_prepare(asl_index *ix, uint64_t serial, uint64_t gen, const float *key, int64_t n, int nq,
                          int nprobe) {
   if (!ix->trained) return fail(ASL_ERR_STATE, "search: index is not trained");
-  ASL_TRY(build_lists(ix));
-  if (!ix->win_ready || ix->win_serial != serial || ix->win_gen != gen) {
+  // (the window-exact index: a stale layout is rebuilt in key order at once, not in id order first)
+  if (ix->kind != ASL_INDEX_WINFLAT) ASL_TRY(build_lists(ix));
+  if (ix->lists_dirty || !ix->win_ready || ix->win_serial != serial || ix->win_gen != gen) {
     ASL_TRY(pipeline_drain());     // batches in flight may still scan the layout about to be rewritten
     ASL_TRY(window_install(ix, n, key, serial, gen));
   }
@@ -474,11 +537,11 @@ int index_window_prepare(asl_index *ix, uint64_t serial, uint64_t gen, const flo
 // The two halves of an IVF search for the two-stream pipeline (search.hip): the coarse
 // quantiser into caller-owned buffers, then index_search_device with those as pre_D / pre_I.
 int index_nprobe(const asl_index *ix, int nprobe) {
-  return ix->kind == ASL_INDEX_FLAT ? 0 : std::max(1, std::min(nprobe, ix->nlist));
+  return !ivf_kind(ix->kind) ? 0 : std::max(1, std::min(nprobe, ix->nlist));
 }
 int index_prepare(asl_index *ix) {   // everything that may allocate or synchronise, up front
   if (!ix->trained) return fail(ASL_ERR_STATE, "search: index is not trained");
-  if (ix->kind == ASL_INDEX_FLAT) return ASL_OK;
+  if (!ivf_kind(ix->kind)) return ASL_OK;      // (the window-exact layout: index_window_prepare)
   if (coarse_sparse_supported(ix->d, ix->nlist)) ASL_TRY(coarse_transposed(ix));
   return build_lists(ix);
 }
@@ -528,7 +591,7 @@ int asl_index_supports_keys(asl_index_t *ix, int32_t k, int32_t nprobe) {
 int asl_index_coarse(asl_index_t *ix, int32_t nq, const float *xq, int32_t nprobe,
                      float *coarse_D, int32_t *coarse_I) {
   clear_error();
-  if (!ix || ix->kind == ASL_INDEX_FLAT || !ix->trained)
+  if (!ix || !ivf_kind(ix->kind) || !ix->trained)
     return fail(ASL_ERR_STATE, "coarse: trained IVF index required");
   if (nq <= 0) return ASL_OK;
   ASL_TRY(clamp_nprobe(ix, &nprobe, "coarse"));
@@ -611,10 +674,12 @@ int asl_index_search_window(asl_index_t *ix, int32_t nq, const float *xq, const 
   if (!xq || !q_pmz || !I) return fail(ASL_ERR_INVALID, "search_window: null xq / q_pmz / I");
   if (mode != ASL_TOL_DA && mode != ASL_TOL_PPM && mode != ASL_TOL_INTERVAL)
     return fail(ASL_ERR_INVALID, "search_window: mode must be Da, ppm or interval");
-  if (const char *why = window_unsupported(ix)) return fail(ASL_ERR_STATE, "%s", why);
+  if (ix->kind != ASL_INDEX_WINFLAT)
+    if (const char *why = window_unsupported(ix)) return fail(ASL_ERR_STATE, "%s", why);
   if (!ix->trained) return fail(ASL_ERR_STATE, "search: index is not trained");
-  ASL_TRY(build_lists(ix));
-  if (!ix->win_ready)
+  // (the window-exact index: add and reset dropped the key with the layout -- nothing is rebuilt to find that out)
+  if (ix->kind != ASL_INDEX_WINFLAT || !ix->lists_dirty) ASL_TRY(build_lists(ix));
+  if (!ix->win_ready || (ix->kind == ASL_INDEX_WINFLAT && ix->lists_dirty))
     return fail(ASL_ERR_STATE, "search_window: no window key (asl_index_set_window_key), or the lists changed since");
   In<float> dq;
   In<double> dp;
@@ -637,7 +702,7 @@ int asl_index_set_selector(asl_index_t *ix, int64_t n, const uint8_t *keep) {
   }
   if (n != ix->ntotal)
     return fail(ASL_ERR_INVALID, "set_selector: %lld flags for %lld vectors", (long long)n, (long long)ix->ntotal);
-  if (ix->kind != ASL_INDEX_FLAT && ix->trained) ASL_TRY(build_lists(ix));   // (a rebuild later drops the selector)
+  if (ivf_kind(ix->kind) && ix->trained) ASL_TRY(build_lists(ix));   // (a rebuild later drops the selector)
   ix->has_selector = false;
   ASL_TRY(ix->selector.reserve((size_t)n));
   HIP_TRY(hipMemcpyAsync(ix->selector.p, keep, (size_t)n, hipMemcpyDefault, stream()));
@@ -657,6 +722,9 @@ int asl_index_search_selected(asl_index_t *ix, int32_t nq, const float *xq, cons
   if (q_pmz && mode != ASL_TOL_DA && mode != ASL_TOL_PPM && mode != ASL_TOL_INTERVAL)
     return fail(ASL_ERR_INVALID, "search_selected: mode must be Da, ppm or interval");
   if (ix->kind == ASL_INDEX_FLAT) return fail(ASL_ERR_STATE, "a selector needs an IVF index (not a Flat index)");
+  if (ix->kind == ASL_INDEX_WINFLAT)
+    return fail(ASL_ERR_STATE, "search_selected: a window-exact index takes a selection through its key column "
+                               "(NaN: unselected), not a selector");
   if (!ix->trained) return fail(ASL_ERR_STATE, "search: index is not trained");
   ASL_TRY(build_lists(ix));
   if (!ix->has_selector)
@@ -683,6 +751,8 @@ int asl_index_search_preassigned(asl_index_t *ix, int32_t nq, const float *xq, i
                                  int32_t nprobe, const float *coarse_D,
                                  const int32_t *coarse_I, float *D, int64_t *I) {
   clear_error();
+  if (ix && ix->kind == ASL_INDEX_WINFLAT)
+    return fail(ASL_ERR_STATE, "search_preassigned: a window-exact index has no probe lists");
   if (!ix || ix->kind == ASL_INDEX_FLAT)
     return fail(ASL_ERR_INVALID, "search_preassigned: IVF index required");
   if (nq <= 0) return ASL_OK;
@@ -707,6 +777,8 @@ int asl_index_search_gated(asl_index_t *ix, int32_t cap, const float *xq, int32_
                            const float *coarse_D, const int32_t *coarse_I, float *D, int64_t *I,
                            const int32_t *count) {
   clear_error();
+  if (ix && ix->kind == ASL_INDEX_WINFLAT)
+    return fail(ASL_ERR_STATE, "search_gated: a window-exact index has no probe lists");
   if (!ix || ix->kind == ASL_INDEX_FLAT) return fail(ASL_ERR_INVALID, "search_gated: IVF index required");
   if (cap <= 0) return ASL_OK;
   if (!xq || !I || !coarse_D || !coarse_I || !count) return fail(ASL_ERR_INVALID, "search_gated: null argument");
@@ -731,6 +803,8 @@ int asl_index_search_entries(asl_index_t *ix, int32_t nq, const uint32_t *entrie
                              int32_t k, int32_t nprobe, const float *coarse_D, const int32_t *coarse_I,
                              float *D, int64_t *I, const int32_t *count) {
   clear_error();
+  if (ix && ix->kind == ASL_INDEX_WINFLAT)
+    return fail(ASL_ERR_STATE, "search_entries: a window-exact index has no probe lists");
   if (!ix || ix->kind == ASL_INDEX_FLAT) return fail(ASL_ERR_INVALID, "search_entries: IVF index required");
   if (nq <= 0) return ASL_OK;
   if (!entries || !counts || !I || !coarse_D || !coarse_I) return fail(ASL_ERR_INVALID, "search_entries: null argument");

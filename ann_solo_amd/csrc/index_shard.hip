@@ -71,6 +71,8 @@ static void shard_owner(const std::vector<int64_t> &sizes, int world, std::vecto
 int asl_index_shard_map(const asl_index_t *cix, int32_t world, int32_t *owner_out) {
   clear_error();
   asl_index *ix = const_cast<asl_index *>(cix);
+  if (ix && ix->kind == ASL_INDEX_WINFLAT)
+    return fail(ASL_ERR_STATE, "shard_map: a window-exact index has one list and is not sharded");
   if (!ix || ix->kind == ASL_INDEX_FLAT || world <= 0 || !owner_out)
     return fail(ASL_ERR_INVALID, "shard_map: IVF index and world > 0 required");
   if (ix->shard_world > 1) return fail(ASL_ERR_STATE, "shard_map: call before sharding");
@@ -84,6 +86,8 @@ int asl_index_shard_map(const asl_index_t *cix, int32_t world, int32_t *owner_ou
 
 int asl_index_shard(asl_index_t *ix, int32_t rank, int32_t world) {
   clear_error();
+  if (ix && ix->kind == ASL_INDEX_WINFLAT)
+    return fail(ASL_ERR_STATE, "shard: a window-exact index has one list and is not sharded");
   if (!ix || ix->kind == ASL_INDEX_FLAT) return fail(ASL_ERR_INVALID, "shard: IVF index required");
   if (world <= 0 || rank < 0 || rank >= world) return fail(ASL_ERR_INVALID, "shard: bad rank/world");
   if (ix->shard_world > 1) return fail(ASL_ERR_STATE, "shard: already sharded");

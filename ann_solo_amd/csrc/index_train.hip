@@ -196,7 +196,7 @@ int asl_index_train(asl_index_t *ix, int64_t n, const float *x, uint64_t seed) {
   clear_error();
   if (!ix) return fail(ASL_ERR_INVALID, "train: null index");
   ASL_TRY(ensure_device());
-  if (ix->kind == ASL_INDEX_FLAT) return ASL_OK;
+  if (!ivf_kind(ix->kind)) return ASL_OK;      // Flat, window-exact: nothing to train
   if (n <= 0 || !x) return fail(ASL_ERR_INVALID, "train: no data");
   if (n < ix->nlist) return fail(ASL_ERR_INVALID, "train: %lld vectors < nlist %d", (long long)n, ix->nlist);
   In<float> dx;

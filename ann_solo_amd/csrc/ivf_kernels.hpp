@@ -8,6 +8,7 @@
 namespace asl {
 
 struct ScanPostFilter;            // common.hpp
+struct ScanRanges;
 
 constexpr int TK_NT = 256;        // threads per top-k workgroup
 constexpr int TK_MAX_K = 2048;    // largest k / nprobe the LDS top-k supports
@@ -98,7 +99,13 @@ int flat_inv_scan(int layout, const float *xq, int nq, int d, const int32_t *coa
                   const int32_t *ids, int k, float *D, int64_t *I64, int32_t *I32, int set_mode,
                   const uint2 *ent, const int32_t *ent_cnt, const int *gate = nullptr,
                   const ScanPostFilter *post = nullptr,   // set-mode int32 rows, k <= 1280 only
-                  const unsigned long long *sel = nullptr);   // selector: flat_selector's words, k <= 1280
+                  const unsigned long long *sel = nullptr,    // selector: flat_selector's words, k <= 1280
+                  const ScanRanges *ranges = nullptr);        // (common.hpp) the window-exact index: range [nq], one run of
+                                                              // positions per query in ONE list; probes and offsets unread
+// the runs of the window-exact index (flat_scan.hip): [lo, hi) per query over the key column by position
+// (ascending, NaN last); q_pmz == nullptr: [0, n) for every query
+int winflat_runs(const double *q_pmz, int nq, const float *key, int64_t n, int charge, double tol, int mode,
+                 int2 *runs, unsigned long long *acc);
 // selector words of the postings layout: flat_selector_words_per_block() per block, bit v of word r of a
 // block = keep[id of the block's position r * 64 + v] (behind the list's end: unselected)
 int flat_selector(const int32_t *list_offsets, const int32_t *blk_offsets, int nlist, int64_t nblocks,

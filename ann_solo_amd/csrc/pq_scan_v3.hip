@@ -651,28 +651,8 @@ __global__ void window_ranges_kernel(const double *__restrict__ q_pmz, int nq,
     if (l >= 0) {
       const float *key = wkey + (size_t)tile_offsets[l] * 64;
       const int n = list_offsets[l + 1] - list_offsets[l];
-      const QueryWindow w = query_window(q_pmz, i / nprobe, mode);
-      const double qm = w.q;
-      int a = 0, b = n;   // p0 = first key with (double)key >= qm (NaN: not below)
-      while (a < b) {
-        const int mid = (a + b) >> 1;
-        if ((double)key[mid] < qm) a = mid + 1; else b = mid;
-      }
-      const int p0 = a;
-      // (interval: p0 is lower_bound(lo) and nothing left of it passes; a NaN bound or lo > hi: no run)
-      a = mode == ASL_TOL_INTERVAL ? p0 : 0, b = p0;      // left side: first key that passes
-      while (a < b) {
-        const int mid = (a + b) >> 1;
-        if (precursor_ok(qm, key[mid], charge, tol, mode)) b = mid; else a = mid + 1;
-      }
-      const int lo = a;
-      a = p0, b = (mode == ASL_TOL_INTERVAL && !(w.q <= w.hi)) ? p0 : n;      // right side: first key that fails
-      while (a < b) {
-        const int mid = (a + b) >> 1;
-        if (precursor_ok(w, key[mid], charge, tol, mode)) a = mid + 1; else b = mid;
-      }
-      r = make_int2(lo, a);
-      cnt = (unsigned long long)(a - lo);
+      r = window_run(key, n, query_window(q_pmz, i / nprobe, mode), charge, tol, mode);
+      cnt = (unsigned long long)(r.y - r.x);
     }
     ranges[i] = r;
   }

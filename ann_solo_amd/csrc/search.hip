@@ -90,7 +90,7 @@ static void batch_scan(BatchScan &s, const SearchBatch &b, const asl_index *idx,
   }
   // The precursor window of the scan: the window scan (asl_index_set_window_scan) when the index is in that
   // mode, else -- no ordered neighbour list asked for -- the scan-side post-filter of THIS library's window column
-  if (idx->window_scan) {
+  if (window_mode(idx)) {
     s.w = {.q_pmz = b.window_operand(), .row_len = as_set ? row_len : nullptr, .tol = P->precursor_tol,
            .mode = P->precursor_mode, .charge = P->charge};
     s.rq.win = &s.w;
@@ -150,7 +150,7 @@ static int search_batch_sync(asl_library *L, asl_index *idx, const asl_peaks_t *
     ASL_TRY(L->knn.reserve((size_t)nq * k));
     ASL_TRY(L->pair_score.reserve((size_t)nq * k));
     ASL_TRY(L->rows_len.reserve((size_t)nq));
-    if (idx->window_scan)
+    if (window_mode(idx))
       ASL_TRY(index_window_prepare(idx, L->serial, L->sel_gen, L->window_col(), L->n, nq, P->nprobe));
     ASL_TRY(encode_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
                           d, P->hash_seed, 1, L->qvec.p));
@@ -187,13 +187,14 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
     ~InCall() { p.in_call = false; }
   } guard(pp);
   const int nq = queries->n, k = P->k, d = idx->d;
-  const int nprobe = index_nprobe(idx, P->nprobe);
+  const bool winflat = idx->kind == ASL_INDEX_WINFLAT;      // no coarse stage: stream A encodes, stream B scans
+  const int nprobe = winflat ? 1 : index_nprobe(idx, P->nprobe);
   PeaksStage Q;
   ASL_TRY(Q.init(queries));   // device pointers + known peak count: no copy, no wait
   const int par = pp.parity;
   // allocations first (growing a buffer synchronises the device: only ever on the first batches)
   ASL_TRY(index_prepare(idx));
-  if (idx->window_scan)      // (the window-ordered layout of THIS library, up front)
+  if (window_mode(idx))      // (the window-ordered layout of THIS library, up front)
     ASL_TRY(index_window_prepare(idx, L->serial, L->sel_gen, L->window_col(), L->n, nq, nprobe));
   ASL_TRY(L->p_qvec[par].reserve((size_t)nq * d));
   ASL_TRY(L->p_cD[par].reserve((size_t)nq * nprobe));
@@ -236,8 +237,11 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
     if (pp.scan_recorded[par]) HIP_TRY(hipStreamWaitEvent(pp.A, pp.ev_scan[par], 0));
     ASL_TRY(encode_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
                           d, P->hash_seed, 1, L->p_qvec[par].p));
-    ASL_TRY(coarse_search(idx, L->p_qvec[par].p, nq, nprobe, L->p_cD[par].p, L->p_cI[par].p,
-                                L->p_ent[par].p, L->p_cnt[par].p, &L->p_have_ent[par]));
+    if (winflat)
+      L->p_have_ent[par] = false;
+    else
+      ASL_TRY(coarse_search(idx, L->p_qvec[par].p, nq, nprobe, L->p_cD[par].p, L->p_cI[par].p,
+                                  L->p_ent[par].p, L->p_cnt[par].p, &L->p_have_ent[par]));
     HIP_TRY(hipEventRecord(pp.ev_front[par], pp.A));
   }
   {
@@ -245,8 +249,9 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
     HIP_TRY(hipStreamWaitEvent(pp.B, pp.ev_front[par], 0));
     if (pp.resc_recorded[par]) HIP_TRY(hipStreamWaitEvent(pp.B, pp.ev_resc[par], 0));
     const bool ent = L->p_have_ent[par];
-    batch_scan(s, b, idx, nprobe, L->p_qvec[par].p, knn_I, L->p_knn[par].p, L->p_rows[par].p, L->p_cD[par].p,
-               L->p_cI[par].p, ent ? L->p_ent[par].p : nullptr, ent ? L->p_cnt[par].p : nullptr);
+    batch_scan(s, b, idx, nprobe, L->p_qvec[par].p, knn_I, L->p_knn[par].p, L->p_rows[par].p,
+               winflat ? nullptr : L->p_cD[par].p, winflat ? nullptr : L->p_cI[par].p,
+               ent ? L->p_ent[par].p : nullptr, ent ? L->p_cnt[par].p : nullptr);
     ASL_TRY(index_search_device(idx, s.rq));
     HIP_TRY(hipEventRecord(pp.ev_scan[par], pp.B));
     pp.scan_recorded[par] = true;
@@ -295,7 +300,8 @@ int asl_search_batch(asl_library_t *L, asl_index_t *idx, const asl_peaks_t *quer
     Pipeline &pp = pipeline();
     auto dev_or_null = [](const void *p) { return !p || is_device_ptr(p); };
     // (an exhaustive ASL_INDEX_FLAT index has no coarse stage to overlap: synchronous path)
-    if (pp.on && P->use_ann && index_nprobe(idx, P->nprobe) > 0 && queries->n_peaks > 0 &&
+    if (pp.on && P->use_ann && (index_nprobe(idx, P->nprobe) > 0 || idx->kind == ASL_INDEX_WINFLAT) &&
+        queries->n_peaks > 0 &&
         peaks_on_device(queries) &&
         is_device_ptr(best_row) && is_device_ptr(best_score) && dev_or_null(n_cand) &&
         dev_or_null(pm_count) && dev_or_null(pm_pairs) && dev_or_null(knn_I)) {

@@ -92,6 +92,8 @@ extern "C" int asl_index_search_sharded_ex(asl_index_t *ix, void *rccl_comm, int
   if (!ix || !rccl_comm || !xq || !I) return fail(ASL_ERR_INVALID, "search_sharded: null argument");
   if (nq <= 0) return fail(ASL_ERR_INVALID, "search_sharded: every rank must bring nq > 0 queries");
   if (k <= 0 || k > TK_MAX_K) return fail(ASL_ERR_CAPACITY, "search_sharded: k=%d outside 1..%d", k, TK_MAX_K);
+  if (ix->kind == ASL_INDEX_WINFLAT)
+    return fail(ASL_ERR_STATE, "search_sharded: a window-exact index has one list and is not sharded");
   ASL_TRY(ensure_device());
   const int world = ix->kind == ASL_INDEX_FLAT ? 0 : ix->shard_world;
   if (world < 1) return fail(ASL_ERR_STATE, "search_sharded: call asl_index_shard first");

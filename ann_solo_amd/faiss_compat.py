@@ -5,7 +5,8 @@ Covers exactly the FAISS surface the reference touches
 ``IndexFlatIP``, ``IndexIVFFlat``, ``METRIC_INNER_PRODUCT``, ``train``, ``add``,
 ``search``, ``nprobe``, ``reset``, ``write_index``/``read_index``, ``get_num_gpus``,
 ``StandardGpuResources``, ``GpuClonerOptions``, ``index_cpu_to_gpu``/``setNumProbes`` --
-plus ``IndexIVFPQ`` (the north star's addition). ``import ann_solo_amd.faiss_compat as
+plus ``IndexIVFPQ`` (the north star's addition) and ``IndexWindowFlat`` (exact search inside a
+query's precursor window; no FAISS counterpart). ``import ann_solo_amd.faiss_compat as
 faiss`` is the whole change at those call sites. Indexes always live on the GPU.
 """
 import ctypes as C
@@ -18,7 +19,7 @@ from . import _lib
 
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
-_KIND_FLAT, _KIND_IVFFLAT, _KIND_IVFPQ = 0, 1, 2
+_KIND_FLAT, _KIND_IVFFLAT, _KIND_IVFPQ, _KIND_WINFLAT = 0, 1, 2, 3
 DEFAULT_SEED = 1234          # FAISS ClusteringParameters.seed
 
 
@@ -135,7 +136,7 @@ class Index:
     def set_window_key(self, key):
         """Window-ordered copy of the IVF-PQ layout: every list sorted by ``key`` (float32 per vector
         id, NaN = never a candidate; len(key) == ntotal). Derived, never saved; add / reset / shard
-        drop it."""
+        drop it. ``IndexWindowFlat``: the order of its one list."""
         key = key.float().contiguous() if hasattr(key, 'data_ptr') else np.ascontiguousarray(key, np.float32)
         _lib.check(_lib.lib().asl_index_set_window_key(self._h, int(key.shape[0]), _lib.ptr(key)))
 
@@ -471,6 +472,20 @@ class IndexIVFFlat(Index):
         self.quantizer = quantizer
         self.nlist = nlist
         super().__init__(_lib.lib().asl_index_create(d, nlist, _KIND_IVFFLAT, 0, 0), d)
+        self.set_storage(storage)
+
+
+class IndexWindowFlat(Index):
+    """Exact search inside a precursor window (``ASL_INDEX_WINFLAT``): float32 vectors as given, no training,
+    one list ordered by ``set_window_key``'s key. ``search_window`` returns the k best (score desc, id asc) of
+    ALL stored vectors whose key passes the query's window -- no coarse quantiser, ``nprobe`` is unread --
+    and ``search`` the k best of all vectors (it needs no key). k <= 1280, sparse vectors (the most non-zeros
+    of a vector, times 8, below d). ``storage``: 'fp32' | 'fx22' as for ``IndexIVFFlat``; identical ids and
+    score bits for the same stored vectors. ``search_selected``, ``rank_of``, ``set_refine``, ``shard`` and
+    the preassigned searches raise."""
+
+    def __init__(self, d, storage='fp32'):
+        super().__init__(_lib.lib().asl_index_create(d, 0, _KIND_WINFLAT, 0, 0), d)
         self.set_storage(storage)
 
 

@@ -219,7 +219,7 @@ class SpectralLibrary:
         if cfg.mode == 'ann':
             create = []
             for z in sorted(self.partitions):
-                if len(self.partitions[z].ids) < cfg.num_list:
+                if len(self.partitions[z].ids) < (1 if cfg.index == 'winflat' else cfg.num_list):
                     continue          # infrequent charge: brute force (spectral_library.py:102-104)
                 base = f'{self._basename}_{self._get_index_hash()[:7]}'
                 self._ann_filenames[z] = os.path.join(self._index_dir or '', f'{base}_{z}{INDEX_EXT}')
@@ -284,7 +284,7 @@ class SpectralLibrary:
             return self._get_hyperparameter_hash()
         d = {hp: cfg[hp] for hp in self._hyperparameters}
         d.update(index=cfg.index, kmeans_niter=cfg.kmeans_niter, seed=cfg.seed)
-        if cfg.index == 'ivfflat' and cfg.flat_storage != 'fp32':
+        if cfg.index in ('ivfflat', 'winflat') and cfg.flat_storage != 'fp32':
             d.update(flat_storage=cfg.flat_storage)
         if cfg.index == 'ivfpq':
             d.update(pq_m=cfg.pq_m, pq_bits=cfg.pq_bits)
@@ -306,6 +306,14 @@ class SpectralLibrary:
         for z in charges:
             part = self.partitions[z]
             vectors = self._encode(part.spectra)
+            if cfg.index == 'winflat':      # the vectors as given: nothing to train
+                ann_index = faiss.IndexWindowFlat(cfg.hash_len, storage=cfg.flat_storage)
+                ann_index.add(vectors)
+                if self._index_dir is not None:
+                    faiss.write_index(ann_index, self._ann_filenames[z])
+                part.index = ann_index
+                del vectors
+                continue
             quantizer = faiss.IndexFlatIP(cfg.hash_len)
             if cfg.index == 'ivfpq':
                 ann_index = faiss.IndexIVFPQ(quantizer, cfg.hash_len, cfg.num_list, cfg.pq_m,
@@ -328,7 +336,10 @@ class SpectralLibrary:
 
     def _index_matches(self, idx: faiss.Index, part: ChargePartition) -> bool:
         cfg, i = self.config, idx.info()
-        kind = 2 if cfg.index == 'ivfpq' else 1
+        kind = {'ivfpq': 2, 'winflat': 3}.get(cfg.index, 1)
+        if kind == 3:       # one list: num_list plays no part
+            return (i.kind == 3 and i.d == cfg.hash_len and i.ntotal == len(part.ids) and i.shard_world == 1 and
+                    idx.storage == cfg.flat_storage)
         return (i.kind == kind and i.d == cfg.hash_len and i.nlist == cfg.num_list and
                 i.ntotal == len(part.ids) and bool(i.trained) and i.shard_world == 1 and
                 (kind != 2 or (i.pq_m == cfg.pq_m and i.pq_ksub == (1 << cfg.pq_bits) and
@@ -385,6 +396,8 @@ class SpectralLibrary:
         the results of the whole batch. Every rank must call ``search`` with the same queries."""
         if self.config.ann_window == 'pre':
             raise ValueError("enable_sharding: ann_window = 'pre' does not run on a sharded index")
+        if self.config.index == 'winflat':
+            raise ValueError("enable_sharding: index = 'winflat' has one list and is not sharded")
         if getattr(self, '_search_subset', False):
             raise ValueError('enable_sharding: a search subset (set_search_subset) does not run on a sharded library')
         import torch.distributed as dist
@@ -701,6 +714,9 @@ class SpectralLibrary:
                                                     _lib.ptr(off), _lib.ptr(rows)))
         lists = [rows[off[i]:off[i + 1]] for i in range(nq)]
         if self.config.mode == 'ann' and mode == 'open' and charge in self._ann_filenames:
+            if self.config.index == 'winflat':      # the k best vectors OF the window: the fused call's neighbour rows
+                I = _to_np(self._search_batch(queries, charge, mode, want_knn=True, windows=windows).knn)
+                return [np.sort(I[i][I[i] >= 0]) for i in range(nq)]
             idx = self._get_ann_index(charge)
             _, I = idx.search(self._encode(queries.to(self.device)), self._num_candidates)
             I = I.cpu().numpy()
@@ -722,6 +738,8 @@ class SpectralLibrary:
             return None
         if getattr(self, '_dist', None) is not None and self._dist.world > 1:
             raise ValueError('candidate_rank: does not run on a sharded index')
+        if self.config.index == 'winflat':
+            raise ValueError("candidate_rank: index = 'winflat' has no neighbour order over probed lists to rank in")
         part = self.partitions[charge]
         idx = self._get_ann_index(charge)
         q = queries.to(self.device).contiguous()

@@ -41,6 +41,8 @@ extern "C" {
 #define ASL_INDEX_FLAT 0      /* IndexFlatIP: exact inner product            */
 #define ASL_INDEX_IVFFLAT 1   /* IndexIVFFlat(IndexFlatIP, d, nlist, IP)     */
 #define ASL_INDEX_IVFPQ 2     /* IVF + product quantiser, by-residual IP ADC */
+#define ASL_INDEX_WINFLAT 3   /* window-exact: every vector in the query's precursor window, exact IP (see
+                               * "Window scan" below); float32 vectors as given, no training, nlist / pq_* unread */
 
 /* The precursor window of a query: which library rows are its candidates, by the float32 window column
  * `key` (lib_pmz_f32; NaN, or unselected under a selection: never a candidate).
@@ -195,8 +197,25 @@ int asl_index_refine(asl_index_t *idx, int32_t nq, const float *xq, int32_t kpri
  * saved; add, add_preassigned, reset and shard drop it. Unsupported (ASL_ERR_STATE, never a silent
  * post-filter): IVF-Flat and Flat, the generic PQ kernel (scan_variant 1, m != 32, bits != 8),
  * k > 1280, a sharded index.
+ * ASL_INDEX_WINFLAT (the window-exact index) is the same idea without a coarse quantiser: ALL stored vectors form
+ * one list ordered by the key (ascending, NaN last, id ascending), cut into blocks of 832 positions that hold the
+ * per-dimension postings of the IVF-Flat scan (asl_index_set_flat_storage: float postings, or fixed-point words
+ * in ASL_FLAT_FX22 when every non-zero is on the grid). asl_index_search_window then returns the top-k among
+ * all stored vectors whose key passes -- a query's window is one contiguous run of blocks, nprobe is unread --
+ * and asl_index_search the top-k of all vectors, NaN keys included (no key needed: before one is set the order
+ * is by id). A score is the ascending-dimension fp32 fmaf chain over the stored non-zeros: the bits of the
+ * IVF-Flat scan and the Flat index. The layout is derived and never saved (a file holds the kind and the
+ * vectors); add, reset and a new key drop it. asl_search_batch and its _topn / _topn_distinct / _topn_hist
+ * siblings always scan the window on this kind, with the library handle's window column as the key (a selection
+ * arrives as NaN keys); asl_index_set_window_scan is a no-op returning 0. ASL_ERR_STATE, with the reason:
+ * asl_index_search_window before a key is set (or after add), k > 1280, vectors too dense for postings (the
+ * most non-zeros of a vector, times 8, reach d), asl_index_search_selected, asl_index_rank,
+ * asl_index_set_refine, asl_index_set_trained, asl_index_add_preassigned, asl_index_shard and the sharded
+ * searches, asl_index_search_preassigned / _gated / _entries, packed-key rows. asl_profile_scanned_vectors
+ * counts the runs' lengths.
  * asl_index_set_window_key: sort key per vector id (float32 precursor m/z, NaN = never a candidate),
- * n == ntotal: copied, and the window-ordered layout built (IVF-PQ, trained, unsharded, no caller ids). */
+ * n == ntotal (else ASL_ERR_INVALID): copied, and the window-ordered layout built (IVF-PQ, trained, unsharded, no
+ * caller ids; or ASL_INDEX_WINFLAT). */
 int asl_index_set_window_key(asl_index_t *idx, int64_t n, const float *key);
 /* top-k (score desc, id asc) among the probed lists' vectors whose key passes
  * precursor_ok(q_pmz[i], key, charge, tol, mode) -- the window test of asl_search_batch, same double

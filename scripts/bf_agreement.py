@@ -34,6 +34,20 @@ def timed_search(sl, q, mode, want_knn=False):
     return res, time.perf_counter() - t
 
 
+def agreement(res, b):
+    """An engine's batch `res` (with its neighbour rows, if it has any) against the brute-force batch `b`."""
+    has = b.best_row >= 0
+    gap = np.where(has, b.best_score - np.where(res.best_row >= 0, res.best_score, 0.0), 0.0)
+    out = {'best_row_agreement': float((res.best_row == b.best_row)[has].mean())}
+    if res.knn is not None:
+        in_topk = (res.knn == b.best_row[:, None].astype(np.int64)).any(1)
+        out['bf_winner_in_topk'] = float(in_topk[has].mean())
+    out.update(score_gap_mean=float(gap[has].mean()), score_gap_p99=float(np.percentile(gap[has], 99)),
+               fraction_with_score_gap=float((gap[has] > 0).mean()),
+               ann_score_above_bf=int((gap < 0).sum()))     # must be 0: the ANN lists are inside the window
+    return out
+
+
 def main():
     from ann_solo_amd import synthetic
     from ann_solo_amd.spectral_library import Config, SpectralLibrary
@@ -82,16 +96,7 @@ def main():
             res, dt = timed_search(sl, q, 'open', want_knn=True)
             b = truth[name]
             has = b.best_row >= 0
-            gap = np.where(has, b.best_score - np.where(res.best_row >= 0, res.best_score, 0.0), 0.0)
-            in_topk = (res.knn == b.best_row[:, None].astype(np.int64)).any(1)
-            out['engines'][ename][name] = {
-                'best_row_agreement': float((res.best_row == b.best_row)[has].mean()),
-                'bf_winner_in_topk': float(in_topk[has].mean()),
-                'score_gap_mean': float(gap[has].mean()),
-                'score_gap_p99': float(np.percentile(gap[has], 99)),
-                'fraction_with_score_gap': float((gap[has] > 0).mean()),
-                'ann_score_above_bf': int((gap < 0).sum()),     # must be 0: the ANN lists are inside the window
-                'ann_seconds_per_batch_unpipelined': dt}
+            out['engines'][ename][name] = dict(agreement(res, b), ann_seconds_per_batch_unpipelined=dt)
             if args.ranks > 1:
                 top = sl.search_batch_topn(q, 2, 'open', args.ranks)
                 among = (top.best_row == b.best_row[:, None]).any(1)
