@@ -4,7 +4,8 @@
 (/root/reference/src/ann_solo/config.py:62-216) plus the ADDITIVE flags of this implementation
 (``index``, ``pq_m``, ``pq_bits``, ``refine_k``, ``kmeans_niter``, ``ann_seed``, ``num_gpus``,
 ``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``, ``pq_by_residual``,
-``precursor_window_open``, ``fragment_tolerance_unit``, ``score_stats``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``precursor_window_open``, ``fragment_tolerance_unit``, ``score_stats``, ``device_decoys``,
+``decoy_tolerance_unit``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -106,8 +107,17 @@ class Config:
     # to score as high as the winner by chance (expect: a log-linear fit to the tail of the losers' score
     # histogram, which the device counts; score_stats.py). Identifications, scores and files do not change
     score_stats: bool = False
+    # make a shuffle-and-reposition decoy of every library spectrum on the device while the library is read
+    # (decoy_generator.py; DESIGN.md 3 "Decoys"): the library then holds decoy and target rows in pairs. The
+    # annotation tolerance is fragment_mz_tolerance in decoy_tolerance_unit, the shuffle's key is ``seed``.
+    # Deliberately NOT the reference's ``add_decoys``: its own reader honours that flag from its global
+    # configuration, and picking it up through ``from_reference`` would add decoys twice.
+    device_decoys: bool = False
+    # 'ppm' (of the theoretical fragment m/z) | 'Da'. The default is the default of the reference's
+    # ``fragment_tol_mode``, which reaches its decoy annotation only; this is the one place it is read
+    decoy_tolerance_unit: str = 'ppm'
 
-    MAX_PEAKS = 256      # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
+    MAX_PEAKS = 256     # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
     MAX_CANDIDATES = 16384   # largest num_candidates: beyond MAX_TOPK in bounded passes (TK_MAX_K_PASSES)
     MAX_MATCHES = 16     # largest num_matches (include/annsolo_mi.h: ASL_MAX_BEST)
@@ -158,6 +168,9 @@ class Config:
         self.score_stats = bool(self.score_stats)
         if self.score_stats and self.num_gpus and int(self.num_gpus) > 1:
             raise ValueError('score_stats does not run on a sharded index (num_gpus > 1)')
+        self.device_decoys = bool(self.device_decoys)
+        if self.decoy_tolerance_unit not in ('Da', 'ppm'):
+            raise ValueError(f"decoy_tolerance_unit = {self.decoy_tolerance_unit!r}: 'Da' or 'ppm'")
         if self.precursor_window_open is not None:
             try:
                 lo, hi = (float(v) for v in self.precursor_window_open)
@@ -302,3 +315,12 @@ def add_arguments(parser) -> None:
                              "log-linear fit to the tail of the query's score histogram; a descriptive "
                              'statistic, not a calibrated p-value); identifications and scores do not change; '
                              'the batches run synchronously; one GPU (default: off)')
+    parser.add_argument('--device_decoys', action='store_true', default=d.device_decoys,
+                        help='add a shuffle-and-reposition decoy of every library spectrum, made on the GPU '
+                             "while the library is read (not the reference's --add_decoys: leave that off); "
+                             'the annotation tolerance is --fragment_mz_tolerance in --decoy_tolerance_unit, '
+                             'the shuffle is keyed by --ann_seed (default: off)')
+    parser.add_argument('--decoy_tolerance_unit', default=d.decoy_tolerance_unit, type=str,
+                        choices=['ppm', 'Da'],
+                        help="with --device_decoys: unit of --fragment_mz_tolerance in the fragment annotation "
+                             "(the reference's --fragment_tol_mode) (default: %(default)s)")

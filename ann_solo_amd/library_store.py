@@ -51,9 +51,88 @@ def store_hash(config, hyperparameter_hash: str, annotation_alignment: str) -> s
     from .config import Config
     config = Config.from_reference(config)
     opts = {k: getattr(config, k, None) for k in _PROCESS_KEYS}
-    b = json.dumps({'hyper': hyperparameter_hash, 'process': opts,
-                    'annotation': annotation_alignment, 'layout': 2}, sort_keys=True)
-    return hashlib.sha1(b.encode('utf-8')).hexdigest()
+    d = {'hyper': hyperparameter_hash, 'process': opts, 'annotation': annotation_alignment, 'layout': 2}
+    if config.device_decoys:        # (off: the key, and so every cached file name, as before the option)
+        d['decoys'] = decoy_options(config)
+    return hashlib.sha1(json.dumps(d, sort_keys=True).encode('utf-8')).hexdigest()
+
+
+def decoy_options(config) -> dict:
+    """What decides the decoy rows of a library read with ``device_decoys``."""
+    return {'tolerance': float(config.fragment_mz_tolerance), 'unit': config.decoy_tolerance_unit,
+            'seed': int(config.seed), 'version': 1}
+
+
+class DecoyReader:
+    """A library reader with the reference reader's surface whose library holds, for every spectrum of
+    ``reader``, its shuffle-and-reposition decoy and then the spectrum itself -- the order in which the
+    reference's reader lists them with ``--add_decoys`` (reader.py:171-183); both rows have the same
+    float32 precursor m/z. ``read_all_spectra()`` buffers ``batch`` targets, makes their decoys in one
+    device call (``decoy_generator.shuffle_and_reposition_batch``; ``batch_fn`` stands in for it in
+    tests) and yields decoy and target objects; as in the reference, the target's per-peak fragment
+    charges are then those of the decoy generator's annotation."""
+
+    def __init__(self, reader, config, device='cuda', batch_fn=None, batch: int = 32768):
+        from .config import Config
+        self._reader = reader
+        self._config = Config.from_reference(config)
+        self._device = device
+        self._batch_fn = batch_fn
+        self._batch = int(batch)
+        self._filename = getattr(reader, '_filename', None)
+        charge = {}
+        for z, info in reader.spec_info['charge'].items():
+            ids = list(np.asarray(info['id']).tolist())
+            for i in ids:
+                if str(i).startswith('DECOY_'):
+                    raise ValueError(f'library spectrum {i!r} is a decoy already: device_decoys needs a '
+                                     "target-only library (was it read with the reference's --add_decoys?)")
+            both = np.empty(2 * len(ids), object)
+            both[0::2] = ['DECOY_' + str(i) for i in ids]
+            both[1::2] = ids
+            charge[z] = {'id': both,
+                         'precursor_mz': np.repeat(np.asarray(info['precursor_mz'], np.float32), 2)}
+        self.spec_info = {'charge': charge}
+
+    @property
+    def is_recreated(self):
+        return getattr(self._reader, 'is_recreated', False)
+
+    def get_version(self):
+        return self._reader.get_version()
+
+    def close(self):
+        if hasattr(self._reader, 'close'):
+            self._reader.close()
+
+    def _flush(self, buf):
+        from . import decoy_generator as dg
+        cfg = self._config
+        raw = pack_raw(buf)
+        fn = self._batch_fn or dg.shuffle_and_reposition_batch
+        decoy, names, ann = fn(raw, [getattr(s, 'peptide', None) for s in buf], cfg.fragment_mz_tolerance,
+                               cfg.decoy_tolerance_unit, cfg.seed, self._device)
+        o, mz, it, _, _, _ = raw.numpy()
+        _, dmz, dit, dchg, _, _ = decoy.numpy()
+        z = ann['z'].cpu().numpy() if hasattr(ann['z'], 'cpu') else np.asarray(ann['z'], np.uint8)
+        for j, s in enumerate(buf):
+            a, b = int(o[j]), int(o[j + 1])
+            rt = getattr(s, 'retention_time', None)
+            yield dg.LibrarySpectrum('DECOY_' + str(s.identifier), s.precursor_mz, s.precursor_charge,
+                                     dmz[a:b], dit[a:b], dchg[a:b], names[j], True, rt)
+            yield dg.LibrarySpectrum(s.identifier, s.precursor_mz, s.precursor_charge, mz[a:b], it[a:b],
+                                     z[a:b], getattr(s, 'peptide', None),
+                                     bool(getattr(s, 'is_decoy', False)), rt)
+
+    def read_all_spectra(self):
+        buf = []
+        for s in self._reader.read_all_spectra():
+            buf.append(s)
+            if len(buf) >= self._batch:
+                yield from self._flush(buf)
+                buf = []
+        if buf:
+            yield from self._flush(buf)
 
 
 def _sorted_peaks(s):

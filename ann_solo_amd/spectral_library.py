@@ -183,6 +183,9 @@ class SpectralLibrary:
         self.partitions: Dict[int, ChargePartition] = {}
         verify_file_existence = True
         if isinstance(library, PackedSpectra):
+            if cfg.device_decoys:
+                raise ValueError('device_decoys needs a library reader or file name: a PackedSpectra holds '
+                                 'processed peaks and no peptides')
             self._index_dir = index_dir
             self._basename = basename or 'library'
             self._init_from_packed(library, identifiers, valid)
@@ -195,6 +198,8 @@ class SpectralLibrary:
             else:
                 self._library_reader = library
                 filename = getattr(library, '_filename', None) or cfg.spectral_library_filename
+            if cfg.device_decoys:       # decoy row, target row for every spectrum the reader lists
+                self._library_reader = ls.DecoyReader(self._library_reader, cfg, self.device)
             if filename:
                 stem = os.path.splitext(filename)[0]
                 self._index_dir = index_dir if index_dir is not None else (os.path.dirname(stem) or '.')
@@ -226,7 +231,7 @@ class SpectralLibrary:
                 ref = os.path.join(self._index_dir or '', f'{self._basename}_'
                                    f'{self._get_hyperparameter_hash()[:7]}_{z}.idxann')
                 if (import_faiss_cache and cfg.index == 'ivfflat' and self._index_dir is not None and
-                        verify_file_existence and os.path.isfile(ref)):
+                        verify_file_existence and os.path.isfile(ref) and not cfg.device_decoys):
                     self._faiss_filenames[z] = ref
                 if (self._index_dir is None or not verify_file_existence or
                         not (os.path.isfile(self._ann_filenames[z]) or z in self._faiss_filenames)):
@@ -280,10 +285,13 @@ class SpectralLibrary:
         pick up a stale file."""
         cfg = self.config
         if (cfg.index == 'ivfflat' and cfg.kmeans_niter == 25 and cfg.seed == 1234 and
-                cfg.flat_storage == 'fp32'):
+                cfg.flat_storage == 'fp32' and not cfg.device_decoys):
             return self._get_hyperparameter_hash()
         d = {hp: cfg[hp] for hp in self._hyperparameters}
         d.update(index=cfg.index, kmeans_niter=cfg.kmeans_niter, seed=cfg.seed)
+        if cfg.device_decoys:           # the index then holds the decoy rows too
+            from .library_store import decoy_options
+            d.update(decoys=decoy_options(cfg))
         if cfg.index in ('ivfflat', 'winflat') and cfg.flat_storage != 'fp32':
             d.update(flat_storage=cfg.flat_storage)
         if cfg.index == 'ivfpq':

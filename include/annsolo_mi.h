@@ -611,6 +611,43 @@ int asl_process_batch(const asl_peaks_t *raw, const asl_process_params_t *params
                       float *out_mz, float *out_intensity, int32_t *out_src,
                       int32_t *out_count, uint8_t *out_valid);
 
+/* ------------------------------------------------------------------ decoy spectra
+ * Replaces the per-spectrum shuffle_and_reposition of src/ann_solo/decoy_generator.py:93-185 (annotate
+ * the library spectrum with its peptide's a / b / p / y fragments, move every annotated peak to the same
+ * fragment of the shuffled peptide, re-sort), batched. The shuffle itself is the caller's: spectrum s
+ * brings its peptide as L = seq_offsets[s+1] - seq_offsets[s] residue masses m[0..L) (residue_mass,
+ * modifications folded into their residue), the permutation perm[0..L) (decoy residue i is target residue
+ * perm[i]; indices inside the spectrum's own slice), the terminal additions nterm[s] / cterm[s], which stay
+ * on the termini, and the largest fragment charge max_fragment_charge[s]. Raw peaks ascending in m/z.
+ * The arithmetic, all in IEEE double without fused multiply-add, is the contract:
+ *  1. ladders, sequential: P[0] = nterm, P[k] = P[k-1] + m[k-1]; S[0] = cterm, S[k] = S[k-1] + m[L-k];
+ *     the same two over m[perm[.]] for the decoy.
+ *  2. fragments, ion types in the order a, b, p, y (codes 1..4): base b = P[k], a = P[k] - 27.994915,
+ *     y = S[k] + 18.010565 for k = 1..L-1; p = (P[L] + cterm) + 18.010565 with k = L only. Fragment charge
+ *     z = 1..max_fragment_charge. Neutral losses in this order (loss index 0..13): 0, -1.007825, -17.026549,
+ *     -18.010565, -27.994915, -43.989829, -45.021464, -46.005479, -63.998301, -79.956818, -79.966331,
+ *     -91.009195, -91.993211, -97.976896. theo = (base + loss) / z + 1.007276466: add, divide, add.
+ *  3. peak i, x = (double)mz[i], matches a fragment iff fabs(x - theo) <= tolerance (ASL_TOL_DA) or
+ *     fabs(x - theo) <= (tolerance * 1e-6) * theo (ASL_TOL_PPM: of the theoretical m/z). It is annotated
+ *     with the match of LOWEST theo; exact ties by ion type, then k, then z, then loss index. No match: no
+ *     annotation.
+ *  4. an annotated peak moves to theo_decoy + (x - theo), theo_decoy being the same (type, k, z, loss) on
+ *     the decoy's ladders; any other peak keeps x. Intensities travel with their peaks.
+ *  5. stable ascending order by the double m/z (ties: raw peak index), then one rounding to float.
+ * Outputs, each nullable, in raw's own CSR layout (element offsets[s] + j): out_mz / out_intensity, out_src
+ * (the raw peak, inside its spectrum, decoy peak j came from), out_charge (its fragment charge, 0 = not
+ * annotated), and in RAW peak order the annotation found: ann_type (0 none, 1 a, 2 b, 3 p, 4 y), ann_n (k),
+ * ann_z, ann_loss (loss index). Spectra without peaks are legal.
+ * Limits, all checked on the host before anything is launched or written: more than 4096 peaks, L > 128 or
+ * max_fragment_charge > 8: ASL_ERR_CAPACITY; L < 2, max_fragment_charge < 1, a perm that is no permutation
+ * of 0..L-1, a non-finite mass, a negative or NaN tolerance, a unit other than the two: ASL_ERR_INVALID. */
+int asl_decoy_batch(const asl_peaks_t *raw, const int32_t *seq_offsets /* [n + 1] */,
+                    const double *residue_mass, const int32_t *perm, const double *nterm /* [n] */,
+                    const double *cterm /* [n] */, const int32_t *max_fragment_charge /* [n] */,
+                    double tolerance, int32_t tolerance_unit, float *out_mz, float *out_intensity,
+                    int32_t *out_src, uint8_t *out_charge, uint8_t *ann_type, uint8_t *ann_n,
+                    uint8_t *ann_z, uint8_t *ann_loss);
+
 /* ------------------------------------------------------------------ SSM features
  * Replaces the per-SSM SpectrumSimilarityCalculator calls of _compute_ssm_features
  *   /root/reference/src/ann_solo/utils.py:344-456
