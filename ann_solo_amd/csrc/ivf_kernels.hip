@@ -1,19 +1,21 @@
-// ivf_kernels.hip -- device kernels of the hand-written IVF index (replaces the
-// FAISS IndexFlatIP / IndexIVFFlat calls at
-// /root/reference/src/ann_solo/spectral_library.py:167-181,443-445 and adds the
-// IVF-PQ the north star asks for).
+// ivf_kernels.hip -- the generic device kernels of SEARCHING the hand-written IVF index (what builds one is in
+// quantizer.hip; the tiled IVF-PQ scan, the postings scan, the re-rank, the exchange and the rank scan have units
+// of their own).
 //
 //   row_select_kernel exact top-k of a SHORT score row held in registers (the coarse
 //                     top-nprobe of nlist): one histogram pass, one small sort
 //   row_topk_kernel   exact streaming top-k of one score row per workgroup (IndexFlatIP,
 //                     long rows, and IVF-Flat through a probed-list bitmap mask)
-//   pq_scan_kernel    per query: per-query ADC look-up table built in LDS, the
-//                     packed PQ codes of the probed lists streamed from HBM
-//                     (32 B/vector, coalesced 16-B loads), fused exact top-k
 //   topk_merge_hist_kernel / topk_merge_kernel  merge of per-shard partial top-k lists
 //                     ((score, id) pairs or packed 64-bit keys), histogram-threshold selection
-//   + small helpers (bitmap, argmax, residual/encode, gathers, L2 assignment)
+//   probe_bitmap_kernel  the probed lists of a query as a bitmap (row_topk_kernel's mask)
+//   gather_rows_f32_kernel / gather_rows_u8_kernel  row gathers
+//   pq_lut_kernel     the ADC look-up table of a query (build_lut_lds), written out
+//   pq_scan_kernel    the IVF-PQ scan of every PQ shape: per-query ADC look-up table built in LDS,
+//                     the packed PQ codes of the probed lists streamed from HBM (adc_score), fused exact top-k
+//   scanned_count_kernel  sum of the probed lists' lengths (the work counter of a scan)
 #include <algorithm>
+#include <type_traits>
 
 #include "common.hpp"
 #include "ivf_kernels.hpp"
@@ -335,53 +337,6 @@ int probe_bitmap(const int32_t *coarse_I, int nq, int nprobe, uint32_t *bitmap, 
   return ASL_OK;
 }
 
-// ------------------------------------------------------------------ row arg-max (ties: lowest col)
-__global__ __launch_bounds__(256) void row_argmax_kernel(const float *__restrict__ scores,
-                                                         int64_t ld, int n,
-                                                         int32_t *__restrict__ out) {
-  __shared__ float s_v[4];
-  __shared__ int s_i[4];
-  const int r = blockIdx.x, tid = threadIdx.x;
-  const float *row = scores + (size_t)r * ld;
-  float bv = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int c = tid; c < n; c += 256) {
-    const float v = row[c];
-    if (v > bv || (v == bv && c < bi)) {
-      bv = v;
-      bi = c;
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(bv, off);
-    const int oi = __shfl_xor(bi, off);
-    if (ov > bv || (ov == bv && oi < bi)) {
-      bv = ov;
-      bi = oi;
-    }
-  }
-  if ((tid & 63) == 0) {
-    s_v[tid >> 6] = bv;
-    s_i[tid >> 6] = bi;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) {
-        bv = s_v[w];
-        bi = s_i[w];
-      }
-    out[r] = bi == 0x7fffffff ? 0 : bi;
-  }
-}
-
-int row_argmax(const float *scores, int64_t ld, int rows, int n, int32_t *out) {
-  if (rows <= 0) return ASL_OK;
-  hipLaunchKernelGGL(row_argmax_kernel, dim3(rows), dim3(256), 0, stream(), scores, ld, n, out);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
 // ------------------------------------------------------------------ gathers
 __global__ void gather_rows_f32_kernel(const float *__restrict__ src, int64_t ld_src,
                                        const int64_t *__restrict__ rows, int64_t n, int d,
@@ -414,331 +369,6 @@ int gather_rows_u8(const uint8_t *src, const int32_t *rows, int64_t n, int m, ui
   if (n <= 0) return ASL_OK;
   hipLaunchKernelGGL(gather_rows_u8_kernel, grid_2d(cdiv(n * m, 256)), dim3(256), 0,
                      stream(), src, rows, n, m, dst);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-// ------------------------------------------------------------------ k-means update
-// One workgroup per cluster: members (ascending point order) are summed in fp32 in
-// that order, then divided by the count -- the oracle's loop, bit for bit.
-__global__ __launch_bounds__(256) void centroid_update_kernel(
-    const float *__restrict__ x, int64_t ld, int d, const int32_t *__restrict__ order,
-    const int32_t *__restrict__ offsets, float *__restrict__ centroids) {
-  const int c = blockIdx.x;
-  const int b = offsets[c], e = offsets[c + 1];
-  if (e == b) return;  // empty: left for the host-side split
-  const float cnt = (float)(e - b);
-  for (int j = threadIdx.x; j < d; j += 256) {
-    float s = 0.0f;
-    for (int t = b; t < e; ++t) s += x[(size_t)order[t] * ld + j];
-    centroids[(size_t)c * d + j] = s / cnt;
-  }
-}
-int centroid_update(const float *x, int64_t ld, int d, int k, const int32_t *order,
-                    const int32_t *offsets, float *centroids) {
-  hipLaunchKernelGGL(centroid_update_kernel, dim3(k), dim3(256), 0, stream(), x, ld, d, order,
-                     offsets, centroids);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-// Spherical k-means (FAISS cp.spherical for inner-product indexes): rows with a non-zero
-// norm are rescaled to unit L2 length. Canonical chain: ascending fmaf from +0, sqrtf, IEEE
-// divide (the encoder's norm) -- one lane walks the chain, the block divides.
-__global__ __launch_bounds__(256) void renorm_rows_kernel(float *__restrict__ c, int d) {
-  __shared__ float s_nrm;
-  float *row = c + (size_t)blockIdx.x * d;
-  if (threadIdx.x == 0) {
-    float acc = 0.0f;
-    for (int j = 0; j < d; ++j) acc = __builtin_fmaf(row[j], row[j], acc);
-    s_nrm = acc > 0.0f ? __builtin_sqrtf(acc) : 0.0f;
-  }
-  __syncthreads();
-  const float nrm = s_nrm;
-  if (nrm > 0.0f)
-    for (int j = threadIdx.x; j < d; j += 256) row[j] = row[j] / nrm;
-}
-int renorm_rows(float *c, int k, int d) {
-  if (k <= 0) return ASL_OK;
-  hipLaunchKernelGGL(renorm_rows_kernel, dim3(k), dim3(256), 0, stream(), c, d);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-// ------------------------------------------------------------------ L2 assignment (PQ)
-// x: [n, ld] (sub-vector view), cb: [ksub, dsub]. Chain
-// acc = fmaf(x-c, x-c, acc) ascending, arg-min with lowest-index ties.
-__global__ __launch_bounds__(256) void l2_assign_kernel(const float *__restrict__ x,
-                                                        int64_t ld, int64_t n, int dsub,
-                                                        const float *__restrict__ cb, int ksub,
-                                                        int32_t *__restrict__ assign) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *s_cb = reinterpret_cast<float *>(smem);
-  for (int i = threadIdx.x; i < ksub * dsub; i += 256) s_cb[i] = cb[i];
-  __syncthreads();
-  const int64_t i = block_linear() * 256 + threadIdx.x;
-  if (i >= n) return;
-  float bs = INFINITY;
-  int best = 0;
-  if (dsub <= PQ_MAX_DSUB) {
-    float xv[PQ_MAX_DSUB];
-#pragma unroll
-    for (int t = 0; t < PQ_MAX_DSUB; ++t) xv[t] = t < dsub ? x[i * ld + t] : 0.0f;
-    for (int c = 0; c < ksub; ++c) {
-      float acc = 0.0f;
-#pragma unroll
-      for (int t = 0; t < PQ_MAX_DSUB; ++t)
-        if (t < dsub) {
-          const float df = xv[t] - s_cb[c * dsub + t];
-          acc = __builtin_fmaf(df, df, acc);
-        }
-      if (acc < bs) {
-        bs = acc;
-        best = c;
-      }
-    }
-  } else {  // wide sub-vectors: operands re-read through L1 (slow path, same arithmetic)
-    for (int c = 0; c < ksub; ++c) {
-      float acc = 0.0f;
-      for (int t = 0; t < dsub; ++t) {
-        const float df = x[i * ld + t] - s_cb[c * dsub + t];
-        acc = __builtin_fmaf(df, df, acc);
-      }
-      if (acc < bs) {
-        bs = acc;
-        best = c;
-      }
-    }
-  }
-  assign[i] = best;
-}
-// A codebook beyond the 64 KB of LDS every kernel may ask for (wide sub-vectors only: d = 800 with
-// m = 4 is 204 800 B, m = 8 102 400 B): staged `chunk` codes at a time, (bs, best) carried from one
-// round to the next by l2_argmin_wide -- the slow path's loop, so the same arg-min. Kernels of their own,
-// and a loop of their own: l2_assign_kernel and pq_encode_kernel, which every codebook within 64 KB still
-// takes in one piece (the default shape among them), stay as they were to the instruction: built on this
-// helper as well, pq_encode_kernel takes 44 VGPRs instead of 42 (profiles/pq_shapes_resource_usage.txt).
-// Launcher and kernel compute `chunk` alike.
-// One round of that slow path, for the two rounds kernels (RES: the operand is the residual xi[t] - ci[t]):
-// codes [c0, c0 + nc) staged at s_cb, ascending c, strict <, the running (bs, best) carried in and out.
-template <bool RES>
-__device__ __forceinline__ void l2_argmin_wide(const float *xi, const float *ci, int dsub,
-                                               const float *s_cb, int c0, int nc, float &bs, int &best) {
-  for (int c = 0; c < nc; ++c) {
-    float acc = 0.0f;
-    for (int t = 0; t < dsub; ++t) {
-      const float df = (RES ? xi[t] - ci[t] : xi[t]) - s_cb[c * dsub + t];
-      acc = __builtin_fmaf(df, df, acc);
-    }
-    if (acc < bs) {
-      bs = acc;
-      best = c0 + c;
-    }
-  }
-}
-__host__ __device__ static inline int pq_cb_chunk(int ksub, int dsub) {
-  const int fit = 64 * 1024 / 4 / dsub;      // (0: not even one code; asl_index_create accepts no such index)
-  return ksub < fit ? ksub : fit;
-}
-__global__ __launch_bounds__(256) void l2_assign_rounds_kernel(const float *__restrict__ x,
-                                                               int64_t ld, int64_t n, int dsub,
-                                                               const float *__restrict__ cb, int ksub,
-                                                               int32_t *__restrict__ assign) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *s_cb = reinterpret_cast<float *>(smem);
-  const int64_t i = block_linear() * 256 + threadIdx.x;
-  const int chunk = pq_cb_chunk(ksub, dsub);
-  float bs = INFINITY;
-  int best = 0;
-  for (int c0 = 0; c0 < ksub; c0 += chunk) {
-    const int nc = min(chunk, ksub - c0);
-    if (c0) __syncthreads();      // every lane is done with the codes before
-    for (int j = threadIdx.x; j < nc * dsub; j += 256) s_cb[j] = cb[(size_t)c0 * dsub + j];
-    __syncthreads();
-    if (i < n) l2_argmin_wide<false>(x + i * ld, nullptr, dsub, s_cb, c0, nc, bs, best);
-  }
-  if (i < n) assign[i] = best;
-}
-int l2_assign(const float *x, int64_t ld, int64_t n, int dsub, const float *cb, int ksub,
-              int32_t *assign) {
-  if (n <= 0) return ASL_OK;
-  const int chunk = pq_cb_chunk(ksub, dsub);
-  if (chunk < 1) return fail(ASL_ERR_CAPACITY, "l2_assign: a sub-vector of %d floats does not fit LDS", dsub);
-  hipLaunchKernelGGL(chunk == ksub ? l2_assign_kernel : l2_assign_rounds_kernel, grid_2d(cdiv(n, 256)),
-                     dim3(256), (size_t)chunk * dsub * 4, stream(), x, ld, n, dsub, cb, ksub, assign);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-// residual r = x - centroid[assign] (fp32 subtract), in place or to dst
-__global__ void residual_kernel(const float *__restrict__ x, const int32_t *__restrict__ assign,
-                                const float *__restrict__ centroids, int64_t n, int d,
-                                float *__restrict__ dst) {
-  const int64_t i = block_linear();
-  if (i >= n) return;
-  const float *c = centroids + (size_t)assign[i] * d;
-  for (int j = threadIdx.x; j < d; j += blockDim.x)
-    dst[i * d + j] = x[i * d + j] - c[j];
-}
-int residual(const float *x, const int32_t *assign, const float *centroids, int64_t n, int d,
-             float *dst) {
-  if (n <= 0) return ASL_OK;
-  hipLaunchKernelGGL(residual_kernel, grid_2d(n), dim3(256), 0, stream(), x, assign,
-                     centroids, n, d, dst);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-// PQ encode: grid (vector tiles, m). code = argmin_c L2(residual_sub, cb[m][c]).
-__global__ __launch_bounds__(256) void pq_encode_kernel(
-    const float *__restrict__ x, const int32_t *__restrict__ assign,
-    const float *__restrict__ centroids, const float *__restrict__ codebooks, int64_t n, int d,
-    int m, int ksub, int dsub, uint8_t *__restrict__ codes) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *s_cb = reinterpret_cast<float *>(smem);
-  const int mi = blockIdx.y;
-  const float *cb = codebooks + (size_t)mi * ksub * dsub;
-  for (int i = threadIdx.x; i < ksub * dsub; i += 256) s_cb[i] = cb[i];
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float *xi = x + (size_t)i * d + (size_t)mi * dsub;
-  const float *ci = centroids + (size_t)assign[i] * d + (size_t)mi * dsub;
-  float bs = INFINITY;
-  int best = 0;
-  if (dsub <= PQ_MAX_DSUB) {
-    float rv[PQ_MAX_DSUB];
-#pragma unroll
-    for (int t = 0; t < PQ_MAX_DSUB; ++t) rv[t] = t < dsub ? xi[t] - ci[t] : 0.0f;
-    for (int c = 0; c < ksub; ++c) {
-      float acc = 0.0f;
-#pragma unroll
-      for (int t = 0; t < PQ_MAX_DSUB; ++t)
-        if (t < dsub) {
-          const float df = rv[t] - s_cb[c * dsub + t];
-          acc = __builtin_fmaf(df, df, acc);
-        }
-      if (acc < bs) {
-        bs = acc;
-        best = c;
-      }
-    }
-  } else {
-    for (int c = 0; c < ksub; ++c) {
-      float acc = 0.0f;
-      for (int t = 0; t < dsub; ++t) {
-        const float df = (xi[t] - ci[t]) - s_cb[c * dsub + t];
-        acc = __builtin_fmaf(df, df, acc);
-      }
-      if (acc < bs) {
-        bs = acc;
-        best = c;
-      }
-    }
-  }
-  codes[(size_t)i * m + mi] = (uint8_t)best;
-}
-// (a codebook beyond 64 KB in rounds of pq_cb_chunk codes, as l2_assign_rounds_kernel)
-__global__ __launch_bounds__(256) void pq_encode_rounds_kernel(
-    const float *__restrict__ x, const int32_t *__restrict__ assign,
-    const float *__restrict__ centroids, const float *__restrict__ codebooks, int64_t n, int d,
-    int m, int ksub, int dsub, uint8_t *__restrict__ codes) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *s_cb = reinterpret_cast<float *>(smem);
-  const int mi = blockIdx.y;
-  const float *cb = codebooks + (size_t)mi * ksub * dsub;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const bool live = i < n;
-  const float *xi = x + (size_t)(live ? i : 0) * d + (size_t)mi * dsub;
-  const float *ci = centroids + (size_t)(live ? assign[i] : 0) * d + (size_t)mi * dsub;
-  const int chunk = pq_cb_chunk(ksub, dsub);
-  float bs = INFINITY;
-  int best = 0;
-  for (int c0 = 0; c0 < ksub; c0 += chunk) {
-    const int nc = min(chunk, ksub - c0);
-    if (c0) __syncthreads();      // every lane is done with the codes before
-    for (int j = threadIdx.x; j < nc * dsub; j += 256) s_cb[j] = cb[(size_t)c0 * dsub + j];
-    __syncthreads();
-    if (live) l2_argmin_wide<true>(xi, ci, dsub, s_cb, c0, nc, bs, best);
-  }
-  if (live) codes[(size_t)i * m + mi] = (uint8_t)best;
-}
-// by_residual off (FAISS' IndexIVFPQ::by_residual = false): code = argmin_c L2(x_sub, cb[m][c]) of the vector
-// itself -- no list assignment, no centroid row. The same three shapes, the same rule (ascending c, strict <,
-// the lowest code wins a tie) and the same fmaf chain as the pair above, in kernels of their own so that those
-// two stay as they are to the instruction (profiles/pq_by_residual_resource_usage.txt).
-__global__ __launch_bounds__(256) void pq_encode_raw_kernel(
-    const float *__restrict__ x, const float *__restrict__ codebooks, int64_t n, int d, int m, int ksub,
-    int dsub, uint8_t *__restrict__ codes) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *s_cb = reinterpret_cast<float *>(smem);
-  const int mi = blockIdx.y;
-  const float *cb = codebooks + (size_t)mi * ksub * dsub;
-  for (int i = threadIdx.x; i < ksub * dsub; i += 256) s_cb[i] = cb[i];
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float *xi = x + (size_t)i * d + (size_t)mi * dsub;
-  float bs = INFINITY;
-  int best = 0;
-  if (dsub <= PQ_MAX_DSUB) {
-    float xv[PQ_MAX_DSUB];
-#pragma unroll
-    for (int t = 0; t < PQ_MAX_DSUB; ++t) xv[t] = t < dsub ? xi[t] : 0.0f;
-    for (int c = 0; c < ksub; ++c) {
-      float acc = 0.0f;
-#pragma unroll
-      for (int t = 0; t < PQ_MAX_DSUB; ++t)
-        if (t < dsub) {
-          const float df = xv[t] - s_cb[c * dsub + t];
-          acc = __builtin_fmaf(df, df, acc);
-        }
-      if (acc < bs) {
-        bs = acc;
-        best = c;
-      }
-    }
-  } else {
-    l2_argmin_wide<false>(xi, nullptr, dsub, s_cb, 0, ksub, bs, best);
-  }
-  codes[(size_t)i * m + mi] = (uint8_t)best;
-}
-__global__ __launch_bounds__(256) void pq_encode_raw_rounds_kernel(
-    const float *__restrict__ x, const float *__restrict__ codebooks, int64_t n, int d, int m, int ksub,
-    int dsub, uint8_t *__restrict__ codes) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *s_cb = reinterpret_cast<float *>(smem);
-  const int mi = blockIdx.y;
-  const float *cb = codebooks + (size_t)mi * ksub * dsub;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const bool live = i < n;
-  const float *xi = x + (size_t)(live ? i : 0) * d + (size_t)mi * dsub;
-  const int chunk = pq_cb_chunk(ksub, dsub);
-  float bs = INFINITY;
-  int best = 0;
-  for (int c0 = 0; c0 < ksub; c0 += chunk) {
-    const int nc = min(chunk, ksub - c0);
-    if (c0) __syncthreads();      // every lane is done with the codes before
-    for (int j = threadIdx.x; j < nc * dsub; j += 256) s_cb[j] = cb[(size_t)c0 * dsub + j];
-    __syncthreads();
-    if (live) l2_argmin_wide<false>(xi, nullptr, dsub, s_cb, c0, nc, bs, best);
-  }
-  if (live) codes[(size_t)i * m + mi] = (uint8_t)best;
-}
-int pq_encode(const float *x, const int32_t *assign, const float *centroids,
-              const float *codebooks, int64_t n, int d, int m, int ksub, int dsub,
-              uint8_t *codes, bool by_residual) {
-  if (n <= 0) return ASL_OK;
-  const int chunk = pq_cb_chunk(ksub, dsub);
-  if (chunk < 1) return fail(ASL_ERR_CAPACITY, "pq_encode: a sub-vector of %d floats does not fit LDS", dsub);
-  if (!by_residual)
-    hipLaunchKernelGGL(chunk == ksub ? pq_encode_raw_kernel : pq_encode_raw_rounds_kernel,
-                       dim3((unsigned)cdiv(n, 256), m), dim3(256), (size_t)chunk * dsub * 4, stream(), x,
-                       codebooks, n, d, m, ksub, dsub, codes);
-  else
-    hipLaunchKernelGGL(chunk == ksub ? pq_encode_kernel : pq_encode_rounds_kernel,
-                       dim3((unsigned)cdiv(n, 256), m), dim3(256), (size_t)chunk * dsub * 4, stream(), x,
-                       assign, centroids, codebooks, n, d, m, ksub, dsub, codes);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }
@@ -869,26 +499,6 @@ size_t pq_scan_lds_bytes(int m, int ksub, int d, int k) {
   return (size_t)topk_cap_for(k) * 8 + 16 + ((size_t)m * ksub + d) * 4;
 }
 
-template <int M>
-static int launch_pq_scan(const float *xq, int nq, int d, const float *codebooks, int ksub,
-                          int dsub, const float *coarse_D, const int32_t *coarse_I, int nprobe,
-                          const int32_t *list_offsets, const int32_t *ids, const uint8_t *codes,
-                          int k, float *D, int64_t *I64, int32_t *I32, int64_t out_ld,
-                          const uint64_t *upper_in, uint64_t *upper_out) {
-  const int cap = topk_cap_for(k);
-  const size_t lds = pq_scan_lds_bytes(M, ksub, d, k);
-  if (lds > (size_t)PQ_MAX_LDS_BYTES) return fail(ASL_ERR_CAPACITY, "pq scan: k=%d / m=%d do not fit LDS", k, M);
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute((const void *)pq_scan_kernel<M>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(pq_scan_kernel<M>, dim3(nq), dim3(TK_NT), lds, stream(), xq, d, codebooks,
-                     ksub, dsub, coarse_D, coarse_I, nprobe, list_offsets, ids, codes, k, cap,
-                     D, I64, I32, out_ld > 0 ? out_ld : (int64_t)k, reinterpret_cast<const u64 *>(upper_in),
-                     reinterpret_cast<u64 *>(upper_out));
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
 int pq_scan(const float *xq, int nq, int d, const float *codebooks, int m, int ksub, int dsub,
             const float *coarse_D, const int32_t *coarse_I, int nprobe,
             const int32_t *list_offsets, const int32_t *ids, const uint8_t *codes, int k,
@@ -896,15 +506,31 @@ int pq_scan(const float *xq, int nq, int d, const float *codebooks, int m, int k
             uint64_t *upper_out) {
   if (nq <= 0) return ASL_OK;
   if (k <= 0 || k > TK_MAX_K) return fail(ASL_ERR_CAPACITY, "pq scan: k=%d outside 1..%d", k, TK_MAX_K);
+  const auto launch = [&](auto m_const) -> int {      // the kernel's M arrives as a std::integral_constant
+    constexpr int M = decltype(m_const)::value;
+    const int cap = topk_cap_for(k);
+    const size_t lds = pq_scan_lds_bytes(M, ksub, d, k);
+    if (lds > (size_t)PQ_MAX_LDS_BYTES) return fail(ASL_ERR_CAPACITY, "pq scan: k=%d / m=%d do not fit LDS", k, M);
+    if (lds > 64 * 1024)
+      HIP_TRY(hipFuncSetAttribute((const void *)pq_scan_kernel<M>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(pq_scan_kernel<M>, dim3(nq), dim3(TK_NT), lds, stream(), xq, d, codebooks,
+                       ksub, dsub, coarse_D, coarse_I, nprobe, list_offsets, ids, codes, k, cap,
+                       D, I64, I32, out_ld > 0 ? out_ld : (int64_t)k, reinterpret_cast<const u64 *>(upper_in),
+                       reinterpret_cast<u64 *>(upper_out));
+    ASL_CHECK_LAUNCH();
+    return ASL_OK;
+  };
   switch (m) {
-    case 4: return launch_pq_scan<4>(xq, nq, d, codebooks, ksub, dsub, coarse_D, coarse_I, nprobe, list_offsets, ids, codes, k, D, I64, I32, out_ld, upper_in, upper_out);
-    case 8: return launch_pq_scan<8>(xq, nq, d, codebooks, ksub, dsub, coarse_D, coarse_I, nprobe, list_offsets, ids, codes, k, D, I64, I32, out_ld, upper_in, upper_out);
-    case 16: return launch_pq_scan<16>(xq, nq, d, codebooks, ksub, dsub, coarse_D, coarse_I, nprobe, list_offsets, ids, codes, k, D, I64, I32, out_ld, upper_in, upper_out);
-    case 32: return launch_pq_scan<32>(xq, nq, d, codebooks, ksub, dsub, coarse_D, coarse_I, nprobe, list_offsets, ids, codes, k, D, I64, I32, out_ld, upper_in, upper_out);
-    case 64: return launch_pq_scan<64>(xq, nq, d, codebooks, ksub, dsub, coarse_D, coarse_I, nprobe, list_offsets, ids, codes, k, D, I64, I32, out_ld, upper_in, upper_out);
+    case 4: return launch(std::integral_constant<int, 4>{});
+    case 8: return launch(std::integral_constant<int, 8>{});
+    case 16: return launch(std::integral_constant<int, 16>{});
+    case 32: return launch(std::integral_constant<int, 32>{});
+    case 64: return launch(std::integral_constant<int, 64>{});
     default: return fail(ASL_ERR_INVALID, "pq scan: pq_m must be one of 4,8,16,32,64 (got %d)", m);
   }
 }
+
 
 // sum over queries of probed list lengths (algorithmic work of a scan launch)
 __global__ void scanned_count_kernel(const int32_t *__restrict__ coarse_I, int64_t n,

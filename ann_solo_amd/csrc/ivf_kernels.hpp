@@ -1,5 +1,5 @@
 // ivf_kernels.hpp -- host-callable wrappers of the IVF device kernels (all pointers
-// are device pointers; everything is enqueued on asl::stream()).
+// are device pointers; everything is enqueued on asl::stream()). One block per translation unit.
 #pragma once
 #include <cstdint>
 
@@ -16,11 +16,13 @@ constexpr int TK_MAX_K_PASSES = 16384;   // largest k of a search: beyond TK_MAX
 constexpr int PQ_MAX_DSUB = 32;   // register fast path of the PQ L2 kernels
 constexpr int PQ_MAX_LDS_BYTES = 160 * 1024;   // a workgroup's LDS: what pq_scan_lds_bytes may come to
 
+// ---- gemm.hip
 // gate != nullptr: the kernel returns at once when *gate <= gate_max (device-side choice
 // between this GEMM and the sparse coarse quantiser)
 int gemm_nt_f32(const float *A, const float *B, float *C, int M, int N, int K, int lda,
                 int ldb, int ldc, const int *gate = nullptr, int gate_max = 0);
-// coarse quantiser for sparse queries (coarse_sparse.hip)
+
+// ---- coarse_sparse.hip: coarse quantiser for sparse queries
 bool coarse_sparse_supported(int d, int nlist);
 int coarse_sparse_cap();
 // ent[q][64] = (dimension * 128, value bits) of the non-zero components of row q, ascending;
@@ -29,6 +31,8 @@ int list_nonzeros(const float *xq, int nq, int d, int64_t ldq, uint2 *ent, int32
 int transpose_f32(const float *in, int rows, int cols, float *out);
 int coarse_sparse(const float *xq, int nq, int d, const float *Ct, int nlist, uint2 *ent,
                   int32_t *cnt, int *n_over, int over_max, float *scores, int ld, int64_t ldq = 0);
+
+// ---- ivf_kernels.hip: top-k and merges, gathers, the ADC table and the generic IVF-PQ scan
 int row_topk(const float *scores, int64_t ld, int rows, int n, int k, const int32_t *ids,
              int32_t id_base, const int32_t *vlist, const uint32_t *bitmap, int bitmap_words,
              float *D, int64_t *I64, int32_t *I32, int64_t out_ld,
@@ -38,10 +42,23 @@ int row_topk(const float *scores, int64_t ld, int rows, int n, int k, const int3
 int topk_merge(const float *Ds, const int64_t *Is, int S, int nq, int k, float *D, int64_t *I);
 int topk_merge_keys(const int64_t *Ks, int S, int nq, int k, float *D, int64_t *I, int unordered);
 int probe_bitmap(const int32_t *coarse_I, int nq, int nprobe, uint32_t *bitmap, int words);
-int row_argmax(const float *scores, int64_t ld, int rows, int n, int32_t *out);
 int gather_rows_f32(const float *src, int64_t ld_src, const int64_t *rows, int64_t n, int d,
                     float *dst, int64_t ld_dst);
 int gather_rows_u8(const uint8_t *src, const int32_t *rows, int64_t n, int m, uint8_t *dst);
+int pq_lut(const float *xq, int nq, int d, const float *codebooks, int m, int ksub, int dsub,
+           float *lut_out);
+int pq_scan(const float *xq, int nq, int d, const float *codebooks, int m, int ksub, int dsub,
+            const float *coarse_D, const int32_t *coarse_I, int nprobe,
+            const int32_t *list_offsets, const int32_t *ids, const uint8_t *codes, int k,
+            float *D, int64_t *I64, int32_t *I32, int64_t out_ld = 0,
+            const uint64_t *upper_in = nullptr, uint64_t *upper_out = nullptr);
+// LDS of a pq_scan workgroup: the top-k buffer of k, the ADC table and the query
+size_t pq_scan_lds_bytes(int m, int ksub, int d, int k);
+int scanned_count(const int32_t *coarse_I, int64_t n, const int32_t *list_offsets,
+                  unsigned long long *out_dev);
+
+// ---- quantizer.hip: what builds an index (k-means, list assignment, the PQ codec)
+int row_argmax(const float *scores, int64_t ld, int rows, int n, int32_t *out);
 int centroid_update(const float *x, int64_t ld, int d, int k, const int32_t *order,
                     const int32_t *offsets, float *centroids);
 int renorm_rows(float *c, int k, int d);
@@ -52,25 +69,17 @@ int residual(const float *x, const int32_t *assign, const float *centroids, int6
 int pq_encode(const float *x, const int32_t *assign, const float *centroids,
               const float *codebooks, int64_t n, int d, int m, int ksub, int dsub,
               uint8_t *codes, bool by_residual = true);   // false: x itself is encoded (assign / centroids unread)
-int pq_lut(const float *xq, int nq, int d, const float *codebooks, int m, int ksub, int dsub,
-           float *lut_out);
-int pq_scan(const float *xq, int nq, int d, const float *codebooks, int m, int ksub, int dsub,
-            const float *coarse_D, const int32_t *coarse_I, int nprobe,
-            const int32_t *list_offsets, const int32_t *ids, const uint8_t *codes, int k,
-            float *D, int64_t *I64, int32_t *I32, int64_t out_ld = 0,
-            const uint64_t *upper_in = nullptr, uint64_t *upper_out = nullptr);
-// tiled IVF-PQ scan (pq_scan_v3.hip): m = 32 sub-quantisers of 8 bits
+
+// ---- pq_scan_v3.hip: tiled IVF-PQ scan, m = 32 sub-quantisers of 8 bits
 bool pq_scan_tiled_supported(int m, int ksub, int k, int nprobe);
-// LDS of a pq_scan workgroup: the top-k buffer of k, the ADC table and the query
-size_t pq_scan_lds_bytes(int m, int ksub, int d, int k);
 int pq_scan_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
                const float *coarse_D, const int32_t *coarse_I, int nprobe,
                const int32_t *list_offsets, const int32_t *tile_offsets,
                const uint8_t *codes_tiled, const int32_t *ids_tiled, int k, float *D,
                int64_t *I64, int32_t *I32, int set_mode, const uint2 *ent = nullptr,
                const int32_t *ent_cnt = nullptr,    // ent / ent_cnt: list_nonzeros (64 entries per query)
-               const int *gate = nullptr,
-               const ScanPostFilter *post = nullptr,   // (common.hpp) set-mode int32 rows, k <= 1280 only          // device-side row count: workgroups past it return at once
+               const int *gate = nullptr,           // device-side row count: workgroups past it return at once
+               const ScanPostFilter *post = nullptr,   // (common.hpp) set-mode int32 rows, k <= 1280 only
                const ScanRanges *ranges = nullptr,   // (common.hpp) window scan of the window-ordered layout, k <= 1280
                const unsigned long long *sel = nullptr,    // selector: a word per tile of the layout scanned, k <= 1280
                const uint8_t *codes_mm = nullptr,          // the sub-quantiser-major copy of codes_tiled and its plane
@@ -81,13 +90,14 @@ int mmajor_codes(const uint8_t *codes_tiled, int64_t ntiles, uint32_t plane, uin
 // selector words of a tiled layout: bit v of words[tile] = keep[slot_ids[tile * 64 + v]] (id -1: unselected)
 int tile_selector(const int32_t *slot_ids, int64_t ntiles, const uint8_t *keep, int64_t n,
                   unsigned long long *words);
-// [lo, hi) of the in-window run of every (query, probe) in the window-ordered layout (pq_scan_v3.hip)
+// [lo, hi) of the in-window run of every (query, probe) in the window-ordered layout
 int window_ranges(const double *q_pmz, int nq, const int32_t *coarse_I, int nprobe,
                   const int32_t *list_offsets, const int32_t *tile_offsets, const float *wkey, int charge,
                   double tol, int mode, int2 *ranges, unsigned long long *acc);
 int tile_codes(const uint8_t *codes, const int32_t *ids, const int32_t *dst_slot, int64_t n,
                int64_t ntiles, uint8_t *codes_tiled, int32_t *ids_tiled);
-// dimension-major IVF-Flat (flat_scan.hip): blocks of FI_BLK vectors with per-dimension postings
+
+// ---- flat_scan.hip: dimension-major IVF-Flat, blocks of FI_BLK vectors with per-dimension postings
 // FI_BLK measured (scan ms at nprobe 128): 512 7.69 | 640 7.14 | 768 6.81 | 832 6.71 | 864 6.70 (the LDS limit of three workgroups per CU) | 1024: two workgroups per CU
 constexpr int FI_BLK = 832;
 bool flat_inv_supported(int d, int k, int nprobe);
@@ -102,7 +112,7 @@ int flat_inv_scan(int layout, const float *xq, int nq, int d, const int32_t *coa
                   const unsigned long long *sel = nullptr,    // selector: flat_selector's words, k <= 1280
                   const ScanRanges *ranges = nullptr);        // (common.hpp) the window-exact index: range [nq], one run of
                                                               // positions per query in ONE list; probes and offsets unread
-// the runs of the window-exact index (flat_scan.hip): [lo, hi) per query over the key column by position
+// the runs of the window-exact index: [lo, hi) per query over the key column by position
 // (ascending, NaN last); q_pmz == nullptr: [0, n) for every query
 int winflat_runs(const double *q_pmz, int nq, const float *key, int64_t n, int charge, double tol, int mode,
                  int2 *runs, unsigned long long *acc);
@@ -113,19 +123,22 @@ int flat_selector(const int32_t *list_offsets, const int32_t *blk_offsets, int n
 int flat_selector_words_per_block();
 int flat_inv_work(const float *xq, int nq, int d, const int32_t *coarse_I, int nprobe,
                   const int32_t *blk_offsets, const uint32_t *seg_tab, unsigned long long *out_dev);
+int flat_fx_work(const float *xq, int nq, int d, const int32_t *coarse_I, int nprobe,
+                 const int32_t *blk_offsets, const uint8_t *tab8, int tab_stride,
+                 const uint16_t *cnt16, unsigned long long *out_dev);
 uint32_t inv_place_block(const uint32_t *cnt, int d, uint32_t *tab, bool *ok);
-// exact re-rank of a short-list against sparse stored rows (refine.hip)
-int refine_stride();
-int refine_append_rows(const float *x, int64_t n, int d, int64_t row0, uint16_t *r_dim, float *r_val,
-                       uint8_t *r_cnt, int *status);
-int refine_topk(const float *xq, int nq, int d, const int32_t *I_in, const int64_t *I_in64, int kp,
-                const uint16_t *r_dim, const float *r_val, const uint8_t *r_cnt, int64_t n_rows, int k, float *D,
-                int64_t *I64, int32_t *I32);
+int count_nnz(const float *vecs, int d, int64_t n, int32_t *nnz, int32_t *nnz_max_dev);
 int inv_count(const float *vecs, int d, const int32_t *order, const int32_t *pos_blk, int64_t n,
               uint32_t *cnt);
 int inv_fill(const float *vecs, int d, const int32_t *order, const int32_t *pos_blk,
              const uint16_t *pos_loc, int64_t n, const uint32_t *blk_base,
              const uint32_t *seg_tab, uint32_t *cursor, char *seg_bytes);
+int inv_order(int64_t nblocks, int d, const uint32_t *blk_base, const uint32_t *seg_tab,
+              char *seg_bytes);
+int fx_fill(const float *vecs, int d, const int32_t *order, const int32_t *pos_blk,
+            const uint16_t *pos_loc, int64_t n, const uint32_t *seg_line, uint32_t *cursor,
+            uint32_t *words);
+int fx_order(int64_t ncell, const uint32_t *seg_line, const uint32_t *count, uint32_t *words);
 // fixed-point storage (22 fractional bits) of IVF-Flat components in [0, 1)
 __host__ __device__ inline float fx22_round(float x) {
   if (!(x >= 0.0f && x < 1.0f)) return x;
@@ -136,7 +149,16 @@ __host__ __device__ inline bool fx22_on_grid(float x) {
   return x > 0.0f && x < 1.0f && x * 4194304.0f == rintf(x * 4194304.0f);
 }
 int quantize_fx22(float *x, int64_t n);
-// the exact top-k exchange of a sharded search (exchange.hip)
+
+// ---- refine.hip: exact re-rank of a short-list against sparse stored rows
+int refine_stride();
+int refine_append_rows(const float *x, int64_t n, int d, int64_t row0, uint16_t *r_dim, float *r_val,
+                       uint8_t *r_cnt, int *status);
+int refine_topk(const float *xq, int nq, int d, const int32_t *I_in, const int64_t *I_in64, int kp,
+                const uint16_t *r_dim, const float *r_val, const uint8_t *r_cnt, int64_t n_rows, int k, float *D,
+                int64_t *I64, int32_t *I32);
+
+// ---- exchange.hip: the exact top-k exchange of a sharded search
 int keys_split(const unsigned long long *K, int64_t nrows, int k, int kp, unsigned long long *head,
                int32_t *floor_out, unsigned long long *rowmin_out = nullptr);
 int keys_merge(const unsigned long long *heads, int S, int nq, int kp, int k, const unsigned long long *xbuf,
@@ -148,19 +170,8 @@ int keys_extras(const unsigned long long *K, const int32_t *floor_in, int64_t nr
                 const unsigned long long *K3 = nullptr, int k3 = 0);
 int rescan_list(const unsigned long long *bounds, const unsigned long long *rowmin, int64_t nrows, int R,
                 int64_t *rowlist, int32_t *rmap, int *count, int32_t *overflow);
-int flat_fx_work(const float *xq, int nq, int d, const int32_t *coarse_I, int nprobe,
-                 const int32_t *blk_offsets, const uint8_t *tab8, int tab_stride,
-                 const uint16_t *cnt16, unsigned long long *out_dev);
-int fx_fill(const float *vecs, int d, const int32_t *order, const int32_t *pos_blk,
-            const uint16_t *pos_loc, int64_t n, const uint32_t *seg_line, uint32_t *cursor,
-            uint32_t *words);
-int fx_order(int64_t ncell, const uint32_t *seg_line, const uint32_t *count, uint32_t *words);
-int inv_order(int64_t nblocks, int d, const uint32_t *blk_base, const uint32_t *seg_tab,
-              char *seg_bytes);
-int count_nnz(const float *vecs, int d, int64_t n, int32_t *nnz, int32_t *nnz_max_dev);
-int scanned_count(const int32_t *coarse_I, int64_t n, const int32_t *list_offsets,
-                  unsigned long long *out_dev);
-// rank of a target vector in the scans' (score desc, id asc) order (rank_scan.hip; asl_index_rank)
+
+// ---- rank_scan.hip: rank of a target vector in the scans' (score desc, id asc) order (asl_index_rank)
 struct RankWindow {                 // the scope's precursor window; key_slot == nullptr: none
   const float *key_slot = nullptr;  // the key column by storage slot (rank_slot_keys)
   const double *q_pmz = nullptr;    // per query

@@ -10,7 +10,10 @@ Per mode, on default and hard queries of synthetic.make_queries:
   * best-match agreement with the brute-force open search (scripts/bf_agreement.py's measure);
   * asl_index_rank: the share of brute-force winners / source rows with rank < 1, 10, 256, 1024 in the
     probed scope, without and with the precursor window (scripts/rank_curve.py's measure);
-  * index training and add times (host clock around the synchronous calls);
+  * index training and add times (host clock around the synchronous calls); `--codec-only` stops after these
+    and adds the add time of 262 144 random unit vectors at (800, 8, 8) -- codebooks of 102 400 B, staged in
+    rounds -- with random unit quantisers installed by set_trained, and measures nothing else (the A/B of the
+    quantiser kernels against another build of the library, ASL_LIB_PATH);
   * the pipelined step over `--steps` steps of `--batch` queries, `--rounds` alternating rounds, and the
     stage timers of ten more steps;
   * where in a query's probe order its top-k hits lie (mean probe position, share in the first 16 of the
@@ -66,9 +69,49 @@ def main():
     ap.add_argument('--refine-k', type=int, default=2048)
     ap.add_argument('--open-da', type=float, default=500.0)
     ap.add_argument('--out', default='pq_by_residual.json')
+    ap.add_argument('--codec-only', action='store_true', help='train / add times only (see above)')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     lib, aux = synthetic.make_library(args.library_size, seed=20240807, device=dev, charges=(2,), charge_p=(1.0,))
+    common = dict(precursor_tolerance_mass_open=args.open_da, precursor_tolerance_mode_open='Da',
+                  batch_size=args.batch, seed=1234)
+    ann = dict(mode='ann', index='ivfpq', pq_m=32, num_list=args.nlist, num_probe=args.nprobe,
+               num_candidates=args.k, kmeans_niter=args.niter, **common)
+
+    def build(by_res):
+        """(engine, train seconds, add seconds) of one mode: the index is trained and filled here under the clock"""
+        sl = SpectralLibrary(lib, config=Config.open_search(pq_by_residual=by_res, **ann), device=dev)
+        vec = sl._encode(sl.partitions[2].spectra)
+        ix = faiss.IndexIVFPQ(faiss.IndexFlatIP(vec.shape[1]), vec.shape[1], args.nlist, 32, 8)
+        ix.by_residual = by_res
+        ix.seed = 1234
+        ix.set_niter(args.niter)
+        _, t_train = clock(lambda: ix.train(vec))
+        _, t_add = clock(lambda: ix.add(vec))
+        return sl, ix, t_train, t_add
+
+    def add_in_rounds(by_res, n=262144, d=800, m=8, nlist=256):
+        """seconds of add() at (800, 8, 8): random unit vectors and quantisers, no training"""
+        g = torch.Generator(device=dev).manual_seed(5)
+        unit = lambda *shape: torch.nn.functional.normalize(torch.randn(*shape, generator=g, device=dev), dim=-1)
+        ix = faiss.IndexIVFPQ(faiss.IndexFlatIP(d), d, nlist, m, 8)
+        ix.by_residual = by_res
+        ix.set_trained(unit(nlist, d).cpu().numpy(), unit(m, 256, d // m).cpu().numpy())
+        x = unit(n, d).contiguous()
+        ix.add(x[:4096])                  # warm-up: the code object is loaded
+        return clock(lambda: ix.add(x))[1]
+
+    if args.codec_only:
+        fig = {}
+        for mname, by_res in MODES:
+            sl, ix, t_train, t_add = build(by_res)
+            del ix
+            sl.shutdown()
+            fig[mname] = {'train_seconds': round(t_train, 4), 'add_seconds': round(t_add, 4),
+                          'add_800_8_8_seconds': round(add_in_rounds(by_res), 4)}
+        print(json.dumps({'library_size': lib.n, 'nlist': args.nlist, 'kmeans_niter': args.niter, 'lib': _lib.LIB_PATH,
+                          'modes': fig}), flush=True)
+        return
     nq = args.queries
     qsets, source = {}, {}
     for name, hard in (('default', 0.0), ('hard', synthetic.HARD_DEFAULT)):
@@ -76,10 +119,6 @@ def main():
         qsets[name], source[name] = q.to(dev).contiguous(), truth['source_row'][:nq].to(dev).to(torch.int64)
     batches = [synthetic.make_queries(lib, aux, args.batch, seed=42 + i, open_range=args.open_da, charge=2)[0]
                .to(dev).contiguous() for i in range(2)]
-    common = dict(precursor_tolerance_mass_open=args.open_da, precursor_tolerance_mode_open='Da',
-                  batch_size=args.batch, seed=1234)
-    ann = dict(mode='ann', index='ivfpq', pq_m=32, num_list=args.nlist, num_probe=args.nprobe,
-               num_candidates=args.k, kmeans_niter=args.niter, **common)
     out = {'library_size': lib.n, 'nlist': args.nlist, 'nprobe': args.nprobe, 'k': args.k, 'pq': 'm32 x 8 bits',
            'kmeans_niter': args.niter, 'open_window_da': args.open_da, 'queries': nq, 'batch': args.batch,
            'steps': args.steps, 'warmup': args.warmup, 'hard_level': synthetic.HARD_DEFAULT,
@@ -93,20 +132,13 @@ def main():
     bf.shutdown()
     print('[bf] done', flush=True)
 
-    # the indexes: trained and filled here under the clock, the engine builds the same ones again (same seed)
+    # the engine builds the same indexes again (same seed)
     sls = {}
     for mname, by_res in MODES:
-        sl = SpectralLibrary(lib, config=Config.open_search(pq_by_residual=by_res, **ann), device=dev)
-        vec = sl._encode(sl.partitions[2].spectra)
-        ix = faiss.IndexIVFPQ(faiss.IndexFlatIP(vec.shape[1]), vec.shape[1], args.nlist, 32, 8)
-        ix.by_residual = by_res
-        ix.seed = 1234
-        ix.set_niter(args.niter)
-        _, t_train = clock(lambda: ix.train(vec))
-        _, t_add = clock(lambda: ix.add(vec))
+        sl, ix, t_train, t_add = build(by_res)
         own = sl._get_ann_index(2)
         assert own.by_residual == by_res and np.array_equal(own.codebooks(), ix.codebooks())
-        del ix, vec
+        del ix
         sls[mname] = sl
         out['modes'][mname] = {'train_seconds': round(t_train, 3), 'add_seconds': round(t_add, 3)}
         print(f'[build] {mname}: train {t_train:.2f} s, add {t_add:.2f} s', flush=True)

@@ -3,8 +3,8 @@
 table and the ADC scan -- pq_m 4 .. 64, 1 .. 8 bits, sub-vectors on both sides of the register
 path of the L2 kernels (dsub <= 32) and codebooks beyond one 64 KB round of LDS. Only pq_m = 32
 with 8 bits and d <= 1020 takes the tiled scan (the last and the first d on either side of that are
-tested); every other shape runs pq_scan_kernel<M> / adc_score<M>, the slow branches of
-l2_assign_kernel / pq_encode_kernel, or both. Everything is compared bit for
+tested); every other shape runs pq_scan_kernel<M> / adc_score<M>, the wide path of l2_argmin (the one
+body of l2_assign_kernel / pq_encode_kernel: in one piece or in rounds), or both. Everything is compared bit for
 bit: score and centroid bits as uint32, ids / codes / offsets as integers, no tolerance, ties
 included (duplicated library vectors and all-zero queries force equal scores; the oracle and the
 kernels both put the lowest id first)."""
@@ -21,13 +21,13 @@ NLIST = 16
 # divide the default hash length 800 (asl_index_create refuses it, see the refusals): its shapes run
 # at the next multiple of 64, vectors hashed to 832 components.
 SHAPES = [
-    (800, 4, 8), (800, 8, 8), (800, 16, 8),   # slow training / encoding paths: dsub 200, 100, 50 (204 800 / 102 400 B codebooks)
+    (800, 4, 8), (800, 8, 8), (800, 16, 8),   # wide training / encoding paths: dsub 200, 100 in rounds (204 800 / 102 400 B codebooks), 50 in one piece
     (832, 64, 8),                             # M = 64 scan (two terms per partial), the largest look-up table
     (800, 16, 4),                             # PQ training subsample: n > 16 * 256
     (800, 8, 6), (800, 32, 5),                # ksub < 256, also at the tiled kernel's own m
     (832, 64, 1), (800, 4, 2),                # extreme small shapes: rows of mostly tied scores
     (128, 4, 8),                              # dsub = 32: last register-path width
-    (132, 4, 8),                              # dsub = 33: first slow-path width
+    (132, 4, 8),                              # dsub = 33: first wide-path width
     (64, 16, 8),                              # dsub = 4
 ]
 SUBSAMPLED = [(800, 16, 4), (832, 64, 1), (800, 4, 2)]
@@ -146,6 +146,33 @@ def test_encode_and_lists_bit_exact(world, shape):
     assert np.array_equal(ids, ivf.ids)
     assert np.array_equal(codes, ivf.payload)
     assert int(codes.max()) < (1 << shape[2])
+
+
+@pytest.mark.parametrize('by_residual', [True, False], ids=['by_residual', 'raw'])
+@pytest.mark.parametrize('shape', [(128, 4, 8), (132, 4, 8), (800, 8, 8)], ids=ids_of)
+def test_encode_blocks_of_one_live_lane_and_exactly_full(O, world, shape, by_residual):
+    """Register path, one-piece wide path and rounds: the lanes of a block past the last vector stay with the
+    block through the staging barriers and write nothing. add() of 1 vector (one live lane), of 256 (a block
+    that is exactly full) and of 1 again: after each, the lists equal the oracle's over the same prefix."""
+    import raw_pq_ref as R
+    w = world(shape)
+    xb, cen, cb, a = w['xb'][:258], w['cen'], w['cb'], w['assign']
+    want = w['codes'] if by_residual else R.raw_codes(O, xb, cb)
+    idx = _new_index(shape)
+    if not by_residual:
+        idx.by_residual = False
+    idx.set_trained(cen, cb)
+    n = 0
+    for step in (1, 256, 1):
+        idx.add(xb[n:n + step])
+        n += step
+        ivf = O.HostIVF(cen, a[:n], want[:n], cb)
+        off, ids, codes = idx.lists()
+        assert idx.ntotal == n
+        assert np.array_equal(off, ivf.list_offsets), n
+        assert np.array_equal(ids, ivf.ids), n
+        assert np.array_equal(codes, ivf.payload), n
+    assert n == 258
 
 
 @pytest.mark.parametrize('shape', [(800, 8, 8), (132, 4, 8), (128, 4, 8)], ids=ids_of)
