@@ -202,25 +202,42 @@ struct HistTopK {
   __device__ __forceinline__ bool free_append(bool p, float score, uint32_t slot, bool counted = false) {
     const unsigned long long m = __ballot(p);
     const int c = __popcll(m);
-    int base = 0;
-    if (lane == 0) base = atomicAdd(&ctl[C_FILL], c);
-    base = __builtin_amdgcn_readfirstlane(base);
+    const int base = reserve_add(c);
     if (base + c > CAP) return false;
     if (p) {
       const int b = score_bucket(score);
-      keys[base + __popcll(m & ((1ull << lane) - 1ull))] = ((u64)f2ord(score) << 32) | (u64)slot;
+      keys[base + rank_in(m)] = ((u64)f2ord(score) << 32) | (u64)slot;
       if (!sort_mode && !counted) atomicAdd(&hist[b], 1);
     }
     return true;
+  }
+  // The reservation's add as the source has it: ONE lane, one ds_add_rtn_u32, one v_readfirstlane; returns the
+  // (wave-uniform) fill level before the add. The compiler's atomic optimizer turns an atomic on a wave-uniform
+  // address into a wave aggregation -- v_mbcnt over exec, a second saveexec, s_bcnt1 and s_mul in front of the
+  // add, v_mul_lo and v_add behind it -- even inside a branch that one lane takes; it leaves an atomic whose
+  // address is a lane's value alone, so the address is handed over as one: a vector register it needs anyway.
+  // (Per unit there is no switch for this that offer()'s many-lane add on the same word could live with.)
+  __device__ __forceinline__ int reserve_add(int c) {
+    // (the other lanes' value is never read -- lane 0 is the first lane of a wave that is whole here -- so it is
+    // the address register itself: no register to clear per reservation)
+    typedef __attribute__((address_space(3))) int lds_int;
+    uint32_t a = (uint32_t)(uintptr_t)(lds_int *)(ctl + C_FILL);
+    asm volatile("" : "+v"(a));
+    int base = (int)a;
+    if (lane == 0)
+      base = __hip_atomic_fetch_add((lds_int *)(uintptr_t)a, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return __builtin_amdgcn_readfirstlane(base);
+  }
+  // the lane's place among the lanes of the (wave-uniform) mask m: the set bits below the lane, v_mbcnt_lo / _hi
+  __device__ __forceinline__ static int rank_in(unsigned long long m) {
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
   }
   // The same in two steps, for a wave that offers several rows at once: one reservation of c
   // slots (c <= 64, wave-uniform; -1: the buffer cannot take them -- nothing was written, go
   // through free_append and the sync it asks for), then the rows' candidates one after the
   // other into base, base + popcount(row 0), ...
   __device__ __forceinline__ int free_reserve(int c) {
-    int base = 0;
-    if (lane == 0) base = atomicAdd(&ctl[C_FILL], c);
-    base = __builtin_amdgcn_readfirstlane(base);
+    const int base = reserve_add(c);
     return base + c > CAP ? -1 : base;
   }
   // count = false: LAZY COUNTS -- the key is not entered into the histogram here; free_sync(true)
@@ -230,7 +247,11 @@ struct HistTopK {
   __device__ __forceinline__ void free_write(bool p, unsigned long long m, float score, uint32_t slot,
                                              int base, bool count = true) {
     if (p) {
-      keys[base + __popcll(m & ((1ull << lane) - 1ull))] = ((u64)f2ord(score) << 32) | (u64)slot;
+      // (f2ord without the select: the sign, spread over the word, or'ed with the sign bit, flips exactly the
+      // bits f2ord flips -- all of a negative score, the sign bit of any other)
+      const uint32_t u = __float_as_uint(score);
+      const uint32_t ob = u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
+      keys[base + rank_in(m)] = ((u64)ob << 32) | (u64)slot;
       if (count && !sort_mode) atomicAdd(&hist[score_bucket(score)], 1);
     }
   }

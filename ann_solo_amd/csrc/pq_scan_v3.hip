@@ -78,6 +78,24 @@ __device__ __forceinline__ void v3_pad() {
 }
 #undef V3_PAD16
 #undef V3_PAD4
+// V3_PAD_LDSRT = N (profiles/pq_passer_path_price.txt): N LDS round trips more per hot-loop step, one after the
+// other, behind the ADC -- a control word of the workgroup read, waited for and consumed by a v_readfirstlane, the
+// next read's address held back until then. What a step's time gains per round trip is what the append's wait for
+// its reservation costs, and what answering it a tile later could save. 0: nothing.
+constexpr int V3_PAD_LDSRT = 0;
+template <int N_>
+__device__ __forceinline__ void v3_pad_ldsrt(const int *word) {
+  if constexpr (N_ > 0) {
+    typedef __attribute__((address_space(3))) int lds_int;
+    uint32_t a = (uint32_t)(uintptr_t)(const lds_int *)word;
+#pragma unroll
+    for (int n = 0; n < N_; ++n) {
+      const int r = __builtin_amdgcn_readfirstlane(
+          __hip_atomic_load((const lds_int *)(uintptr_t)a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+      asm volatile("" : "+v"(a) : "s"(r));
+    }
+  }
+}
 constexpr int V3_WAVES_PER_SIMD = 6;   // occupancy the 2048-key instantiation is compiled for (3 workgroups per CU)
 
 template <int NT_>
@@ -381,16 +399,20 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     // test is the ordered key's and m is made again; the ordered key of the lanes that pass is made in
     // free_write. The reservation's verdict is settled before the lanes part to write their keys:
     // `pending` stays a scalar, and with it every branch of the wave's loop.
-    auto append = [&](unsigned long long m, bool thresholded = false) {
-      if (!thresholded && thr_hi_u != 0) {
+    // The reservation (hist_topk.hpp: one lane's add on C_FILL, refused when it ends beyond CAP) is spelled out
+    // here: the verdict is an add, a compare and the branch, with no -1 to encode and decode in between.
+    // hot: the hot loop's call -- thresholded, and m != 0 is known from its one test.
+    auto append = [&](unsigned long long m, bool hot = false) {
+      if (!hot && thr_hi_u != 0) {
         float sc = p_score;
         asm volatile("; exact flushes" : "+v"(sc));
         m = __ballot(f2ord(sc) >= thr_hi_u) & in_mask();
       }
       pending = false;
-      if (m) {
-        const int base = top.free_reserve(__builtin_amdgcn_readfirstlane(__popcll(m)));   // wave-uniform; -1: the buffer is full
-        pending = base < 0;
+      if (hot || m) {
+        const int c = __builtin_amdgcn_readfirstlane(__popcll(m));   // wave-uniform
+        const int base = top.reserve_add(c);
+        pending = base + c > CAP;                                    // the buffer cannot take them: nothing is written
         if (!pending) top.free_write(__builtin_amdgcn_inverse_ballot_w64(m), m, p_score, (p_tile_nv << 6) + (uint32_t)lane, base, false);
       }
     };
@@ -442,6 +464,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
           if (i >= nent) return -1;
           step(s);
           v3_pad<V3_PAD_SALU, V3_PAD_VALU>();
+          v3_pad_ldsrt<V3_PAD_LDSRT>(s_done);
           const unsigned long long m = passers();
           if (__builtin_expect(((uint32_t)m | (uint32_t)(m >> 32) | (uint32_t)flag_u | thr_hi_u) != 0u, 0)) {
             if (((uint32_t)flag_u | thr_hi_u) != 0u) return s;
