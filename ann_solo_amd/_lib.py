@@ -89,6 +89,7 @@ EXPORTS = [
     'asl_library_set_selection', 'asl_index_set_selector', 'asl_index_search_selected',
     'asl_rescore_batch_topn_hist', 'asl_search_batch_topn_hist', 'asl_rescore_knn_topn_hist',
     'asl_decoy_batch',
+    'asl_localize_batch',
 ]
 
 
@@ -292,6 +293,9 @@ def lib():
         if hasattr(L, 'asl_decoy_batch'):
             L.asl_decoy_batch.argtypes = [C.POINTER(AslPeaks)] + [C.c_void_p] * 6 + [C.c_double, C.c_int32] + \
                 [C.c_void_p] * 8
+        if hasattr(L, 'asl_localize_batch'):
+            L.asl_localize_batch.argtypes = [C.POINTER(AslPeaks)] + [C.c_void_p] * 6 + [C.c_double, C.c_int32] + \
+                [C.c_void_p] * 9
         if hasattr(L, 'asl_index_set_by_residual'):
             L.asl_index_set_by_residual.argtypes = [C.c_void_p, C.c_int32]
             L.asl_index_get_by_residual.argtypes = [C.c_void_p]

@@ -5,7 +5,7 @@
 (``index``, ``pq_m``, ``pq_bits``, ``refine_k``, ``kmeans_niter``, ``ann_seed``, ``num_gpus``,
 ``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``, ``pq_by_residual``,
 ``precursor_window_open``, ``fragment_tolerance_unit``, ``score_stats``, ``device_decoys``,
-``decoy_tolerance_unit``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``decoy_tolerance_unit``, ``localize_modifications``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -116,6 +116,12 @@ class Config:
     # 'ppm' (of the theoretical fragment m/z) | 'Da'. The default is the default of the reference's
     # ``fragment_tol_mode``, which reaches its decoy annotation only; this is the one place it is read
     decoy_tolerance_unit: str = 'ppm'
+    # after the search, say for every open-level identification with a real precursor mass difference which
+    # residue of the library peptide the query's peaks put that mass on (localize.py; DESIGN.md 3
+    # "Localisation"): the SSMs' mod_* columns. The tolerance is fragment_mz_tolerance in
+    # fragment_tolerance_unit, ppm being of the THEORETICAL fragment m/z here. A post-step: identifications,
+    # scores, FDR, files and every hash are what they are without it
+    localize_modifications: bool = False
 
     MAX_PEAKS = 256     # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
@@ -171,6 +177,9 @@ class Config:
         self.device_decoys = bool(self.device_decoys)
         if self.decoy_tolerance_unit not in ('Da', 'ppm'):
             raise ValueError(f"decoy_tolerance_unit = {self.decoy_tolerance_unit!r}: 'Da' or 'ppm'")
+        self.localize_modifications = bool(self.localize_modifications)
+        if self.localize_modifications and self.num_gpus and int(self.num_gpus) > 1:
+            raise ValueError('localize_modifications does not run on a sharded index (num_gpus > 1)')
         if self.precursor_window_open is not None:
             try:
                 lo, hi = (float(v) for v in self.precursor_window_open)
@@ -324,3 +333,10 @@ def add_arguments(parser) -> None:
                         choices=['ppm', 'Da'],
                         help="with --device_decoys: unit of --fragment_mz_tolerance in the fragment annotation "
                              "(the reference's --fragment_tol_mode) (default: %(default)s)")
+    parser.add_argument('--localize_modifications', action='store_true', default=d.localize_modifications,
+                        help='after the search, localise the precursor mass difference of every open-search '
+                             'identification on its library peptide from the query spectrum (plain and shifted '
+                             'b / y fragments within --fragment_mz_tolerance; ppm is of the theoretical m/z): '
+                             'the SSMs gain mod_mass, mod_site_lo / _hi (0-based residues), mod_site_score, '
+                             '_margin and _gain; identifications, scores and files do not change; one GPU '
+                             '(default: off)')

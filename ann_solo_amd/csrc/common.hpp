@@ -322,6 +322,14 @@ struct PeaksStage {  // stages an asl_peaks_t whose arrays may be on the host
 };
 bool peaks_on_device(const asl_peaks_t *p);
 
+// Orders a wave's own LDS traffic (waves that share nothing with the rest of their workgroup need no
+// workgroup barrier).
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // Inclusive prefix sum over the 64 lanes of a wave in seven DPP adds (row_shr 1 / 2 / 3, row_shr 4
 // and 8 under bank masks, row_bcast 15 and 31 under row masks) -- no LDS crossbar round trips:
 // the ds_bpermute chain this replaces (six dependent __shfl_up) was ~0.3 us of latency per scan,

@@ -11,16 +11,11 @@
 // fragment that can still match is found by bisection, the winner over all series is the match of lowest
 // theoretical m/z. The repositioned peaks are ordered by a bitonic sort of (fp64 m/z, raw index) in LDS,
 // sized to the largest spectrum of the batch (256 / 1024 / 4096).
-#include <cmath>
-#include <vector>
-
-#include "common.hpp"
+#include "fragments.hpp"
 
 namespace asl {
 
-constexpr int DC_NT = 256, DC_MAXN = 4096, DC_MAXL = 128, DC_MAXZ = 8, DC_NLOSS = 14;
-constexpr int DC_LAD = DC_MAXL + 1;
-constexpr double DC_PROTON = 1.007276466, DC_CO = 27.994915, DC_H2O = 18.010565;
+constexpr int DC_NT = 256, DC_NLOSS = 14;
 
 __constant__ double dc_loss[DC_NLOSS] = {0.0,        -1.007825,  -17.026549, -18.010565, -27.994915,
                                          -43.989829, -45.021464, -46.005479, -63.998301, -79.956818,
@@ -47,9 +42,6 @@ __device__ __forceinline__ double frag_base(const double *P, const double *S, in
   if (type == 3) return (P[L] + cterm) + DC_H2O;
   return S[n] + DC_H2O;
 }
-__device__ __forceinline__ double frag_theo(double base, double loss, int z) {
-  return (base + loss) / (double)z + DC_PROTON;     // add, divide, add
-}
 
 struct Ann {
   double theo;
@@ -64,19 +56,6 @@ __device__ __forceinline__ void offer(Ann &b, double theo, int type, int n, int 
     else better = loss < b.loss;
   }
   if (better) b = Ann{theo, type, n, z, loss};
-}
-
-// fp64 -> u64 whose unsigned order is the numeric order (-0 and +0 share a key, NaN last)
-__device__ __forceinline__ uint64_t d2ord(double v) {
-  if (v != v) return 0xFFFFFFFFFFFFFFFEull;
-  if (v == 0.0) return 0x8000000000000000ull;
-  const uint64_t b = (uint64_t)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ord2d(uint64_t k) {
-  if (k == 0xFFFFFFFFFFFFFFFEull) return __longlong_as_double(0x7FF8000000000000ll);
-  const uint64_t b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-  return __longlong_as_double((long long)b);
 }
 
 __global__ __launch_bounds__(DC_NT) void decoy_kernel(DevPeaks raw, DecoyArgs A, int nsort_max) {
@@ -98,20 +77,10 @@ __global__ __launch_bounds__(DC_NT) void decoy_kernel(DevPeaks raw, DecoyArgs A,
   const float *mz = raw.mz + o, *inten = raw.intensity + o;
   // 1. ladders: P[0] = nterm, P[k] = P[k-1] + m[k-1]; S[0] = cterm, S[k] = S[k-1] + m[L-k]
   if (tid < 4) {
-    double *out = lad + tid * DC_LAD;
-    const bool dec = tid >= 2, suf = tid & 1;
-    double acc = suf ? cterm : nterm;
+    const bool dec = tid >= 2;
     // the bisection below needs ladders that rise by clear steps inside a moderate range (see there)
-    bool steady = fabs(acc) <= 1e6;
-    out[0] = acc;
-    for (int k = 1; k <= L; ++k) {
-      const int pos = suf ? L - k : k - 1;
-      const double m = A.mass[q0 + (dec ? A.perm[q0 + pos] : pos)];
-      acc = acc + m;
-      out[k] = acc;
-      steady = steady && m >= 1e-3;
-    }
-    ctl[tid] = steady && fabs(acc) <= 1e6;
+    ctl[tid] = build_ladder(lad + tid * DC_LAD, (tid & 1) ? cterm : nterm, L, tid & 1,
+                            [&](int pos) { return A.mass[q0 + (dec ? A.perm[q0 + pos] : pos)]; });
   }
   __syncthreads();
   const double *P = lad, *S = lad + DC_LAD, *Pd = lad + 2 * DC_LAD, *Sd = lad + 3 * DC_LAD;
@@ -209,13 +178,6 @@ __global__ __launch_bounds__(DC_NT) void decoy_kernel(DevPeaks raw, DecoyArgs A,
   }
 }
 
-template <class T>
-static int to_host(std::vector<T> &h, const T *src, size_t n) {
-  h.resize(n);
-  if (n) HIP_TRY(hipMemcpyAsync(h.data(), src, n * sizeof(T), hipMemcpyDefault, stream()));
-  return ASL_OK;
-}
-
 }  // namespace asl
 
 using namespace asl;
@@ -246,25 +208,8 @@ extern "C" int asl_decoy_batch(const asl_peaks_t *raw, const int32_t *seq_offset
   ASL_TRY(to_host(h_nt, nterm, (size_t)n));
   ASL_TRY(to_host(h_ct, cterm, (size_t)n));
   ASL_TRY(sync_stream());
-  if (h_off[0] < 0 || h_seq[0] < 0) return fail(ASL_ERR_INVALID, "decoy_batch: negative offsets");
   int max_n = 0;
-  for (int s = 0; s < n; ++s) {
-    const int c = h_off[s + 1] - h_off[s], L = h_seq[s + 1] - h_seq[s];
-    if (c < 0) return fail(ASL_ERR_INVALID, "decoy_batch: peak offsets descend at spectrum %d", s);
-    if (c > DC_MAXN)
-      return fail(ASL_ERR_CAPACITY, "decoy_batch: spectrum %d has more than %d peaks", s, DC_MAXN);
-    if (L < 2) return fail(ASL_ERR_INVALID, "decoy_batch: spectrum %d: a peptide needs 2 residues or more", s);
-    if (L > DC_MAXL)
-      return fail(ASL_ERR_CAPACITY, "decoy_batch: spectrum %d: more than %d residues", s, DC_MAXL);
-    if (h_z[s] < 1) return fail(ASL_ERR_INVALID, "decoy_batch: spectrum %d: max_fragment_charge < 1", s);
-    if (h_z[s] > DC_MAXZ)
-      return fail(ASL_ERR_CAPACITY, "decoy_batch: spectrum %d: max_fragment_charge above %d", s, DC_MAXZ);
-    if (!std::isfinite(h_nt[s]) || !std::isfinite(h_ct[s]))
-      return fail(ASL_ERR_INVALID, "decoy_batch: spectrum %d: non-finite terminal mass", s);
-    max_n = c > max_n ? c : max_n;
-  }
-  if (raw->n_peaks > 0 && (int64_t)h_off[n] > raw->n_peaks)
-    return fail(ASL_ERR_INVALID, "decoy_batch: offsets run past n_peaks");
+  ASL_TRY(check_fragment_batch("decoy_batch", n, raw->n_peaks, h_off, h_seq, h_z, h_nt, h_ct, &max_n));
   const size_t R = (size_t)h_seq[n];
   ASL_TRY(to_host(h_mass, residue_mass, R));
   ASL_TRY(to_host(h_perm, perm, R));

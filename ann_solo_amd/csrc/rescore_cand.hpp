@@ -7,12 +7,6 @@ namespace asl {
 
 enum { RS_STATUS_OK = 0, RS_STATUS_PEAKS = 1, RS_STATUS_MATCHES = 2, RS_STATUS_WINDOW = 4 };
 
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Candidate addressing: CSR (cand_offsets != null) or fixed stride; the CSR form either lists
 // row ids (rows64 / rows32) or, for the window-only modes, is a run of the precursor-sorted view
 // per query (win_begin: rescore.hpp, WindowRows).

@@ -863,7 +863,72 @@ class SpectralLibrary:
                                   score_ssms, uid)
         n_identified += int((t2.q < cfg.fdr).sum())
         logging.info('%d spectra identified after the open search', n_identified)   # :257
-        return SSMTable.concat([t1, t2])
+        out = SSMTable.concat([t1, t2])
+        if cfg.localize_modifications:      # a post-step on the identifications; off: nothing is launched
+            self.localize_modifications(out, query_spectra)
+        return out
+
+    def localize_modifications(self, table: 'SSMTable', query_spectra: Dict[int, PackedSpectra]) -> 'SSMTable':
+        """Fill the ``mod_*`` columns of ``table`` (in place; also returned): for every SSM of the open
+        cascade level whose precursor mass difference ``table.mass_diffs()`` passes the shift gate of the
+        rescoring (``|delta| >= fragment_mz_tolerance``, in ppm ``>= fragment_mz_tolerance * 1e-6 *`` the
+        query's precursor m/z) and whose library row has a ``peptide`` of 2 .. 128 residues, the site of
+        that mass on the peptide as the processed query spectrum ``query_spectra[charge][qrow]`` shows it
+        (localize.py, 32 768 SSMs per kernel launch). The tolerance is ``fragment_mz_tolerance`` in
+        ``fragment_tolerance_unit``; ppm here is of the THEORETICAL fragment m/z, as for the decoys, not of
+        the query peak as in the dot product. A peptide that does not parse (an unknown modification name,
+        say) is skipped: one warning per call names their number and the first. Every other SSM keeps the
+        defaults (NaN, -1). One GPU: ``ValueError`` on a sharded library."""
+        from . import localize as lz
+        from .decoy_generator import parse_peptide
+        d = getattr(self, '_dist', None)
+        if d is not None and d.world > 1:
+            raise ValueError('localize_modifications does not run on a sharded index')
+        cfg = self.config
+        if len(table) == 0:
+            return table
+        delta = table.mass_diffs()
+        gate = float(cfg.fragment_mz_tolerance)
+        if cfg.fragment_tolerance_unit == 'ppm':    # rescore.hip, rs_frag_tol at the shift gate
+            gate = gate * 1e-6 * table._column(table.query_meta, table.qrow, 'precursor_mz', np.float64)
+        wanted = np.nonzero(table.open_level & (np.abs(delta) >= gate))[0]
+        parsed: Dict[str, object] = {}
+        n_bad, first_bad = 0, None
+        for z in np.unique(table.charge[wanted]):
+            lm = table.library_meta[int(z)]
+            rows, peps = [], []
+            for i in wanted[table.charge[wanted] == z]:
+                rec = lm[int(table.lib_row[i])]
+                text = rec.get('peptide') if hasattr(rec, 'get') else rec['peptide']
+                if text not in parsed:
+                    try:
+                        parsed[text] = parse_peptide(text, spectrum=rec['identifier'])
+                    except ValueError as e:
+                        parsed[text] = None
+                        first_bad = first_bad or str(e)
+                pep = parsed[text]
+                if pep is None:
+                    n_bad += 1
+                elif 2 <= len(pep.sequence) <= lz.MAX_RESIDUES:
+                    rows.append(int(i))
+                    peps.append(pep)
+            qs = query_spectra[int(z)]
+            for b0 in range(0, len(rows), lz.BATCH):
+                sel = np.asarray(rows[b0:b0 + lz.BATCH], np.int64)
+                q = qs.select(torch.as_tensor(table.qrow[sel]))
+                out = lz.localize_batch(q, *lz.peptide_arrays(peps[b0:b0 + lz.BATCH], [int(z)] * len(sel)),
+                                        delta[sel], cfg.fragment_mz_tolerance, cfg.fragment_tolerance_unit,
+                                        self.device)
+                out = {k: _to_np(out[k]) for k in lz.SSM_KEYS}
+                table.mod_mass[sel] = delta[sel]
+                table.mod_site_lo[sel], table.mod_site_hi[sel] = out['best_lo'], out['best_hi']
+                table.mod_site_score[sel] = out['best_score']
+                table.mod_site_margin[sel] = out['best_score'] - out['runner_score']
+                table.mod_site_gain[sel] = out['best_score'] - out['none_score']
+        if n_bad:
+            logging.warning('modification localisation skipped %d SSMs whose library peptide does not parse; '
+                            'the first: %s', n_bad, first_bad)
+        return table
 
     def _open_level_windows(self, qs: PackedSpectra, query_meta, charge: int) -> Optional[np.ndarray]:
         """The open level's per-query intervals for one charge set ([qs.n, 2] float64), or None for the
@@ -951,6 +1016,7 @@ class SpectralLibrary:
                    for charge, sel, q, res in pending]
         for (charge, sel, q, res), cos in zip(pending, cosines):
             table.add_batch(charge, sel, _to_np(res.best_row), _to_np(cos), res)
+        table.open_level[:] = mode == 'open'
         if uid is not None:
             table = table.first_per_uid(uid)
         acc = getattr(self, 'level_seconds', None)
@@ -1053,7 +1119,20 @@ class SSMTable:
     ``expect[len]``, how many of them were expected to score at least as high as the match by chance
     (``score_stats.expect_value`` over the batch's score histograms; NaN where no tail could be fitted:
     fewer than 10 losers, fewer than 3 fit points, a slope that is not negative). Without the option
-    the columns hold 0 and NaN."""
+    the columns hold 0 and NaN.
+
+    ``open_level[len]`` says which matches come from the open cascade level. With ``localize_modifications``
+    (``SpectralLibrary.localize_modifications``) those with a real precursor mass difference carry where the
+    query's peaks put it on the library peptide: ``mod_mass`` (the mass, Da), ``mod_site_lo`` /
+    ``mod_site_hi`` (first and last of the equally best sites, 0-based residue indices),
+    ``mod_site_score`` (the summed intensity of the best site's plain and shifted b / y fragments),
+    ``mod_site_margin`` (best minus the best different score; 0 when every site ties) and ``mod_site_gain``
+    (best minus the score without the mass). Everywhere else: NaN and -1."""
+
+    # columns that are filled after the batches are filed: (name, dtype, default)
+    _LATE = (('open_level', bool, False), ('mod_mass', np.float64, np.nan), ('mod_site_lo', np.int32, -1),
+             ('mod_site_hi', np.int32, -1), ('mod_site_score', np.float64, np.nan),
+             ('mod_site_margin', np.float64, np.nan), ('mod_site_gain', np.float64, np.nan))
 
     def __init__(self, query_meta, library_meta, n_alt: int = 0):
         self.query_meta, self.library_meta = query_meta, library_meta
@@ -1073,6 +1152,8 @@ class SSMTable:
         self.pos = np.zeros(0, np.int32)         # row inside that batch
         self._batches: list = []
         self._pending: list = []
+        for name, dt, _ in self._LATE:
+            setattr(self, name, np.zeros(0, dt))
 
     def add_batch(self, charge, qrows, best_row, score, res) -> None:
         hit = np.nonzero(best_row >= 0)[0]       # queries without a candidate: no SSM (:359)
@@ -1113,6 +1194,9 @@ class SSMTable:
         self.lib_row, self.score = cat(self.lib_row, cols[2]), cat(self.score, cols[3])
         self.batch, self.pos = cat(self.batch, cols[4]), cat(self.pos, cols[5])
         self.q = np.concatenate([self.q, np.full(len(self.charge) - len(self.q), np.nan)])
+        for name, dt, default in self._LATE:
+            old = getattr(self, name)
+            setattr(self, name, np.concatenate([old, np.full(len(self.charge) - len(old), default, dt)]))
 
     def __len__(self):
         return len(self.charge)
@@ -1124,7 +1208,7 @@ class SSMTable:
         out = SSMTable(self.query_meta, self.library_meta, self.n_alt)
         out._batches, out._alt_batches = self._batches, self._alt_batches
         for name in ('charge', 'qrow', 'lib_row', 'score', 'q', 'batch', 'pos', 'alt_lib_row', 'alt_score',
-                     'delta_score', 'n_scored', 'expect'):
+                     'delta_score', 'n_scored', 'expect') + tuple(c[0] for c in self._LATE):
             setattr(out, name, getattr(self, name)[idx])
         return out
 
@@ -1138,7 +1222,8 @@ class SSMTable:
             pad = ((0, 0), (0, out.n_alt - t.n_alt))
             out.alt_lib_row = np.concatenate([out.alt_lib_row, np.pad(t.alt_lib_row, pad, constant_values=-1)])
             out.alt_score = np.concatenate([out.alt_score, np.pad(t.alt_score, pad)])
-            for name in ('charge', 'qrow', 'lib_row', 'score', 'q', 'pos', 'delta_score', 'n_scored', 'expect'):
+            for name in ('charge', 'qrow', 'lib_row', 'score', 'q', 'pos', 'delta_score', 'n_scored',
+                         'expect') + tuple(c[0] for c in SSMTable._LATE):
                 setattr(out, name, np.concatenate([getattr(out, name), getattr(t, name)]))
             out.batch = np.concatenate([out.batch, t.batch + shift])
             shift += len(t._batches)
@@ -1233,7 +1318,9 @@ class SSMTable:
             qm.get('retention_time'), qm['precursor_charge'], qm['precursor_mz'],
             lm['precursor_mz'], lm.get('is_decoy', False), float(self.score[i]), float(self.q[i]),
             self._peak_matches(i), float(self.delta_score[i]), self._alternatives(i),
-            int(self.n_scored[i]), float(self.expect[i]))
+            int(self.n_scored[i]), float(self.expect[i]), float(self.mod_mass[i]), int(self.mod_site_lo[i]),
+            int(self.mod_site_hi[i]), float(self.mod_site_score[i]), float(self.mod_site_margin[i]),
+            float(self.mod_site_gain[i]))
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))

@@ -149,6 +149,16 @@ class SpectrumSpectrumMatch:
     # without the option
     n_scored: int = 0
     expect: float = float('nan')
+    # localize_modifications: the precursor mass difference of an open-search match and where the query's
+    # peaks put it on the peptide -- first / last of the equally best sites (0-based residues), the best
+    # site's score, its margin over the next different score and its gain over the unmodified peptide; NaN
+    # and -1 where the SSM was not localised
+    mod_mass: float = float('nan')
+    mod_site_lo: int = -1
+    mod_site_hi: int = -1
+    mod_site_score: float = float('nan')
+    mod_site_margin: float = float('nan')
+    mod_site_gain: float = float('nan')
 
 
 def ssms_from_batch(result, query_meta, library_meta, scores=None, q_values=None

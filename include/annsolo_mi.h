@@ -648,6 +648,51 @@ int asl_decoy_batch(const asl_peaks_t *raw, const int32_t *seq_offsets /* [n + 1
                     int32_t *out_src, uint8_t *out_charge, uint8_t *ann_type, uint8_t *ann_n,
                     uint8_t *ann_z, uint8_t *ann_loss);
 
+/* ------------------------------------------------------------------ modification site localisation
+ * An open-modification match says "this query spectrum is library peptide P carrying an unknown mass
+ * delta"; this call says which residue of P the query's own peaks put that mass on, batched over SSMs.
+ * SSM s brings: its query spectrum (spectrum s of `queries`, peaks ascending in m/z, intensities used as
+ * given; precursor_mz / precursor_charge / charge are not read), the library peptide as L = seq_offsets[s+1]
+ * - seq_offsets[s] residue masses m[0..L) (the peptide's own modifications folded in) with nterm[s], cterm[s]
+ * and max_fragment_charge[s], the mass to place delta[s] (Da, neutral; 0 is legal) and one tolerance for the
+ * batch (ASL_TOL_DA, or ASL_TOL_PPM: of the THEORETICAL m/z, as for the decoys).
+ * The arithmetic, all in IEEE double without fused multiply-add, is the contract:
+ *  1. ladders, sequential, exactly asl_decoy_batch's step 1: P[0] = nterm, P[k] = P[k-1] + m[k-1];
+ *     S[0] = cterm, S[k] = S[k-1] + m[L-k].
+ *  2. fragments: k = 1..L-1, ion types b then y, variant v = 0 (plain) or 1 (carries the modification):
+ *     b base P[k], and P[k] + delta for v = 1; y base S[k] + 18.010565, and (S[k] + 18.010565) + delta for
+ *     v = 1. Charge z = 1..max_fragment_charge, theo = base / z + 1.007276466. No a ions, no precursor
+ *     ion, no neutral losses.
+ *  3. evidence: peak i, x = (double)mz[i], matches iff -R <= x - theo && x - theo <= R with R = tolerance
+ *     (Da) or (tolerance * 1e-6) * theo (ppm). A fragment at charge z contributes (double)intensity[i] of
+ *     its most intense matching peak (ties: the lowest i) and 1 to a hit count; nothing matching: 0.0 and
+ *     0. E[type][k][v] is the sum of the contributions over z = 1, 2, .. in that order from 0.0,
+ *     C[type][k][v] the hit count.
+ *  4. sites j = 0..L-1 (residue index, N-terminal residue first): b_k carries the modification iff
+ *     k >= j + 1, y_k iff k >= L - j. score[j] is the sequential double sum, from 0.0, over k = 1..L-1 of
+ *     E[b][k][v_b] then E[y][k][v_y]; count[j] the same sum over C. none_score / none_count: the same with
+ *     every v = 0.
+ *  5. summary: best_score is the largest score[j]; best_lo / best_hi the first and last site whose score
+ *     equals it by exact double equality (two sites that no present fragment tells apart add the same
+ *     addends in the same order, so they tie bit for bit), n_best their number, best_count =
+ *     count[best_lo]; runner_score the largest score strictly below best_score, or best_score itself when
+ *     every site ties.
+ * Outputs, each nullable, host or device memory: per site, in the peptides' own CSR layout (element
+ * seq_offsets[s] + j), site_score and site_count; per SSM best_lo, best_hi, n_best, best_count, best_score,
+ * runner_score, none_score. A spectrum without peaks is legal: every score 0, best_lo = 0, best_hi = L - 1.
+ * Limits, those of the decoys, all checked on host copies of the small arrays before anything is launched or
+ * written: more than 4096 peaks, L > 128 or max_fragment_charge > 8: ASL_ERR_CAPACITY; L < 2,
+ * max_fragment_charge < 1, a non-finite mass / terminus / delta, a negative or NaN tolerance, a unit other
+ * than the two: ASL_ERR_INVALID. Ascending m/z is a precondition for the result, not for safety: no step
+ * reads outside a spectrum's slice whatever the order of its peaks. Synchronous. */
+int asl_localize_batch(const asl_peaks_t *queries, const int32_t *seq_offsets /* [n + 1] */,
+                       const double *residue_mass, const double *nterm /* [n] */,
+                       const double *cterm /* [n] */, const int32_t *max_fragment_charge /* [n] */,
+                       const double *delta /* [n] */, double tolerance, int32_t tolerance_unit,
+                       double *site_score, int32_t *site_count, int32_t *best_lo, int32_t *best_hi,
+                       int32_t *n_best, int32_t *best_count, double *best_score, double *runner_score,
+                       double *none_score);
+
 /* ------------------------------------------------------------------ SSM features
  * Replaces the per-SSM SpectrumSimilarityCalculator calls of _compute_ssm_features
  *   /root/reference/src/ann_solo/utils.py:344-456
