@@ -10,61 +10,12 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "flat_postings.hpp"
 #include "hist_topk.hpp"
-#include "ivf_kernels.hpp"
 #include "pq_tile.hpp"
 
 namespace asl {
 
-// non-zeros per vector (one wave per vector) and their maximum: decides at build time whether
-// the postings layout pays
-// nnz_max[1] is raised when a non-zero component is NOT a fixed-point value (0 < x < 1 on the
-// grid of 2^-22): such an index keeps float postings
-__global__ void count_nnz_kernel(const float *__restrict__ vecs, int d, int64_t n,
-                                 int32_t *__restrict__ nnz, int32_t *__restrict__ nnz_max) {
-  const int64_t v = block_linear() * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (v >= n) return;
-  int c = 0;
-  bool off_grid = false;
-  for (int j = lane; j < d; j += 64) {
-    const float x = vecs[v * d + j];
-    c += x != 0.0f;
-    off_grid |= x != 0.0f && !fx22_on_grid(x);
-  }
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
-  if (__ballot(off_grid) && lane == 0) atomicMax(nnz_max + 1, 1);
-  if (lane == 0) {
-    nnz[v] = c;
-    atomicMax(nnz_max, c);
-  }
-}
-
-// add() of an IVF-Flat index in fixed-point storage mode: components in [0, 1) go to the nearest
-// multiple of 2^-22 (ties to even; the largest is 1 - 2^-22); anything else is stored as given
-// (and keeps the whole index on float postings). The oracle's orc_quantize_fx22 is the same rule.
-__global__ void quantize_fx22_kernel(float *__restrict__ x, int64_t n) {
-  const int64_t i = block_linear() * blockDim.x + threadIdx.x;
-  if (i < n) x[i] = fx22_round(x[i]);
-}
-
-int quantize_fx22(float *x, int64_t n) {
-  if (n <= 0) return ASL_OK;
-  hipLaunchKernelGGL(quantize_fx22_kernel, grid_2d(cdiv(n, 256)), dim3(256), 0, stream(), x, n);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-int count_nnz(const float *vecs, int d, int64_t n, int32_t *nnz, int32_t *nnz_max_dev) {
-  HIP_TRY(hipMemsetAsync(nnz_max_dev, 0, 2 * sizeof(int32_t), stream()));
-  if (n <= 0) return ASL_OK;
-  hipLaunchKernelGGL(count_nnz_kernel, grid_2d(cdiv(n, 4)), dim3(256), 0, stream(), vecs, d,
-                     n, nnz, nnz_max_dev);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-// ---------------------------------------------------------------------------------------
 // Dimension-major ("postings") IVF-Flat. Streaming EVERY stored non-zero of the probed lists
 // (~27 per vector; the sparse-tile scan of round 1) reads 16x more than needed: a query has
 // <= ~50 non-zero components of 800 and only stored entries in those dimensions can
@@ -93,7 +44,6 @@ int count_nnz(const float *vecs, int d, int64_t n, int32_t *nnz, int32_t *nnz_ma
 // FI_CHUNK: blocks of a query listed at a time (a query of the bench probes ~150: one chunk, so the
 // waves of a workgroup wait for each other once per query)
 constexpr int FI_NW = 8, FI_NT = 64 * FI_NW, FI_CHUNK = 256, FI_U = 8;   // FI_U: rows in flight per wave
-constexpr int FI_ROWS = (FI_BLK + 63) / 64;      // rows of accumulators in a block
 static_assert(64 % FI_U == 0, "a batch of dimensions must not straddle the 64 lanes of a chunk");
 
 // (wave_incl_scan -- the seven-DPP-add prefix sum of hist_topk.hpp -- runs twice per block in the
@@ -132,7 +82,7 @@ struct FiUnit {
 // never counted or offered: wherever a position is tested with v < nb, its bit is tested too.
 //
 // RANGED (the window-exact index, ASL_INDEX_WINFLAT; the 2048-key instantiations only): the index is ONE list
-// in precursor order and rg.range[q] = [lo, hi) is the query's run of positions (winflat_runs_kernel below);
+// in precursor order and rg.range[q] = [lo, hi) is the query's run of positions (winflat_runs_kernel, flat_tools.hip);
 // coarse_I, nprobe, list_offsets and blk_offsets are unread. The unit table lists the blocks lo / FI_BLK ..
 // (hi - 1) / FI_BLK -- a whole block outside the run is never listed and none of its lines are fetched -- and
 // a unit's first and one-past-last in-run position follow from its pos0 and the run. An out-of-run vector of a
@@ -152,7 +102,7 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
   static_assert(!SEL || FI_CAP <= 2048, "the selector is built into the 2048-key instantiations only");
   static_assert(!RANGED || (FI_CAP <= 2048 && !WIDE && !SEL), "the ranged form: 2048 keys, no probes, no selector");
   if (gate && (int)blockIdx.x >= *gate) return;      // device-side row count (see pq_scan_v3_kernel)
-  constexpr float FX_SCALE = FX ? 1.0f / 4194304.0f : 1.0f;      // 2^-22, folded into the query values
+  constexpr float FX_SCALE = FX ? 1.0f / FX_GRID : 1.0f;      // 2^-22, folded into the query values
   using TopK = HistTopK<FI_CAP, FI_NT, FI_NT>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float *s_acc = reinterpret_cast<float *>(smem + TopK::lds_bytes());      // [FI_NW][FI_BLK]
@@ -220,18 +170,7 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
       s_misc[10] = 0;     // finished waves
     }
   } else if (wave == 0) {
-    int base = 0;
-    for (int j0 = 0; j0 < d; j0 += 64) {
-      const int j = j0 + lane;
-      const float x = j < d ? s_q[j] : 0.0f;
-      const unsigned long long m = __ballot(x != 0.0f);
-      if (x != 0.0f) {
-        const int t = base + __popcll(m & ((1ull << lane) - 1ull));
-        s_nzd[t] = (uint16_t)j;
-        s_nzv[t] = x * FX_SCALE;
-      }
-      base += __popcll(m);
-    }
+    const int base = list_row_nonzeros(s_q, d, lane, FX_SCALE, s_nzd, s_nzv);
     if (lane == 0) {
       s_misc[8] = base;
       s_misc[9] = 0;      // sync flag
@@ -339,7 +278,7 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
             }
           } else if (kk < K) {
             const uint32_t w = erow[s_nzd[kk]];
-            e = make_uint2((w >> 16) * 64u, w & 0xffffu);
+            e = make_uint2(inv_word_start(w) * 64u, inv_word_count(w));
             qv = s_nzv[kk];
           }
           // The unit of work is a ROW: up to 64 postings of one dimension. A dimension of a
@@ -414,8 +353,8 @@ __global__ __launch_bounds__(FI_NT, FI_CAP <= 2048 ? 6 : 4) void flat_inv_scan_k
 #define FI_APPLY(u)                                                     \
   {                                                                     \
     if constexpr (FX) {                                                 \
-      const uint32_t l_ = loc[u] & 1023u;                               \
-      acc[l_] = __builtin_fmaf(qj[u], (float)(loc[u] >> 10), acc[l_]);  \
+      const uint32_t l_ = fx_word_loc(loc[u]);                          \
+      acc[l_] = __builtin_fmaf(qj[u], (float)fx_word_num(loc[u]), acc[l_]); \
     } else {                                                            \
       acc[loc[u]] = __builtin_fmaf(qj[u], val[u], acc[loc[u]]);         \
     }                                                                   \
@@ -557,501 +496,58 @@ bool flat_inv_supported(int d, int k, int nprobe) {
   return d <= 4096 && nprobe <= 2 * FI_NT && k >= 1 && k + FI_NT + 256 <= 4096;
 }
 
-template <int FI_CAP, bool FX, bool WIDE, bool SEL = false, bool RANGED = false>
-static int launch_flat_inv(const float *xq, int nq, int d, const int32_t *coarse_I, int nprobe,
-                           const int32_t *list_offsets, const int32_t *blk_offsets,
-                           const uint32_t *blk_base, const uint32_t *seg_tab,
-                           const char *seg_bytes, const int32_t *ids, int k, float *D,
-                           int64_t *I64, int32_t *I32, int set_mode, const uint2 *ent,
-                           const int32_t *ent_cnt, int tab_stride, const int *gate, const ScanPostFilter &pf,
-                           const unsigned long long *sel = nullptr, const ScanRanges &rg = ScanRanges()) {
+// The one launch: the view and the request unpacked into the kernel's parameter list.
+template <int FI_CAP, bool FX, bool WIDE, bool SEL, bool RANGED>
+static int launch_flat_inv(const FlatPostings &P, const FlatScan &rq) {
   using TopK = HistTopK<FI_CAP, FI_NT, FI_NT>;
+  const int d = P.d;
   const size_t lds = TopK::lds_bytes() + (size_t)FI_NW * FI_BLK * 4 + (size_t)((d + 3) & ~3) * 4 +
                      (size_t)FI_CHUNK * (sizeof(FiUnit) + 2) + 64 + (size_t)((d + 7) & ~7) * 2;
   if (lds > 160 * 1024) return fail(ASL_ERR_CAPACITY, "flat scan: d=%d does not fit LDS", d);
   if (lds > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute((const void *)flat_inv_scan_kernel<FI_CAP, FX, WIDE, SEL, RANGED>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((flat_inv_scan_kernel<FI_CAP, FX, WIDE, SEL, RANGED>), dim3(nq), dim3(FI_NT), lds, stream(), xq, d,
-                     coarse_I, nprobe, list_offsets, blk_offsets, blk_base, seg_tab, seg_bytes, ids,
-                     k, D, I64, I32, set_mode, ent, ent_cnt, tab_stride, gate, pf, sel, rg);
+  // (the kernel reads the byte table of the fixed-point layout through its table pointer)
+  const uint32_t *seg_tab = FX ? reinterpret_cast<const uint32_t *>(P.tab8) : P.tab32;
+  const ScanPostFilter pf = rq.post.idpay ? rq.post : ScanPostFilter();
+  hipLaunchKernelGGL((flat_inv_scan_kernel<FI_CAP, FX, WIDE, SEL, RANGED>), dim3(rq.nq), dim3(FI_NT), lds, stream(),
+                     rq.xq, d, rq.coarse_I, rq.nprobe, P.list_offsets, P.blk_offsets, P.blk_base, seg_tab,
+                     P.seg_bytes, P.ids, rq.k, rq.D, rq.I64, rq.I32, rq.set_mode, rq.ent, rq.ent_cnt, P.tab_stride,
+                     rq.gate, pf, rq.sel, rq.ranges);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
 }
 
-// layout: 1 = float postings behind a 4-byte table word (seg_tab u32 [nblocks, d], blk_base in
-// 64-byte units); 2 = fixed-point posting words behind a byte table (seg_tab = u8 [nblocks,
-// tab_stride], blk_base in 128-byte lines)
-int flat_inv_scan(int layout, const float *xq, int nq, int d, const int32_t *coarse_I, int nprobe,
-                  const int32_t *list_offsets, const int32_t *blk_offsets,
-                  const uint32_t *blk_base, const void *seg_tab, int tab_stride, const char *seg_bytes,
-                  const int32_t *ids, int k, float *D, int64_t *I64, int32_t *I32, int set_mode,
-                  const uint2 *ent, const int32_t *ent_cnt, const int *gate, const ScanPostFilter *post,
-                  const unsigned long long *sel, const ScanRanges *ranges) {
-  if (nq <= 0) return ASL_OK;
-  const uint32_t *tab = reinterpret_cast<const uint32_t *>(seg_tab);
-  const bool small = k + FI_NT + 256 <= 2048;
-  if (ranges && ranges->range) {      // one precursor-ordered list, a run of positions per query (RANGED)
-    if (!small || set_mode == 2 || sel || gate || (post && post->idpay))
-      return fail(ASL_ERR_STATE, "postings scan: the ranged form needs k <= 1280 and rows of ids, and takes no "
-                                 "selector, gate or post-filter");
-    const ScanPostFilter none;
-    if (layout == 2)
-      return launch_flat_inv<2048, true, false, false, true>(xq, nq, d, nullptr, 0, nullptr, nullptr, blk_base, tab,
-                                                             seg_bytes, ids, k, D, I64, I32, set_mode, ent, ent_cnt,
-                                                             tab_stride, nullptr, none, nullptr, *ranges);
-    return launch_flat_inv<2048, false, false, false, true>(xq, nq, d, nullptr, 0, nullptr, nullptr, blk_base, tab,
-                                                            seg_bytes, ids, k, D, I64, I32, set_mode, ent, ent_cnt,
-                                                            tab_stride, nullptr, none, nullptr, *ranges);
+// FX and WIDE of a (FI_CAP, SEL, RANGED) the dispatcher chose; the ranged form has no probes, so it is never WIDE
+template <int FI_CAP, bool SEL, bool RANGED>
+static int launch_flat_form(bool fx, bool wide, const FlatPostings &P, const FlatScan &rq) {
+  if constexpr (!RANGED) {
+    if (wide)      // (the one-probe form keeps its registers)
+      return fx ? launch_flat_inv<FI_CAP, true, true, SEL, false>(P, rq) : launch_flat_inv<FI_CAP, false, true, SEL, false>(P, rq);
   }
-  ScanPostFilter pf;       // the set-mode finish of the 2048-key instantiation only (scratch behind the keys)
-  if (post && post->idpay) {
-    if (!(set_mode == 1 && I32 && small))
-      return fail(ASL_ERR_STATE, "postings scan: a post-filter needs set-mode int32 rows and k <= 1280");
-    pf = *post;
-  }
-  if (sel) {      // one word per 64 positions of every block (flat_selector)
-    if (!small || set_mode == 2) return fail(ASL_ERR_STATE, "postings scan: a selector needs k <= 1280 and rows of ids");
-#define FI_SEL_LAUNCH(FX, WIDE)                                                                                  \
-  return launch_flat_inv<2048, FX, WIDE, true>(xq, nq, d, coarse_I, nprobe, list_offsets, blk_offsets, blk_base, \
-                                               tab, seg_bytes, ids, k, D, I64, I32, set_mode, ent, ent_cnt,      \
-                                               tab_stride, gate, pf, sel)
-    if (layout == 2) {
-      if (nprobe > FI_NT) FI_SEL_LAUNCH(true, true);
-      FI_SEL_LAUNCH(true, false);
-    }
-    if (nprobe > FI_NT) FI_SEL_LAUNCH(false, true);
-    FI_SEL_LAUNCH(false, false);
-#undef FI_SEL_LAUNCH
-  }
-#define FI_LAUNCH(CAP, FX)                                                                                 \
-  do {                                                                                                     \
-    if (nprobe > FI_NT)       /* two probes per thread (the one-probe form keeps its registers) */          \
-      return launch_flat_inv<CAP, FX, true>(xq, nq, d, coarse_I, nprobe, list_offsets, blk_offsets, blk_base, \
-                                            tab, seg_bytes, ids, k, D, I64, I32, set_mode, ent, ent_cnt,      \
-                                            tab_stride, gate, pf);                                            \
-    return launch_flat_inv<CAP, FX, false>(xq, nq, d, coarse_I, nprobe, list_offsets, blk_offsets, blk_base, \
-                                           tab, seg_bytes, ids, k, D, I64, I32, set_mode, ent, ent_cnt,      \
-                                           tab_stride, gate, pf);                                            \
-  } while (0)
-  if (layout == 2) {
-    if (small) FI_LAUNCH(2048, true);
-    FI_LAUNCH(4096, true);
-  }
-  if (small) FI_LAUNCH(2048, false);
-  FI_LAUNCH(4096, false);
-#undef FI_LAUNCH
+  return fx ? launch_flat_inv<FI_CAP, true, false, SEL, RANGED>(P, rq) : launch_flat_inv<FI_CAP, false, false, SEL, RANGED>(P, rq);
 }
 
-// ---- the run [lo, hi) of every query in the one precursor-ordered list of the window-exact index (RANGED above):
-// window_run (common.hpp), the two binary searches window_ranges_kernel makes per (query, probe), once per
-// query over the whole key column (ascending, NaN last). q_pmz == nullptr: the
-// window that passes everything, NaN keys included: [0, n). acc (optional): += sum of hi - lo.
-__global__ void winflat_runs_kernel(const double *__restrict__ q_pmz, int nq, const float *__restrict__ key, int n,
-                                    int charge, double tol, int mode, int2 *__restrict__ runs,
-                                    unsigned long long *__restrict__ acc) {
-  const int64_t i = block_linear() * blockDim.x + threadIdx.x;
-  unsigned long long cnt = 0;
-  if (i < nq) {
-    int2 r = make_int2(0, n);
-    if (q_pmz) {
-      r = window_run(key, n, query_window(q_pmz, i, mode), charge, tol, mode);
-    }
-    runs[i] = r;
-    cnt = (unsigned long long)(r.y - r.x);
-  }
-  if (acc) {
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(acc, cnt);
-  }
-}
-
-int winflat_runs(const double *q_pmz, int nq, const float *key, int64_t n, int charge, double tol, int mode,
-                 int2 *runs, unsigned long long *acc) {
-  if (nq <= 0) return ASL_OK;
-  hipLaunchKernelGGL(winflat_runs_kernel, grid_2d(cdiv(nq, 256)), dim3(256), 0, stream(), q_pmz, nq, key, (int)n,
-                     charge, tol, mode, runs, acc);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-// ---- selector words of the postings layout (SEL above): FI_ROWS words per block, one wave per word. The
-// block's list comes from a binary search of blk_offsets; a position behind the list's end is unselected.
-__global__ __launch_bounds__(256) void flat_selector_kernel(const int32_t *__restrict__ list_offsets,
-                                                            const int32_t *__restrict__ blk_offsets, int nlist,
-                                                            const int32_t *__restrict__ ids,
-                                                            const uint8_t *__restrict__ keep, int64_t n,
-                                                            int64_t nwords, unsigned long long *__restrict__ words) {
-  const int64_t w = block_linear() * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (w >= nwords) return;             // (wave-uniform)
-  const int blk = (int)(w / FI_ROWS), r = (int)(w % FI_ROWS);
-  int a = 0, b = nlist;                // the last list with blk_offsets[l] <= blk
-  while (b - a > 1) {
-    const int mid = (a + b) >> 1;
-    if (blk_offsets[mid] <= blk) a = mid; else b = mid;
-  }
-  const int64_t pos = (int64_t)list_offsets[a] + (int64_t)(blk - blk_offsets[a]) * FI_BLK + r * 64 + lane;
-  bool on = false;
-  if (blk < blk_offsets[a + 1] && pos < list_offsets[a + 1]) {
-    const int32_t id = ids[pos];
-    on = id >= 0 && id < n && keep[id] != 0;
-  }
-  const unsigned long long m = __ballot(on);
-  if (lane == 0) words[w] = m;
-}
-
-int flat_selector(const int32_t *list_offsets, const int32_t *blk_offsets, int nlist, int64_t nblocks,
-                  const int32_t *ids, const uint8_t *keep, int64_t n, unsigned long long *words) {
-  const int64_t nwords = nblocks * FI_ROWS;
-  if (nwords <= 0 || nlist <= 0) return ASL_OK;
-  hipLaunchKernelGGL(flat_selector_kernel, grid_2d(cdiv(nwords, 4)), dim3(256), 0, stream(), list_offsets,
-                     blk_offsets, nlist, ids, keep, n, nwords, words);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-int flat_selector_words_per_block() { return FI_ROWS; }
-
-// ---- algorithmic work of a postings scan (bench.py: the roofline of this kernel). Per (query,
-// probed block, non-zero query dimension) the scan needs the 4-byte table word and the
-// dimension's postings (6 bytes each): out[0] += 4 + 6 c. out[1] counts what that costs in
-// 128-byte lines: the lines every non-empty segment spans plus the distinct lines of the
-// block's table row that hold a wanted word. One workgroup per query, outside any timed region.
-__global__ __launch_bounds__(256) void flat_inv_work_kernel(
-    const float *__restrict__ xq, int d, const int32_t *__restrict__ coarse_I, int nprobe,
-    const int32_t *__restrict__ blk_offsets, const uint32_t *__restrict__ seg_tab,
-    unsigned long long *__restrict__ out) {
-  extern __shared__ int s_work[];          // [d] non-zero dimensions, then 1 counter
-  int *s_dim = s_work, *s_n = s_work + d;
-  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  if (tid == 0) *s_n = 0;
-  __syncthreads();
-  for (int j = tid; j < d; j += 256)
-    if (xq[(size_t)q * d + j] != 0.0f) s_dim[atomicAdd(s_n, 1)] = j;
-  __syncthreads();
-  const int K = *s_n;
-  unsigned long long bytes = 0, lines = 0;
-  for (int p = 0; p < nprobe; ++p) {
-    const int l = coarse_I[(size_t)q * nprobe + p];
-    if (l < 0) continue;
-    for (int b = blk_offsets[l]; b < blk_offsets[l + 1]; ++b) {
-      const uint32_t *row = seg_tab + (size_t)b * d;
-      for (int t = tid; t < K; t += 256) {
-        const uint32_t w = row[s_dim[t]];
-        const uint32_t c = w & 0xffffu, st = (w >> 16) * 64u;
-        bytes += 4ull + 6ull * c;
-        if (c) lines += ((st + 6u * c - 1u) >> 7) - (st >> 7) + 1u;
-      }
-      // distinct table lines: one wave walks the query's dimensions in line order
-      if (tid < 64) {
-        for (int ln0 = 0; ln0 * 32 < d; ln0 += 64) {      // 32 words per 128-byte line
-          const int ln = ln0 + lane;
-          bool hit = false;
-          for (int t = 0; t < K; ++t) hit |= (s_dim[t] >> 5) == ln;
-          lines += __popcll(__ballot(hit)) * (lane == 0);
-        }
-      }
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    bytes += __shfl_xor(bytes, off);
-    lines += __shfl_xor(lines, off);
-  }
-  if (lane == 0) {
-    atomicAdd(&out[0], bytes);
-    atomicAdd(&out[1], lines);
-  }
-}
-
-int flat_inv_work(const float *xq, int nq, int d, const int32_t *coarse_I, int nprobe,
-                  const int32_t *blk_offsets, const uint32_t *seg_tab, unsigned long long *out_dev) {
-  if (nq <= 0) return ASL_OK;
-  hipLaunchKernelGGL(flat_inv_work_kernel, dim3(nq), dim3(256), (size_t)(d + 1) * 4, stream(), xq, d,
-                     coarse_I, nprobe, blk_offsets, seg_tab, out_dev);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-// Placement of a block's segments (counts cnt[0..d) -> table words tab[0..d)); returns the
-// block's size in 64-byte units, or 0 with *ok = false when a start does not fit 16 bits.
-uint32_t inv_place_block(const uint32_t *cnt, int d, uint32_t *tab, bool *ok) {
-  uint32_t pos = 0;     // 64-byte units; even = on a 128-byte line
-  for (int j = 0; j < d; j++) {
-    const uint32_t c = cnt[j];
-    if (c == 0) {
-      tab[j] = 0u;
-      continue;
-    }
-    const uint32_t units = (6u * c + 63u) / 64u;
-    if (units >= 2u && (pos & 1u)) ++pos;     // a full line or more: start on a line
-    if (pos > 0xffffu || c > 0xffffu) {
-      *ok = false;
-      return 0;
-    }
-    tab[j] = (pos << 16) | c;
-    pos += units;
-  }
-  return pos;
-}
-
-// ---- building the postings from dense rows. pos_blk / pos_loc: block and local index of
-// the list-ordered position i (add-order row order[i]).
-__global__ void inv_count_kernel(const float *__restrict__ vecs, int d,
-                                 const int32_t *__restrict__ order,
-                                 const int32_t *__restrict__ pos_blk, int64_t n,
-                                 uint32_t *__restrict__ cnt) {
-  const int64_t i = block_linear() * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (i >= n) return;
-  const float *row = vecs + (size_t)order[i] * d;
-  uint32_t *c = cnt + (size_t)pos_blk[i] * d;
-  for (int j = lane; j < d; j += 64)
-    if (row[j] != 0.0f) atomicAdd(&c[j], 1u);
-}
-
-__global__ void inv_fill_kernel(const float *__restrict__ vecs, int d,
-                                const int32_t *__restrict__ order,
-                                const int32_t *__restrict__ pos_blk,
-                                const uint16_t *__restrict__ pos_loc, int64_t n,
-                                const uint32_t *__restrict__ blk_base,
-                                const uint32_t *__restrict__ seg_tab,
-                                uint32_t *__restrict__ cursor, char *__restrict__ seg_bytes) {
-  const int64_t i = block_linear() * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (i >= n) return;
-  const float *row = vecs + (size_t)order[i] * d;
-  const size_t b = (size_t)pos_blk[i] * d;
-  char *bptr = seg_bytes + (size_t)blk_base[pos_blk[i]] * 64;
-  const uint16_t loc = pos_loc[i];
-  for (int j = lane; j < d; j += 64) {
-    const float x = row[j];
-    if (x != 0.0f) {
-      const uint32_t w = seg_tab[b + j];
-      const size_t st = (size_t)(w >> 16) * 64;
-      const uint32_t c = w & 0xffffu;
-      const uint32_t p = atomicAdd(&cursor[b + j], 1u);     // any order inside a segment
-      *reinterpret_cast<float *>(bptr + st + 4 * (size_t)p) = x;
-      *reinterpret_cast<uint16_t *>(bptr + st + 4 * (size_t)c + 2 * (size_t)p) = loc;
-    }
-  }
-}
-
-// ---- canonical order inside every segment. inv_fill_kernel leaves the postings of a segment
-// in the order its atomics happened to run; a vector occurs at most once per dimension, so ANY
-// order gives the same accumulators. This pass (one wave per segment) makes the layout
-// deterministic -- postings sorted by local index -- and, for segments longer than a row, deals
-// each row of 64 to its first and second half (the LDS services lanes {0-31} and {32-63} of a
-// ds instruction separately) so that the banks (local index mod 32) inside a half are distinct
-// where the row allows it. Measured (profiles/r03_flat_scan_notes.txt): bank conflicts are NOT
-// what this kernel waits for -- a layout without any conflict runs at the same speed -- the
-// sorted order is worth 1 %; it is kept for the reproducible file image.
-constexpr int IO_WAVES = 4;
-__global__ __launch_bounds__(64 * IO_WAVES) void inv_order_kernel(
-    int64_t nseg, int d, const uint32_t *__restrict__ blk_base,
-    const uint32_t *__restrict__ seg_tab, char *__restrict__ seg_bytes) {
-  __shared__ float s_val[IO_WAVES][2][FI_BLK];
-  __shared__ uint16_t s_loc[IO_WAVES][2][FI_BLK];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t seg = (int64_t)blockIdx.x * IO_WAVES + wave;
-  if (seg >= nseg) return;
-  const uint32_t w = seg_tab[seg];
-  const int c = (int)(w & 0xffffu);
-  if (c <= 1 || c > FI_BLK) return;
-  char *ptr = seg_bytes + (size_t)blk_base[seg / d] * 64 + (size_t)(w >> 16) * 64;
-  float *gv = reinterpret_cast<float *>(ptr);
-  uint16_t *gl = reinterpret_cast<uint16_t *>(ptr + 4 * (size_t)c);
-  float *v0 = s_val[wave][0], *v1 = s_val[wave][1];
-  uint16_t *l0 = s_loc[wave][0], *l1 = s_loc[wave][1];
-  for (int i = lane; i < c; i += 64) {
-    v0[i] = gv[i];
-    l0[i] = gl[i];
-  }
-  __builtin_amdgcn_wave_barrier();
-  // rank sort by local index (unique inside a segment)
-  for (int i = lane; i < c; i += 64) {
-    const uint16_t me = l0[i];
-    int r = 0;
-    for (int t = 0; t < c; ++t) r += l0[t] < me;
-    v1[r] = v0[i];
-    l1[r] = me;
-  }
-  __builtin_amdgcn_wave_barrier();
-  // greedy deal, serial per row (c is ~30; a shared fragment bin has a few hundred)
-  if (lane == 0) {
-    for (int r0 = 0; r0 < c; r0 += 64) {
-      const int n = min(64, c - r0);
-      const int cap0 = min(n, 32), cap1 = n - cap0;      // lanes 0-31 | lanes 32-63 of the row
-      uint32_t used0 = 0, used1 = 0;
-      int n0 = 0, n1 = 0;
-      for (int t = 0; t < n; ++t) {
-        const uint32_t bit = 1u << (l1[r0 + t] & 31);
-        int g;
-        if (!(used0 & bit) && n0 < cap0) g = 0;
-        else if (!(used1 & bit) && n1 < cap1) g = 1;
-        else g = (n0 < cap0 && (n1 >= cap1 || n0 - cap0 <= n1 - cap1)) ? 0 : 1;
-        int dst;
-        if (g == 0) {
-          used0 |= bit;
-          dst = r0 + n0++;
-        } else {
-          used1 |= bit;
-          dst = r0 + cap0 + n1++;
-        }
-        v0[dst] = v1[r0 + t];
-        l0[dst] = l1[r0 + t];
-      }
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  for (int i = lane; i < c; i += 64) {
-    gv[i] = v0[i];
-    gl[i] = l0[i];
-  }
-}
-
-int inv_order(int64_t nblocks, int d, const uint32_t *blk_base, const uint32_t *seg_tab,
-              char *seg_bytes) {
-  const int64_t nseg = nblocks * d;
-  if (nseg <= 0) return ASL_OK;
-  hipLaunchKernelGGL(inv_order_kernel, dim3((unsigned)cdiv(nseg, IO_WAVES)), dim3(64 * IO_WAVES), 0,
-                     stream(), nseg, d, blk_base, seg_tab, seg_bytes);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-int inv_count(const float *vecs, int d, const int32_t *order, const int32_t *pos_blk, int64_t n,
-              uint32_t *cnt) {
-  if (n <= 0) return ASL_OK;
-  hipLaunchKernelGGL(inv_count_kernel, grid_2d(cdiv(n, 4)), dim3(256), 0, stream(), vecs, d,
-                     order, pos_blk, n, cnt);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-int inv_fill(const float *vecs, int d, const int32_t *order, const int32_t *pos_blk,
-             const uint16_t *pos_loc, int64_t n, const uint32_t *blk_base,
-             const uint32_t *seg_tab, uint32_t *cursor, char *seg_bytes) {
-  if (n <= 0) return ASL_OK;
-  hipLaunchKernelGGL(inv_fill_kernel, grid_2d(cdiv(n, 4)), dim3(256), 0, stream(), vecs, d,
-                     order, pos_blk, pos_loc, n, blk_base, seg_tab, cursor, seg_bytes);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-// ---- the fixed-point layout (flat_inv_scan_kernel<.., true>): work accounting and builders.
-// Algorithmic bytes per (query, probed block, non-zero query dimension): the table byte + 4 bytes
-// per posting (cnt16: the real number of postings of every cell, kept for this accounting only);
-// lines: the block's table row (tab_stride / 128, read whole) + the lines of the wanted segments.
-__global__ __launch_bounds__(256) void flat_fx_work_kernel(
-    const float *__restrict__ xq, int d, const int32_t *__restrict__ coarse_I, int nprobe,
-    const int32_t *__restrict__ blk_offsets, const uint8_t *__restrict__ tab8, int tab_stride,
-    const uint16_t *__restrict__ cnt16, unsigned long long *__restrict__ out) {
-  extern __shared__ int s_work[];          // [d] non-zero dimensions, then 1 counter
-  int *s_dim = s_work, *s_n = s_work + d;
-  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  if (tid == 0) *s_n = 0;
-  __syncthreads();
-  for (int j = tid; j < d; j += 256)
-    if (xq[(size_t)q * d + j] != 0.0f) s_dim[atomicAdd(s_n, 1)] = j;
-  __syncthreads();
-  const int K = *s_n;
-  unsigned long long bytes = 0, lines = 0;
-  for (int p = 0; p < nprobe; ++p) {
-    const int l = coarse_I[(size_t)q * nprobe + p];
-    if (l < 0) continue;
-    for (int b = blk_offsets[l]; b < blk_offsets[l + 1]; ++b) {
-      for (int t = tid; t < K; t += 256) {
-        bytes += 1ull + 4ull * cnt16[(size_t)b * d + s_dim[t]];
-        lines += tab8[(size_t)b * tab_stride + s_dim[t]];
-      }
-      if (tid == 0) lines += (unsigned long long)((d + 127) / 128);
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    bytes += __shfl_xor(bytes, off);
-    lines += __shfl_xor(lines, off);
-  }
-  if (lane == 0) {
-    atomicAdd(&out[0], bytes);
-    atomicAdd(&out[1], lines);
-  }
-}
-
-int flat_fx_work(const float *xq, int nq, int d, const int32_t *coarse_I, int nprobe,
-                 const int32_t *blk_offsets, const uint8_t *tab8, int tab_stride,
-                 const uint16_t *cnt16, unsigned long long *out_dev) {
-  if (nq <= 0) return ASL_OK;
-  hipLaunchKernelGGL(flat_fx_work_kernel, dim3(nq), dim3(256), (size_t)(d + 1) * 4, stream(), xq, d,
-                     coarse_I, nprobe, blk_offsets, tab8, tab_stride, cnt16, out_dev);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-// posting words into their segments, in the order the atomics run (fx_order_kernel sorts them).
-// seg_line[cell]: first line of the cell's segment, counted from the start of the data.
-__global__ void fx_fill_kernel(const float *__restrict__ vecs, int d,
-                               const int32_t *__restrict__ order,
-                               const int32_t *__restrict__ pos_blk,
-                               const uint16_t *__restrict__ pos_loc, int64_t n,
-                               const uint32_t *__restrict__ seg_line,
-                               uint32_t *__restrict__ cursor, uint32_t *__restrict__ words) {
-  const int64_t i = block_linear() * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (i >= n) return;
-  const float *row = vecs + (size_t)order[i] * d;
-  const size_t b = (size_t)pos_blk[i] * d;
-  const uint32_t loc = pos_loc[i];
-  for (int j = lane; j < d; j += 64) {
-    const float x = row[j];
-    if (x != 0.0f) {
-      const uint32_t p = atomicAdd(&cursor[b + j], 1u);
-      words[(size_t)seg_line[b + j] * 32 + p] = ((uint32_t)(x * 4194304.0f) << 10) | loc;   // exact: x is on the grid
-    }
-  }
-}
-
-// canonical image of every segment: postings ascending in the local index (unique inside a
-// segment), the rest of the last line filled with repeats of the last posting. One wave per cell.
-__global__ __launch_bounds__(64 * IO_WAVES) void fx_order_kernel(
-    int64_t ncell, const uint32_t *__restrict__ seg_line, const uint32_t *__restrict__ count,
-    uint32_t *__restrict__ words) {
-  __shared__ uint32_t s_w[IO_WAVES][2][FI_BLK];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t cell = (int64_t)blockIdx.x * IO_WAVES + wave;
-  if (cell >= ncell) return;
-  const int c = (int)count[cell];
-  if (c <= 0 || c > FI_BLK) return;
-  uint32_t *g = words + (size_t)seg_line[cell] * 32;
-  uint32_t *a = s_w[wave][0], *b = s_w[wave][1];
-  for (int i = lane; i < c; i += 64) a[i] = g[i];
-  __builtin_amdgcn_wave_barrier();
-  for (int i = lane; i < c; i += 64) {
-    const uint32_t me = a[i] & 1023u;
-    int r = 0;
-    for (int t = 0; t < c; ++t) r += (a[t] & 1023u) < me;
-    b[r] = a[i];
-  }
-  __builtin_amdgcn_wave_barrier();
-  const int padded = (c + 31) & ~31;
-  for (int i = lane; i < padded; i += 64) g[i] = b[min(i, c - 1)];
-}
-
-int fx_fill(const float *vecs, int d, const int32_t *order, const int32_t *pos_blk,
-            const uint16_t *pos_loc, int64_t n, const uint32_t *seg_line, uint32_t *cursor,
-            uint32_t *words) {
-  if (n <= 0) return ASL_OK;
-  hipLaunchKernelGGL(fx_fill_kernel, grid_2d(cdiv(n, 4)), dim3(256), 0, stream(), vecs, d, order,
-                     pos_blk, pos_loc, n, seg_line, cursor, words);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-int fx_order(int64_t ncell, const uint32_t *seg_line, const uint32_t *count, uint32_t *words) {
-  if (ncell <= 0) return ASL_OK;
-  hipLaunchKernelGGL(fx_order_kernel, dim3((unsigned)cdiv(ncell, IO_WAVES)), dim3(64 * IO_WAVES), 0,
-                     stream(), ncell, seg_line, count, words);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
+// What each form accepts, then the one choice of (FI_CAP, FX, WIDE, SEL, RANGED): 14 instantiations -- plain
+// requests at both key capacities, the selector and the ranged form at 2048 keys only (the kernel's static_asserts).
+int flat_inv_scan(const FlatPostings &P, const FlatScan &rq) {
+  if (rq.nq <= 0) return ASL_OK;
+  const bool small = rq.k + FI_NT + 256 <= 2048;      // k <= 1280: the 2048-key buffer, three workgroups per CU
+  const bool ranged = rq.ranges.range != nullptr;     // one precursor-ordered list, a run of positions per query
+  const bool filtered = rq.post.idpay != nullptr;     // the set-mode finish of the 2048-key instantiations only
+  if (ranged && (!small || rq.set_mode == 2 || rq.sel || rq.gate || filtered))
+    return fail(ASL_ERR_STATE, "postings scan: the ranged form needs k <= 1280 and rows of ids, and takes no "
+                               "selector, gate or post-filter");
+  if (!ranged && filtered && !(rq.set_mode == 1 && rq.I32 && small))
+    return fail(ASL_ERR_STATE, "postings scan: a post-filter needs set-mode int32 rows and k <= 1280");
+  if (!ranged && rq.sel && (!small || rq.set_mode == 2))      // one word per 64 positions of every block (flat_selector)
+    return fail(ASL_ERR_STATE, "postings scan: a selector needs k <= 1280 and rows of ids");
+  const bool fx = P.layout == 2, wide = rq.nprobe > FI_NT;      // wide: two probes per thread
+  if (ranged) return launch_flat_form<2048, false, true>(fx, false, P, rq);
+  if (rq.sel) return launch_flat_form<2048, true, false>(fx, wide, P, rq);
+  return small ? launch_flat_form<2048, false, false>(fx, wide, P, rq)
+               : launch_flat_form<4096, false, false>(fx, wide, P, rq);
 }
 
 }  // namespace asl
+

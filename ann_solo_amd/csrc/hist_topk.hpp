@@ -1,6 +1,6 @@
 // hist_topk.hpp -- exact top-k of a long candidate stream for one workgroup of NT = 256 or
 // 512 threads
-// WITHOUT sorting while streaming (used by pq_scan_v3.hip and flat_scan.hip).
+// WITHOUT sorting while streaming (used by pq_scan_v3.hip and flat_scan.hip, the scan of flat_postings.hpp).
 //
 //   * hist[512]: counts of the appended candidates per score bucket (monotone linear
 //     bucketing of the fp32 score over [-0.25, 1)),

@@ -2,6 +2,7 @@
 // the index_*.hip units share and what search.hip / sharded.hip call. Private to the library.
 #pragma once
 #include "common.hpp"
+#include "flat_postings.hpp"
 #include "ivf_kernels.hpp"
 
 namespace asl {
@@ -127,7 +128,7 @@ struct asl_index {
   uint32_t mm_plane = 0;
   bool mm_ready = false;
   bool scan_mmajor = true;       // asl_index_set_scan_variant(2) clears it: variant 0 with the tile-major codes only
-  // selector words of the scans (ivf_kernels.hpp: tile_selector / flat_selector), derived like idpay: never
+  // selector words of the scans (tile_selector, ivf_kernels.hpp / flat_selector, flat_postings.hpp), derived like idpay: never
   // saved, dropped by build_lists, rebuilt when (serial, generation) of the selector or the lists change.
   // sel_words: per tile of the default layout (IVF-PQ) or per 64 positions of a block (IVF-Flat);
   // wsel_words: per tile of the window-ordered copy (dropped with it)
@@ -139,14 +140,16 @@ struct asl_index {
   bool has_selector = false;
   uint64_t selector_gen = 0;
   int64_t n_blocks = 0;               // blocks of the postings layout
-  // dimension-major postings for flat_inv_scan (IVF-Flat): blocks of FI_BLK vectors
+  // dimension-major postings for flat_inv_scan (IVF-Flat): blocks of FI_BLK vectors. flat_postings.hpp owns the
+  // two layouts and their encodings; the scans, the selector, the rank and the work counter read them through
+  // postings_view() below, the one place that picks inv_tab or inv_tab8
   asl::DevBuf<int32_t> blk_offsets;   // [nlist + 1] first block of each list
   asl::DevBuf<uint32_t> blk_base;     // [nblocks] start of the block's postings, 64-byte units
-  asl::DevBuf<uint32_t> inv_tab;      // [nblocks * d] (start from the block's base in 64-byte units) << 16 | postings
+  asl::DevBuf<uint32_t> inv_tab;      // [nblocks * d] table words (inv_word)
   asl::DevBuf<char> inv_data;         // segments: c values (f32) then c local vector indices (u16), placed by 128-byte line
   bool has_inv = false;
   // the fixed-point layout (inv_layout 2): blk_base in 128-byte lines, one byte per (block,
-  // dimension) = lines of the segment, posting words (numerator << 10 | local index) in inv_data
+  // dimension) = lines of the segment, posting words (fx_word) in inv_data
   int flat_storage = ASL_FLAT_F32;   // ASL_FLAT_F32 (default): components as given; ASL_FLAT_FX22: add() rounds
                                      // components in [0, 1) to 22 fractional bits
   int inv_layout = 0;            // what build_lists found the data fit for: 0 none, 1 float postings, 2 fixed-point words
@@ -194,6 +197,17 @@ inline bool ivf_kind(int kind) { return kind == ASL_INDEX_IVFFLAT || kind == ASL
 inline bool window_mode(const asl_index *ix) { return ix->window_scan || ix->kind == ASL_INDEX_WINFLAT; }
 inline bool tiled_index(const asl_index *ix) {
   return ix->kind == ASL_INDEX_IVFPQ && ix->pq_m == 32 && ix->ksub == 256 && ix->d <= PQ_TILED_MAX_D;
+}
+// The postings an index holds, as its readers take them (layout 0: none -- an empty window-exact index, whose
+// every run is empty, is scanned in the float form and reads nothing).
+inline FlatPostings postings_view(const asl_index *ix) {
+  FlatPostings P;
+  P.layout = ix->has_inv ? ix->inv_layout : 0, P.d = ix->d, P.nlist = ix->nlist, P.n_blocks = ix->n_blocks;
+  P.list_offsets = ix->list_offsets.p, P.blk_offsets = ix->blk_offsets.p, P.blk_base = ix->blk_base.p;
+  if (P.layout == 2) P.tab8 = ix->inv_tab8.p, P.cnt16 = ix->inv_cnt16.p;
+  else P.tab32 = ix->inv_tab.p;
+  P.tab_stride = ix->tab_stride, P.seg_bytes = ix->inv_data.p, P.ids = ix->ids.p;
+  return P;
 }
 // index_train.hip
 int assign_ip(asl_index *ix, const float *x, int64_t ld, int64_t n, const float *cent, int k, int d,

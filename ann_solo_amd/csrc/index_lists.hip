@@ -9,105 +9,110 @@
 
 namespace asl {
 
-// The per-dimension postings (flat_scan.hip) of ix->vecs in a position order: the builder of the IVF-Flat lists
-// and of the one list of the window-exact index (index.hpp says what the arguments are).
+// What the two builders of build_postings share: the position order (device), the per-cell counts (host) and the
+// fill's zeroed cursors (device, [ncell]). A builder that fits sets inv_layout; the caller sets has_inv.
+struct PostingsInput {
+  const int32_t *order, *pos_blk;     // the add-order row and the block of every position
+  const uint16_t *pos_loc;            // ... and its local index
+  int64_t n;
+  size_t nblk, ncell;                 // blocks (at least 1), blocks * d
+  const std::vector<uint32_t> &h_cnt; // postings per (block, dimension)
+  uint32_t *cursor;
+};
+
+// Layout 2 (flat_postings.hpp): whole lines of posting words behind a byte table; the lines must fit 32 bits.
+static int build_fx_postings(asl_index *ix, const PostingsInput &in) {
+  const size_t d = (size_t)ix->d, stride = (d + 127) & ~(size_t)127;
+  std::vector<uint8_t> h_tab8(in.nblk * stride, 0);
+  std::vector<uint16_t> h_c16(in.ncell);
+  std::vector<uint32_t> h_line(in.ncell), h_base(in.nblk);
+  uint64_t run = 0;     // 128-byte lines
+  for (size_t b = 0; b < in.nblk; b++) {
+    h_base[b] = (uint32_t)run;
+    run += fx_place_block(in.h_cnt.data() + b * d, ix->d, (uint32_t)run, h_tab8.data() + b * stride,
+                          h_c16.data() + b * d, h_line.data() + b * d);
+  }
+  if (run >= (1ull << 32)) return ASL_OK;
+  const size_t bytes = (size_t)std::max<uint64_t>(run, 1) * 128 + 512;
+  DevBuf<uint32_t> line_dev;
+  ASL_TRY(line_dev.upload(h_line.data(), in.ncell));
+  ASL_TRY(ix->blk_base.upload(h_base.data(), in.nblk));
+  ASL_TRY(ix->inv_tab8.upload(h_tab8.data(), h_tab8.size()));
+  ASL_TRY(ix->inv_cnt16.upload(h_c16.data(), in.ncell));
+  ASL_TRY(ix->inv_data.reserve(bytes));
+  HIP_TRY(hipMemsetAsync(ix->inv_data.p, 0, bytes, stream()));
+  ASL_TRY(fx_fill(ix->vecs.p, ix->d, in.order, in.pos_blk, in.pos_loc, in.n, (int64_t)in.ncell, line_dev.p, in.cursor,
+                  reinterpret_cast<uint32_t *>(ix->inv_data.p)));
+  ASL_TRY(sync_stream());      // (line_dev and the host tables are freed on return)
+  ix->tab_stride = (int)stride;
+  ix->inv_layout = 2;
+  return ASL_OK;
+}
+
+// Layout 1: float postings, segments placed block by block; starts and counts must fit 16 bits, the units 32.
+static int build_float_postings(asl_index *ix, const PostingsInput &in) {
+  const size_t d = (size_t)ix->d;
+  std::vector<uint32_t> h_tab(in.ncell), h_base(in.nblk);
+  uint64_t run = 0;     // 64-byte units
+  bool ok = true;
+  for (size_t b = 0; b < in.nblk && ok; b++) {
+    h_base[b] = (uint32_t)run;
+    run += inv_place_block(in.h_cnt.data() + b * d, ix->d, h_tab.data() + b * d, &ok);
+    run += run & 1ull;      // every block starts on a 128-byte line
+  }
+  if (!ok || run >= (1ull << 32)) return ASL_OK;     // 32-bit unit offsets (256 GB of postings)
+  // (+ 512: the scan reads a full wave-width from the start of an empty segment)
+  const size_t bytes = (size_t)std::max<uint64_t>(run, 2) * 64 + 512;
+  ASL_TRY(ix->blk_base.upload(h_base.data(), in.nblk));
+  ASL_TRY(ix->inv_tab.upload(h_tab.data(), in.ncell));
+  ASL_TRY(ix->inv_data.reserve(bytes));
+  HIP_TRY(hipMemsetAsync(ix->inv_data.p, 0, bytes, stream()));
+  ASL_TRY(inv_fill(ix->vecs.p, ix->d, in.order, in.pos_blk, in.pos_loc, in.n, (int64_t)in.nblk, ix->blk_base.p,
+                   ix->inv_tab.p, in.cursor, ix->inv_data.p));
+  ASL_TRY(sync_stream());      // (the host tables are freed on return)
+  ix->inv_layout = 1;
+  return ASL_OK;
+}
+
+// The per-dimension postings (flat_postings.hpp) of ix->vecs in a position order, for the IVF-Flat lists and the
+// one list of the window-exact index (index.hpp says what the arguments are). Count, decide, build: fixed-point
+// words when every non-zero is on the 2^-22 grid inside (0, 1) and a table row fits one load per lane (the
+// window-exact index: only in fixed-point storage mode), else -- or when those do not fit -- float postings.
 int build_postings(asl_index *ix, const int32_t *order_dev, int64_t n, const std::vector<int32_t> &blk_off,
                    const std::vector<int32_t> &pos_blk, const std::vector<uint16_t> &pos_loc) {
   DevBuf<int32_t> nnz, nnz_max;
   ASL_TRY(nnz.reserve((size_t)n));
   ASL_TRY(nnz_max.reserve(2));
   ASL_TRY(count_nnz(ix->vecs.p, ix->d, n, nnz.p, nnz_max.p));
-  int32_t h_nm[2] = {0, 0};
+  int32_t h_nm[2] = {0, 0};     // the most non-zeros of a vector; 1 when a non-zero is off the grid
   ASL_TRY(nnz_max.download(h_nm, 2));
   ASL_TRY(sync_stream());
-  const int32_t h_max = h_nm[0];
-  ix->nnz_max = h_max;
-  // every non-zero on the 2^-22 grid inside (0, 1): posting words (flat_scan.hip, FX)
-  // (the window-exact index: only in fixed-point storage mode)
-  const bool fixed_point = h_nm[1] == 0 && ix->d <= 1024 && FI_BLK <= 1024 &&
+  ix->nnz_max = h_nm[0];
+  if (!(h_nm[0] > 0 && (size_t)h_nm[0] * 8 < (size_t)ix->d)) return ASL_OK;     // too dense: the postings do not pay
+  const size_t nblk = (size_t)std::max<int32_t>(blk_off.back(), 1), ncell = nblk * (size_t)ix->d;
+  ix->n_blocks = blk_off.back();
+  DevBuf<int32_t> pos_blk_dev;
+  DevBuf<uint16_t> pos_loc_dev;
+  DevBuf<uint32_t> cnt_dev;
+  ASL_TRY(pos_blk_dev.upload(pos_blk.data(), (size_t)n));
+  ASL_TRY(pos_loc_dev.upload(pos_loc.data(), (size_t)n));
+  ASL_TRY(cnt_dev.reserve(ncell));
+  HIP_TRY(hipMemsetAsync(cnt_dev.p, 0, ncell * 4, stream()));
+  ASL_TRY(inv_count(ix->vecs.p, ix->d, order_dev, pos_blk_dev.p, n, cnt_dev.p));
+  std::vector<uint32_t> h_cnt(ncell);
+  ASL_TRY(cnt_dev.download(h_cnt.data(), ncell));
+  ASL_TRY(sync_stream());
+  HIP_TRY(hipMemsetAsync(cnt_dev.p, 0, ncell * 4, stream()));      // the counts become the fill's cursors
+  ix->inv_layout = 0;
+  const PostingsInput in{order_dev, pos_blk_dev.p, pos_loc_dev.p, n, nblk, ncell, h_cnt, cnt_dev.p};
+  const bool fixed_point = h_nm[1] == 0 && ix->d <= FX_MAX_D &&
                            (ix->kind != ASL_INDEX_WINFLAT || ix->flat_storage == ASL_FLAT_FX22);
-  // dimension-major postings (the default IVF-Flat scan)
-  if (h_max > 0 && (size_t)h_max * 8 < (size_t)ix->d) {
-    const size_t nblk = (size_t)std::max<int32_t>(blk_off.back(), 1);
-    ix->n_blocks = blk_off.back();
-    const size_t ncell = nblk * (size_t)ix->d;
-    DevBuf<int32_t> pos_blk_dev;
-    DevBuf<uint16_t> pos_loc_dev;
-    DevBuf<uint32_t> cnt_dev;
-    ASL_TRY(pos_blk_dev.upload(pos_blk.data(), (size_t)n));
-    ASL_TRY(pos_loc_dev.upload(pos_loc.data(), (size_t)n));
-    ASL_TRY(cnt_dev.reserve(ncell));
-    HIP_TRY(hipMemsetAsync(cnt_dev.p, 0, ncell * 4, stream()));
-    ASL_TRY(inv_count(ix->vecs.p, ix->d, order_dev, pos_blk_dev.p, n, cnt_dev.p));
-    std::vector<uint32_t> h_cnt(ncell);
-    ASL_TRY(cnt_dev.download(h_cnt.data(), ncell));
-    ASL_TRY(sync_stream());
-    ix->inv_layout = 0;
-    if (fixed_point) {
-      // whole lines of 32 posting words per (block, dimension); the table byte is the line count
-      const int stride = (ix->d + 127) & ~127;
-      std::vector<uint8_t> h_tab8(nblk * (size_t)stride, 0);
-      std::vector<uint16_t> h_c16(ncell);
-      std::vector<uint32_t> h_line(ncell), h_base(nblk);
-      uint64_t run = 0;     // 128-byte lines
-      for (size_t b = 0; b < nblk; b++) {
-        h_base[b] = (uint32_t)run;
-        for (int j = 0; j < ix->d; j++) {
-          const uint32_t c = h_cnt[b * (size_t)ix->d + j];       // <= FI_BLK: at most 26 lines
-          h_line[b * (size_t)ix->d + j] = (uint32_t)run;
-          h_c16[b * (size_t)ix->d + j] = (uint16_t)c;
-          h_tab8[b * (size_t)stride + j] = (uint8_t)((c + 31) / 32);
-          run += (c + 31) / 32;
-        }
-      }
-      if (run < (1ull << 32)) {
-        const size_t bytes = (size_t)std::max<uint64_t>(run, 1) * 128 + 512;
-        DevBuf<uint32_t> line_dev;
-        ASL_TRY(line_dev.upload(h_line.data(), ncell));
-        ASL_TRY(ix->blk_offsets.upload(blk_off.data(), blk_off.size()));
-        ASL_TRY(ix->blk_base.upload(h_base.data(), nblk));
-        ASL_TRY(ix->inv_tab8.upload(h_tab8.data(), h_tab8.size()));
-        ASL_TRY(ix->inv_cnt16.upload(h_c16.data(), ncell));
-        ASL_TRY(ix->inv_data.reserve(bytes));
-        HIP_TRY(hipMemsetAsync(ix->inv_data.p, 0, bytes, stream()));
-        HIP_TRY(hipMemsetAsync(cnt_dev.p, 0, ncell * 4, stream()));
-        ASL_TRY(fx_fill(ix->vecs.p, ix->d, order_dev, pos_blk_dev.p, pos_loc_dev.p, n, line_dev.p,
-                        cnt_dev.p, reinterpret_cast<uint32_t *>(ix->inv_data.p)));
-        ASL_TRY(fx_order((int64_t)ncell, line_dev.p, cnt_dev.p, reinterpret_cast<uint32_t *>(ix->inv_data.p)));
-        ASL_TRY(sync_stream());
-        ix->tab_stride = stride;
-        ix->has_inv = true;
-        ix->inv_layout = 2;
-      }
-    }
-    if (!ix->has_inv) {
-    // segments placed block by block (flat_scan.hip: inv_place_block)
-    std::vector<uint32_t> h_tab(ncell), h_base(nblk);
-    uint64_t run = 0;     // 64-byte units
-    bool ok = true;
-    for (size_t b = 0; b < nblk && ok; b++) {
-      h_base[b] = (uint32_t)run;
-      run += inv_place_block(h_cnt.data() + b * (size_t)ix->d, ix->d, h_tab.data() + b * (size_t)ix->d, &ok);
-      run += run & 1ull;      // every block starts on a 128-byte line
-    }
-    if (ok && run < (1ull << 32)) {     // 32-bit unit offsets (256 GB of postings)
-      // (+ 512: the scan reads a full wave-width from the start of an empty segment)
-      const size_t bytes = (size_t)std::max<uint64_t>(run, 2) * 64 + 512;
-      ASL_TRY(ix->blk_offsets.upload(blk_off.data(), blk_off.size()));
-      ASL_TRY(ix->blk_base.upload(h_base.data(), nblk));
-      ASL_TRY(ix->inv_tab.upload(h_tab.data(), ncell));
-      ASL_TRY(ix->inv_data.reserve(bytes));
-      HIP_TRY(hipMemsetAsync(ix->inv_data.p, 0, bytes, stream()));
-      HIP_TRY(hipMemsetAsync(cnt_dev.p, 0, ncell * 4, stream()));
-      ASL_TRY(inv_fill(ix->vecs.p, ix->d, order_dev, pos_blk_dev.p, pos_loc_dev.p, n,
-                       ix->blk_base.p, ix->inv_tab.p, cnt_dev.p, ix->inv_data.p));
-      ASL_TRY(inv_order((int64_t)nblk, ix->d, ix->blk_base.p, ix->inv_tab.p, ix->inv_data.p));
-      ASL_TRY(sync_stream());
-      ix->has_inv = true;
-      ix->inv_layout = 1;
-    }
-    }
-  }
+  if (fixed_point) ASL_TRY(build_fx_postings(ix, in));
+  if (!ix->inv_layout) ASL_TRY(build_float_postings(ix, in));
+  if (!ix->inv_layout) return ASL_OK;      // neither fits its offsets: no postings
+  ASL_TRY(ix->blk_offsets.upload(blk_off.data(), blk_off.size()));
+  ASL_TRY(sync_stream());
+  ix->has_inv = true;
   return ASL_OK;
 }
 
@@ -287,8 +292,7 @@ int selector_words(asl_index *ix, const IndexSearch &rq, bool window, const unsi
       ASL_TRY(tile_selector(window ? ix->wids_tiled.p : ix->ids_tiled.p, ntiles, rq.sel_keep, rq.sel_n, buf.p));
     } else {
       ASL_TRY(buf.reserve((size_t)std::max<int64_t>(ix->n_blocks, 1) * flat_selector_words_per_block()));
-      ASL_TRY(flat_selector(ix->list_offsets.p, ix->blk_offsets.p, ix->nlist, ix->n_blocks, ix->ids.p, rq.sel_keep,
-                            rq.sel_n, buf.p));
+      ASL_TRY(flat_selector(postings_view(ix), rq.sel_keep, rq.sel_n, buf.p));
     }
     serial = rq.serial;
     gen = rq.gen;

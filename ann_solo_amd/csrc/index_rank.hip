@@ -67,9 +67,8 @@ static int index_rank_device(asl_index *ix, int nq, const float *xq, const int64
                       ix->list_offsets.p, ix->tile_offsets.p, ix->codes_tiled.p, ix->ids_tiled.p, target + r0, inv.p,
                       win, tkey.p + r0, tscore.p + r0, counts.p + (size_t)r0 * 2, scope != nullptr));
     } else {
-      ASL_TRY(rank_flat(x, m, d, nlist, ix->ntotal, cI, nprobe, ix->list_offsets.p, ix->blk_offsets.p, ix->blk_base.p,
-                        ix->inv_tab.p, ix->inv_data.p, ix->ids.p, target + r0, inv.p, win, tkey.p + r0, tscore.p + r0,
-                        counts.p + (size_t)r0 * 2, scope != nullptr));
+      ASL_TRY(rank_flat(postings_view(ix), x, m, ix->ntotal, cI, nprobe, target + r0, inv.p, win, tkey.p + r0,
+                        tscore.p + r0, counts.p + (size_t)r0 * 2, scope != nullptr));
     }
   }
   ASL_TRY(rank_finish(tkey.p, tscore.p, counts.p, nq, rank, score, scope));
@@ -98,6 +97,9 @@ int asl_index_rank(asl_index_t *ix, int32_t nq, const float *xq, const int64_t *
   if (!ix->trained) return fail(ASL_ERR_STATE, "rank: index is not trained");
   ASL_TRY(build_lists(ix));
   if (ix->kind == ASL_INDEX_IVFFLAT) {
+    // rank_flat_block (rank_scan.hip) reads float postings only. A fixed-point index (layout 2; its view carries
+    // tab8, no tab32) is refused here and never reaches it. Ranking one is open: the walk would need the FX
+    // decoding of flat_inv_scan_kernel (line counts summed into starts, 2^-22 folded into the query values).
     if (ix->n_store > 0 && ix->has_inv && ix->inv_layout == 2)
       return fail(ASL_ERR_STATE, "rank: fixed-point postings (ASL_FLAT_FX22) are not supported, only float postings");
     if (ix->n_store > 0 && !(ix->has_inv && ix->inv_layout == 1))

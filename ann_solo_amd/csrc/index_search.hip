@@ -319,7 +319,7 @@ static int search_gemm_topk(asl_index *ix, const IndexSearch &rq, const int32_t 
   return upper ? sync_stream() : ASL_OK;
 }
 
-// IVF-Flat: the postings scan (flat_scan.hip) when the lists have postings, else the GEMM
+// IVF-Flat: the postings scan (flat_scan.hip; flat_postings.hpp) when the lists have postings, else the GEMM
 static int search_ivfflat(asl_index *ix, IndexSearch &rq, const SearchPlan &pl) {
   const int nq = rq.nq, nprobe = pl.nprobe;
   bool own_ent = false;
@@ -339,12 +339,11 @@ static int search_ivfflat(asl_index *ix, IndexSearch &rq, const SearchPlan &pl) 
   if (rq.sel_keep) ASL_TRY(selector_words(ix, rq, false, &sel));
   {
     ProfScope ps("scan");     // the scan kernel itself
-    const bool fx = ix->inv_layout == 2;
-    ASL_TRY(flat_inv_scan(ix->inv_layout, rq.xq, nq, ix->d, cI, nprobe, ix->list_offsets.p,
-                          ix->blk_offsets.p, ix->blk_base.p,
-                          fx ? (const void *)ix->inv_tab8.p : (const void *)ix->inv_tab.p,
-                          ix->tab_stride, ix->inv_data.p, ix->ids.p, rq.k, rq.D, rq.I64, rq.I32,
-                          mode_, q_ent, q_cnt, rq.gate, &pf, sel));
+    FlatScan fs;
+    fs.xq = rq.xq, fs.ent = q_ent, fs.ent_cnt = q_cnt, fs.nq = nq, fs.k = rq.k;
+    fs.coarse_I = cI, fs.nprobe = nprobe, fs.gate = rq.gate, fs.post = pf, fs.sel = sel;
+    fs.D = rq.D, fs.I64 = rq.I64, fs.I32 = rq.I32, fs.set_mode = mode_;
+    ASL_TRY(flat_inv_scan(postings_view(ix), fs));
   }
   return rq.gate ? ASL_OK : count_scanned(ix, cI, nq, nprobe);
 }
@@ -366,15 +365,14 @@ static int search_winflat(asl_index *ix, IndexSearch &rq, const SearchPlan &pl) 
                          w ? w->mode : ASL_TOL_DA, ix->win_ranges.p,
                          prof_counts() ? prof_scanned_dev() : nullptr));      // work: sum of hi - lo
   }
-  ScanRanges rg;
-  rg.range = ix->win_ranges.p;
-  rg.row_len = (rq.win && mode_ == 1) ? rq.win->row_len : nullptr;
-  rq.rows_filtered = rg.row_len != nullptr;
+  FlatScan fs;      // no probes: the runs stand for them
+  fs.xq = rq.xq, fs.ent = q_ent, fs.ent_cnt = q_cnt, fs.nq = nq, fs.k = rq.k;
+  fs.D = rq.D, fs.I64 = rq.I64, fs.I32 = rq.I32, fs.set_mode = mode_;
+  fs.ranges.range = ix->win_ranges.p;
+  fs.ranges.row_len = (rq.win && mode_ == 1) ? rq.win->row_len : nullptr;
+  rq.rows_filtered = fs.ranges.row_len != nullptr;
   ProfScope ps("scan");
-  const bool fx = ix->has_inv && ix->inv_layout == 2;      // (an empty index: every run is empty, no layout is read)
-  return flat_inv_scan(fx ? 2 : 1, rq.xq, nq, ix->d, nullptr, 0, nullptr, nullptr, ix->blk_base.p,
-                       fx ? (const void *)ix->inv_tab8.p : (const void *)ix->inv_tab.p, ix->tab_stride, ix->inv_data.p,
-                       ix->ids.p, rq.k, rq.D, rq.I64, rq.I32, mode_, q_ent, q_cnt, nullptr, nullptr, nullptr, &rg);
+  return flat_inv_scan(postings_view(ix), fs);      // (an empty index: every run is empty, no layout is read)
 }
 
 // [m][dsub][ksub] copy of the codebooks for the tiled scan's LUT build (rebuilt after train / set_trained)
@@ -623,11 +621,7 @@ int asl_index_postings_work(asl_index_t *ix, int32_t nq, const float *xq, int32_
   DevBuf<unsigned long long> acc;
   ASL_TRY(acc.reserve(2));
   HIP_TRY(hipMemsetAsync(acc.p, 0, 16, stream()));
-  if (ix->inv_layout == 2)
-    ASL_TRY(flat_fx_work(dq.d, nq, ix->d, ix->coarse_I.p, nprobe, ix->blk_offsets.p, ix->inv_tab8.p,
-                         ix->tab_stride, ix->inv_cnt16.p, acc.p));
-  else
-    ASL_TRY(flat_inv_work(dq.d, nq, ix->d, ix->coarse_I.p, nprobe, ix->blk_offsets.p, ix->inv_tab.p, acc.p));
+  ASL_TRY(flat_postings_work(postings_view(ix), dq.d, nq, ix->coarse_I.p, nprobe, acc.p));
   unsigned long long h[2] = {0, 0};
   ASL_TRY(acc.download(h, 2));
   ASL_TRY(sync_stream());

@@ -9,6 +9,7 @@ namespace asl {
 
 struct ScanPostFilter;            // common.hpp
 struct ScanRanges;
+struct FlatPostings;              // flat_postings.hpp
 
 constexpr int TK_NT = 256;        // threads per top-k workgroup
 constexpr int TK_MAX_K = 2048;    // largest k / nprobe the LDS top-k supports
@@ -97,58 +98,7 @@ int window_ranges(const double *q_pmz, int nq, const int32_t *coarse_I, int npro
 int tile_codes(const uint8_t *codes, const int32_t *ids, const int32_t *dst_slot, int64_t n,
                int64_t ntiles, uint8_t *codes_tiled, int32_t *ids_tiled);
 
-// ---- flat_scan.hip: dimension-major IVF-Flat, blocks of FI_BLK vectors with per-dimension postings
-// FI_BLK measured (scan ms at nprobe 128): 512 7.69 | 640 7.14 | 768 6.81 | 832 6.71 | 864 6.70 (the LDS limit of three workgroups per CU) | 1024: two workgroups per CU
-constexpr int FI_BLK = 832;
-bool flat_inv_supported(int d, int k, int nprobe);
-// layout 1: float postings (seg_tab u32 [nblocks, d]); 2: fixed-point posting words behind a byte
-// table (seg_tab u8 [nblocks, tab_stride]); see flat_scan.hip
-int flat_inv_scan(int layout, const float *xq, int nq, int d, const int32_t *coarse_I, int nprobe,
-                  const int32_t *list_offsets, const int32_t *blk_offsets,
-                  const uint32_t *blk_base, const void *seg_tab, int tab_stride, const char *seg_bytes,
-                  const int32_t *ids, int k, float *D, int64_t *I64, int32_t *I32, int set_mode,
-                  const uint2 *ent, const int32_t *ent_cnt, const int *gate = nullptr,
-                  const ScanPostFilter *post = nullptr,   // set-mode int32 rows, k <= 1280 only
-                  const unsigned long long *sel = nullptr,    // selector: flat_selector's words, k <= 1280
-                  const ScanRanges *ranges = nullptr);        // (common.hpp) the window-exact index: range [nq], one run of
-                                                              // positions per query in ONE list; probes and offsets unread
-// the runs of the window-exact index: [lo, hi) per query over the key column by position
-// (ascending, NaN last); q_pmz == nullptr: [0, n) for every query
-int winflat_runs(const double *q_pmz, int nq, const float *key, int64_t n, int charge, double tol, int mode,
-                 int2 *runs, unsigned long long *acc);
-// selector words of the postings layout: flat_selector_words_per_block() per block, bit v of word r of a
-// block = keep[id of the block's position r * 64 + v] (behind the list's end: unselected)
-int flat_selector(const int32_t *list_offsets, const int32_t *blk_offsets, int nlist, int64_t nblocks,
-                  const int32_t *ids, const uint8_t *keep, int64_t n, unsigned long long *words);
-int flat_selector_words_per_block();
-int flat_inv_work(const float *xq, int nq, int d, const int32_t *coarse_I, int nprobe,
-                  const int32_t *blk_offsets, const uint32_t *seg_tab, unsigned long long *out_dev);
-int flat_fx_work(const float *xq, int nq, int d, const int32_t *coarse_I, int nprobe,
-                 const int32_t *blk_offsets, const uint8_t *tab8, int tab_stride,
-                 const uint16_t *cnt16, unsigned long long *out_dev);
-uint32_t inv_place_block(const uint32_t *cnt, int d, uint32_t *tab, bool *ok);
-int count_nnz(const float *vecs, int d, int64_t n, int32_t *nnz, int32_t *nnz_max_dev);
-int inv_count(const float *vecs, int d, const int32_t *order, const int32_t *pos_blk, int64_t n,
-              uint32_t *cnt);
-int inv_fill(const float *vecs, int d, const int32_t *order, const int32_t *pos_blk,
-             const uint16_t *pos_loc, int64_t n, const uint32_t *blk_base,
-             const uint32_t *seg_tab, uint32_t *cursor, char *seg_bytes);
-int inv_order(int64_t nblocks, int d, const uint32_t *blk_base, const uint32_t *seg_tab,
-              char *seg_bytes);
-int fx_fill(const float *vecs, int d, const int32_t *order, const int32_t *pos_blk,
-            const uint16_t *pos_loc, int64_t n, const uint32_t *seg_line, uint32_t *cursor,
-            uint32_t *words);
-int fx_order(int64_t ncell, const uint32_t *seg_line, const uint32_t *count, uint32_t *words);
-// fixed-point storage (22 fractional bits) of IVF-Flat components in [0, 1)
-__host__ __device__ inline float fx22_round(float x) {
-  if (!(x >= 0.0f && x < 1.0f)) return x;
-  const float m = rintf(x * 4194304.0f);          // a power of two: exact; ties to even
-  return (m < 4194303.0f ? m : 4194303.0f) * (1.0f / 4194304.0f);
-}
-__host__ __device__ inline bool fx22_on_grid(float x) {
-  return x > 0.0f && x < 1.0f && x * 4194304.0f == rintf(x * 4194304.0f);
-}
-int quantize_fx22(float *x, int64_t n);
+// ---- flat_scan.hip, flat_build.hip, flat_tools.hip (the IVF-Flat postings): flat_postings.hpp
 
 // ---- refine.hip: exact re-rank of a short-list against sparse stored rows
 int refine_stride();
@@ -181,11 +131,9 @@ struct RankWindow {                 // the scope's precursor window; key_slot ==
 int rank_invert(const int32_t *slot_ids, int64_t nslots, int64_t ntotal, int32_t *inv);
 int rank_slot_keys(const int32_t *slot_ids, int64_t nslots, const float *key, int64_t ntotal, float *key_slot);
 // tkey [nq] (0: the target is not in scope) / tscore [nq] are written, counts [nq][2] (rank, scope) added to
-int rank_flat(const float *xq, int nq, int d, int nlist, int64_t ntotal, const int32_t *coarse_I, int nprobe,
-              const int32_t *list_offsets, const int32_t *blk_offsets, const uint32_t *blk_base,
-              const uint32_t *seg_tab, const char *seg_bytes, const int32_t *ids, const int64_t *target,
-              const int32_t *inv, const RankWindow &win, unsigned long long *tkey, float *tscore,
-              unsigned long long *counts, int want_scope);
+int rank_flat(const FlatPostings &P, const float *xq, int nq, int64_t ntotal, const int32_t *coarse_I, int nprobe,
+              const int64_t *target, const int32_t *inv, const RankWindow &win, unsigned long long *tkey,
+              float *tscore, unsigned long long *counts, int want_scope);      // (float postings only)
 int rank_pq(const float *xq, int nq, int d, const float *cbT, int dsub, int nlist, int64_t ntotal,
             const float *coarse_D, const int32_t *coarse_I, int nprobe, const float *coarse_all,
             const int32_t *list_offsets, const int32_t *tile_offsets, const uint8_t *codes_tiled,

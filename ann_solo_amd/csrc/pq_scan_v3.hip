@@ -254,7 +254,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
   const uint32_t chunkA = MM ? (liveA ? (uint32_t)ma * mm_plane + (uint32_t)(rho * 16) : V3_MM_DEAD) : (uint32_t)(rho * 512 + ma * 16);
   const uint32_t chunkB = liveB ? (uint32_t)mb * mm_plane + (uint32_t)(rho * 16) : V3_MM_DEAD;   // (MM only)
 
-  // ---- free-running appends (HistTopK's free_* protocol, as in flat_scan.hip) -------------------
+  // ---- free-running appends (HistTopK's free_* protocol, as in flat_scan.hip: flat_inv_scan_kernel) -----
   // A wave walks its own share of a table chunk (entries wave, wave + NW, ...) with its own register
   // prefetch pipeline and appends what passes the threshold with one reservation per tile; the waves
   // meet only when the key buffer is full (a sync) and at the end of a chunk. The histogram is not

@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "flat_postings.hpp"
 #include "ivf_kernels.hpp"
 #include "pq_tile.hpp"
 #include "topk.hpp"
@@ -107,7 +108,7 @@ __device__ __forceinline__ void rank_flat_block(float *acc, int nb, const uint32
   for (int o = lane; o < nb; o += 64) acc[o] = 0.0f;
   for (int k0 = 0; k0 < K; k0 += 64) {
     const int kk = k0 + lane;
-    const uint32_t w = kk < K ? erow[nzd[kk]] : 0u;      // (start in 64-byte units) << 16 | postings; 0 past the end
+    const uint32_t w = kk < K ? erow[nzd[kk]] : 0u;      // the table word (flat_postings.hpp: inv_word); 0 past the end
     const float qv = kk < K ? nzv[kk] : 0.0f;
     const int n = min(64, K - k0);
     for (int j0 = 0; j0 < n; j0 += RK_U) {               // 64 % RK_U == 0: j0 + u stays a lane
@@ -116,7 +117,7 @@ __device__ __forceinline__ void rank_flat_block(float *acc, int nb, const uint32
 #pragma unroll
       for (int u = 0; u < RK_U; ++u) {
         const uint32_t wj = (uint32_t)__builtin_amdgcn_readlane((int)w, j0 + u);
-        const uint32_t st = (wj >> 16) * 64u, c = wj & 0xffffu;
+        const uint32_t st = inv_word_start(wj) * 64u, c = inv_word_count(wj);
         val[u] = 0.0f, loc[u] = 0u;
         if ((uint32_t)lane < c) {
           val[u] = *reinterpret_cast<const float *>(bptr + st + 4u * (uint32_t)lane);
@@ -126,7 +127,7 @@ __device__ __forceinline__ void rank_flat_block(float *acc, int nb, const uint32
 #pragma unroll
       for (int u = 0; u < RK_U; ++u) {
         const uint32_t wj = (uint32_t)__builtin_amdgcn_readlane((int)w, j0 + u);
-        const uint32_t st = (wj >> 16) * 64u, c = wj & 0xffffu;
+        const uint32_t st = inv_word_start(wj) * 64u, c = inv_word_count(wj);
         const float qj = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, qv), j0 + u));
         if ((uint32_t)lane < c) acc[loc[u]] = __builtin_fmaf(qj, val[u], acc[loc[u]]);
         for (uint32_t p = 64u + (uint32_t)lane; p < c; p += 64u) {
@@ -158,19 +159,7 @@ __global__ __launch_bounds__(64 * NW) void rank_flat_kernel(
   if (!TARGET && tk == 0ull && !want_scope) return;       // not in scope and nobody asks for the scope's size
   // the query's non-zero components, ascending, listed from the dense row (any number of them)
   if (wave == 0) {
-    const float *xrow = xq + (size_t)q * d;
-    int base = 0;
-    for (int j0 = 0; j0 < d; j0 += 64) {
-      const int j = j0 + lane;
-      const float x = j < d ? xrow[j] : 0.0f;
-      const unsigned long long m = __ballot(x != 0.0f);
-      if (x != 0.0f) {
-        const int t = base + __popcll(m & ((1ull << lane) - 1ull));
-        s_nzd[t] = (uint16_t)j;
-        s_nzv[t] = x;
-      }
-      base += __popcll(m);
-    }
+    const int base = list_row_nonzeros(xq + (size_t)q * d, d, lane, 1.0f, s_nzd, s_nzv);
     if (lane == 0) {
       s_cnt[0] = 0u, s_cnt[1] = 0u;
       s_cnt[2] = (unsigned int)base;
@@ -238,17 +227,16 @@ static size_t rank_flat_lds(int nw, int d) {
   return (size_t)nw * FI_BLK * 4 + (size_t)((d + 3) & ~3) * 4 + 16 + (size_t)((d + 7) & ~7) * 2;
 }
 
-int rank_flat(const float *xq, int nq, int d, int nlist, int64_t ntotal, const int32_t *coarse_I, int nprobe,
-              const int32_t *list_offsets, const int32_t *blk_offsets, const uint32_t *blk_base,
-              const uint32_t *seg_tab, const char *seg_bytes, const int32_t *ids, const int64_t *target,
-              const int32_t *inv, const RankWindow &win, unsigned long long *tkey, float *tscore,
-              unsigned long long *counts, int want_scope) {
+int rank_flat(const FlatPostings &P, const float *xq, int nq, int64_t ntotal, const int32_t *coarse_I, int nprobe,
+              const int64_t *target, const int32_t *inv, const RankWindow &win, unsigned long long *tkey,
+              float *tscore, unsigned long long *counts, int want_scope) {
   if (nq <= 0) return ASL_OK;
+  const int d = P.d, nlist = P.nlist;
   if (rank_flat_lds(RK_FLAT_NW, d) > 64 * 1024) return fail(ASL_ERR_CAPACITY, "rank: d=%d does not fit LDS", d);
   const int L = nprobe ? nprobe : nlist;
   const int per = std::max<int>(RK_FLAT_LISTS, (int)cdiv(L, 65535));
-#define RK_ARGS xq, d, nlist, ntotal, coarse_I, nprobe, per, list_offsets, blk_offsets, blk_base, seg_tab, seg_bytes, \
-                ids, target, inv, win, tkey, tscore, counts, want_scope
+#define RK_ARGS xq, d, nlist, ntotal, coarse_I, nprobe, per, P.list_offsets, P.blk_offsets, P.blk_base, P.tab32, \
+                P.seg_bytes, P.ids, target, inv, win, tkey, tscore, counts, want_scope
   hipLaunchKernelGGL((rank_flat_kernel<1, true>), dim3(nq), dim3(64), rank_flat_lds(1, d), stream(), RK_ARGS);
   ASL_CHECK_LAUNCH();
   hipLaunchKernelGGL((rank_flat_kernel<RK_FLAT_NW, false>), dim3(nq, (unsigned)cdiv(L, per)), dim3(64 * RK_FLAT_NW),

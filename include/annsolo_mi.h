@@ -287,7 +287,8 @@ int asl_index_rank(asl_index_t *idx, int32_t nq, const float *xq, const int64_t 
  * |dx| <= 1.2e-7) and stores anything else as given. When ALL stored non-zeros are such values --
  * unit-norm hashed spectra always are -- the inverted lists are kept as 4-byte postings
  * (22-bit numerator | 10-bit local index) in whole 128-byte lines behind a one-byte-per-dimension
- * table (csrc/flat_scan.hip) instead of 6-byte postings behind 4-byte table words. Scores are
+ * table (csrc/flat_postings.hpp: the layouts; csrc/flat_scan.hip: the scan) instead of 6-byte postings
+ * behind 4-byte table words. Scores are
  * the canonical ascending-dimension fp32 fmaf chain over the STORED components either way, so
  * both layouts (and the generic kernels of asl_index_set_scan_variant) return identical ids and
  * score bits for the same stored vectors. Set

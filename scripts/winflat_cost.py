@@ -12,8 +12,9 @@ Algorithmic work of the ranged scan, counted (`ranged_work`): the layout is rebu
 column and the encoded vectors -- the same order (key ascending, id ascending), the same 832-position blocks --
 as the number of postings per (block, dimension); a query's run [lo, hi) comes from the window test itself, and
 over its blocks lo / 832 .. (hi - 1) / 832 and its non-zero dimensions the work is summed by the definitions of
-flat_inv_work_kernel (4-byte table word + 6 bytes per posting) and flat_fx_work_kernel (table byte + 4 bytes per
-posting; lines: the block's table row + the whole lines of the segments). The sum of hi - lo is checked against
+flat_postings_work_kernel (csrc/flat_tools.hip): float postings, 4-byte table word + 6 bytes per posting; fixed-point
+words, table byte + 4 bytes per posting (lines: the block's table row + the whole lines of the segments). The sum of
+hi - lo is checked against
 asl_profile_scanned_vectors. IVF-Flat's own figure comes from asl_index_postings_work over a sample of the batch.
 
   python scripts/winflat_cost.py --out profiles/winflat_cost.json

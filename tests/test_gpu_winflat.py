@@ -14,7 +14,7 @@ from test_gpu_window_scan import _queries, _tie_library
 
 pytestmark = pytest.mark.gpu
 
-FI_BLK, FI_CHUNK = 832, 256            # csrc/ivf_kernels.hpp, csrc/flat_scan.hip
+FI_BLK, FI_CHUNK = 832, 256            # csrc/flat_postings.hpp, csrc/flat_scan.hip
 FIELDS = ('best_row', 'best_score', 'n_candidates', 'pm_count', 'pm_pairs')
 STATE = 'error -3'                     # ASL_ERR_STATE in the message of AnnSoloMiError
 
