@@ -6,6 +6,7 @@ device is present, every compute call raises ``AnnSoloMiError``.
 import ctypes as C
 import os
 import subprocess
+from ctypes import byref
 
 import numpy as np
 
@@ -90,7 +91,16 @@ EXPORTS = [
     'asl_rescore_batch_topn_hist', 'asl_search_batch_topn_hist', 'asl_rescore_knn_topn_hist',
     'asl_decoy_batch',
     'asl_localize_batch',
+    'asl_l2svm_fit', 'asl_linear_scores',
 ]
+
+SVM_MAX_DIM = 63          # include/annsolo_mi.h: ASL_SVM_MAX_DIM
+SVM_MAX_PROBLEMS = 32     # ASL_SVM_MAX_PROBLEMS
+
+
+class AslL2SvmParams(C.Structure):
+    _fields_ = [('C', C.c_double), ('gtol_abs', C.c_double), ('gtol_rel', C.c_double),
+                ('max_newton', C.c_int32)]
 
 
 def build(force: bool = False) -> str:
@@ -296,6 +306,10 @@ def lib():
         if hasattr(L, 'asl_localize_batch'):
             L.asl_localize_batch.argtypes = [C.POINTER(AslPeaks)] + [C.c_void_p] * 6 + [C.c_double, C.c_int32] + \
                 [C.c_void_p] * 9
+        if hasattr(L, 'asl_l2svm_fit'):
+            L.asl_l2svm_fit.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.POINTER(AslL2SvmParams)] + [C.c_void_p] * 4
+            L.asl_linear_scores.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         if hasattr(L, 'asl_index_set_by_residual'):
             L.asl_index_set_by_residual.argtypes = [C.c_void_p, C.c_int32]
             L.asl_index_get_by_residual.argtypes = [C.c_void_p]
@@ -381,3 +395,63 @@ def peaks_struct(p) -> AslPeaks:
     mz = arrs[1]
     n_peaks = int(mz.numel()) if hasattr(mz, 'numel') else int(len(mz))
     return AslPeaks(n, *[ptr(a) for a in arrs], n_peaks)
+
+
+def _as_f64(a, ndim: int, what: str):
+    """``a`` as C-contiguous float64, numpy (host) or torch (wherever it lives)."""
+    if hasattr(a, 'data_ptr'):
+        import torch
+        a = a.to(torch.float64).contiguous()
+    else:
+        a = np.ascontiguousarray(a, np.float64)
+    if a.ndim != ndim:
+        raise ValueError(f'{what}: {ndim} dimensions expected, got {a.ndim}')
+    return a
+
+
+def l2svm_fit(X, label, cw, C: float = 1.0, gtol_abs: float = 1e-9, gtol_rel: float = 0.0,
+              max_newton: int = 100, wb=None):
+    """``asl_l2svm_fit``: P L2-regularised squared-hinge linear SVMs over one matrix ``X [n, d]`` (float64;
+    numpy or torch, host or device). ``label [P, n]`` int8 in {+1, -1, 0} (0: the row is not part of the
+    problem; numpy or torch), ``cw [P, 2]`` the weights of the -1 / +1 class, ``wb [P, d + 1]`` the starting
+    point (default zeros). Returns ``(wb, objective, n_newton, status)`` as numpy arrays; status 0 converged
+    (``||g|| <= max(gtol_abs, gtol_rel * ||g0||)``), 1 iteration cap, 2 line search stalled."""
+    X = _as_f64(X, 2, 'X')
+    n, d = int(X.shape[0]), int(X.shape[1])
+    if hasattr(label, 'data_ptr'):
+        import torch
+        label = label.to(torch.int8).contiguous()
+    else:
+        label = np.ascontiguousarray(label, np.int8)
+    if label.ndim != 2 or int(label.shape[1]) != n:
+        raise ValueError(f'label: [P, {n}] expected, got {tuple(label.shape)}')
+    P = int(label.shape[0])
+    cw = np.ascontiguousarray(cw, np.float64)
+    if cw.shape != (P, 2):
+        raise ValueError(f'cw: [{P}, 2] expected, got {cw.shape}')
+    wb = np.zeros((P, d + 1), np.float64) if wb is None else np.array(wb, np.float64, order='C')
+    if wb.shape != (P, d + 1):
+        raise ValueError(f'wb: [{P}, {d + 1}] expected, got {wb.shape}')
+    objective, n_newton, status = np.zeros(P, np.float64), np.zeros(P, np.int32), np.zeros(P, np.int32)
+    params = AslL2SvmParams(float(C), float(gtol_abs), float(gtol_rel), int(max_newton))
+    check(lib().asl_l2svm_fit(ptr(X) if n else None, n, d, ptr(label) if n else None, ptr(cw), P,
+                              byref(params), ptr(wb), ptr(objective), ptr(n_newton), ptr(status)))
+    return wb, objective, n_newton, status
+
+
+def linear_scores(X, wb):
+    """``asl_linear_scores``: ``out[p, i] = wb[p, :d] . X[i] + wb[p, d]``, ``[P, n]`` float64; lives where
+    ``X`` lives (numpy, or a torch tensor on ``X``'s device)."""
+    X = _as_f64(X, 2, 'X')
+    n, d = int(X.shape[0]), int(X.shape[1])
+    wb = np.ascontiguousarray(wb, np.float64)
+    if wb.ndim != 2 or wb.shape[1] != d + 1:
+        raise ValueError(f'wb: [P, {d + 1}] expected, got {wb.shape}')
+    P = int(wb.shape[0])
+    if hasattr(X, 'data_ptr'):
+        import torch
+        out = torch.empty((P, n), dtype=torch.float64, device=X.device)
+    else:
+        out = np.empty((P, n), np.float64)
+    check(lib().asl_linear_scores(ptr(X) if n else None, n, d, ptr(wb), P, ptr(out) if n else None))
+    return out

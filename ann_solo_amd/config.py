@@ -5,7 +5,7 @@
 (``index``, ``pq_m``, ``pq_bits``, ``refine_k``, ``kmeans_niter``, ``ann_seed``, ``num_gpus``,
 ``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``, ``pq_by_residual``,
 ``precursor_window_open``, ``fragment_tolerance_unit``, ``score_stats``, ``device_decoys``,
-``decoy_tolerance_unit``, ``localize_modifications``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``decoy_tolerance_unit``, ``localize_modifications``, ``device_fdr``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -64,9 +64,9 @@ class Config:
     fragment_mz_tolerance: float = 0.02
     allow_peak_shifts: bool = False
     no_gpu: bool = False
-    # SSM scoring (config.py:158-164): carried for the caller's scorer. The engine itself has no
-    # FDR model (out of scope): ``score_ssms=`` is injected; without one every SSM is
-    # accepted with its cosine as the score and q = 0.
+    # SSM scoring (config.py:158-164): carried for the caller's scorer, ``score_ssms=``; without one every
+    # SSM is accepted with its cosine as the score and q = 0 -- unless ``device_fdr`` (below) is set, which
+    # makes the engine build its own scorer from this value.
     model: Optional[str] = None
     # --- additive flags of this implementation
     index: str = 'ivfflat'                  # 'ivfflat' (the reference's index type) | 'ivfpq' | 'winflat' (exact
@@ -122,6 +122,12 @@ class Config:
     # fragment_tolerance_unit, ppm being of the THEORETICAL fragment m/z here. A post-step: identifications,
     # scores, FDR, files and every hash are what they are without it
     localize_modifications: bool = False
+    # the engine's own FDR step (fdr.py; DESIGN.md 3 "Rescoring model"): without an injected ``score_ssms`` the
+    # cascade levels are gated by ``model`` -- None / 'none': target-decoy q-values on the cosine; 'svm': a
+    # Percolator-like linear SVM over the reference's feature table, trained on the device -- at ``fdr``, open
+    # level grouped with ``fdr_min_group_size``. 'rf' is not provided (ValueError). An injected callable always
+    # wins; off: every SSM is accepted with q = 0, as ever
+    device_fdr: bool = False
 
     MAX_PEAKS = 256     # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
@@ -180,6 +186,14 @@ class Config:
         self.localize_modifications = bool(self.localize_modifications)
         if self.localize_modifications and self.num_gpus and int(self.num_gpus) > 1:
             raise ValueError('localize_modifications does not run on a sharded index (num_gpus > 1)')
+        self.device_fdr = bool(self.device_fdr)
+        if self.device_fdr:
+            if self.model not in (None, 'none', 'svm'):
+                raise ValueError(f"device_fdr: model = {self.model!r} is not provided; None / 'none' (q-values on "
+                                 "the cosine) or 'svm' (the Percolator-like linear SVM)")
+            if self.num_gpus and int(self.num_gpus) > 1:
+                # (a level's SSMs are gathered on rank 0 only after its gate)
+                raise ValueError('device_fdr does not run on a sharded index (num_gpus > 1)')
         if self.precursor_window_open is not None:
             try:
                 lo, hi = (float(v) for v in self.precursor_window_open)
@@ -340,3 +354,9 @@ def add_arguments(parser) -> None:
                              'the SSMs gain mod_mass, mod_site_lo / _hi (0-based residues), mod_site_score, '
                              '_margin and _gain; identifications, scores and files do not change; one GPU '
                              '(default: off)')
+    parser.add_argument('--device_fdr', action='store_true', default=d.device_fdr,
+                        help="gate both cascade levels by the engine's own FDR step at --fdr: with --model none "
+                             'target-decoy q-values on the cosine, with --model svm a Percolator-like linear SVM '
+                             "over the reference's SSM features, trained on the GPU (--model rf is not provided); "
+                             'open-level q-values per mass-difference group of --fdr_min_group_size; one GPU '
+                             '(default: off -- the caller scores the SSMs)')

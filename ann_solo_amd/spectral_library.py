@@ -177,6 +177,9 @@ class SpectralLibrary:
         self._current_index: Tuple[Optional[int], Optional[faiss.Index]] = (None, None)
         self._query_reader = query_reader or _reference_query_reader
         self._score_ssms = score_ssms
+        if cfg.device_fdr and score_ssms is None:       # the engine's own FDR step; an injected callable wins
+            from . import fdr
+            self._score_ssms = fdr.make_scorer(cfg, self.device)
         self._dist = None
         self._library_reader = None
         self.library_meta: Optional[Dict[int, list]] = None
@@ -411,6 +414,9 @@ class SpectralLibrary:
         import torch.distributed as dist
         world = dist.get_world_size(group) if dist.is_initialized() else 1
         rank = dist.get_rank(group) if dist.is_initialized() else 0
+        if world > 1 and self.config.device_fdr:
+            # (a level's SSMs are gathered on rank 0 only after its gate: every rank would train on its own)
+            raise ValueError('enable_sharding: device_fdr does not run on a sharded index')
         if self._dist is not None and self._dist.world > 1:
             raise RuntimeError('enable_sharding: the indexes are sharded already')
         self._dist = SimpleNamespace(group=group, world=world, rank=rank, backends={})
@@ -825,8 +831,10 @@ class SpectralLibrary:
         mode)`` with a list of SSM records it assigns ``search_engine_score`` / ``q`` and
         returns the SSMs to keep; a callable with the attribute ``columnar = True`` receives the
         ``SSMTable`` itself instead, writes ``table.q`` (and ``table.score``) and may return a
-        keep-mask -- no per-SSM Python objects on the search path. Default: cosine as the score,
-        q = 0 (everything accepted).
+        keep-mask -- no per-SSM Python objects on the search path; one with ``uses_features = True``
+        also finds the batches' 33 similarity columns in ``table.features``. Default: with
+        ``Config.device_fdr`` the engine's own scorer (fdr.py: ``CosineTDC`` or ``PercolatorTDC`` by
+        ``Config.model``), else cosine as the score, q = 0 (everything accepted).
 
         Returns the identifications (one per query identifier) as an ``SSMTable``: a sequence
         of SSM records materialised on access (``len``, iteration, indexing), ready for
@@ -1011,11 +1019,23 @@ class SpectralLibrary:
                 self.set_pipeline(False)         # synchronises first
         # default search-engine score: the cosine over the winner's peak matches -- every batch's
         # kernel is enqueued before the first result is copied back (a copy waits for its kernel)
-        cosines = [spectrum_similarity.ssm_cosine(q, self.partitions[charge].spectra, res.best_row,
-                                                  res.pm_pairs, res.pm_count)
-                   for charge, sel, q, res in pending]
-        for (charge, sel, q, res), cos in zip(pending, cosines):
-            table.add_batch(charge, sel, _to_np(res.best_row), _to_np(cos), res)
+        if getattr(score_ssms, 'uses_features', False):
+            # a scorer that learns from the SSMs (fdr.PercolatorTDC): all 33 similarity columns of every batch;
+            # column 0 has the bits of ssm_cosine, so the score does not change
+            cfg = self.config
+            feats = [spectrum_similarity.ssm_features(q, self.partitions[charge].spectra, res.best_row,
+                                                      res.pm_pairs, res.pm_count, cfg.min_mz, cfg.max_mz,
+                                                      cfg.bin_size)
+                     for charge, sel, q, res in pending]
+            for (charge, sel, q, res), F in zip(pending, feats):
+                F = _to_np(F)
+                table.add_batch(charge, sel, _to_np(res.best_row), F[:, 0], res, F)
+        else:
+            cosines = [spectrum_similarity.ssm_cosine(q, self.partitions[charge].spectra, res.best_row,
+                                                      res.pm_pairs, res.pm_count)
+                       for charge, sel, q, res in pending]
+            for (charge, sel, q, res), cos in zip(pending, cosines):
+                table.add_batch(charge, sel, _to_np(res.best_row), _to_np(cos), res)
         table.open_level[:] = mode == 'open'
         if uid is not None:
             table = table.first_per_uid(uid)
@@ -1054,6 +1074,13 @@ class SpectralLibrary:
 
 def _to_np(a):
     return a.detach().cpu().numpy() if hasattr(a, 'detach') else np.asarray(a)
+
+
+def _cat_features(blocks) -> np.ndarray:
+    """``SSMTable.features`` of several row blocks: [len, 33], or [len, 0] when none carries the columns (a
+    block without them under one with them, an empty level say, is NaN)."""
+    width = max(b.shape[1] for b in blocks)
+    return np.concatenate([b if b.shape[1] == width else np.full((len(b), width), np.nan) for b in blocks])
 
 
 def open_window_intervals(precursor_mz, charge: int, window_da) -> np.ndarray:
@@ -1127,7 +1154,10 @@ class SSMTable:
     ``mod_site_hi`` (first and last of the equally best sites, 0-based residue indices),
     ``mod_site_score`` (the summed intensity of the best site's plain and shifted b / y fragments),
     ``mod_site_margin`` (best minus the best different score; 0 when every site ties) and ``mod_site_gain``
-    (best minus the score without the mass). Everywhere else: NaN and -1."""
+    (best minus the score without the mass). Everywhere else: NaN and -1.
+
+    ``features[len, 33]`` (float64) holds the similarity columns of ``spectrum_similarity.FEATURE_NAMES`` when
+    the level ran for a scorer that learns from them (``fdr.PercolatorTDC``); ``[len, 0]`` otherwise."""
 
     # columns that are filled after the batches are filed: (name, dtype, default)
     _LATE = (('open_level', bool, False), ('mod_mass', np.float64, np.nan), ('mod_site_lo', np.int32, -1),
@@ -1142,6 +1172,7 @@ class SSMTable:
         self.delta_score = np.zeros(0, np.float64)
         self.n_scored = np.zeros(0, np.int32)
         self.expect = np.zeros(0, np.float64)
+        self.features = np.zeros((0, 0), np.float64)
         self._alt_batches: list = []             # per batch: its TopnBatchResult (None: single winner)
         self.charge = np.zeros(0, np.int32)
         self.qrow = np.zeros(0, np.int64)
@@ -1155,8 +1186,10 @@ class SSMTable:
         for name, dt, _ in self._LATE:
             setattr(self, name, np.zeros(0, dt))
 
-    def add_batch(self, charge, qrows, best_row, score, res) -> None:
+    def add_batch(self, charge, qrows, best_row, score, res, features=None) -> None:
         hit = np.nonzero(best_row >= 0)[0]       # queries without a candidate: no SSM (:359)
+        feats = np.zeros((len(hit), 0)) if features is None else np.asarray(features, np.float64)[hit]
+        self.features = _cat_features([self.features, feats])
         b = len(self._batches)
         self._batches.append(res)
         top = getattr(res, 'topn', None)
@@ -1208,7 +1241,7 @@ class SSMTable:
         out = SSMTable(self.query_meta, self.library_meta, self.n_alt)
         out._batches, out._alt_batches = self._batches, self._alt_batches
         for name in ('charge', 'qrow', 'lib_row', 'score', 'q', 'batch', 'pos', 'alt_lib_row', 'alt_score',
-                     'delta_score', 'n_scored', 'expect') + tuple(c[0] for c in self._LATE):
+                     'delta_score', 'n_scored', 'expect', 'features') + tuple(c[0] for c in self._LATE):
             setattr(out, name, getattr(self, name)[idx])
         return out
 
@@ -1227,6 +1260,7 @@ class SSMTable:
                 setattr(out, name, np.concatenate([getattr(out, name), getattr(t, name)]))
             out.batch = np.concatenate([out.batch, t.batch + shift])
             shift += len(t._batches)
+        out.features = _cat_features([t.features for t in tables])
         return out
 
     def uids(self, uid) -> np.ndarray:

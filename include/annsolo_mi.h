@@ -739,6 +739,44 @@ int asl_ssm_cosine_batch(const asl_peaks_t *queries, const asl_peaks_t *library,
                          const int32_t *pm_count /* [nq] */, int32_t pm_stride,
                          double *cosine /* [nq] */);
 
+/* ------------------------------------------------------------------ SSM rescoring model
+ * The model behind utils.score_ssms(model = 'svm') (/root/reference/src/ann_solo/utils.py:152-155: mokapot's
+ * PercolatorModel, a LinearSVC(dual = False)): P L2-regularised squared-hinge linear SVMs over one feature
+ * matrix, by a generalised Newton method with Armijo backtracking, all in fp64 (csrc/l2svm.hip). Per
+ * iteration X is streamed twice (Newton pass, line pass), each row fetched once for all P problems; partial
+ * sums are added in a fixed order, so two calls with the same inputs give the same bits. */
+#define ASL_SVM_MAX_DIM      63   /* d; the bias makes D = d + 1 <= 64 */
+#define ASL_SVM_MAX_PROBLEMS 32
+typedef struct {
+  double C;                   /* LinearSVC's C */
+  double gtol_abs, gtol_rel;  /* stop when ||g||_2 <= max(gtol_abs, gtol_rel * ||g at the start||_2) */
+  int32_t max_newton;         /* iteration cap per problem */
+} asl_l2svm_params_t;
+/* P problems over ONE matrix. label[p, i] in {+1, -1, 0}; 0 = row i is not part of problem p.
+ * cw[p, 0] / cw[p, 1]: weight of the -1 / +1 class (sklearn's class_weight).
+ * Minimises, per problem, over w in R^d and b:
+ *   f = 0.5 * (w.w + b*b) + C * sum_i cw[p, cls(i)] * max(0, 1 - label[p,i] * (w.x_i + b))^2
+ * This is LinearSVC(penalty='l2', loss='squared_hinge', dual=False, fit_intercept=True,
+ * intercept_scaling=1): the bias is regularised. wb[p, 0..d) = w, wb[p, d] = b; read as the starting
+ * point, written with the result. objective[p] = f at the result; n_newton[p] = steps taken.
+ * Per step: g and H = I + 2 C sum cw x~x~^T over the rows with a positive margin deficit, H s = -g by
+ * Cholesky on the host, then the first t in 1, 1/2 .. 2^-7 with f(w~ + t s) <= f(w~) + 1e-4 t g.s.
+ * status[p]: 0 converged, 1 iteration cap, 2 line search stalled.
+ * X, label: host or device memory, as the other entry points detect it; so are the small arrays.
+ * Checked on the host before anything is launched or written: d > 63 or P > 32: ASL_ERR_CAPACITY;
+ * d < 1, P < 1, n < 0, a label outside {-1, 0, +1}, a negative or non-finite class weight or C, a
+ * negative or NaN tolerance or cap, a non-finite starting point: ASL_ERR_INVALID. A non-finite X is the
+ * caller's precondition: it is not checked and gives non-finite results, never a fault. n = 0, a problem
+ * whose labels are all 0 or of one class only are legal (no rows: w~ = 0, objective 0, status 0). */
+int asl_l2svm_fit(const double *X /* [n, d] row-major */, int64_t n, int32_t d,
+                  const int8_t *label /* [P, n] */, const double *cw /* [P, 2] */, int32_t P,
+                  const asl_l2svm_params_t *params, double *wb /* [P, d + 1] */,
+                  double *objective /* [P] */, int32_t *n_newton /* [P] */, int32_t *status /* [P] */);
+/* out[p, i] = wb[p, 0..d) . x_i + wb[p, d]: the decision function of P models over X (X, wb, out: host
+ * or device memory; the same limits on d, P and n) */
+int asl_linear_scores(const double *X, int64_t n, int32_t d, const double *wb, int32_t P,
+                      double *out /* [P, n] */);
+
 /* ------------------------------------------------------------------ hot path
  * One batch of same-charge queries through
  *   SpectralLibrary._search_batch / _get_library_candidates
