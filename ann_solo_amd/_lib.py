@@ -90,7 +90,7 @@ EXPORTS = [
     'asl_library_set_selection', 'asl_index_set_selector', 'asl_index_search_selected',
     'asl_rescore_batch_topn_hist', 'asl_search_batch_topn_hist', 'asl_rescore_knn_topn_hist',
     'asl_decoy_batch',
-    'asl_localize_batch',
+    'asl_localize_batch', 'asl_deplete_batch',
     'asl_l2svm_fit', 'asl_linear_scores',
 ]
 
@@ -306,6 +306,9 @@ def lib():
         if hasattr(L, 'asl_localize_batch'):
             L.asl_localize_batch.argtypes = [C.POINTER(AslPeaks)] + [C.c_void_p] * 6 + [C.c_double, C.c_int32] + \
                 [C.c_void_p] * 9
+        if hasattr(L, 'asl_deplete_batch'):
+            L.asl_deplete_batch.argtypes = [C.POINTER(AslPeaks), C.POINTER(AslPeaks), C.c_void_p, C.c_double, C.c_int,
+                                            C.c_int32, C.c_double, C.c_int32] + [C.c_void_p] * 6
         if hasattr(L, 'asl_l2svm_fit'):
             L.asl_l2svm_fit.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                         C.POINTER(AslL2SvmParams)] + [C.c_void_p] * 4

@@ -5,7 +5,8 @@
 (``index``, ``pq_m``, ``pq_bits``, ``refine_k``, ``kmeans_niter``, ``ann_seed``, ``num_gpus``,
 ``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``, ``pq_by_residual``,
 ``precursor_window_open``, ``fragment_tolerance_unit``, ``score_stats``, ``device_decoys``,
-``decoy_tolerance_unit``, ``localize_modifications``, ``device_fdr``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``decoy_tolerance_unit``, ``localize_modifications``, ``device_fdr``, ``chimeric_search``,
+``chimeric_window``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -128,6 +129,14 @@ class Config:
     # level grouped with ``fdr_min_group_size``. 'rf' is not provided (ValueError). An injected callable always
     # wins; off: every SSM is accepted with q = 0, as ever
     device_fdr: bool = False
+    # chimeric spectra (chimeric.py; DESIGN.md 3 "Chimeric search"): after the last cascade level every accepted
+    # identification's explained peaks are removed from its query and the residue is searched once more, without
+    # peak shifts, against the library rows of the same charge inside the query's isolation window -- the
+    # ``isolation_window`` of the query metadata, else ``chimeric_window`` (full width, m/z) around its precursor.
+    # Matches of another peptide are appended with ``chimeric_rank`` 1. Off: nothing is launched and every
+    # result, hash and output byte is what it is without the switch
+    chimeric_search: bool = False
+    chimeric_window: float = 2.0
 
     MAX_PEAKS = 256     # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
@@ -194,6 +203,12 @@ class Config:
             if self.num_gpus and int(self.num_gpus) > 1:
                 # (a level's SSMs are gathered on rank 0 only after its gate)
                 raise ValueError('device_fdr does not run on a sharded index (num_gpus > 1)')
+        self.chimeric_search = bool(self.chimeric_search)
+        self.chimeric_window = float(self.chimeric_window)
+        if not self.chimeric_window >= 0.0:     # (NaN fails too)
+            raise ValueError(f'chimeric_window = {self.chimeric_window}: a width in m/z, >= 0')
+        if self.chimeric_search and self.num_gpus and int(self.num_gpus) > 1:
+            raise ValueError('chimeric_search does not run on a sharded index (num_gpus > 1)')
         if self.precursor_window_open is not None:
             try:
                 lo, hi = (float(v) for v in self.precursor_window_open)
@@ -360,3 +375,12 @@ def add_arguments(parser) -> None:
                              "over the reference's SSM features, trained on the GPU (--model rf is not provided); "
                              'open-level q-values per mass-difference group of --fdr_min_group_size; one GPU '
                              '(default: off -- the caller scores the SSMs)')
+    parser.add_argument('--chimeric_search', action='store_true', default=d.chimeric_search,
+                        help='after the last cascade level, remove the peaks every accepted identification explains '
+                             'from its query spectrum and search the residue once more (no peak shifts) among the '
+                             "library spectra of the same charge inside the query's isolation window; a match of "
+                             'another peptide is reported as a second PSM of the spectrum (chimeric_rank 1, '
+                             'explained_intensity); one GPU (default: off)')
+    parser.add_argument('--chimeric_window', default=d.chimeric_window, type=float,
+                        help="with --chimeric_search: full width in m/z of the window around the query's precursor "
+                             'when the queries carry no isolation_window (default: %(default)s)')

@@ -417,6 +417,8 @@ class SpectralLibrary:
         if world > 1 and self.config.device_fdr:
             # (a level's SSMs are gathered on rank 0 only after its gate: every rank would train on its own)
             raise ValueError('enable_sharding: device_fdr does not run on a sharded index')
+        if world > 1 and self.config.chimeric_search:
+            raise ValueError('enable_sharding: chimeric_search does not run on a sharded index')
         if self._dist is not None and self._dist.world > 1:
             raise RuntimeError('enable_sharding: the indexes are sharded already')
         self._dist = SimpleNamespace(group=group, world=world, rank=rank, backends={})
@@ -483,21 +485,26 @@ class SpectralLibrary:
         return self.config.mode == 'ann' and mode == 'open' and charge in self._ann_filenames
 
     def _search_batch(self, queries: PackedSpectra, charge: int, mode: str,
-                      want_knn: bool = False, device_out: bool = False, windows=None) -> Optional[BatchResult]:
+                      want_knn: bool = False, device_out: bool = False, windows=None,
+                      shifts: Optional[bool] = None) -> Optional[BatchResult]:
         """One batch of same-charge, processed query spectra (spectral_library.py:328-370):
         through the device hot path of this GPU, or -- after ``enable_sharding`` on more than
         one rank -- over all ranks. Returns None when the library has no spectra of that charge
         (:411-412). ``windows``: None, or one closed interval (lo, hi) of library precursor m/z per query
         ([nq, 2] float64, numpy or a device tensor) -- the candidates are then the rows whose float32
         precursor m/z lies inside it (``ASL_TOL_INTERVAL``), whatever the level's tolerance is; scores
-        still use the query's own precursor m/z. One GPU."""
+        still use the query's own precursor m/z. ``shifts``: None, or whether the dot product shifts peaks,
+        whatever ``Config.allow_peak_shifts`` says (the chimeric level: False). One GPU, both."""
         d = getattr(self, '_dist', None)
         if d is None or d.world == 1:
+            if shifts is not None:
+                return self._search_batch_local(queries, charge, mode, want_knn, device_out, windows=windows,
+                                                shifts=shifts)
             if windows is None:     # (engines that override _search_batch_local with its older signature)
                 return self._search_batch_local(queries, charge, mode, want_knn, device_out)
             return self._search_batch_local(queries, charge, mode, want_knn, device_out, windows=windows)
-        if windows is not None:
-            raise ValueError('windows= does not run on a sharded index')
+        if windows is not None or shifts is not None:
+            raise ValueError('windows= / shifts= do not run on a sharded index')
         tol_val, tol_mode = self._tolerance(mode)
         if tol_mode not in ('Da', 'ppm'):
             raise ValueError('Unknown precursor tolerance mode')
@@ -510,7 +517,8 @@ class SpectralLibrary:
 
     def _search_batch_local(self, queries: PackedSpectra, charge: int, mode: str,
                             want_knn: bool = False, device_out: bool = False,
-                            pm_stride: Optional[int] = None, windows=None) -> Optional[BatchResult]:
+                            pm_stride: Optional[int] = None, windows=None,
+                            shifts: Optional[bool] = None) -> Optional[BatchResult]:
         """One batch on this GPU alone (the index must not be sharded for open searches)."""
         tol_val, tol_mode = self._tolerance(mode)
         if tol_mode not in ('Da', 'ppm'):
@@ -541,7 +549,8 @@ class SpectralLibrary:
         P = _lib.AslSearchParams(min_bound, cfg.bin_size, HASH_SEED, k, self._num_probe, charge,
                                  float(tol_val), 0 if tol_mode == 'Da' else 1,
                                  cfg.fragment_mz_tolerance,
-                                 score_flags(cfg.allow_peak_shifts, cfg.fragment_tolerance_unit),
+                                 score_flags(cfg.allow_peak_shifts if shifts is None else shifts,
+                                             cfg.fragment_tolerance_unit),
                                  int(use_ann))
         windows = self._interval_windows(P, windows, nq)
         _lib.check(_lib.lib().asl_search_batch(
@@ -645,13 +654,14 @@ class SpectralLibrary:
     def search_batch_topn(self, queries: PackedSpectra, charge: int, mode: str, n_best: int,
                           want_knn: bool = False, device_out: bool = False,
                           pm_stride: Optional[int] = None, distinct: bool = False,
-                          windows=None, score_hist: bool = False) -> Optional[TopnBatchResult]:
+                          windows=None, score_hist: bool = False,
+                          shifts: Optional[bool] = None) -> Optional[TopnBatchResult]:
         """``_search_batch_local`` for the ``n_best`` (1 .. 16) best library matches of every query
         (``asl_search_batch_topn``): every cascade level and index mode, on this GPU alone.
         Synchronous -- the call never joins the two-stream pipeline. Rank 0 (and ``n_candidates``,
         ``knn``) is what ``_search_batch_local`` returns, bit for bit. ``distinct``: one rank per
         group of ``set_match_groups`` (``asl_search_batch_topn_distinct``; an error without groups).
-        ``windows``: as in ``_search_batch``. ``score_hist``: the result also carries the histogram of
+        ``windows``, ``shifts``: as in ``_search_batch``. ``score_hist``: the result also carries the histogram of
         every query's candidate scores, ``[nq, 128]`` int32 (``asl_search_batch_topn_hist``; 128 bins of
         width 1/128, ``score_stats.bin_of``), whose rows sum to ``n_candidates``; nothing else changes."""
         d = getattr(self, '_dist', None)
@@ -684,7 +694,8 @@ class SpectralLibrary:
         P = _lib.AslSearchParams(min_bound, cfg.bin_size, HASH_SEED, k, self._num_probe, charge,
                                  float(tol_val), 0 if tol_mode == 'Da' else 1,
                                  cfg.fragment_mz_tolerance,
-                                 score_flags(cfg.allow_peak_shifts, cfg.fragment_tolerance_unit),
+                                 score_flags(cfg.allow_peak_shifts if shifts is None else shifts,
+                                             cfg.fragment_tolerance_unit),
                                  int(use_ann))
         windows = self._interval_windows(P, windows, nq)
         if score_hist:
@@ -836,6 +847,11 @@ class SpectralLibrary:
         ``Config.device_fdr`` the engine's own scorer (fdr.py: ``CosineTDC`` or ``PercolatorTDC`` by
         ``Config.model``), else cosine as the score, q = 0 (everything accepted).
 
+        With ``Config.chimeric_search`` one more level follows the last one (``_chimeric_level``): the peaks
+        every accepted identification explains are taken out of its query and the residue is searched again
+        inside the query's isolation window; what it finds is appended with ``chimeric_rank`` 1. The table may
+        then hold TWO SSMs for one query identifier (mzTab allows several PSMs per spectrum).
+
         Returns the identifications (one per query identifier) as an ``SSMTable``: a sequence
         of SSM records materialised on access (``len``, iteration, indexing), ready for
         ``writer.write_mztab``; its columns (``charge, qrow, lib_row, score, q``) are there for
@@ -856,6 +872,8 @@ class SpectralLibrary:
         # (message parsed by the reference's notebooks: kept verbatim, spectral_library.py:243)
         logging.info('%d spectra identified after the standard search', n_identified)
         if not do_cascade_open:
+            if cfg.chimeric_search:
+                t1 = self._chimeric_level(t1, query_spectra, query_meta, library_meta, score_ssms, uid, n_identified)
             return t1
         t1 = t1.take(t1.q < cfg.fdr)
         # cascade level 2: open search on the queries not identified so far (:249-259)
@@ -872,6 +890,8 @@ class SpectralLibrary:
         n_identified += int((t2.q < cfg.fdr).sum())
         logging.info('%d spectra identified after the open search', n_identified)   # :257
         out = SSMTable.concat([t1, t2])
+        if cfg.chimeric_search:             # one more level on what the winners leave; off: nothing is launched
+            out = self._chimeric_level(out, query_spectra, query_meta, library_meta, score_ssms, uid, n_identified)
         if cfg.localize_modifications:      # a post-step on the identifications; off: nothing is launched
             self.localize_modifications(out, query_spectra)
         return out
@@ -938,6 +958,74 @@ class SpectralLibrary:
                             'the first: %s', n_bad, first_bad)
         return table
 
+    def _chimeric_level(self, table: 'SSMTable', query_spectra, query_meta, library_meta, score_ssms, uid,
+                        n_identified: int = 0) -> 'SSMTable':
+        """``Config.chimeric_search``: ``table`` followed by the SSMs of one more level on the residues of its
+        accepted identifications (``q < fdr``). Per charge, the queries of those SSMs are depleted by their
+        winners (chimeric.py, 32 768 SSMs per kernel launch; the flag word is the search's own) and the valid
+        residues are searched through ``_search_cascade`` -- window path, never the ANN index, no peak shifts
+        (the precursor offset inside an isolation window is no modification), the fragment tolerance unit
+        honoured -- against the rows of the same charge whose precursor m/z lies in the query's
+        ``isolation_window`` when every query of the charge has one, else within ``chimeric_window / 2`` of
+        its precursor m/z. A residue whose best match is the primary's peptide again (``peptide``, else
+        ``sequence`` of the library metadata; without either: the library row) is dropped before the scorer,
+        which is called with mode ``'std'``. The new rows carry ``chimeric_rank`` 1 and
+        ``explained_intensity`` = 1 - the depletion's ``kept_energy``; ``open_level`` is False, so they are
+        not localised. Their peak matches index the RESIDUE's peaks. One GPU."""
+        from . import chimeric
+        d = getattr(self, '_dist', None)
+        if d is not None and d.world > 1:
+            raise ValueError('chimeric_search does not run on a sharded index')
+        cfg = self.config
+        accepted = np.nonzero(table.q < cfg.fdr)[0]
+        flags = score_flags(cfg.allow_peak_shifts, cfg.fragment_tolerance_unit)
+        lvl = CascadeLevel('chimeric', {}, {}, {}, shifts=False)
+        primary, explained = {}, {}
+        for z in query_spectra:
+            idx = accepted[table.charge[accepted] == z]
+            if len(idx) == 0 or z not in self.partitions:
+                continue
+            qs = query_spectra[z]
+            qrows, lib_rows = table.qrow[idx], table.lib_row[idx].astype(np.int64)
+            pack, src, energy = chimeric.residues(qs.select(torch.as_tensor(qrows)), self.partitions[z].spectra,
+                                                  lib_rows, cfg.fragment_mz_tolerance, flags, cfg.min_peaks,
+                                                  cfg.min_mz_range, self.device)
+            if pack.n == 0:
+                continue
+            lvl.spectra[z], lvl.qrow[z], primary[z] = pack, qrows[src], lib_rows[src]
+            explained[z] = 1.0 - energy[src].astype(np.float64)
+            meta = query_meta.get(z) if hasattr(query_meta, 'get') else None
+            iso = isolation_windows(meta, qs.n)
+            lvl.windows[z] = (iso[lvl.qrow[z]] if iso is not None else
+                              chimeric_window_intervals(_to_np(qs.precursor_mz)[lvl.qrow[z]], cfg.chimeric_window))
+        if not lvl.spectra:         # nothing accepted, or no residue is a valid spectrum: no level, no scorer call
+            logging.info('%d spectra identified after the chimeric search', n_identified)
+            return table
+
+        def peptide(z, row):
+            rec = library_meta[z][int(row)]
+            get = rec.get if hasattr(rec, 'get') else (lambda k: None)
+            for name in ('peptide', 'sequence'):
+                v = get(name)
+                if v is not None:
+                    return v
+            return ('row', int(row))
+
+        def other_peptide(z, sel, best):
+            return np.fromiter((r >= 0 and peptide(z, r) != peptide(z, p) for r, p in zip(best, primary[z][sel])),
+                               bool, len(best))
+        lvl.keep = other_peptide
+        rows = {z: np.arange(p.n, dtype=np.int64) for z, p in lvl.spectra.items()}
+        t3 = self._search_cascade(query_spectra, query_meta, library_meta, rows, 'std', score_ssms, uid, level=lvl)
+        t3.chimeric_rank[:] = 1
+        for z in lvl.spectra:
+            m = t3.charge == z
+            order = np.argsort(lvl.qrow[z], kind='stable')      # (one accepted SSM per query of a charge set)
+            t3.explained_intensity[m] = explained[z][order][np.searchsorted(lvl.qrow[z][order], t3.qrow[m])]
+        n_identified += int((t3.q < cfg.fdr).sum())
+        logging.info('%d spectra identified after the chimeric search', n_identified)
+        return SSMTable.concat([table, t3])
+
     def _open_level_windows(self, qs: PackedSpectra, query_meta, charge: int) -> Optional[np.ndarray]:
         """The open level's per-query intervals for one charge set ([qs.n, 2] float64), or None for the
         symmetric window of ``precursor_tolerance_mass_open``: the queries' isolation windows when every
@@ -956,11 +1044,15 @@ class SpectralLibrary:
         return open_window_intervals(_to_np(qs.precursor_mz), charge, self.config.precursor_window_open)
 
     def _search_cascade(self, query_spectra, query_meta, library_meta, rows_by_charge, mode,
-                        score_ssms=None, uid=None) -> 'SSMTable':
+                        score_ssms=None, uid=None, level: Optional['CascadeLevel'] = None) -> 'SSMTable':
         """One cascade level (:264-326): batches of ``batch_size`` same-charge queries through
         ``_search_batch``; per query identifier the FIRST match is kept (the reference compares
         ``search_engine_score`` values that are still NaN at this point, :312-316, so a later
-        duplicate never replaces an earlier one). Host work is per batch, not per query."""
+        duplicate never replaces an earlier one). Host work is per batch, not per query.
+        ``level``: None for the reference's two levels, or what a further level changes (``CascadeLevel``):
+        the spectra it searches in place of ``query_spectra`` (``rows_by_charge`` then index those), their
+        rows in ``query_spectra`` / ``query_meta`` for the table, their precursor intervals, the peak shifts
+        and which matches never reach the scorer. ``mode`` stays what the batches and the scorer are given."""
         import time
         from . import spectrum_similarity
         bs = self.config.batch_size
@@ -984,10 +1076,15 @@ class SpectralLibrary:
         try:
             for charge, rows in rows_by_charge.items():
                 rows = np.asarray(rows, np.int64)
-                qs = query_spectra[charge]
+                qs = query_spectra[charge] if level is None else level.spectra[charge]
                 # open level: per-query intervals instead of the symmetric window (isolation windows of the
                 # queries' metadata, else Config.precursor_window_open); None: the level's tolerance
-                level_win = self._open_level_windows(qs, query_meta, charge) if mode == 'open' else None
+                if level is not None:
+                    level_win = level.windows[charge]
+                else:
+                    level_win = self._open_level_windows(qs, query_meta, charge) if mode == 'open' else None
+                # (no keyword without a level: the signatures of older overrides keep working)
+                more = {} if level is None else dict(shifts=level.shifts)
                 for b0 in range(0, len(rows), bs):
                     sel = rows[b0:b0 + bs]
                     if len(sel) == 0:
@@ -997,13 +1094,13 @@ class SpectralLibrary:
                     win = None if level_win is None else level_win[sel]
                     if stats:           # the histogram call, at num_matches = 1 too
                         top = self.search_batch_topn(q, charge, mode, n_best, device_out=True,
-                                                     distinct=distinct, windows=win, score_hist=True)
+                                                     distinct=distinct, windows=win, score_hist=True, **more)
                         res = None if top is None else top.rank0()
                         if res is not None:
                             res.topn = top
                     elif n_best > 1:    # rank 0 goes the single winner's way, the rest rides along
                         top = self.search_batch_topn(q, charge, mode, n_best, device_out=True,
-                                                     distinct=distinct, windows=win)
+                                                     distinct=distinct, windows=win, **more)
                         res = None if top is None else top.rank0()
                         if res is not None:
                             res.topn = top
@@ -1011,12 +1108,22 @@ class SpectralLibrary:
                         # (no keyword without windows: engines that override _search_batch with its older
                         # signature, as the oracle-backed ones of the tests do, keep working)
                         res = (self._search_batch(q, charge, mode, device_out=True) if win is None else
-                               self._search_batch(q, charge, mode, device_out=True, windows=win))
+                               self._search_batch(q, charge, mode, device_out=True, windows=win, **more))
                     if res is not None:
                         pending.append((charge, sel, q, res))
         finally:
             if piped:
                 self.set_pipeline(False)         # synchronises first
+        def filed(charge, sel, res):
+            """(charge, rows of query_spectra, winners) as the table files a batch: a further level names its
+            queries by their rows in query_spectra and withholds the matches it drops (row -1: no SSM)."""
+            best = _to_np(res.best_row)
+            if level is None:
+                return charge, sel, best
+            qrows = level.qrow[charge][sel]
+            if level.keep is not None:
+                best = np.where(level.keep(charge, sel, best), best, -1).astype(best.dtype)
+            return charge, qrows, best
         # default search-engine score: the cosine over the winner's peak matches -- every batch's
         # kernel is enqueued before the first result is copied back (a copy waits for its kernel)
         if getattr(score_ssms, 'uses_features', False):
@@ -1029,21 +1136,22 @@ class SpectralLibrary:
                      for charge, sel, q, res in pending]
             for (charge, sel, q, res), F in zip(pending, feats):
                 F = _to_np(F)
-                table.add_batch(charge, sel, _to_np(res.best_row), F[:, 0], res, F)
+                table.add_batch(*filed(charge, sel, res), F[:, 0], res, F)
         else:
             cosines = [spectrum_similarity.ssm_cosine(q, self.partitions[charge].spectra, res.best_row,
                                                       res.pm_pairs, res.pm_count)
                        for charge, sel, q, res in pending]
             for (charge, sel, q, res), cos in zip(pending, cosines):
-                table.add_batch(charge, sel, _to_np(res.best_row), _to_np(cos), res)
+                table.add_batch(*filed(charge, sel, res), _to_np(cos), res)
         table.open_level[:] = mode == 'open'
         if uid is not None:
             table = table.first_per_uid(uid)
         acc = getattr(self, 'level_seconds', None)
         if acc is not None:       # bench.py: wall time, queries in, SSMs out of every cascade level
             torch.cuda.synchronize() if self.device.type == 'cuda' else None
-            sec, a, b = acc.get(mode, (0.0, 0, 0))
-            acc[mode] = (sec + time.perf_counter() - t_level, a + n_in, b + len(table))
+            key = mode if level is None else level.name
+            sec, a, b = acc.get(key, (0.0, 0, 0))
+            acc[key] = (sec + time.perf_counter() - t_level, a + n_in, b + len(table))
         if score_ssms is None:    # no scorer: cosine (spectrum_similarity.py:81-106), accepted
             cascade = self.config.precursor_tolerance_mass_open is not None
             if (cascade or self.config.model is not None) and not getattr(self, '_warned_model', False):
@@ -1090,6 +1198,30 @@ def open_window_intervals(precursor_mz, charge: int, window_da) -> np.ndarray:
     lo_da, hi_da = (float(v) for v in window_da)
     q = np.asarray(precursor_mz, np.float64)
     return np.stack([q - hi_da / charge, q - lo_da / charge], axis=1)
+
+
+def chimeric_window_intervals(precursor_mz, width) -> np.ndarray:
+    """``Config.chimeric_window`` as intervals of library precursor m/z, [n, 2] float64: [q - width / 2,
+    q + width / 2] around every query's precursor m/z (computed in float64; the bounds are inclusive)."""
+    q = np.asarray(precursor_mz, np.float64)
+    half = float(width) / 2.0
+    return np.stack([q - half, q + half], axis=1)
+
+
+@dataclass
+class CascadeLevel:
+    """What a cascade level beyond the reference's two hands ``_search_cascade``: the spectra it searches, per
+    charge, in place of the queries (residues, say); ``qrow[charge][i]``, the row of ``query_spectra`` /
+    ``query_meta`` spectrum ``i`` stands for in the table; ``windows[charge]``, one closed interval of library
+    precursor m/z per spectrum ([n, 2] float64: the candidates, as ``_search_batch(windows=)`` takes them);
+    whether the dot product shifts peaks; ``keep(charge, rows, best_row) -> bool mask``, the winners that
+    reach the table and the scorer (None: all); ``name``, its key in ``level_seconds``."""
+    name: str
+    spectra: Dict[int, PackedSpectra]
+    qrow: Dict[int, np.ndarray]
+    windows: Dict[int, np.ndarray]
+    shifts: bool = False
+    keep: Optional[object] = None
 
 
 def isolation_windows(meta, n: int) -> Optional[np.ndarray]:
@@ -1156,13 +1288,19 @@ class SSMTable:
     ``mod_site_margin`` (best minus the best different score; 0 when every site ties) and ``mod_site_gain``
     (best minus the score without the mass). Everywhere else: NaN and -1.
 
+    With ``chimeric_search`` the table ends with the matches of the residue level: ``chimeric_rank`` 1 (0 for
+    everything else) and ``explained_intensity``, the share of the query's squared intensity its PRIMARY match
+    explains (NaN on rank-0 rows). Such a row names the same query as a rank-0 row: the table may hold two SSMs
+    for one identifier, and the peak matches of the second index the residue spectrum's peaks.
+
     ``features[len, 33]`` (float64) holds the similarity columns of ``spectrum_similarity.FEATURE_NAMES`` when
     the level ran for a scorer that learns from them (``fdr.PercolatorTDC``); ``[len, 0]`` otherwise."""
 
     # columns that are filled after the batches are filed: (name, dtype, default)
     _LATE = (('open_level', bool, False), ('mod_mass', np.float64, np.nan), ('mod_site_lo', np.int32, -1),
              ('mod_site_hi', np.int32, -1), ('mod_site_score', np.float64, np.nan),
-             ('mod_site_margin', np.float64, np.nan), ('mod_site_gain', np.float64, np.nan))
+             ('mod_site_margin', np.float64, np.nan), ('mod_site_gain', np.float64, np.nan),
+             ('chimeric_rank', np.int32, 0), ('explained_intensity', np.float64, np.nan))
 
     def __init__(self, query_meta, library_meta, n_alt: int = 0):
         self.query_meta, self.library_meta = query_meta, library_meta
@@ -1354,7 +1492,7 @@ class SSMTable:
             self._peak_matches(i), float(self.delta_score[i]), self._alternatives(i),
             int(self.n_scored[i]), float(self.expect[i]), float(self.mod_mass[i]), int(self.mod_site_lo[i]),
             int(self.mod_site_hi[i]), float(self.mod_site_score[i]), float(self.mod_site_margin[i]),
-            float(self.mod_site_gain[i]))
+            float(self.mod_site_gain[i]), int(self.chimeric_rank[i]), float(self.explained_intensity[i]))
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))

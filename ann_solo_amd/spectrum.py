@@ -159,6 +159,11 @@ class SpectrumSpectrumMatch:
     mod_site_score: float = float('nan')
     mod_site_margin: float = float('nan')
     mod_site_gain: float = float('nan')
+    # chimeric_search: 1 for a match of the residue its query's primary identification leaves (a second PSM of
+    # the spectrum), 0 otherwise; on rank-1 matches the share of the query's squared intensity the primary
+    # explains, NaN elsewhere
+    chimeric_rank: int = 0
+    explained_intensity: float = float('nan')
 
 
 def ssms_from_batch(result, query_meta, library_meta, scores=None, q_values=None

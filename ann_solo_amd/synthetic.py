@@ -178,12 +178,16 @@ def hard_levers(h: float) -> Dict[str, float]:
 
 def make_queries(lib: PackedSpectra, aux: Dict[str, torch.Tensor], nq: int, seed: int = 42,
                  mod_frac: float = 0.5, open_range: float = 500.0,
-                 charge: int = None, hard: float = 0.0) -> Tuple[PackedSpectra, Dict[str, torch.Tensor]]:
+                 charge: int = None, hard: float = 0.0,
+                 with_partner: bool = False) -> Tuple[PackedSpectra, Dict[str, torch.Tensor]]:
     """Query spectra re-drawn from library peptides: half unmodified (5 ppm precursor
     jitter), half with one PTM on a random residue; 0.005 Da fragment jitter, 10 % of
     the peaks dropped, 10 noise peaks. ``hard`` > 0 (``hard_levers``): noisier spectra --
     more dropped peaks, stronger intensity noise, larger jitter, more and stronger noise
-    peaks, a co-fragmented second spectrum; ``hard`` = 0 draws exactly the default queries."""
+    peaks, a co-fragmented second spectrum; ``hard`` = 0 draws exactly the default queries. The second
+    return value names, per query, its ``source_row``, ``is_modified`` and ``delta_mass``; ``with_partner`` adds
+    ``partner_row``, the library row of the co-fragmented spectrum (drawn anywhere in the library; -1 without
+    one). The draws do not depend on it."""
     lv = hard_levers(hard)
     dev = lib.device
     g = torch.Generator(device=dev)
@@ -193,7 +197,7 @@ def make_queries(lib: PackedSpectra, aux: Dict[str, torch.Tensor], nq: int, seed
     else:
         pool = torch.nonzero(lib.precursor_charge == charge).squeeze(1)
     out_parts = []
-    truth_src, truth_mod, truth_dm = [], [], []
+    truth_src, truth_mod, truth_dm, truth_oth = [], [], [], []
     chunk = 1 << 16
     for c0 in range(0, nq, chunk):
         m = min(chunk, nq - c0)
@@ -231,6 +235,7 @@ def make_queries(lib: PackedSpectra, aux: Dict[str, torch.Tensor], nq: int, seed
         mz = torch.cat([mz, nmz], 1)
         raw = torch.cat([raw, nin], 1)
         hard_draws = hard > 0           # (extra draws come last in the chunk: hard = 0 is the default stream)
+        oth = torch.full((mm,), -1, dtype=src.dtype, device=dev)
         pmz = lib.precursor_mz[src] + dm / z
         ppm = 5e-6 * torch.randn(mm, generator=g, device=dev, dtype=torch.float64)
         pmz = pmz * (1 + ppm)
@@ -264,6 +269,7 @@ def make_queries(lib: PackedSpectra, aux: Dict[str, torch.Tensor], nq: int, seed
         truth_src.append(src[keep])
         truth_mod.append(is_mod[keep])
         truth_dm.append(dm[keep])
+        truth_oth.append(oth[keep])
     offs = [out_parts[0][0]]
     base = int(out_parts[0][0][-1])
     for p in out_parts[1:]:
@@ -274,4 +280,6 @@ def make_queries(lib: PackedSpectra, aux: Dict[str, torch.Tensor], nq: int, seed
                       torch.cat([p[2] for p in out_parts]), torch.cat([p[3] for p in out_parts]))
     truth = dict(source_row=torch.cat(truth_src), is_modified=torch.cat(truth_mod),
                  delta_mass=torch.cat(truth_dm))
+    if with_partner:
+        truth['partner_row'] = torch.cat(truth_oth)
     return q, truth

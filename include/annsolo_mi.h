@@ -694,6 +694,46 @@ int asl_localize_batch(const asl_peaks_t *queries, const int32_t *seq_offsets /*
                        int32_t *n_best, int32_t *best_count, double *best_score, double *runner_score,
                        double *none_score);
 
+/* ------------------------------------------------------------------ chimeric spectra: depletion
+ * A co-fragmented scan holds the peaks of two peptides. This call takes an identification, removes from the
+ * query every peak its winner explains and hands back the rest as a processed spectrum to search again.
+ * SSM s is query spectrum s of `queries` against row lib_rows[s] of `library` (peaks ascending in m/z in both;
+ * queries->charge and queries->precursor_charge are not read; library->charge == NULL: every charge 0).
+ * "Explained" is the dot product's own window test -- the peak could have entered SpectrumMatcher::dot's match
+ * list -- and the arithmetic, all in IEEE double without fused multiply-add, is the contract:
+ *  1. shifts: z the library row's precursor charge, t = fragment_mz_tolerance,
+ *       pmd = (q_pmz - l_pmz) * (double)z.
+ *     `allow_shift` is asl_rescore_batch's FLAG WORD (any other bit: ASL_ERR_INVALID). ASL_SCORE_FRAGMENT_PPM
+ *     clear: tol_i = t for every query peak i and the gate is fabs(pmd) >= t. Set: rel = t * 1e-6, tol_i =
+ *     rel * (double)q_mz[i], the gate is fabs(pmd) >= rel * q_pmz.
+ *       num_shifts = (ASL_SCORE_SHIFT && gate) ? z + 1 : 1; mass_diff[0] = 0, mass_diff[c] = pmd / c, c >= 1.
+ *     The rescoring names no largest charge (it reads whatever the row holds; z + 1 <= 0: no shift at all,
+ *     not even c = 0), and neither does this call.
+ *  2. explained: query peak i iff there is a library peak j and a c < num_shifts with
+ *       fabs((double)q_mz[i] - ((double)l_mz[j] + mass_diff[c])) <= tol_i  and
+ *       (c == 0 || l_charge[j] == c || l_charge[j] == 0)     (the dot product's match_multiplier > 0).
+ *     There is no cursor: any (j, c) will do.
+ *  3. residue: the unexplained peaks in their order, out_mz / out_src (the peak's index in its query) as they
+ *     are; intensities re-normalised exactly as asl_process_batch normalises: acc = 0.0f, acc = fmaf(v, v, acc)
+ *     over the kept intensities v in ascending order (float32), nrm = sqrtf(acc), out_intensity = v / nrm (IEEE
+ *     divide). kept_energy[s] = acc: for a unit-norm query the share of squared intensity the winner leaves.
+ *  4. out_count[s] = n, the kept peaks; out_valid[s] = n >= min_peaks && n > 0 && (double)(mz_last - mz_first)
+ *     >= min_mz_range with the float32 difference of the last and first kept m/z (asl_process_batch's is_valid).
+ * Rows with lib_rows[s] < 0: count 0, valid 0, energy 0. out_mz / out_intensity / out_src are [n, out_stride]
+ * and every slot is written: zero beyond out_count[s]. out_src and kept_energy may be NULL; every array may
+ * live in host or device memory.
+ * Limits, all checked on host copies of the small arrays before anything is launched or written: more than
+ * 4096 peaks in a query or in a named library row, or out_stride below the largest query: ASL_ERR_CAPACITY; a
+ * negative or NaN tolerance, a flag bit other than the two, a row >= library->n: ASL_ERR_INVALID. Ascending
+ * m/z is a precondition for the result, not for safety: no step reads outside a spectrum's slice whatever the
+ * order of its peaks. No atomics: equal inputs give equal bits. Synchronous. */
+int asl_deplete_batch(const asl_peaks_t *queries, const asl_peaks_t *library,
+                      const int64_t *lib_rows /* [n]; < 0: skip */,
+                      double fragment_mz_tolerance, int allow_shift /* the flag word */,
+                      int32_t min_peaks, double min_mz_range, int32_t out_stride,
+                      float *out_mz, float *out_intensity, int32_t *out_src /* nullable */,
+                      int32_t *out_count, uint8_t *out_valid, float *kept_energy /* nullable */);
+
 /* ------------------------------------------------------------------ SSM features
  * Replaces the per-SSM SpectrumSimilarityCalculator calls of _compute_ssm_features
  *   /root/reference/src/ann_solo/utils.py:344-456
