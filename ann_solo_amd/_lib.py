@@ -92,6 +92,7 @@ EXPORTS = [
     'asl_decoy_batch',
     'asl_localize_batch', 'asl_deplete_batch',
     'asl_l2svm_fit', 'asl_linear_scores',
+    'asl_forest_bin', 'asl_forest_fit', 'asl_forest_predict', 'asl_set_forest_workspace',
 ]
 
 SVM_MAX_DIM = 63          # include/annsolo_mi.h: ASL_SVM_MAX_DIM
@@ -101,6 +102,22 @@ SVM_MAX_PROBLEMS = 32     # ASL_SVM_MAX_PROBLEMS
 class AslL2SvmParams(C.Structure):
     _fields_ = [('C', C.c_double), ('gtol_abs', C.c_double), ('gtol_rel', C.c_double),
                 ('max_newton', C.c_int32)]
+
+
+FOREST_MAX_BINS = 256     # ASL_FOREST_MAX_BINS
+FOREST_MAX_DEPTH = 12     # ASL_FOREST_MAX_DEPTH
+FOREST_MAX_TREES = 1024   # ASL_FOREST_MAX_TREES
+FOREST_NODES = 8191       # ASL_FOREST_NODES
+FOREST_ROW = 64           # ASL_FOREST_ROW
+
+
+class AslForestParams(C.Structure):
+    _fields_ = [('trees', C.c_int32), ('max_depth', C.c_int32), ('seed', C.c_uint32)]
+
+
+class AslForestModel(C.Structure):
+    _fields_ = [('trees', C.c_int32), ('max_depth', C.c_int32), ('col', C.c_void_p), ('bin', C.c_void_p),
+                ('n0', C.c_void_p), ('n1', C.c_void_p), ('value', C.c_void_p)]
 
 
 def build(force: bool = False) -> str:
@@ -313,6 +330,14 @@ def lib():
             L.asl_l2svm_fit.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                         C.POINTER(AslL2SvmParams)] + [C.c_void_p] * 4
             L.asl_linear_scores.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        if hasattr(L, 'asl_forest_fit'):
+            L.asl_forest_bin.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.asl_forest_fit.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.POINTER(AslForestParams), C.POINTER(AslForestModel)]
+            L.asl_forest_predict.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(AslForestModel), C.c_int32,
+                                             C.c_int32, C.c_void_p]
+            L.asl_set_forest_workspace.argtypes = [C.c_int64]
+            L.asl_set_forest_workspace.restype = C.c_int64
         if hasattr(L, 'asl_index_set_by_residual'):
             L.asl_index_set_by_residual.argtypes = [C.c_void_p, C.c_int32]
             L.asl_index_get_by_residual.argtypes = [C.c_void_p]
@@ -458,3 +483,127 @@ def linear_scores(X, wb):
         out = np.empty((P, n), np.float64)
     check(lib().asl_linear_scores(ptr(X) if n else None, n, d, ptr(wb), P, ptr(out) if n else None))
     return out
+
+
+class ForestModel:
+    """P forests as ``asl_forest_fit`` writes them: ``col`` int16, ``bin`` uint8, ``n0`` / ``n1`` uint32 and
+    ``value`` float64, each ``[P, trees, FOREST_NODES]`` (numpy, or torch tensors on one device), and the depth
+    they were grown to."""
+    FIELDS = (('col', np.int16), ('bin', np.uint8), ('n0', np.uint32), ('n1', np.uint32), ('value', np.float64))
+
+    def __init__(self, P: int, trees: int, max_depth: int, device=None):
+        self.P, self.trees, self.max_depth = int(P), int(trees), int(max_depth)
+        shape = (self.P, self.trees, FOREST_NODES)
+        for name, dt in self.FIELDS:
+            if device is None:
+                a = np.empty(shape, dt)
+            else:
+                import torch
+                # (the counts travel as int32 bits on the torch side: numpy() reads them back as uint32)
+                a = torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name.replace('uint32', 'int32')),
+                                device=device)
+            setattr(self, name, a)
+
+    def struct(self) -> AslForestModel:
+        return AslForestModel(self.trees, self.max_depth, *[ptr(getattr(self, name)) for name, _ in self.FIELDS])
+
+    def numpy(self) -> dict:
+        """The five arrays on the host."""
+        return {name: (a.cpu().numpy().view(dt) if hasattr(a, 'cpu') else a)
+                for name, dt, a in ((name, dt, getattr(self, name)) for name, dt in self.FIELDS)}
+
+
+def _as_bins(bins):
+    if hasattr(bins, 'data_ptr'):
+        import torch
+        if bins.dtype != torch.uint8:
+            raise ValueError(f'bins: uint8 expected, got {bins.dtype}')
+        bins = bins.contiguous()
+    else:
+        bins = np.asarray(bins)
+        if bins.dtype != np.uint8:
+            raise ValueError(f'bins: uint8 expected, got {bins.dtype}')
+        bins = np.ascontiguousarray(bins)
+    if bins.ndim != 2 or int(bins.shape[1]) != FOREST_ROW:
+        raise ValueError(f'bins: [n, {FOREST_ROW}] expected, got {tuple(bins.shape)}')
+    return bins
+
+
+def forest_bin(X, edges, n_edges):
+    """``asl_forest_bin``: ``X [n, d]`` float64 (numpy or torch, host or device) to ``[n, 64]`` uint8 rows, where
+    ``X`` lives: byte j of a row is the number of ``edges[j, :n_edges[j]]`` (ascending; ``[d, 255]``) below
+    ``X[i, j]``, bytes d .. 63 are 0."""
+    X = _as_f64(X, 2, 'X')
+    n, d = int(X.shape[0]), int(X.shape[1])
+    edges = np.ascontiguousarray(edges, np.float64)
+    n_edges = np.ascontiguousarray(n_edges, np.int32)
+    if edges.shape != (d, FOREST_MAX_BINS - 1):
+        raise ValueError(f'edges: [{d}, {FOREST_MAX_BINS - 1}] expected, got {edges.shape}')
+    if n_edges.shape != (d,):
+        raise ValueError(f'n_edges: [{d}] expected, got {n_edges.shape}')
+    if hasattr(X, 'data_ptr'):
+        import torch
+        out = torch.empty((n, FOREST_ROW), dtype=torch.uint8, device=X.device)
+    else:
+        out = np.empty((n, FOREST_ROW), np.uint8)
+    check(lib().asl_forest_bin(ptr(X) if n else None, n, d, ptr(edges), ptr(n_edges), ptr(out) if n else None))
+    return out
+
+
+def forest_fit(bins, d: int, label, cw, trees: int = 100, max_depth: int = FOREST_MAX_DEPTH, seed: int = 1,
+               n_bins=None) -> ForestModel:
+    """``asl_forest_fit``: P histogram forests of ``trees`` trees over one binned matrix ``bins [n, 64]`` uint8
+    with ``d`` columns (numpy or torch, host or device). ``label [P, n]`` int8 in {+1, -1, 0} (0: the row is not
+    part of the problem), ``cw [P, 2]`` the weights of the -1 / +1 class, ``n_bins [d]`` the columns' bin counts
+    (checked against ``bins`` when given). The model lives where ``bins`` lives."""
+    bins = _as_bins(bins)
+    n = int(bins.shape[0])
+    if hasattr(label, 'data_ptr'):
+        import torch
+        label = label.to(torch.int8).contiguous()
+    else:
+        label = np.ascontiguousarray(label, np.int8)
+    if label.ndim != 2 or int(label.shape[1]) != n:
+        raise ValueError(f'label: [P, {n}] expected, got {tuple(label.shape)}')
+    P = int(label.shape[0])
+    cw = np.ascontiguousarray(cw, np.float64)
+    if cw.shape != (P, 2):
+        raise ValueError(f'cw: [{P}, 2] expected, got {cw.shape}')
+    if n_bins is not None:
+        n_bins = np.ascontiguousarray(n_bins, np.int32)
+        if n_bins.shape != (int(d),):
+            raise ValueError(f'n_bins: [{int(d)}] expected, got {n_bins.shape}')
+    if not 1 <= P <= SVM_MAX_PROBLEMS or not 1 <= int(trees) <= FOREST_MAX_TREES:
+        raise ValueError(f'forest_fit: P = {P} (1 .. {SVM_MAX_PROBLEMS}), trees = {trees} (1 .. {FOREST_MAX_TREES})')
+    model = ForestModel(P, trees, max_depth, bins.device if hasattr(bins, 'data_ptr') and bins.is_cuda else None)
+    params = AslForestParams(int(trees), int(max_depth), int(seed) & 0xffffffff)
+    ms = model.struct()
+    check(lib().asl_forest_fit(ptr(bins) if n else None, n, int(d), ptr(label) if n else None, ptr(cw), P,
+                               ptr(n_bins), byref(params), byref(ms)))
+    return model
+
+
+def forest_predict(bins, d: int, model: ForestModel, max_depth=None):
+    """``asl_forest_predict``: ``proba [P, n]`` float64 where ``bins`` lives -- the mean over the trees of the
+    value of the node where a row stops after at most ``max_depth`` levels (default: the depth grown)."""
+    bins = _as_bins(bins)
+    n = int(bins.shape[0])
+    depth = model.max_depth if max_depth is None else int(max_depth)
+    if hasattr(bins, 'data_ptr'):
+        import torch
+        out = torch.empty((model.P, n), dtype=torch.float64, device=bins.device)
+    else:
+        out = np.empty((model.P, n), np.float64)
+    ms = model.struct()
+    check(lib().asl_forest_predict(ptr(bins) if n else None, n, int(d), byref(ms), model.P, depth,
+                                   ptr(out) if n else None))
+    return out
+
+
+def set_forest_workspace(nbytes: int) -> int:
+    """``asl_set_forest_workspace``: the device bytes one batch of (problem, tree) pairs may take while
+    ``forest_fit`` grows a level; returns the previous value. The result does not depend on it."""
+    prev = lib().asl_set_forest_workspace(int(nbytes))
+    if prev <= 0:
+        check(int(prev))
+    return int(prev)

@@ -5,8 +5,8 @@
 (``index``, ``pq_m``, ``pq_bits``, ``refine_k``, ``kmeans_niter``, ``ann_seed``, ``num_gpus``,
 ``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``, ``pq_by_residual``,
 ``precursor_window_open``, ``fragment_tolerance_unit``, ``score_stats``, ``device_decoys``,
-``decoy_tolerance_unit``, ``localize_modifications``, ``device_fdr``, ``chimeric_search``,
-``chimeric_window``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``decoy_tolerance_unit``, ``localize_modifications``, ``device_fdr``, ``device_forest``,
+``forest_trees``, ``chimeric_search``, ``chimeric_window``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -126,9 +126,14 @@ class Config:
     # the engine's own FDR step (fdr.py; DESIGN.md 3 "Rescoring model"): without an injected ``score_ssms`` the
     # cascade levels are gated by ``model`` -- None / 'none': target-decoy q-values on the cosine; 'svm': a
     # Percolator-like linear SVM over the reference's feature table, trained on the device -- at ``fdr``, open
-    # level grouped with ``fdr_min_group_size``. 'rf' is not provided (ValueError). An injected callable always
+    # level grouped with ``fdr_min_group_size``. 'rf' alone is not provided (ValueError; see device_forest). An injected callable always
     # wins; off: every SSM is accepted with q = 0, as ever
     device_fdr: bool = False
+    # with device_fdr and model = 'rf': the engine's histogram forest (fdr.ForestTDC, csrc/forest.hip; DESIGN.md 3
+    # "Rescoring model: forest") of ``forest_trees`` trees per forest. A switch of its own because the forest is a
+    # restatement -- binned splits, not scikit-learn's exact ones -- and must not silently stand for 'rf'
+    device_forest: bool = False
+    forest_trees: int = 100         # scikit-learn's n_estimators default; 1 .. MAX_FOREST_TREES
     # chimeric spectra (chimeric.py; DESIGN.md 3 "Chimeric search"): after the last cascade level every accepted
     # identification's explained peaks are removed from its query and the residue is searched once more, without
     # peak shifts, against the library rows of the same charge inside the query's isolation window -- the
@@ -142,6 +147,7 @@ class Config:
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
     MAX_CANDIDATES = 16384   # largest num_candidates: beyond MAX_TOPK in bounded passes (TK_MAX_K_PASSES)
     MAX_MATCHES = 16     # largest num_matches (include/annsolo_mi.h: ASL_MAX_BEST)
+    MAX_FOREST_TREES = 1024  # largest forest_trees (ASL_FOREST_MAX_TREES)
 
     def __post_init__(self):
         for name in ('max_peaks_used', 'max_peaks_used_library'):
@@ -196,8 +202,18 @@ class Config:
         if self.localize_modifications and self.num_gpus and int(self.num_gpus) > 1:
             raise ValueError('localize_modifications does not run on a sharded index (num_gpus > 1)')
         self.device_fdr = bool(self.device_fdr)
+        self.device_forest = bool(self.device_forest)
+        self.forest_trees = int(self.forest_trees)
+        if not 1 <= self.forest_trees <= self.MAX_FOREST_TREES:
+            raise ValueError(f'forest_trees = {self.forest_trees}: 1 .. {self.MAX_FOREST_TREES}')
+        if self.device_forest:
+            if not self.device_fdr or self.model != 'rf':
+                raise ValueError("device_forest is the forest of the engine's own FDR step: it needs device_fdr "
+                                 f"and model = 'rf' (device_fdr = {self.device_fdr}, model = {self.model!r})")
+            if self.num_gpus and int(self.num_gpus) > 1:
+                raise ValueError('device_forest does not run on a sharded index (num_gpus > 1)')
         if self.device_fdr:
-            if self.model not in (None, 'none', 'svm'):
+            if self.model not in (None, 'none', 'svm') and not (self.model == 'rf' and self.device_forest):
                 raise ValueError(f"device_fdr: model = {self.model!r} is not provided; None / 'none' (q-values on "
                                  "the cosine) or 'svm' (the Percolator-like linear SVM)")
             if self.num_gpus and int(self.num_gpus) > 1:
@@ -372,9 +388,16 @@ def add_arguments(parser) -> None:
     parser.add_argument('--device_fdr', action='store_true', default=d.device_fdr,
                         help="gate both cascade levels by the engine's own FDR step at --fdr: with --model none "
                              'target-decoy q-values on the cosine, with --model svm a Percolator-like linear SVM '
-                             "over the reference's SSM features, trained on the GPU (--model rf is not provided); "
+                             "over the reference's SSM features, trained on the GPU (--model rf needs --device_forest); "
                              'open-level q-values per mass-difference group of --fdr_min_group_size; one GPU '
                              '(default: off -- the caller scores the SSMs)')
+    parser.add_argument('--device_forest', action='store_true', default=d.device_forest,
+                        help="with --device_fdr and --model rf: the engine's histogram random forest, grown and "
+                             'evaluated on the GPU -- binned splits (at most 256 bins per feature), depth at most '
+                             "12, not scikit-learn's exact-split forest, hence a switch of its own; one GPU "
+                             '(default: off -- --model rf is not provided)')
+    parser.add_argument('--forest_trees', default=d.forest_trees, type=int,
+                        help='with --device_forest: trees per forest (default: %(default)s)')
     parser.add_argument('--chimeric_search', action='store_true', default=d.chimeric_search,
                         help='after the last cascade level, remove the peaks every accepted identification explains '
                              'from its query spectrum and search the residue once more (no peak shifts) among the '

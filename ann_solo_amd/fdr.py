@@ -10,7 +10,12 @@ the columns of an ``SSMTable``.
 
 The reference delegates the training procedure to mokapot (``PercolatorModel`` + ``brew``), which is not
 vendored with it; ``PercolatorTDC`` RESTATES that procedure (DESIGN.md 3 "Rescoring model") and claims no bit
-parity with mokapot. The random forest (``--model rf``) is not provided."""
+parity with mokapot.
+
+  * ``ForestTDC``      -- ``--model rf`` WITH ``--device_forest``: the same procedure around a histogram forest
+    grown and evaluated on the device by ``asl_forest_fit`` / ``asl_forest_predict`` (csrc/forest.hip). It is a
+    restatement too -- a binned forest, not scikit-learn's exact-split one (DESIGN.md 3 "Rescoring model:
+    forest") -- so ``--model rf`` alone does not stand for it: without the switch ``rf`` is not provided."""
 import logging
 from typing import Optional
 
@@ -19,7 +24,7 @@ import numpy as np
 from .spectrum_similarity import FEATURE_NAMES
 
 __all__ = ['tdc_qvalues', 'ssm_groups', 'CosineTDC', 'feature_table', 'FeatureScaler', 'PercolatorTDC',
-           'MODEL_COLUMNS', 'make_scorer']
+           'ForestTDC', 'MODEL_COLUMNS', 'make_scorer']
 
 #: the model's columns in the key order of the reference's feature dictionary (utils.py:297-340); ``index``,
 #: ``sequence`` and ``is_target`` are metadata, not features
@@ -259,42 +264,33 @@ def _device_solver(device):
     return _lib.l2svm_fit, scores, prepare
 
 
-class PercolatorTDC:
-    """The reference's ``--model svm`` (mokapot's ``PercolatorModel`` under ``brew``), restated:
+class _SemiSupervisedTDC:
+    """The procedure ``PercolatorTDC`` and ``ForestTDC`` share (mokapot's ``brew``, restated; the steps are listed
+    under ``PercolatorTDC``): folds, start labels from the cosine, the parameter choice once per fold, ``max_iter``
+    relabelling rounds, calibration, grouped TDC, the fallbacks and the ``trace``. A model supplies four hooks:
 
-    1. the SSMs with peak matches are split into ``folds`` parts by a seeded permutation;
-    2. per part, a model is trained on the other parts: the features are scaled (``FeatureScaler``, fitted on
-       the training rows); the start labels come from the cosine by TDC at ``fdr`` in the direction that passes
-       more targets (+1 target with q <= fdr, 0 other target, -1 decoy); the class weights are chosen once from
-       ``GRID`` by a seeded 3-fold inner cross-validation (accuracy on the held-out labelled rows, the first of
-       equal means) -- 27 problems in ONE ``l2svm_fit`` call; then ``max_iter`` rounds of fit on the rows
-       labelled +-1, score the training rows, relabel by TDC at ``fdr``. The LAST round's weights are the model;
-    3. every part is scored by its model and calibrated: (s - s_t) / (s_t - s_d), s_t the lowest score of a
-       target passing ``fdr``, s_d the median decoy score;
-    4. merged; q-values by TDC, per mass-difference group at ``mode == 'open'`` as ``CosineTDC``;
-    5. targets get the calibrated score and q, decoys and SSMs without peak matches NaN for both.
-
-    A stage without a passing target, or a training set with one class only: ``CosineTDC`` for that call, a
-    warning, ``self.fallback = True``. ``solver``: the ``(fit, scores)`` pair, default the device's
-    (``_lib.l2svm_fit``, ``_lib.linear_scores`` with the matrix on ``device``). ``self.trace`` keeps, per fold,
-    the grid point chosen, the labels of every round and the weights, for the tests."""
+      ``_open()``                      -> ``(ctx, prepare)``: the solver and where it wants the matrix;
+      ``_model_input(ctx, X, train)``  -> what the solver reads in place of the scaled matrix (default: ``X``);
+      ``_choose(ctx, X, lab, held)``   -> ``(grid point, mean held-out accuracies)``;
+      ``_round(ctx, X, lab, best, tr, state)`` -> ``(scores of all rows, state)``: one fit on the labelled rows."""
     columnar = True
     uses_features = True        # SpectralLibrary: the level keeps the batches' 33 similarity columns
 
     def __init__(self, fdr: float = 0.01, min_group_size: int = 100, folds: int = 3, max_iter: int = 10,
-                 seed: int = 1, solver=None, device='cuda', C: float = 1.0):
+                 seed: int = 1, solver=None, device='cuda'):
         if folds < 2 or max_iter < 1:
-            raise ValueError('PercolatorTDC: folds >= 2 and max_iter >= 1')
+            raise ValueError(f'{type(self).__name__}: folds >= 2 and max_iter >= 1')
         self.fdr, self.min_group_size = float(fdr), int(min_group_size)
-        self.folds, self.max_iter, self.seed, self.C = int(folds), int(max_iter), int(seed), float(C)
+        self.folds, self.max_iter, self.seed = int(folds), int(max_iter), int(seed)
         self.solver, self.device = solver, device
         self.fallback = False
         self.n_groups: Optional[int] = None
         self.trace: list = []
         self.n_fit_calls = 0
-        self.n_newton = 0
 
-    # -- the procedure over a feature matrix ------------------------------------------------------------
+    def _model_input(self, ctx, X, train):
+        return X
+
     def _labels(self, scores, target, train, desc=True):
         """(+1 target with q <= fdr, 0 other target, -1 decoy) over the rows ``train``, 0 elsewhere."""
         lab = np.zeros(len(scores), np.int8)
@@ -304,46 +300,23 @@ class PercolatorTDC:
         lab[train[~t]] = -1
         return lab
 
-    def _fit(self, fit, X, label, cw, wb=None):
-        wb, _, steps, status = fit(X, label, cw, C=self.C, gtol_abs=GTOL_ABS, gtol_rel=GTOL_REL, wb=wb)
-        self.n_fit_calls += 1
-        self.n_newton += int(np.max(steps)) if len(steps) else 0
-        if np.any(status != 0):
-            logging.debug('l2svm_fit: status %s after %s Newton steps', status.tolist(), steps.tolist())
-        return wb
-
-    def _train(self, fit, scores_of, X, target, cos, train, fold: int):
+    def _train(self, ctx, X, target, cos, train, fold: int):
         start = [self._labels(cos, target, train, desc) for desc in (True, False)]
         lab = start[0] if (start[0] == 1).sum() >= (start[1] == 1).sum() else start[1]
         if not (lab == 1).any() or not (lab == -1).any():
             raise _Fallback('no target passes the training FDR on the cosine' if (lab == -1).any()
                             else 'a training set without decoys')
-        # class weights: 9 grid points x 3 inner folds over the labelled rows, one fit, one scoring call
+        # the parameters: grid points x 3 inner folds over the labelled rows
         labelled = np.nonzero(lab != 0)[0]
         perm = np.random.default_rng([self.seed, fold]).permutation(len(labelled))
         held = [labelled[p] for p in np.array_split(perm, INNER_FOLDS)]
-        P = len(GRID) * INNER_FOLDS
-        labels = np.repeat(lab[None, :], P, axis=0)
-        cw = np.zeros((P, 2))
-        for g, pair in enumerate(GRID):
-            for f in range(INNER_FOLDS):
-                labels[g * INNER_FOLDS + f, held[f]] = 0
-                cw[g * INNER_FOLDS + f] = pair
-        s = scores_of(X, self._fit(fit, X, labels, cw))
-        acc = np.zeros((len(GRID), INNER_FOLDS))
-        for g in range(len(GRID)):
-            for f in range(INNER_FOLDS):
-                pred = np.where(s[g * INNER_FOLDS + f, held[f]] > 0, 1, -1)
-                acc[g, f] = np.mean(pred == lab[held[f]]) if len(held[f]) else 0.0
-        best = int(np.argmax(acc.mean(axis=1)))     # the first of equal means
-        tr = dict(grid=best, accuracy=acc.mean(axis=1), labels=[], wb=[])
-        wb = None
+        best, accuracy = self._choose(ctx, X, lab, held)
+        tr = dict(grid=best, accuracy=accuracy, labels=[])
+        state = None
         for it in range(self.max_iter):
             tr['labels'].append(lab.copy())
-            wb = self._fit(fit, X, lab[None, :], np.asarray([GRID[best]]), wb)
-            tr['wb'].append(wb[0].copy())
-            s = scores_of(X, wb)[0]
-            if it + 1 < self.max_iter:          # (the last round's weights are the model: no labels after it)
+            s, state = self._round(ctx, X, lab, best, tr, state)
+            if it + 1 < self.max_iter:          # (the last round's model is the model: no labels after it)
                 lab = self._labels(s, target, train)
                 if not (lab == 1).any():
                     raise _Fallback('no target passes the training FDR on the model score')
@@ -358,10 +331,7 @@ class PercolatorTDC:
         cos = np.asarray(cosine, np.float64)
         m = len(F)
         self.trace = []
-        if self.solver is None:
-            fit, scores_of, prepare = _device_solver(self.device)
-        else:
-            (fit, scores_of), prepare = self.solver, (lambda X: X)
+        ctx, prepare = self._open()
         if m < self.folds or target.all() or not target.any():
             raise _Fallback('too few SSMs, or one class only')
         if not np.isfinite(F).all():        # (the reference's LinearSVC refuses them too)
@@ -374,7 +344,7 @@ class PercolatorTDC:
             X = FeatureScaler().fit(Fs[train]).transform(Fs)
             if X.shape[1] == 0:
                 raise _Fallback('no feature with variance')
-            s = self._train(fit, scores_of, X, target, cos, train, fold)[test]
+            s = self._train(ctx, self._model_input(ctx, X, train), target, cos, train, fold)[test]
             t = target[test]
             q = tdc_qvalues(s, t)
             passing = t & (q <= self.fdr)
@@ -399,7 +369,8 @@ class PercolatorTDC:
             rows, F = feature_table(table)
             score, q = self.score_features(F, target[rows], F[:, MODEL_COLUMNS.index('cosine')], groups[rows])
         except _Fallback as e:
-            logging.warning('PercolatorTDC falls back to the cosine (CosineTDC) for this %s level: %s', mode, e)
+            logging.warning('%s falls back to the cosine (CosineTDC) for this %s level: %s', type(self).__name__,
+                            mode, e)
             self.fallback = True
             gate = CosineTDC(self.min_group_size)
             gate(table, mode)
@@ -414,12 +385,182 @@ class PercolatorTDC:
         return None
 
 
+class PercolatorTDC(_SemiSupervisedTDC):
+    """The reference's ``--model svm`` (mokapot's ``PercolatorModel`` under ``brew``), restated:
+
+    1. the SSMs with peak matches are split into ``folds`` parts by a seeded permutation;
+    2. per part, a model is trained on the other parts: the features are scaled (``FeatureScaler``, fitted on
+       the training rows); the start labels come from the cosine by TDC at ``fdr`` in the direction that passes
+       more targets (+1 target with q <= fdr, 0 other target, -1 decoy); the class weights are chosen once from
+       ``GRID`` by a seeded 3-fold inner cross-validation (accuracy on the held-out labelled rows, the first of
+       equal means) -- 27 problems in ONE ``l2svm_fit`` call; then ``max_iter`` rounds of fit on the rows
+       labelled +-1, score the training rows, relabel by TDC at ``fdr``. The LAST round's weights are the model;
+    3. every part is scored by its model and calibrated: (s - s_t) / (s_t - s_d), s_t the lowest score of a
+       target passing ``fdr``, s_d the median decoy score;
+    4. merged; q-values by TDC, per mass-difference group at ``mode == 'open'`` as ``CosineTDC``;
+    5. targets get the calibrated score and q, decoys and SSMs without peak matches NaN for both.
+
+    A stage without a passing target, or a training set with one class only: ``CosineTDC`` for that call, a
+    warning, ``self.fallback = True``. ``solver``: the ``(fit, scores)`` pair, default the device's
+    (``_lib.l2svm_fit``, ``_lib.linear_scores`` with the matrix on ``device``). ``self.trace`` keeps, per fold,
+    the grid point chosen, the labels of every round and the weights, for the tests."""
+    def __init__(self, fdr: float = 0.01, min_group_size: int = 100, folds: int = 3, max_iter: int = 10,
+                 seed: int = 1, solver=None, device='cuda', C: float = 1.0):
+        super().__init__(fdr, min_group_size, folds, max_iter, seed, solver, device)
+        self.C = float(C)
+        self.n_newton = 0
+
+    def _open(self):
+        if self.solver is None:
+            fit, scores_of, prepare = _device_solver(self.device)
+        else:
+            (fit, scores_of), prepare = self.solver, (lambda X: X)
+        return (fit, scores_of), prepare
+
+    def _fit(self, fit, X, label, cw, wb=None):
+        wb, _, steps, status = fit(X, label, cw, C=self.C, gtol_abs=GTOL_ABS, gtol_rel=GTOL_REL, wb=wb)
+        self.n_fit_calls += 1
+        self.n_newton += int(np.max(steps)) if len(steps) else 0
+        if np.any(status != 0):
+            logging.debug('l2svm_fit: status %s after %s Newton steps', status.tolist(), steps.tolist())
+        return wb
+
+    def _choose(self, ctx, X, lab, held):
+        # class weights: 9 grid points x 3 inner folds over the labelled rows, one fit, one scoring call
+        fit, scores_of = ctx
+        P = len(GRID) * INNER_FOLDS
+        labels = np.repeat(lab[None, :], P, axis=0)
+        cw = np.zeros((P, 2))
+        for g, pair in enumerate(GRID):
+            for f in range(INNER_FOLDS):
+                labels[g * INNER_FOLDS + f, held[f]] = 0
+                cw[g * INNER_FOLDS + f] = pair
+        s = scores_of(X, self._fit(fit, X, labels, cw))
+        acc = np.zeros((len(GRID), INNER_FOLDS))
+        for g in range(len(GRID)):
+            for f in range(INNER_FOLDS):
+                pred = np.where(s[g * INNER_FOLDS + f, held[f]] > 0, 1, -1)
+                acc[g, f] = np.mean(pred == lab[held[f]]) if len(held[f]) else 0.0
+        return int(np.argmax(acc.mean(axis=1))), acc.mean(axis=1)     # the first of equal means
+
+    def _round(self, ctx, X, lab, best, tr, wb):
+        fit, scores_of = ctx
+        wb = self._fit(fit, X, lab[None, :], np.asarray([GRID[best]]), wb)
+        tr.setdefault('wb', []).append(wb[0].copy())
+        return scores_of(X, wb)[0], wb
+
+
+#: the reference's forest grid (utils.py:156-179) in ``ParameterGrid``'s key order: class weight major, depth
+#: fastest; class weights as (weight of decoys, weight of targets), ``None`` = (1, 1); depth ``None`` = 12
+FOREST_CLASS_WEIGHTS = ((1.0, 1.0), (0.1, 1.0), (0.1, 10.0), (1.0, 0.1), (1.0, 10.0), (10.0, 0.1), (10.0, 1.0))
+FOREST_DEPTHS = (3, 5, 7, 9, 12)
+FOREST_GRID = tuple((cw, depth) for cw in FOREST_CLASS_WEIGHTS for depth in FOREST_DEPTHS)
+
+
+def _forest_device_solver(device):
+    """(bin, fit, predict) over ``asl_forest_*`` with the matrix and the models resident on ``device``."""
+    from . import _lib
+
+    def prepare(X):
+        import torch
+        return torch.as_tensor(X, dtype=torch.float64).to(device).contiguous()
+
+    def predict(bins, d, model, max_depth=None):
+        return _lib.forest_predict(bins, d, model, max_depth).cpu().numpy()
+    return (_lib.forest_bin, _lib.forest_fit, predict), prepare
+
+
+def forest_bin_edges(X, train):
+    """``(edges [d, 255], n_edges [d])`` of the binning (DESIGN.md 3 "Rescoring model: forest"): per column of
+    ``X`` the sorted values over the rows ``train`` at the ranks ``floor(k * n_train / 256)``, k = 1 .. 255,
+    duplicates removed. No interpolation: the host's sort and the device's give the same edges bit for bit."""
+    ranks = (np.arange(1, 256) * len(train)) // 256
+    if hasattr(X, 'data_ptr'):
+        import torch
+        S = torch.sort(X[torch.as_tensor(train, device=X.device)], dim=0).values
+        S = S[torch.as_tensor(ranks, device=X.device)].cpu().numpy() if len(train) else np.zeros((0, X.shape[1]))
+    else:
+        S = np.sort(np.asarray(X, np.float64)[train], axis=0)[ranks] if len(train) else np.zeros((0, X.shape[1]))
+    d = int(X.shape[1])
+    edges, n_edges = np.zeros((d, 255)), np.zeros(d, np.int32)
+    for j in range(d if len(S) else 0):
+        e = np.unique(S[:, j])
+        edges[j, :len(e)], n_edges[j] = e, len(e)
+    return edges, n_edges
+
+
+class ForestTDC(_SemiSupervisedTDC):
+    """The reference's ``--model rf`` (its default: a ``GridSearchCV(RandomForestClassifier)`` under mokapot's
+    ``brew``), restated with a HISTOGRAM forest grown on the device (``Config.device_forest``; csrc/forest.hip;
+    DESIGN.md 3 "Rescoring model: forest" lists every deviation from scikit-learn's exact-split forest). The five
+    steps, the fallbacks and the ``trace`` are ``PercolatorTDC``'s; what differs:
+
+    * the scaled matrix is binned per fold (``forest_bin_edges`` over the fold's training rows, ``forest_bin``);
+    * the score is ``proba``, the forest's mean leaf value (mokapot: ``predict_proba[:, 1]``);
+    * the grid is ``FOREST_GRID``, 7 class weights x 5 depths: the 7 x 3 problems are ONE ``forest_fit`` call at
+      depth 12, the five depths five ``forest_predict`` calls on it -- a tree cut at depth d is the tree grown to
+      depth d; a held-out row is predicted +1 iff ``proba > 0.5``; the first of equal mean accuracies wins;
+    * every relabelling round is one ``forest_fit`` with P = 1 at the chosen depth, then one ``forest_predict``.
+
+    ``solver``: the ``(bin, fit, predict)`` triple, default the device's (``_lib.forest_bin`` / ``forest_fit`` /
+    ``forest_predict`` with the matrix on ``device``)."""
+
+    def __init__(self, fdr: float = 0.01, min_group_size: int = 100, folds: int = 3, max_iter: int = 10,
+                 seed: int = 1, solver=None, device='cuda', trees: int = 100):
+        super().__init__(fdr, min_group_size, folds, max_iter, seed, solver, device)
+        self.trees = int(trees)
+        if self.trees < 1:
+            raise ValueError('ForestTDC: trees >= 1')
+
+    def _open(self):
+        if self.solver is None:
+            return _forest_device_solver(self.device)
+        return tuple(self.solver), (lambda X: X)
+
+    def _model_input(self, ctx, X, train):
+        edges, n_edges = forest_bin_edges(X, train)
+        return ctx[0](X, edges, n_edges), int(X.shape[1]), n_edges + 1
+
+    def _choose(self, ctx, X, lab, held):
+        (_, fit, predict), (bins, d, n_bins) = ctx, X
+        P = len(FOREST_CLASS_WEIGHTS) * INNER_FOLDS
+        labels = np.repeat(lab[None, :], P, axis=0)
+        cw = np.zeros((P, 2))
+        for g, pair in enumerate(FOREST_CLASS_WEIGHTS):
+            for f in range(INNER_FOLDS):
+                labels[g * INNER_FOLDS + f, held[f]] = 0
+                cw[g * INNER_FOLDS + f] = pair
+        model = fit(bins, d, labels, cw, trees=self.trees, max_depth=max(FOREST_DEPTHS), seed=self.seed,
+                    n_bins=n_bins)
+        self.n_fit_calls += 1
+        acc = np.zeros((len(FOREST_CLASS_WEIGHTS), len(FOREST_DEPTHS), INNER_FOLDS))
+        for k, depth in enumerate(FOREST_DEPTHS):
+            proba = predict(bins, d, model, depth)
+            for g in range(len(FOREST_CLASS_WEIGHTS)):
+                for f in range(INNER_FOLDS):
+                    pred = np.where(proba[g * INNER_FOLDS + f, held[f]] > 0.5, 1, -1)
+                    acc[g, k, f] = np.mean(pred == lab[held[f]]) if len(held[f]) else 0.0
+        mean = acc.mean(axis=2).reshape(-1)             # class-weight major, depth fastest: FOREST_GRID's order
+        return int(np.argmax(mean)), mean               # the first of equal means
+
+    def _round(self, ctx, X, lab, best, tr, state):
+        (_, fit, predict), (bins, d, n_bins) = ctx, X
+        cw, depth = FOREST_GRID[best]
+        model = fit(bins, d, lab[None, :], np.asarray([cw]), trees=self.trees, max_depth=depth, seed=self.seed,
+                    n_bins=n_bins)
+        self.n_fit_calls += 1
+        return predict(bins, d, model, depth)[0], None
+
+
 def make_scorer(config, device='cuda'):
     """The scorer ``Config.device_fdr`` stands for: ``model`` None / 'none' -> ``CosineTDC``, 'svm' ->
-    ``PercolatorTDC``; anything else (the reference's 'rf' included) is a ``ValueError``."""
+    ``PercolatorTDC``; 'rf' with ``device_forest`` -> ``ForestTDC``; anything else (the reference's 'rf' without
+    that switch included) is a ``ValueError``."""
     model = config.model
     if model is None or model == 'none':
         return CosineTDC(config.fdr_min_group_size)
     if model == 'svm':
         return PercolatorTDC(config.fdr, config.fdr_min_group_size, device=device)
+    if model == 'rf' and getattr(config, 'device_forest', False):
+        return ForestTDC(config.fdr, config.fdr_min_group_size, device=device, trees=config.forest_trees)
     raise ValueError(f"device_fdr: model = {model!r} is not provided; None / 'none' (cosine) or 'svm'")

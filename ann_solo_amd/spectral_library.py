@@ -844,8 +844,8 @@ class SpectralLibrary:
         ``SSMTable`` itself instead, writes ``table.q`` (and ``table.score``) and may return a
         keep-mask -- no per-SSM Python objects on the search path; one with ``uses_features = True``
         also finds the batches' 33 similarity columns in ``table.features``. Default: with
-        ``Config.device_fdr`` the engine's own scorer (fdr.py: ``CosineTDC`` or ``PercolatorTDC`` by
-        ``Config.model``), else cosine as the score, q = 0 (everything accepted).
+        ``Config.device_fdr`` the engine's own scorer (fdr.py: ``CosineTDC``, ``PercolatorTDC`` or, with
+        ``Config.device_forest``, ``ForestTDC`` by ``Config.model``), else cosine as the score, q = 0 (everything accepted).
 
         With ``Config.chimeric_search`` one more level follows the last one (``_chimeric_level``): the peaks
         every accepted identification explains are taken out of its query and the residue is searched again

@@ -817,6 +817,63 @@ int asl_l2svm_fit(const double *X /* [n, d] row-major */, int64_t n, int32_t d,
 int asl_linear_scores(const double *X, int64_t n, int32_t d, const double *wb, int32_t P,
                       double *out /* [P, n] */);
 
+/* ------------------------------------------------------------------ SSM rescoring model: forest
+ * The model behind utils.score_ssms(model = 'rf'), restated as a HISTOGRAM forest (DESIGN.md 3 "Rescoring
+ * model: forest"; csrc/forest.hip): every column of the matrix is a uint8 bin index, a split is (column, s)
+ * with bins <= s going left, the criterion is Gini on class-weighted INTEGER counts, evaluated in fp64 in one
+ * written order, and every random draw is a counter-based integer hash. Equal inputs give equal bits, and the
+ * numpy restatement tests/forest_ref.py reproduces every node and every probability bit for bit. */
+#define ASL_FOREST_MAX_BINS  256
+#define ASL_FOREST_MAX_DEPTH 12
+#define ASL_FOREST_MAX_TREES 1024
+#define ASL_FOREST_NODES     8191 /* 2^(ASL_FOREST_MAX_DEPTH + 1) - 1: a complete heap, children 2i+1 / 2i+2 */
+#define ASL_FOREST_ROW       64   /* bytes of a binned row (d <= ASL_SVM_MAX_DIM = 63: one row, one line) */
+typedef struct {
+  int32_t trees;      /* 1 .. ASL_FOREST_MAX_TREES */
+  int32_t max_depth;  /* 1 .. ASL_FOREST_MAX_DEPTH: levels of splits; the leaves of a full tree are at this level */
+  uint32_t seed;
+} asl_forest_params_t;
+/* P forests of `trees` heaps each; every array is [P, trees, ASL_FOREST_NODES], host or device memory.
+ * col: the split column, -1 = a leaf or an absent node; bin: the split bin s (bins <= s go left);
+ * n0 / n1: the node's in-bag count of the -1 / +1 class, with multiplicity; value = w1 / (w0 + w1) with
+ * w_c = cw[p, c] * n_c (0.5 where w0 + w1 = 0), kept for internal nodes too: a forest grown to depth D and
+ * read at depth d <= D IS the forest grown to depth d. */
+typedef struct {
+  int32_t trees, max_depth;   /* written by asl_forest_fit, read by asl_forest_predict */
+  int16_t *col;
+  uint8_t *bin;
+  uint32_t *n0, *n1;
+  double *value;
+} asl_forest_model_t;
+/* out[i, j] = the number of edges[j, 0 .. n_edges[j]) that are < X[i, j] (edges ascending), as a byte;
+ * out is [n, ASL_FOREST_ROW], bytes d .. 63 of a row are 0. edges: [d, ASL_FOREST_MAX_BINS - 1] doubles.
+ * d > 63: ASL_ERR_CAPACITY; d < 1, n < 0, an n_edges outside 0 .. 255: ASL_ERR_INVALID. */
+int asl_forest_bin(const double *X /* [n, d] */, int64_t n, int32_t d, const double *edges,
+                   const int32_t *n_edges /* [d] */, uint8_t *out /* [n, 64] */);
+/* Grows P forests over ONE binned matrix. label[p, i] in {+1, -1, 0}; 0 = row i is not part of problem p.
+ * cw[p, 0] / cw[p, 1]: weight of the -1 / +1 class. n_bins[j] (or NULL: 256 each): bins of column j.
+ * Tree t draws n rows with replacement from all n rows (shared by the P problems) and, per node,
+ * mtry = max(1, floor(sqrt(d))) distinct columns keyed by (seed, t, node); the best (column, bin) among them
+ * maximises (wL1^2 + wL0^2) / wL + (wR1^2 + wR0^2) / wR, must exceed the node's (w1^2 + w0^2) / w strictly and
+ * leave at least one in-bag row and a positive weight on either side; ties: the first drawn column, then the
+ * lowest bin. A node of one class, or without such a split, is a leaf.
+ * Checked on the host before anything is launched or written: d > 63, P > 32, max_depth > 12 or trees above
+ * the cap: ASL_ERR_CAPACITY; d < 1, P < 1, n < 0 or n >= 2^31, trees < 1, max_depth < 1, a label outside
+ * {-1, 0, +1}, a negative or non-finite class weight, an n_bins outside 1 .. 256 or a bin >= its column's
+ * n_bins: ASL_ERR_INVALID. n = 0, a problem whose labels are all 0 or of one class only are legal: the root is
+ * then a leaf, with value 0.5 for a problem without rows and 0 or 1 for a single class. */
+int asl_forest_fit(const uint8_t *bins /* [n, 64] */, int64_t n, int32_t d, const int8_t *label /* [P, n] */,
+                   const double *cw /* [P, 2] */, int32_t P, const int32_t *n_bins /* [d] or NULL */,
+                   const asl_forest_params_t *params, asl_forest_model_t *model_out);
+/* proba[p, i] = the mean over the trees of forest p, summed in tree order in fp64, of the value of the node
+ * where row i stops when it walks at most max_depth levels (0 .. 12; may be lower than the grown depth). */
+int asl_forest_predict(const uint8_t *bins /* [n, 64] */, int64_t n, int32_t d, const asl_forest_model_t *model,
+                       int32_t P, int32_t max_depth, double *proba /* [P, n] */);
+/* Bytes of device workspace one batch of (problem, tree) pairs may take while a level is grown (per pair: the
+ * rows' node indices and the level's histograms); at least one pair always runs. Returns the previous value,
+ * or a negative error for bytes <= 0. Default 2^31. The result does not depend on it. */
+int64_t asl_set_forest_workspace(int64_t bytes);
+
 /* ------------------------------------------------------------------ hot path
  * One batch of same-charge queries through
  *   SpectralLibrary._search_batch / _get_library_candidates
