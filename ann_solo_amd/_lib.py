@@ -93,6 +93,7 @@ EXPORTS = [
     'asl_localize_batch', 'asl_deplete_batch',
     'asl_l2svm_fit', 'asl_linear_scores',
     'asl_forest_bin', 'asl_forest_fit', 'asl_forest_predict', 'asl_set_forest_workspace',
+    'asl_tdc_qvalues',
 ]
 
 SVM_MAX_DIM = 63          # include/annsolo_mi.h: ASL_SVM_MAX_DIM
@@ -338,6 +339,8 @@ def lib():
                                              C.c_int32, C.c_void_p]
             L.asl_set_forest_workspace.argtypes = [C.c_int64]
             L.asl_set_forest_workspace.restype = C.c_int64
+        if hasattr(L, 'asl_tdc_qvalues'):
+            L.asl_tdc_qvalues.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]
         if hasattr(L, 'asl_index_set_by_residual'):
             L.asl_index_set_by_residual.argtypes = [C.c_void_p, C.c_int32]
             L.asl_index_get_by_residual.argtypes = [C.c_void_p]
@@ -607,3 +610,51 @@ def set_forest_workspace(nbytes: int) -> int:
     if prev <= 0:
         check(int(prev))
     return int(prev)
+
+
+TDC_TILE = 1024           # ASL_TDC_TILE
+
+
+def _as_column(a, like, np_dtype, n: int, what: str):
+    """``a`` as a contiguous ``[n]`` column of ``np_dtype`` (bool columns as 0 / 1 bytes) of the kind ``like``
+    is: a torch tensor on ``like``'s device, or numpy."""
+    if hasattr(like, 'data_ptr'):
+        import torch
+        dt = getattr(torch, np.dtype(np_dtype).name)
+        a = torch.as_tensor(a, device=like.device) if not hasattr(a, 'data_ptr') else a.to(like.device)
+        a = (a != 0).to(dt) if np_dtype is np.uint8 else a.to(dt)
+        a = a.contiguous()
+    else:
+        if hasattr(a, 'cpu'):
+            a = a.cpu().numpy()
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a != 0, np.uint8) if np_dtype is np.uint8 else np.ascontiguousarray(a, np_dtype)
+    if a.ndim != 1 or int(a.shape[0]) != n:
+        raise ValueError(f'{what}: [{n}] expected, got {tuple(a.shape)}')
+    return a
+
+
+def tdc_qvalues(score, is_target, group=None, use=None, desc: bool = True, fdr=None):
+    """``asl_tdc_qvalues``: q-values by target-decoy competition (``fdr.tdc_qvalues``) inside every group
+    (``fdr._grouped_q``) over the rows where ``use`` is non-zero (default: all). ``score [n]`` float64 (numpy or
+    torch, host or device), ``is_target [n]`` and ``use [n]`` bool or 0 / non-0, ``group [n]`` int32 ids
+    (default: one group), ``desc``: a higher score is better. Returns ``q [n]`` (NaN for unused rows), or with
+    ``fdr`` given ``(q, label)``: label int8, +1 used target with q <= fdr, 0 other used target and every
+    unused row, -1 used decoy. The outputs live where ``score`` lives (numpy, or torch on its device)."""
+    score = _as_f64(score, 1, 'score')
+    n = int(score.shape[0])
+    is_target = _as_column(is_target, score, np.uint8, n, 'is_target')
+    group = None if group is None else _as_column(group, score, np.int32, n, 'group')
+    use = None if use is None else _as_column(use, score, np.uint8, n, 'use')
+    if hasattr(score, 'data_ptr'):
+        import torch
+        q = torch.empty(n, dtype=torch.float64, device=score.device)
+        label = None if fdr is None else torch.empty(n, dtype=torch.int8, device=score.device)
+    else:
+        q = np.empty(n, np.float64)
+        label = None if fdr is None else np.empty(n, np.int8)
+    check(lib().asl_tdc_qvalues(ptr(score) if n else None, ptr(is_target) if n else None,
+                                ptr(group) if n else None, ptr(use) if n else None, n, 1 if desc else 0,
+                                0.0 if fdr is None else float(fdr), ptr(q) if n else None,
+                                ptr(label) if n and label is not None else None))
+    return q if fdr is None else (q, label)

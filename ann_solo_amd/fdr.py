@@ -15,7 +15,10 @@ parity with mokapot.
   * ``ForestTDC``      -- ``--model rf`` WITH ``--device_forest``: the same procedure around a histogram forest
     grown and evaluated on the device by ``asl_forest_fit`` / ``asl_forest_predict`` (csrc/forest.hip). It is a
     restatement too -- a binned forest, not scikit-learn's exact-split one (DESIGN.md 3 "Rescoring model:
-    forest") -- so ``--model rf`` alone does not stand for it: without the switch ``rf`` is not provided."""
+    forest") -- so ``--model rf`` alone does not stand for it: without the switch ``rf`` is not provided.
+
+All three take ``qvalues='device'`` (``Config.device_qvalues``): their target-decoy q-values then come from
+``asl_tdc_qvalues`` (csrc/tdc.hip) instead of ``tdc_qvalues`` / ``_grouped_q`` below, byte for byte the same."""
 import logging
 from typing import Optional
 
@@ -125,16 +128,40 @@ def _grouped_q(scores, target, groups) -> np.ndarray:
     return q
 
 
+def _device_tdc(device):
+    """``tdc(scores, target, group=None, use=None, desc=True, fdr=None)`` over ``asl_tdc_qvalues`` (csrc/tdc.hip):
+    the columns go to ``device``, ``q`` -- and the labels where ``fdr`` is given -- come back as numpy."""
+    from . import _lib
+
+    def tdc(scores, target, group=None, use=None, desc=True, fdr=None):
+        import torch
+
+        def put(a, dtype):
+            return None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype)).to(device)
+        out = _lib.tdc_qvalues(put(scores, np.float64), put(target, np.uint8), put(group, np.int32),
+                               put(use, np.uint8), desc, fdr)
+        return out.cpu().numpy() if fdr is None else tuple(o.cpu().numpy() for o in out)
+    return tdc
+
+
+def _check_qvalues(qvalues):
+    if qvalues not in (None, 'device'):
+        raise ValueError(f"qvalues = {qvalues!r}: None (numpy on the host) or 'device' (asl_tdc_qvalues)")
+    return qvalues
+
+
 class CosineTDC:
     """The reference's ``--model none``: q-values from the cosine by target-decoy competition, grouped by
     mass difference for the open level (utils.py:118, :139-142). Targets get their cosine as
     ``search_engine_score`` and a q-value; decoys keep NaN for both (mokapot's confidence table lists targets
-    only, utils.py:186-200), so the ``q < fdr`` gate drops them."""
+    only, utils.py:186-200), so the ``q < fdr`` gate drops them. ``qvalues='device'`` (``Config.device_qvalues``):
+    the grouped q-values are one ``asl_tdc_qvalues`` call on ``device`` instead of numpy -- the same bytes."""
     columnar = True
 
-    def __init__(self, min_group_size: int = 100):
+    def __init__(self, min_group_size: int = 100, qvalues=None, device='cuda'):
         self.min_group_size = int(min_group_size)
         self.n_groups: Optional[int] = None      # of the last grouped call (utils.py:127-131)
+        self.qvalues, self.device = _check_qvalues(qvalues), device     # 'device': one grouped asl_tdc_qvalues call
 
     def __call__(self, table, mode: str):
         target = ~table.is_decoy()
@@ -142,7 +169,8 @@ class CosineTDC:
         groups = _level_groups(table, mode, self.min_group_size)
         if mode == 'open':
             self.n_groups = len(np.unique(groups))
-        q = _grouped_q(cos, target, groups)
+        q = _grouped_q(cos, target, groups) if self.qvalues is None else \
+            _device_tdc(self.device)(cos, target, group=groups)
         table.q = np.where(target, q, np.nan)
         table.score = np.where(target, cos, np.nan)
         return None
@@ -272,17 +300,25 @@ class _SemiSupervisedTDC:
       ``_open()``                      -> ``(ctx, prepare)``: the solver and where it wants the matrix;
       ``_model_input(ctx, X, train)``  -> what the solver reads in place of the scaled matrix (default: ``X``);
       ``_choose(ctx, X, lab, held)``   -> ``(grid point, mean held-out accuracies)``;
-      ``_round(ctx, X, lab, best, tr, state)`` -> ``(scores of all rows, state)``: one fit on the labelled rows."""
+      ``_round(ctx, X, lab, best, tr, state)`` -> ``(scores of all rows, state)``: one fit on the labelled rows.
+
+    ``qvalues``: ``None`` -- every target-decoy competition is ``tdc_qvalues`` in numpy; ``'device'``
+    (``Config.device_qvalues``) -- each is one ``asl_tdc_qvalues`` call on ``device`` (csrc/tdc.hip; DESIGN.md 3
+    "Target-decoy q-values"): the labels of a round with the training rows as ``use``, the held-out q, the grouped
+    q with ``group``. The bytes are the same; ``trace['labels']`` stays numpy."""
     columnar = True
     uses_features = True        # SpectralLibrary: the level keeps the batches' 33 similarity columns
 
     def __init__(self, fdr: float = 0.01, min_group_size: int = 100, folds: int = 3, max_iter: int = 10,
-                 seed: int = 1, solver=None, device='cuda'):
+                 seed: int = 1, solver=None, device='cuda', qvalues=None):
         if folds < 2 or max_iter < 1:
             raise ValueError(f'{type(self).__name__}: folds >= 2 and max_iter >= 1')
         self.fdr, self.min_group_size = float(fdr), int(min_group_size)
         self.folds, self.max_iter, self.seed = int(folds), int(max_iter), int(seed)
         self.solver, self.device = solver, device
+        # None: numpy on the host; 'device': every TDC of the procedure is one asl_tdc_qvalues call (the same bytes)
+        self._tdc = _device_tdc(device) if _check_qvalues(qvalues) == 'device' else None
+        self.qvalues = qvalues
         self.fallback = False
         self.n_groups: Optional[int] = None
         self.trace: list = []
@@ -293,6 +329,10 @@ class _SemiSupervisedTDC:
 
     def _labels(self, scores, target, train, desc=True):
         """(+1 target with q <= fdr, 0 other target, -1 decoy) over the rows ``train``, 0 elsewhere."""
+        if self._tdc is not None:
+            use = np.zeros(len(scores), np.uint8)
+            use[train] = 1
+            return self._tdc(scores, target, use=use, desc=desc, fdr=self.fdr)[1]
         lab = np.zeros(len(scores), np.int8)
         q = tdc_qvalues(scores[train], target[train], desc)
         t = target[train]
@@ -346,7 +386,7 @@ class _SemiSupervisedTDC:
                 raise _Fallback('no feature with variance')
             s = self._train(ctx, self._model_input(ctx, X, train), target, cos, train, fold)[test]
             t = target[test]
-            q = tdc_qvalues(s, t)
+            q = tdc_qvalues(s, t) if self._tdc is None else self._tdc(s, t)
             passing = t & (q <= self.fdr)
             if not passing.any() or t.all():
                 raise _Fallback('no target of a held-out part passes the FDR')
@@ -355,7 +395,8 @@ class _SemiSupervisedTDC:
                 raise _Fallback('a held-out part whose targets do not score above its decoys')
             score[test] = (s - s_t) / (s_t - s_d)
         groups = np.zeros(m, np.int32) if groups is None else np.asarray(groups)
-        return score, _grouped_q(score, target, groups)
+        return score, (_grouped_q(score, target, groups) if self._tdc is None else
+                       self._tdc(score, target, group=groups))
 
     # -- the scorer ---------------------------------------------------------------------------------------
     def __call__(self, table, mode: str):
@@ -372,7 +413,7 @@ class _SemiSupervisedTDC:
             logging.warning('%s falls back to the cosine (CosineTDC) for this %s level: %s', type(self).__name__,
                             mode, e)
             self.fallback = True
-            gate = CosineTDC(self.min_group_size)
+            gate = CosineTDC(self.min_group_size, self.qvalues, self.device)
             gate(table, mode)
             self.n_groups = gate.n_groups
             return None
@@ -405,8 +446,8 @@ class PercolatorTDC(_SemiSupervisedTDC):
     (``_lib.l2svm_fit``, ``_lib.linear_scores`` with the matrix on ``device``). ``self.trace`` keeps, per fold,
     the grid point chosen, the labels of every round and the weights, for the tests."""
     def __init__(self, fdr: float = 0.01, min_group_size: int = 100, folds: int = 3, max_iter: int = 10,
-                 seed: int = 1, solver=None, device='cuda', C: float = 1.0):
-        super().__init__(fdr, min_group_size, folds, max_iter, seed, solver, device)
+                 seed: int = 1, solver=None, device='cuda', C: float = 1.0, qvalues=None):
+        super().__init__(fdr, min_group_size, folds, max_iter, seed, solver, device, qvalues)
         self.C = float(C)
         self.n_newton = 0
 
@@ -506,8 +547,8 @@ class ForestTDC(_SemiSupervisedTDC):
     ``forest_predict`` with the matrix on ``device``)."""
 
     def __init__(self, fdr: float = 0.01, min_group_size: int = 100, folds: int = 3, max_iter: int = 10,
-                 seed: int = 1, solver=None, device='cuda', trees: int = 100):
-        super().__init__(fdr, min_group_size, folds, max_iter, seed, solver, device)
+                 seed: int = 1, solver=None, device='cuda', trees: int = 100, qvalues=None):
+        super().__init__(fdr, min_group_size, folds, max_iter, seed, solver, device, qvalues)
         self.trees = int(trees)
         if self.trees < 1:
             raise ValueError('ForestTDC: trees >= 1')
@@ -555,12 +596,14 @@ class ForestTDC(_SemiSupervisedTDC):
 def make_scorer(config, device='cuda'):
     """The scorer ``Config.device_fdr`` stands for: ``model`` None / 'none' -> ``CosineTDC``, 'svm' ->
     ``PercolatorTDC``; 'rf' with ``device_forest`` -> ``ForestTDC``; anything else (the reference's 'rf' without
-    that switch included) is a ``ValueError``."""
+    that switch included) is a ``ValueError``. ``Config.device_qvalues`` hands every scorer ``qvalues='device'``."""
     model = config.model
+    qvalues = 'device' if getattr(config, 'device_qvalues', False) else None
     if model is None or model == 'none':
-        return CosineTDC(config.fdr_min_group_size)
+        return CosineTDC(config.fdr_min_group_size, qvalues=qvalues, device=device)
     if model == 'svm':
-        return PercolatorTDC(config.fdr, config.fdr_min_group_size, device=device)
+        return PercolatorTDC(config.fdr, config.fdr_min_group_size, device=device, qvalues=qvalues)
     if model == 'rf' and getattr(config, 'device_forest', False):
-        return ForestTDC(config.fdr, config.fdr_min_group_size, device=device, trees=config.forest_trees)
+        return ForestTDC(config.fdr, config.fdr_min_group_size, device=device, trees=config.forest_trees,
+                         qvalues=qvalues)
     raise ValueError(f"device_fdr: model = {model!r} is not provided; None / 'none' (cosine) or 'svm'")

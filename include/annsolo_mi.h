@@ -874,6 +874,32 @@ int asl_forest_predict(const uint8_t *bins /* [n, 64] */, int64_t n, int32_t d, 
  * or a negative error for bytes <= 0. Default 2^31. The result does not depend on it. */
 int64_t asl_set_forest_workspace(int64_t bytes);
 
+/* ------------------------------------------------------------------ target-decoy q-values
+ * The primitive of every FDR scorer (fdr.tdc_qvalues, fdr._grouped_q) on the device (csrc/tdc.hip; DESIGN.md 3
+ * "Target-decoy q-values"). Within a group, walking the used rows from best to worst: FDR = (decoys so far + 1)
+ * / targets so far, 1 while there is no target yet; rows of equal score (compared as doubles: -0.0 == +0.0) form
+ * one run, which takes the FDR at its end, capped at 1; q = the smallest FDR of this run or any worse run.
+ * Targets and decoys both get a q. The rows are ordered by an LSD radix sort of 8 bits a pass over the key
+ * (group id with its sign bit flipped, order-preserving map of the score's bits) in tiles of ASL_TDC_TILE keys;
+ * the counts are integer prefix sums, a run's end does one fp64 division, the rest is a min: equal inputs give
+ * equal bytes, and the bytes are those of the numpy code. */
+#define ASL_TDC_TILE 1024 /* keys per workgroup of a sort pass */
+/* q[i] for every used row, by target-decoy competition inside the row's group
+ * (fdr.tdc_qvalues per group = fdr._grouped_q).
+ * Every array is host or device memory, as the other entry points detect it; q and label are written where
+ * they live. Checked before q or label is written: n >= 2^31: ASL_ERR_CAPACITY (before any pointer is touched);
+ * n < 0, desc outside {0, 1}, a NaN or negative fdr when label is given, a NaN score in a used row:
+ * ASL_ERR_INVALID. Legal: n == 0 (launches nothing), +-inf scores, a NaN score in an unused row. */
+int asl_tdc_qvalues(const double *score      /* [n] */,
+                    const uint8_t *is_target /* [n], 0 / non-0 */,
+                    const int32_t *group     /* [n] or NULL: one group; any int32 value is a group id */,
+                    const uint8_t *use       /* [n] or NULL: all rows; rows with 0 take no part */,
+                    int64_t n, int32_t desc  /* 1: a higher score is better; 0: lower */,
+                    double fdr               /* read only when label is given */,
+                    double *q                /* [n]; NaN for unused rows */,
+                    int8_t *label            /* [n] or NULL: +1 used target with q <= fdr, 0 other used
+                                                target and every unused row, -1 used decoy */);
+
 /* ------------------------------------------------------------------ hot path
  * One batch of same-charge queries through
  *   SpectralLibrary._search_batch / _get_library_candidates
