@@ -29,7 +29,7 @@ SCORE_HIST_BINS = 128     # include/annsolo_mi.h: ASL_SCORE_HIST_BINS
 
 
 class AnnSoloMiError(RuntimeError):
-    pass
+    code = None     # the negative ASL_ERR_* value where the error came from the library (``check``)
 
 
 class AslPeaks(C.Structure):
@@ -94,6 +94,7 @@ EXPORTS = [
     'asl_l2svm_fit', 'asl_linear_scores',
     'asl_forest_bin', 'asl_forest_fit', 'asl_forest_predict', 'asl_set_forest_workspace',
     'asl_tdc_qvalues',
+    'asl_ssm_groups',
 ]
 
 SVM_MAX_DIM = 63          # include/annsolo_mi.h: ASL_SVM_MAX_DIM
@@ -341,6 +342,9 @@ def lib():
             L.asl_set_forest_workspace.restype = C.c_int64
         if hasattr(L, 'asl_tdc_qvalues'):
             L.asl_tdc_qvalues.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]
+        if hasattr(L, 'asl_ssm_groups'):
+            L.asl_ssm_groups.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, c_i64p, c_i64p, C.c_void_p,
+                                         C.c_void_p]
         if hasattr(L, 'asl_index_set_by_residual'):
             L.asl_index_set_by_residual.argtypes = [C.c_void_p, C.c_int32]
             L.asl_index_get_by_residual.argtypes = [C.c_void_p]
@@ -361,7 +365,9 @@ def lib():
 def check(rc: int):
     if rc != 0:
         msg = lib().asl_last_error()
-        raise AnnSoloMiError(f'libannsolo_mi error {rc}: {msg.decode() if msg else ""}')
+        err = AnnSoloMiError(f'libannsolo_mi error {rc}: {msg.decode() if msg else ""}')
+        err.code = int(rc)
+        raise err
 
 
 def ptr(a):
@@ -658,3 +664,37 @@ def tdc_qvalues(score, is_target, group=None, use=None, desc: bool = True, fdr=N
                                 0.0 if fdr is None else float(fdr), ptr(q) if n else None,
                                 ptr(label) if n and label is not None else None))
     return q if fdr is None else (q, label)
+
+
+GROUPS_MAX_SPAN = 65536   # ASL_GROUPS_MAX_SPAN
+ERR_INVALID, ERR_CAPACITY = -1, -4      # ASL_ERR_INVALID, ASL_ERR_CAPACITY
+
+
+def ssm_groups(mass_diff, min_group_size: int, profile: bool = False):
+    """``asl_ssm_groups``: the open level's mass-difference group labels (``fdr.ssm_groups``, the same bytes) from
+    ``mass_diff [n]`` float64 (numpy or torch, host or device). Returns ``(group [n] int32, n_labels)`` --
+    ``n_labels`` the number of distinct values in ``group``, -1 included when present -- or with ``profile``
+    ``(group, n_labels, peak_mass [n_peaks] float64, peak_size [n_peaks] int64)``: per id handed out BEFORE ids of
+    fewer than ``min_group_size`` SSMs were folded into -1, the left bin edge of its histogram peak and the SSMs
+    assigned to it. The arrays live where ``mass_diff`` lives. A non-finite value or a negative
+    ``min_group_size`` is ``AnnSoloMiError`` with ``code == ERR_INVALID``; nominal mass differences that span more
+    than ``GROUPS_MAX_SPAN`` intervals ``code == ERR_CAPACITY``."""
+    md = _as_f64(mass_diff, 1, 'mass_diff')
+    n = int(md.shape[0])
+    if hasattr(md, 'data_ptr'):
+        import torch
+
+        def empty(dtype):
+            return torch.empty(n, dtype=getattr(torch, dtype), device=md.device)
+    else:
+        def empty(dtype):
+            return np.empty(n, dtype)
+    group = empty('int32')
+    mass, size = (empty('float64'), empty('int64')) if profile else (None, None)
+    n_peaks, n_labels = C.c_int64(0), C.c_int64(0)
+    check(lib().asl_ssm_groups(ptr(md) if n else None, n, int(min_group_size), ptr(group) if n else None,
+                               byref(n_peaks), byref(n_labels), ptr(mass) if n and profile else None,
+                               ptr(size) if n and profile else None))
+    if not profile:
+        return group, int(n_labels.value)
+    return group, int(n_labels.value), mass[:n_peaks.value], size[:n_peaks.value]

@@ -6,7 +6,7 @@
 ``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``, ``pq_by_residual``,
 ``precursor_window_open``, ``fragment_tolerance_unit``, ``score_stats``, ``device_decoys``,
 ``decoy_tolerance_unit``, ``localize_modifications``, ``device_fdr``, ``device_forest``,
-``forest_trees``, ``device_qvalues``, ``chimeric_search``, ``chimeric_window``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``forest_trees``, ``device_qvalues``, ``device_groups``, ``chimeric_search``, ``chimeric_window``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -138,6 +138,10 @@ class Config:
     # the grouped step -- by ``asl_tdc_qvalues`` on the device (csrc/tdc.hip; DESIGN.md 3 "Target-decoy q-values")
     # in place of numpy on the host; the same bytes either way. Off: nothing new is launched
     device_qvalues: bool = False
+    # with device_fdr: the open level's mass-difference group labels by ``asl_ssm_groups`` on the device
+    # (csrc/groups.hip; DESIGN.md 3 "Mass-difference groups") in place of ``fdr.ssm_groups`` on the host; the same
+    # bytes either way, and the scorer keeps the modification profile (``group_profile``). Off: nothing new is launched
+    device_groups: bool = False
     # chimeric spectra (chimeric.py; DESIGN.md 3 "Chimeric search"): after the last cascade level every accepted
     # identification's explained peaks are removed from its query and the residue is searched once more, without
     # peak shifts, against the library rows of the same charge inside the query's isolation window -- the
@@ -230,6 +234,13 @@ class Config:
                                  f'device_fdr (device_fdr = {self.device_fdr})')
             if self.num_gpus and int(self.num_gpus) > 1:
                 raise ValueError('device_qvalues does not run on a sharded index (num_gpus > 1)')
+        self.device_groups = bool(self.device_groups)
+        if self.device_groups:
+            if not self.device_fdr:
+                raise ValueError("device_groups is the grouping step of the engine's own FDR step: it needs "
+                                 f'device_fdr (device_fdr = {self.device_fdr})')
+            if self.num_gpus and int(self.num_gpus) > 1:
+                raise ValueError('device_groups does not run on a sharded index (num_gpus > 1)')
         self.chimeric_search = bool(self.chimeric_search)
         self.chimeric_window = float(self.chimeric_window)
         if not self.chimeric_window >= 0.0:     # (NaN fails too)
@@ -413,6 +424,11 @@ def add_arguments(parser) -> None:
                         help="with --device_fdr: the FDR step's target-decoy q-values (every relabelling round, the "
                              'held-out parts, the grouped step) by a radix sort and scans on the GPU instead of '
                              'numpy on the host; the same bytes either way; one GPU (default: off)')
+    parser.add_argument('--device_groups', action='store_true', default=d.device_groups,
+                        help="with --device_fdr: the open level's mass-difference groups (histogram peaks per nominal "
+                             'mass difference) by integer histograms on the GPU instead of scipy on the host; the '
+                             'same labels either way, and the scorer keeps the modification profile; one GPU '
+                             '(default: off)')
     parser.add_argument('--chimeric_search', action='store_true', default=d.chimeric_search,
                         help='after the last cascade level, remove the peaks every accepted identification explains '
                              'from its query spectrum and search the residue once more (no peak shifts) among the '

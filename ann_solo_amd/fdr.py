@@ -18,7 +18,10 @@ parity with mokapot.
     forest") -- so ``--model rf`` alone does not stand for it: without the switch ``rf`` is not provided.
 
 All three take ``qvalues='device'`` (``Config.device_qvalues``): their target-decoy q-values then come from
-``asl_tdc_qvalues`` (csrc/tdc.hip) instead of ``tdc_qvalues`` / ``_grouped_q`` below, byte for byte the same."""
+``asl_tdc_qvalues`` (csrc/tdc.hip) instead of ``tdc_qvalues`` / ``_grouped_q`` below, byte for byte the same; and
+``groups='device'`` (``Config.device_groups``): the open level's group labels then come from ``asl_ssm_groups``
+(csrc/groups.hip) instead of ``ssm_groups`` below, byte for byte the same, and the scorer keeps the modification
+profile of the level as ``group_profile``."""
 import logging
 from typing import Optional
 
@@ -137,11 +140,18 @@ def _device_tdc(device):
         import torch
 
         def put(a, dtype):
-            return None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype)).to(device)
+            if a is None or hasattr(a, 'data_ptr'):      # (a column that is on the device already stays there)
+                return a
+            return torch.as_tensor(np.ascontiguousarray(a, dtype)).to(device)
         out = _lib.tdc_qvalues(put(scores, np.float64), put(target, np.uint8), put(group, np.int32),
                                put(use, np.uint8), desc, fdr)
         return out.cpu().numpy() if fdr is None else tuple(o.cpu().numpy() for o in out)
     return tdc
+
+
+def _as_index(rows, device):
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(rows, np.int64)).to(device)
 
 
 def _check_qvalues(qvalues):
@@ -150,28 +160,89 @@ def _check_qvalues(qvalues):
     return qvalues
 
 
-class CosineTDC:
+def _check_groups(groups):
+    if groups not in (None, 'device'):
+        raise ValueError(f"groups = {groups!r}: None (ssm_groups on the host) or 'device' (asl_ssm_groups)")
+    return groups
+
+
+class _OpenLevelGroups:
+    """The group column of a level, for the three scorers (they set ``groups``, ``qvalues``, ``device``,
+    ``min_group_size`` and ``fdr``). ``groups=None``: ``ssm_groups`` on the host. ``groups='device'``
+    (``Config.device_groups``): the open level's labels are one ``asl_ssm_groups`` call on ``device`` (csrc/groups.hip;
+    DESIGN.md 3 "Mass-difference groups"), the same bytes; with ``qvalues='device'`` the column stays a device
+    tensor and goes straight into ``asl_tdc_qvalues``, and ``n_groups`` is the call's ``n_labels``. After such an
+    open call ``group_profile`` holds the modification profile of the level as numpy columns: ``group`` (the ids
+    that remain, ascending, then -1), ``mass`` (the left edge of the group's histogram bin; NaN for -1), ``size``
+    (SSMs of the group; the rows sum to the table's length) and ``accepted`` (its targets with ``q < fdr``). Mass
+    differences that span more than ``ASL_GROUPS_MAX_SPAN`` intervals: one warning, ``ssm_groups`` on the host for
+    that call (the same labels) and no profile; a non-finite mass difference: ``ValueError``."""
+    group_profile = None
+
+    def _level_labels(self, table, mode: str):
+        """``(group column, its number of distinct labels or None)``; numpy unless both switches are 'device'."""
+        self.group_profile, self._peaks = None, None
+        if mode != 'open' or self.groups is None or len(table) == 0:
+            return _level_groups(table, mode, self.min_group_size), None
+        import torch
+        from . import _lib
+        md = table.mass_diffs()
+        try:
+            g, n_labels, mass, size = _lib.ssm_groups(
+                torch.as_tensor(np.ascontiguousarray(md, np.float64)).to(self.device), self.min_group_size, True)
+        except _lib.AnnSoloMiError as e:
+            if e.code == _lib.ERR_INVALID:
+                raise ValueError(f'non-finite precursor mass differences at the open level: {e}') from e
+            if e.code != _lib.ERR_CAPACITY:
+                raise
+            logging.warning('the mass differences of this open level span more than %d intervals: its groups come '
+                            'from ssm_groups on the host (%s)', _lib.GROUPS_MAX_SPAN, e)
+            return ssm_groups(md, self.min_group_size), None
+        self._peaks = (g, mass.cpu().numpy(), size.cpu().numpy())
+        return (g if self.qvalues == 'device' else g.cpu().numpy()), n_labels
+
+    def _publish_profile(self, target, q):
+        """``group_profile`` of the open call whose labels ``_level_labels`` took from the device; ``q [n]`` with
+        NaN where a row has none."""
+        if self._peaks is None:
+            return
+        g, mass, size = self._peaks
+        self._peaks = None
+        g = g.cpu().numpy()
+        kept = np.nonzero((size > 0) & (size >= self.min_group_size))[0]
+        hit = np.bincount(g[np.asarray(target, bool) & (np.asarray(q) < self.fdr)] + 1, minlength=len(size) + 1)
+        self.group_profile = dict(
+            group=np.append(kept, -1).astype(np.int32), mass=np.append(mass[kept], np.nan),
+            size=np.append(size[kept], len(g) - size[kept].sum()).astype(np.int64),
+            accepted=np.append(hit[kept + 1], hit[0]).astype(np.int64))
+
+
+class CosineTDC(_OpenLevelGroups):
     """The reference's ``--model none``: q-values from the cosine by target-decoy competition, grouped by
     mass difference for the open level (utils.py:118, :139-142). Targets get their cosine as
     ``search_engine_score`` and a q-value; decoys keep NaN for both (mokapot's confidence table lists targets
     only, utils.py:186-200), so the ``q < fdr`` gate drops them. ``qvalues='device'`` (``Config.device_qvalues``):
-    the grouped q-values are one ``asl_tdc_qvalues`` call on ``device`` instead of numpy -- the same bytes."""
+    the grouped q-values are one ``asl_tdc_qvalues`` call on ``device`` instead of numpy -- the same bytes.
+    ``groups='device'`` (``Config.device_groups``): ``_OpenLevelGroups``; ``fdr`` is the level ``group_profile``
+    counts its accepted targets at."""
     columnar = True
 
-    def __init__(self, min_group_size: int = 100, qvalues=None, device='cuda'):
+    def __init__(self, min_group_size: int = 100, qvalues=None, device='cuda', groups=None, fdr: float = 0.01):
         self.min_group_size = int(min_group_size)
+        self.groups, self.fdr = _check_groups(groups), float(fdr)
         self.n_groups: Optional[int] = None      # of the last grouped call (utils.py:127-131)
         self.qvalues, self.device = _check_qvalues(qvalues), device     # 'device': one grouped asl_tdc_qvalues call
 
     def __call__(self, table, mode: str):
         target = ~table.is_decoy()
         cos = np.asarray(table.score, np.float64)
-        groups = _level_groups(table, mode, self.min_group_size)
+        groups, n_labels = self._level_labels(table, mode)
         if mode == 'open':
-            self.n_groups = len(np.unique(groups))
+            self.n_groups = len(np.unique(groups)) if n_labels is None else n_labels
         q = _grouped_q(cos, target, groups) if self.qvalues is None else \
             _device_tdc(self.device)(cos, target, group=groups)
         table.q = np.where(target, q, np.nan)
+        self._publish_profile(target, table.q)
         table.score = np.where(target, cos, np.nan)
         return None
 
@@ -292,7 +363,7 @@ def _device_solver(device):
     return _lib.l2svm_fit, scores, prepare
 
 
-class _SemiSupervisedTDC:
+class _SemiSupervisedTDC(_OpenLevelGroups):
     """The procedure ``PercolatorTDC`` and ``ForestTDC`` share (mokapot's ``brew``, restated; the steps are listed
     under ``PercolatorTDC``): folds, start labels from the cosine, the parameter choice once per fold, ``max_iter``
     relabelling rounds, calibration, grouped TDC, the fallbacks and the ``trace``. A model supplies four hooks:
@@ -305,12 +376,12 @@ class _SemiSupervisedTDC:
     ``qvalues``: ``None`` -- every target-decoy competition is ``tdc_qvalues`` in numpy; ``'device'``
     (``Config.device_qvalues``) -- each is one ``asl_tdc_qvalues`` call on ``device`` (csrc/tdc.hip; DESIGN.md 3
     "Target-decoy q-values"): the labels of a round with the training rows as ``use``, the held-out q, the grouped
-    q with ``group``. The bytes are the same; ``trace['labels']`` stays numpy."""
+    q with ``group``. The bytes are the same; ``trace['labels']`` stays numpy. ``groups``: ``_OpenLevelGroups``."""
     columnar = True
     uses_features = True        # SpectralLibrary: the level keeps the batches' 33 similarity columns
 
     def __init__(self, fdr: float = 0.01, min_group_size: int = 100, folds: int = 3, max_iter: int = 10,
-                 seed: int = 1, solver=None, device='cuda', qvalues=None):
+                 seed: int = 1, solver=None, device='cuda', qvalues=None, groups=None):
         if folds < 2 or max_iter < 1:
             raise ValueError(f'{type(self).__name__}: folds >= 2 and max_iter >= 1')
         self.fdr, self.min_group_size = float(fdr), int(min_group_size)
@@ -318,7 +389,7 @@ class _SemiSupervisedTDC:
         self.solver, self.device = solver, device
         # None: numpy on the host; 'device': every TDC of the procedure is one asl_tdc_qvalues call (the same bytes)
         self._tdc = _device_tdc(device) if _check_qvalues(qvalues) == 'device' else None
-        self.qvalues = qvalues
+        self.qvalues, self.groups = qvalues, _check_groups(groups)
         self.fallback = False
         self.n_groups: Optional[int] = None
         self.trace: list = []
@@ -394,7 +465,10 @@ class _SemiSupervisedTDC:
             if not s_t > s_d:
                 raise _Fallback('a held-out part whose targets do not score above its decoys')
             score[test] = (s - s_t) / (s_t - s_d)
-        groups = np.zeros(m, np.int32) if groups is None else np.asarray(groups)
+        if groups is None:
+            groups = np.zeros(m, np.int32)
+        elif not hasattr(groups, 'data_ptr'):       # (a device column of groups='device' stays where it is)
+            groups = np.asarray(groups)
         return score, (_grouped_q(score, target, groups) if self._tdc is None else
                        self._tdc(score, target, group=groups))
 
@@ -405,24 +479,27 @@ class _SemiSupervisedTDC:
         if n == 0:              # an empty level (every query identified before it, say): nothing to score
             return None
         target = ~table.is_decoy()
-        groups = _level_groups(table, mode, self.min_group_size)
+        groups, n_labels = self._level_labels(table, mode)
         try:
             rows, F = feature_table(table)
-            score, q = self.score_features(F, target[rows], F[:, MODEL_COLUMNS.index('cosine')], groups[rows])
+            sub = groups[rows] if not hasattr(groups, 'data_ptr') else \
+                groups[_as_index(rows, groups.device)].contiguous()
+            score, q = self.score_features(F, target[rows], F[:, MODEL_COLUMNS.index('cosine')], sub)
         except _Fallback as e:
             logging.warning('%s falls back to the cosine (CosineTDC) for this %s level: %s', type(self).__name__,
                             mode, e)
             self.fallback = True
-            gate = CosineTDC(self.min_group_size, self.qvalues, self.device)
+            gate = CosineTDC(self.min_group_size, self.qvalues, self.device, self.groups, self.fdr)
             gate(table, mode)
-            self.n_groups = gate.n_groups
+            self.n_groups, self.group_profile = gate.n_groups, gate.group_profile
             return None
         if mode == 'open':
-            self.n_groups = len(np.unique(groups))
+            self.n_groups = len(np.unique(groups)) if n_labels is None else n_labels
         full_s, full_q = np.full(n, np.nan), np.full(n, np.nan)
         t = target[rows]
         full_s[rows[t]], full_q[rows[t]] = score[t], q[t]
         table.score, table.q = full_s, full_q
+        self._publish_profile(target, full_q)
         return None
 
 
@@ -446,8 +523,8 @@ class PercolatorTDC(_SemiSupervisedTDC):
     (``_lib.l2svm_fit``, ``_lib.linear_scores`` with the matrix on ``device``). ``self.trace`` keeps, per fold,
     the grid point chosen, the labels of every round and the weights, for the tests."""
     def __init__(self, fdr: float = 0.01, min_group_size: int = 100, folds: int = 3, max_iter: int = 10,
-                 seed: int = 1, solver=None, device='cuda', C: float = 1.0, qvalues=None):
-        super().__init__(fdr, min_group_size, folds, max_iter, seed, solver, device, qvalues)
+                 seed: int = 1, solver=None, device='cuda', C: float = 1.0, qvalues=None, groups=None):
+        super().__init__(fdr, min_group_size, folds, max_iter, seed, solver, device, qvalues, groups)
         self.C = float(C)
         self.n_newton = 0
 
@@ -547,8 +624,8 @@ class ForestTDC(_SemiSupervisedTDC):
     ``forest_predict`` with the matrix on ``device``)."""
 
     def __init__(self, fdr: float = 0.01, min_group_size: int = 100, folds: int = 3, max_iter: int = 10,
-                 seed: int = 1, solver=None, device='cuda', trees: int = 100, qvalues=None):
-        super().__init__(fdr, min_group_size, folds, max_iter, seed, solver, device, qvalues)
+                 seed: int = 1, solver=None, device='cuda', trees: int = 100, qvalues=None, groups=None):
+        super().__init__(fdr, min_group_size, folds, max_iter, seed, solver, device, qvalues, groups)
         self.trees = int(trees)
         if self.trees < 1:
             raise ValueError('ForestTDC: trees >= 1')
@@ -596,14 +673,16 @@ class ForestTDC(_SemiSupervisedTDC):
 def make_scorer(config, device='cuda'):
     """The scorer ``Config.device_fdr`` stands for: ``model`` None / 'none' -> ``CosineTDC``, 'svm' ->
     ``PercolatorTDC``; 'rf' with ``device_forest`` -> ``ForestTDC``; anything else (the reference's 'rf' without
-    that switch included) is a ``ValueError``. ``Config.device_qvalues`` hands every scorer ``qvalues='device'``."""
+    that switch included) is a ``ValueError``. ``Config.device_qvalues`` hands every scorer ``qvalues='device'``,
+    ``Config.device_groups`` ``groups='device'``."""
     model = config.model
     qvalues = 'device' if getattr(config, 'device_qvalues', False) else None
+    groups = 'device' if getattr(config, 'device_groups', False) else None
     if model is None or model == 'none':
-        return CosineTDC(config.fdr_min_group_size, qvalues=qvalues, device=device)
+        return CosineTDC(config.fdr_min_group_size, qvalues=qvalues, device=device, groups=groups, fdr=config.fdr)
     if model == 'svm':
-        return PercolatorTDC(config.fdr, config.fdr_min_group_size, device=device, qvalues=qvalues)
+        return PercolatorTDC(config.fdr, config.fdr_min_group_size, device=device, qvalues=qvalues, groups=groups)
     if model == 'rf' and getattr(config, 'device_forest', False):
         return ForestTDC(config.fdr, config.fdr_min_group_size, device=device, trees=config.forest_trees,
-                         qvalues=qvalues)
+                         qvalues=qvalues, groups=groups)
     raise ValueError(f"device_fdr: model = {model!r} is not provided; None / 'none' (cosine) or 'svm'")

@@ -900,6 +900,38 @@ int asl_tdc_qvalues(const double *score      /* [n] */,
                     int8_t *label            /* [n] or NULL: +1 used target with q <= fdr, 0 other used
                                                 target and every unused row, -1 used decoy */);
 
+/* ------------------------------------------------------------------ mass-difference groups
+ * The group labels of the open level (fdr.ssm_groups = the reference's utils._get_ssm_groups, utils.py:204-274) on
+ * the device (csrc/groups.hip; DESIGN.md 3 "Mass-difference groups"), byte for byte the host code's. The rule:
+ *   - nominal = rint(md), half to even. The SSMs of one nominal value g form one interval.
+ *   - Its 101 edges, as numpy.linspace(g - 0.5, g + 0.5, 101) forms them: edge[i] = fl(fl(i * 0.01) + (g - 0.5))
+ *     for i < 100 -- a rounded product, then a rounded sum, never an FMA -- and edge[100] = g + 0.5.
+ *   - An SSM is counted into the bin i with edge[i] <= md < edge[i + 1]; bin 99 also takes md == edge[100].
+ *   - Peaks of the 100 counts (scipy.signal.find_peaks): a strict local maximum; a plateau counts once, at
+ *     (first + last) / 2 rounded down; bins 0 and 99 are never peaks; a plateau that reaches bin 99 is no peak.
+ *   - Bases of a peak (peak_prominences, wlen = None): walk outward from the peak while the count is <= the
+ *     peak's count; the base is the position of the minimum met on the way, of equal minima the one nearest the
+ *     peak, the peak itself if nothing lower is met.
+ *   - An SSM belongs to the peak with the smallest |edge[peak] - md| (one rounded fp64 difference) among the peaks
+ *     with edge[left base] < md < edge[right base], both strict; equal distances go to the lower peak index;
+ *     with no such peak the SSM gets -1.
+ *   - Group id = (number of peaks in all intervals of lower nominal value) + the peak's index in its interval.
+ *   - The reference's quirks: the interval of the largest md is skipped (no peaks, no ids) when it holds exactly
+ *     one SSM and n > 1; with n == 1 nothing is assigned.
+ *   - Last, every id with fewer than min_group_size SSMs becomes -1. Ids are not renumbered.
+ * Arrays are host or device memory, as the other entry points detect it; the outputs are written where they live.
+ * peak_mass and peak_size are written for ids 0 .. *n_peaks - 1 only (an id's peak bin holds an SSM, so *n_peaks
+ * <= n). Checked before any output is written: n < 0, min_group_size < 0, a non-finite md: ASL_ERR_INVALID;
+ * n >= 2^31, or max nominal - min nominal + 1 > ASL_GROUPS_MAX_SPAN: ASL_ERR_CAPACITY (a +-500 Da window needs
+ * 1 001 intervals). n == 0 is legal, launches nothing and sets both counts to 0. */
+#define ASL_GROUPS_MAX_SPAN 65536 /* intervals between the smallest and the largest nominal mass difference */
+int asl_ssm_groups(const double *mass_diff /* [n] */, int64_t n, int64_t min_group_size,
+                   int32_t *group      /* [n] out */,
+                   int64_t *n_peaks    /* out (host): number of group ids handed out, before folding */,
+                   int64_t *n_labels   /* out (host): distinct values in group[], -1 included when present */,
+                   double  *peak_mass  /* [n] or NULL: peak_mass[g] = left bin edge of group g's peak */,
+                   int64_t *peak_size  /* [n] or NULL: peak_size[g] = SSMs assigned to g before folding */);
+
 /* ------------------------------------------------------------------ hot path
  * One batch of same-charge queries through
  *   SpectralLibrary._search_batch / _get_library_candidates

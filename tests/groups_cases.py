@@ -1,0 +1,174 @@
+"""Named inputs of ``asl_ssm_groups`` shared by test_groups_cpu.py and test_gpu_groups.py: ``CASES[name] = (md,
+min_group_size)``, the smallest shapes at which each kernel of csrc/groups.hip can go wrong. The builders assert
+what their case is about, so a case that stops showing it fails at import.
+
+  sizes       0, 1, 2 (same nominal / different nominals: the last SSM is alone and skipped), 63, 64, 65, 257, and
+              300 001 rows
+  rounding    +-0.5, 1.5, 2.5, -1.5: half to even, values that sit on edge[0] / edge[100]
+  edges       md on edge[i] as numpy forms it and one ulp to either side, at nominal 0, 1, -1, 499, 30 000, -30 000.
+              Where an FMA would form another edge than the two roundings do -- nominal 0, 1, -1: the sum cancels, so
+              the product's rounding survives -- a planted value lies between the two edges (asserted). At 499 and
+              +-30 000 no edge can differ: the product's rounding error, at most 2^-54, is far below half an ulp of
+              the sum, and the builder asserts that the two forms agree for every i there.
+  shapes      a peak in bin 1 / bin 98, counts only in bin 0 / bin 99, plateaus of width 2 and 3, a plateau running
+              into bin 99, two peaks with a shared base, equal minima on the way to a base, an SSM on a left / right
+              base edge (strict), an SSM between the bases of no peak, an SSM equidistant from two peaks (exact)
+  contention  5 000 rows in one bin; 20 000 rows in three adjacent bins around 0 on a sparse background
+  span        one interval; nominals -32 768 and 32 767 (span 65 536, legal); -32 768 and 32 768 (over the cap:
+              ``OVER_SPAN``, not in ``CASES``)
+  min_group_size 0, 1, 2, 100, n + 1 on the realistic mixture
+  realistic   planted modification masses with Gaussian error on a uniform background
+"""
+import numpy as np
+
+import groups_ref as R
+
+EDGE_NOMINALS = (0, 1, -1, 499, 30000, -30000)
+CONTRACTION_NOMINALS = (0, 1, -1)          # where an FMA changes an edge; see the module comment
+
+
+def _centres(g: float, counts: dict) -> np.ndarray:
+    """``counts[bin]`` SSMs spread inside each named bin of the interval of ``g``."""
+    e = R.edges(g)
+    out = []
+    for b, k in counts.items():
+        out.append(e[b] + (e[b + 1] - e[b]) * (np.arange(k) + 0.5) / k)
+    md = np.concatenate(out) if out else np.zeros(0)
+    assert (np.rint(md) == g).all() and (np.bincount(R.bin_of(md, e), minlength=100)[list(counts)] ==
+                                         list(counts.values())).all()
+    return md
+
+
+def _shape(counts: dict, g: float = 3.0, extra=()) -> np.ndarray:
+    """One interval of the given counts, then two SSMs in a higher interval so that it is not the last one."""
+    return np.concatenate([_centres(g, counts), np.asarray(extra, np.float64), _centres(g + 4, {50: 2})])
+
+
+def _counts(md, g):
+    return np.bincount(R.bin_of(md[np.rint(md) == g], R.edges(g)), minlength=100)
+
+
+def _build():
+    rng = np.random.default_rng(20)
+    C = {}
+    # ---- sizes
+    C['n0'] = (np.zeros(0), 1)
+    C['n1'] = (np.array([0.3]), 0)
+    C['n2-same'] = (np.array([0.301, 0.302]), 1)
+    C['n2-apart'] = (np.array([5.2, 0.3]), 1)
+    for n in (63, 64, 65, 257):
+        C[f'n{n}'] = (np.round(rng.normal(0, 0.02, n), 4) + rng.integers(-1, 3, n), 2)
+    big = np.concatenate([rng.normal(0, 0.004, 80001), rng.normal(15.9949, 0.003, 40000),
+                          rng.normal(-17.0265, 0.003, 30000), rng.uniform(-150, 500, 150000)])
+    C['n300001'] = (big[rng.permutation(len(big))], 100)
+    assert len(big) == 300001
+    # ---- rounding: half to even, and values on edge[0] / edge[100] of their interval
+    r = np.array([0.5, -0.5, 1.5, 2.5, -1.5, 0.49, 0.51, 2.2, 2.21, 2.2, -1.7, -1.7])
+    assert (np.rint(r[:5]) == [0, -0, 2, 2, -2]).all()
+    assert r[0] == R.edges(0)[100] and r[1] == R.edges(0)[0] and r[2] == R.edges(2)[0] and r[3] == R.edges(2)[100]
+    C['rounding'] = (r, 1)
+    # ---- edges
+    for g in EDGE_NOMINALS:
+        e, ef = R.edges(float(g)), R.edges_contracted(float(g))
+        md = np.concatenate([e[1:100], np.nextafter(e[1:100], -np.inf), np.nextafter(e[1:100], np.inf)])
+        assert (np.rint(md) == g).all()
+        differ = np.nonzero(e != ef)[0]
+        if g in CONTRACTION_NOMINALS:
+            # a planted value that the contracted edge would put into the neighbouring bin
+            assert len(differ) and any(((md >= e[i]) != (md >= ef[i])).any() for i in differ), g
+        else:
+            assert len(differ) == 0, g
+        C[f'edges-{g}'] = (np.concatenate([md, [g + 4.25, g + 4.26]])[rng.permutation(len(md) + 2)], 1)
+    # ---- peak shapes (interval of nominal 3; bins not named hold nothing)
+    shapes = {
+        'peak-bin1': {0: 1, 1: 5, 2: 2}, 'peak-bin98': {97: 2, 98: 5, 99: 1},
+        'only-bin0': {0: 4}, 'only-bin99': {99: 4},
+        'plateau2': {10: 1, 11: 4, 12: 4, 13: 2}, 'plateau3': {10: 1, 11: 4, 12: 4, 13: 4, 14: 3},
+        'plateau-into-99': {40: 2, 41: 6, 42: 1, 96: 1, 97: 3, 98: 3, 99: 3},
+        'shared-base': {8: 9, 9: 2, 10: 5, 11: 1, 12: 5, 13: 2, 14: 9},
+        'equal-minima': {25: 10, 26: 5, 27: 2, 28: 4, 29: 2, 30: 9, 31: 2, 32: 3, 33: 2, 34: 12},
+        'no-enclosing-peak': {0: 2, 50: 5, 99: 1},
+    }
+    expect_peaks = {'peak-bin1': [1], 'peak-bin98': [98], 'only-bin0': [], 'only-bin99': [], 'plateau2': [11],
+                    'plateau3': [12], 'plateau-into-99': [41], 'shared-base': [8, 10, 12, 14],
+                    'equal-minima': [25, 28, 30, 32, 34], 'no-enclosing-peak': [50]}
+    for name, counts in shapes.items():
+        md = _shape(counts)
+        assert R.peaks_of(_counts(md, 3.0)) == expect_peaks[name], name
+        C[name] = (md, 1)
+    c = _counts(C['shared-base'][0], 3.0)
+    assert R.bases_of(c, 10)[1] == 11 == R.bases_of(c, 12)[0]
+    c = _counts(C['equal-minima'][0], 3.0)
+    assert R.bases_of(c, 30) == (29, 31)                  # of the equal minima 27 / 29 and 31 / 33 the nearest
+    assert (R.ssm_groups(C['no-enclosing-peak'][0], 1)[0] == -1).sum() == 3
+    # an SSM ON a base edge: the comparison is strict, so it goes to the farther peak that still encloses it
+    e = R.edges(3.0)
+    md = _shape({38: 3, 40: 2, 41: 9}, extra=[e[39]])     # peak 38's right base is bin 39
+    c = _counts(md, 3.0)
+    assert c[39] == 1 and R.peaks_of(c) == [38, 41] and R.bases_of(c, 38)[1] == 39 and R.bases_of(c, 41)[0] < 39
+    assert abs(e[38] - e[39]) < abs(e[41] - e[39]) and R.ssm_groups(md, 1)[0][np.nonzero(md == e[39])[0][0]] == 1
+    C['on-right-base'] = (md, 1)
+    md = _shape({36: 9, 37: 2, 39: 3}, extra=[e[38]])     # peak 39's left base is bin 38
+    c = _counts(md, 3.0)
+    assert c[38] == 1 and R.peaks_of(c) == [36, 39] and R.bases_of(c, 39)[0] == 38 and R.bases_of(c, 36)[1] > 38
+    assert abs(e[39] - e[38]) < abs(e[36] - e[38]) and R.ssm_groups(md, 1)[0][np.nonzero(md == e[38])[0][0]] == 0
+    C['on-left-base'] = (md, 1)
+    # an SSM at exactly the same fp64 distance from two peaks of equal height at nominal 0: the lower index
+    e = R.edges(0.0)
+    for p in range(2, 96):
+        x = (e[p] + e[p + 2]) / 2
+        if abs(e[p] - x) == abs(e[p + 2] - x) and e[p + 1] <= x < e[p + 2]:
+            break
+    else:
+        raise AssertionError('no exactly equidistant pair of peaks at nominal 0')
+    md = _shape({p: 5, p + 2: 5}, g=0.0, extra=[x])
+    c = _counts(md, 0.0)
+    assert R.peaks_of(c) == [p, p + 2] and R.bases_of(c, p)[1] > p + 2 and R.bases_of(c, p + 2)[0] < p
+    assert R.ssm_groups(md, 1)[0][np.nonzero(md == x)[0][0]] == 0
+    C['equidistant'] = (md, 1)
+    # ---- contention
+    C['one-bin-5000'] = (np.concatenate([np.full(5000, 0.0012) + rng.uniform(0, 0.005, 5000), [3.3, 3.31]]), 100)
+    assert len(np.unique(R.bin_of(C['one-bin-5000'][0][:5000], R.edges(0.0)))) == 1
+    hot = np.concatenate([rng.uniform(-0.02, 0.01, 20000), rng.uniform(-200, 200, 2000)])
+    assert len(np.unique(R.bin_of(hot[:20000], R.edges(0.0)))) == 3
+    C['three-bins-20000'] = (hot[rng.permutation(len(hot))], 100)
+    # ---- span
+    C['one-interval'] = (rng.normal(7.0, 0.05, 500).clip(6.51, 7.49), 10)
+    wide = np.concatenate([rng.normal(-32768, 0.01, 40), rng.normal(32767, 0.01, 40), rng.normal(0, 0.01, 40)])
+    assert np.rint(wide).min() == -32768 and np.rint(wide).max() == 32767
+    C['span-65536'] = (wide, 5)
+    # ---- the realistic mixture, at every min_group_size
+    mods = (0.0, 0.984, 15.9949, 42.0106, 79.9663, -17.0265, -18.0106, 1.0034, 14.0157)
+    mix = np.concatenate([rng.normal(m, 0.002, k) for m, k in zip(mods, (900, 150, 400, 120, 99, 101, 60, 200, 30))]
+                         + [rng.uniform(-100, 300, 1500)])
+    mix = mix[rng.permutation(len(mix))]
+    for size in (0, 1, 2, 100, len(mix) + 1):
+        C[f'realistic-min{size}'] = (mix, size)
+    for md, _ in C.values():
+        md.setflags(write=False)
+    return C
+
+
+CASES = _build()
+NAMES = list(CASES)
+#: nominals -32 768 and 32 768 together: 65 537 intervals, one over ASL_GROUPS_MAX_SPAN
+OVER_SPAN = np.concatenate([np.full(30, -32768.0) + np.linspace(-0.01, 0.01, 30),
+                            np.full(30, 32768.0) + np.linspace(-0.01, 0.01, 30)])
+_host, _ref = {}, {}
+
+
+def host(name: str) -> np.ndarray:
+    """``fdr.ssm_groups`` on the case, computed once: the reference of every comparison."""
+    if name not in _host:
+        from ann_solo_amd import fdr
+        g = fdr.ssm_groups(*CASES[name])
+        g.setflags(write=False)
+        _host[name] = g
+    return _host[name]
+
+
+def ref(name: str):
+    """The restatement's five outputs on the case, computed once."""
+    if name not in _ref:
+        _ref[name] = R.ssm_groups(*CASES[name])
+    return _ref[name]
