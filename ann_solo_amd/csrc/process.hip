@@ -162,9 +162,18 @@ __global__ __launch_bounds__(PS_NT) void process_kernel(
     }
   }
   // spectrum.py:97-99 filter_intensity: rank by (intensity desc, index desc)
+  // A NaN that got here is intensity.max(): its key goes to the top of the order whatever its sign
+  // bit says (f2ord alone ranks a negative-sign NaN below every number), the threshold below is
+  // NaN, nothing is above it and the spectrum is invalid -- oracle: the isnan scan before qsort.
   const int nsort = n <= 256 ? 256 : (n <= 1024 ? 1024 : 4096);
-  for (int i = tid; i < nsort; i += PS_NT)
-    keys[i] = (i < n && keep[i]) ? (((u64)f2ord(inten[i]) << 32) | (u64)(uint32_t)i) : 0ull;
+  for (int i = tid; i < nsort; i += PS_NT) {
+    u64 key = 0ull;
+    if (i < n && keep[i]) {
+      const float v = inten[i];
+      key = ((u64)(v != v ? 0xFFFFFFFFu : f2ord(v)) << 32) | (u64)(uint32_t)i;
+    }
+    keys[i] = key;
+  }
   __syncthreads();
   const int lead = P.max_peaks < nsort ? P.max_peaks : nsort;
   if (nsort == 256)

@@ -192,7 +192,8 @@ def process_in_chunks(items: Iterable, is_library: bool, config, device, chunk: 
                       annotation_alignment: str = 'peaks'):
     """Batched ``process_spectrum`` over an iterator of ``(spectrum object, precursor charge,
     tag)`` triples: yields ``(objects, charges, tags, processed PackedSpectra on the host,
-    valid bool ndarray)`` per chunk."""
+    valid bool ndarray)`` per chunk. One raw spectrum above 4096 peaks fails its whole chunk
+    (``process_spectra``): split or pre-filter such spectra before they get here."""
     from .spectrum import process_spectra
     buf, chg, tags = [], [], []
 

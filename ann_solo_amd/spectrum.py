@@ -85,7 +85,8 @@ def process_spectra(raw, is_library: bool, config=None, device='cuda'):
     reference's preprocessing flags (``ann_solo_amd.spectral_library.Config`` lacks them, so
     the reference defaults are used for missing attributes). Returns ``(processed
     PackedSpectra on ``device``, valid bool tensor)``; invalid spectra come back empty.
-    Peak charge annotations follow their peaks."""
+    Peak charge annotations follow their peaks. One raw spectrum above 4096 peaks fails the whole
+    call (``AnnSoloMiError``, code ``_lib.ERR_CAPACITY``), so callers must split or pre-filter."""
     import ctypes as C
     import torch
     from .packed import PackedSpectra

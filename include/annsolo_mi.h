@@ -594,7 +594,13 @@ int asl_rescore_batch_topn_hist(const asl_peaks_t *queries, const asl_peaks_t *l
  * in m/z, <= 4096 per spectrum. Outputs are padded to max_peaks per spectrum: out_mz /
  * out_intensity / out_src [n, max_peaks] (out_src = index of the kept peak inside its raw
  * spectrum -- after rounding: of the most intense of the merged peaks, whose annotation
- * survives --, may be NULL), out_count[n], out_valid[n] (is_valid).
+ * survives --, may be NULL), out_count[n], out_valid[n] (is_valid). Only the first out_count[s]
+ * slots of a spectrum's row are defined (none for an invalid spectrum); what the rest hold is
+ * unspecified. One raw spectrum above 4096 peaks fails the WHOLE call with ASL_ERR_CAPACITY (the
+ * outputs of the others are not to be used), so callers must split or pre-filter such spectra.
+ * A NaN intensity of either sign among the peaks that reach the intensity filter (in range, after
+ * the merge's sums, not removed with the precursor) makes its spectrum invalid: it is the base
+ * peak, and nothing is above a NaN threshold.
  * scaling: 0 none, 1 rank, 2 root. */
 typedef struct {
   double min_mz, max_mz;              /* config.min_mz / max_mz (inclusive) */

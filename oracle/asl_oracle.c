@@ -252,6 +252,11 @@ int orc_process_spectrum(const float *mz_in, const float *intensity_in, int32_t 
     if (!spectrum_ok(mz, keep, n, p->min_peaks, p->min_mz_range)) goto done;
   }
   /* spectrum.py:97-99 filter_intensity: strictly above min_intensity * max, top max_peaks */
+  /* a NaN among the peaks that got here (one that came through the range filter, a merged sum,
+   * precursor removal) is intensity.max(): nothing is strictly above a NaN threshold, so the
+   * spectrum is invalid -- and pk_cmp is no order over NaNs, so they never reach qsort */
+  for (int32_t i = 0; i < n; i++)
+    if (keep[i] && isnan(intensity[i])) goto done;
   pk = (orc_pk_t *)malloc(sizeof(orc_pk_t) * (size_t)n);
   int m = 0;
   for (int32_t i = 0; i < n; i++)
