@@ -25,26 +25,23 @@ __device__ __forceinline__ float dpp_mov(float x) {
 typedef float pqt_f2 __attribute__((ext_vector_type(2)));
 
 // The table entries lut[c * 32 + m] of two neighbouring code bytes of word (bytes 2 * half and 2 * half + 1).
-// lane_at: the LDS address of lut[m], as the bits of a float.
-// The address c * 128 + lane_at is made by the FLOAT unit, from two full-rate instructions per look-up: a mask
-// (byte 3: a shift) and one v_fma_f32. By profiles/pq_adc_addr_issue_rate.txt v_lshl_add_u32, v_bfe_u32,
-// v_and_or_b32, v_bfi_b32, v_mad_u32_u24, the SDWA shifts and v_cvt_f32_ubyteN all issue at about half the rate
-// of v_and_b32, v_lshrrev_b32 and v_fma_f32. A bit pattern p below 2^24 is, read as a float, exactly
-// p * 2^-149 (a denormal, or a normal of the first binade, which has the same spacing). So with the byte left
-// where it stands, p = c << (8 * i), fma(p, 2^(7 - 8 * i), lane_at) is (c * 128 + lane_at) * 2^-149 without
-// rounding -- product and sum are integers below 2^23 in that unit -- and its bit pattern is the address.
-// This needs fp32 denormals on (FP_DENORM mode 3, what hipcc compiles kernels for unless asked to flush them);
-// v_fma_f32 handles them at full rate. With denormals flushed every look-up would read lut[0], inside the table
-// but wrong: tests/test_gpu_pq_adc_address.py compares every byte value at every position.
-__device__ __forceinline__ pqt_f2 lut_at2(uint32_t word, int half, float lane_at) {
+// lane_at: the LDS address of lut[m].
+// The address c * 128 + lane_at is ONE instruction per look-up, for any byte position: v_dot4_u32_u8 computes
+// D = a.u8[0] * b.u8[0] + ... + a.u8[3] * b.u8[3] + c in 32-bit integers, and with the one-hot selector
+// b = 0x80 << (8 * k) that is byte k of the word, times 128, plus the lane's part: no mask, no shift, and every
+// address bit kept (behind the 32 KB key buffer of the 4096-key kernels the addresses pass 2^16). The four
+// selectors sit in scalar registers. By profiles/pq_adc_dot4_issue_rate.txt the instruction issues at about half
+// the rate of v_and_b32 or v_fma_f32 (1.8 ns against 1.0 to 1.1 per SIMD at six waves), below the 2.1 to 2.2 ns of
+// the mask + v_fma_f32 on denormal bit patterns that made the address before, and it took 28 % of the scan's
+// executed vector instructions away (profiles/pq_adc_dot4_before_after.txt, pq_adc_dot4_ab.txt).
+// tests/test_gpu_pq_adc_address.py and tests/test_gpu_pq_adc_dot4.py compare every byte value at every position.
+__device__ __forceinline__ pqt_f2 lut_at2(uint32_t word, int half, uint32_t lane_at) {
   typedef const __attribute__((address_space(3))) float *lds_f;
-  const uint32_t p0 = half == 0 ? word & 0xffu : word & 0xff0000u;
-  const uint32_t p1 = half == 0 ? word & 0xff00u : word >> 24;
-  const float a0 = __builtin_fmaf(__builtin_bit_cast(float, p0), half == 0 ? 128.0f : 0x1p-9f, lane_at);
-  const float a1 = __builtin_fmaf(__builtin_bit_cast(float, p1), half == 0 ? 0.5f : 128.0f, lane_at);
+  const uint32_t a0 = __builtin_amdgcn_udot4(word, 0x80u << (16 * half), lane_at, false);
+  const uint32_t a1 = __builtin_amdgcn_udot4(word, 0x8000u << (16 * half), lane_at, false);
   pqt_f2 r;
-  r.x = *(lds_f)(uintptr_t)__builtin_bit_cast(uint32_t, a0);
-  r.y = *(lds_f)(uintptr_t)__builtin_bit_cast(uint32_t, a1);
+  r.x = *(lds_f)(uintptr_t)a0;
+  r.y = *(lds_f)(uintptr_t)a1;
   return r;
 }
 
@@ -58,7 +55,7 @@ __device__ __forceinline__ float tile_adc(const char *lut_bytes, const uint4 A, 
                                           uint32_t offA_u, uint32_t offB_u) {
   // the table's LDS address goes into the lane constant: the address register is all a read needs
   const uint32_t lut0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)lut_bytes;
-  const float offA = __builtin_bit_cast(float, lut0 + offA_u), offB = __builtin_bit_cast(float, lut0 + offB_u);
+  const uint32_t offA = lut0 + offA_u, offB = lut0 + offB_u;
   float v[16];
   const uint32_t a[4] = {A.x, A.y, A.z, A.w};
   const uint32_t b[4] = {B.x, B.y, B.z, B.w};

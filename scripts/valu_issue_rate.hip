@@ -1,6 +1,6 @@
 // Issue rate of wave64 vector instructions: what one SIMD sustains at W waves per SIMD, and what the profiler's
 // VALU counters say of a kernel that does nothing else (profiles/pq_mmajor_before.txt); and the prices of what a look-up
-// address of the PQ scan can be made of (profiles/pq_adc_addr_issue_rate.txt).
+// address of the PQ scan can be made of (profiles/pq_adc_addr_issue_rate.txt, profiles/pq_adc_dot4_issue_rate.txt).
 //   hipcc -O3 --offload-arch=gfx950 -o valu_issue_rate scripts/valu_issue_rate.hip && ./valu_issue_rate
 //   rocprofv3 --pmc VALUBusy SQ_INSTS_VALU SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE -- ./valu_issue_rate
 // Workgroups of 4 waves (one per SIMD); the LDS size keeps exactly W of them on a CU. Per wave: s_memtime ticks
@@ -26,11 +26,46 @@ __global__ void k(float *out, long long *ticks, float seed) {
   int v7 = 7;
   asm volatile("" : "+v"(v7));
   int smask = __builtin_amdgcn_readfirstlane(0x7f80 + (int)seed - 1);   // a mask in a scalar register
+  // v_dot4_u32_u8 D = sum of a.u8[i] * b.u8[i], plus c: with the one-hot selector 0x80 << (8 k) that is
+  // byte k of a, times 128, plus c (profiles/pq_adc_dot4_issue_rate.txt). KIND 30 + k: the selector in a scalar
+  // register; 34 + k: in a vector register; vadd: the addend, a vector register in all of them
+  constexpr int DOTK = KIND >= 30 && KIND <= 37 ? (KIND - 30) & 3 : KIND == 39 ? 3 : KIND == 38 ? 1 : 0;
+  const int ssel = __builtin_amdgcn_readfirstlane((0x80 << (8 * DOTK)) + (int)seed - 1);
+  int vsel = ssel, vadd = (int)(threadIdx.x & 31) * 4;
+  asm volatile("" : "+v"(vsel), "+v"(vadd));
+  if (KIND >= 30 && KIND <= 45)   // small integers: as floats they are the denormals of the mixed loops' v_fma_f32
+    for (int i = 0; i < UNR; i++) a[i] = __int_as_float((int)(threadIdx.x & 127) + i);
   __syncthreads();
   const long long t0 = __builtin_readcyclecounter();
   for (int it = 0; it < ITER; it++) {
 #pragma unroll
     for (int i = 0; i < UNR; i++) {
+      if (KIND >= 30 && KIND <= 33) asm volatile("v_dot4_u32_u8 %0, %0, %1, %2" : "+v"(a[i]) : "s"(ssel), "v"(vadd));
+      if (KIND >= 34 && KIND <= 37) asm volatile("v_dot4_u32_u8 %0, %0, %1, %2" : "+v"(a[i]) : "v"(vsel), "v"(vadd));
+      if (KIND == 38) asm volatile("v_dot4_u32_u8 %0, %0, %1, 0" : "+v"(a[i]) : "s"(ssel));        // no addend register
+      if (KIND == 39) asm volatile("v_dot4_u32_u8 %0, %1, %2, %0" : "+v"(a[i]) : "v"(vadd), "s"(ssel));   // the addend is the chain
+      // mixed loops, 1:1: does the price of v_dot4_u32_u8 add to a full-rate instruction's or overlap with it
+      if (KIND == 40 || KIND == 41 || KIND == 43) {
+        if (i & 1) {
+          if (KIND == 40) asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(a[i]) : "v"(one), "v"(tiny));
+          if (KIND == 41) asm volatile("v_and_b32 %0, 0xff, %0" : "+v"(a[i]));
+          if (KIND == 43) asm volatile("v_lshrrev_b32 %0, 1, %0" : "+v"(a[i]));
+        } else {
+          asm volatile("v_dot4_u32_u8 %0, %0, %1, %2" : "+v"(a[i]) : "s"(ssel), "v"(vadd));
+        }
+      }
+      if (KIND == 42) {   // today's pair: v_and_b32 and the denormal v_fma_f32, 1:1
+        if (i & 1) asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(a[i]) : "v"(one), "v"(tiny));
+        else asm volatile("v_and_b32 %0, 0xff, %0" : "+v"(a[i]));
+      }
+      if (KIND == 44) {   // byte 3 today: v_lshrrev_b32 and the denormal v_fma_f32, 1:1
+        if (i & 1) asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(a[i]) : "v"(one), "v"(tiny));
+        else asm volatile("v_lshrrev_b32 %0, 1, %0" : "+v"(a[i]));
+      }
+      if (KIND == 45) {   // dot4 and a half-rate instruction, 1:1
+        if (i & 1) asm volatile("v_lshl_add_u32 %0, %0, 7, %1" : "+v"(a[i]) : "v"(b));
+        else asm volatile("v_dot4_u32_u8 %0, %0, %1, %2" : "+v"(a[i]) : "s"(ssel), "v"(vadd));
+      }
       if (KIND == 0) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(a[i]) : "v"(b), "v"(c));
       if (KIND == 1) asm volatile("v_add_f32 %0, %0, %1" : "+v"(a[i]) : "v"(b));
       if (KIND == 2) asm volatile("v_add_f32_dpp %0, %1, %0 row_mirror row_mask:0xf bank_mask:0xf" : "+v"(a[i]) : "v"(a[(i + 1) % UNR]));
@@ -149,6 +184,22 @@ int main() {
     run("fmamk_f32_denorm", k<26>, W, out, ticks);
     run("v_lshlrev_b32", k<24>, W, out, ticks);
     run("and_b32_sgpr", k<25>, W, out, ticks);
+    run("dot4_ssel_b0", k<30>, W, out, ticks);
+    run("dot4_ssel_b1", k<31>, W, out, ticks);
+    run("dot4_ssel_b2", k<32>, W, out, ticks);
+    run("dot4_ssel_b3", k<33>, W, out, ticks);
+    run("dot4_vsel_b0", k<34>, W, out, ticks);
+    run("dot4_vsel_b1", k<35>, W, out, ticks);
+    run("dot4_vsel_b2", k<36>, W, out, ticks);
+    run("dot4_vsel_b3", k<37>, W, out, ticks);
+    run("dot4_ssel_add0", k<38>, W, out, ticks);
+    run("dot4_ssel_acc", k<39>, W, out, ticks);
+    run("dot4+fma_denorm", k<40>, W, out, ticks);
+    run("dot4+and_b32", k<41>, W, out, ticks);
+    run("dot4+lshrrev", k<43>, W, out, ticks);
+    run("dot4+lshl_add", k<45>, W, out, ticks);
+    run("and+fma_denorm", k<42>, W, out, ticks);
+    run("lshr+fma_denorm", k<44>, W, out, ticks);
   }
   return 0;
 }
