@@ -32,8 +32,15 @@
 // when the key buffer is full and at the end of a table chunk; the histogram is brought up to
 // date where it is read, in that sync (see "free-running appends" in the kernel).
 //
-// LDS: LUT 32 KB + key buffer (2048 or 4096 keys) + histogram + tile table => three (two)
-// workgroups of 8 waves per CU.
+// What a wave scans. The tile-major, window and selected instantiations fill a table of tiles (256
+// per chunk, 168 with a window) and a wave walks the entries wave, wave + 8, ... of it. The
+// sub-quantiser-major instantiations (MM) keep one entry per PROBE instead (128 per chunk: nprobe <=
+// 128 is one chunk per query, no scan of tile counts, no refill) and hand the lists out whole by a
+// ticket counter; a tile's entry is scalar arithmetic on the list's (see "whole lists per wave").
+// A plain request with nprobe < 32 takes the tile-major instantiation (pq_scan_v3()).
+//
+// LDS: LUT 32 KB + key buffer (2048 or 4096 keys) + histogram + tile / probe table (2 KB) => three
+// (two) workgroups of 8 waves per CU.
 #include "common.hpp"
 #include "hist_topk.hpp"
 #include "ivf_kernels.hpp"
@@ -132,6 +139,19 @@ struct TileEnt12 {
 constexpr int V3_CHUNK_RANGED = 168;
 static_assert(V3_CHUNK_RANGED * sizeof(TileEnt12) <= V3_CHUNK * sizeof(TileEnt8), "the ranged table fits the 2 KB");
 
+// The MM instantiations keep no tile table: a tile's index (tile0 + local), its coarse term (the list's) and its
+// count (64 except in the list's last tile) follow from 12 bytes per PROBE, all of it wave-uniform. The table
+// holds one entry per probe, 128 of them in the same 2 KB: nprobe <= 128 is one chunk per query, and a wave
+// takes whole lists from it by a ticket counter (see "whole lists per wave" in the kernel).
+struct ProbeEnt {
+  uint32_t tile0;     // the list's first tile
+  int32_t len;        // its vectors; 0: not probed (l < 0) or empty, skipped by the walk
+  float coarse;
+  uint32_t pad;
+};
+constexpr int V3_CHUNK_PROBES = 128;
+static_assert(V3_CHUNK_PROBES * sizeof(ProbeEnt) <= V3_CHUNK * sizeof(TileEnt8), "the probe table fits the 2 KB");
+
 // NW = waves per workgroup. LDS (LUT 32 KB + keys 16 KB + ...) allows three workgroups per CU
 // whatever their size, so 8 waves per workgroup (one tile per wave and round) double the
 // waves that share one LUT and one key buffer: 24 waves per CU at 80 VGPRs instead of 12 at
@@ -167,7 +187,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
   static_assert(T == 1, "one tile per wave at a time (two lost on registers: profiles/HISTORY.md)");
   constexpr int NT = 64 * NW, ROUND_VECS = NW * 64;
   using TopK = HistTopK<CAP, ROUND_VECS, NT>;
-  using Ent = typename std::conditional<RANGED, TileEnt12, TileEnt8>::type;
+  using Ent = typename std::conditional<RANGED, TileEnt12, typename std::conditional<MM, ProbeEnt, TileEnt8>::type>::type;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float *s_lut = reinterpret_cast<float *>(smem + TopK::lds_bytes());
   Ent *table = reinterpret_cast<Ent *>(s_lut + PQT_KSUB * PQT_M);
@@ -198,7 +218,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
           my_len[pp] = list_offsets[l + 1] - list_offsets[l];
           my_tile0[pp] = tile_offsets[l];
         }
-        my_nt[pp] = (my_len[pp] + 63) >> 6;
+        if constexpr (!MM) my_nt[pp] = (my_len[pp] + 63) >> 6;
         my_coarse[pp] = coarse_D[(size_t)q * nprobe + p];
       }
     }
@@ -224,16 +244,19 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
   }
 
   // ---- exclusive scan of the probes' tile counts (probe order: p, then p + NT)
-  int total = 0;
-  int *scan_part = reinterpret_cast<int *>(table);   // table is not live yet
+  // (MM: the table is per probe -- nothing to scan, `total` counts probes)
+  int total = MM ? nprobe : 0;
+  if constexpr (!MM) {
+    int *scan_part = reinterpret_cast<int *>(table);   // table is not live yet
 #pragma unroll
-  for (int pp = 0; pp < PP; ++pp) {
-    int part_total;
-    my_pre[pp] = total + block_excl_scan<NW>(my_nt[pp], scan_part, tid, part_total);
-    total += part_total;
-    __syncthreads();
+    for (int pp = 0; pp < PP; ++pp) {
+      int part_total;
+      my_pre[pp] = total + block_excl_scan<NW>(my_nt[pp], scan_part, tid, part_total);
+      total += part_total;
+      __syncthreads();
+    }
+    total = __builtin_amdgcn_readfirstlane(total);   // the same in every thread: the loops below are scalar
   }
-  total = __builtin_amdgcn_readfirstlane(total);   // the same in every thread: the loops below are scalar
 
   TopK top;   // init zeroes the keys (which aliased s_q)
   top.init(smem, k, ids_tiled, tid);
@@ -286,8 +309,17 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
   // reservation pending; a finished wave raises the flag only to join, and each request of an unfinished
   // wave was answered by a complete sync before that wave could finish, so at that point no sync is open or
   // can open. The retry of a refused tile ends: a sync leaves at least ROUND_VECS = NW * 64 free slots.
+  // MM, whole lists by ticket: the ticket counter adds no wait -- taking a ticket is one atomic add, which
+  // always returns, and the walk over empty entries ends because every round takes a higher ticket. "No entry
+  // left" is then: a ticket at or past the chunk's probe count was drawn (every later one is too: the counter
+  // only grows until thread 0 clears it between the chunk's two barriers, where no wave draws), both list
+  // sets are empty and no tile is in flight; a wave in that state draws no further ticket, fetches nothing
+  // and scores nothing, so it counts itself finished once and stays finished, and (a), (b) stand as above.
+  // The table is read only through tickets below the probe count, i.e. entries written before the barrier
+  // behind the fill; the last read of a chunk's table precedes its reader's count in s_done.
   int *s_flag = top.ctl + TopK::C_USER;            // a wave asks for a sync (C_USER is free until finish_set)
   int *s_done = top.ctl + TopK::C_USER + 1;        // waves that finished their share, summed over the chunks
+  int *s_ticket = top.ctl + TopK::C_USER + 2;      // MM: the chunk's next list to hand out (cleared per chunk)
   if (tid == 0) {
     *s_flag = 0;
     *s_done = 0;
@@ -300,23 +332,37 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
   uint32_t thr_hi_u = 0;          // != 0 exactly while exact flushes are in use (a flush then leaves k keys)
   int flag_u = 0;
 
-  constexpr int CHUNK = RANGED ? V3_CHUNK_RANGED : V3_CHUNK;
+  constexpr int CHUNK = RANGED ? V3_CHUNK_RANGED : MM ? V3_CHUNK_PROBES : V3_CHUNK;
   for (int c0 = 0; c0 < total; c0 += CHUNK) {
+    if constexpr (MM) {
+      // the probes [c0, c0 + CHUNK) of the query: thread p writes its own probe's entry, one 16-byte store
+      // (a probe past nprobe, with l < 0 or of an empty list has len 0); the tickets start over
 #pragma unroll
-    for (int pp = 0; pp < PP; ++pp) {
-      // (my probe as values of their own: what the fill derives from them is made here, once per chunk,
-      // not kept in registers across the tile loop)
-      // (the probe's tile count is made again from its length here: a register less across the tile loop)
-      asm volatile("" : "+v"(my_pre[pp]), "+v"(my_tile0[pp]), "+v"(my_len[pp]));
-      const int lo = max(my_pre[pp], c0), hi = min(my_pre[pp] + ((my_len[pp] + 63) >> 6), c0 + CHUNK);
-      for (int t = lo; t < hi; ++t) {
-        const int local = t - my_pre[pp];
-        Ent e;
-        const uint32_t tile0 = RANGED ? (uint32_t)my_tile0[pp] & 0x3ffffffu : (uint32_t)my_tile0[pp];
-        e.tile_nv = (tile0 + (uint32_t)local) | ((uint32_t)(min(64, my_len[pp] - local * 64) - 1) << 26);
-        e.coarse = my_coarse[pp];
-        if constexpr (RANGED) e.first = local == 0 ? (uint32_t)my_tile0[pp] >> 26 : 0u;
-        table[t - c0] = e;
+      for (int pp = 0; pp < PP; ++pp) {
+        const uint32_t local = (uint32_t)(tid + pp * NT - c0);
+        if (local < (uint32_t)CHUNK)
+          *reinterpret_cast<uint4 *>(&table[local]) =
+              make_uint4((uint32_t)my_tile0[pp], (uint32_t)my_len[pp], __float_as_uint(my_coarse[pp]), 0u);
+      }
+      if (tid == 0) __hip_atomic_store(s_ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    if constexpr (!MM) {
+#pragma unroll
+      for (int pp = 0; pp < PP; ++pp) {
+        // (my probe as values of their own: what the fill derives from them is made here, once per chunk,
+        // not kept in registers across the tile loop)
+        // (the probe's tile count is made again from its length here: a register less across the tile loop)
+        asm volatile("" : "+v"(my_pre[pp]), "+v"(my_tile0[pp]), "+v"(my_len[pp]));
+        const int lo = max(my_pre[pp], c0), hi = min(my_pre[pp] + ((my_len[pp] + 63) >> 6), c0 + CHUNK);
+        for (int t = lo; t < hi; ++t) {
+          const int local = t - my_pre[pp];
+          Ent e;
+          const uint32_t tile0 = RANGED ? (uint32_t)my_tile0[pp] & 0x3ffffffu : (uint32_t)my_tile0[pp];
+          e.tile_nv = (tile0 + (uint32_t)local) | ((uint32_t)(min(64, my_len[pp] - local * 64) - 1) << 26);
+          e.coarse = my_coarse[pp];
+          if constexpr (RANGED) e.first = local == 0 ? (uint32_t)my_tile0[pp] >> 26 : 0u;
+          table[t - c0] = e;
+        }
       }
     }
     __syncthreads();
@@ -336,21 +382,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
       uint32_t first;     // RANGED: first lane
       unsigned long long sel;   // SEL: the tile's selector word
     } e[NS];
-    // (real: false past the end of the wave's share, MM only -- the loads are issued all the same, of an empty
-    // resource: every lane out of range, nothing fetched)
-    // The entry to fetch is read at a running LDS address (a lane register that a step advances by its
-    // wave's stride), not at an index turned into an address per tile. num_records: the resource's size,
-    // 0 for a fetch past the end of the wave's share (MM only -- the loads are issued all the same, of
-    // an empty resource: every lane out of range, nothing fetched).
-    auto fetch = [&](uint32_t taddr, uint4 &a, uint4 &b, Tile &en, uint32_t num_records = 0) {
-      // (tile_nv, coarse: one 8-byte read -- the table is 16-byte aligned, an entry 8 or 12 bytes long)
-      typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-      const u32x2 t = *(const __attribute__((address_space(3))) u32x2 *)(uintptr_t)taddr;
-      en.tile_nv = __builtin_amdgcn_readfirstlane(t.x);
-      en.coarse = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane((int)t.y));
-      if constexpr (RANGED)
-        en.first = __builtin_amdgcn_readfirstlane(*(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)(taddr + 8u));
-      if constexpr (SEL) en.sel = sel[en.tile_nv & 0x3ffffffu];   // (a scalar load: the tile is wave-uniform)
+    // The two code loads of tile en.tile_nv. num_records: the resource's size, 0 for a fetch past the wave's last
+    // tile (MM only -- the loads are issued all the same, of an empty resource: every lane out of range, nothing
+    // fetched).
+    auto load_tile = [&](uint4 &a, uint4 &b, const Tile &en, uint32_t num_records) {
       // the tile's address is a scalar and the lane's part a 32-bit offset of its own: the loads take
       // them as they are (scalar base + lane offset), no 64-bit lane addresses to keep or add up per tile
       // (the second chunk's offset is made here from the first: a lane constant less to keep)
@@ -377,8 +412,79 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
         b = load_codes16<V3_NT>(base + offb);
       }
     };
+    // Tile table (not MM): the entry to fetch is read at a running LDS address (a lane register that a step
+    // advances by its wave's stride), not at an index turned into an address per tile.
+    auto fetch = [&](uint32_t taddr, uint4 &a, uint4 &b, Tile &en) {
+      // (tile_nv, coarse: one 8-byte read -- the table is 16-byte aligned, an entry 8 or 12 bytes long)
+      typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+      const u32x2 t = *(const __attribute__((address_space(3))) u32x2 *)(uintptr_t)taddr;
+      en.tile_nv = __builtin_amdgcn_readfirstlane(t.x);
+      en.coarse = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane((int)t.y));
+      if constexpr (RANGED)
+        en.first = __builtin_amdgcn_readfirstlane(*(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)(taddr + 8u));
+      if constexpr (SEL) en.sel = sel[en.tile_nv & 0x3ffffffu];   // (a scalar load: the tile is wave-uniform)
+      load_tile(a, b, en, 0u);
+    };
     constexpr uint32_t ENT_STRIDE = NW * sizeof(Ent);   // from one entry of a wave to its next
     const uint32_t mm_size = (uint32_t)PQT_M * mm_plane;
+    // ---- whole lists per wave (MM) ------------------------------------------------------------------------
+    // The lists of a chunk are handed out whole, in probe order (best coarse score first), by the ticket
+    // counter: a wave that needs a list takes the next ticket -- one lane's add, as HistTopK::reserve_add --
+    // and reads that probe's entry; a ticket at or past the chunk's probe count means no list is left, an
+    // entry of len 0 is skipped by taking the next ticket. A wave holds two lists as scalars -- (next tile,
+    // tiles left, coarse, last tile's count - 1) of the one it fetches from and of the one it takes up next --
+    // and draws the ticket for the second when it starts fetching the first, so neither LDS round trip is
+    // waited for with no code load in flight. A tile's entry is scalar arithmetic on the first set; left == 0
+    // there says that the wave has nothing left to fetch in this chunk.
+    uint32_t cur_tile = 0, cur_last = 0, nx_tile = 0, nx_last = 0;
+    int cur_left = 0, nx_left = 0;
+    float cur_coarse = 0.0f, nx_coarse = 0.0f;
+    int inflight = 0;             // tiles fetched and not yet scored
+    auto take_list = [&]() {      // the look-ahead list: the next non-empty one, or none (nx_left == 0)
+      typedef __attribute__((address_space(3))) int lds_int;
+      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+      nx_left = 0;
+      nx_tile = 0;                // (a valid tile for the fetches past the end, which read nothing)
+      for (;;) {                  // wave-uniform
+        // (the address as a lane value: the atomic optimizer leaves such an add alone, see reserve_add)
+        uint32_t ta = (uint32_t)(uintptr_t)(lds_int *)s_ticket;
+        asm volatile("" : "+v"(ta));
+        int t = (int)ta;
+        if (lane == 0)
+          t = __hip_atomic_fetch_add((lds_int *)(uintptr_t)ta, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        t = __builtin_amdgcn_readfirstlane(t);
+        if (t >= nent) break;
+        const u32x4 v = *(const __attribute__((address_space(3))) u32x4 *)(uintptr_t)(
+            (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)reinterpret_cast<const char *>(table) +
+            (uint32_t)t * (uint32_t)sizeof(ProbeEnt));
+        const int len = __builtin_amdgcn_readfirstlane((int)v.y);
+        if (len > 0) {
+          nx_tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)v.x);
+          nx_coarse = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane((int)v.z));
+          nx_left = (len + 63) >> 6;
+          nx_last = (uint32_t)(len - 1) & 63u;
+          break;
+        }
+      }
+    };
+    auto next_list = [&]() {      // the look-ahead list becomes the current one; the ticket for the one behind it
+      cur_tile = nx_tile, cur_left = nx_left, cur_coarse = nx_coarse, cur_last = nx_last;
+      if (cur_left != 0) take_list();
+    };
+    // Fetch my next tile (its entry made here), or -- nothing left -- any valid tile with an empty resource:
+    // the loads issued per step stay a compile-time count. The list advance is a wave-uniform branch, taken
+    // about every eighth tile. Counts the tile in `inflight`.
+    auto fetch_mm = [&](uint4 &a, uint4 &b, Tile &en) {
+      const bool real = cur_left != 0;
+      en.tile_nv = cur_tile | ((cur_left == 1 ? cur_last : 63u) << 26);
+      en.coarse = cur_coarse;
+      load_tile(a, b, en, real ? mm_size : 0u);
+      if (real) {
+        ++inflight;
+        ++cur_tile;
+        if (--cur_left == 0) next_list();
+      }
+    };
     // the tile whose candidates are offered: its scores and (scalar) its entry
     float p_score = 0.0f;
     uint32_t p_tile_nv = 0, p_first = 0;
@@ -418,16 +524,24 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     };
     const uint32_t table_lds = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)reinterpret_cast<const char *>(table);
     int i = wave_u;               // my next entry; between syncs its codes are in set 0, the next tiles' behind
-    if (i < nent) {
+    if constexpr (MM) {           // my first two lists, and the first tiles in flight
+      take_list();
+      next_list();
+#pragma unroll
+      for (int s = 0; s < DEPTH; ++s)
+        if (cur_left != 0) fetch_mm(A[s], B[s], e[s]);
+    } else if (i < nent) {
       uint32_t t0 = table_lds + (uint32_t)i * (uint32_t)sizeof(Ent);
       asm volatile("" : "+v"(t0));
 #pragma unroll
       for (int s = 0; s < DEPTH; ++s)
-        if (i + s * NW < nent) fetch(t0 + s * ENT_STRIDE, A[s], B[s], e[s], mm_size);
+        if (i + s * NW < nent) fetch(t0 + s * ENT_STRIDE, A[s], B[s], e[s]);
     }
-    // One step: the flag and the next table entry are read (one LDS wait for both), the next tile's codes
-    // fetched, the tile in set s scored. taddr: the LDS address of the entry fetched last.
-    // MM: the fetch is unconditional -- past the end of my share the last entry fetched again, with an empty
+    // a tile to score in the set the rotation is at? (MM: a tile in flight; else: an entry of my share left)
+    auto more = [&]() -> bool { return MM ? inflight != 0 : i < nent; };
+    // One step: the flag is read (and, with a tile table, the next entry: one LDS wait for both), the next tile's
+    // codes fetched, the tile in set s scored. taddr: the LDS address of the entry fetched last.
+    // MM: the fetch is unconditional -- with no tile left, of any valid tile with an empty
     // resource, never scored -- so the loads issued per step are a compile-time count and the wait in front of
     // the ADC leaves this step's two in flight under it (vmcnt(3) / vmcnt(2); the older pair is waited for
     // before the issue). The other instantiations keep the conditional fetch and with it the full wait behind
@@ -436,11 +550,11 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     auto step = [&](int s) {
       const int f = (s + DEPTH) % NS;
       const int fl = flag_up();
-      const bool real = i + DEPTH * NW < nent;
       if constexpr (MM) {
-        taddr += real ? ENT_STRIDE : 0u;
-        fetch(taddr, A[f], B[f], e[f], real ? mm_size : 0u);
-      } else if (real) {
+        fetch_mm(A[f], B[f], e[f]);
+        --inflight;               // (the tile scored below)
+        asm volatile("" : "+s"(inflight));   // (a count in a scalar register, not a lane mask made of `real`)
+      } else if (i + DEPTH * NW < nent) {
         taddr += ENT_STRIDE;
         fetch(taddr, A[f], B[f], e[f]);
       }
@@ -461,7 +575,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
       for (;;) {
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          if (i >= nent) return -1;
+          if (!more()) return -1;
           step(s);
           v3_pad<V3_PAD_SALU, V3_PAD_VALU>();
           v3_pad_ldsrt<V3_PAD_LDSRT>(s_done);
@@ -478,8 +592,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
     for (;;) {                    // every condition below is wave-uniform
       // (the entry fetched last is DEPTH - 1 strides ahead of i; where that is past the share, no entry is
       // fetched any more and the address only has to be one of the table)
-      taddr = table_lds + (uint32_t)(DEPTH == 1 ? min(i, CHUNK - 1) : min(i + (DEPTH - 1) * NW, nent - 1)) * (uint32_t)sizeof(Ent);
-      asm volatile("" : "+v"(taddr));
+      if constexpr (!MM) {
+        taddr = table_lds + (uint32_t)(DEPTH == 1 ? min(i, CHUNK - 1) : min(i + (DEPTH - 1) * NW, nent - 1)) * (uint32_t)sizeof(Ent);
+        asm volatile("" : "+v"(taddr));
+      }
       int ev = hot();
       asm volatile("" : "+s"(ev));          // (one way out of the hot loop, whatever is made of ev below)
       bool meet = false;
@@ -491,7 +607,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (CAP <= 2048 ? V3_WAVES_PER_SIM
       for (int s = 0; s < NS; ++s) {
         if (ev < 0 || s < ev % NS || meet) continue;
         if (s > ev % NS) {
-          if (i >= nent) continue;
+          if (!more()) continue;
           step(s);
         }
         if (!(ev >= NS && s == ev % NS)) append(passers());   // (ev >= NS: offered in the hot loop and refused)
@@ -628,7 +744,10 @@ int pq_scan_v3(const float *xq, int nq, int d, const float *codebooks, int dsub,
     if (nprobe > 512) return launch_v3<2048, 1, 8, V3_DEPTH, true, false, true>(V3_ARGS, none, sel);
     return launch_v3<2048, 1, 8, V3_DEPTH, false, false, true>(V3_ARGS, none, sel);
   }
-  if (codes_mm && !gate) {    // the sub-quantiser-major copy: plain requests (the caller gives it to no other)
+  // the sub-quantiser-major copy: plain requests (the caller gives it to no other). Its instantiations hand
+  // out whole lists: with fewer than four lists per wave (nprobe < 32) that leaves waves idle, the strided
+  // tile table does not, and such scans are short -- they take the tile-major instantiation below.
+  if (codes_mm && !gate && nprobe >= 32) {
 #define V3_MM_ARGS xq, nq, d, codebooks, dsub, coarse_D, coarse_I, nprobe, list_offsets, tile_offsets, \
                    codes_mm, ids_tiled, k, D, I64, I32, set_mode, ent, ent_cnt, gate, pf, none, nullptr, mm_plane
     if (nprobe > 512) {
