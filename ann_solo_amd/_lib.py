@@ -95,6 +95,7 @@ EXPORTS = [
     'asl_forest_bin', 'asl_forest_fit', 'asl_forest_predict', 'asl_set_forest_workspace',
     'asl_tdc_qvalues',
     'asl_ssm_groups',
+    'asl_mgf_measure', 'asl_mgf_fill', 'asl_mgf_sort', 'asl_mgf_number',
 ]
 
 SVM_MAX_DIM = 63          # include/annsolo_mi.h: ASL_SVM_MAX_DIM
@@ -345,6 +346,11 @@ def lib():
         if hasattr(L, 'asl_ssm_groups'):
             L.asl_ssm_groups.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, c_i64p, c_i64p, C.c_void_p,
                                          C.c_void_p]
+        if hasattr(L, 'asl_mgf_measure'):
+            L.asl_mgf_measure.argtypes = [C.c_void_p, C.c_int64, C.c_int32, c_i64p]
+            L.asl_mgf_fill.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 10
+            L.asl_mgf_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, c_i64p]
+            L.asl_mgf_number.argtypes = [C.c_char_p, C.c_int32, c_f64p]
         if hasattr(L, 'asl_index_set_by_residual'):
             L.asl_index_set_by_residual.argtypes = [C.c_void_p, C.c_int32]
             L.asl_index_get_by_residual.argtypes = [C.c_void_p]
@@ -668,6 +674,18 @@ def tdc_qvalues(score, is_target, group=None, use=None, desc: bool = True, fdr=N
 
 GROUPS_MAX_SPAN = 65536   # ASL_GROUPS_MAX_SPAN
 ERR_INVALID, ERR_CAPACITY = -1, -4      # ASL_ERR_INVALID, ASL_ERR_CAPACITY
+MGF_TILE = 256            # ASL_MGF_TILE
+MGF_MAX_PEAKS = 4096      # ASL_MGF_MAX_PEAKS
+MGF_MAX_LINE = 65536      # ASL_MGF_MAX_LINE
+
+
+def mgf_number(token):
+    """``asl_mgf_number``: the numeral ``token`` (bytes or str) as the device converts it -- ``(0, value)``, or
+    ``(1, None)`` where the device defers the token to the host's ``float()``. Host only: needs no GPU."""
+    b = token.encode('utf-8') if isinstance(token, str) else bytes(token)
+    out = C.c_double(0.0)
+    rc = lib().asl_mgf_number(b, len(b), byref(out))
+    return (0, out.value) if rc == 0 else (1, None)
 
 
 def ssm_groups(mass_diff, min_group_size: int, profile: bool = False):

@@ -6,7 +6,8 @@
 ``flat_storage``, ``ann_window``, ``num_matches``, ``distinct_matches``, ``pq_by_residual``,
 ``precursor_window_open``, ``fragment_tolerance_unit``, ``score_stats``, ``device_decoys``,
 ``decoy_tolerance_unit``, ``localize_modifications``, ``device_fdr``, ``device_forest``,
-``forest_trees``, ``device_qvalues``, ``device_groups``, ``chimeric_search``, ``chimeric_window``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``forest_trees``, ``device_qvalues``, ``device_groups``, ``chimeric_search``, ``chimeric_window``,
+``device_mgf``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -150,6 +151,12 @@ class Config:
     # result, hash and output byte is what it is without the switch
     chimeric_search: bool = False
     chimeric_window: float = 2.0
+    # ``SpectralLibrary.search(filename)`` reads a query file whose name ends in ``.mgf`` (any letter case) with
+    # the engine's own reader (mgf.py, csrc/mgf.hip; DESIGN.md 3 "Query files"): the text is parsed by kernels and
+    # the raw peaks go to the preprocessing where they lie, in place of ``query_reader`` and ``pack_queries``; the
+    # same packed queries either way. Other extensions keep the injected or the reference's reader. Off: nothing
+    # new is launched
+    device_mgf: bool = False
 
     MAX_PEAKS = 256     # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
@@ -247,6 +254,7 @@ class Config:
             raise ValueError(f'chimeric_window = {self.chimeric_window}: a width in m/z, >= 0')
         if self.chimeric_search and self.num_gpus and int(self.num_gpus) > 1:
             raise ValueError('chimeric_search does not run on a sharded index (num_gpus > 1)')
+        self.device_mgf = bool(self.device_mgf)
         if self.precursor_window_open is not None:
             try:
                 lo, hi = (float(v) for v in self.precursor_window_open)
@@ -438,3 +446,8 @@ def add_arguments(parser) -> None:
     parser.add_argument('--chimeric_window', default=d.chimeric_window, type=float,
                         help="with --chimeric_search: full width in m/z of the window around the query's precursor "
                              'when the queries carry no isolation_window (default: %(default)s)')
+    parser.add_argument('--device_mgf', action='store_true', default=d.device_mgf,
+                        help='read a query file whose name ends in .mgf with the GPU reader: lines, parameters and '
+                             "numerals are parsed by kernels and the peaks never become Python objects; the same "
+                             'queries as the host reader gives; malformed blocks raise an error naming the line or '
+                             'spectrum; other query formats are read as before (default: off)')

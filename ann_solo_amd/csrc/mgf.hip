@@ -1,0 +1,837 @@
+// mgf.hip -- MGF query files parsed on the device (asl_mgf_measure / asl_mgf_fill / asl_mgf_sort) and the numeral
+// converter on the host (asl_mgf_number). gfx950 only. DESIGN.md 3 "Query files"; the dialect is stated in
+// include/annsolo_mi.h and restated in tests/mgf_ref.py.
+//
+//   starts   count the line starts (MG_SPAN bytes a thread), scan the counts, write line_start[]
+//   lines    one thread per line: strip, classify (BEGIN, END, the five parameters, other parameter, peak, skip)
+//            and convert its numerals (mgf_number.hpp); what the converter defers is flagged, never guessed
+//   state    a scan that composes the lines' maps of the two states {outside, inside a block}: BEGIN -> inside,
+//            END -> outside, anything else keeps the state. (A +1 / -1 depth sum would go negative on a stray
+//            END outside a block, which the dialect ignores; the composed maps saturate by construction.)
+//   counts   a scan of (blocks opened, blocks closed, in-block peaks, in-block deferred tokens, byte and line
+//            behind the last closed block): spectrum ordinal, peak slot and deferred slot of every line
+//   resolve  per line: nested BEGIN / one-token peak line -> the first structural error (integer atomicMin of
+//            line << 8 | kind); "the last duplicate wins" -> integer atomicMax of the line number per (spectrum,
+//            key); BEGIN and END lines record their block's extent
+//   fill     peaks scattered to their slots, the deferred tokens' byte ranges and destinations, the per-spectrum
+//            columns
+//   sort     one adjacent compare per peak flags the spectra that descend anywhere; those alone are sorted, one
+//            workgroup each, by a bitonic network over at most 4096 unique keys (m/z bits, ordinal) in LDS
+//
+// Every scan is reduce -> scan of the block partials (recursively) -> apply, as separate launches on the library's
+// stream: no kernel waits on another workgroup. Integer atomics only, and none whose arrival order reaches the
+// output. Every byte index is bounded by the chunk length and every line by line_start[n_lines] == n.
+#include <algorithm>
+#include <cmath>
+
+#include "common.hpp"
+#include "mgf_number.hpp"
+
+namespace asl {
+
+constexpr int MG_NT = ASL_MGF_TILE;            // threads of every kernel here = elements per block of a scan level
+constexpr int MG_SPAN = 16;                    // bytes per thread of the line-start passes
+constexpr int MG_MAX_PEAKS = ASL_MGF_MAX_PEAKS;
+static_assert(MG_NT == 256, "four waves: mg_block_scan's wave totals");
+static_assert((MG_MAX_PEAKS & (MG_MAX_PEAKS - 1)) == 0, "the bitonic network pads to a power of two");
+
+enum : uint8_t {   // what a line is, whatever surrounds it
+  MK_SKIP = 0, MK_BEGIN, MK_END, MK_TITLE, MK_SCAN, MK_PEPMASS, MK_CHARGE, MK_RT, MK_OTHER, MK_PEAK, MK_PEAK1
+};
+constexpr int MG_KEYS = 5;                     // MK_TITLE .. MK_RT
+
+struct MgTotals {   // the counts scan's result over all lines
+  uint32_t opens, closes, peaks, defers, cons_byte, cons_line;
+};
+struct MgFinal {    // written by the resolve and check kernels
+  unsigned long long err;   // (line << 8 | kind) of the first structural error, ~0: none
+  uint32_t n_peaks, n_def;  // at the last closed block's END
+  uint32_t cap_spec;        // first spectrum above MG_MAX_PEAKS, ~0: none
+  uint32_t long_line;       // first line above ASL_MGF_MAX_LINE bytes, ~0: none
+};
+
+// ---------------------------------------------------------------------------------------------- scans
+struct MgSum {
+  using T = uint32_t;
+  __device__ static T identity() { return 0u; }
+  __device__ static T op(T a, T b) { return a + b; }
+};
+// A line as a map of the block state: bit x of the value is the state after the line when the state before is x.
+struct MgState {
+  using T = uint32_t;
+  __device__ static T identity() { return 2u; }
+  __device__ static T op(T a, T b) { return ((b >> (a & 1u)) & 1u) | (((b >> ((a >> 1) & 1u)) & 1u) << 1); }
+};
+struct MgCount {
+  using T = MgTotals;
+  __device__ static T identity() { return {0u, 0u, 0u, 0u, 0u, 0u}; }
+  __device__ static T op(T a, T b) {
+    return {a.opens + b.opens, a.closes + b.closes, a.peaks + b.peaks, a.defers + b.defers,
+            a.cons_byte > b.cons_byte ? a.cons_byte : b.cons_byte,
+            a.cons_line > b.cons_line ? a.cons_line : b.cons_line};
+  }
+};
+
+template <class T>
+__device__ __forceinline__ T mg_shfl_up(T v, int delta) {
+  static_assert(sizeof(T) % 4 == 0, "whole words");
+  uint32_t w[sizeof(T) / 4];
+  __builtin_memcpy(w, &v, sizeof(T));
+#pragma unroll
+  for (size_t k = 0; k < sizeof(T) / 4; ++k) w[k] = (uint32_t)__shfl_up((int)w[k], delta, 64);
+  __builtin_memcpy(&v, w, sizeof(T));
+  return v;
+}
+
+// inclusive scan over the block's MG_NT values in thread order; *total: the block's sum, in every thread
+template <class Op>
+__device__ __forceinline__ typename Op::T mg_block_scan(typename Op::T x, typename Op::T *total) {
+  using T = typename Op::T;
+  __shared__ T wave_tot[MG_NT / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const T o = mg_shfl_up(x, d);
+    if (lane >= d) x = Op::op(o, x);
+  }
+  if (lane == 63) wave_tot[wave] = x;
+  __syncthreads();
+  T pre = Op::identity(), all = Op::identity();
+#pragma unroll
+  for (int w = 0; w < MG_NT / 64; ++w) {
+    if (w < wave) pre = Op::op(pre, wave_tot[w]);
+    all = Op::op(all, wave_tot[w]);
+  }
+  *total = all;
+  return Op::op(pre, x);
+}
+
+// A view names a scan's operator (Op), reads element i (load) and takes its inclusive result (store).
+template <class V>
+__global__ __launch_bounds__(MG_NT) void mgf_scan_reduce_kernel(V view, int64_t n, typename V::Op::T *partial) {
+  using Op = typename V::Op;
+  const int64_t i = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  typename Op::T total;
+  mg_block_scan<Op>(i < n ? view.load(i) : Op::identity(), &total);
+  if (threadIdx.x == 0) partial[blockIdx.x] = total;
+}
+// partial: the INCLUSIVE scan of the blocks' sums (block b starts from partial[b - 1]), or nullptr for one block
+template <class V>
+__global__ __launch_bounds__(MG_NT) void mgf_scan_apply_kernel(V view, int64_t n, const typename V::Op::T *partial) {
+  using Op = typename V::Op;
+  const int64_t i = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  const typename Op::T own = i < n ? view.load(i) : Op::identity();
+  typename Op::T total;
+  typename Op::T incl = mg_block_scan<Op>(own, &total);
+  if (partial != nullptr && blockIdx.x > 0) incl = Op::op(partial[blockIdx.x - 1], incl);
+  if (i < n) view.store(i, incl, own);
+}
+
+template <class O>
+struct MgPlainView {   // an array scanned in place (the upper levels)
+  using Op = O;
+  typename O::T *a;
+  __device__ typename O::T load(int64_t i) const { return a[i]; }
+  __device__ void store(int64_t i, typename O::T incl, typename O::T) const { a[i] = incl; }
+};
+
+// ---------------------------------------------------------------------------------------------- line starts
+// Bit k of the result: byte 16 e + k is a '\n' that is followed by another byte, i.e. byte 16 e + k + 1 starts a
+// line. vec: t is 16-byte aligned.
+__device__ __forceinline__ uint32_t mg_newlines(const uint8_t *__restrict__ t, int64_t n, int64_t e, bool vec) {
+  const int64_t j0 = e * MG_SPAN;
+  uint32_t m = 0u;
+  if (vec && j0 + MG_SPAN <= n) {
+    const uint4 v = *reinterpret_cast<const uint4 *>(t + j0);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (((w[q] >> (8 * b)) & 255u) == (uint32_t)'\n') m |= 1u << (4 * q + b);
+  } else {
+    for (int k = 0; k < MG_SPAN; ++k)
+      if (j0 + k < n && t[j0 + k] == (uint8_t)'\n') m |= 1u << k;
+  }
+  const int64_t last = n - 1 - j0;   // (the chunk's last byte starts nothing behind it)
+  if (last >= 0 && last < MG_SPAN) m &= ~(1u << last);
+  return m;
+}
+__device__ __forceinline__ uint32_t mg_starts(const uint8_t *__restrict__ t, int64_t n, int64_t e, bool vec) {
+  return (uint32_t)__popc(mg_newlines(t, n, e, vec)) + (e == 0 && n > 0 ? 1u : 0u);
+}
+
+__global__ __launch_bounds__(MG_NT) void mgf_count_lines_kernel(const uint8_t *__restrict__ t, int64_t n, int64_t ne,
+                                                                int vec, unsigned long long *__restrict__ total) {
+  const int64_t e = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  uint32_t tot;
+  mg_block_scan<MgSum>(e < ne ? mg_starts(t, n, e, vec != 0) : 0u, &tot);
+  if (threadIdx.x == 0 && tot != 0u) atomicAdd(total, (unsigned long long)tot);   // (an integer count)
+}
+
+struct LineStartView {   // element e: the line starts its MG_SPAN bytes produce, in file order
+  using Op = MgSum;
+  const uint8_t *t;
+  int64_t n;
+  int vec;
+  uint32_t *line_start;   // [n_lines + 1]
+  uint32_t n_lines;
+  __device__ uint32_t load(int64_t e) const { return mg_starts(t, n, e, vec != 0); }
+  __device__ void store(int64_t e, uint32_t incl, uint32_t own) const {
+    uint32_t o = incl - own;
+    if (e == 0 && n > 0 && o < n_lines) line_start[o++] = 0u;
+    uint32_t m = mg_newlines(t, n, e, vec != 0);
+    while (m != 0u) {
+      const int k = __ffs((int)m) - 1;
+      m &= m - 1u;
+      if (o < n_lines) line_start[o++] = (uint32_t)(e * MG_SPAN + k + 1);
+    }
+  }
+};
+
+// ---------------------------------------------------------------------------------------------- one line
+__device__ __forceinline__ bool mg_ws(uint8_t c) { return c == 32 || (c >= 9 && c <= 13); }   // bytes.strip / split
+
+// [p, q): line L without the blanks around it (a == b gives p == q)
+__device__ __forceinline__ void mg_strip(const uint8_t *__restrict__ t, uint32_t a, uint32_t b, uint32_t *p,
+                                         uint32_t *q) {
+  while (b > a && mg_ws(t[b - 1])) --b;
+  while (a < b && mg_ws(t[a])) ++a;
+  *p = a, *q = b;
+}
+__device__ __forceinline__ bool mg_is(const uint8_t *__restrict__ t, uint32_t p, uint32_t len, const char *lit,
+                                      uint32_t lit_len, bool fold) {
+  if (len != lit_len) return false;
+  for (uint32_t k = 0; k < lit_len; ++k) {
+    uint8_t c = t[p + k];
+    if (fold && c >= 'A' && c <= 'Z') c += 32;
+    if (c != (uint8_t)lit[k]) return false;
+  }
+  return true;
+}
+__device__ __forceinline__ uint32_t mg_find(const uint8_t *__restrict__ t, uint32_t p, uint32_t q, uint8_t c) {
+  while (p < q && t[p] != c) ++p;
+  return p;
+}
+__device__ __forceinline__ uint32_t mg_token_end(const uint8_t *__restrict__ t, uint32_t p, uint32_t q) {
+  while (p < q && !mg_ws(t[p])) ++p;
+  return p;
+}
+__device__ __forceinline__ uint32_t mg_skip_ws(const uint8_t *__restrict__ t, uint32_t p, uint32_t q) {
+  while (p < q && mg_ws(t[p])) ++p;
+  return p;
+}
+// The two tokens a peak line reads; t1a == q: there is no second one.
+struct MgPeakTokens {
+  uint32_t t0a, t0b, t1a, t1b;
+};
+__device__ __forceinline__ MgPeakTokens mg_peak_tokens(const uint8_t *__restrict__ t, uint32_t p, uint32_t q) {
+  MgPeakTokens k;
+  k.t0a = p;
+  k.t0b = mg_token_end(t, p, q);
+  k.t1a = mg_skip_ws(t, k.t0b, q);
+  k.t1b = mg_token_end(t, k.t1a, q);
+  return k;
+}
+// The numeral a PEPMASS (first token of the value) or RTINSECONDS (the whole value) line reads; [p, q) stripped.
+__device__ __forceinline__ void mg_param_token(const uint8_t *__restrict__ t, uint32_t p, uint32_t q, uint8_t kind,
+                                               uint32_t *ta, uint32_t *tb) {
+  const uint32_t v = mg_skip_ws(t, mg_find(t, p, q, (uint8_t)'=') + 1u, q);   // ('=' exists: v <= q)
+  *ta = v < q ? v : q;
+  *tb = kind == MK_PEPMASS ? mg_token_end(t, *ta, q) : q;
+}
+// The first element of a charge list: digits with the sign before or behind them; what follows is the end, a
+// comma or "and". 1 .. 255, else -1.
+__device__ __forceinline__ int mg_charge(const uint8_t *__restrict__ t, uint32_t i, uint32_t q) {
+  int sign = 0;
+  if (i < q && (t[i] == '+' || t[i] == '-')) sign = t[i++] == '-' ? -1 : 1;
+  int v = 0, nd = 0;
+  for (; i < q && t[i] >= '0' && t[i] <= '9'; ++i, ++nd)
+    if (v < 100000) v = v * 10 + (t[i] - '0');
+  if (nd == 0) return -1;
+  if (sign == 0 && i < q && (t[i] == '+' || t[i] == '-')) sign = t[i++] == '-' ? -1 : 1;
+  i = mg_skip_ws(t, i, q);
+  const bool ends = i == q || t[i] == ',' || (q - i >= 3u && t[i] == 'a' && t[i + 1] == 'n' && t[i + 2] == 'd');
+  if (!ends || sign < 0 || v < 1 || v > 255) return -1;
+  return v;
+}
+
+__device__ __forceinline__ uint64_t mg_pack_peak(double mz, double it) {
+  return (uint64_t)__float_as_uint((float)mz) | ((uint64_t)__float_as_uint((float)it) << 32);
+}
+
+// kind, dflag (bit k: numeral k of the line was deferred) and val (a peak's two float32, a parameter's double or
+// charge) of every line
+__global__ __launch_bounds__(MG_NT) void mgf_lines_kernel(const uint8_t *__restrict__ t,
+                                                          const uint32_t *__restrict__ line_start, int64_t n_lines,
+                                                          int last, uint8_t *__restrict__ kind,
+                                                          uint8_t *__restrict__ dflag, uint64_t *__restrict__ val,
+                                                          MgFinal *__restrict__ fin) {
+  const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  if (L >= n_lines) return;
+  const uint32_t a = line_start[L], b = line_start[L + 1];
+  // A thread walks its line byte by byte: a line beyond the cap is not walked at all (the call fails).
+  // The final line of a chunk that is not the file's last may be cut anywhere: it is not looked at either.
+  const bool too_long = b - a > (uint32_t)ASL_MGF_MAX_LINE;
+  if (too_long) atomicMin(&fin->long_line, (uint32_t)L);
+  if (too_long || (last == 0 && L == n_lines - 1 && t[b - 1] != (uint8_t)'\n')) {
+    kind[L] = MK_SKIP, dflag[L] = 0, val[L] = 0;
+    return;
+  }
+  uint32_t p, q;
+  mg_strip(t, a, b, &p, &q);
+  uint8_t k = MK_SKIP, df = 0;
+  uint64_t v = 0;
+  const uint8_t c = p < q ? t[p] : (uint8_t)'#';
+  if (c == '#' || c == ';' || c == '!' || c == '/') {
+    k = MK_SKIP;
+  } else if (mg_is(t, p, q - p, "BEGIN IONS", 10, false)) {
+    k = MK_BEGIN;
+  } else if (mg_is(t, p, q - p, "END IONS", 8, false)) {
+    k = MK_END;
+  } else {
+    const uint32_t eq = mg_find(t, p, q, (uint8_t)'=');
+    if (eq < q) {
+      const uint32_t kl = eq - p;
+      k = mg_is(t, p, kl, "title", 5, true) ? MK_TITLE
+          : mg_is(t, p, kl, "scan", 4, true) ? MK_SCAN
+          : mg_is(t, p, kl, "pepmass", 7, true) ? MK_PEPMASS
+          : mg_is(t, p, kl, "charge", 6, true) ? MK_CHARGE
+          : mg_is(t, p, kl, "rtinseconds", 11, true) ? MK_RT : MK_OTHER;
+      if (k == MK_PEPMASS || k == MK_RT) {
+        uint32_t ta, tb;
+        mg_param_token(t, p, q, k, &ta, &tb);
+        double d = 0.0;
+        df = (uint8_t)mgf_number(reinterpret_cast<const char *>(t) + ta, (int)(tb - ta), &d);
+        v = (uint64_t)__double_as_longlong(d);
+      } else if (k == MK_CHARGE) {
+        v = (uint64_t)(int64_t)mg_charge(t, mg_skip_ws(t, eq + 1u, q), q);
+      }
+    } else {
+      const MgPeakTokens tk = mg_peak_tokens(t, p, q);
+      if (tk.t1a == q) {
+        k = MK_PEAK1;
+      } else {
+        k = MK_PEAK;
+        double d0 = 0.0, d1 = 0.0;
+        df = (uint8_t)(mgf_number(reinterpret_cast<const char *>(t) + tk.t0a, (int)(tk.t0b - tk.t0a), &d0) |
+                       (mgf_number(reinterpret_cast<const char *>(t) + tk.t1a, (int)(tk.t1b - tk.t1a), &d1) << 1));
+        v = mg_pack_peak(d0, d1);
+      }
+    }
+  }
+  kind[L] = k, dflag[L] = df, val[L] = v;
+}
+
+struct StateView {   // after[L]: is line L + 1 inside a block?
+  using Op = MgState;
+  const uint8_t *kind;
+  uint8_t *after;
+  __device__ uint32_t load(int64_t L) const {
+    const uint8_t k = kind[L];
+    return k == MK_BEGIN ? 3u : k == MK_END ? 0u : 2u;
+  }
+  __device__ void store(int64_t L, uint32_t incl, uint32_t) const { after[L] = (uint8_t)(incl & 1u); }   // from outside
+};
+
+struct CountView {   // spec[L]: blocks opened up to and including L; slot / dslot: peaks / deferred tokens before L
+  using Op = MgCount;
+  const uint8_t *kind, *dflag, *after;
+  const uint32_t *line_start;
+  uint32_t *spec, *slot, *dslot;
+  MgTotals *totals;
+  int64_t n_lines;
+  __device__ MgTotals load(int64_t L) const {
+    const bool in = L > 0 && after[L - 1] != 0;
+    const uint8_t k = kind[L];
+    MgTotals v = {0u, 0u, 0u, 0u, 0u, 0u};
+    if (!in) {
+      v.opens = k == MK_BEGIN ? 1u : 0u;
+      return v;
+    }
+    if (k == MK_END) v.closes = 1u, v.cons_byte = line_start[L + 1], v.cons_line = (uint32_t)(L + 1);
+    if (k == MK_PEAK) v.peaks = 1u;
+    if (k == MK_PEAK || k == MK_PEPMASS || k == MK_RT) v.defers = (uint32_t)__popc((uint32_t)dflag[L]);
+    return v;
+  }
+  __device__ void store(int64_t L, MgTotals incl, MgTotals own) const {
+    spec[L] = incl.opens, slot[L] = incl.peaks - own.peaks, dslot[L] = incl.defers - own.defers;
+    if (L == n_lines - 1) *totals = incl;
+  }
+};
+
+// gate: lines behind it belong to a block this chunk does not close (they come again with the next chunk)
+__global__ __launch_bounds__(MG_NT) void mgf_resolve_kernel(const uint8_t *__restrict__ kind,
+                                                            const uint8_t *__restrict__ after,
+                                                            const uint32_t *__restrict__ spec,
+                                                            const uint32_t *__restrict__ slot,
+                                                            const uint32_t *__restrict__ dslot, int64_t n_lines,
+                                                            int64_t gate, uint32_t n_open, uint32_t n_closed,
+                                                            uint32_t *__restrict__ first_line,
+                                                            uint32_t *__restrict__ peak_begin,
+                                                            uint32_t *__restrict__ peak_end,
+                                                            uint32_t *__restrict__ key_line, MgFinal *__restrict__ fin) {
+  const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  if (L >= n_lines) return;
+  const bool in = L > 0 && after[L - 1] != 0;
+  const uint8_t k = kind[L];
+  const uint32_t s = spec[L] - 1u;   // (in a block, or opening one: spec[L] >= 1)
+  if (!in) {
+    if (k == MK_BEGIN && s < n_open) first_line[s] = (uint32_t)L, peak_begin[s] = slot[L];
+    return;
+  }
+  if (s >= n_open) return;           // (cannot happen: kept as the bound of every per-spectrum store)
+  if ((k == MK_BEGIN || k == MK_PEAK1) && L < gate)
+    atomicMin(&fin->err, ((unsigned long long)L << 8) | (k == MK_BEGIN ? ASL_MGF_ERR_NESTED : ASL_MGF_ERR_ONE_TOKEN));
+  if (k == MK_END) {
+    peak_end[s] = slot[L];
+    if (s + 1u == n_closed) fin->n_peaks = slot[L], fin->n_def = dslot[L];
+  }
+  if (k >= MK_TITLE && k <= MK_RT) atomicMax(&key_line[(size_t)s * MG_KEYS + (k - MK_TITLE)], (uint32_t)(L + 1));
+}
+
+__global__ __launch_bounds__(MG_NT) void mgf_capacity_kernel(const uint32_t *__restrict__ peak_begin,
+                                                             const uint32_t *__restrict__ peak_end, uint32_t n_closed,
+                                                             MgFinal *__restrict__ fin) {
+  const uint32_t s = blockIdx.x * MG_NT + threadIdx.x;
+  if (s < n_closed && peak_end[s] - peak_begin[s] > (uint32_t)MG_MAX_PEAKS) atomicMin(&fin->cap_spec, s);
+}
+
+// ---------------------------------------------------------------------------------------------- fill
+// rec: [n_def, 5] (offset, length, destination kind, destination index, line)
+__global__ __launch_bounds__(MG_NT) void mgf_fill_lines_kernel(
+    const uint8_t *__restrict__ t, const uint32_t *__restrict__ line_start, const uint8_t *__restrict__ kind,
+    const uint8_t *__restrict__ dflag, const uint64_t *__restrict__ val, const uint8_t *__restrict__ after,
+    const uint32_t *__restrict__ spec, const uint32_t *__restrict__ slot, const uint32_t *__restrict__ dslot,
+    int64_t n_lines, uint32_t n_blocks, uint32_t n_peaks, uint32_t n_def, float *__restrict__ mz,
+    float *__restrict__ intensity, uint8_t *__restrict__ charge, int32_t *__restrict__ rec) {
+  const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  if (L >= n_lines) return;
+  if (!(L > 0 && after[L - 1] != 0) || spec[L] - 1u >= n_blocks) return;   // (an open block's slots lie behind n_peaks)
+  const uint8_t k = kind[L], df = dflag[L];
+  if (k == MK_PEAK) {
+    const uint32_t o = slot[L];
+    if (o < n_peaks) {
+      const uint64_t v = val[L];
+      mz[o] = __uint_as_float((uint32_t)v), intensity[o] = __uint_as_float((uint32_t)(v >> 32));
+      if (charge != nullptr) charge[o] = 0;
+    }
+  }
+  if (df == 0 || !(k == MK_PEAK || k == MK_PEPMASS || k == MK_RT)) return;
+  uint32_t p, q, r = dslot[L];
+  mg_strip(t, line_start[L], line_start[L + 1], &p, &q);
+  if (k == MK_PEAK) {
+    const MgPeakTokens tk = mg_peak_tokens(t, p, q);
+    if ((df & 1) && r < n_def) {
+      int32_t *o = rec + (size_t)r * 5;
+      o[0] = (int32_t)tk.t0a, o[1] = (int32_t)(tk.t0b - tk.t0a), o[2] = ASL_MGF_DEST_MZ, o[3] = (int32_t)slot[L];
+      o[4] = (int32_t)L;
+      ++r;
+    }
+    if ((df & 2) && r < n_def) {
+      int32_t *o = rec + (size_t)r * 5;
+      o[0] = (int32_t)tk.t1a, o[1] = (int32_t)(tk.t1b - tk.t1a), o[2] = ASL_MGF_DEST_INTENSITY;
+      o[3] = (int32_t)slot[L], o[4] = (int32_t)L;
+    }
+  } else if (r < n_def) {   // (the spectrum kernel names the destination of the line that wins)
+    uint32_t ta, tb;
+    mg_param_token(t, p, q, k, &ta, &tb);
+    int32_t *o = rec + (size_t)r * 5;
+    o[0] = (int32_t)ta, o[1] = (int32_t)(tb - ta), o[2] = ASL_MGF_DEST_NONE, o[3] = (int32_t)(spec[L] - 1u);
+    o[4] = (int32_t)L;
+  }
+}
+
+__global__ __launch_bounds__(MG_NT) void mgf_fill_spectra_kernel(
+    const uint8_t *__restrict__ t, const uint32_t *__restrict__ line_start, const uint8_t *__restrict__ dflag,
+    const uint64_t *__restrict__ val, const uint32_t *__restrict__ dslot, const uint32_t *__restrict__ first_line,
+    const uint32_t *__restrict__ peak_begin, const uint32_t *__restrict__ key_line, uint32_t n_closed,
+    uint32_t n_peaks, uint32_t n_def, int32_t *__restrict__ offsets, double *__restrict__ pmz,
+    int32_t *__restrict__ pcharge, double *__restrict__ rt, int32_t *__restrict__ ident,
+    int32_t *__restrict__ first, int32_t *__restrict__ rec) {
+  const uint32_t s = blockIdx.x * MG_NT + threadIdx.x;
+  if (s >= n_closed) return;
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  offsets[s] = (int32_t)peak_begin[s];
+  if (s + 1u == n_closed) offsets[n_closed] = (int32_t)n_peaks;
+  first[s] = (int32_t)first_line[s];
+  const uint32_t *kl = key_line + (size_t)s * MG_KEYS;
+  double *const dst[2] = {pmz, rt};
+  const int which[2] = {MK_PEPMASS - MK_TITLE, MK_RT - MK_TITLE};
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const uint32_t l = kl[which[j]];
+    double v = nan;
+    if (l != 0u) {
+      if (dflag[l - 1u] == 0) {
+        v = __longlong_as_double((long long)val[l - 1u]);
+      } else if (dslot[l - 1u] < n_def) {
+        rec[(size_t)dslot[l - 1u] * 5 + 2] = j == 0 ? ASL_MGF_DEST_PEPMASS : ASL_MGF_DEST_RT;
+      }
+    }
+    dst[j][s] = v;
+  }
+  const uint32_t lc = kl[MK_CHARGE - MK_TITLE];
+  pcharge[s] = lc != 0u ? (int32_t)(int64_t)val[lc - 1u] : 0;
+  const uint32_t li = kl[0] != 0u ? kl[0] : kl[MK_SCAN - MK_TITLE];
+  int32_t io = 0, il = -1;
+  if (li != 0u) {
+    uint32_t p, q;
+    mg_strip(t, line_start[li - 1u], line_start[li], &p, &q);
+    const uint32_t v = mg_skip_ws(t, mg_find(t, p, q, (uint8_t)'=') + 1u, q);
+    io = (int32_t)(v < q ? v : q), il = (int32_t)(q - (uint32_t)io);
+  }
+  ident[2 * (size_t)s] = io, ident[2 * (size_t)s + 1] = il;
+}
+
+// ---------------------------------------------------------------------------------------------- sort
+__global__ __launch_bounds__(MG_NT) void mgf_descending_kernel(const int32_t *__restrict__ offsets,
+                                                               const float *__restrict__ mz, int32_t n_spec,
+                                                               int64_t n_peaks, uint32_t *__restrict__ flag,
+                                                               uint32_t *__restrict__ list,
+                                                               uint32_t *__restrict__ n_list) {
+  const int64_t i = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  if (i + 1 >= n_peaks || !(mz[i + 1] < mz[i])) return;
+  int lo = 0, hi = n_spec;            // the last spectrum with offsets[s] <= i
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((int64_t)offsets[mid] <= i) lo = mid; else hi = mid;
+  }
+  if (i + 1 >= (int64_t)offsets[lo + 1]) return;   // the pair straddles two spectra
+  if (atomicExch(&flag[lo], 1u) == 0u) list[atomicAdd(n_list, 1u)] = (uint32_t)lo;   // (once per spectrum)
+}
+
+// Ascending in (float32 m/z, file order): -0.0 and +0.0 are one key, as in numpy's stable argsort.
+__device__ __forceinline__ uint64_t mg_sort_key(float mz, uint32_t ordinal) {
+  uint32_t u = mz == 0.0f ? 0u : __float_as_uint(mz);
+  u = (u >> 31) ? ~u : (u | 0x80000000u);
+  return ((uint64_t)u << 32) | ordinal;
+}
+
+__global__ __launch_bounds__(MG_NT) void mgf_sort_kernel(const uint32_t *__restrict__ list,
+                                                         const int32_t *__restrict__ offsets,
+                                                         const float *__restrict__ mz,
+                                                         const float *__restrict__ intensity,
+                                                         float *__restrict__ mz_tmp, float *__restrict__ it_tmp,
+                                                         uint32_t *__restrict__ too_long) {
+  __shared__ uint64_t key[MG_MAX_PEAKS];
+  const uint32_t s = list[blockIdx.x];
+  const int a = offsets[s], cnt = offsets[s + 1] - a;
+  if (cnt > MG_MAX_PEAKS) {            // (the same for the whole workgroup)
+    if (threadIdx.x == 0) atomicOr(too_long, 1u);
+    return;
+  }
+  int P = 2;
+  while (P < cnt) P <<= 1;
+  for (int i = threadIdx.x; i < P; i += MG_NT) key[i] = i < cnt ? mg_sort_key(mz[a + i], (uint32_t)i) : ~0ull;
+  __syncthreads();
+  for (int k = 2; k <= P; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < P; i += MG_NT) {
+        const int o = i ^ j;
+        if (o > i) {
+          const uint64_t x = key[i], y = key[o];
+          if ((x > y) == ((i & k) == 0)) key[i] = y, key[o] = x;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = threadIdx.x; i < cnt; i += MG_NT) {
+    const int src = (int)(uint32_t)key[i];
+    mz_tmp[a + i] = mz[a + src], it_tmp[a + i] = intensity[a + src];
+  }
+}
+
+__global__ __launch_bounds__(MG_NT) void mgf_sort_copy_kernel(const uint32_t *__restrict__ list,
+                                                              const int32_t *__restrict__ offsets,
+                                                              const float *__restrict__ mz_tmp,
+                                                              const float *__restrict__ it_tmp, float *__restrict__ mz,
+                                                              float *__restrict__ intensity) {
+  const uint32_t s = list[blockIdx.x];
+  const int a = offsets[s], cnt = offsets[s + 1] - a;
+  if (cnt > MG_MAX_PEAKS) return;
+  for (int i = threadIdx.x; i < cnt; i += MG_NT) mz[a + i] = mz_tmp[a + i], intensity[a + i] = it_tmp[a + i];
+}
+
+namespace {
+
+// grow-only device workspace; asl_mgf_fill reads what the asl_mgf_measure before it left here
+struct MgfWork {
+  DevBuf<uint32_t> line_start, spec, slot, dslot, first_line, peak_begin, peak_end, key_line, flag, list, small;
+  DevBuf<uint8_t> kind, dflag, after;
+  DevBuf<uint64_t> val;
+  DevBuf<unsigned long long> count;
+  DevBuf<MgTotals> partial, totals;
+  DevBuf<MgFinal> fin;
+  DevBuf<float> mz_tmp, it_tmp;
+  // the measured chunk
+  const void *text = nullptr;
+  int64_t n = -1, n_lines = 0;
+  uint32_t n_closed = 0, n_peaks = 0, n_def = 0;
+  uint32_t n_blocks = 0;   // blocks whose deferred tokens are listed: the closed ones, at the file's end the open one too
+};
+MgfWork &work() {
+  static MgfWork w;
+  return w;
+}
+
+int64_t partial_slots(int64_t n) {   // block partials of all levels of a scan over n elements
+  int64_t total = 0;
+  while (n > MG_NT) {
+    n = cdiv(n, MG_NT);
+    total += n;
+  }
+  return total;
+}
+
+template <class O>
+int scan_in_place(typename O::T *a, int64_t n, typename O::T *scratch) {   // inclusive, the upper levels
+  MgPlainView<O> v{a};
+  const int64_t nb = cdiv(n, MG_NT);
+  if (nb > 1) {
+    hipLaunchKernelGGL(mgf_scan_reduce_kernel<MgPlainView<O>>, dim3((unsigned)nb), dim3(MG_NT), 0, stream(), v, n,
+                       scratch);
+    ASL_CHECK_LAUNCH();
+    ASL_TRY(scan_in_place<O>(scratch, nb, scratch + nb));
+  }
+  hipLaunchKernelGGL(mgf_scan_apply_kernel<MgPlainView<O>>, dim3((unsigned)nb), dim3(MG_NT), 0, stream(), v, n,
+                     nb > 1 ? scratch : nullptr);
+  ASL_CHECK_LAUNCH();
+  return ASL_OK;
+}
+
+template <class V>
+int scan_view(const V &v, int64_t n, void *scratch_bytes) {
+  using T = typename V::Op::T;
+  T *scratch = static_cast<T *>(scratch_bytes);
+  const int64_t nb = cdiv(n, MG_NT);
+  if (nb > 1) {
+    hipLaunchKernelGGL(mgf_scan_reduce_kernel<V>, dim3((unsigned)nb), dim3(MG_NT), 0, stream(), v, n, scratch);
+    ASL_CHECK_LAUNCH();
+    ASL_TRY(scan_in_place<typename V::Op>(scratch, nb, scratch + nb));
+  }
+  hipLaunchKernelGGL(mgf_scan_apply_kernel<V>, dim3((unsigned)nb), dim3(MG_NT), 0, stream(), v, n,
+                     nb > 1 ? scratch : nullptr);
+  ASL_CHECK_LAUNCH();
+  return ASL_OK;
+}
+
+inline unsigned blocks_of(int64_t n) { return (unsigned)std::max<int64_t>(cdiv(n, MG_NT), 1); }
+
+}  // namespace
+}  // namespace asl
+
+using namespace asl;
+
+extern "C" int asl_mgf_number(const char *s, int32_t n, double *out) {
+  if (s == nullptr || n < 0 || out == nullptr) return 1;
+  return mgf_number(s, (int)n, out);
+}
+
+extern "C" int asl_mgf_measure(const uint8_t *text, int64_t n, int32_t last, int64_t *counts) {
+  clear_error();
+  if (n >= ((int64_t)1 << 31)) return fail(ASL_ERR_CAPACITY, "mgf_measure: n = %lld, below 2^31", (long long)n);
+  if (n < 0) return fail(ASL_ERR_INVALID, "mgf_measure: n < 0");
+  if (counts == nullptr) return fail(ASL_ERR_INVALID, "mgf_measure: null counts");
+  if (last != 0 && last != 1) return fail(ASL_ERR_INVALID, "mgf_measure: last = %d, 0 or 1", (int)last);
+  MgfWork &W = work();
+  W.text = nullptr, W.n = -1;   // (nothing to fill until this call succeeds)
+  for (int k = 0; k < ASL_MGF_COUNTS; ++k) counts[k] = 0;
+  counts[ASL_MGF_ERR_LINE] = -1;
+  if (n == 0) {
+    W.text = text, W.n = 0, W.n_lines = 0, W.n_closed = W.n_peaks = W.n_def = W.n_blocks = 0;
+    return ASL_OK;
+  }
+  if (text == nullptr) return fail(ASL_ERR_INVALID, "mgf_measure: null text");
+  ASL_TRY(ensure_device());
+  if (!is_device_ptr(text)) return fail(ASL_ERR_INVALID, "mgf_measure: text must be device memory");
+  ProfScope ps("mgf_measure");
+  const int vec = (reinterpret_cast<uintptr_t>(text) & 15u) == 0 ? 1 : 0;
+  const int64_t ne = cdiv(n, MG_SPAN);
+  // line starts
+  ASL_TRY(W.count.reserve(1));
+  HIP_TRY(hipMemsetAsync(W.count.p, 0, sizeof(unsigned long long), stream()));
+  hipLaunchKernelGGL(mgf_count_lines_kernel, dim3(blocks_of(ne)), dim3(MG_NT), 0, stream(), text, n, ne, vec,
+                     W.count.p);
+  ASL_CHECK_LAUNCH();
+  unsigned long long h_lines = 0;
+  HIP_TRY(hipMemcpyAsync(&h_lines, W.count.p, sizeof(h_lines), hipMemcpyDeviceToHost, stream()));
+  ASL_TRY(sync_stream());
+  const int64_t nl = (int64_t)h_lines;   // >= 1
+  ASL_TRY(W.partial.reserve((size_t)(partial_slots(std::max(ne, nl)) + 1)));
+  ASL_TRY(W.line_start.reserve((size_t)nl + 1));
+  ASL_TRY(scan_view(LineStartView{text, n, vec, W.line_start.p, (uint32_t)nl}, ne, W.partial.p));
+  const uint32_t end = (uint32_t)n;
+  HIP_TRY(hipMemcpyAsync(W.line_start.p + nl, &end, sizeof(end), hipMemcpyHostToDevice, stream()));
+  // lines, block state, counts
+  ASL_TRY(W.kind.reserve((size_t)nl));
+  ASL_TRY(W.dflag.reserve((size_t)nl));
+  ASL_TRY(W.after.reserve((size_t)nl));
+  ASL_TRY(W.val.reserve((size_t)nl));
+  ASL_TRY(W.spec.reserve((size_t)nl));
+  ASL_TRY(W.slot.reserve((size_t)nl));
+  ASL_TRY(W.dslot.reserve((size_t)nl));
+  ASL_TRY(W.totals.reserve(1));
+  ASL_TRY(W.fin.reserve(1));
+  MgFinal F{~0ull, 0u, 0u, ~0u, ~0u};
+  HIP_TRY(hipMemcpyAsync(W.fin.p, &F, sizeof(F), hipMemcpyHostToDevice, stream()));
+  hipLaunchKernelGGL(mgf_lines_kernel, dim3(blocks_of(nl)), dim3(MG_NT), 0, stream(), text, W.line_start.p, nl,
+                     (int)last, W.kind.p, W.dflag.p, W.val.p, W.fin.p);
+  ASL_CHECK_LAUNCH();
+  ASL_TRY(scan_view(StateView{W.kind.p, W.after.p}, nl, W.partial.p));
+  ASL_TRY(scan_view(CountView{W.kind.p, W.dflag.p, W.after.p, W.line_start.p, W.spec.p, W.slot.p, W.dslot.p,
+                              W.totals.p, nl},
+                    nl, W.partial.p));
+  MgTotals T;
+  HIP_TRY(hipMemcpyAsync(&T, W.totals.p, sizeof(T), hipMemcpyDeviceToHost, stream()));
+  ASL_TRY(sync_stream());
+  // per block: extent, winning parameter lines, the first structural error, the capacity
+  const uint32_t n_open = T.opens, n_closed = T.closes;
+  const size_t ns = std::max<size_t>(n_open, 1);
+  ASL_TRY(W.first_line.reserve(ns));
+  ASL_TRY(W.peak_begin.reserve(ns));
+  ASL_TRY(W.peak_end.reserve(ns));
+  ASL_TRY(W.key_line.reserve(ns * MG_KEYS));
+  HIP_TRY(hipMemsetAsync(W.key_line.p, 0, ns * MG_KEYS * sizeof(uint32_t), stream()));
+  const int64_t gate = last != 0 ? nl : (int64_t)T.cons_line;
+  hipLaunchKernelGGL(mgf_resolve_kernel, dim3(blocks_of(nl)), dim3(MG_NT), 0, stream(), W.kind.p, W.after.p,
+                     W.spec.p, W.slot.p, W.dslot.p, nl, gate, n_open, n_closed, W.first_line.p, W.peak_begin.p,
+                     W.peak_end.p, W.key_line.p, W.fin.p);
+  ASL_CHECK_LAUNCH();
+  if (n_closed > 0) {
+    hipLaunchKernelGGL(mgf_capacity_kernel, dim3(blocks_of(n_closed)), dim3(MG_NT), 0, stream(), W.peak_begin.p,
+                       W.peak_end.p, n_closed, W.fin.p);
+    ASL_CHECK_LAUNCH();
+  }
+  HIP_TRY(hipMemcpyAsync(&F, W.fin.p, sizeof(F), hipMemcpyDeviceToHost, stream()));
+  ASL_TRY(sync_stream());
+  if (F.long_line != ~0u)
+    return fail(ASL_ERR_CAPACITY, "mgf_measure: line %u of the chunk is longer than %d bytes", (unsigned)F.long_line + 1u,
+                ASL_MGF_MAX_LINE);
+  // at the file's end the numerals of an unclosed last block are reported too, so that the caller can refuse them
+  const uint32_t n_def = last != 0 ? T.defers : F.n_def;
+  counts[ASL_MGF_N_LINES] = nl;
+  counts[ASL_MGF_N_SPECTRA] = n_closed;
+  counts[ASL_MGF_N_PEAKS] = F.n_peaks;
+  counts[ASL_MGF_N_DEFERRED] = n_def;
+  counts[ASL_MGF_CONSUMED] = T.cons_byte;
+  counts[ASL_MGF_CONSUMED_LINES] = T.cons_line;
+  counts[ASL_MGF_OPEN] = n_open > n_closed ? 1 : 0;
+  if (F.err != ~0ull) {
+    counts[ASL_MGF_ERR_KIND] = (int64_t)(F.err & 255u);
+    counts[ASL_MGF_ERR_LINE] = (int64_t)(F.err >> 8);
+  }
+  if (F.cap_spec != ~0u)
+    return fail(ASL_ERR_CAPACITY, "mgf_measure: spectrum %u of the chunk has more than %d peak lines",
+                (unsigned)F.cap_spec + 1u, MG_MAX_PEAKS);
+  W.text = text, W.n = n, W.n_lines = nl, W.n_closed = n_closed, W.n_peaks = F.n_peaks, W.n_def = n_def;
+  W.n_blocks = last != 0 ? n_open : n_closed;
+  return ASL_OK;
+}
+
+extern "C" int asl_mgf_fill(const uint8_t *text, int64_t n, int32_t *offsets, float *mz, float *intensity,
+                            uint8_t *charge, double *precursor_mz, int32_t *precursor_charge,
+                            double *retention_time, int32_t *identifier, int32_t *first_line, int32_t *deferred) {
+  clear_error();
+  MgfWork &W = work();
+  if (W.n < 0 || text != W.text || n != W.n)
+    return fail(ASL_ERR_STATE, "mgf_fill: not the chunk the last successful asl_mgf_measure measured");
+  if (offsets == nullptr) return fail(ASL_ERR_INVALID, "mgf_fill: null offsets");
+  const uint32_t ns = W.n_closed, np = W.n_peaks, nd = W.n_def;
+  if (ns == 0 && nd == 0) {
+    if (is_device_ptr(offsets)) {
+      HIP_TRY(hipMemsetAsync(offsets, 0, sizeof(int32_t), stream()));
+      ASL_TRY(sync_stream());
+    } else {
+      offsets[0] = 0;
+    }
+    return ASL_OK;
+  }
+  if ((np > 0 && (!mz || !intensity)) ||
+      (ns > 0 && (!precursor_mz || !precursor_charge || !retention_time || !identifier || !first_line)) ||
+      (nd > 0 && !deferred))
+    return fail(ASL_ERR_INVALID, "mgf_fill: a null output");
+  ASL_TRY(ensure_device());
+  ProfScope ps("mgf_fill");
+  Out<int32_t> oOff, oZ, oId, oFirst, oRec;
+  Out<float> oMz, oIt;
+  Out<uint8_t> oChg;
+  Out<double> oPmz, oRt;
+  ASL_TRY(oOff.init(offsets, (size_t)ns + 1));
+  ASL_TRY(oMz.init(mz, np));
+  ASL_TRY(oIt.init(intensity, np));
+  ASL_TRY(oChg.init(charge, np));
+  ASL_TRY(oPmz.init(precursor_mz, ns));
+  ASL_TRY(oZ.init(precursor_charge, ns));
+  ASL_TRY(oRt.init(retention_time, ns));
+  ASL_TRY(oId.init(identifier, (size_t)ns * 2));
+  ASL_TRY(oFirst.init(first_line, ns));
+  ASL_TRY(oRec.init(deferred, (size_t)nd * 5));
+  hipLaunchKernelGGL(mgf_fill_lines_kernel, dim3(blocks_of(W.n_lines)), dim3(MG_NT), 0, stream(), text,
+                     W.line_start.p, W.kind.p, W.dflag.p, W.val.p, W.after.p, W.spec.p, W.slot.p, W.dslot.p,
+                     W.n_lines, W.n_blocks, np, nd, oMz.d, oIt.d, oChg.d, oRec.d);
+  ASL_CHECK_LAUNCH();
+  if (ns > 0) {   // (none: the deferred tokens of an unclosed last block alone)
+    hipLaunchKernelGGL(mgf_fill_spectra_kernel, dim3(blocks_of(ns)), dim3(MG_NT), 0, stream(), text, W.line_start.p,
+                       W.dflag.p, W.val.p, W.dslot.p, W.first_line.p, W.peak_begin.p, W.key_line.p, ns, np, nd, oOff.d,
+                       oPmz.d, oZ.d, oRt.d, oId.d, oFirst.d, oRec.d);
+    ASL_CHECK_LAUNCH();
+  } else if (oOff.d != nullptr) {
+    HIP_TRY(hipMemsetAsync(oOff.d, 0, sizeof(int32_t), stream()));
+  }
+  ASL_TRY(oOff.finish());
+  ASL_TRY(oMz.finish());
+  ASL_TRY(oIt.finish());
+  ASL_TRY(oChg.finish());
+  ASL_TRY(oPmz.finish());
+  ASL_TRY(oZ.finish());
+  ASL_TRY(oRt.finish());
+  ASL_TRY(oId.finish());
+  ASL_TRY(oFirst.finish());
+  ASL_TRY(oRec.finish());
+  ASL_TRY(sync_stream());
+  return ASL_OK;
+}
+
+extern "C" int asl_mgf_sort(const int32_t *offsets, float *mz, float *intensity, int32_t n_spectra, int64_t n_peaks,
+                            int64_t *n_sorted) {
+  clear_error();
+  if (n_spectra < 0 || n_peaks < 0) return fail(ASL_ERR_INVALID, "mgf_sort: a negative count");
+  if (n_peaks >= ((int64_t)1 << 31)) return fail(ASL_ERR_CAPACITY, "mgf_sort: n_peaks = %lld, below 2^31",
+                                                 (long long)n_peaks);
+  if (n_sorted != nullptr) *n_sorted = 0;
+  if (n_spectra == 0 || n_peaks < 2) return ASL_OK;
+  if (!offsets || !mz || !intensity) return fail(ASL_ERR_INVALID, "mgf_sort: null offsets / mz / intensity");
+  ASL_TRY(ensure_device());
+  if (!is_device_ptr(offsets) || !is_device_ptr(mz) || !is_device_ptr(intensity))
+    return fail(ASL_ERR_INVALID, "mgf_sort: the pack must be device memory");
+  MgfWork &W = work();
+  ProfScope ps("mgf_sort");
+  ASL_TRY(W.flag.reserve((size_t)n_spectra));
+  ASL_TRY(W.list.reserve((size_t)n_spectra));
+  ASL_TRY(W.small.reserve(2));     // [0]: flagged spectra, [1]: one of them is above the capacity
+  HIP_TRY(hipMemsetAsync(W.flag.p, 0, (size_t)n_spectra * sizeof(uint32_t), stream()));
+  HIP_TRY(hipMemsetAsync(W.small.p, 0, 2 * sizeof(uint32_t), stream()));
+  hipLaunchKernelGGL(mgf_descending_kernel, dim3(blocks_of(n_peaks)), dim3(MG_NT), 0, stream(), offsets, mz,
+                     n_spectra, n_peaks, W.flag.p, W.list.p, W.small.p);
+  ASL_CHECK_LAUNCH();
+  uint32_t h[2] = {0u, 0u};
+  HIP_TRY(hipMemcpyAsync(h, W.small.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
+  ASL_TRY(sync_stream());
+  if (n_sorted != nullptr) *n_sorted = h[0];
+  if (h[0] == 0u) return ASL_OK;   // ascending everywhere: no sort is launched
+  ASL_TRY(W.mz_tmp.reserve((size_t)n_peaks));
+  ASL_TRY(W.it_tmp.reserve((size_t)n_peaks));
+  hipLaunchKernelGGL(mgf_sort_kernel, dim3(h[0]), dim3(MG_NT), 0, stream(), W.list.p, offsets, mz, intensity,
+                     W.mz_tmp.p, W.it_tmp.p, W.small.p + 1);
+  ASL_CHECK_LAUNCH();
+  hipLaunchKernelGGL(mgf_sort_copy_kernel, dim3(h[0]), dim3(MG_NT), 0, stream(), W.list.p, offsets, W.mz_tmp.p,
+                     W.it_tmp.p, mz, intensity);
+  ASL_CHECK_LAUNCH();
+  HIP_TRY(hipMemcpyAsync(h, W.small.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
+  ASL_TRY(sync_stream());
+  if (h[1] != 0u)
+    return fail(ASL_ERR_CAPACITY, "mgf_sort: a descending spectrum has more than %d peaks", MG_MAX_PEAKS);
+  return ASL_OK;
+}

@@ -806,15 +806,24 @@ class SpectralLibrary:
         (``identifier, precursor_mz, precursor_charge`` -- None: tried at 2 and 3, :213-223 --
         ``mz, intensity``, optional ``retention_time, index``), or the packed form of
         ``search_packed``. Queries are preprocessed in batches on the device, low-quality ones
-        dropped (:225-228). Returns the identifications as SSM records with the attributes
+        dropped (:225-228). With ``Config.device_mgf`` a file name ending in ``.mgf`` (any letter case)
+        is read by ``mgf.read_mgf_packed`` -- parsed on the device, the same packed queries -- instead of
+        ``query_reader`` and ``pack_queries``. Returns the identifications as SSM records with the attributes
         ``writer.write_mztab`` consumes (writer.py:129-148)."""
         if isinstance(query, dict):
             return self.search_packed(query, query_meta, library_meta, score_ssms)
         from .library_store import pack_queries
-        if isinstance(query, (str, os.PathLike)):
+        if (self.config.device_mgf and isinstance(query, (str, os.PathLike)) and
+                os.fspath(query).lower().endswith('.mgf')):
+            # the engine's own reader: parsed by kernels, no query_reader, no pack_queries (mgf.py)
+            from .mgf import read_mgf_packed
             logging.info('Process file %s', query)
-            query = self._query_reader(os.fspath(query))
-        query_spectra, qmeta = pack_queries(query, self.config, self.device)
+            query_spectra, qmeta = read_mgf_packed(os.fspath(query), self.config, self.device)
+        else:
+            if isinstance(query, (str, os.PathLike)):
+                logging.info('Process file %s', query)
+                query = self._query_reader(os.fspath(query))
+            query_spectra, qmeta = pack_queries(query, self.config, self.device)
         lmeta = library_meta if library_meta is not None else self.library_meta
         if lmeta is None:
             raise ValueError('search(): no library metadata (library built from a PackedSpectra); '

@@ -938,6 +938,89 @@ int asl_ssm_groups(const double *mass_diff /* [n] */, int64_t n, int64_t min_gro
                    double  *peak_mass  /* [n] or NULL: peak_mass[g] = left bin edge of group g's peak */,
                    int64_t *peak_size  /* [n] or NULL: peak_size[g] = SSMs assigned to g before folding */);
 
+/* ------------------------------------------------------------------ MGF query files
+ * A chunk of an MGF file, resident in device memory, parsed by kernels (csrc/mgf.hip; DESIGN.md 3 "Query files")
+ * into the raw pack asl_process_batch takes. The dialect (what the reference's read_mgf reads through pyteomics'
+ * mgf.MGF, restated; tests/mgf_ref.py is the same statement in Python):
+ *   - Lines end at '\n'; a line is looked at without the blanks around it (space, \t, \n, \v, \f, \r). The last
+ *     line need not end in '\n'.
+ *   - Outside a block a line that is exactly BEGIN IONS opens one; every other line there is ignored.
+ *   - Inside a block: an empty line or one whose first byte is one of # ; ! / is skipped; END IONS closes the
+ *     block; a line with '=' is a parameter (key: the bytes before the first '=', ASCII lower-cased; value: the
+ *     rest, stripped; the last duplicate wins); any other line is a peak line, split at blanks: m/z, intensity,
+ *     further tokens unread.
+ *   - Parameters read: title, else scan (the identifier); pepmass (its first token); charge (the first element of
+ *     the list split at ',' or 'and': digits with the sign before or behind them); rtinseconds.
+ *   - Structural errors: BEGIN IONS inside a block, a peak line of one token.
+ * Numerals are converted on the device only where one correctly rounded fp64 operation is exact (asl_mgf_number
+ * states the rule); every other token is DEFERRED: reported by byte range and destination, for the caller to
+ * convert and store before asl_mgf_sort. Peaks are float32((double) numeral), in file order.
+ * The calls go in this order: asl_mgf_measure(text) -- counts, errors, `consumed` --, asl_mgf_fill(the same text)
+ * into arrays sized by those counts, then, the deferred values stored, asl_mgf_sort on the pack. The library keeps
+ * what measure found until the next measure; a fill for another (text, n) is ASL_ERR_STATE. */
+#define ASL_MGF_TILE 256       /* lines (and 16-byte spans of text) per workgroup of every scan level */
+#define ASL_MGF_MAX_PEAKS 4096 /* peak lines of one spectrum: the limit of asl_process_batch */
+#define ASL_MGF_MAX_LINE 65536 /* bytes of one line, its '\n' included: one thread walks a line */
+/* counts[] of asl_mgf_measure */
+#define ASL_MGF_N_LINES 0
+#define ASL_MGF_N_SPECTRA 1       /* closed blocks */
+#define ASL_MGF_N_PEAKS 2         /* two-token peak lines inside them */
+#define ASL_MGF_N_DEFERRED 3      /* deferred tokens inside them */
+#define ASL_MGF_CONSUMED 4        /* the byte behind the last closed block's END IONS line; 0 without one */
+#define ASL_MGF_CONSUMED_LINES 5  /* the lines before that byte */
+#define ASL_MGF_ERR_KIND 6        /* the first structural error: ASL_MGF_ERR_*, 0 = none */
+#define ASL_MGF_ERR_LINE 7        /* its line, 0-based in the chunk; -1 = none */
+#define ASL_MGF_OPEN 8            /* 1: the chunk ends inside a block (dropped by the caller at the file's end) */
+#define ASL_MGF_COUNTS 9
+#define ASL_MGF_ERR_NESTED 1      /* BEGIN IONS inside a block */
+#define ASL_MGF_ERR_ONE_TOKEN 2   /* a peak line with one token */
+/* destination kinds of a deferred token */
+#define ASL_MGF_DEST_MZ 0         /* index: peak slot */
+#define ASL_MGF_DEST_INTENSITY 1  /* index: peak slot */
+#define ASL_MGF_DEST_PEPMASS 2    /* index: spectrum */
+#define ASL_MGF_DEST_RT 3         /* index: spectrum */
+#define ASL_MGF_DEST_NONE 4       /* a pepmass / rtinseconds line that a later duplicate overrides: unread */
+/* text: [n] bytes in device memory; last != 0: the chunk ends the file. Then the lines of an unclosed last block
+ * are checked too: its structural errors are reported and its deferred tokens listed (counted in
+ * ASL_MGF_N_DEFERRED, with peak slots >= ASL_MGF_N_PEAKS: to be converted and refused or forgotten, never stored).
+ * With last == 0 only lines before `consumed` are reported, the rest comes again with the next chunk, and a final
+ * line that does not end in '\n' is not looked at, since it may be cut anywhere: it neither opens nor closes a block.
+ * n >= 2^31: ASL_ERR_CAPACITY, before any pointer is touched; a line of more than ASL_MGF_MAX_LINE bytes anywhere
+ * in the chunk (a file that is no text), or a closed block of more than ASL_MGF_MAX_PEAKS peak lines:
+ * ASL_ERR_CAPACITY, whatever structural error the chunk also holds; n < 0, last outside {0, 1}, host memory:
+ * ASL_ERR_INVALID. n == 0 is legal and launches nothing. counts: [ASL_MGF_COUNTS], host. */
+int asl_mgf_measure(const uint8_t *text, int64_t n, int32_t last, int64_t *counts);
+/* The measured chunk into caller-allocated arrays, host or device memory: the raw pack (the asl_peaks_t fields;
+ * charge may be NULL, else it is zeroed), and per spectrum the precursor m/z (NaN: no pepmass line, or deferred),
+ * the charge (0: no charge line; -1: outside 1 .. 255 or not a charge), the retention time (NaN: no rtinseconds
+ * line, or deferred), the identifier's (offset, length) in the chunk (length -1: neither title nor scan) and the
+ * block's BEGIN IONS line (0-based in the chunk). deferred: [n_deferred, 5] = (offset, length, destination kind,
+ * destination index, line). An array of no elements may be NULL (with no closed block: all but offsets and,
+ * where an unclosed last block has deferred tokens, deferred). */
+int asl_mgf_fill(const uint8_t *text, int64_t n,
+                 int32_t *offsets            /* [n_spectra + 1] */,
+                 float *mz                   /* [n_peaks] */,
+                 float *intensity            /* [n_peaks] */,
+                 uint8_t *charge             /* [n_peaks] or NULL */,
+                 double *precursor_mz        /* [n_spectra] */,
+                 int32_t *precursor_charge   /* [n_spectra] */,
+                 double *retention_time      /* [n_spectra] */,
+                 int32_t *identifier         /* [n_spectra, 2] */,
+                 int32_t *first_line         /* [n_spectra] */,
+                 int32_t *deferred           /* [n_deferred, 5] */);
+/* Every spectrum of the device-resident pack whose float32 m/z descend anywhere is sorted by m/z, stably (equal
+ * m/z, -0.0 and +0.0 among them, keep file order): numpy.argsort(kind = 'stable') of library_store._sorted_peaks.
+ * Spectra that ascend are not touched and launch nothing. *n_sorted (host, may be NULL): the spectra sorted.
+ * A descending spectrum above ASL_MGF_MAX_PEAKS: ASL_ERR_CAPACITY; host memory: ASL_ERR_INVALID. */
+int asl_mgf_sort(const int32_t *offsets, float *mz, float *intensity, int32_t n_spectra, int64_t n_peaks,
+                 int64_t *n_sorted);
+/* Host only: the numeral s[0 .. n) as the device converts it (csrc/mgf_number.hpp). Returns 0 and writes *out
+ * where one correctly rounded fp64 operation gives float(s): [+-]? (digits [. digits*] | . digits) ([eE] [+-]?
+ * digits)?, whose significand without leading zeros has at most 19 digits and is below 2^53, and whose decimal
+ * exponent, counted from the last digit, lies in -22 .. 22 (a zero significand converts at any exponent). Returns
+ * 1 (deferred, *out untouched) for every other byte string. */
+int asl_mgf_number(const char *s, int32_t n, double *out);
+
 /* ------------------------------------------------------------------ hot path
  * One batch of same-charge queries through
  *   SpectralLibrary._search_batch / _get_library_candidates
