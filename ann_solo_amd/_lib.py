@@ -96,6 +96,7 @@ EXPORTS = [
     'asl_tdc_qvalues',
     'asl_ssm_groups',
     'asl_mgf_measure', 'asl_mgf_fill', 'asl_mgf_sort', 'asl_mgf_number',
+    'asl_mgf_sort_charged', 'asl_sptxt_measure', 'asl_sptxt_fill', 'asl_sptxt_fragment_charge',
 ]
 
 SVM_MAX_DIM = 63          # include/annsolo_mi.h: ASL_SVM_MAX_DIM
@@ -351,6 +352,11 @@ def lib():
             L.asl_mgf_fill.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 10
             L.asl_mgf_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, c_i64p]
             L.asl_mgf_number.argtypes = [C.c_char_p, C.c_int32, c_f64p]
+        if hasattr(L, 'asl_sptxt_measure'):
+            L.asl_mgf_sort_charged.argtypes = [C.c_void_p] * 4 + [C.c_int32, C.c_int64, c_i64p]
+            L.asl_sptxt_measure.argtypes = [C.c_void_p, C.c_int64, C.c_int32, c_i64p]
+            L.asl_sptxt_fill.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7
+            L.asl_sptxt_fragment_charge.argtypes = [C.c_char_p, C.c_int32]
         if hasattr(L, 'asl_index_set_by_residual'):
             L.asl_index_set_by_residual.argtypes = [C.c_void_p, C.c_int32]
             L.asl_index_get_by_residual.argtypes = [C.c_void_p]
@@ -686,6 +692,13 @@ def mgf_number(token):
     out = C.c_double(0.0)
     rc = lib().asl_mgf_number(b, len(b), byref(out))
     return (0, out.value) if rc == 0 else (1, None)
+
+
+def sptxt_fragment_charge(annotation) -> int:
+    """``asl_sptxt_fragment_charge``: the fragment charge the device reads from the annotation field of a .sptxt
+    peak line (bytes or str); 0 = unannotated. Host only: needs no GPU."""
+    b = annotation.encode('utf-8') if isinstance(annotation, str) else bytes(annotation)
+    return int(lib().asl_sptxt_fragment_charge(b, len(b)))
 
 
 def ssm_groups(mass_diff, min_group_size: int, profile: bool = False):

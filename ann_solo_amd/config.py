@@ -7,7 +7,7 @@
 ``precursor_window_open``, ``fragment_tolerance_unit``, ``score_stats``, ``device_decoys``,
 ``decoy_tolerance_unit``, ``localize_modifications``, ``device_fdr``, ``device_forest``,
 ``forest_trees``, ``device_qvalues``, ``device_groups``, ``chimeric_search``, ``chimeric_window``,
-``device_mgf``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``device_mgf``, ``device_library``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -157,6 +157,12 @@ class Config:
     # same packed queries either way. Other extensions keep the injected or the reference's reader. Off: nothing
     # new is launched
     device_mgf: bool = False
+    # ``SpectralLibrary(filename)`` reads a library whose name ends in ``.sptxt`` (any letter case) with the engine's
+    # own reader (sptxt.py, csrc/sptxt.hip; DESIGN.md 3 "Library files") in place of ``reader_factory``: the text is
+    # parsed by kernels, the raw peaks go to the preprocessing where they lie, and the packed store is what
+    # ``build_library_store`` makes of the same file. Other extensions keep the injected or the reference's reader.
+    # Off: nothing new is launched and every result, hash and cached file name is what it is without the switch
+    device_library: bool = False
 
     MAX_PEAKS = 256     # peaks per spectrum the preprocessing / rescoring kernels hold (csrc/process.hip)
     MAX_TOPK = 2048      # largest nprobe / single-pass k of the LDS top-k (csrc/ivf_kernels.hpp: TK_MAX_K)
@@ -255,6 +261,7 @@ class Config:
         if self.chimeric_search and self.num_gpus and int(self.num_gpus) > 1:
             raise ValueError('chimeric_search does not run on a sharded index (num_gpus > 1)')
         self.device_mgf = bool(self.device_mgf)
+        self.device_library = bool(self.device_library)
         if self.precursor_window_open is not None:
             try:
                 lo, hi = (float(v) for v in self.precursor_window_open)
@@ -451,3 +458,9 @@ def add_arguments(parser) -> None:
                              "numerals are parsed by kernels and the peaks never become Python objects; the same "
                              'queries as the host reader gives; malformed blocks raise an error naming the line or '
                              'spectrum; other query formats are read as before (default: off)')
+    parser.add_argument('--device_library', action='store_true', default=d.device_library,
+                        help='read a spectral library whose name ends in .sptxt with the GPU reader: records, '
+                             'precursors, peaks and annotations are parsed by kernels, no reference package is '
+                             'needed and no .spcfg / .hdf5 is written; the same packed store as the host reader '
+                             'gives; malformed records raise an error naming the line or record; other library '
+                             'formats are read as before (default: off)')

@@ -2,7 +2,8 @@
 // converter on the host (asl_mgf_number). gfx950 only. DESIGN.md 3 "Query files"; the dialect is stated in
 // include/annsolo_mi.h and restated in tests/mgf_ref.py.
 //
-//   starts   count the line starts (MG_SPAN bytes a thread), scan the counts, write line_start[]
+//   starts   count the line starts (MG_SPAN bytes a thread), scan the counts, write line_start[] (text_scan.hpp,
+//            with the scan kernels: shared with sptxt.hip)
 //   lines    one thread per line: strip, classify (BEGIN, END, the five parameters, other parameter, peak, skip)
 //            and convert its numerals (mgf_number.hpp); what the converter defers is flagged, never guessed
 //   state    a scan that composes the lines' maps of the two states {outside, inside a block}: BEGIN -> inside,
@@ -16,7 +17,8 @@
 //   fill     peaks scattered to their slots, the deferred tokens' byte ranges and destinations, the per-spectrum
 //            columns
 //   sort     one adjacent compare per peak flags the spectra that descend anywhere; those alone are sorted, one
-//            workgroup each, by a bitonic network over at most 4096 unique keys (m/z bits, ordinal) in LDS
+//            workgroup each, by a bitonic network over at most 4096 unique keys (m/z bits, ordinal) in LDS;
+//            asl_mgf_sort_charged moves the fragment charges of a library's peaks with them, a third payload
 //
 // Every scan is reduce -> scan of the block partials (recursively) -> apply, as separate launches on the library's
 // stream: no kernel waits on another workgroup. Integer atomics only, and none whose arrival order reaches the
@@ -26,13 +28,11 @@
 
 #include "common.hpp"
 #include "mgf_number.hpp"
+#include "text_scan.hpp"
 
 namespace asl {
 
-constexpr int MG_NT = ASL_MGF_TILE;            // threads of every kernel here = elements per block of a scan level
-constexpr int MG_SPAN = 16;                    // bytes per thread of the line-start passes
 constexpr int MG_MAX_PEAKS = ASL_MGF_MAX_PEAKS;
-static_assert(MG_NT == 256, "four waves: mg_block_scan's wave totals");
 static_assert((MG_MAX_PEAKS & (MG_MAX_PEAKS - 1)) == 0, "the bitonic network pads to a power of two");
 
 enum : uint8_t {   // what a line is, whatever surrounds it
@@ -51,11 +51,6 @@ struct MgFinal {    // written by the resolve and check kernels
 };
 
 // ---------------------------------------------------------------------------------------------- scans
-struct MgSum {
-  using T = uint32_t;
-  __device__ static T identity() { return 0u; }
-  __device__ static T op(T a, T b) { return a + b; }
-};
 // A line as a map of the block state: bit x of the value is the state after the line when the state before is x.
 struct MgState {
   using T = uint32_t;
@@ -72,133 +67,7 @@ struct MgCount {
   }
 };
 
-template <class T>
-__device__ __forceinline__ T mg_shfl_up(T v, int delta) {
-  static_assert(sizeof(T) % 4 == 0, "whole words");
-  uint32_t w[sizeof(T) / 4];
-  __builtin_memcpy(w, &v, sizeof(T));
-#pragma unroll
-  for (size_t k = 0; k < sizeof(T) / 4; ++k) w[k] = (uint32_t)__shfl_up((int)w[k], delta, 64);
-  __builtin_memcpy(&v, w, sizeof(T));
-  return v;
-}
-
-// inclusive scan over the block's MG_NT values in thread order; *total: the block's sum, in every thread
-template <class Op>
-__device__ __forceinline__ typename Op::T mg_block_scan(typename Op::T x, typename Op::T *total) {
-  using T = typename Op::T;
-  __shared__ T wave_tot[MG_NT / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T o = mg_shfl_up(x, d);
-    if (lane >= d) x = Op::op(o, x);
-  }
-  if (lane == 63) wave_tot[wave] = x;
-  __syncthreads();
-  T pre = Op::identity(), all = Op::identity();
-#pragma unroll
-  for (int w = 0; w < MG_NT / 64; ++w) {
-    if (w < wave) pre = Op::op(pre, wave_tot[w]);
-    all = Op::op(all, wave_tot[w]);
-  }
-  *total = all;
-  return Op::op(pre, x);
-}
-
-// A view names a scan's operator (Op), reads element i (load) and takes its inclusive result (store).
-template <class V>
-__global__ __launch_bounds__(MG_NT) void mgf_scan_reduce_kernel(V view, int64_t n, typename V::Op::T *partial) {
-  using Op = typename V::Op;
-  const int64_t i = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
-  typename Op::T total;
-  mg_block_scan<Op>(i < n ? view.load(i) : Op::identity(), &total);
-  if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-// partial: the INCLUSIVE scan of the blocks' sums (block b starts from partial[b - 1]), or nullptr for one block
-template <class V>
-__global__ __launch_bounds__(MG_NT) void mgf_scan_apply_kernel(V view, int64_t n, const typename V::Op::T *partial) {
-  using Op = typename V::Op;
-  const int64_t i = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
-  const typename Op::T own = i < n ? view.load(i) : Op::identity();
-  typename Op::T total;
-  typename Op::T incl = mg_block_scan<Op>(own, &total);
-  if (partial != nullptr && blockIdx.x > 0) incl = Op::op(partial[blockIdx.x - 1], incl);
-  if (i < n) view.store(i, incl, own);
-}
-
-template <class O>
-struct MgPlainView {   // an array scanned in place (the upper levels)
-  using Op = O;
-  typename O::T *a;
-  __device__ typename O::T load(int64_t i) const { return a[i]; }
-  __device__ void store(int64_t i, typename O::T incl, typename O::T) const { a[i] = incl; }
-};
-
-// ---------------------------------------------------------------------------------------------- line starts
-// Bit k of the result: byte 16 e + k is a '\n' that is followed by another byte, i.e. byte 16 e + k + 1 starts a
-// line. vec: t is 16-byte aligned.
-__device__ __forceinline__ uint32_t mg_newlines(const uint8_t *__restrict__ t, int64_t n, int64_t e, bool vec) {
-  const int64_t j0 = e * MG_SPAN;
-  uint32_t m = 0u;
-  if (vec && j0 + MG_SPAN <= n) {
-    const uint4 v = *reinterpret_cast<const uint4 *>(t + j0);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-        if (((w[q] >> (8 * b)) & 255u) == (uint32_t)'\n') m |= 1u << (4 * q + b);
-  } else {
-    for (int k = 0; k < MG_SPAN; ++k)
-      if (j0 + k < n && t[j0 + k] == (uint8_t)'\n') m |= 1u << k;
-  }
-  const int64_t last = n - 1 - j0;   // (the chunk's last byte starts nothing behind it)
-  if (last >= 0 && last < MG_SPAN) m &= ~(1u << last);
-  return m;
-}
-__device__ __forceinline__ uint32_t mg_starts(const uint8_t *__restrict__ t, int64_t n, int64_t e, bool vec) {
-  return (uint32_t)__popc(mg_newlines(t, n, e, vec)) + (e == 0 && n > 0 ? 1u : 0u);
-}
-
-__global__ __launch_bounds__(MG_NT) void mgf_count_lines_kernel(const uint8_t *__restrict__ t, int64_t n, int64_t ne,
-                                                                int vec, unsigned long long *__restrict__ total) {
-  const int64_t e = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
-  uint32_t tot;
-  mg_block_scan<MgSum>(e < ne ? mg_starts(t, n, e, vec != 0) : 0u, &tot);
-  if (threadIdx.x == 0 && tot != 0u) atomicAdd(total, (unsigned long long)tot);   // (an integer count)
-}
-
-struct LineStartView {   // element e: the line starts its MG_SPAN bytes produce, in file order
-  using Op = MgSum;
-  const uint8_t *t;
-  int64_t n;
-  int vec;
-  uint32_t *line_start;   // [n_lines + 1]
-  uint32_t n_lines;
-  __device__ uint32_t load(int64_t e) const { return mg_starts(t, n, e, vec != 0); }
-  __device__ void store(int64_t e, uint32_t incl, uint32_t own) const {
-    uint32_t o = incl - own;
-    if (e == 0 && n > 0 && o < n_lines) line_start[o++] = 0u;
-    uint32_t m = mg_newlines(t, n, e, vec != 0);
-    while (m != 0u) {
-      const int k = __ffs((int)m) - 1;
-      m &= m - 1u;
-      if (o < n_lines) line_start[o++] = (uint32_t)(e * MG_SPAN + k + 1);
-    }
-  }
-};
-
 // ---------------------------------------------------------------------------------------------- one line
-__device__ __forceinline__ bool mg_ws(uint8_t c) { return c == 32 || (c >= 9 && c <= 13); }   // bytes.strip / split
-
-// [p, q): line L without the blanks around it (a == b gives p == q)
-__device__ __forceinline__ void mg_strip(const uint8_t *__restrict__ t, uint32_t a, uint32_t b, uint32_t *p,
-                                         uint32_t *q) {
-  while (b > a && mg_ws(t[b - 1])) --b;
-  while (a < b && mg_ws(t[a])) ++a;
-  *p = a, *q = b;
-}
 __device__ __forceinline__ bool mg_is(const uint8_t *__restrict__ t, uint32_t p, uint32_t len, const char *lit,
                                       uint32_t lit_len, bool fold) {
   if (len != lit_len) return false;
@@ -512,7 +381,9 @@ __global__ __launch_bounds__(MG_NT) void mgf_sort_kernel(const uint32_t *__restr
                                                          const int32_t *__restrict__ offsets,
                                                          const float *__restrict__ mz,
                                                          const float *__restrict__ intensity,
+                                                         const uint8_t *__restrict__ charge,
                                                          float *__restrict__ mz_tmp, float *__restrict__ it_tmp,
+                                                         uint8_t *__restrict__ chg_tmp,
                                                          uint32_t *__restrict__ too_long) {
   __shared__ uint64_t key[MG_MAX_PEAKS];
   const uint32_t s = list[blockIdx.x];
@@ -540,18 +411,24 @@ __global__ __launch_bounds__(MG_NT) void mgf_sort_kernel(const uint32_t *__restr
   for (int i = threadIdx.x; i < cnt; i += MG_NT) {
     const int src = (int)(uint32_t)key[i];
     mz_tmp[a + i] = mz[a + src], it_tmp[a + i] = intensity[a + src];
+    if (charge != nullptr) chg_tmp[a + i] = charge[a + src];
   }
 }
 
 __global__ __launch_bounds__(MG_NT) void mgf_sort_copy_kernel(const uint32_t *__restrict__ list,
                                                               const int32_t *__restrict__ offsets,
                                                               const float *__restrict__ mz_tmp,
-                                                              const float *__restrict__ it_tmp, float *__restrict__ mz,
-                                                              float *__restrict__ intensity) {
+                                                              const float *__restrict__ it_tmp,
+                                                              const uint8_t *__restrict__ chg_tmp,
+                                                              float *__restrict__ mz, float *__restrict__ intensity,
+                                                              uint8_t *__restrict__ charge) {
   const uint32_t s = list[blockIdx.x];
   const int a = offsets[s], cnt = offsets[s + 1] - a;
   if (cnt > MG_MAX_PEAKS) return;
-  for (int i = threadIdx.x; i < cnt; i += MG_NT) mz[a + i] = mz_tmp[a + i], intensity[a + i] = it_tmp[a + i];
+  for (int i = threadIdx.x; i < cnt; i += MG_NT) {
+    mz[a + i] = mz_tmp[a + i], intensity[a + i] = it_tmp[a + i];
+    if (charge != nullptr) charge[a + i] = chg_tmp[a + i];
+  }
 }
 
 namespace {
@@ -565,6 +442,7 @@ struct MgfWork {
   DevBuf<MgTotals> partial, totals;
   DevBuf<MgFinal> fin;
   DevBuf<float> mz_tmp, it_tmp;
+  DevBuf<uint8_t> chg_tmp;
   // the measured chunk
   const void *text = nullptr;
   int64_t n = -1, n_lines = 0;
@@ -575,49 +453,6 @@ MgfWork &work() {
   static MgfWork w;
   return w;
 }
-
-int64_t partial_slots(int64_t n) {   // block partials of all levels of a scan over n elements
-  int64_t total = 0;
-  while (n > MG_NT) {
-    n = cdiv(n, MG_NT);
-    total += n;
-  }
-  return total;
-}
-
-template <class O>
-int scan_in_place(typename O::T *a, int64_t n, typename O::T *scratch) {   // inclusive, the upper levels
-  MgPlainView<O> v{a};
-  const int64_t nb = cdiv(n, MG_NT);
-  if (nb > 1) {
-    hipLaunchKernelGGL(mgf_scan_reduce_kernel<MgPlainView<O>>, dim3((unsigned)nb), dim3(MG_NT), 0, stream(), v, n,
-                       scratch);
-    ASL_CHECK_LAUNCH();
-    ASL_TRY(scan_in_place<O>(scratch, nb, scratch + nb));
-  }
-  hipLaunchKernelGGL(mgf_scan_apply_kernel<MgPlainView<O>>, dim3((unsigned)nb), dim3(MG_NT), 0, stream(), v, n,
-                     nb > 1 ? scratch : nullptr);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-template <class V>
-int scan_view(const V &v, int64_t n, void *scratch_bytes) {
-  using T = typename V::Op::T;
-  T *scratch = static_cast<T *>(scratch_bytes);
-  const int64_t nb = cdiv(n, MG_NT);
-  if (nb > 1) {
-    hipLaunchKernelGGL(mgf_scan_reduce_kernel<V>, dim3((unsigned)nb), dim3(MG_NT), 0, stream(), v, n, scratch);
-    ASL_CHECK_LAUNCH();
-    ASL_TRY(scan_in_place<typename V::Op>(scratch, nb, scratch + nb));
-  }
-  hipLaunchKernelGGL(mgf_scan_apply_kernel<V>, dim3((unsigned)nb), dim3(MG_NT), 0, stream(), v, n,
-                     nb > 1 ? scratch : nullptr);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-inline unsigned blocks_of(int64_t n) { return (unsigned)std::max<int64_t>(cdiv(n, MG_NT), 1); }
 
 }  // namespace
 }  // namespace asl
@@ -647,23 +482,8 @@ extern "C" int asl_mgf_measure(const uint8_t *text, int64_t n, int32_t last, int
   ASL_TRY(ensure_device());
   if (!is_device_ptr(text)) return fail(ASL_ERR_INVALID, "mgf_measure: text must be device memory");
   ProfScope ps("mgf_measure");
-  const int vec = (reinterpret_cast<uintptr_t>(text) & 15u) == 0 ? 1 : 0;
-  const int64_t ne = cdiv(n, MG_SPAN);
-  // line starts
-  ASL_TRY(W.count.reserve(1));
-  HIP_TRY(hipMemsetAsync(W.count.p, 0, sizeof(unsigned long long), stream()));
-  hipLaunchKernelGGL(mgf_count_lines_kernel, dim3(blocks_of(ne)), dim3(MG_NT), 0, stream(), text, n, ne, vec,
-                     W.count.p);
-  ASL_CHECK_LAUNCH();
-  unsigned long long h_lines = 0;
-  HIP_TRY(hipMemcpyAsync(&h_lines, W.count.p, sizeof(h_lines), hipMemcpyDeviceToHost, stream()));
-  ASL_TRY(sync_stream());
-  const int64_t nl = (int64_t)h_lines;   // >= 1
-  ASL_TRY(W.partial.reserve((size_t)(partial_slots(std::max(ne, nl)) + 1)));
-  ASL_TRY(W.line_start.reserve((size_t)nl + 1));
-  ASL_TRY(scan_view(LineStartView{text, n, vec, W.line_start.p, (uint32_t)nl}, ne, W.partial.p));
-  const uint32_t end = (uint32_t)n;
-  HIP_TRY(hipMemcpyAsync(W.line_start.p + nl, &end, sizeof(end), hipMemcpyHostToDevice, stream()));
+  int64_t nl = 0;   // >= 1
+  ASL_TRY(line_starts(text, n, W.count, W.partial, W.line_start, &nl));
   // lines, block state, counts
   ASL_TRY(W.kind.reserve((size_t)nl));
   ASL_TRY(W.dflag.reserve((size_t)nl));
@@ -796,6 +616,11 @@ extern "C" int asl_mgf_fill(const uint8_t *text, int64_t n, int32_t *offsets, fl
 
 extern "C" int asl_mgf_sort(const int32_t *offsets, float *mz, float *intensity, int32_t n_spectra, int64_t n_peaks,
                             int64_t *n_sorted) {
+  return asl_mgf_sort_charged(offsets, mz, intensity, nullptr, n_spectra, n_peaks, n_sorted);
+}
+
+extern "C" int asl_mgf_sort_charged(const int32_t *offsets, float *mz, float *intensity, uint8_t *charge,
+                                    int32_t n_spectra, int64_t n_peaks, int64_t *n_sorted) {
   clear_error();
   if (n_spectra < 0 || n_peaks < 0) return fail(ASL_ERR_INVALID, "mgf_sort: a negative count");
   if (n_peaks >= ((int64_t)1 << 31)) return fail(ASL_ERR_CAPACITY, "mgf_sort: n_peaks = %lld, below 2^31",
@@ -806,6 +631,8 @@ extern "C" int asl_mgf_sort(const int32_t *offsets, float *mz, float *intensity,
   ASL_TRY(ensure_device());
   if (!is_device_ptr(offsets) || !is_device_ptr(mz) || !is_device_ptr(intensity))
     return fail(ASL_ERR_INVALID, "mgf_sort: the pack must be device memory");
+  if (charge != nullptr && !is_device_ptr(charge))
+    return fail(ASL_ERR_INVALID, "mgf_sort: the charges must be device memory");
   MgfWork &W = work();
   ProfScope ps("mgf_sort");
   ASL_TRY(W.flag.reserve((size_t)n_spectra));
@@ -823,11 +650,12 @@ extern "C" int asl_mgf_sort(const int32_t *offsets, float *mz, float *intensity,
   if (h[0] == 0u) return ASL_OK;   // ascending everywhere: no sort is launched
   ASL_TRY(W.mz_tmp.reserve((size_t)n_peaks));
   ASL_TRY(W.it_tmp.reserve((size_t)n_peaks));
+  if (charge != nullptr) ASL_TRY(W.chg_tmp.reserve((size_t)n_peaks));
   hipLaunchKernelGGL(mgf_sort_kernel, dim3(h[0]), dim3(MG_NT), 0, stream(), W.list.p, offsets, mz, intensity,
-                     W.mz_tmp.p, W.it_tmp.p, W.small.p + 1);
+                     charge, W.mz_tmp.p, W.it_tmp.p, W.chg_tmp.p, W.small.p + 1);
   ASL_CHECK_LAUNCH();
   hipLaunchKernelGGL(mgf_sort_copy_kernel, dim3(h[0]), dim3(MG_NT), 0, stream(), W.list.p, offsets, W.mz_tmp.p,
-                     W.it_tmp.p, mz, intensity);
+                     W.it_tmp.p, W.chg_tmp.p, mz, intensity, charge);
   ASL_CHECK_LAUNCH();
   HIP_TRY(hipMemcpyAsync(h, W.small.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
   ASL_TRY(sync_stream());

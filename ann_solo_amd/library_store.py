@@ -22,8 +22,10 @@ optionally ``annotation`` (objects with ``.charge`` or None) / ``charge``, ``pep
 ``is_decoy``, ``retention_time``, ``index`` -- the attributes of the reference's
 ``MsmsSpectrum`` subclass that the hot path and the writer consume.
 
-No file parsing happens here: ``.splib/.sptxt/.mgf`` parsing stays with the reference's reader
-(out of scope).
+No file parsing happens here. ``.sptxt`` libraries have a reader of this package's own (``sptxt.py``,
+``Config.device_library``), which builds the same ``LibraryStore`` from the file's text on the device and
+shares ``store_hash`` / ``save_library_store`` / ``load_library_store`` with this module; ``.splib``, library-side
+``.mgf`` and ``.fasta`` parsing stays with the reference's reader (DESIGN.md 3 "Library files").
 """
 import hashlib
 import json
@@ -54,6 +56,9 @@ def store_hash(config, hyperparameter_hash: str, annotation_alignment: str) -> s
     d = {'hyper': hyperparameter_hash, 'process': opts, 'annotation': annotation_alignment, 'layout': 2}
     if config.device_decoys:        # (off: the key, and so every cached file name, as before the option)
         d['decoys'] = decoy_options(config)
+    if config.device_library:       # (off: likewise)
+        from .sptxt import READER_VERSION
+        d['reader'] = {'sptxt': READER_VERSION}
     return hashlib.sha1(json.dumps(d, sort_keys=True).encode('utf-8')).hexdigest()
 
 
@@ -221,6 +226,7 @@ class LibraryStore:
     valid: np.ndarray                       # bool [n]: is_valid after process_spectrum
     ranges: Dict[int, Tuple[int, int]]      # charge -> [first row, last row) of ``spectra``
     meta: Dict[int, List[dict]]             # charge -> per-row identifier / peptide / precursor_mz / is_decoy
+    source: Optional[dict] = None           # size and mtime_ns of the library file (the device reader's stores)
 
 
 def build_library_store(reader, config, device, annotation_alignment: str = 'peaks',
@@ -289,6 +295,8 @@ def save_library_store(store: LibraryStore, path: str, key: str) -> None:
              'ranges': {str(z): list(r) for z, r in store.ranges.items()},
              'peptide': [m['peptide'] for z in store.ranges for m in store.meta[z]],
              'is_decoy': [int(m['is_decoy']) for z in store.ranges for m in store.meta[z]]}
+    if store.source is not None:
+        extra['source'] = store.source
     store.spectra.save(path, key, extra=extra)
 
 
@@ -302,7 +310,7 @@ def load_library_store(path: str, key: str) -> LibraryStore:
     flat = [dict(identifier=pack.identifiers[i], peptide=extra['peptide'][i],
                  precursor_mz=float(pmz[i]), is_decoy=bool(extra['is_decoy'][i]))
             for i in range(n)]
-    return LibraryStore(pack, valid, ranges, {z: flat[a:b] for z, (a, b) in ranges.items()})
+    return LibraryStore(pack, valid, ranges, {z: flat[a:b] for z, (a, b) in ranges.items()}, extra.get('source'))
 
 
 def load_or_build_library_store(reader, config, device, path: Optional[str], key: str,

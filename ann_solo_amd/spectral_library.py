@@ -134,7 +134,8 @@ class SpectralLibrary:
           (spectral_library.py:46-116): ``reader_factory(filename, hyper_hash)`` (default: the
           reference's ``SpectralLibraryReader``) opens it, the packed store and the ANN indexes
           are cached next to it as ``<library>_<hash7>.spstore`` / ``<library>_<hash7>_<charge>
-          .idxmi``;
+          .idxmi``; with ``Config.device_library`` a name ending in ``.sptxt`` (any letter case) is read by
+          the engine's own reader (``sptxt.read_library``) and ``reader_factory`` is not called;
         * a reader object with the reference reader's surface (``spec_info``,
           ``read_all_spectra()``, optional ``is_recreated`` / ``get_version()`` / ``close()``);
         * a ``PackedSpectra`` of already processed library spectra (``identifiers``: library
@@ -194,14 +195,20 @@ class SpectralLibrary:
             self._init_from_packed(library, identifiers, valid)
         else:
             from . import library_store as ls
+            own_reader = False
             if isinstance(library, (str, os.PathLike)):
                 filename = os.fspath(library)
-                self._library_reader = (reader_factory or _reference_reader_factory)(
-                    filename, self._get_hyperparameter_hash())
+                own_reader = cfg.device_library and filename.lower().endswith('.sptxt')
+                if own_reader and annotation_alignment != 'peaks':
+                    raise ValueError(f"annotation_alignment = {annotation_alignment!r} with device_library: the "
+                                     "device reader keeps every charge with its peak ('peaks')")
+                if not own_reader:
+                    self._library_reader = (reader_factory or _reference_reader_factory)(
+                        filename, self._get_hyperparameter_hash())
             else:
                 self._library_reader = library
                 filename = getattr(library, '_filename', None) or cfg.spectral_library_filename
-            if cfg.device_decoys:       # decoy row, target row for every spectrum the reader lists
+            if cfg.device_decoys and not own_reader:    # decoy row, target row for every spectrum the reader lists
                 self._library_reader = ls.DecoyReader(self._library_reader, cfg, self.device)
             if filename:
                 stem = os.path.splitext(filename)[0]
@@ -209,14 +216,20 @@ class SpectralLibrary:
                 self._basename = basename or os.path.basename(stem)
             else:
                 self._index_dir, self._basename = index_dir, basename or 'library'
-            if getattr(self._library_reader, 'is_recreated', False):
-                logging.warning('ANN indexes were created using non-compatible settings')
-                verify_file_existence = False
             key = ls.store_hash(cfg, self._get_hyperparameter_hash(), annotation_alignment)
             path = None if self._index_dir is None else os.path.join(
                 self._index_dir, f'{self._basename}_{key[:7]}{ls.STORE_EXT}')
-            store = ls.load_or_build_library_store(self._library_reader, cfg, self.device, path,
-                                                   key, annotation_alignment)
+            if own_reader:              # the engine's own reader (sptxt.py): no reader_factory, no objects
+                from . import sptxt
+                self._library_reader = sptxt.read_library(filename, cfg, self.device, path, key)
+            if getattr(self._library_reader, 'is_recreated', False):
+                logging.warning('ANN indexes were created using non-compatible settings')
+                verify_file_existence = False
+            if own_reader:
+                store = self._library_reader.store
+            else:
+                store = ls.load_or_build_library_store(self._library_reader, cfg, self.device, path,
+                                                       key, annotation_alignment)
             self.library_meta = store.meta
             for z, (a, b) in store.ranges.items():
                 rows = torch.arange(a, b)

@@ -1020,6 +1020,88 @@ int asl_mgf_sort(const int32_t *offsets, float *mz, float *intensity, int32_t n_
  * exponent, counted from the last digit, lies in -22 .. 22 (a zero significand converts at any exponent). Returns
  * 1 (deferred, *out untouched) for every other byte string. */
 int asl_mgf_number(const char *s, int32_t n, double *out);
+/* asl_mgf_sort with the per-peak fragment charges as a third payload: charge [n_peaks], device memory, travels with
+ * its peak. charge == NULL is asl_mgf_sort. */
+int asl_mgf_sort_charged(const int32_t *offsets, float *mz, float *intensity, uint8_t *charge, int32_t n_spectra,
+                         int64_t n_peaks, int64_t *n_sorted);
+
+/* ------------------------------------------------------------------ Library files (.sptxt)
+ * A chunk of a SpectraST .sptxt library, resident in device memory, parsed by kernels (csrc/sptxt.hip; DESIGN.md 3
+ * "Library files") into the raw pack asl_process_batch takes, with the per-peak fragment charges. The dialect (the
+ * well-formed subset of what the reference's sptxt reader accepts, restated; tests/sptxt_ref.py is the same
+ * statement in Python):
+ *   - Lines end at '\n'; a line is looked at without the blanks around it (space, \t, \n, \v, \f, \r), peak lines
+ *     excepted. The last line need not end in '\n'. Keys are matched in any letter case.
+ *   - A line whose head is `Name:` starts a record, which runs to the next such line or the end of the file; the
+ *     lines before the first record are ignored. A `Name:` that is not preceded by a letter anywhere else in any
+ *     line is refused (ERR_SECOND_NAME).
+ *   - The identifier of a record is its ordinal in the file, from 1, as a decimal string.
+ *   - Name line: the peptide is the text behind the last space before the first '/' (upper-case letters only), the
+ *     precursor charge the text between that '/' and the next one or the line's end, stripped: digits only, 1 .. 255.
+ *   - Metadata: the lines from the Name line to the `Num Peaks:` / `NumPeaks:` line (key, at most one blank, digits,
+ *     nothing else: ERR_NUMPEAKS; the number is not read). Precursor m/z: the first line whose head is
+ *     `PrecursorMZ:` (at most one blank, the numeral, nothing else: ERR_PRECURSOR), else the first `Parent=` of the
+ *     first line that holds one (at most one blank, then the run of digits and points). The numeral is
+ *     digits [. digits]. A `PrecursorMZ:` or `Num Peaks:` key that stands inside a metadata line, not at its
+ *     head, is refused (ERR_STRAY_KEY): the reference's expressions would read it. is_decoy: `decoy` occurs in the Name line or in a metadata line that is no PrecursorMZ
+ *     line. Modifications: the first `Mods=` of the first such line that holds one, up to the first blank.
+ *   - Peaks: the lines behind the Num Peaks line (a second one in a record: ERR_SECOND_NUMPEAKS). A peak line is
+ *     cut at the first '#', else loses its '\r' '\n' end; one that is then blank is skipped; the others are split at
+ *     tabs: m/z and intensity (numerals, stripped), annotation (as it stands), further fields unread; fewer than three
+ *     fields: ERR_FEW_FIELDS. Peaks are float32((double) numeral), in file order, deferred as in the MGF reader.
+ *   - Fragment charge of a peak: asl_sptxt_fragment_charge of its annotation field.
+ * Everything else a record must satisfy (a peptide, a charge, a precursor, one peak or more, well-formed Mods=) is
+ * checked by the caller from the columns asl_sptxt_fill returns.
+ * The calls go as for the MGF reader: asl_sptxt_measure(text), asl_sptxt_fill(the same text), the deferred values
+ * stored, asl_mgf_sort_charged on the pack. A record is closed by the next Name line, or by the end of the chunk when
+ * last != 0; with last == 0 the lines from the last Name line on are neither reported nor checked: they come again. */
+/* counts[] of asl_sptxt_measure */
+#define ASL_SPTXT_N_LINES 0
+#define ASL_SPTXT_N_RECORDS 1       /* closed records */
+#define ASL_SPTXT_N_PEAKS 2         /* peak lines inside them */
+#define ASL_SPTXT_N_DEFERRED 3      /* deferred tokens inside them */
+#define ASL_SPTXT_CONSUMED 4        /* the byte at which the first record that is not closed starts; n with last != 0;
+                                       0 without a Name line */
+#define ASL_SPTXT_CONSUMED_LINES 5  /* the lines checked: those before that byte; all of them without a Name line */
+#define ASL_SPTXT_ERR_KIND 6        /* the first structural error: ASL_SPTXT_ERR_*, 0 = none */
+#define ASL_SPTXT_ERR_LINE 7        /* its line, 0-based in the chunk; -1 = none */
+#define ASL_SPTXT_OPEN 8            /* 1: the chunk ends inside a record */
+#define ASL_SPTXT_COUNTS 9
+#define ASL_SPTXT_ERR_SECOND_NAME 1
+#define ASL_SPTXT_ERR_SECOND_NUMPEAKS 2
+#define ASL_SPTXT_ERR_NUMPEAKS 3
+#define ASL_SPTXT_ERR_FEW_FIELDS 4
+#define ASL_SPTXT_ERR_PRECURSOR 5
+#define ASL_SPTXT_ERR_STRAY_KEY 6
+/* destination kinds of a deferred token */
+#define ASL_SPTXT_DEST_MZ 0         /* index: peak slot */
+#define ASL_SPTXT_DEST_INTENSITY 1  /* index: peak slot */
+#define ASL_SPTXT_DEST_PRECURSOR 2  /* index: record */
+#define ASL_SPTXT_DEST_NONE 3       /* a precursor numeral on a line that does not decide the precursor: unread */
+/* info[] of a record */
+#define ASL_SPTXT_INFO 8            /* precursor charge (-1: not 1 .. 255, or no '/'), precursor status, is_decoy,
+                                       peptide offset and length (-1: no '/'), Mods= offset and length (-1: none; the
+                                       range starts at the key), Name line (0-based in the chunk) */
+#define ASL_SPTXT_PRECURSOR_OK 0      /* converted, or deferred (then precursor_mz is NaN and the token is listed) */
+#define ASL_SPTXT_PRECURSOR_MISSING 1 /* neither a PrecursorMZ line nor a Parent= */
+#define ASL_SPTXT_PRECURSOR_BAD 2     /* the Parent= numeral is not digits [. digits] */
+/* As asl_mgf_measure: n >= 2^31, a line above ASL_MGF_MAX_LINE bytes or a closed record above ASL_MGF_MAX_PEAKS peak
+ * lines: ASL_ERR_CAPACITY; n == 0 is legal and launches nothing. counts: [ASL_SPTXT_COUNTS], host. */
+int asl_sptxt_measure(const uint8_t *text, int64_t n, int32_t last, int64_t *counts);
+/* The measured chunk into caller-allocated arrays, host or device memory. precursor_mz: NaN where missing, bad or
+ * deferred. deferred: [n_deferred, 5] = (offset, length, destination kind, destination index, line). */
+int asl_sptxt_fill(const uint8_t *text, int64_t n,
+                   int32_t *offsets            /* [n_records + 1] */,
+                   float *mz                   /* [n_peaks] */,
+                   float *intensity            /* [n_peaks] */,
+                   uint8_t *charge             /* [n_peaks] */,
+                   double *precursor_mz        /* [n_records] */,
+                   int32_t *info               /* [n_records, ASL_SPTXT_INFO] */,
+                   int32_t *deferred           /* [n_deferred, 5] */);
+/* Host only: the fragment charge of the annotation s[0 .. n) as the device reads it (csrc/sptxt_annot.hpp). 0 for an
+ * empty field or a first byte other than a b y p; else the leading digits behind the first '^' that stands before
+ * the first '/', at most 255, and 1 without a '^' or without digits behind it. */
+int asl_sptxt_fragment_charge(const char *s, int32_t n);
 
 /* ------------------------------------------------------------------ hot path
  * One batch of same-charge queries through
