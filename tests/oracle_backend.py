@@ -11,6 +11,19 @@ except ImportError:
     from tests import exchange_ref as X
 
 
+def oracle_ivf(O, idx):
+    """The oracle's host IVF over the lists of a device index (``faiss_compat.Index``): the same centroids, list
+    assignments, payload and codebooks, so that ``O.search_batch`` searches what the engine searches."""
+    off, ids, payload = idx.lists()
+    info = idx.info()
+    ivf = O.HostIVF.__new__(O.HostIVF)
+    ivf.centroids, ivf.nlist, ivf.d = idx.centroids(), info.nlist, info.d
+    ivf.list_offsets, ivf.ids, ivf.payload = off, ids, payload
+    ivf.codebooks = idx.codebooks() if info.kind == 2 else None
+    ivf.kind = 1 if info.kind == 2 else 0
+    return ivf
+
+
 class OracleShardBackend:
     def __init__(self, lib_np, lib_pmz32, centroids, assign, payload, codebooks, rank, world,
                  charge, k, nprobe, prec_tol, prec_mode, frag_tol, allow_shift, owner_fn):

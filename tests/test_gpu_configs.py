@@ -15,15 +15,7 @@ def iprg(O):
     return lib, aux
 
 
-def _oracle_ivf(O, idx):
-    off, ids, payload = idx.lists()
-    info = idx.info()
-    ivf = O.HostIVF.__new__(O.HostIVF)
-    ivf.centroids, ivf.nlist, ivf.d = idx.centroids(), info.nlist, info.d
-    ivf.list_offsets, ivf.ids, ivf.payload = off, ids, payload
-    ivf.codebooks = idx.codebooks() if info.kind == 2 else None
-    ivf.kind = 1 if info.kind == 2 else 0
-    return ivf
+from oracle_backend import oracle_ivf as _oracle_ivf      # noqa: E402
 
 
 def test_config0_bruteforce_cosine_plumbing(O, iprg):
