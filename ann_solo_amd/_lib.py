@@ -171,6 +171,10 @@ def lib():
             raise AnnSoloMiError(
                 f'{LIB_PATH} is missing: build it with __graft_entry__.build() '
                 '(there is no CPU fallback)')
+        # torch first: it ships a HIP runtime of its own, and in a process where this library was loaded
+        # and touched the device before torch was imported, torch finds no GPU afterwards ("No HIP GPUs
+        # are available"); with torch imported first both work (tests/test_gpu_index.py)
+        import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         L.asl_last_error.restype = C.c_char_p
         L.asl_version.restype = C.c_char_p

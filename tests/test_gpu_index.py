@@ -630,15 +630,22 @@ def test_sharded_search_merges_to_unsharded(O, vecs, trained):
         assert np.array_equal(Im, Io)
 
 
-@pytest.mark.parametrize('S,k,quant', [(8, 1024, 0), (8, 1024, 64), (2, 1000, 8), (5, 700, 0),
-                                       (2, 64, 0), (16, 1024, 2)])
-def test_topk_merge_synthetic_lists(O, S, k, quant):
+@pytest.mark.parametrize('S,k,quant,span', [
+    pytest.param(8, 1024, 0, (-0.2, 1.0), id='8-1024-0'), pytest.param(8, 1024, 64, (-0.2, 1.0), id='8-1024-64'),
+    pytest.param(2, 1000, 8, (-0.2, 1.0), id='2-1000-8'), pytest.param(5, 700, 0, (-0.2, 1.0), id='5-700-0'),
+    pytest.param(2, 64, 0, (-0.2, 1.0), id='2-64-0'), pytest.param(16, 1024, 2, (-0.2, 1.0), id='16-1024-2'),
+    pytest.param(8, 1024, 64, (1.0, 3.0), id='8-1024-64-above_one'),
+    pytest.param(3, 2048, 0, (-40.0, -0.26), id='3-2048-0-far_below'),
+    pytest.param(8, 1024, 0, (0.5, 1.5), id='8-1024-0-across_one')])
+def test_topk_merge_synthetic_lists(O, S, k, quant, span):
     """Merge of S partial lists: unsorted inputs, -1 padding, heavy score ties (quant levels),
-    ids unique across lists -- identical to the oracle under (score desc, id asc)."""
+    ids unique across lists -- identical to the oracle under (score desc, id asc). The last three sets lie
+    entirely at or above 1, entirely below -0.25 -- outside the merge histogram's bucket range, every score
+    in one end bucket (both capacities of `topk_merge_hist_kernel`) -- and on both sides of 1."""
     from ann_solo_amd import faiss_compat as faiss
     rng = np.random.default_rng(S * 1000 + k + quant)
     nq = 37
-    Ds = rng.uniform(-0.2, 1.0, (S, nq, k)).astype(np.float32)
+    Ds = rng.uniform(span[0], span[1], (S, nq, k)).astype(np.float32)
     if quant:
         Ds = (np.floor(Ds * quant) / quant).astype(np.float32)
     Is = np.empty((S, nq, k), np.int64)
@@ -647,6 +654,8 @@ def test_topk_merge_synthetic_lists(O, S, k, quant):
     pad = rng.random((S, nq, k)) < 0.15
     pad[:, 0, :] = True                     # a query with no candidates at all
     pad[1:, 1, :] = True                    # a query served by one list only
+    if span != (-0.2, 1.0):
+        assert (Ds >= 1.0).all() or (Ds < -0.25).all() or ((Ds >= 1.0).any(-1) & (Ds < 1.0).any(-1)).all()
     Is[pad] = -1
     Ds[pad] = -3.402823466e+38
     Dm, Im = faiss.topk_merge(Ds, Is)
@@ -672,6 +681,27 @@ def test_save_load_roundtrip(tmp_path, vecs, pq_index):
     assert idx2.ntotal == 0
     with pytest.raises(Exception):
         faiss.read_index(os.path.join(tmp_path, 'missing.idxmi'))
+
+
+def test_numpy_only_use_leaves_torch_its_gpu():
+    """A fresh process that searches through faiss_compat with numpy arrays only -- torch not imported by
+    the caller -- and then moves a tensor to the GPU: loading the library must not cost torch its device."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ('import sys, numpy as np\n'
+            'sys.path.insert(0, %r)\n'
+            'from ann_solo_amd import faiss_compat as faiss\n'
+            'x = np.eye(8, dtype=np.float32)\n'
+            'idx = faiss.IndexFlatIP(8)\n'
+            'idx.add(x)\n'
+            'D, I = idx.search(x, 2)\n'
+            'assert (I[:, 0] == np.arange(8)).all()\n'
+            'import torch\n'
+            'assert torch.cuda.is_available()\n'
+            'print(int(torch.arange(4).cuda().sum()))\n' % root)
+    out = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip().endswith('6'), (out.stdout[-500:], out.stderr[-2000:])
 
 
 def test_error_behaviour(vecs):
