@@ -1,9 +1,10 @@
-// mgf.hip -- MGF query files parsed on the device (asl_mgf_measure / asl_mgf_fill / asl_mgf_sort) and the numeral
-// converter on the host (asl_mgf_number). gfx950 only. DESIGN.md 3 "Query files"; the dialect is stated in
-// include/annsolo_mi.h and restated in tests/mgf_ref.py.
+// mgf.hip -- MGF query files parsed on the device (asl_mgf_measure / asl_mgf_fill) and the numeral converter on the
+// host (asl_mgf_number). gfx950 only. DESIGN.md 3 "Query files"; the dialect is stated in include/annsolo_mi.h and
+// restated in tests/mgf_ref.py. Shared with sptxt.hip: the scans and the line starts (text_scan.hpp); the counts
+// operator, the walk guard, the peak and deferred-token stores, the capacity check and the grammar-free host parts
+// of measure and fill (text_records.hpp). The sort of descending spectra, asl_mgf_sort, is peak_sort.hip.
 //
-//   starts   count the line starts (MG_SPAN bytes a thread), scan the counts, write line_start[] (text_scan.hpp,
-//            with the scan kernels: shared with sptxt.hip)
+//   starts   count the line starts (MG_SPAN bytes a thread), scan the counts, write line_start[] (text_scan.hpp)
 //   lines    one thread per line: strip, classify (BEGIN, END, the five parameters, other parameter, peak, skip)
 //            and convert its numerals (mgf_number.hpp); what the converter defers is flagged, never guessed
 //   state    a scan that composes the lines' maps of the two states {outside, inside a block}: BEGIN -> inside,
@@ -16,9 +17,6 @@
 //            key); BEGIN and END lines record their block's extent
 //   fill     peaks scattered to their slots, the deferred tokens' byte ranges and destinations, the per-spectrum
 //            columns
-//   sort     one adjacent compare per peak flags the spectra that descend anywhere; those alone are sorted, one
-//            workgroup each, by a bitonic network over at most 4096 unique keys (m/z bits, ordinal) in LDS;
-//            asl_mgf_sort_charged moves the fragment charges of a library's peaks with them, a third payload
 //
 // Every scan is reduce -> scan of the block partials (recursively) -> apply, as separate launches on the library's
 // stream: no kernel waits on another workgroup. Integer atomics only, and none whose arrival order reaches the
@@ -28,12 +26,9 @@
 
 #include "common.hpp"
 #include "mgf_number.hpp"
-#include "text_scan.hpp"
+#include "text_records.hpp"
 
 namespace asl {
-
-constexpr int MG_MAX_PEAKS = ASL_MGF_MAX_PEAKS;
-static_assert((MG_MAX_PEAKS & (MG_MAX_PEAKS - 1)) == 0, "the bitonic network pads to a power of two");
 
 enum : uint8_t {   // what a line is, whatever surrounds it
   MK_SKIP = 0, MK_BEGIN, MK_END, MK_TITLE, MK_SCAN, MK_PEPMASS, MK_CHARGE, MK_RT, MK_OTHER, MK_PEAK, MK_PEAK1
@@ -43,12 +38,7 @@ constexpr int MG_KEYS = 5;                     // MK_TITLE .. MK_RT
 struct MgTotals {   // the counts scan's result over all lines
   uint32_t opens, closes, peaks, defers, cons_byte, cons_line;
 };
-struct MgFinal {    // written by the resolve and check kernels
-  unsigned long long err;   // (line << 8 | kind) of the first structural error, ~0: none
-  uint32_t n_peaks, n_def;  // at the last closed block's END
-  uint32_t cap_spec;        // first spectrum above MG_MAX_PEAKS, ~0: none
-  uint32_t long_line;       // first line above ASL_MGF_MAX_LINE bytes, ~0: none
-};
+using MgCount = TextCount<MgTotals, &MgTotals::opens, &MgTotals::closes, &MgTotals::peaks, &MgTotals::defers>;
 
 // ---------------------------------------------------------------------------------------------- scans
 // A line as a map of the block state: bit x of the value is the state after the line when the state before is x.
@@ -56,15 +46,6 @@ struct MgState {
   using T = uint32_t;
   __device__ static T identity() { return 2u; }
   __device__ static T op(T a, T b) { return ((b >> (a & 1u)) & 1u) | (((b >> ((a >> 1) & 1u)) & 1u) << 1); }
-};
-struct MgCount {
-  using T = MgTotals;
-  __device__ static T identity() { return {0u, 0u, 0u, 0u, 0u, 0u}; }
-  __device__ static T op(T a, T b) {
-    return {a.opens + b.opens, a.closes + b.closes, a.peaks + b.peaks, a.defers + b.defers,
-            a.cons_byte > b.cons_byte ? a.cons_byte : b.cons_byte,
-            a.cons_line > b.cons_line ? a.cons_line : b.cons_line};
-  }
 };
 
 // ---------------------------------------------------------------------------------------------- one line
@@ -125,25 +106,17 @@ __device__ __forceinline__ int mg_charge(const uint8_t *__restrict__ t, uint32_t
   return v;
 }
 
-__device__ __forceinline__ uint64_t mg_pack_peak(double mz, double it) {
-  return (uint64_t)__float_as_uint((float)mz) | ((uint64_t)__float_as_uint((float)it) << 32);
-}
-
 // kind, dflag (bit k: numeral k of the line was deferred) and val (a peak's two float32, a parameter's double or
 // charge) of every line
 __global__ __launch_bounds__(MG_NT) void mgf_lines_kernel(const uint8_t *__restrict__ t,
                                                           const uint32_t *__restrict__ line_start, int64_t n_lines,
                                                           int last, uint8_t *__restrict__ kind,
                                                           uint8_t *__restrict__ dflag, uint64_t *__restrict__ val,
-                                                          MgFinal *__restrict__ fin) {
+                                                          TextFinal *__restrict__ fin) {
   const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
   if (L >= n_lines) return;
   const uint32_t a = line_start[L], b = line_start[L + 1];
-  // A thread walks its line byte by byte: a line beyond the cap is not walked at all (the call fails).
-  // The final line of a chunk that is not the file's last may be cut anywhere: it is not looked at either.
-  const bool too_long = b - a > (uint32_t)ASL_MGF_MAX_LINE;
-  if (too_long) atomicMin(&fin->long_line, (uint32_t)L);
-  if (too_long || (last == 0 && L == n_lines - 1 && t[b - 1] != (uint8_t)'\n')) {
+  if (!text_walks_line(t, a, b, L, n_lines, last, fin)) {
     kind[L] = MK_SKIP, dflag[L] = 0, val[L] = 0;
     return;
   }
@@ -185,7 +158,7 @@ __global__ __launch_bounds__(MG_NT) void mgf_lines_kernel(const uint8_t *__restr
         double d0 = 0.0, d1 = 0.0;
         df = (uint8_t)(mgf_number(reinterpret_cast<const char *>(t) + tk.t0a, (int)(tk.t0b - tk.t0a), &d0) |
                        (mgf_number(reinterpret_cast<const char *>(t) + tk.t1a, (int)(tk.t1b - tk.t1a), &d1) << 1));
-        v = mg_pack_peak(d0, d1);
+        v = pack_peak(d0, d1);
       }
     }
   }
@@ -239,7 +212,8 @@ __global__ __launch_bounds__(MG_NT) void mgf_resolve_kernel(const uint8_t *__res
                                                             uint32_t *__restrict__ first_line,
                                                             uint32_t *__restrict__ peak_begin,
                                                             uint32_t *__restrict__ peak_end,
-                                                            uint32_t *__restrict__ key_line, MgFinal *__restrict__ fin) {
+                                                            uint32_t *__restrict__ key_line,
+                                                            TextFinal *__restrict__ fin) {
   const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
   if (L >= n_lines) return;
   const bool in = L > 0 && after[L - 1] != 0;
@@ -259,15 +233,8 @@ __global__ __launch_bounds__(MG_NT) void mgf_resolve_kernel(const uint8_t *__res
   if (k >= MK_TITLE && k <= MK_RT) atomicMax(&key_line[(size_t)s * MG_KEYS + (k - MK_TITLE)], (uint32_t)(L + 1));
 }
 
-__global__ __launch_bounds__(MG_NT) void mgf_capacity_kernel(const uint32_t *__restrict__ peak_begin,
-                                                             const uint32_t *__restrict__ peak_end, uint32_t n_closed,
-                                                             MgFinal *__restrict__ fin) {
-  const uint32_t s = blockIdx.x * MG_NT + threadIdx.x;
-  if (s < n_closed && peak_end[s] - peak_begin[s] > (uint32_t)MG_MAX_PEAKS) atomicMin(&fin->cap_spec, s);
-}
-
 // ---------------------------------------------------------------------------------------------- fill
-// rec: [n_def, 5] (offset, length, destination kind, destination index, line)
+// rec: [n_def, 5], the records of put_deferred
 __global__ __launch_bounds__(MG_NT) void mgf_fill_lines_kernel(
     const uint8_t *__restrict__ t, const uint32_t *__restrict__ line_start, const uint8_t *__restrict__ kind,
     const uint8_t *__restrict__ dflag, const uint64_t *__restrict__ val, const uint8_t *__restrict__ after,
@@ -281,8 +248,7 @@ __global__ __launch_bounds__(MG_NT) void mgf_fill_lines_kernel(
   if (k == MK_PEAK) {
     const uint32_t o = slot[L];
     if (o < n_peaks) {
-      const uint64_t v = val[L];
-      mz[o] = __uint_as_float((uint32_t)v), intensity[o] = __uint_as_float((uint32_t)(v >> 32));
+      put_peak(mz, intensity, o, val[L]);
       if (charge != nullptr) charge[o] = 0;
     }
   }
@@ -291,23 +257,12 @@ __global__ __launch_bounds__(MG_NT) void mgf_fill_lines_kernel(
   mg_strip(t, line_start[L], line_start[L + 1], &p, &q);
   if (k == MK_PEAK) {
     const MgPeakTokens tk = mg_peak_tokens(t, p, q);
-    if ((df & 1) && r < n_def) {
-      int32_t *o = rec + (size_t)r * 5;
-      o[0] = (int32_t)tk.t0a, o[1] = (int32_t)(tk.t0b - tk.t0a), o[2] = ASL_MGF_DEST_MZ, o[3] = (int32_t)slot[L];
-      o[4] = (int32_t)L;
-      ++r;
-    }
-    if ((df & 2) && r < n_def) {
-      int32_t *o = rec + (size_t)r * 5;
-      o[0] = (int32_t)tk.t1a, o[1] = (int32_t)(tk.t1b - tk.t1a), o[2] = ASL_MGF_DEST_INTENSITY;
-      o[3] = (int32_t)slot[L], o[4] = (int32_t)L;
-    }
+    if ((df & 1) && r < n_def) put_deferred(rec, r++, tk.t0a, tk.t0b, ASL_MGF_DEST_MZ, slot[L], L);
+    if ((df & 2) && r < n_def) put_deferred(rec, r, tk.t1a, tk.t1b, ASL_MGF_DEST_INTENSITY, slot[L], L);
   } else if (r < n_def) {   // (the spectrum kernel names the destination of the line that wins)
     uint32_t ta, tb;
     mg_param_token(t, p, q, k, &ta, &tb);
-    int32_t *o = rec + (size_t)r * 5;
-    o[0] = (int32_t)ta, o[1] = (int32_t)(tb - ta), o[2] = ASL_MGF_DEST_NONE, o[3] = (int32_t)(spec[L] - 1u);
-    o[4] = (int32_t)L;
+    put_deferred(rec, r, ta, tb, ASL_MGF_DEST_NONE, spec[L] - 1u, L);
   }
 }
 
@@ -353,101 +308,11 @@ __global__ __launch_bounds__(MG_NT) void mgf_fill_spectra_kernel(
   ident[2 * (size_t)s] = io, ident[2 * (size_t)s + 1] = il;
 }
 
-// ---------------------------------------------------------------------------------------------- sort
-__global__ __launch_bounds__(MG_NT) void mgf_descending_kernel(const int32_t *__restrict__ offsets,
-                                                               const float *__restrict__ mz, int32_t n_spec,
-                                                               int64_t n_peaks, uint32_t *__restrict__ flag,
-                                                               uint32_t *__restrict__ list,
-                                                               uint32_t *__restrict__ n_list) {
-  const int64_t i = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
-  if (i + 1 >= n_peaks || !(mz[i + 1] < mz[i])) return;
-  int lo = 0, hi = n_spec;            // the last spectrum with offsets[s] <= i
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if ((int64_t)offsets[mid] <= i) lo = mid; else hi = mid;
-  }
-  if (i + 1 >= (int64_t)offsets[lo + 1]) return;   // the pair straddles two spectra
-  if (atomicExch(&flag[lo], 1u) == 0u) list[atomicAdd(n_list, 1u)] = (uint32_t)lo;   // (once per spectrum)
-}
-
-// Ascending in (float32 m/z, file order): -0.0 and +0.0 are one key, as in numpy's stable argsort.
-__device__ __forceinline__ uint64_t mg_sort_key(float mz, uint32_t ordinal) {
-  uint32_t u = mz == 0.0f ? 0u : __float_as_uint(mz);
-  u = (u >> 31) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)u << 32) | ordinal;
-}
-
-__global__ __launch_bounds__(MG_NT) void mgf_sort_kernel(const uint32_t *__restrict__ list,
-                                                         const int32_t *__restrict__ offsets,
-                                                         const float *__restrict__ mz,
-                                                         const float *__restrict__ intensity,
-                                                         const uint8_t *__restrict__ charge,
-                                                         float *__restrict__ mz_tmp, float *__restrict__ it_tmp,
-                                                         uint8_t *__restrict__ chg_tmp,
-                                                         uint32_t *__restrict__ too_long) {
-  __shared__ uint64_t key[MG_MAX_PEAKS];
-  const uint32_t s = list[blockIdx.x];
-  const int a = offsets[s], cnt = offsets[s + 1] - a;
-  if (cnt > MG_MAX_PEAKS) {            // (the same for the whole workgroup)
-    if (threadIdx.x == 0) atomicOr(too_long, 1u);
-    return;
-  }
-  int P = 2;
-  while (P < cnt) P <<= 1;
-  for (int i = threadIdx.x; i < P; i += MG_NT) key[i] = i < cnt ? mg_sort_key(mz[a + i], (uint32_t)i) : ~0ull;
-  __syncthreads();
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < P; i += MG_NT) {
-        const int o = i ^ j;
-        if (o > i) {
-          const uint64_t x = key[i], y = key[o];
-          if ((x > y) == ((i & k) == 0)) key[i] = y, key[o] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  for (int i = threadIdx.x; i < cnt; i += MG_NT) {
-    const int src = (int)(uint32_t)key[i];
-    mz_tmp[a + i] = mz[a + src], it_tmp[a + i] = intensity[a + src];
-    if (charge != nullptr) chg_tmp[a + i] = charge[a + src];
-  }
-}
-
-__global__ __launch_bounds__(MG_NT) void mgf_sort_copy_kernel(const uint32_t *__restrict__ list,
-                                                              const int32_t *__restrict__ offsets,
-                                                              const float *__restrict__ mz_tmp,
-                                                              const float *__restrict__ it_tmp,
-                                                              const uint8_t *__restrict__ chg_tmp,
-                                                              float *__restrict__ mz, float *__restrict__ intensity,
-                                                              uint8_t *__restrict__ charge) {
-  const uint32_t s = list[blockIdx.x];
-  const int a = offsets[s], cnt = offsets[s + 1] - a;
-  if (cnt > MG_MAX_PEAKS) return;
-  for (int i = threadIdx.x; i < cnt; i += MG_NT) {
-    mz[a + i] = mz_tmp[a + i], intensity[a + i] = it_tmp[a + i];
-    if (charge != nullptr) charge[a + i] = chg_tmp[a + i];
-  }
-}
-
 namespace {
 
-// grow-only device workspace; asl_mgf_fill reads what the asl_mgf_measure before it left here
-struct MgfWork {
-  DevBuf<uint32_t> line_start, spec, slot, dslot, first_line, peak_begin, peak_end, key_line, flag, list, small;
-  DevBuf<uint8_t> kind, dflag, after;
-  DevBuf<uint64_t> val;
-  DevBuf<unsigned long long> count;
-  DevBuf<MgTotals> partial, totals;
-  DevBuf<MgFinal> fin;
-  DevBuf<float> mz_tmp, it_tmp;
-  DevBuf<uint8_t> chg_tmp;
-  // the measured chunk
-  const void *text = nullptr;
-  int64_t n = -1, n_lines = 0;
-  uint32_t n_closed = 0, n_peaks = 0, n_def = 0;
-  uint32_t n_blocks = 0;   // blocks whose deferred tokens are listed: the closed ones, at the file's end the open one too
+// n_rec: the closed blocks; n_blocks: they, and at the file's end the open one too
+struct MgfWork : ChunkWork<MgTotals> {
+  DevBuf<uint32_t> key_line;
 };
 MgfWork &work() {
   static MgfWork w;
@@ -466,41 +331,19 @@ extern "C" int asl_mgf_number(const char *s, int32_t n, double *out) {
 
 extern "C" int asl_mgf_measure(const uint8_t *text, int64_t n, int32_t last, int64_t *counts) {
   clear_error();
-  if (n >= ((int64_t)1 << 31)) return fail(ASL_ERR_CAPACITY, "mgf_measure: n = %lld, below 2^31", (long long)n);
-  if (n < 0) return fail(ASL_ERR_INVALID, "mgf_measure: n < 0");
-  if (counts == nullptr) return fail(ASL_ERR_INVALID, "mgf_measure: null counts");
-  if (last != 0 && last != 1) return fail(ASL_ERR_INVALID, "mgf_measure: last = %d, 0 or 1", (int)last);
   MgfWork &W = work();
-  W.text = nullptr, W.n = -1;   // (nothing to fill until this call succeeds)
-  for (int k = 0; k < ASL_MGF_COUNTS; ++k) counts[k] = 0;
-  counts[ASL_MGF_ERR_LINE] = -1;
-  if (n == 0) {
-    W.text = text, W.n = 0, W.n_lines = 0, W.n_closed = W.n_peaks = W.n_def = W.n_blocks = 0;
-    return ASL_OK;
-  }
-  if (text == nullptr) return fail(ASL_ERR_INVALID, "mgf_measure: null text");
-  ASL_TRY(ensure_device());
-  if (!is_device_ptr(text)) return fail(ASL_ERR_INVALID, "mgf_measure: text must be device memory");
+  ASL_TRY(measure_begin("mgf", W, text, n, last, counts));
+  if (n == 0) return ASL_OK;
   ProfScope ps("mgf_measure");
   int64_t nl = 0;   // >= 1
   ASL_TRY(line_starts(text, n, W.count, W.partial, W.line_start, &nl));
   // lines, block state, counts
-  ASL_TRY(W.kind.reserve((size_t)nl));
-  ASL_TRY(W.dflag.reserve((size_t)nl));
-  ASL_TRY(W.after.reserve((size_t)nl));
-  ASL_TRY(W.val.reserve((size_t)nl));
-  ASL_TRY(W.spec.reserve((size_t)nl));
-  ASL_TRY(W.slot.reserve((size_t)nl));
-  ASL_TRY(W.dslot.reserve((size_t)nl));
-  ASL_TRY(W.totals.reserve(1));
-  ASL_TRY(W.fin.reserve(1));
-  MgFinal F{~0ull, 0u, 0u, ~0u, ~0u};
-  HIP_TRY(hipMemcpyAsync(W.fin.p, &F, sizeof(F), hipMemcpyHostToDevice, stream()));
+  ASL_TRY(measure_lines(W, nl));
   hipLaunchKernelGGL(mgf_lines_kernel, dim3(blocks_of(nl)), dim3(MG_NT), 0, stream(), text, W.line_start.p, nl,
                      (int)last, W.kind.p, W.dflag.p, W.val.p, W.fin.p);
   ASL_CHECK_LAUNCH();
   ASL_TRY(scan_view(StateView{W.kind.p, W.after.p}, nl, W.partial.p));
-  ASL_TRY(scan_view(CountView{W.kind.p, W.dflag.p, W.after.p, W.line_start.p, W.spec.p, W.slot.p, W.dslot.p,
+  ASL_TRY(scan_view(CountView{W.kind.p, W.dflag.p, W.after.p, W.line_start.p, W.rec.p, W.slot.p, W.dslot.p,
                               W.totals.p, nl},
                     nl, W.partial.p));
   MgTotals T;
@@ -516,38 +359,26 @@ extern "C" int asl_mgf_measure(const uint8_t *text, int64_t n, int32_t last, int
   HIP_TRY(hipMemsetAsync(W.key_line.p, 0, ns * MG_KEYS * sizeof(uint32_t), stream()));
   const int64_t gate = last != 0 ? nl : (int64_t)T.cons_line;
   hipLaunchKernelGGL(mgf_resolve_kernel, dim3(blocks_of(nl)), dim3(MG_NT), 0, stream(), W.kind.p, W.after.p,
-                     W.spec.p, W.slot.p, W.dslot.p, nl, gate, n_open, n_closed, W.first_line.p, W.peak_begin.p,
+                     W.rec.p, W.slot.p, W.dslot.p, nl, gate, n_open, n_closed, W.first_line.p, W.peak_begin.p,
                      W.peak_end.p, W.key_line.p, W.fin.p);
   ASL_CHECK_LAUNCH();
   if (n_closed > 0) {
-    hipLaunchKernelGGL(mgf_capacity_kernel, dim3(blocks_of(n_closed)), dim3(MG_NT), 0, stream(), W.peak_begin.p,
-                       W.peak_end.p, n_closed, W.fin.p);
+    hipLaunchKernelGGL(text_capacity_kernel, dim3(blocks_of(n_closed)), dim3(MG_NT), 0, stream(), W.peak_begin.p,
+                       W.peak_end.p, n_closed, 0, 0u, W.fin.p);
     ASL_CHECK_LAUNCH();
   }
-  HIP_TRY(hipMemcpyAsync(&F, W.fin.p, sizeof(F), hipMemcpyDeviceToHost, stream()));
-  ASL_TRY(sync_stream());
-  if (F.long_line != ~0u)
-    return fail(ASL_ERR_CAPACITY, "mgf_measure: line %u of the chunk is longer than %d bytes", (unsigned)F.long_line + 1u,
-                ASL_MGF_MAX_LINE);
-  // at the file's end the numerals of an unclosed last block are reported too, so that the caller can refuse them
-  const uint32_t n_def = last != 0 ? T.defers : F.n_def;
+  TextFinal F;
+  ASL_TRY(measure_final("mgf", W, &F));
   counts[ASL_MGF_N_LINES] = nl;
   counts[ASL_MGF_N_SPECTRA] = n_closed;
   counts[ASL_MGF_N_PEAKS] = F.n_peaks;
-  counts[ASL_MGF_N_DEFERRED] = n_def;
+  // at the file's end the numerals of an unclosed last block are reported too, so that the caller can refuse them
+  counts[ASL_MGF_N_DEFERRED] = last != 0 ? T.defers : F.n_def;
   counts[ASL_MGF_CONSUMED] = T.cons_byte;
   counts[ASL_MGF_CONSUMED_LINES] = T.cons_line;
   counts[ASL_MGF_OPEN] = n_open > n_closed ? 1 : 0;
-  if (F.err != ~0ull) {
-    counts[ASL_MGF_ERR_KIND] = (int64_t)(F.err & 255u);
-    counts[ASL_MGF_ERR_LINE] = (int64_t)(F.err >> 8);
-  }
-  if (F.cap_spec != ~0u)
-    return fail(ASL_ERR_CAPACITY, "mgf_measure: spectrum %u of the chunk has more than %d peak lines",
-                (unsigned)F.cap_spec + 1u, MG_MAX_PEAKS);
-  W.text = text, W.n = n, W.n_lines = nl, W.n_closed = n_closed, W.n_peaks = F.n_peaks, W.n_def = n_def;
   W.n_blocks = last != 0 ? n_open : n_closed;
-  return ASL_OK;
+  return measure_end("mgf", "spectrum", W, F, text, n, counts);
 }
 
 extern "C" int asl_mgf_fill(const uint8_t *text, int64_t n, int32_t *offsets, float *mz, float *intensity,
@@ -555,19 +386,9 @@ extern "C" int asl_mgf_fill(const uint8_t *text, int64_t n, int32_t *offsets, fl
                             double *retention_time, int32_t *identifier, int32_t *first_line, int32_t *deferred) {
   clear_error();
   MgfWork &W = work();
-  if (W.n < 0 || text != W.text || n != W.n)
-    return fail(ASL_ERR_STATE, "mgf_fill: not the chunk the last successful asl_mgf_measure measured");
-  if (offsets == nullptr) return fail(ASL_ERR_INVALID, "mgf_fill: null offsets");
-  const uint32_t ns = W.n_closed, np = W.n_peaks, nd = W.n_def;
-  if (ns == 0 && nd == 0) {
-    if (is_device_ptr(offsets)) {
-      HIP_TRY(hipMemsetAsync(offsets, 0, sizeof(int32_t), stream()));
-      ASL_TRY(sync_stream());
-    } else {
-      offsets[0] = 0;
-    }
-    return ASL_OK;
-  }
+  ASL_TRY(fill_begin("mgf", W, text, n, offsets));
+  const uint32_t ns = W.n_rec, np = W.n_peaks, nd = W.n_def;
+  if (ns == 0 && nd == 0) return fill_empty(offsets);
   if ((np > 0 && (!mz || !intensity)) ||
       (ns > 0 && (!precursor_mz || !precursor_charge || !retention_time || !identifier || !first_line)) ||
       (nd > 0 && !deferred))
@@ -589,7 +410,7 @@ extern "C" int asl_mgf_fill(const uint8_t *text, int64_t n, int32_t *offsets, fl
   ASL_TRY(oFirst.init(first_line, ns));
   ASL_TRY(oRec.init(deferred, (size_t)nd * 5));
   hipLaunchKernelGGL(mgf_fill_lines_kernel, dim3(blocks_of(W.n_lines)), dim3(MG_NT), 0, stream(), text,
-                     W.line_start.p, W.kind.p, W.dflag.p, W.val.p, W.after.p, W.spec.p, W.slot.p, W.dslot.p,
+                     W.line_start.p, W.kind.p, W.dflag.p, W.val.p, W.after.p, W.rec.p, W.slot.p, W.dslot.p,
                      W.n_lines, W.n_blocks, np, nd, oMz.d, oIt.d, oChg.d, oRec.d);
   ASL_CHECK_LAUNCH();
   if (ns > 0) {   // (none: the deferred tokens of an unclosed last block alone)
@@ -600,66 +421,5 @@ extern "C" int asl_mgf_fill(const uint8_t *text, int64_t n, int32_t *offsets, fl
   } else if (oOff.d != nullptr) {
     HIP_TRY(hipMemsetAsync(oOff.d, 0, sizeof(int32_t), stream()));
   }
-  ASL_TRY(oOff.finish());
-  ASL_TRY(oMz.finish());
-  ASL_TRY(oIt.finish());
-  ASL_TRY(oChg.finish());
-  ASL_TRY(oPmz.finish());
-  ASL_TRY(oZ.finish());
-  ASL_TRY(oRt.finish());
-  ASL_TRY(oId.finish());
-  ASL_TRY(oFirst.finish());
-  ASL_TRY(oRec.finish());
-  ASL_TRY(sync_stream());
-  return ASL_OK;
-}
-
-extern "C" int asl_mgf_sort(const int32_t *offsets, float *mz, float *intensity, int32_t n_spectra, int64_t n_peaks,
-                            int64_t *n_sorted) {
-  return asl_mgf_sort_charged(offsets, mz, intensity, nullptr, n_spectra, n_peaks, n_sorted);
-}
-
-extern "C" int asl_mgf_sort_charged(const int32_t *offsets, float *mz, float *intensity, uint8_t *charge,
-                                    int32_t n_spectra, int64_t n_peaks, int64_t *n_sorted) {
-  clear_error();
-  if (n_spectra < 0 || n_peaks < 0) return fail(ASL_ERR_INVALID, "mgf_sort: a negative count");
-  if (n_peaks >= ((int64_t)1 << 31)) return fail(ASL_ERR_CAPACITY, "mgf_sort: n_peaks = %lld, below 2^31",
-                                                 (long long)n_peaks);
-  if (n_sorted != nullptr) *n_sorted = 0;
-  if (n_spectra == 0 || n_peaks < 2) return ASL_OK;
-  if (!offsets || !mz || !intensity) return fail(ASL_ERR_INVALID, "mgf_sort: null offsets / mz / intensity");
-  ASL_TRY(ensure_device());
-  if (!is_device_ptr(offsets) || !is_device_ptr(mz) || !is_device_ptr(intensity))
-    return fail(ASL_ERR_INVALID, "mgf_sort: the pack must be device memory");
-  if (charge != nullptr && !is_device_ptr(charge))
-    return fail(ASL_ERR_INVALID, "mgf_sort: the charges must be device memory");
-  MgfWork &W = work();
-  ProfScope ps("mgf_sort");
-  ASL_TRY(W.flag.reserve((size_t)n_spectra));
-  ASL_TRY(W.list.reserve((size_t)n_spectra));
-  ASL_TRY(W.small.reserve(2));     // [0]: flagged spectra, [1]: one of them is above the capacity
-  HIP_TRY(hipMemsetAsync(W.flag.p, 0, (size_t)n_spectra * sizeof(uint32_t), stream()));
-  HIP_TRY(hipMemsetAsync(W.small.p, 0, 2 * sizeof(uint32_t), stream()));
-  hipLaunchKernelGGL(mgf_descending_kernel, dim3(blocks_of(n_peaks)), dim3(MG_NT), 0, stream(), offsets, mz,
-                     n_spectra, n_peaks, W.flag.p, W.list.p, W.small.p);
-  ASL_CHECK_LAUNCH();
-  uint32_t h[2] = {0u, 0u};
-  HIP_TRY(hipMemcpyAsync(h, W.small.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
-  ASL_TRY(sync_stream());
-  if (n_sorted != nullptr) *n_sorted = h[0];
-  if (h[0] == 0u) return ASL_OK;   // ascending everywhere: no sort is launched
-  ASL_TRY(W.mz_tmp.reserve((size_t)n_peaks));
-  ASL_TRY(W.it_tmp.reserve((size_t)n_peaks));
-  if (charge != nullptr) ASL_TRY(W.chg_tmp.reserve((size_t)n_peaks));
-  hipLaunchKernelGGL(mgf_sort_kernel, dim3(h[0]), dim3(MG_NT), 0, stream(), W.list.p, offsets, mz, intensity,
-                     charge, W.mz_tmp.p, W.it_tmp.p, W.chg_tmp.p, W.small.p + 1);
-  ASL_CHECK_LAUNCH();
-  hipLaunchKernelGGL(mgf_sort_copy_kernel, dim3(h[0]), dim3(MG_NT), 0, stream(), W.list.p, offsets, W.mz_tmp.p,
-                     W.it_tmp.p, W.chg_tmp.p, mz, intensity, charge);
-  ASL_CHECK_LAUNCH();
-  HIP_TRY(hipMemcpyAsync(h, W.small.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
-  ASL_TRY(sync_stream());
-  if (h[1] != 0u)
-    return fail(ASL_ERR_CAPACITY, "mgf_sort: a descending spectrum has more than %d peaks", MG_MAX_PEAKS);
-  return ASL_OK;
+  return finish_outputs(oOff, oMz, oIt, oChg, oPmz, oZ, oRt, oId, oFirst, oRec);
 }

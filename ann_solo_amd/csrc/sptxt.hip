@@ -1,8 +1,10 @@
 // sptxt.hip -- SpectraST .sptxt libraries parsed on the device (asl_sptxt_measure / asl_sptxt_fill) and the
 // annotation rule on the host (asl_sptxt_fragment_charge). gfx950 only. DESIGN.md 3 "Library files"; the dialect is
-// stated in include/annsolo_mi.h and restated in tests/sptxt_ref.py.
+// stated in include/annsolo_mi.h and restated in tests/sptxt_ref.py. Shared with mgf.hip: the scans and the line
+// starts (text_scan.hpp); the counts operator, the walk guard, the peak and deferred-token stores, the capacity check
+// and the grammar-free host parts of measure and fill (text_records.hpp).
 //
-//   starts    the line starts of the chunk (text_scan.hpp, shared with mgf.hip)
+//   starts    the line starts of the chunk (text_scan.hpp)
 //   classify  one thread per line looks at the head of the stripped line: Name:, Num Peaks:, PrecursorMZ:, other
 //   state     a scan that composes the lines' maps of the three states {outside a record, in its metadata, in its
 //             peaks}: Name: -> metadata, Num Peaks: in the metadata -> peaks, anything else keeps the state
@@ -18,19 +20,17 @@
 //             destinations, the per-record columns (one thread per record reads its Name: line and the lines that won)
 //
 // A record is closed by the next Name: line, or by the end of the file when `last` is set. The sort of descending
-// spectra is asl_mgf_sort_charged (mgf.hip). Integer atomics only, and none whose arrival order reaches the output.
-// Every byte index is bounded by the chunk length and every line by line_start[n_lines] == n.
+// spectra is asl_mgf_sort_charged (peak_sort.hip). Integer atomics only, and none whose arrival order reaches the
+// output. Every byte index is bounded by the chunk length and every line by line_start[n_lines] == n.
 #include <algorithm>
 
 #include "common.hpp"
 #include "mgf_number.hpp"
 #include "sptxt_annot.hpp"
-#include "text_scan.hpp"
+#include "text_records.hpp"
 
 namespace asl {
 namespace {
-
-constexpr int SP_MAX_PEAKS = ASL_MGF_MAX_PEAKS;
 
 enum : uint8_t { SK_SKIP = 0, SK_NAME, SK_NUMPEAKS, SK_PMZ, SK_OTHER };   // the head of a line, whatever surrounds it
 enum : uint8_t {                                                          // what the parse found in a line
@@ -41,12 +41,7 @@ enum : uint32_t { SS_OUT = 0, SS_META = 1, SS_PEAKS = 2 };
 struct SpTotals {   // the counts scan's result over all lines
   uint32_t opens, peaks, defers, cons_byte, cons_line;
 };
-struct SpFinal {    // written by the classify, resolve and capacity kernels
-  unsigned long long err;   // (line << 8 | kind) of the first structural error, ~0: none
-  uint32_t n_peaks, n_def;  // before the Name: line of the first record that is not closed
-  uint32_t cap_rec;         // first record above SP_MAX_PEAKS, ~0: none
-  uint32_t long_line;       // first line above ASL_MGF_MAX_LINE bytes, ~0: none
-};
+using SpCount = TextCount<SpTotals, &SpTotals::opens, &SpTotals::peaks, &SpTotals::defers>;
 
 // A line as a map of the record state: bits 2 x, 2 x + 1 of the value hold the state after the line when the state
 // before it is x.
@@ -58,15 +53,6 @@ struct SpState {
 #pragma unroll
     for (int s = 0; s < 3; ++s) r |= ((b >> (2u * ((a >> (2 * s)) & 3u))) & 3u) << (2 * s);
     return r;
-  }
-};
-struct SpCount {
-  using T = SpTotals;
-  __device__ static T identity() { return {0u, 0u, 0u, 0u, 0u}; }
-  __device__ static T op(T a, T b) {
-    return {a.opens + b.opens, a.peaks + b.peaks, a.defers + b.defers,
-            a.cons_byte > b.cons_byte ? a.cons_byte : b.cons_byte,
-            a.cons_line > b.cons_line ? a.cons_line : b.cons_line};
   }
 };
 
@@ -144,23 +130,16 @@ __device__ __forceinline__ SpFields sp_fields(const uint8_t *__restrict__ t, uin
   f.f2b = i;
   return f;
 }
-__device__ __forceinline__ uint64_t sp_pack_peak(double mz, double it) {
-  return (uint64_t)__float_as_uint((float)mz) | ((uint64_t)__float_as_uint((float)it) << 32);
-}
 
 // ---------------------------------------------------------------------------------------------- lines
 __global__ __launch_bounds__(MG_NT) void sptxt_classify_kernel(const uint8_t *__restrict__ t,
                                                                const uint32_t *__restrict__ line_start,
                                                                int64_t n_lines, int last, uint8_t *__restrict__ kind,
-                                                               SpFinal *__restrict__ fin) {
+                                                               TextFinal *__restrict__ fin) {
   const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
   if (L >= n_lines) return;
   const uint32_t a = line_start[L], b = line_start[L + 1];
-  // A thread walks its line byte by byte: a line beyond the cap is not walked at all (the call fails).
-  // The final line of a chunk that is not the file's last may be cut anywhere: it is not looked at either.
-  const bool too_long = b - a > (uint32_t)ASL_MGF_MAX_LINE;
-  if (too_long) atomicMin(&fin->long_line, (uint32_t)L);
-  if (too_long || (last == 0 && L == n_lines - 1 && t[b - 1] != (uint8_t)'\n')) {
+  if (!text_walks_line(t, a, b, L, n_lines, last, fin)) {
     kind[L] = SK_SKIP;
     return;
   }
@@ -256,7 +235,7 @@ __global__ __launch_bounds__(MG_NT) void sptxt_parse_kernel(const uint8_t *__res
           double d0 = 0.0, d1 = 0.0;
           df = (uint8_t)(mgf_number(reinterpret_cast<const char *>(t) + m0, (int)(m1 - m0), &d0) |
                          (mgf_number(reinterpret_cast<const char *>(t) + i0, (int)(i1 - i0), &d1) << 1));
-          v = sp_pack_peak(d0, d1);
+          v = pack_peak(d0, d1);
           cz = (uint8_t)sptxt_fragment_charge(reinterpret_cast<const char *>(t) + f.f2a, (int)(f.f2b - f.f2a));
         }
       }
@@ -292,7 +271,7 @@ __global__ __launch_bounds__(MG_NT) void sptxt_resolve_kernel(
     int64_t n_lines, int64_t gate, uint32_t n_open, uint32_t n_rec, uint32_t *__restrict__ first_line,
     uint32_t *__restrict__ peak_begin, uint32_t *__restrict__ peak_end, uint32_t *__restrict__ pmz_line,
     uint32_t *__restrict__ parent_line, uint32_t *__restrict__ mods_line, uint32_t *__restrict__ decoy,
-    SpFinal *__restrict__ fin) {
+    TextFinal *__restrict__ fin) {
   const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
   if (L >= n_lines) return;
   const uint8_t k = kind[L], fl = flags[L];
@@ -321,19 +300,8 @@ __global__ __launch_bounds__(MG_NT) void sptxt_resolve_kernel(
   if (fl & SF_MODS) atomicMin(&mods_line[s], (uint32_t)L);
 }
 
-// end_peaks: where the last record's peaks end when the file's end closes it (else its successor's Name: line did)
-__global__ __launch_bounds__(MG_NT) void sptxt_capacity_kernel(const uint32_t *__restrict__ peak_begin,
-                                                               uint32_t *__restrict__ peak_end, uint32_t n_rec,
-                                                               int last, uint32_t end_peaks,
-                                                               SpFinal *__restrict__ fin) {
-  const uint32_t s = blockIdx.x * MG_NT + threadIdx.x;
-  if (s >= n_rec) return;
-  if (last != 0 && s + 1u == n_rec) peak_end[s] = end_peaks;
-  if (peak_end[s] - peak_begin[s] > (uint32_t)SP_MAX_PEAKS) atomicMin(&fin->cap_rec, s);
-}
-
 // ---------------------------------------------------------------------------------------------- fill
-// out: [n_def, 5] (offset, length, destination kind, destination index, line)
+// out: [n_def, 5], the records of put_deferred
 __global__ __launch_bounds__(MG_NT) void sptxt_fill_lines_kernel(
     const uint8_t *__restrict__ t, const uint32_t *__restrict__ line_start, const uint8_t *__restrict__ kind,
     const uint8_t *__restrict__ flags, const uint8_t *__restrict__ dflag, const uint8_t *__restrict__ chg,
@@ -347,8 +315,7 @@ __global__ __launch_bounds__(MG_NT) void sptxt_fill_lines_kernel(
   if (fl & SF_PEAK) {
     const uint32_t o = slot[L];
     if (o < n_peaks) {
-      const uint64_t v = val[L];
-      mz[o] = __uint_as_float((uint32_t)v), intensity[o] = __uint_as_float((uint32_t)(v >> 32));
+      put_peak(mz, intensity, o, val[L]);
       charge[o] = chg[L];
     }
   }
@@ -362,25 +329,18 @@ __global__ __launch_bounds__(MG_NT) void sptxt_fill_lines_kernel(
     uint32_t x0, x1;
     if ((df & 1) && r < n_def) {
       mg_strip(t, f.f0a, f.f0b, &x0, &x1);
-      int32_t *o = out + (size_t)r * 5;
-      o[0] = (int32_t)x0, o[1] = (int32_t)(x1 - x0), o[2] = ASL_SPTXT_DEST_MZ, o[3] = (int32_t)slot[L];
-      o[4] = (int32_t)L;
-      ++r;
+      put_deferred(out, r++, x0, x1, ASL_SPTXT_DEST_MZ, slot[L], L);
     }
     if ((df & 2) && r < n_def) {
       mg_strip(t, f.f1a, f.f1b, &x0, &x1);
-      int32_t *o = out + (size_t)r * 5;
-      o[0] = (int32_t)x0, o[1] = (int32_t)(x1 - x0), o[2] = ASL_SPTXT_DEST_INTENSITY, o[3] = (int32_t)slot[L];
-      o[4] = (int32_t)L;
+      put_deferred(out, r, x0, x1, ASL_SPTXT_DEST_INTENSITY, slot[L], L);
     }
   } else if (r < n_def) {   // a precursor numeral: the record kernel names the destination of the line that wins
     uint32_t p, q, ta, tb;
     mg_strip(t, a, b, &p, &q);
     if (kind[L] == SK_PMZ) sp_precursor_token(t, p + 12u, q, true, &ta, &tb);
     else sp_precursor_token(t, sp_find(t, p, q, "parent=", 7) + 7u, q, false, &ta, &tb);
-    int32_t *o = out + (size_t)r * 5;
-    o[0] = (int32_t)ta, o[1] = (int32_t)(tb - ta), o[2] = ASL_SPTXT_DEST_NONE, o[3] = (int32_t)(rec[L] - 1u);
-    o[4] = (int32_t)L;
+    put_deferred(out, r, ta, tb, ASL_SPTXT_DEST_NONE, rec[L] - 1u, L);
   }
 }
 
@@ -447,20 +407,10 @@ __global__ __launch_bounds__(MG_NT) void sptxt_fill_records_kernel(
   o[7] = (int32_t)first_line[s];
 }
 
-// grow-only device workspace; asl_sptxt_fill reads what the asl_sptxt_measure before it left here
-struct SptxtWork {
-  DevBuf<uint32_t> line_start, rec, slot, dslot, first_line, peak_begin, peak_end, pmz_line, parent_line, mods_line,
-      decoy;
-  DevBuf<uint8_t> kind, flags, dflag, chg, after;
-  DevBuf<uint64_t> val;
-  DevBuf<unsigned long long> count;
-  DevBuf<SpTotals> partial, totals;
-  DevBuf<SpFinal> fin;
-  // the measured chunk
-  const void *text = nullptr;
-  int64_t n = -1, n_lines = 0;
-  uint32_t n_rec = 0, n_peaks = 0, n_def = 0;
-  uint32_t n_blocks = 0;   // records whose deferred tokens are listed: the closed ones
+// n_rec == n_blocks: the closed records
+struct SptxtWork : ChunkWork<SpTotals> {
+  DevBuf<uint32_t> pmz_line, parent_line, mods_line, decoy;
+  DevBuf<uint8_t> flags, chg;
 };
 SptxtWork &work() {
   static SptxtWork w;
@@ -479,21 +429,9 @@ extern "C" int asl_sptxt_fragment_charge(const char *s, int32_t n) {
 
 extern "C" int asl_sptxt_measure(const uint8_t *text, int64_t n, int32_t last, int64_t *counts) {
   clear_error();
-  if (n >= ((int64_t)1 << 31)) return fail(ASL_ERR_CAPACITY, "sptxt_measure: n = %lld, below 2^31", (long long)n);
-  if (n < 0) return fail(ASL_ERR_INVALID, "sptxt_measure: n < 0");
-  if (counts == nullptr) return fail(ASL_ERR_INVALID, "sptxt_measure: null counts");
-  if (last != 0 && last != 1) return fail(ASL_ERR_INVALID, "sptxt_measure: last = %d, 0 or 1", (int)last);
   SptxtWork &W = work();
-  W.text = nullptr, W.n = -1;   // (nothing to fill until this call succeeds)
-  for (int k = 0; k < ASL_SPTXT_COUNTS; ++k) counts[k] = 0;
-  counts[ASL_SPTXT_ERR_LINE] = -1;
-  if (n == 0) {
-    W.text = text, W.n = 0, W.n_lines = 0, W.n_rec = W.n_peaks = W.n_def = W.n_blocks = 0;
-    return ASL_OK;
-  }
-  if (text == nullptr) return fail(ASL_ERR_INVALID, "sptxt_measure: null text");
-  ASL_TRY(ensure_device());
-  if (!is_device_ptr(text)) return fail(ASL_ERR_INVALID, "sptxt_measure: text must be device memory");
+  ASL_TRY(measure_begin("sptxt", W, text, n, last, counts));
+  if (n == 0) return ASL_OK;
   ProfScope ps("sptxt_measure");
   int64_t nl = 0;   // >= 1
   {
@@ -501,19 +439,9 @@ extern "C" int asl_sptxt_measure(const uint8_t *text, int64_t n, int32_t last, i
     ASL_TRY(line_starts(text, n, W.count, W.partial, W.line_start, &nl));
   }
   // heads, record state, the lines themselves, counts
-  ASL_TRY(W.kind.reserve((size_t)nl));
   ASL_TRY(W.flags.reserve((size_t)nl));
-  ASL_TRY(W.dflag.reserve((size_t)nl));
   ASL_TRY(W.chg.reserve((size_t)nl));
-  ASL_TRY(W.after.reserve((size_t)nl));
-  ASL_TRY(W.val.reserve((size_t)nl));
-  ASL_TRY(W.rec.reserve((size_t)nl));
-  ASL_TRY(W.slot.reserve((size_t)nl));
-  ASL_TRY(W.dslot.reserve((size_t)nl));
-  ASL_TRY(W.totals.reserve(1));
-  ASL_TRY(W.fin.reserve(1));
-  SpFinal F{~0ull, 0u, 0u, ~0u, ~0u};
-  HIP_TRY(hipMemcpyAsync(W.fin.p, &F, sizeof(F), hipMemcpyHostToDevice, stream()));
+  ASL_TRY(measure_lines(W, nl));
   {
     ProfScope p2("sptxt_classify");
     hipLaunchKernelGGL(sptxt_classify_kernel, dim3(blocks_of(nl)), dim3(MG_NT), 0, stream(), text, W.line_start.p,
@@ -562,15 +490,12 @@ extern "C" int asl_sptxt_measure(const uint8_t *text, int64_t n, int32_t last, i
                      W.peak_end.p, W.pmz_line.p, W.parent_line.p, W.mods_line.p, W.decoy.p, W.fin.p);
   ASL_CHECK_LAUNCH();
   if (n_rec > 0) {
-    hipLaunchKernelGGL(sptxt_capacity_kernel, dim3(blocks_of(n_rec)), dim3(MG_NT), 0, stream(), W.peak_begin.p,
+    hipLaunchKernelGGL(text_capacity_kernel, dim3(blocks_of(n_rec)), dim3(MG_NT), 0, stream(), W.peak_begin.p,
                        W.peak_end.p, n_rec, (int)last, T.peaks, W.fin.p);
     ASL_CHECK_LAUNCH();
   }
-  HIP_TRY(hipMemcpyAsync(&F, W.fin.p, sizeof(F), hipMemcpyDeviceToHost, stream()));
-  ASL_TRY(sync_stream());
-  if (F.long_line != ~0u)
-    return fail(ASL_ERR_CAPACITY, "sptxt_measure: line %u of the chunk is longer than %d bytes",
-                (unsigned)F.long_line + 1u, ASL_MGF_MAX_LINE);
+  TextFinal F;
+  ASL_TRY(measure_final("sptxt", W, &F));
   const bool open = last == 0 && n_open > 0u;
   const uint32_t n_peaks = open ? F.n_peaks : T.peaks, n_def = open ? F.n_def : T.defers;
   counts[ASL_SPTXT_N_LINES] = nl;
@@ -580,36 +505,17 @@ extern "C" int asl_sptxt_measure(const uint8_t *text, int64_t n, int32_t last, i
   counts[ASL_SPTXT_CONSUMED] = last != 0 ? n : (n_open > 0u ? (int64_t)T.cons_byte : 0);
   counts[ASL_SPTXT_CONSUMED_LINES] = gate;
   counts[ASL_SPTXT_OPEN] = open ? 1 : 0;
-  if (F.err != ~0ull) {
-    counts[ASL_SPTXT_ERR_KIND] = (int64_t)(F.err & 255u);
-    counts[ASL_SPTXT_ERR_LINE] = (int64_t)(F.err >> 8);
-  }
-  if (F.cap_rec != ~0u)
-    return fail(ASL_ERR_CAPACITY, "sptxt_measure: record %u of the chunk has more than %d peak lines",
-                (unsigned)F.cap_rec + 1u, SP_MAX_PEAKS);
-  W.text = text, W.n = n, W.n_lines = nl, W.n_rec = n_rec;
-  W.n_peaks = (uint32_t)counts[ASL_SPTXT_N_PEAKS], W.n_def = (uint32_t)counts[ASL_SPTXT_N_DEFERRED];
   W.n_blocks = n_rec;
-  return ASL_OK;
+  return measure_end("sptxt", "record", W, F, text, n, counts);
 }
 
 extern "C" int asl_sptxt_fill(const uint8_t *text, int64_t n, int32_t *offsets, float *mz, float *intensity,
                               uint8_t *charge, double *precursor_mz, int32_t *info, int32_t *deferred) {
   clear_error();
   SptxtWork &W = work();
-  if (W.n < 0 || text != W.text || n != W.n)
-    return fail(ASL_ERR_STATE, "sptxt_fill: not the chunk the last successful asl_sptxt_measure measured");
-  if (offsets == nullptr) return fail(ASL_ERR_INVALID, "sptxt_fill: null offsets");
+  ASL_TRY(fill_begin("sptxt", W, text, n, offsets));
   const uint32_t ns = W.n_rec, np = W.n_peaks, nd = W.n_def;
-  if (ns == 0) {
-    if (is_device_ptr(offsets)) {
-      HIP_TRY(hipMemsetAsync(offsets, 0, sizeof(int32_t), stream()));
-      ASL_TRY(sync_stream());
-    } else {
-      offsets[0] = 0;
-    }
-    return ASL_OK;
-  }
+  if (ns == 0) return fill_empty(offsets);
   if ((np > 0 && (!mz || !intensity || !charge)) || !precursor_mz || !info || (nd > 0 && !deferred))
     return fail(ASL_ERR_INVALID, "sptxt_fill: a null output");
   ASL_TRY(ensure_device());
@@ -637,13 +543,5 @@ extern "C" int asl_sptxt_fill(const uint8_t *text, int64_t n, int32_t *offsets, 
                      W.flags.p, W.dflag.p, W.val.p, W.dslot.p, W.first_line.p, W.peak_begin.p, W.pmz_line.p,
                      W.parent_line.p, W.mods_line.p, W.decoy.p, ns, np, nd, oOff.d, oPmz.d, oInfo.d, oRec.d);
   ASL_CHECK_LAUNCH();
-  ASL_TRY(oOff.finish());
-  ASL_TRY(oMz.finish());
-  ASL_TRY(oIt.finish());
-  ASL_TRY(oChg.finish());
-  ASL_TRY(oPmz.finish());
-  ASL_TRY(oInfo.finish());
-  ASL_TRY(oRec.finish());
-  ASL_TRY(sync_stream());
-  return ASL_OK;
+  return finish_outputs(oOff, oMz, oIt, oChg, oPmz, oInfo, oRec);
 }

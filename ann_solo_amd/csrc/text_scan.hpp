@@ -1,5 +1,7 @@
 // text_scan.hpp -- what the text readers share (mgf.hip, sptxt.hip): the block scan and its reduce / apply kernels,
 // the line-start pass over a chunk of text, the blanks of bytes.strip, and the host's scan drivers. gfx950 only.
+// What the two share about records -- counts, stores, the host's measure and fill -- is text_records.hpp, which
+// includes this header.
 //
 // Every scan is reduce -> scan of the block partials (recursively) -> apply, as separate launches on the library's
 // stream: no kernel waits on another workgroup. Everything here has internal linkage: each translation unit that

@@ -6,16 +6,14 @@ records -- without a Python object per spectrum or per peak: the text is uploade
 classified and converted by the kernels of ``csrc/mgf.hip`` (``asl_mgf_measure`` / ``asl_mgf_fill`` /
 ``asl_mgf_sort``), and the raw pack goes to the existing ``process_spectra`` where it lies. The host's part: the
 header (a few lines before the first ``BEGIN IONS``), the few numerals the device defers (Python's ``float``),
-the identifiers (UTF-8 slices of the chunk) and the meta records.
+the identifiers (UTF-8 slices of the chunk) and the meta records. The chunk loop and what else is not about the
+dialect is ``text_reader.ChunkedReader``, shared with ``sptxt.py``; the sort is ``csrc/peak_sort.hip``.
 
 The dialect is stated in ``include/annsolo_mi.h`` and restated in ``tests/mgf_ref.py``. pyteomics is not a
 dependency: the statement is unpinned, like FAISS and spectrum_utils elsewhere in this package.
 """
 import ctypes as C
-import io
 import logging
-import math
-import os
 import re
 import time
 from typing import Dict, List, Optional
@@ -25,14 +23,12 @@ import torch
 
 from . import _lib
 from .packed import PackedSpectra
+from .text_reader import MAX_CHUNK, N_DEFERRED, N_PEAKS, N_RECORDS, OPEN, ChunkedReader, _float, opt
 
 SCAN_TILE = _lib.MGF_TILE           # lines per workgroup of the reader's scans (ASL_MGF_TILE)
 MAX_PEAKS = _lib.MGF_MAX_PEAKS      # peak lines of one spectrum (ASL_MGF_MAX_PEAKS)
-MAX_CHUNK = (1 << 31) - 1           # bytes of one chunk: the ABI's limit
 PROCESS_ROWS = 1 << 17              # spectra per ``process_spectra`` call
 
-# counts[] of asl_mgf_measure
-_N_LINES, _N_SPECTRA, _N_PEAKS, _N_DEFERRED, _CONSUMED, _CONSUMED_LINES, _ERR_KIND, _ERR_LINE, _OPEN = range(9)
 _DEST_MZ, _DEST_INTENSITY, _DEST_PEPMASS, _DEST_RT, _DEST_NONE = range(5)
 _ERR_TEXT = {1: 'BEGIN IONS inside a block', 2: 'a peak line with one token'}
 _COMMENT = (b'#', b';', b'!', b'/')
@@ -71,96 +67,58 @@ class _Header:
                 self.params[k.lower()] = v.strip()
 
 
-def _float(token: bytes):
-    """(value, None) or (None, reason)."""
-    try:
-        v = float(token)
-    except ValueError:
-        return None, f'{token!r} is not a number'
-    if not math.isfinite(v):
-        return None, f'non-finite {token!r}'
-    return v, None
+class _Reader(ChunkedReader):
+    PREFIX, RECORD, COUNT_KEY, ERR_TEXT = 'MGF: ', 'a block of spectrum', 'n_spectra', _ERR_TEXT
 
-
-class _Reader:
     def __init__(self, config, device, stats: Optional[dict], keep_raw: bool = False):
         from .config import Config
+        super().__init__(device, stats)
         self.config = Config.from_reference(config)
         self.raw = [] if keep_raw else None     # the chunks' raw packs instead of the preprocessing
-        self.device = torch.device(device)
-        self.timed = stats is not None      # only then are the parts synchronised for their timers
-        self.stats = stats if stats is not None else {}
-        self.stats.update(chunks=0, n_lines=0, n_spectra=0, n_peaks=0, n_deferred=0, n_sorted=0, grown=0,
-                          read_s=0.0, parse_s=0.0, process_s=0.0)
         self.header = _Header()
-        self.line0 = 0                      # lines of the file before the chunk
-        self.spec0 = 0                      # spectra of the file before the chunk
         self.pieces: Dict[int, List[PackedSpectra]] = {}
         self.metas: Dict[int, List[dict]] = {}
 
     # ------------------------------------------------------------------ one chunk
     def measure(self, text: torch.Tensor, n: int, last: bool) -> np.ndarray:
         counts = np.zeros(16, np.int64)
-        _lib.check(_lib.lib().asl_mgf_measure(_lib.ptr(text) if n else None, n, int(last),
-                                              counts.ctypes.data_as(_lib.c_i64p)))
+        _lib.check(_lib.lib().asl_mgf_measure(_lib.ptr(text), n, int(last), counts.ctypes.data_as(_lib.c_i64p)))
         return counts
+
+    def before_chunk(self, buf: bytearray, consumed: int, counts: np.ndarray, last: bool) -> None:
+        if last and counts[OPEN]:
+            logging.warning('MGF: the last block is not closed at the end of the file: dropped')
+        self.header.feed(buf, consumed)
 
     def chunk(self, buf: bytearray, text: torch.Tensor, counts: np.ndarray, end_line: int) -> None:
         """Fill, patch, sort and preprocess the closed blocks of the measured chunk ``buf`` (``text`` on the
         device). ``end_line``: the lines of the chunk this call consumes."""
         dev, n = self.device, len(buf)
-        ns, npk, nd = int(counts[_N_SPECTRA]), int(counts[_N_PEAKS]), int(counts[_N_DEFERRED])
-        errors = []                         # (line or surrogate, 0 line-level | 1 block-level, message)
-        if counts[_ERR_KIND]:
-            ln = int(counts[_ERR_LINE])
-            errors.append((ln, 0, f'line {self.line0 + ln + 1}: {_ERR_TEXT[int(counts[_ERR_KIND])]}'))
+        ns, npk, nd = int(counts[N_RECORDS]), int(counts[N_PEAKS]), int(counts[N_DEFERRED])
+        errors = self.structural_errors(counts)
         if ns == 0 and nd == 0:
             self._raise_first(errors)
             return
         t0 = time.perf_counter()
-        offsets = torch.empty(ns + 1, dtype=torch.int32, device=dev)
-        mz = torch.empty(npk, dtype=torch.float32, device=dev)
-        it = torch.empty(npk, dtype=torch.float32, device=dev)
-        chg = torch.empty(npk, dtype=torch.uint8, device=dev)
-        pmz = torch.empty(ns, dtype=torch.float64, device=dev)
+        offsets, mz, it, chg, pmz, rec = self.columns(ns, npk, nd)
         pz = torch.empty(ns, dtype=torch.int32, device=dev)
         rt = torch.empty(ns, dtype=torch.float64, device=dev)
         ident = torch.empty((ns, 2), dtype=torch.int32, device=dev)
         first = torch.empty(ns, dtype=torch.int32, device=dev)
-        rec = torch.empty((nd, 5), dtype=torch.int32, device=dev)
-        opt = lambda a: _lib.ptr(a) if a.numel() else None
         _lib.check(_lib.lib().asl_mgf_fill(_lib.ptr(text), n, _lib.ptr(offsets), opt(mz), opt(it), opt(chg),
                                            opt(pmz), opt(pz), opt(rt), opt(ident), opt(first), opt(rec)))
         pmz_h, pz_h, rt_h = pmz.cpu().numpy(), pz.cpu().numpy(), rt.cpu().numpy()
         ident_h, first_h = ident.cpu().numpy(), first.cpu().numpy()
-        # block-level errors stand at the line behind their block
-        behind = np.append(first_h[1:], end_line).astype(np.int64)
-        # the few tokens the device defers: Python's float(), stored before the sort and the pack
+        behind = self.behind(first_h, end_line)
+
+        def block_numeral(kind, idx, v, why):           # a PEPMASS or RTINSECONDS numeral the device deferred
+            what = 'pepmass' if kind == _DEST_PEPMASS else 'rtinseconds'
+            if why:
+                errors.append((int(behind[idx]), 1, f'spectrum {self.rec0 + idx + 1}: {what} {why}'))
+                v = 0.0
+            (pmz_h if kind == _DEST_PEPMASS else rt_h)[idx] = v
         if nd:
-            slots = {_DEST_MZ: ([], []), _DEST_INTENSITY: ([], [])}      # kind -> (peak slots, values)
-            for o, l, kind, idx, ln in rec.cpu().numpy().tolist():
-                if kind == _DEST_NONE:
-                    continue
-                v, why = _float(bytes(buf[o:o + l]))
-                if kind in (_DEST_MZ, _DEST_INTENSITY):
-                    if why:
-                        what = 'm/z' if kind == _DEST_MZ else 'intensity'
-                        errors.append((ln, 0, f'line {self.line0 + ln + 1}: {what} {why}'))
-                    elif idx < npk:         # (beyond: the unclosed last block, checked and dropped)
-                        slots[kind][0].append(idx)
-                        slots[kind][1].append(v)
-                else:
-                    what = 'pepmass' if kind == _DEST_PEPMASS else 'rtinseconds'
-                    if why:
-                        errors.append((int(behind[idx]), 1, f'spectrum {self.spec0 + idx + 1}: {what} {why}'))
-                        v = 0.0
-                    (pmz_h if kind == _DEST_PEPMASS else rt_h)[idx] = v
-            for kind, column in ((_DEST_MZ, mz), (_DEST_INTENSITY, it)):
-                if slots[kind][0]:
-                    with np.errstate(over='ignore'):        # (a finite double beyond float32 is inf there)
-                        v32 = np.asarray(slots[kind][1], np.float64).astype(np.float32)
-                    column[torch.as_tensor(slots[kind][0], dtype=torch.int64, device=dev)] = \
-                        torch.as_tensor(v32, device=dev)
+            self.patch_deferred(buf, rec, mz, it, _DEST_NONE, errors, block_numeral)
         if ns == 0:                         # nothing but an unclosed last block
             self._raise_first(errors)
             return
@@ -172,26 +130,26 @@ class _Reader:
             tok = hp.get(b'pepmass', None)
             if tok is None:
                 s = int(np.argmax(missing))
-                errors.append((int(behind[s]), 1, f'spectrum {self.spec0 + s + 1}: no PEPMASS'))
+                errors.append((int(behind[s]), 1, f'spectrum {self.rec0 + s + 1}: no PEPMASS'))
             else:
                 first_tok = tok.split()
                 v, why = _float(first_tok[0] if first_tok else b'')
                 if why:
                     s = int(np.argmax(missing))
-                    errors.append((int(behind[s]), 1, f'spectrum {self.spec0 + s + 1}: pepmass {why}'))
+                    errors.append((int(behind[s]), 1, f'spectrum {self.rec0 + s + 1}: pepmass {why}'))
                     v = 0.0
                 pmz_h[missing] = v
         if b'charge' in hp and (pz_h == 0).any():
             pz_h[pz_h == 0] = _header_charge(hp[b'charge'])
         if (pz_h < 0).any():
             s = int(np.argmax(pz_h < 0))
-            errors.append((int(behind[s]), 1, f'spectrum {self.spec0 + s + 1}: charge outside 1 .. 255'))
+            errors.append((int(behind[s]), 1, f'spectrum {self.rec0 + s + 1}: charge outside 1 .. 255'))
         rt_none = np.isnan(rt_h)
         if b'rtinseconds' in hp and rt_none.any():
             v, why = _float(hp[b'rtinseconds'])
             if why:
                 s = int(np.argmax(rt_none))
-                errors.append((int(behind[s]), 1, f'spectrum {self.spec0 + s + 1}: rtinseconds {why}'))
+                errors.append((int(behind[s]), 1, f'spectrum {self.rec0 + s + 1}: rtinseconds {why}'))
             else:
                 rt_h[rt_none] = v
                 rt_none = np.zeros(ns, bool)
@@ -206,24 +164,7 @@ class _Reader:
             self.raw.append((raw, np.where(rt_none, np.nan, rt_h), ids))
         else:
             self._preprocess(raw, pz_h, pmz_h, rt_h, rt_none, ids)
-        self._sync()
-        st = self.stats
-        st['parse_s'] += t1 - t0
-        st['process_s'] += time.perf_counter() - t1
-        st['n_spectra'] += ns
-        st['n_peaks'] += npk
-        st['n_deferred'] += nd
-        st['n_sorted'] += int(n_sorted.value)
-
-    def _sync(self) -> None:
-        """The timers of ``stats`` want finished work; without a caller's ``stats`` nothing waits here."""
-        if self.timed and self.device.type == 'cuda':
-            torch.cuda.synchronize(self.device)
-
-    @staticmethod
-    def _raise_first(errors) -> None:
-        if errors:
-            raise ValueError('MGF: ' + min(errors, key=lambda e: (e[0], e[1]))[2])
+        self.account(t0, t1, ns, npk, nd, int(n_sorted.value))
 
     def _identifiers(self, buf, ident_h, hp, errors, behind) -> List[Optional[str]]:
         """title, else scan, of the block over the header's: the identifiers as str."""
@@ -240,7 +181,7 @@ class _Reader:
             elif h_title is not None or h_scan is not None:
                 ids.append((h_title if h_title is not None else h_scan).decode('utf-8'))
             else:
-                errors.append((int(behind[s]), 1, f'spectrum {self.spec0 + s + 1}: neither TITLE nor SCAN'))
+                errors.append((int(behind[s]), 1, f'spectrum {self.rec0 + s + 1}: neither TITLE nor SCAN'))
                 ids.append(None)
         return ids
 
@@ -271,62 +212,9 @@ class _Reader:
                 self.pieces.setdefault(c, []).append(out.select(torch.as_tensor(sel)).to('cpu'))
                 meta = self.metas.setdefault(c, [])
                 for s in r[sel].tolist():
-                    meta.append(dict(identifier=ids[s], index=self.spec0 + s + 1,
+                    meta.append(dict(identifier=ids[s], index=self.rec0 + s + 1,
                                      retention_time=None if rt_none[s] else float(rt_h[s]),
                                      precursor_charge=c, precursor_mz=float(pmz_h[s])))
-
-    # ------------------------------------------------------------------ the file
-    def read(self, f, chunk_bytes: int) -> None:
-        size = max(int(chunk_bytes), 1)
-        if size > MAX_CHUNK:
-            raise ValueError(f'chunk_bytes = {chunk_bytes}: at most {MAX_CHUNK}')
-        buf, eof = bytearray(), False
-        while True:
-            t0 = time.perf_counter()
-            want = size - len(buf)
-            if want > 0 and not eof:
-                more = f.read(want)
-                eof = len(more) < want
-                buf += more
-            n, last = len(buf), eof
-            if n == 0:
-                break
-            t1 = time.perf_counter()
-            text = torch.frombuffer(buf, dtype=torch.uint8).to(self.device)
-            counts = self.measure(text, n, last)        # (returns synchronised)
-            self.stats['read_s'] += t1 - t0
-            self.stats['parse_s'] += time.perf_counter() - t1
-            n_lines = int(counts[_N_LINES])
-            if last:
-                consumed, end_line = n, n_lines
-                if counts[_OPEN]:
-                    logging.warning('MGF: the last block is not closed at the end of the file: dropped')
-            elif counts[_OPEN]:
-                consumed, end_line = int(counts[_CONSUMED]), int(counts[_CONSUMED_LINES])
-            elif buf.endswith(b'\n'):
-                consumed, end_line = n, n_lines
-            else:                           # a cut last line: it may be the start of a BEGIN IONS
-                consumed, end_line = buf.rfind(b'\n') + 1, n_lines - 1
-            if consumed == 0 and not last:  # one block (or line) does not fit: a larger chunk
-                if size >= MAX_CHUNK:
-                    err = _lib.AnnSoloMiError(f'MGF: a block of spectrum {self.spec0 + 1} does not fit a chunk of '
-                                              f'{MAX_CHUNK} bytes')
-                    err.code = _lib.ERR_CAPACITY
-                    raise err
-                size = min(2 * size, MAX_CHUNK)
-                self.stats['grown'] += 1
-                del text
-                continue
-            self.header.feed(buf, consumed)
-            self.chunk(buf, text, counts, end_line)
-            self.stats['chunks'] += 1
-            self.stats['n_lines'] += end_line
-            self.line0 += end_line
-            self.spec0 += int(counts[_N_SPECTRA])
-            del text
-            del buf[:consumed]
-            if last:
-                break
 
     def result(self):
         from .library_store import concat_packs
@@ -338,14 +226,6 @@ class _Reader:
         return packs, self.metas
 
 
-def _read(reader: _Reader, source, chunk_bytes: int) -> None:
-    if isinstance(source, (str, os.PathLike)):
-        with open(source, 'rb') as f:
-            reader.read(f, chunk_bytes)
-    else:
-        reader.read(io.BytesIO(bytes(source)), chunk_bytes)
-
-
 def read_mgf_raw(source, device='cuda', chunk_bytes: int = 256 << 20, stats: Optional[dict] = None):
     """The parse alone: ``(raw, retention_time, identifiers)`` -- the file's spectra as one raw
     ``PackedSpectra`` on ``device`` (what ``library_store.pack_raw`` makes of the reader's objects: float32
@@ -353,7 +233,7 @@ def read_mgf_raw(source, device='cuda', chunk_bytes: int = 256 << 20, stats: Opt
     times (float64 numpy, NaN = none) and the identifiers. Arguments and errors as ``read_mgf_packed``."""
     from .library_store import concat_packs
     reader = _Reader(None, device, stats, keep_raw=True)
-    _read(reader, source, chunk_bytes)
+    reader.read_source(source, chunk_bytes)
     if not reader.raw:
         z = lambda dt: torch.zeros(0, dtype=dt, device=reader.device)
         return (PackedSpectra(torch.zeros(1, dtype=torch.int32, device=reader.device), z(torch.float32),
@@ -377,5 +257,5 @@ def read_mgf_packed(source, config=None, device='cuda', chunk_bytes: int = 256 <
     ``AnnSoloMiError`` with ``code == ERR_CAPACITY`` (before the ``ValueError``s of the same chunk). An unclosed
     last block is dropped with a warning; a deviation on one of its lines is reported like any other."""
     reader = _Reader(config, device, stats)
-    _read(reader, source, chunk_bytes)
+    reader.read_source(source, chunk_bytes)
     return reader.result()

@@ -7,15 +7,14 @@ Python object per spectrum or per peak and without the reference package: the te
 into lines, classified and converted by the kernels of ``csrc/sptxt.hip`` (``asl_sptxt_measure`` /
 ``asl_sptxt_fill``, then ``asl_mgf_sort_charged``), and the raw pack goes to the existing ``process_spectra`` where
 it lies. The host's part: the few numerals the device defers (Python's ``float``), the peptide strings (``proforma``,
-from byte ranges the device returns), the checks a whole record must pass and the meta records.
+from byte ranges the device returns), the checks a whole record must pass and the meta records. The chunk loop and
+what else is not about the dialect is ``text_reader.ChunkedReader``, shared with ``mgf.py``.
 
 The dialect is stated in ``include/annsolo_mi.h`` and restated in ``tests/sptxt_ref.py``. pyteomics and
 spectrum_utils are not dependencies: the statement is unpinned, like the MGF reader's.
 """
 import ctypes as C
-import io
 import logging
-import math
 import os
 import re
 import time
@@ -26,14 +25,12 @@ import torch
 
 from . import _lib
 from .packed import PackedSpectra
+from .text_reader import MAX_CHUNK, N_DEFERRED, N_PEAKS, N_RECORDS, ChunkedReader, opt
 
 MAX_PEAKS = _lib.MGF_MAX_PEAKS      # peak lines of one record (ASL_MGF_MAX_PEAKS)
-MAX_CHUNK = (1 << 31) - 1           # bytes of one chunk: the ABI's limit
 PROCESS_ROWS = 1 << 15              # spectra per ``process_spectra`` call
 READER_VERSION = 1                  # in the packed store's key (``library_store.store_hash``)
 
-# counts[] of asl_sptxt_measure
-_N_LINES, _N_RECORDS, _N_PEAKS, _N_DEFERRED, _CONSUMED, _CONSUMED_LINES, _ERR_KIND, _ERR_LINE, _OPEN = range(9)
 _DEST_MZ, _DEST_INTENSITY, _DEST_PRECURSOR, _DEST_NONE = range(4)
 _INFO = 8                           # ASL_SPTXT_INFO
 _ERR_TEXT = {1: 'a second Name: in the line', 2: 'a second Num Peaks line in the record',
@@ -72,88 +69,43 @@ def proforma(peptide: str, mods: Optional[str]) -> str:
     return ''.join(out)
 
 
-def _float(token: bytes):
-    """(value, None) or (None, reason)."""
-    try:
-        v = float(token)
-    except ValueError:
-        return None, f'{token!r} is not a number'
-    if not math.isfinite(v):
-        return None, f'non-finite {token!r}'
-    return v, None
+class _Reader(ChunkedReader):
+    PREFIX, RECORD, COUNT_KEY, ERR_TEXT = 'sptxt: ', 'record', 'n_records', _ERR_TEXT
 
-
-class _Reader:
     def __init__(self, device, stats: Optional[dict]):
-        self.device = torch.device(device)
-        self.timed = stats is not None      # only then are the parts synchronised for their timers
-        self.stats = stats if stats is not None else {}
-        self.stats.update(chunks=0, n_lines=0, n_records=0, n_peaks=0, n_deferred=0, n_sorted=0, grown=0,
-                          read_s=0.0, parse_s=0.0, process_s=0.0)
-        self.line0 = 0                      # lines of the file before the chunk
-        self.rec0 = 0                       # records of the file before the chunk
+        super().__init__(device, stats)
         self.sink = None                    # called with (raw pack on the device, columns) per chunk
 
-    def _sync(self) -> None:
-        if self.timed and self.device.type == 'cuda':
-            torch.cuda.synchronize(self.device)
-
-    @staticmethod
-    def _raise_first(errors) -> None:
-        if errors:
-            raise ValueError('sptxt: ' + min(errors, key=lambda e: (e[0], e[1]))[2])
+    def measure(self, text: torch.Tensor, n: int, last: bool) -> np.ndarray:
+        counts = np.zeros(16, np.int64)
+        _lib.check(_lib.lib().asl_sptxt_measure(_lib.ptr(text), n, int(last), counts.ctypes.data_as(_lib.c_i64p)))
+        return counts
 
     def chunk(self, buf: bytearray, text: torch.Tensor, counts: np.ndarray, end_line: int) -> None:
         """Fill, patch, check and sort the closed records of the measured chunk ``buf`` (``text`` on the device),
         then hand them to the sink. ``end_line``: the lines of the chunk this call consumes."""
         dev, n = self.device, len(buf)
-        ns, npk, nd = int(counts[_N_RECORDS]), int(counts[_N_PEAKS]), int(counts[_N_DEFERRED])
-        errors = []                         # (line or surrogate, 0 line-level | 1 record-level, message)
-        if counts[_ERR_KIND]:
-            ln = int(counts[_ERR_LINE])
-            errors.append((ln, 0, f'line {self.line0 + ln + 1}: {_ERR_TEXT[int(counts[_ERR_KIND])]}'))
+        ns, npk, nd = int(counts[N_RECORDS]), int(counts[N_PEAKS]), int(counts[N_DEFERRED])
+        errors = self.structural_errors(counts)
         if ns == 0:
             self._raise_first(errors)
             return
         t0 = time.perf_counter()
-        offsets = torch.empty(ns + 1, dtype=torch.int32, device=dev)
-        mz = torch.empty(npk, dtype=torch.float32, device=dev)
-        it = torch.empty(npk, dtype=torch.float32, device=dev)
-        chg = torch.empty(npk, dtype=torch.uint8, device=dev)
-        pmz = torch.empty(ns, dtype=torch.float64, device=dev)
+        offsets, mz, it, chg, pmz, rec = self.columns(ns, npk, nd)
         info = torch.empty((ns, _INFO), dtype=torch.int32, device=dev)
-        rec = torch.empty((nd, 5), dtype=torch.int32, device=dev)
-        opt = lambda a: _lib.ptr(a) if a.numel() else None
         _lib.check(_lib.lib().asl_sptxt_fill(_lib.ptr(text), n, _lib.ptr(offsets), opt(mz), opt(it), opt(chg),
                                              _lib.ptr(pmz), _lib.ptr(info), opt(rec)))
         pmz_h, info_h, off_h = pmz.cpu().numpy(), info.cpu().numpy(), offsets.cpu().numpy()
-        first_h = info_h[:, 7]
-        # record-level errors stand at the line behind their record
-        behind = np.append(first_h[1:], end_line).astype(np.int64)
+        behind = self.behind(info_h[:, 7], end_line)
         bad_pmz = {}                        # record -> why its deferred precursor numeral was refused
+
+        def precursor_numeral(kind, idx, v, why):       # (_DEST_PRECURSOR: a record's only deferred numeral)
+            if why:
+                bad_pmz[idx] = why
+            else:
+                pmz_h[idx] = v
         if nd:
-            slots = {_DEST_MZ: ([], []), _DEST_INTENSITY: ([], [])}      # kind -> (peak slots, values)
-            for o, l, kind, idx, ln in rec.cpu().numpy().tolist():
-                if kind == _DEST_NONE:
-                    continue
-                v, why = _float(bytes(buf[o:o + l]))
-                if kind == _DEST_PRECURSOR:
-                    if why:
-                        bad_pmz[idx] = why
-                    else:
-                        pmz_h[idx] = v
-                elif why:
-                    what = 'm/z' if kind == _DEST_MZ else 'intensity'
-                    errors.append((ln, 0, f'line {self.line0 + ln + 1}: {what} {why}'))
-                else:
-                    slots[kind][0].append(idx)
-                    slots[kind][1].append(v)
-            for kind, column in ((_DEST_MZ, mz), (_DEST_INTENSITY, it)):
-                if slots[kind][0]:
-                    with np.errstate(over='ignore'):        # (a finite double beyond float32 is inf there)
-                        v32 = np.asarray(slots[kind][1], np.float64).astype(np.float32)
-                    column[torch.as_tensor(slots[kind][0], dtype=torch.int64, device=dev)] = \
-                        torch.as_tensor(v32, device=dev)
+            self.patch_deferred(buf, rec, mz, it, _DEST_NONE, errors, precursor_numeral)
         # what a whole record must satisfy, in the order the restatement checks it; the first failure ends the look
         peptides: List[Optional[str]] = [None] * ns
         view = memoryview(buf)
@@ -195,72 +147,7 @@ class _Reader:
         t1 = time.perf_counter()
         self.sink(raw, dict(identifier=ids, peptide=peptides, precursor_mz=pmz_h, precursor_charge=pz_h,
                             is_decoy=info_h[:, 2].astype(bool)))
-        self._sync()
-        st = self.stats
-        st['parse_s'] += t1 - t0
-        st['process_s'] += time.perf_counter() - t1
-        st['n_records'] += ns
-        st['n_peaks'] += npk
-        st['n_deferred'] += nd
-        st['n_sorted'] += int(n_sorted.value)
-
-    # ------------------------------------------------------------------ the file
-    def read(self, f, chunk_bytes: int) -> None:
-        size = max(int(chunk_bytes), 1)
-        if size > MAX_CHUNK:
-            raise ValueError(f'chunk_bytes = {chunk_bytes}: at most {MAX_CHUNK}')
-        buf, eof = bytearray(), False
-        while True:
-            t0 = time.perf_counter()
-            want = size - len(buf)
-            if want > 0 and not eof:
-                more = f.read(want)
-                eof = len(more) < want
-                buf += more
-            n, last = len(buf), eof
-            if n == 0:
-                break
-            t1 = time.perf_counter()
-            text = torch.frombuffer(buf, dtype=torch.uint8).to(self.device)
-            counts = np.zeros(16, np.int64)
-            _lib.check(_lib.lib().asl_sptxt_measure(_lib.ptr(text), n, int(last),      # (returns synchronised)
-                                                    counts.ctypes.data_as(_lib.c_i64p)))
-            self.stats['read_s'] += t1 - t0
-            self.stats['parse_s'] += time.perf_counter() - t1
-            n_lines = int(counts[_N_LINES])
-            if last or counts[_OPEN]:
-                consumed, end_line = int(counts[_CONSUMED]), int(counts[_CONSUMED_LINES])
-            elif buf.endswith(b'\n'):       # no record yet: the preamble's whole lines
-                consumed, end_line = n, n_lines
-            else:                           # a cut last line: it may be the start of a Name line
-                consumed, end_line = buf.rfind(b'\n') + 1, n_lines - 1
-            if consumed == 0 and not last:  # one record (or line) does not fit: a larger chunk
-                if size >= MAX_CHUNK:
-                    err = _lib.AnnSoloMiError(f'sptxt: record {self.rec0 + 1} does not fit a chunk of '
-                                              f'{MAX_CHUNK} bytes')
-                    err.code = _lib.ERR_CAPACITY
-                    raise err
-                size = min(2 * size, MAX_CHUNK)
-                self.stats['grown'] += 1
-                del text
-                continue
-            self.chunk(buf, text, counts, end_line)
-            self.stats['chunks'] += 1
-            self.stats['n_lines'] += end_line
-            self.line0 += end_line
-            self.rec0 += int(counts[_N_RECORDS])
-            del text
-            del buf[:consumed]
-            if last:
-                break
-
-
-def _read(reader: _Reader, source, chunk_bytes: int) -> None:
-    if isinstance(source, (str, os.PathLike)):
-        with open(source, 'rb') as f:
-            reader.read(f, chunk_bytes)
-    else:
-        reader.read(io.BytesIO(bytes(source)), chunk_bytes)
+        self.account(t0, t1, ns, npk, nd, int(n_sorted.value))
 
 
 def read_sptxt_raw(source, device='cuda', chunk_bytes: int = 256 << 20, stats: Optional[dict] = None):
@@ -278,7 +165,7 @@ def read_sptxt_raw(source, device='cuda', chunk_bytes: int = 256 << 20, stats: O
     reader = _Reader(device, stats)
     packs, cols = [], []
     reader.sink = lambda raw, c: (packs.append(raw), cols.append(c))
-    _read(reader, source, chunk_bytes)
+    reader.read_source(source, chunk_bytes)
     return packs, _join_columns(cols)
 
 
@@ -353,7 +240,7 @@ def build_store(source, config=None, device='cuda', chunk_bytes: int = 256 << 20
         cols.append(c)
 
     reader.sink = sink
-    _read(reader, source, chunk_bytes)
+    reader.read_source(source, chunk_bytes)
     c = _join_columns(cols)
     n = len(c['identifier'])
     pz = c['precursor_charge']
