@@ -62,6 +62,19 @@ int sync_stream() {
   return ASL_OK;
 }
 
+int cu_count(int *cus) {
+  static int cached = 0;
+  if (cached == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipGetDeviceProperties(&prop, dev));
+    cached = std::max(1, prop.multiProcessorCount);
+  }
+  *cus = cached;
+  return ASL_OK;
+}
+
 StreamScope::StreamScope(hipStream_t s) : prev(g_stream) { g_stream = s; }
 StreamScope::~StreamScope() { g_stream = prev; }
 

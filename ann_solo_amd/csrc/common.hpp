@@ -137,13 +137,15 @@ struct Out {
     return ASL_OK;
   }
   bool to_host() const { return host != nullptr; }
-  int finish() {  // enqueue the copy-back (caller synchronises once at the end)
-    if (host && n) HIP_TRY(hipMemcpyAsync(host, d, n * sizeof(T), hipMemcpyDeviceToHost, stream()));
+  int finish(size_t count) {  // enqueue the copy-back of the first count elements (caller synchronises at the end)
+    if (host && count) HIP_TRY(hipMemcpyAsync(host, d, count * sizeof(T), hipMemcpyDeviceToHost, stream()));
     return ASL_OK;
   }
+  int finish() { return finish(n); }
 };
 
 int sync_stream();
+int cu_count(int *cus);   // compute units of the current device, >= 1 (asked once per process)
 
 // Work issued inside the scope goes to `s` (every kernel launch reads stream()).
 struct StreamScope {

@@ -20,7 +20,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.hpp"
+#include "fit_args.hpp"
 
 namespace asl {
 
@@ -311,27 +311,10 @@ struct ForestWork {
   DevBuf<uint16_t> state;
   DevBuf<double> cw, edges;
   DevBuf<int32_t> n_edges;
-  int cus = 0;
 };
 ForestWork &fwork() {
   static ForestWork w;
   return w;
-}
-
-template <class T>
-int fo_copy_in(std::vector<T> &h, const T *src, size_t n) {   // host copy of an array on either side
-  h.resize(n);
-  if (n) HIP_TRY(hipMemcpy(h.data(), src, n * sizeof(T), hipMemcpyDefault));
-  return ASL_OK;
-}
-
-int fo_check_shape(const char *who, int64_t n, int32_t d, int32_t P) {
-  if (d < 1 || P < 1 || n < 0 || n >= (1ll << 31))
-    return fail(ASL_ERR_INVALID, "%s: needs d >= 1, P >= 1, 0 <= n < 2^31", who);
-  if (d > ASL_SVM_MAX_DIM) return fail(ASL_ERR_CAPACITY, "%s: d = %d, at most %d", who, d, ASL_SVM_MAX_DIM);
-  if (P > ASL_SVM_MAX_PROBLEMS)
-    return fail(ASL_ERR_CAPACITY, "%s: P = %d, at most %d", who, P, ASL_SVM_MAX_PROBLEMS);
-  return ASL_OK;
 }
 
 int fo_mtry(int d) {
@@ -379,12 +362,12 @@ extern "C" int64_t asl_set_forest_workspace(int64_t bytes) {
 extern "C" int asl_forest_bin(const double *X, int64_t n, int32_t d, const double *edges, const int32_t *n_edges,
                               uint8_t *out) {
   clear_error();
-  ASL_TRY(fo_check_shape("forest_bin", n, d, 1));
+  ASL_TRY(check_shape("forest_bin", n, d, 1, true));
   if (!edges || !n_edges) return fail(ASL_ERR_INVALID, "forest_bin: null edges / n_edges");
   if (n > 0 && (!X || !out)) return fail(ASL_ERR_INVALID, "forest_bin: null X / out");
   ASL_TRY(ensure_device());
   std::vector<int32_t> h_ne;
-  ASL_TRY(fo_copy_in(h_ne, n_edges, (size_t)d));
+  ASL_TRY(host_copy(h_ne, n_edges, (size_t)d));
   for (int j = 0; j < d; ++j)
     if (h_ne[j] < 0 || h_ne[j] > ASL_FOREST_MAX_BINS - 1)
       return fail(ASL_ERR_INVALID, "forest_bin: n_edges[%d] = %d, not in 0 .. %d", j, h_ne[j],
@@ -414,7 +397,7 @@ extern "C" int asl_forest_fit(const uint8_t *bins, int64_t n, int32_t d, const i
   clear_error();
   if (!cw || !params || !model || !model->col || !model->bin || !model->n0 || !model->n1 || !model->value)
     return fail(ASL_ERR_INVALID, "forest_fit: null argument");
-  ASL_TRY(fo_check_shape("forest_fit", n, d, P));
+  ASL_TRY(check_shape("forest_fit", n, d, P, true));
   const int T = params->trees, D = params->max_depth;
   if (T > ASL_FOREST_MAX_TREES) return fail(ASL_ERR_CAPACITY, "forest_fit: trees = %d, at most %d", T, ASL_FOREST_MAX_TREES);
   if (D > ASL_FOREST_MAX_DEPTH)
@@ -423,49 +406,30 @@ extern "C" int asl_forest_fit(const uint8_t *bins, int64_t n, int32_t d, const i
   if (n > 0 && (!bins || !label)) return fail(ASL_ERR_INVALID, "forest_fit: null bins / label");
   ASL_TRY(ensure_device());
   std::vector<double> h_cw;
-  ASL_TRY(fo_copy_in(h_cw, cw, (size_t)P * 2));
-  for (double v : h_cw)
-    if (!(v >= 0.0) || !std::isfinite(v))
-      return fail(ASL_ERR_INVALID, "forest_fit: class weights must be finite and >= 0");
+  ASL_TRY(host_copy(h_cw, cw, (size_t)P * 2));
+  ASL_TRY(check_class_weights("forest_fit", h_cw));
   std::vector<int32_t> h_nb(d, ASL_FOREST_MAX_BINS);
-  if (n_bins) ASL_TRY(fo_copy_in(h_nb, n_bins, (size_t)d));
+  if (n_bins) ASL_TRY(host_copy(h_nb, n_bins, (size_t)d));
   for (int j = 0; j < d; ++j)
     if (h_nb[j] < 1 || h_nb[j] > ASL_FOREST_MAX_BINS)
       return fail(ASL_ERR_INVALID, "forest_fit: n_bins[%d] = %d, not in 1 .. %d", j, h_nb[j], ASL_FOREST_MAX_BINS);
-  {   // the labels and the bins, on the host, before anything is launched
-    std::vector<int8_t> h_label;
-    const int8_t *lp = label;
-    const size_t cnt = (size_t)P * (size_t)n;
-    if (cnt && is_device_ptr(label)) {
-      ASL_TRY(fo_copy_in(h_label, label, cnt));
-      lp = h_label.data();
+  ASL_TRY(check_labels("forest_fit", label, P, n));   // ... and the bins: on the host, before anything is launched
+  if (n_bins) {
+    std::vector<uint8_t> h_bins;
+    const uint8_t *bp = bins;
+    if (n && is_device_ptr(bins)) {
+      ASL_TRY(host_copy(h_bins, bins, (size_t)n * ASL_FOREST_ROW));
+      bp = h_bins.data();
     }
-    for (size_t i = 0; i < cnt; ++i)
-      if (lp[i] < -1 || lp[i] > 1)
-        return fail(ASL_ERR_INVALID, "forest_fit: label[%lld, %lld] = %d, not in {-1, 0, +1}", (long long)(i / n),
-                    (long long)(i % n), (int)lp[i]);
-    if (n_bins) {
-      std::vector<uint8_t> h_bins;
-      const uint8_t *bp = bins;
-      if (n && is_device_ptr(bins)) {
-        ASL_TRY(fo_copy_in(h_bins, bins, (size_t)n * ASL_FOREST_ROW));
-        bp = h_bins.data();
-      }
-      for (int64_t i = 0; i < n; ++i)
-        for (int j = 0; j < d; ++j)
-          if (bp[i * ASL_FOREST_ROW + j] >= h_nb[j])
-            return fail(ASL_ERR_INVALID, "forest_fit: bins[%lld, %d] = %d, the column has %d bins", (long long)i, j,
-                        (int)bp[i * ASL_FOREST_ROW + j], h_nb[j]);
-    }
+    for (int64_t i = 0; i < n; ++i)
+      for (int j = 0; j < d; ++j)
+        if (bp[i * ASL_FOREST_ROW + j] >= h_nb[j])
+          return fail(ASL_ERR_INVALID, "forest_fit: bins[%lld, %d] = %d, the column has %d bins", (long long)i, j,
+                      (int)bp[i * ASL_FOREST_ROW + j], h_nb[j]);
   }
   ForestWork &W = fwork();
-  if (W.cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipGetDeviceProperties(&prop, dev));
-    W.cus = std::max(1, prop.multiProcessorCount);
-  }
+  int cus = 0;
+  ASL_TRY(cu_count(&cus));
   const int mtry = fo_mtry(d);
   const int64_t pairs = (int64_t)P * T;
   const size_t total = (size_t)pairs * ASL_FOREST_NODES;
@@ -506,7 +470,7 @@ extern "C" int asl_forest_fit(const uint8_t *bins, int64_t n, int32_t d, const i
     for (int64_t q0 = 0; q0 < pairs; q0 += B) {
       A.q0 = (int32_t)q0, A.nq = (int32_t)std::min<int64_t>(B, pairs - q0);
       // pairs per workgroup: every staged row serves them all; enough workgroups to fill the chip
-      const int64_t want_y = std::min<int64_t>(A.nq, std::max<int64_t>(1, cdiv(2 * W.cus, row_blocks)));
+      const int64_t want_y = std::min<int64_t>(A.nq, std::max<int64_t>(1, cdiv(2 * cus, row_blocks)));
       A.group = (int32_t)cdiv(A.nq, want_y);
       const unsigned gy = (unsigned)cdiv(A.nq, A.group);
       for (int level = 0; level < D; ++level) {
@@ -540,7 +504,7 @@ extern "C" int asl_forest_predict(const uint8_t *bins, int64_t n, int32_t d, con
   clear_error();
   if (!model || !model->col || !model->bin || !model->n0 || !model->n1 || !model->value)
     return fail(ASL_ERR_INVALID, "forest_predict: null model");
-  ASL_TRY(fo_check_shape("forest_predict", n, d, P));
+  ASL_TRY(check_shape("forest_predict", n, d, P, true));
   const int T = model->trees;
   if (T > ASL_FOREST_MAX_TREES)
     return fail(ASL_ERR_CAPACITY, "forest_predict: trees = %d, at most %d", T, ASL_FOREST_MAX_TREES);

@@ -17,7 +17,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.hpp"
+#include "device_scan.hpp"
 
 namespace asl {
 
@@ -25,6 +25,7 @@ constexpr int GR_NT = 256;                    // threads of the per-SSM kernels 
 constexpr int GR_BINS = 100;                  // bins of an interval
 constexpr int GR_MAX_PEAKS = 49;              // strict local maxima among bins 1 .. 98
 constexpr int GR_RANGE_BLOCKS = 1024;         // most partials of the range pass
+static_assert(GR_NT == SCAN_NT, "groups_scan_kernel's rounds are block_scan's blocks");
 
 // edge i of the interval of nominal value g, as numpy.linspace(g - 0.5, g + 0.5, 101) forms it
 __device__ __forceinline__ double gr_edge(double g, int i) {
@@ -205,29 +206,15 @@ __global__ __launch_bounds__(64) void groups_peaks_kernel(const uint32_t *__rest
 __global__ __launch_bounds__(GR_NT) void groups_scan_kernel(const uint32_t *__restrict__ count, int span,
                                                             uint32_t *__restrict__ offs,
                                                             unsigned long long *__restrict__ counters) {
-  __shared__ uint32_t wave_tot[GR_NT / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint32_t carry = 0u;
   for (int base = 0; base < span; base += GR_NT) {
     const int i = base + threadIdx.x;
     const uint32_t own = i < span ? count[i] : 0u;
-    uint32_t v = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = (uint32_t)__shfl_up((int)v, d, 64);
-      if (lane >= d) v += o;
-    }
-    if (lane == 63) wave_tot[wave] = v;
-    __syncthreads();
-    uint32_t pre = 0u, all = 0u;
-#pragma unroll
-    for (int w = 0; w < GR_NT / 64; ++w) {
-      if (w < wave) pre += wave_tot[w];
-      all += wave_tot[w];
-    }
-    if (i < span) offs[i] = carry + pre + v - own;
-    carry += all;
-    __syncthreads();
+    uint32_t all;
+    const uint32_t incl = block_scan<SumU32>(own, &all);
+    if (i < span) offs[i] = carry + incl - own;
+    carry += (uint32_t)__builtin_amdgcn_readfirstlane((int)all);   // (the same in every thread: a scalar register)
+    __syncthreads();   // (the next round writes block_scan's wave totals)
   }
   if (threadIdx.x == 0) counters[0] = carry;
 }
@@ -308,9 +295,6 @@ struct GroupsWork {
   DevBuf<uint32_t> flag, hist, count, offs, size;
   DevBuf<uint8_t> trip;
   DevBuf<unsigned long long> counters;
-  DevBuf<int32_t> group;
-  DevBuf<double> mass;
-  DevBuf<int64_t> psize;
 };
 GroupsWork &work() {
   static GroupsWork w;
@@ -368,22 +352,12 @@ extern "C" int asl_ssm_groups(const double *mass_diff, int64_t n, int64_t min_gr
   ASL_TRY(W.offs.reserve((size_t)span));
   ASL_TRY(W.trip.reserve((size_t)span * GR_MAX_PEAKS * 3));
   ASL_TRY(W.size.reserve((size_t)cap));
-  const bool group_on_host = !is_device_ptr(group);
-  int32_t *d_group = group;
-  if (group_on_host) {
-    ASL_TRY(W.group.reserve((size_t)n));
-    d_group = W.group.p;
-  }
-  double *d_mass = peak_mass;
-  if (peak_mass != nullptr && !is_device_ptr(peak_mass)) {
-    ASL_TRY(W.mass.reserve((size_t)cap));
-    d_mass = W.mass.p;
-  }
-  int64_t *d_psize = peak_size;
-  if (peak_size != nullptr && !is_device_ptr(peak_size)) {
-    ASL_TRY(W.psize.reserve((size_t)cap));
-    d_psize = W.psize.p;
-  }
+  Out<int32_t> oG;
+  Out<double> oM;      // (nullptr where the masses / sizes are not asked for)
+  Out<int64_t> oS;
+  ASL_TRY(oG.init(group, (size_t)n));
+  ASL_TRY(oM.init(peak_mass, (size_t)cap));
+  ASL_TRY(oS.init(peak_size, (size_t)cap));
   HIP_TRY(hipMemsetAsync(W.hist.p, 0, (size_t)span * GR_BINS * sizeof(uint32_t), stream()));
   HIP_TRY(hipMemsetAsync(W.size.p, 0, (size_t)cap * sizeof(uint32_t), stream()));
   HIP_TRY(hipMemsetAsync(W.counters.p, 0, 3 * sizeof(unsigned long long), stream()));
@@ -396,31 +370,29 @@ extern "C" int asl_ssm_groups(const double *mass_diff, int64_t n, int64_t min_gr
                      W.counters.p);
   ASL_CHECK_LAUNCH();
   hipLaunchKernelGGL(groups_assign_kernel, dim3(n_blocks), dim3(GR_NT), 0, stream(), iM.d, n, g_min, span, W.count.p,
-                     W.offs.p, W.trip.p, cap, d_group, W.size.p);
+                     W.offs.p, W.trip.p, cap, oG.d, W.size.p);
   ASL_CHECK_LAUNCH();
-  if (d_mass != nullptr) {
+  if (oM.d != nullptr) {
     hipLaunchKernelGGL(groups_mass_kernel, dim3((unsigned)span), dim3(64), 0, stream(), g_min, W.count.p, W.offs.p,
-                       W.trip.p, cap, d_mass);
+                       W.trip.p, cap, oM.d);
     ASL_CHECK_LAUNCH();
   }
   if (min_group_size > 1) {       // (a size an id has is at least 1)
     hipLaunchKernelGGL(groups_fold_kernel, dim3(n_blocks), dim3(GR_NT), 0, stream(), n, min_group_size, W.size.p,
-                       d_group);
+                       oG.d);
     ASL_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(groups_labels_kernel, dim3((unsigned)cdiv(cap, GR_NT)), dim3(GR_NT), 0, stream(), cap,
-                     min_group_size, W.size.p, W.counters.p, d_psize);
+                     min_group_size, W.size.p, W.counters.p, oS.d);
   ASL_CHECK_LAUNCH();
   unsigned long long h_counters[3] = {0ull, 0ull, 0ull};
   HIP_TRY(hipMemcpyAsync(h_counters, W.counters.p, sizeof(h_counters), hipMemcpyDeviceToHost, stream()));
-  if (group_on_host) HIP_TRY(hipMemcpyAsync(group, d_group, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream()));
+  ASL_TRY(oG.finish());
   ASL_TRY(sync_stream());
   const size_t ids = (size_t)std::min<int64_t>((int64_t)h_counters[0], cap);
-  if (ids > 0 && d_mass != peak_mass)
-    HIP_TRY(hipMemcpyAsync(peak_mass, d_mass, ids * sizeof(double), hipMemcpyDeviceToHost, stream()));
-  if (ids > 0 && d_psize != peak_size)
-    HIP_TRY(hipMemcpyAsync(peak_size, d_psize, ids * sizeof(int64_t), hipMemcpyDeviceToHost, stream()));
-  if (ids > 0 && (d_mass != peak_mass || d_psize != peak_size)) ASL_TRY(sync_stream());
+  ASL_TRY(oM.finish(ids));      // (the ids that exist: known only now)
+  ASL_TRY(oS.finish(ids));
+  if (ids > 0 && (oM.to_host() || oS.to_host())) ASL_TRY(sync_stream());
   if (n_peaks) *n_peaks = (int64_t)ids;
   if (n_labels) *n_labels = (int64_t)h_counters[1] + ((int64_t)h_counters[2] < n ? 1 : 0);
   return ASL_OK;

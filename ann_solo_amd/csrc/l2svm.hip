@@ -19,7 +19,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.hpp"
+#include "fit_args.hpp"
 
 namespace asl {
 
@@ -290,23 +290,10 @@ struct SvmWork {
   DevBuf<double> part, sums, cw, wb, sdir;
   DevBuf<int32_t> plist;
   DevBuf<uint8_t> blk;
-  int cus = 0;
 };
 SvmWork &work() {
   static SvmWork w;
   return w;
-}
-
-template <class T>
-int copy_in(std::vector<T> &h, const T *src, size_t n) {   // host copy of an array on either side
-  h.resize(n);
-  if (n) HIP_TRY(hipMemcpy(h.data(), src, n * sizeof(T), hipMemcpyDefault));
-  return ASL_OK;
-}
-template <class T>
-int copy_out(T *dst, const std::vector<T> &h) {
-  if (!h.empty()) HIP_TRY(hipMemcpy(dst, h.data(), h.size() * sizeof(T), hipMemcpyDefault));
-  return ASL_OK;
 }
 
 struct Grid {
@@ -314,25 +301,11 @@ struct Grid {
   int64_t rows_per_block = 0;
 };
 int make_grid(int64_t n, Grid *g) {   // from the CU count, not from n: a fixed run of whole tiles per block
-  SvmWork &W = work();
-  if (W.cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipGetDeviceProperties(&prop, dev));
-    W.cus = std::max(1, prop.multiProcessorCount);
-  }
-  const int64_t tiles = cdiv(n, SV_ROWS), per = cdiv(tiles, W.cus);
+  int cus = 0;
+  ASL_TRY(cu_count(&cus));
+  const int64_t tiles = cdiv(n, SV_ROWS), per = cdiv(tiles, cus);
   g->blocks = (int)cdiv(tiles, per);
   g->rows_per_block = per * SV_ROWS;
-  return ASL_OK;
-}
-
-int check_shape(const char *who, int64_t n, int32_t d, int32_t P) {
-  if (d < 1 || P < 1 || n < 0) return fail(ASL_ERR_INVALID, "%s: needs d >= 1, P >= 1, n >= 0", who);
-  if (d > ASL_SVM_MAX_DIM) return fail(ASL_ERR_CAPACITY, "%s: d = %d, at most %d", who, d, ASL_SVM_MAX_DIM);
-  if (P > ASL_SVM_MAX_PROBLEMS)
-    return fail(ASL_ERR_CAPACITY, "%s: P = %d, at most %d", who, P, ASL_SVM_MAX_PROBLEMS);
   return ASL_OK;
 }
 
@@ -368,7 +341,7 @@ extern "C" int asl_l2svm_fit(const double *X, int64_t n, int32_t d, const int8_t
   clear_error();
   if (!cw || !params || !wb || !objective || !n_newton || !status)
     return fail(ASL_ERR_INVALID, "l2svm_fit: null argument");
-  ASL_TRY(check_shape("l2svm_fit", n, d, P));
+  ASL_TRY(check_shape("l2svm_fit", n, d, P, false));
   if (n > 0 && (!X || !label)) return fail(ASL_ERR_INVALID, "l2svm_fit: null X / label");
   const double C = params->C;
   if (!(C >= 0.0) || !std::isfinite(C)) return fail(ASL_ERR_INVALID, "l2svm_fit: C must be finite and >= 0");
@@ -377,26 +350,12 @@ extern "C" int asl_l2svm_fit(const double *X, int64_t n, int32_t d, const int8_t
   ASL_TRY(ensure_device());
   const int D = d + 1;
   std::vector<double> h_cw, h_wb;
-  ASL_TRY(copy_in(h_cw, cw, (size_t)P * 2));
-  ASL_TRY(copy_in(h_wb, wb, (size_t)P * D));
-  for (double v : h_cw)
-    if (!(v >= 0.0) || !std::isfinite(v))
-      return fail(ASL_ERR_INVALID, "l2svm_fit: class weights must be finite and >= 0");
+  ASL_TRY(host_copy(h_cw, cw, (size_t)P * 2));
+  ASL_TRY(host_copy(h_wb, wb, (size_t)P * D));
+  ASL_TRY(check_class_weights("l2svm_fit", h_cw));
   for (double v : h_wb)
     if (!std::isfinite(v)) return fail(ASL_ERR_INVALID, "l2svm_fit: non-finite starting point");
-  {   // the labels, on the host, before anything is launched
-    std::vector<int8_t> h_label;
-    const int8_t *lp = label;
-    const size_t cnt = (size_t)P * (size_t)n;
-    if (cnt && is_device_ptr(label)) {
-      ASL_TRY(copy_in(h_label, label, cnt));
-      lp = h_label.data();
-    }
-    for (size_t i = 0; i < cnt; ++i)
-      if (lp[i] < -1 || lp[i] > 1)
-        return fail(ASL_ERR_INVALID, "l2svm_fit: label[%lld, %lld] = %d, not in {-1, 0, +1}", (long long)(i / n),
-                    (long long)(i % n), (int)lp[i]);
-  }
+  ASL_TRY(check_labels("l2svm_fit", label, P, n));
   SvmWork &W = work();
   In<double> iX;
   In<int8_t> iL;
@@ -543,17 +502,17 @@ extern "C" int asl_l2svm_fit(const double *X, int64_t n, int32_t d, const int8_t
       h_newton[p] += 1;
     }
   }
-  ASL_TRY(copy_out(wb, h_wb));
-  ASL_TRY(copy_out(objective, h_obj));
-  ASL_TRY(copy_out(n_newton, h_newton));
-  ASL_TRY(copy_out(status, h_status));
+  ASL_TRY(host_copy_back(wb, h_wb));
+  ASL_TRY(host_copy_back(objective, h_obj));
+  ASL_TRY(host_copy_back(n_newton, h_newton));
+  ASL_TRY(host_copy_back(status, h_status));
   return ASL_OK;
 }
 
 extern "C" int asl_linear_scores(const double *X, int64_t n, int32_t d, const double *wb, int32_t P, double *out) {
   clear_error();
   if (!wb) return fail(ASL_ERR_INVALID, "linear_scores: null argument");
-  ASL_TRY(check_shape("linear_scores", n, d, P));
+  ASL_TRY(check_shape("linear_scores", n, d, P, false));
   if (n == 0) return ASL_OK;
   if (!X || !out) return fail(ASL_ERR_INVALID, "linear_scores: null X / out");
   ASL_TRY(ensure_device());

@@ -108,12 +108,12 @@ __device__ __forceinline__ int mg_charge(const uint8_t *__restrict__ t, uint32_t
 
 // kind, dflag (bit k: numeral k of the line was deferred) and val (a peak's two float32, a parameter's double or
 // charge) of every line
-__global__ __launch_bounds__(MG_NT) void mgf_lines_kernel(const uint8_t *__restrict__ t,
+__global__ __launch_bounds__(SCAN_NT) void mgf_lines_kernel(const uint8_t *__restrict__ t,
                                                           const uint32_t *__restrict__ line_start, int64_t n_lines,
                                                           int last, uint8_t *__restrict__ kind,
                                                           uint8_t *__restrict__ dflag, uint64_t *__restrict__ val,
                                                           TextFinal *__restrict__ fin) {
-  const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  const int64_t L = (int64_t)blockIdx.x * SCAN_NT + threadIdx.x;
   if (L >= n_lines) return;
   const uint32_t a = line_start[L], b = line_start[L + 1];
   if (!text_walks_line(t, a, b, L, n_lines, last, fin)) {
@@ -203,7 +203,7 @@ struct CountView {   // spec[L]: blocks opened up to and including L; slot / dsl
 };
 
 // gate: lines behind it belong to a block this chunk does not close (they come again with the next chunk)
-__global__ __launch_bounds__(MG_NT) void mgf_resolve_kernel(const uint8_t *__restrict__ kind,
+__global__ __launch_bounds__(SCAN_NT) void mgf_resolve_kernel(const uint8_t *__restrict__ kind,
                                                             const uint8_t *__restrict__ after,
                                                             const uint32_t *__restrict__ spec,
                                                             const uint32_t *__restrict__ slot,
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(MG_NT) void mgf_resolve_kernel(const uint8_t *__res
                                                             uint32_t *__restrict__ peak_end,
                                                             uint32_t *__restrict__ key_line,
                                                             TextFinal *__restrict__ fin) {
-  const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  const int64_t L = (int64_t)blockIdx.x * SCAN_NT + threadIdx.x;
   if (L >= n_lines) return;
   const bool in = L > 0 && after[L - 1] != 0;
   const uint8_t k = kind[L];
@@ -235,13 +235,13 @@ __global__ __launch_bounds__(MG_NT) void mgf_resolve_kernel(const uint8_t *__res
 
 // ---------------------------------------------------------------------------------------------- fill
 // rec: [n_def, 5], the records of put_deferred
-__global__ __launch_bounds__(MG_NT) void mgf_fill_lines_kernel(
+__global__ __launch_bounds__(SCAN_NT) void mgf_fill_lines_kernel(
     const uint8_t *__restrict__ t, const uint32_t *__restrict__ line_start, const uint8_t *__restrict__ kind,
     const uint8_t *__restrict__ dflag, const uint64_t *__restrict__ val, const uint8_t *__restrict__ after,
     const uint32_t *__restrict__ spec, const uint32_t *__restrict__ slot, const uint32_t *__restrict__ dslot,
     int64_t n_lines, uint32_t n_blocks, uint32_t n_peaks, uint32_t n_def, float *__restrict__ mz,
     float *__restrict__ intensity, uint8_t *__restrict__ charge, int32_t *__restrict__ rec) {
-  const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  const int64_t L = (int64_t)blockIdx.x * SCAN_NT + threadIdx.x;
   if (L >= n_lines) return;
   if (!(L > 0 && after[L - 1] != 0) || spec[L] - 1u >= n_blocks) return;   // (an open block's slots lie behind n_peaks)
   const uint8_t k = kind[L], df = dflag[L];
@@ -266,14 +266,14 @@ __global__ __launch_bounds__(MG_NT) void mgf_fill_lines_kernel(
   }
 }
 
-__global__ __launch_bounds__(MG_NT) void mgf_fill_spectra_kernel(
+__global__ __launch_bounds__(SCAN_NT) void mgf_fill_spectra_kernel(
     const uint8_t *__restrict__ t, const uint32_t *__restrict__ line_start, const uint8_t *__restrict__ dflag,
     const uint64_t *__restrict__ val, const uint32_t *__restrict__ dslot, const uint32_t *__restrict__ first_line,
     const uint32_t *__restrict__ peak_begin, const uint32_t *__restrict__ key_line, uint32_t n_closed,
     uint32_t n_peaks, uint32_t n_def, int32_t *__restrict__ offsets, double *__restrict__ pmz,
     int32_t *__restrict__ pcharge, double *__restrict__ rt, int32_t *__restrict__ ident,
     int32_t *__restrict__ first, int32_t *__restrict__ rec) {
-  const uint32_t s = blockIdx.x * MG_NT + threadIdx.x;
+  const uint32_t s = blockIdx.x * SCAN_NT + threadIdx.x;
   if (s >= n_closed) return;
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   offsets[s] = (int32_t)peak_begin[s];
@@ -339,7 +339,7 @@ extern "C" int asl_mgf_measure(const uint8_t *text, int64_t n, int32_t last, int
   ASL_TRY(line_starts(text, n, W.count, W.partial, W.line_start, &nl));
   // lines, block state, counts
   ASL_TRY(measure_lines(W, nl));
-  hipLaunchKernelGGL(mgf_lines_kernel, dim3(blocks_of(nl)), dim3(MG_NT), 0, stream(), text, W.line_start.p, nl,
+  hipLaunchKernelGGL(mgf_lines_kernel, dim3(blocks_of(nl)), dim3(SCAN_NT), 0, stream(), text, W.line_start.p, nl,
                      (int)last, W.kind.p, W.dflag.p, W.val.p, W.fin.p);
   ASL_CHECK_LAUNCH();
   ASL_TRY(scan_view(StateView{W.kind.p, W.after.p}, nl, W.partial.p));
@@ -358,12 +358,12 @@ extern "C" int asl_mgf_measure(const uint8_t *text, int64_t n, int32_t last, int
   ASL_TRY(W.key_line.reserve(ns * MG_KEYS));
   HIP_TRY(hipMemsetAsync(W.key_line.p, 0, ns * MG_KEYS * sizeof(uint32_t), stream()));
   const int64_t gate = last != 0 ? nl : (int64_t)T.cons_line;
-  hipLaunchKernelGGL(mgf_resolve_kernel, dim3(blocks_of(nl)), dim3(MG_NT), 0, stream(), W.kind.p, W.after.p,
+  hipLaunchKernelGGL(mgf_resolve_kernel, dim3(blocks_of(nl)), dim3(SCAN_NT), 0, stream(), W.kind.p, W.after.p,
                      W.rec.p, W.slot.p, W.dslot.p, nl, gate, n_open, n_closed, W.first_line.p, W.peak_begin.p,
                      W.peak_end.p, W.key_line.p, W.fin.p);
   ASL_CHECK_LAUNCH();
   if (n_closed > 0) {
-    hipLaunchKernelGGL(text_capacity_kernel, dim3(blocks_of(n_closed)), dim3(MG_NT), 0, stream(), W.peak_begin.p,
+    hipLaunchKernelGGL(text_capacity_kernel, dim3(blocks_of(n_closed)), dim3(SCAN_NT), 0, stream(), W.peak_begin.p,
                        W.peak_end.p, n_closed, 0, 0u, W.fin.p);
     ASL_CHECK_LAUNCH();
   }
@@ -409,12 +409,12 @@ extern "C" int asl_mgf_fill(const uint8_t *text, int64_t n, int32_t *offsets, fl
   ASL_TRY(oId.init(identifier, (size_t)ns * 2));
   ASL_TRY(oFirst.init(first_line, ns));
   ASL_TRY(oRec.init(deferred, (size_t)nd * 5));
-  hipLaunchKernelGGL(mgf_fill_lines_kernel, dim3(blocks_of(W.n_lines)), dim3(MG_NT), 0, stream(), text,
+  hipLaunchKernelGGL(mgf_fill_lines_kernel, dim3(blocks_of(W.n_lines)), dim3(SCAN_NT), 0, stream(), text,
                      W.line_start.p, W.kind.p, W.dflag.p, W.val.p, W.after.p, W.rec.p, W.slot.p, W.dslot.p,
                      W.n_lines, W.n_blocks, np, nd, oMz.d, oIt.d, oChg.d, oRec.d);
   ASL_CHECK_LAUNCH();
   if (ns > 0) {   // (none: the deferred tokens of an unclosed last block alone)
-    hipLaunchKernelGGL(mgf_fill_spectra_kernel, dim3(blocks_of(ns)), dim3(MG_NT), 0, stream(), text, W.line_start.p,
+    hipLaunchKernelGGL(mgf_fill_spectra_kernel, dim3(blocks_of(ns)), dim3(SCAN_NT), 0, stream(), text, W.line_start.p,
                        W.dflag.p, W.val.p, W.dslot.p, W.first_line.p, W.peak_begin.p, W.key_line.p, ns, np, nd, oOff.d,
                        oPmz.d, oZ.d, oRt.d, oId.d, oFirst.d, oRec.d);
     ASL_CHECK_LAUNCH();

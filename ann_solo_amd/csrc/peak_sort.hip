@@ -11,7 +11,7 @@
 
 namespace asl {
 
-constexpr int MG_NT = ASL_MGF_TILE;            // threads of every kernel here, as in the readers (text_scan.hpp)
+constexpr int MG_NT = ASL_MGF_TILE;            // threads of every kernel here, as in the readers (SCAN_NT there)
 constexpr int MG_MAX_PEAKS = ASL_MGF_MAX_PEAKS;
 static_assert((MG_MAX_PEAKS & (MG_MAX_PEAKS - 1)) == 0, "the bitonic network pads to a power of two");
 

@@ -132,11 +132,11 @@ __device__ __forceinline__ SpFields sp_fields(const uint8_t *__restrict__ t, uin
 }
 
 // ---------------------------------------------------------------------------------------------- lines
-__global__ __launch_bounds__(MG_NT) void sptxt_classify_kernel(const uint8_t *__restrict__ t,
+__global__ __launch_bounds__(SCAN_NT) void sptxt_classify_kernel(const uint8_t *__restrict__ t,
                                                                const uint32_t *__restrict__ line_start,
                                                                int64_t n_lines, int last, uint8_t *__restrict__ kind,
                                                                TextFinal *__restrict__ fin) {
-  const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  const int64_t L = (int64_t)blockIdx.x * SCAN_NT + threadIdx.x;
   if (L >= n_lines) return;
   const uint32_t a = line_start[L], b = line_start[L + 1];
   if (!text_walks_line(t, a, b, L, n_lines, last, fin)) {
@@ -164,13 +164,13 @@ struct SpStateView {   // after[L]: the state line L + 1 finds
 
 // flags, dflag (bit k: numeral k of the line was deferred), val (a peak's two float32, or the precursor's double)
 // and chg (a peak's fragment charge) of every line
-__global__ __launch_bounds__(MG_NT) void sptxt_parse_kernel(const uint8_t *__restrict__ t,
+__global__ __launch_bounds__(SCAN_NT) void sptxt_parse_kernel(const uint8_t *__restrict__ t,
                                                             const uint32_t *__restrict__ line_start, int64_t n_lines,
                                                             const uint8_t *__restrict__ kind,
                                                             const uint8_t *__restrict__ after,
                                                             uint8_t *__restrict__ flags, uint8_t *__restrict__ dflag,
                                                             uint8_t *__restrict__ chg, uint64_t *__restrict__ val) {
-  const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  const int64_t L = (int64_t)blockIdx.x * SCAN_NT + threadIdx.x;
   if (L >= n_lines) return;
   const uint8_t k = kind[L];
   uint8_t fl = 0, df = 0, cz = 0;
@@ -265,14 +265,14 @@ struct SpCountView {   // rec[L]: Name: lines up to and including L; slot / dslo
 };
 
 // gate: lines from it on belong to a record this chunk does not close (they come again with the next chunk)
-__global__ __launch_bounds__(MG_NT) void sptxt_resolve_kernel(
+__global__ __launch_bounds__(SCAN_NT) void sptxt_resolve_kernel(
     const uint8_t *__restrict__ kind, const uint8_t *__restrict__ flags, const uint8_t *__restrict__ after,
     const uint32_t *__restrict__ rec, const uint32_t *__restrict__ slot, const uint32_t *__restrict__ dslot,
     int64_t n_lines, int64_t gate, uint32_t n_open, uint32_t n_rec, uint32_t *__restrict__ first_line,
     uint32_t *__restrict__ peak_begin, uint32_t *__restrict__ peak_end, uint32_t *__restrict__ pmz_line,
     uint32_t *__restrict__ parent_line, uint32_t *__restrict__ mods_line, uint32_t *__restrict__ decoy,
     TextFinal *__restrict__ fin) {
-  const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  const int64_t L = (int64_t)blockIdx.x * SCAN_NT + threadIdx.x;
   if (L >= n_lines) return;
   const uint8_t k = kind[L], fl = flags[L];
   const uint32_t sb = L > 0 ? after[L - 1] : SS_OUT;
@@ -302,13 +302,13 @@ __global__ __launch_bounds__(MG_NT) void sptxt_resolve_kernel(
 
 // ---------------------------------------------------------------------------------------------- fill
 // out: [n_def, 5], the records of put_deferred
-__global__ __launch_bounds__(MG_NT) void sptxt_fill_lines_kernel(
+__global__ __launch_bounds__(SCAN_NT) void sptxt_fill_lines_kernel(
     const uint8_t *__restrict__ t, const uint32_t *__restrict__ line_start, const uint8_t *__restrict__ kind,
     const uint8_t *__restrict__ flags, const uint8_t *__restrict__ dflag, const uint8_t *__restrict__ chg,
     const uint64_t *__restrict__ val, const uint32_t *__restrict__ rec, const uint32_t *__restrict__ slot,
     const uint32_t *__restrict__ dslot, int64_t n_lines, uint32_t n_blocks, uint32_t n_peaks, uint32_t n_def,
     float *__restrict__ mz, float *__restrict__ intensity, uint8_t *__restrict__ charge, int32_t *__restrict__ out) {
-  const int64_t L = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  const int64_t L = (int64_t)blockIdx.x * SCAN_NT + threadIdx.x;
   if (L >= n_lines) return;
   if (rec[L] == 0u || rec[L] - 1u >= n_blocks) return;   // (an open record's slots lie behind n_peaks)
   const uint8_t fl = flags[L], df = dflag[L];
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(MG_NT) void sptxt_fill_lines_kernel(
 }
 
 // info: [n_rec, ASL_SPTXT_INFO]
-__global__ __launch_bounds__(MG_NT) void sptxt_fill_records_kernel(
+__global__ __launch_bounds__(SCAN_NT) void sptxt_fill_records_kernel(
     const uint8_t *__restrict__ t, const uint32_t *__restrict__ line_start, const uint8_t *__restrict__ flags,
     const uint8_t *__restrict__ dflag, const uint64_t *__restrict__ val, const uint32_t *__restrict__ dslot,
     const uint32_t *__restrict__ first_line, const uint32_t *__restrict__ peak_begin,
@@ -353,7 +353,7 @@ __global__ __launch_bounds__(MG_NT) void sptxt_fill_records_kernel(
     const uint32_t *__restrict__ mods_line, const uint32_t *__restrict__ decoy, uint32_t n_rec, uint32_t n_peaks,
     uint32_t n_def, int32_t *__restrict__ offsets, double *__restrict__ pmz, int32_t *__restrict__ info,
     int32_t *__restrict__ out) {
-  const uint32_t s = blockIdx.x * MG_NT + threadIdx.x;
+  const uint32_t s = blockIdx.x * SCAN_NT + threadIdx.x;
   if (s >= n_rec) return;
   offsets[s] = (int32_t)peak_begin[s];
   if (s + 1u == n_rec) offsets[n_rec] = (int32_t)n_peaks;
@@ -444,7 +444,7 @@ extern "C" int asl_sptxt_measure(const uint8_t *text, int64_t n, int32_t last, i
   ASL_TRY(measure_lines(W, nl));
   {
     ProfScope p2("sptxt_classify");
-    hipLaunchKernelGGL(sptxt_classify_kernel, dim3(blocks_of(nl)), dim3(MG_NT), 0, stream(), text, W.line_start.p,
+    hipLaunchKernelGGL(sptxt_classify_kernel, dim3(blocks_of(nl)), dim3(SCAN_NT), 0, stream(), text, W.line_start.p,
                        nl, (int)last, W.kind.p, W.fin.p);
     ASL_CHECK_LAUNCH();
   }
@@ -454,7 +454,7 @@ extern "C" int asl_sptxt_measure(const uint8_t *text, int64_t n, int32_t last, i
   }
   {
     ProfScope p4("sptxt_parse");
-    hipLaunchKernelGGL(sptxt_parse_kernel, dim3(blocks_of(nl)), dim3(MG_NT), 0, stream(), text, W.line_start.p, nl,
+    hipLaunchKernelGGL(sptxt_parse_kernel, dim3(blocks_of(nl)), dim3(SCAN_NT), 0, stream(), text, W.line_start.p, nl,
                        W.kind.p, W.after.p, W.flags.p, W.dflag.p, W.chg.p, W.val.p);
     ASL_CHECK_LAUNCH();
   }
@@ -485,12 +485,12 @@ extern "C" int asl_sptxt_measure(const uint8_t *text, int64_t n, int32_t last, i
   // (without a Name: line the chunk is preamble: all its lines are checked; a cut final line was not looked at)
   const int64_t gate = last != 0 || n_open == 0u ? nl : (int64_t)T.cons_line;
   ProfScope p6("sptxt_resolve");
-  hipLaunchKernelGGL(sptxt_resolve_kernel, dim3(blocks_of(nl)), dim3(MG_NT), 0, stream(), W.kind.p, W.flags.p,
+  hipLaunchKernelGGL(sptxt_resolve_kernel, dim3(blocks_of(nl)), dim3(SCAN_NT), 0, stream(), W.kind.p, W.flags.p,
                      W.after.p, W.rec.p, W.slot.p, W.dslot.p, nl, gate, n_open, n_rec, W.first_line.p, W.peak_begin.p,
                      W.peak_end.p, W.pmz_line.p, W.parent_line.p, W.mods_line.p, W.decoy.p, W.fin.p);
   ASL_CHECK_LAUNCH();
   if (n_rec > 0) {
-    hipLaunchKernelGGL(text_capacity_kernel, dim3(blocks_of(n_rec)), dim3(MG_NT), 0, stream(), W.peak_begin.p,
+    hipLaunchKernelGGL(text_capacity_kernel, dim3(blocks_of(n_rec)), dim3(SCAN_NT), 0, stream(), W.peak_begin.p,
                        W.peak_end.p, n_rec, (int)last, T.peaks, W.fin.p);
     ASL_CHECK_LAUNCH();
   }
@@ -533,13 +533,13 @@ extern "C" int asl_sptxt_fill(const uint8_t *text, int64_t n, int32_t *offsets, 
   ASL_TRY(oRec.init(deferred, (size_t)nd * 5));
   {
     ProfScope p1("sptxt_fill_lines");
-    hipLaunchKernelGGL(sptxt_fill_lines_kernel, dim3(blocks_of(W.n_lines)), dim3(MG_NT), 0, stream(), text,
+    hipLaunchKernelGGL(sptxt_fill_lines_kernel, dim3(blocks_of(W.n_lines)), dim3(SCAN_NT), 0, stream(), text,
                        W.line_start.p, W.kind.p, W.flags.p, W.dflag.p, W.chg.p, W.val.p, W.rec.p, W.slot.p, W.dslot.p,
                        W.n_lines, W.n_blocks, np, nd, oMz.d, oIt.d, oChg.d, oRec.d);
     ASL_CHECK_LAUNCH();
   }
   ProfScope p2("sptxt_fill_records");
-  hipLaunchKernelGGL(sptxt_fill_records_kernel, dim3(blocks_of(ns)), dim3(MG_NT), 0, stream(), text, W.line_start.p,
+  hipLaunchKernelGGL(sptxt_fill_records_kernel, dim3(blocks_of(ns)), dim3(SCAN_NT), 0, stream(), text, W.line_start.p,
                      W.flags.p, W.dflag.p, W.val.p, W.dslot.p, W.first_line.p, W.peak_begin.p, W.pmz_line.p,
                      W.parent_line.p, W.mods_line.p, W.decoy.p, ns, np, nd, oOff.d, oPmz.d, oInfo.d, oRec.d);
   ASL_CHECK_LAUNCH();

@@ -13,14 +13,14 @@
 //            q[index] and label[index]
 //   fill     NaN / 0 into the rows that take no part
 //
-// Every scan is reduce -> scan of the block partials (recursively) -> apply, as separate launches on the library's
-// stream: no kernel waits on another workgroup. No floating-point sum or atomic anywhere: the counts are integers,
-// a run's end does ONE fp64 division, min is exact. Rows of one (group, score) run get one q, so the order a sort
-// leaves inside a run cannot reach the output.
+// Every scan is device_scan.hpp's: reduce -> scan of the block partials (recursively) -> apply, as separate launches
+// on the library's stream, so no kernel waits on another workgroup. No floating-point sum or atomic anywhere: the
+// counts are integers, a run's end does ONE fp64 division, min is exact. Rows of one (group, score) run get one q,
+// so the order a sort leaves inside a run cannot reach the output.
 #include <algorithm>
 #include <cmath>
 
-#include "common.hpp"
+#include "device_scan.hpp"
 
 namespace asl {
 
@@ -28,17 +28,12 @@ constexpr int TD_NT = 256;                     // threads of every kernel here (
 constexpr int TD_TILE = ASL_TDC_TILE;          // keys per sort tile
 constexpr int TD_ROUNDS = TD_TILE / TD_NT;     // a thread's keys: element e = round * TD_NT + tid
 constexpr int TD_SLOTS = TD_ROUNDS * (TD_NT / 64);
-constexpr int TD_SCAN = TD_NT;                 // elements per block of a scan level
 constexpr int TD_PASSES = 12;                  // 8 score bytes, then 4 group bytes
 constexpr uint32_t TD_TARGET = 0x80000000u;
 static_assert(TD_TILE % TD_NT == 0, "whole rounds");
+static_assert(TD_NT == SCAN_NT, "one block size for the sort and the scans");
 
 // ---------------------------------------------------------------------------------------------- scans
-struct SumU32 {
-  using T = uint32_t;
-  __device__ static T identity() { return 0u; }
-  __device__ static T op(T a, T b) { return a + b; }
-};
 struct CountHead {   // s: targets so far; m: the largest head position so far
   uint32_t s, m;
 };
@@ -57,68 +52,7 @@ struct GroupMinOp {
   __device__ static T op(T a, T b) { return (b.g < a.g || (b.g == a.g && b.v < a.v)) ? b : a; }
 };
 
-template <class T>
-__device__ __forceinline__ T shfl_up_words(T v, int delta) {
-  static_assert(sizeof(T) % 4 == 0, "whole words");
-  uint32_t w[sizeof(T) / 4];
-  __builtin_memcpy(w, &v, sizeof(T));
-#pragma unroll
-  for (size_t k = 0; k < sizeof(T) / 4; ++k) w[k] = (uint32_t)__shfl_up((int)w[k], delta, 64);
-  __builtin_memcpy(&v, w, sizeof(T));
-  return v;
-}
-
-// inclusive scan over the block's TD_NT values in thread order; *total: the block's sum, in every thread
-template <class Op>
-__device__ __forceinline__ typename Op::T block_scan(typename Op::T x, typename Op::T *total) {
-  using T = typename Op::T;
-  __shared__ T wave_tot[TD_NT / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T o = shfl_up_words(x, d);
-    if (lane >= d) x = Op::op(o, x);
-  }
-  if (lane == 63) wave_tot[wave] = x;
-  __syncthreads();
-  T pre = Op::identity(), all = Op::identity();
-#pragma unroll
-  for (int w = 0; w < TD_NT / 64; ++w) {
-    if (w < wave) pre = Op::op(pre, wave_tot[w]);
-    all = Op::op(all, wave_tot[w]);
-  }
-  *total = all;
-  return Op::op(pre, x);
-}
-
-// A view names a scan's operator (Op), reads element i (load) and takes its inclusive result (store).
-template <class V>
-__global__ __launch_bounds__(TD_NT) void scan_reduce_kernel(V view, int64_t n, typename V::Op::T *partial) {
-  using Op = typename V::Op;
-  const int64_t i = (int64_t)blockIdx.x * TD_SCAN + threadIdx.x;
-  typename Op::T total;
-  block_scan<Op>(i < n ? view.load(i) : Op::identity(), &total);
-  if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-// partial: the INCLUSIVE scan of the blocks' sums (block b starts from partial[b - 1]), or nullptr for one block
-template <class V>
-__global__ __launch_bounds__(TD_NT) void scan_apply_kernel(V view, int64_t n, const typename V::Op::T *partial) {
-  using Op = typename V::Op;
-  const int64_t i = (int64_t)blockIdx.x * TD_SCAN + threadIdx.x;
-  const typename Op::T own = i < n ? view.load(i) : Op::identity();
-  typename Op::T total;
-  typename Op::T incl = block_scan<Op>(own, &total);
-  if (partial != nullptr && blockIdx.x > 0) incl = Op::op(partial[blockIdx.x - 1], incl);
-  if (i < n) view.store(i, incl, own);
-}
-
-template <class O>
-struct PlainView {   // an array scanned in place (the upper levels)
-  using Op = O;
-  typename O::T *a;
-  __device__ typename O::T load(int64_t i) const { return a[i]; }
-  __device__ void store(int64_t i, typename O::T incl, typename O::T) const { a[i] = incl; }
-};
+// the views (device_scan.hpp: an operator, load(i), store(i, inclusive, own))
 struct ExclusiveU32View {   // counts -> offsets, in place
   using Op = SumU32;
   uint32_t *a;
@@ -322,46 +256,6 @@ struct TdcWork {
 TdcWork &work() {
   static TdcWork w;
   return w;
-}
-
-int64_t partial_slots(int64_t n) {   // block partials of all levels of a scan over n elements
-  int64_t total = 0;
-  while (n > TD_SCAN) {
-    n = cdiv(n, TD_SCAN);
-    total += n;
-  }
-  return total;
-}
-
-template <class O>
-int scan_in_place(typename O::T *a, int64_t n, typename O::T *scratch) {   // inclusive, the upper levels
-  PlainView<O> v{a};
-  const int64_t nb = cdiv(n, TD_SCAN);
-  if (nb > 1) {
-    hipLaunchKernelGGL(scan_reduce_kernel<PlainView<O>>, dim3((unsigned)nb), dim3(TD_NT), 0, stream(), v, n, scratch);
-    ASL_CHECK_LAUNCH();
-    ASL_TRY(scan_in_place<O>(scratch, nb, scratch + nb));
-  }
-  hipLaunchKernelGGL(scan_apply_kernel<PlainView<O>>, dim3((unsigned)nb), dim3(TD_NT), 0, stream(), v, n,
-                     nb > 1 ? scratch : nullptr);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-template <class V>
-int scan_view(const V &v, int64_t n, void *scratch_bytes) {
-  using T = typename V::Op::T;
-  T *scratch = static_cast<T *>(scratch_bytes);
-  const int64_t nb = cdiv(n, TD_SCAN);
-  if (nb > 1) {
-    hipLaunchKernelGGL(scan_reduce_kernel<V>, dim3((unsigned)nb), dim3(TD_NT), 0, stream(), v, n, scratch);
-    ASL_CHECK_LAUNCH();
-    ASL_TRY(scan_in_place<typename V::Op>(scratch, nb, scratch + nb));
-  }
-  hipLaunchKernelGGL(scan_apply_kernel<V>, dim3((unsigned)nb), dim3(TD_NT), 0, stream(), v, n,
-                     nb > 1 ? scratch : nullptr);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
 }
 
 }  // namespace

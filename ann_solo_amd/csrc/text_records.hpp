@@ -62,11 +62,11 @@ __device__ __forceinline__ void put_deferred(int32_t *__restrict__ rec, uint32_t
 }
 
 // close_last: the file's end closes the last record, at peak slot end_peaks (else every record has its end already)
-__global__ __launch_bounds__(MG_NT) void text_capacity_kernel(const uint32_t *__restrict__ peak_begin,
+__global__ __launch_bounds__(SCAN_NT) void text_capacity_kernel(const uint32_t *__restrict__ peak_begin,
                                                               uint32_t *__restrict__ peak_end, uint32_t n_rec,
                                                               int close_last, uint32_t end_peaks,
                                                               TextFinal *__restrict__ fin) {
-  const uint32_t s = blockIdx.x * MG_NT + threadIdx.x;
+  const uint32_t s = blockIdx.x * SCAN_NT + threadIdx.x;
   if (s >= n_rec) return;
   if (close_last != 0 && s + 1u == n_rec) peak_end[s] = end_peaks;
   if (peak_end[s] - peak_begin[s] > (uint32_t)ASL_MGF_MAX_PEAKS) atomicMin(&fin->cap_rec, s);

@@ -1,92 +1,19 @@
-// text_scan.hpp -- what the text readers share (mgf.hip, sptxt.hip): the block scan and its reduce / apply kernels,
-// the line-start pass over a chunk of text, the blanks of bytes.strip, and the host's scan drivers. gfx950 only.
-// What the two share about records -- counts, stores, the host's measure and fill -- is text_records.hpp, which
-// includes this header.
+// text_scan.hpp -- what the text readers share (mgf.hip, sptxt.hip) below their records: the line-start pass over a
+// chunk of text and the blanks of bytes.strip, on the scan of device_scan.hpp. gfx950 only. What the two share about
+// records -- counts, stores, the host's measure and fill -- is text_records.hpp, which includes this header.
 //
-// Every scan is reduce -> scan of the block partials (recursively) -> apply, as separate launches on the library's
-// stream: no kernel waits on another workgroup. Everything here has internal linkage: each translation unit that
-// includes the header holds its own kernels.
+// Every kernel of the readers has SCAN_NT threads. Everything here has internal linkage, as in device_scan.hpp:
+// each translation unit that includes the header holds its own kernels.
 #pragma once
 #include <algorithm>
 
-#include "common.hpp"
+#include "device_scan.hpp"
 
 namespace asl {
 namespace {
 
-constexpr int MG_NT = ASL_MGF_TILE;            // threads of every kernel here = elements per block of a scan level
 constexpr int MG_SPAN = 16;                    // bytes per thread of the line-start passes
-static_assert(MG_NT == 256, "four waves: mg_block_scan's wave totals");
-
-// ---------------------------------------------------------------------------------------------- scans
-struct MgSum {
-  using T = uint32_t;
-  __device__ static T identity() { return 0u; }
-  __device__ static T op(T a, T b) { return a + b; }
-};
-
-template <class T>
-__device__ __forceinline__ T mg_shfl_up(T v, int delta) {
-  static_assert(sizeof(T) % 4 == 0, "whole words");
-  uint32_t w[sizeof(T) / 4];
-  __builtin_memcpy(w, &v, sizeof(T));
-#pragma unroll
-  for (size_t k = 0; k < sizeof(T) / 4; ++k) w[k] = (uint32_t)__shfl_up((int)w[k], delta, 64);
-  __builtin_memcpy(&v, w, sizeof(T));
-  return v;
-}
-
-// inclusive scan over the block's MG_NT values in thread order; *total: the block's sum, in every thread
-template <class Op>
-__device__ __forceinline__ typename Op::T mg_block_scan(typename Op::T x, typename Op::T *total) {
-  using T = typename Op::T;
-  __shared__ T wave_tot[MG_NT / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T o = mg_shfl_up(x, d);
-    if (lane >= d) x = Op::op(o, x);
-  }
-  if (lane == 63) wave_tot[wave] = x;
-  __syncthreads();
-  T pre = Op::identity(), all = Op::identity();
-#pragma unroll
-  for (int w = 0; w < MG_NT / 64; ++w) {
-    if (w < wave) pre = Op::op(pre, wave_tot[w]);
-    all = Op::op(all, wave_tot[w]);
-  }
-  *total = all;
-  return Op::op(pre, x);
-}
-
-// A view names a scan's operator (Op), reads element i (load) and takes its inclusive result (store).
-template <class V>
-__global__ __launch_bounds__(MG_NT) void mgf_scan_reduce_kernel(V view, int64_t n, typename V::Op::T *partial) {
-  using Op = typename V::Op;
-  const int64_t i = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
-  typename Op::T total;
-  mg_block_scan<Op>(i < n ? view.load(i) : Op::identity(), &total);
-  if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-// partial: the INCLUSIVE scan of the blocks' sums (block b starts from partial[b - 1]), or nullptr for one block
-template <class V>
-__global__ __launch_bounds__(MG_NT) void mgf_scan_apply_kernel(V view, int64_t n, const typename V::Op::T *partial) {
-  using Op = typename V::Op;
-  const int64_t i = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
-  const typename Op::T own = i < n ? view.load(i) : Op::identity();
-  typename Op::T total;
-  typename Op::T incl = mg_block_scan<Op>(own, &total);
-  if (partial != nullptr && blockIdx.x > 0) incl = Op::op(partial[blockIdx.x - 1], incl);
-  if (i < n) view.store(i, incl, own);
-}
-
-template <class O>
-struct MgPlainView {   // an array scanned in place (the upper levels)
-  using Op = O;
-  typename O::T *a;
-  __device__ typename O::T load(int64_t i) const { return a[i]; }
-  __device__ void store(int64_t i, typename O::T incl, typename O::T) const { a[i] = incl; }
-};
+static_assert(ASL_MGF_TILE == SCAN_NT, "mgf.SCAN_TILE is the scan's block");
 
 // ---------------------------------------------------------------------------------------------- line starts
 // Bit k of the result: byte 16 e + k is a '\n' that is followed by another byte, i.e. byte 16 e + k + 1 starts a
@@ -114,16 +41,16 @@ __device__ __forceinline__ uint32_t mg_starts(const uint8_t *__restrict__ t, int
   return (uint32_t)__popc(mg_newlines(t, n, e, vec)) + (e == 0 && n > 0 ? 1u : 0u);
 }
 
-__global__ __launch_bounds__(MG_NT) void mgf_count_lines_kernel(const uint8_t *__restrict__ t, int64_t n, int64_t ne,
+__global__ __launch_bounds__(SCAN_NT) void mgf_count_lines_kernel(const uint8_t *__restrict__ t, int64_t n, int64_t ne,
                                                                 int vec, unsigned long long *__restrict__ total) {
-  const int64_t e = (int64_t)blockIdx.x * MG_NT + threadIdx.x;
+  const int64_t e = (int64_t)blockIdx.x * SCAN_NT + threadIdx.x;
   uint32_t tot;
-  mg_block_scan<MgSum>(e < ne ? mg_starts(t, n, e, vec != 0) : 0u, &tot);
+  block_scan<SumU32>(e < ne ? mg_starts(t, n, e, vec != 0) : 0u, &tot);
   if (threadIdx.x == 0 && tot != 0u) atomicAdd(total, (unsigned long long)tot);   // (an integer count)
 }
 
 struct LineStartView {   // element e: the line starts its MG_SPAN bytes produce, in file order
-  using Op = MgSum;
+  using Op = SumU32;
   const uint8_t *t;
   int64_t n;
   int vec;
@@ -154,48 +81,7 @@ __device__ __forceinline__ void mg_strip(const uint8_t *__restrict__ t, uint32_t
 }
 
 // ---------------------------------------------------------------------------------------------- host
-inline int64_t partial_slots(int64_t n) {   // block partials of all levels of a scan over n elements
-  int64_t total = 0;
-  while (n > MG_NT) {
-    n = cdiv(n, MG_NT);
-    total += n;
-  }
-  return total;
-}
-
-template <class O>
-int scan_in_place(typename O::T *a, int64_t n, typename O::T *scratch) {   // inclusive, the upper levels
-  MgPlainView<O> v{a};
-  const int64_t nb = cdiv(n, MG_NT);
-  if (nb > 1) {
-    hipLaunchKernelGGL(mgf_scan_reduce_kernel<MgPlainView<O>>, dim3((unsigned)nb), dim3(MG_NT), 0, stream(), v, n,
-                       scratch);
-    ASL_CHECK_LAUNCH();
-    ASL_TRY(scan_in_place<O>(scratch, nb, scratch + nb));
-  }
-  hipLaunchKernelGGL(mgf_scan_apply_kernel<MgPlainView<O>>, dim3((unsigned)nb), dim3(MG_NT), 0, stream(), v, n,
-                     nb > 1 ? scratch : nullptr);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-template <class V>
-int scan_view(const V &v, int64_t n, void *scratch_bytes) {
-  using T = typename V::Op::T;
-  T *scratch = static_cast<T *>(scratch_bytes);
-  const int64_t nb = cdiv(n, MG_NT);
-  if (nb > 1) {
-    hipLaunchKernelGGL(mgf_scan_reduce_kernel<V>, dim3((unsigned)nb), dim3(MG_NT), 0, stream(), v, n, scratch);
-    ASL_CHECK_LAUNCH();
-    ASL_TRY(scan_in_place<typename V::Op>(scratch, nb, scratch + nb));
-  }
-  hipLaunchKernelGGL(mgf_scan_apply_kernel<V>, dim3((unsigned)nb), dim3(MG_NT), 0, stream(), v, n,
-                     nb > 1 ? scratch : nullptr);
-  ASL_CHECK_LAUNCH();
-  return ASL_OK;
-}
-
-inline unsigned blocks_of(int64_t n) { return (unsigned)std::max<int64_t>(cdiv(n, MG_NT), 1); }
+inline unsigned blocks_of(int64_t n) { return (unsigned)std::max<int64_t>(cdiv(n, SCAN_NT), 1); }
 
 // The line starts of the chunk text[0 .. n), n > 0: *n_lines (>= 1) and line_start[0 .. *n_lines], the last
 // entry being n. count: one word; partial: grown to what a scan over max(spans, lines) elements needs.
@@ -206,7 +92,7 @@ int line_starts(const uint8_t *text, int64_t n, DevBuf<unsigned long long> &coun
   const int64_t ne = cdiv(n, MG_SPAN);
   ASL_TRY(count.reserve(1));
   HIP_TRY(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), stream()));
-  hipLaunchKernelGGL(mgf_count_lines_kernel, dim3(blocks_of(ne)), dim3(MG_NT), 0, stream(), text, n, ne, vec,
+  hipLaunchKernelGGL(mgf_count_lines_kernel, dim3(blocks_of(ne)), dim3(SCAN_NT), 0, stream(), text, n, ne, vec,
                      count.p);
   ASL_CHECK_LAUNCH();
   unsigned long long h_lines = 0;

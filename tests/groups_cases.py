@@ -16,6 +16,10 @@ what their case is about, so a case that stops showing it fails at import.
   contention  5 000 rows in one bin; 20 000 rows in three adjacent bins around 0 on a sparse background
   span        one interval; nominals -32 768 and 32 767 (span 65 536, legal); -32 768 and 32 768 (over the cap:
               ``OVER_SPAN``, not in ``CASES``)
+  carry       spans of 255, 256, 257 and 513 intervals -- one short of a round of groups_scan_kernel's carry loop (256
+              intervals a round), exactly one, one over, and one over two: a peak in the first and in the last
+              interval and, where the span has them, in the intervals at offsets 255, 256 and 257 from the smallest
+              nominal, the first interval with two peaks. A wrong carry, or a wrong total of the peaks, shifts an id
   min_group_size 0, 1, 2, 100, n + 1 on the realistic mixture
   realistic   planted modification masses with Gaussian error on a uniform background
 """
@@ -137,6 +141,18 @@ def _build():
     wide = np.concatenate([rng.normal(-32768, 0.01, 40), rng.normal(32767, 0.01, 40), rng.normal(0, 0.01, 40)])
     assert np.rint(wide).min() == -32768 and np.rint(wide).max() == 32767
     C['span-65536'] = (wide, 5)
+    # ---- the scan's carry: peaks on both sides of every round boundary of the span
+    for span in (255, 256, 257, 513):
+        g0, at = -100.0, sorted({0, span - 1} | {k for k in (255, 256, 257) if k < span})
+        md = np.concatenate([_centres(g0 + k, {20: 1, 21: 4, 22: 1, **({60: 1, 61: 5, 62: 1} if k == 0 else {})})
+                             for k in at])
+        group, n_peaks, _, mass, size = R.ssm_groups(md, 1)
+        assert np.rint(md).max() - np.rint(md).min() + 1 == span and len(md) == 6 * len(at) + 7
+        assert n_peaks == len(at) + 1 and size.tolist() == [6, 7] + [6] * (len(at) - 1)
+        assert mass.tolist() == [R.edges(g0)[21], R.edges(g0)[61]] + [R.edges(g0 + k)[21] for k in at[1:]]
+        for j, k in enumerate(at[1:]):                    # the id an interval's rows get counts every peak before it
+            assert (group[np.rint(md) == g0 + k] == j + 2).all()
+        C[f'span-{span}'] = (md[rng.permutation(len(md))], 1)
     # ---- the realistic mixture, at every min_group_size
     mods = (0.0, 0.984, 15.9949, 42.0106, 79.9663, -17.0265, -18.0106, 1.0034, 14.0157)
     mix = np.concatenate([rng.normal(m, 0.002, k) for m, k in zip(mods, (900, 150, 400, 120, 99, 101, 60, 200, 30))]

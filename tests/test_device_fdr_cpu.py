@@ -371,6 +371,15 @@ def test_limits_come_before_the_device():
     assert L.asl_linear_scores(_lib.ptr(X), 4, 64, _lib.ptr(wb), 1, _lib.ptr(out[0])) == -4
     assert L.asl_linear_scores(_lib.ptr(X), 4, 2, _lib.ptr(wb), 0, _lib.ptr(out[0])) == -1
     assert b'at most 63' in L.asl_last_error() or b'needs' in L.asl_last_error()
+    # the texts of the shape check the two entry points share with the forest's: no row limit is named here
+    err = L.asl_last_error
+    assert fit(d=64) == -4 and err() == b'l2svm_fit: d = 64, at most 63'
+    assert fit(P=33) == -4 and err() == b'l2svm_fit: P = 33, at most 32'
+    assert fit(n=-1) == -1 and err() == b'l2svm_fit: needs d >= 1, P >= 1, n >= 0'
+    assert L.asl_linear_scores(_lib.ptr(X), 4, 2, _lib.ptr(wb), 0, _lib.ptr(out[0])) == -1
+    assert err() == b'linear_scores: needs d >= 1, P >= 1, n >= 0'
+    assert L.asl_linear_scores(_lib.ptr(X), 4, 2, _lib.ptr(wb), 33, _lib.ptr(out[0])) == -4
+    assert err() == b'linear_scores: P = 33, at most 32'
 
 
 # ------------------------------------------------------------------ an empty level, a sharded engine

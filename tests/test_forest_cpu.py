@@ -381,14 +381,24 @@ def test_limits_come_before_the_device():
     assert b'at most' in L.asl_last_error()
     assert fit(d=0) == INVALID and fit(P=0) == INVALID and fit(n=-1) == INVALID and fit(n=1 << 31) == INVALID
     assert fit(trees=0) == INVALID and fit(depth=0) == INVALID
+    # the texts of the shape check the three entry points share with the SVM's: this unit's also name the row limit
+    err = L.asl_last_error
+    assert fit(d=64) == CAPACITY and err() == b'forest_fit: d = 64, at most 63'
+    assert fit(P=33) == CAPACITY and err() == b'forest_fit: P = 33, at most 32'
+    assert fit(n=1 << 31) == INVALID and err() == b'forest_fit: needs d >= 1, P >= 1, 0 <= n < 2^31'
 
     def predict(n=4, d=2, P=1, depth=1):
         return L.asl_forest_predict(_lib.ptr(bins), n, d, C.byref(ms), P, depth, _lib.ptr(out))
     assert predict(d=64) == CAPACITY and predict(P=33) == CAPACITY and predict(depth=13) == CAPACITY
     assert predict(d=0) == INVALID and predict(n=-1) == INVALID and predict(depth=-1) == INVALID
+    assert predict(n=-1) == INVALID and err() == b'forest_predict: needs d >= 1, P >= 1, 0 <= n < 2^31'
+    assert predict(P=33) == CAPACITY and err() == b'forest_predict: P = 33, at most 32'
     assert predict(n=0) == 0                                     # nothing to do, no device asked for
     X, edges, ne = np.zeros((4, 2)), np.zeros((2, 255)), np.zeros(2, np.int32)
     ob = np.zeros((4, 64), np.uint8)
     assert L.asl_forest_bin(_lib.ptr(X), 4, 64, _lib.ptr(edges), _lib.ptr(ne), _lib.ptr(ob)) == CAPACITY
     assert L.asl_forest_bin(_lib.ptr(X), 4, 0, _lib.ptr(edges), _lib.ptr(ne), _lib.ptr(ob)) == INVALID
     assert L.asl_forest_bin(_lib.ptr(X), -1, 2, _lib.ptr(edges), _lib.ptr(ne), _lib.ptr(ob)) == INVALID
+    assert err() == b'forest_bin: needs d >= 1, P >= 1, 0 <= n < 2^31'
+    assert L.asl_forest_bin(_lib.ptr(X), 4, 64, _lib.ptr(edges), _lib.ptr(ne), _lib.ptr(ob)) == CAPACITY
+    assert err() == b'forest_bin: d = 64, at most 63'

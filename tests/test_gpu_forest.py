@@ -133,14 +133,16 @@ def test_binning_equals_the_restatement(n, d):
 def test_bad_values_are_refused_before_anything_runs():
     from ann_solo_amd import _lib
     (bins, n_bins, label, cw), _ = _case(63, 6, 3, 3, 5)
-    with pytest.raises(_lib.AnnSoloMiError, match='label'):
+    p, i = (int(v[0]) for v in np.nonzero(label))                # the first row that carries a label
+    text = r'forest_fit: label\[%d, %d\] = %d, not in \{-1, 0, \+1\}' % (p, i, 2 * label[p, i])
+    with pytest.raises(_lib.AnnSoloMiError, match=text):
         _lib.forest_fit(bins, 6, (label * 2).astype(np.int8), cw, trees=1)
-    with pytest.raises(_lib.AnnSoloMiError, match='label'):
+    with pytest.raises(_lib.AnnSoloMiError, match=text):
         _lib.forest_fit(bins, 6, torch.from_numpy((label * 2).astype(np.int8)).cuda(), cw, trees=1)
     for bad in (-1.0, np.nan, np.inf):
         w = cw.copy()
         w[1, 0] = bad
-        with pytest.raises(_lib.AnnSoloMiError, match='class weights'):
+        with pytest.raises(_lib.AnnSoloMiError, match='forest_fit: class weights must be finite and >= 0'):
             _lib.forest_fit(bins, 6, label, w, trees=1)
     few = n_bins.copy()
     few[2] = 100                                                 # column 2 holds bins up to 254

@@ -115,11 +115,11 @@ def test_limits_return_their_code_and_write_nothing():
         lab[1, 39] = bad
         assert fit(label=lab) == INVALID
         assert fit(label=lab, device=True) == INVALID
-    assert b'label[1, 39]' in L.asl_last_error()
+    assert L.asl_last_error() == b'l2svm_fit: label[1, 39] = -128, not in {-1, 0, +1}'
     for bad in (-0.5, np.nan, np.inf, -np.inf):
         cw = np.ones((2, 2))
         cw[1, 0] = bad
-        assert fit(cw=cw) == INVALID
+        assert fit(cw=cw) == INVALID and L.asl_last_error() == b'l2svm_fit: class weights must be finite and >= 0'
         assert fit(C_=bad) == INVALID
     assert fit(gtol=-1.0) == INVALID and fit(gtol=np.nan) == INVALID and fit(cap=-1) == INVALID
     assert fit(wb=np.full((2, 4), np.nan)) == INVALID
