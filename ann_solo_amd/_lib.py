@@ -97,6 +97,7 @@ EXPORTS = [
     'asl_ssm_groups',
     'asl_mgf_measure', 'asl_mgf_fill', 'asl_mgf_sort', 'asl_mgf_number',
     'asl_mgf_sort_charged', 'asl_sptxt_measure', 'asl_sptxt_fill', 'asl_sptxt_fragment_charge',
+    'asl_mzml_measure', 'asl_mzml_fill', 'asl_mzml_inflate',
 ]
 
 SVM_MAX_DIM = 63          # include/annsolo_mi.h: ASL_SVM_MAX_DIM
@@ -361,6 +362,10 @@ def lib():
             L.asl_sptxt_measure.argtypes = [C.c_void_p, C.c_int64, C.c_int32, c_i64p]
             L.asl_sptxt_fill.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7
             L.asl_sptxt_fragment_charge.argtypes = [C.c_char_p, C.c_int32]
+        if hasattr(L, 'asl_mzml_measure'):
+            L.asl_mzml_measure.argtypes = [C.c_void_p, C.c_int64, C.c_int32, c_i64p]
+            L.asl_mzml_fill.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 14
+            L.asl_mzml_inflate.argtypes = [C.c_char_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, c_i64p]
         if hasattr(L, 'asl_index_set_by_residual'):
             L.asl_index_set_by_residual.argtypes = [C.c_void_p, C.c_int32]
             L.asl_index_get_by_residual.argtypes = [C.c_void_p]
@@ -703,6 +708,29 @@ def sptxt_fragment_charge(annotation) -> int:
     peak line (bytes or str); 0 = unannotated. Host only: needs no GPU."""
     b = annotation.encode('utf-8') if isinstance(annotation, str) else bytes(annotation)
     return int(lib().asl_sptxt_fragment_charge(b, len(b)))
+
+
+MZML_MAX_TAG = 4096       # ASL_MZML_MAX_TAG
+MZML_SMALL_PEAKS = 512    # ASL_MZML_SMALL_PEAKS
+MZML_INF_TEXT = {1: 'a byte that is not base64', 2: 'base64 of a length that is no multiple of 4',
+                 3: 'base64 padding inside the text', 4: 'a compressed stream longer than the array allows',
+                 5: 'a bad zlib header', 6: 'an invalid DEFLATE block type', 7: 'invalid stored block lengths',
+                 8: 'an invalid set of code lengths', 9: 'an invalid code', 10: 'a distance too far back',
+                 11: 'a truncated zlib stream', 12: 'more values than defaultArrayLength',
+                 13: 'a wrong Adler-32', 14: 'fewer values than defaultArrayLength'}      # ASL_MZML_INF_*
+
+
+def mzml_inflate(b64, use_zlib: bool, cap: int):
+    """``asl_mzml_inflate``: the characters ``b64`` of one ``<binary>`` as the device decodes them -- base64, then
+    zlib where ``use_zlib`` -- into at most ``cap`` bytes: ``(0, bytes)`` or ``(code, None)``, ``code`` a key of
+    ``MZML_INF_TEXT``. Host only: needs no GPU."""
+    b = b64.encode('ascii') if isinstance(b64, str) else bytes(b64)
+    out = C.create_string_buffer(max(int(cap), 1))
+    n_out = C.c_int64(0)
+    rc = lib().asl_mzml_inflate(b, len(b), int(bool(use_zlib)), out, int(cap), byref(n_out))
+    if rc < 0:
+        raise ValueError('asl_mzml_inflate: an invalid argument')
+    return (0, out.raw[:n_out.value]) if rc == 0 else (rc, None)
 
 
 def ssm_groups(mass_diff, min_group_size: int, profile: bool = False):

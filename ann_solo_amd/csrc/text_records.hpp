@@ -1,5 +1,5 @@
 // text_records.hpp -- what the readers of record-structured text share beyond the scans of text_scan.hpp (mgf.hip,
-// sptxt.hip): the counts scan's operator, the result block of a measure, the guard of a line walk, the peak and
+// sptxt.hip, mzml.hip; a "line" here is the format's unit: mzml.hip's is a tag): the counts scan's operator, the result block of a measure, the guard of a line walk, the peak and
 // deferred-token stores, the capacity check, and on the host the workspace of a measured chunk with the grammar-free
 // parts of asl_*_measure / asl_*_fill. gfx950 only. Everything here has internal linkage, as in text_scan.hpp; the
 // grammars -- what a line is, what opens and closes a record -- stay in their units.
@@ -19,7 +19,7 @@ struct TextFinal {   // written by the line, resolve and capacity kernels
   unsigned long long err;   // (line << 8 | kind) of the first structural error, ~0: none
   uint32_t n_peaks, n_def;  // before the first record that is not closed
   uint32_t cap_rec;         // first record above ASL_MGF_MAX_PEAKS, ~0: none
-  uint32_t long_line;       // first line above ASL_MGF_MAX_LINE bytes, ~0: none
+  uint32_t long_line;       // first line (unit) above its cap in bytes, ~0: none
 };
 
 // The counts scan over a format's totals: the fields named in Sum are summed, of cons_byte and cons_line (byte and
@@ -61,8 +61,9 @@ __device__ __forceinline__ void put_deferred(int32_t *__restrict__ rec, uint32_t
   o[0] = (int32_t)begin, o[1] = (int32_t)(end - begin), o[2] = dest, o[3] = (int32_t)index, o[4] = (int32_t)line;
 }
 
-// close_last: the file's end closes the last record, at peak slot end_peaks (else every record has its end already)
-__global__ __launch_bounds__(SCAN_NT) void text_capacity_kernel(const uint32_t *__restrict__ peak_begin,
+// close_last: the file's end closes the last record, at peak slot end_peaks (else every record has its end already).
+// (unused by mzml.hip, whose peak counts are an attribute of the record.)
+__attribute__((unused)) __global__ __launch_bounds__(SCAN_NT) void text_capacity_kernel(const uint32_t *__restrict__ peak_begin,
                                                               uint32_t *__restrict__ peak_end, uint32_t n_rec,
                                                               int close_last, uint32_t end_peaks,
                                                               TextFinal *__restrict__ fin) {
@@ -128,15 +129,15 @@ int measure_lines(W &w, int64_t nl) {
   return ASL_OK;
 }
 
-// The result block read back (the call's last synchronisation); a line above the cap fails the call here, before
-// the format fills counts[].
+// The result block read back (the call's last synchronisation); a unit (a line, a tag) above its cap fails the call
+// here, before the format fills counts[].
 template <class W>
-int measure_final(const char *who, W &w, TextFinal *F) {
+int measure_final(const char *who, W &w, TextFinal *F, const char *unit = "line", int cap = ASL_MGF_MAX_LINE) {
   HIP_TRY(hipMemcpyAsync(F, w.fin.p, sizeof(*F), hipMemcpyDeviceToHost, stream()));
   ASL_TRY(sync_stream());
   if (F->long_line != ~0u)
-    return fail(ASL_ERR_CAPACITY, "%s_measure: line %u of the chunk is longer than %d bytes", who,
-                (unsigned)F->long_line + 1u, ASL_MGF_MAX_LINE);
+    return fail(ASL_ERR_CAPACITY, "%s_measure: %s %u of the chunk is longer than %d bytes", who, unit,
+                (unsigned)F->long_line + 1u, cap);
   return ASL_OK;
 }
 
@@ -144,14 +145,14 @@ int measure_final(const char *who, W &w, TextFinal *F) {
 // the format calls a record), and the measured chunk remembered for the fill.
 template <class W>
 int measure_end(const char *who, const char *noun, W &w, const TextFinal &F, const uint8_t *text, int64_t n,
-                int64_t *counts) {
+                int64_t *counts, const char *peaks = "peak lines") {
   if (F.err != ~0ull) {
     counts[ASL_MGF_ERR_KIND] = (int64_t)(F.err & 255u);
     counts[ASL_MGF_ERR_LINE] = (int64_t)(F.err >> 8);
   }
   if (F.cap_rec != ~0u)
-    return fail(ASL_ERR_CAPACITY, "%s_measure: %s %u of the chunk has more than %d peak lines", who, noun,
-                (unsigned)F.cap_rec + 1u, ASL_MGF_MAX_PEAKS);
+    return fail(ASL_ERR_CAPACITY, "%s_measure: %s %u of the chunk has more than %d %s", who, noun,
+                (unsigned)F.cap_rec + 1u, ASL_MGF_MAX_PEAKS, peaks);
   w.text = text, w.n = n, w.n_lines = counts[ASL_MGF_N_LINES], w.n_rec = (uint32_t)counts[ASL_MGF_N_SPECTRA];
   w.n_peaks = (uint32_t)counts[ASL_MGF_N_PEAKS], w.n_def = (uint32_t)counts[ASL_MGF_N_DEFERRED];
   return ASL_OK;

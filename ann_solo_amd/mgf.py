@@ -7,7 +7,8 @@ classified and converted by the kernels of ``csrc/mgf.hip`` (``asl_mgf_measure``
 ``asl_mgf_sort``), and the raw pack goes to the existing ``process_spectra`` where it lies. The host's part: the
 header (a few lines before the first ``BEGIN IONS``), the few numerals the device defers (Python's ``float``),
 the identifiers (UTF-8 slices of the chunk) and the meta records. The chunk loop and what else is not about the
-dialect is ``text_reader.ChunkedReader``, shared with ``sptxt.py``; the sort is ``csrc/peak_sort.hip``.
+dialect is ``text_reader.ChunkedReader``, shared with ``sptxt.py``, and what follows the parse
+``text_reader.QueryReader``, shared with ``mzml.py``; the sort is ``csrc/peak_sort.hip``.
 
 The dialect is stated in ``include/annsolo_mi.h`` and restated in ``tests/mgf_ref.py``. pyteomics is not a
 dependency: the statement is unpinned, like FAISS and spectrum_utils elsewhere in this package.
@@ -23,11 +24,10 @@ import torch
 
 from . import _lib
 from .packed import PackedSpectra
-from .text_reader import MAX_CHUNK, N_DEFERRED, N_PEAKS, N_RECORDS, OPEN, ChunkedReader, _float, opt
+from .text_reader import MAX_CHUNK, N_DEFERRED, N_PEAKS, N_RECORDS, OPEN, QueryReader, _float, opt
 
 SCAN_TILE = _lib.MGF_TILE           # lines per workgroup of the reader's scans (ASL_MGF_TILE)
 MAX_PEAKS = _lib.MGF_MAX_PEAKS      # peak lines of one spectrum (ASL_MGF_MAX_PEAKS)
-PROCESS_ROWS = 1 << 17              # spectra per ``process_spectra`` call
 
 _DEST_MZ, _DEST_INTENSITY, _DEST_PEPMASS, _DEST_RT, _DEST_NONE = range(5)
 _ERR_TEXT = {1: 'BEGIN IONS inside a block', 2: 'a peak line with one token'}
@@ -67,17 +67,12 @@ class _Header:
                 self.params[k.lower()] = v.strip()
 
 
-class _Reader(ChunkedReader):
+class _Reader(QueryReader):
     PREFIX, RECORD, COUNT_KEY, ERR_TEXT = 'MGF: ', 'a block of spectrum', 'n_spectra', _ERR_TEXT
 
     def __init__(self, config, device, stats: Optional[dict], keep_raw: bool = False):
-        from .config import Config
-        super().__init__(device, stats)
-        self.config = Config.from_reference(config)
-        self.raw = [] if keep_raw else None     # the chunks' raw packs instead of the preprocessing
+        super().__init__(config, device, stats, keep_raw)
         self.header = _Header()
-        self.pieces: Dict[int, List[PackedSpectra]] = {}
-        self.metas: Dict[int, List[dict]] = {}
 
     # ------------------------------------------------------------------ one chunk
     def measure(self, text: torch.Tensor, n: int, last: bool) -> np.ndarray:
@@ -160,10 +155,7 @@ class _Reader(ChunkedReader):
                             torch.as_tensor(pz_h, device=dev))
         self._sync()
         t1 = time.perf_counter()
-        if self.raw is not None:
-            self.raw.append((raw, np.where(rt_none, np.nan, rt_h), ids))
-        else:
-            self._preprocess(raw, pz_h, pmz_h, rt_h, rt_none, ids)
+        self.take(raw, pz_h, pmz_h, rt_h, rt_none, ids, self.rec0 + 1 + np.arange(ns))
         self.account(t0, t1, ns, npk, nd, int(n_sorted.value))
 
     def _identifiers(self, buf, ident_h, hp, errors, behind) -> List[Optional[str]]:
@@ -185,62 +177,15 @@ class _Reader(ChunkedReader):
                 ids.append(None)
         return ids
 
-    def _preprocess(self, raw: PackedSpectra, pz_h, pmz_h, rt_h, rt_none, ids) -> None:
-        """``pack_queries`` from the raw pack on: unknown charges entered at 2 and 3, ``process_spectra``, the
-        invalid copies dropped, rows and meta records appended per charge."""
-        from .spectrum import process_spectra
-        ns = raw.n
-        unknown = pz_h == 0
-        reps = np.where(unknown, 2, 1)
-        rows = np.repeat(np.arange(ns), reps)
-        z = np.repeat(pz_h, reps).astype(np.int32)
-        if unknown.any():
-            second = np.r_[False, rows[1:] == rows[:-1]]
-            z = np.where(np.repeat(unknown, reps), np.where(second, 3, 2), z).astype(np.int32)
-        for a in range(0, len(rows), PROCESS_ROWS):
-            r, zz = rows[a:a + PROCESS_ROWS], z[a:a + PROCESS_ROWS]
-            part = raw if (len(r) == ns and not unknown.any()) else raw.select(torch.as_tensor(r))
-            part = PackedSpectra(part.offsets, part.mz, part.intensity, part.charge, part.precursor_mz,
-                                 torch.as_tensor(zz, device=self.device))
-            out, valid = process_spectra(part, False, self.config, self.device)
-            ok = valid.cpu().numpy()
-            keep = np.nonzero(ok)[0]
-            _, first_at = np.unique(zz[keep], return_index=True)
-            for j in np.sort(first_at):                   # charges in order of first appearance
-                c = int(zz[keep[j]])
-                sel = keep[zz[keep] == c]
-                self.pieces.setdefault(c, []).append(out.select(torch.as_tensor(sel)).to('cpu'))
-                meta = self.metas.setdefault(c, [])
-                for s in r[sel].tolist():
-                    meta.append(dict(identifier=ids[s], index=self.rec0 + s + 1,
-                                     retention_time=None if rt_none[s] else float(rt_h[s]),
-                                     precursor_charge=c, precursor_mz=float(pmz_h[s])))
-
-    def result(self):
-        from .library_store import concat_packs
-        packs = {}
-        for c, meta in self.metas.items():
-            p = concat_packs(self.pieces[c])
-            packs[c] = PackedSpectra(p.offsets, p.mz, p.intensity, p.charge, p.precursor_mz, p.precursor_charge,
-                                     identifiers=[m['identifier'] for m in meta])
-        return packs, self.metas
-
 
 def read_mgf_raw(source, device='cuda', chunk_bytes: int = 256 << 20, stats: Optional[dict] = None):
     """The parse alone: ``(raw, retention_time, identifiers)`` -- the file's spectra as one raw
     ``PackedSpectra`` on ``device`` (what ``library_store.pack_raw`` makes of the reader's objects: float32
     peaks in file order, stably sorted by m/z where they descend; precursor charge 0 = unknown), the retention
     times (float64 numpy, NaN = none) and the identifiers. Arguments and errors as ``read_mgf_packed``."""
-    from .library_store import concat_packs
     reader = _Reader(None, device, stats, keep_raw=True)
     reader.read_source(source, chunk_bytes)
-    if not reader.raw:
-        z = lambda dt: torch.zeros(0, dtype=dt, device=reader.device)
-        return (PackedSpectra(torch.zeros(1, dtype=torch.int32, device=reader.device), z(torch.float32),
-                              z(torch.float32), z(torch.uint8), z(torch.float64), z(torch.int32)),
-                np.zeros(0, np.float64), [])
-    raw = concat_packs([r for r, _, _ in reader.raw])
-    return raw, np.concatenate([rt for _, rt, _ in reader.raw]), [i for _, _, ids in reader.raw for i in ids]
+    return reader.raw_result()[:3]
 
 
 def read_mgf_packed(source, config=None, device='cuda', chunk_bytes: int = 256 << 20, stats: Optional[dict] = None):

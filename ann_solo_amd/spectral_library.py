@@ -821,7 +821,8 @@ class SpectralLibrary:
         ``search_packed``. Queries are preprocessed in batches on the device, low-quality ones
         dropped (:225-228). With ``Config.device_mgf`` a file name ending in ``.mgf`` (any letter case)
         is read by ``mgf.read_mgf_packed`` -- parsed on the device, the same packed queries -- instead of
-        ``query_reader`` and ``pack_queries``. Returns the identifications as SSM records with the attributes
+        ``query_reader`` and ``pack_queries``; with ``Config.device_mzml`` a name ending in ``.mzml`` is read by
+        ``mzml.read_mzml_packed`` in the same way. Returns the identifications as SSM records with the attributes
         ``writer.write_mztab`` consumes (writer.py:129-148)."""
         if isinstance(query, dict):
             return self.search_packed(query, query_meta, library_meta, score_ssms)
@@ -832,6 +833,12 @@ class SpectralLibrary:
             from .mgf import read_mgf_packed
             logging.info('Process file %s', query)
             query_spectra, qmeta = read_mgf_packed(os.fspath(query), self.config, self.device)
+        elif (self.config.device_mzml and isinstance(query, (str, os.PathLike)) and
+                os.fspath(query).lower().endswith('.mzml')):
+            # tags parsed and arrays decoded by kernels (mzml.py)
+            from .mzml import read_mzml_packed
+            logging.info('Process file %s', query)
+            query_spectra, qmeta = read_mzml_packed(os.fspath(query), self.config, self.device)
         else:
             if isinstance(query, (str, os.PathLike)):
                 logging.info('Process file %s', query)

@@ -1,16 +1,18 @@
-"""What the readers of record-structured text files share on the host (``mgf.py``, ``sptxt.py``): the chunk loop --
-read, upload, measure, carry what the chunk does not close into the next one, double a chunk that closes nothing --
-and, per chunk, the tensors of a fill, the few numerals the device defers (Python's ``float``), the ranking of the
-errors and the ``stats``. The device's side of the same split is ``csrc/text_records.hpp``.
+"""What the readers of record-structured text files share on the host (``mgf.py``, ``sptxt.py``, ``mzml.py``): the
+chunk loop -- read, upload, measure, carry what the chunk does not close into the next one, double a chunk that closes
+nothing -- and, per chunk, the tensors of a fill, the few numerals the device defers (Python's ``float``), the ranking
+of the errors and the ``stats``. The device's side of the same split is ``csrc/text_records.hpp``. A "line" below is
+the format's unit: a line behind a ``\\n`` or, for mzML, a tag at a ``<``.
 
 A format subclasses ``ChunkedReader`` with its ``measure``, its ``chunk``, optionally ``before_chunk``, and the class
-attributes below; everything about its dialect stays in its module.
+attributes below; everything about its dialect stays in its module. ``QueryReader`` adds what the query formats
+(``mgf.py``, ``mzml.py``) share behind the parse: ``pack_queries`` from a chunk's raw pack on.
 """
 import io
 import math
 import os
 import time
-from typing import Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -44,6 +46,8 @@ class ChunkedReader:
     RECORD = ''                     # what does not fit a chunk: 'record' (its 1-based ordinal follows)
     COUNT_KEY = ''                  # the records' key in ``stats``: 'n_records'
     ERR_TEXT = {}                   # counts[ERR_KIND] -> message
+    UNIT = b'\n'                    # the byte that delimits the units: a line starts behind it; any other byte (a
+                                    # tag's b'<') starts its unit itself
 
     def __init__(self, device, stats: Optional[dict]):
         self.device = torch.device(device)
@@ -157,10 +161,14 @@ class ChunkedReader:
                 consumed, end_line = n, n_lines
             elif counts[OPEN]:
                 consumed, end_line = int(counts[CONSUMED]), int(counts[CONSUMED_LINES])
-            elif buf.endswith(b'\n'):       # no record is open: the chunk's whole lines
-                consumed, end_line = n, n_lines
-            else:                           # a cut last line: it may be the start of a record
-                consumed, end_line = buf.rfind(b'\n') + 1, n_lines - 1
+            elif self.UNIT == b'\n':
+                if buf.endswith(b'\n'):     # no record is open: the chunk's whole lines
+                    consumed, end_line = n, n_lines
+                else:                       # a cut last line: it may be the start of a record
+                    consumed, end_line = buf.rfind(b'\n') + 1, n_lines - 1
+            else:                           # the last unit may be cut anywhere: it comes again with the next chunk
+                cut = buf.rfind(self.UNIT)
+                consumed, end_line = (n, n_lines) if cut < 0 else (cut, n_lines - 1)
             if consumed == 0 and not last:  # one record (or line) does not fit: a larger chunk
                 if size >= MAX_CHUNK:
                     err = _lib.AnnSoloMiError(f'{self.PREFIX}{self.RECORD} {self.rec0 + 1} does not fit a chunk of '
@@ -189,3 +197,79 @@ class ChunkedReader:
                 self.read(f, chunk_bytes)
         else:
             self.read(io.BytesIO(bytes(source)), chunk_bytes)
+
+
+PROCESS_ROWS = 1 << 17              # spectra per ``process_spectra`` call
+
+
+class QueryReader(ChunkedReader):
+    """A reader of query files: its ``chunk`` hands every chunk's raw pack to ``take``, which keeps it
+    (``keep_raw``: the parse alone) or preprocesses it as ``library_store.pack_queries`` does."""
+
+    def __init__(self, config, device, stats: Optional[dict], keep_raw: bool = False):
+        from .config import Config
+        super().__init__(device, stats)
+        self.config = Config.from_reference(config)
+        self.raw = [] if keep_raw else None     # the chunks' raw packs instead of the preprocessing
+        self.pieces: Dict[int, List] = {}
+        self.metas: Dict[int, List[dict]] = {}
+
+    def take(self, raw, pz_h, pmz_h, rt_h, rt_none, ids, index) -> None:
+        if self.raw is not None:
+            self.raw.append((raw, np.where(rt_none, np.nan, rt_h), ids, np.asarray(index)))
+        else:
+            self._preprocess(raw, pz_h, pmz_h, rt_h, rt_none, ids, index)
+
+    def _preprocess(self, raw, pz_h, pmz_h, rt_h, rt_none, ids, index) -> None:
+        """``pack_queries`` from the raw pack on: unknown charges entered at 2 and 3, ``process_spectra``, the
+        invalid copies dropped, rows and meta records appended per charge. ``index``: the spectra's ``index``."""
+        from .packed import PackedSpectra
+        from .spectrum import process_spectra
+        ns = raw.n
+        unknown = pz_h == 0
+        reps = np.where(unknown, 2, 1)
+        rows = np.repeat(np.arange(ns), reps)
+        z = np.repeat(pz_h, reps).astype(np.int32)
+        if unknown.any():
+            second = np.r_[False, rows[1:] == rows[:-1]]
+            z = np.where(np.repeat(unknown, reps), np.where(second, 3, 2), z).astype(np.int32)
+        for a in range(0, len(rows), PROCESS_ROWS):
+            r, zz = rows[a:a + PROCESS_ROWS], z[a:a + PROCESS_ROWS]
+            part = raw if (len(r) == ns and not unknown.any()) else raw.select(torch.as_tensor(r))
+            part = PackedSpectra(part.offsets, part.mz, part.intensity, part.charge, part.precursor_mz,
+                                 torch.as_tensor(zz, device=self.device))
+            out, valid = process_spectra(part, False, self.config, self.device)
+            ok = valid.cpu().numpy()
+            keep = np.nonzero(ok)[0]
+            _, first_at = np.unique(zz[keep], return_index=True)
+            for j in np.sort(first_at):                   # charges in order of first appearance
+                c = int(zz[keep[j]])
+                sel = keep[zz[keep] == c]
+                self.pieces.setdefault(c, []).append(out.select(torch.as_tensor(sel)).to('cpu'))
+                meta = self.metas.setdefault(c, [])
+                for s in r[sel].tolist():
+                    meta.append(dict(identifier=ids[s], index=int(index[s]),
+                                     retention_time=None if rt_none[s] else float(rt_h[s]),
+                                     precursor_charge=c, precursor_mz=float(pmz_h[s])))
+
+    def result(self):
+        from .library_store import concat_packs
+        from .packed import PackedSpectra
+        packs = {}
+        for c, meta in self.metas.items():
+            p = concat_packs(self.pieces[c])
+            packs[c] = PackedSpectra(p.offsets, p.mz, p.intensity, p.charge, p.precursor_mz, p.precursor_charge,
+                                     identifiers=[m['identifier'] for m in meta])
+        return packs, self.metas
+
+    def raw_result(self):
+        """``(raw, retention_time, identifiers, index)`` of a ``keep_raw`` reader."""
+        from .library_store import concat_packs
+        from .packed import PackedSpectra
+        if not self.raw:
+            z = lambda dt: torch.zeros(0, dtype=dt, device=self.device)
+            return (PackedSpectra(torch.zeros(1, dtype=torch.int32, device=self.device), z(torch.float32),
+                                  z(torch.float32), z(torch.uint8), z(torch.float64), z(torch.int32)),
+                    np.zeros(0, np.float64), [], np.zeros(0, np.int64))
+        return (concat_packs([r[0] for r in self.raw]), np.concatenate([r[1] for r in self.raw]),
+                [i for r in self.raw for i in r[2]], np.concatenate([r[3] for r in self.raw]).astype(np.int64))

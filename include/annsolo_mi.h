@@ -1103,6 +1103,97 @@ int asl_sptxt_fill(const uint8_t *text, int64_t n,
  * the first '/', at most 255, and 1 without a '^' or without digits behind it. */
 int asl_sptxt_fragment_charge(const char *s, int32_t n);
 
+/* ------------------------------------------------------------------ mzML query files
+ * A chunk of an mzML file, resident in device memory, parsed and decoded by kernels (csrc/mzml.hip, csrc/inflate.hpp;
+ * DESIGN.md 3 "Query files") into the raw pack asl_process_batch takes. The dialect (what the reference's read_mzml
+ * reads through pyteomics' mzml.MzML, restated; tests/mzml_ref.py is the same statement in Python):
+ *   - The text is a sequence of tags, each starting at a '<' and ending at the first '>' outside quotes (" or ');
+ *     newlines mean nothing. A tag of more than ASL_MZML_MAX_TAG bytes: ASL_ERR_CAPACITY. The content of <binary>
+ *     runs from its '>' to the next '<'.
+ *   - Every <spectrum> element has the 0-based ordinal `index`, whatever its MS level. Only spectra with a cvParam
+ *     MS:1000511 of value "2" directly below <spectrum> are read; the others cost the tag pass alone. A
+ *     <spectrum> inside a <spectrum>: ASL_MZML_ERR_NESTED.
+ *   - Retention time: MS:1000016 in the first <scan>, value as written. Precursor m/z: MS:1000744 in the first
+ *     <selectedIon> of the first <precursor>; charge: MS:1000041 there (digits, 1 .. 255), else exactly one
+ *     MS:1000633, else unknown (0). Of a duplicated parameter the first wins. Numerals are converted as the MGF
+ *     reader's (asl_mgf_number), or deferred: their byte ranges are handed back.
+ *   - Arrays: the first <binaryDataArray> with MS:1000514 is m/z, the first with MS:1000515 intensity; precision
+ *     MS:1000523 (64-bit float) or MS:1000521 (32-bit float); compression MS:1000576 (none) or MS:1000574 (zlib).
+ *     Each holds exactly defaultArrayLength values; they become float32 by round-to-nearest, in file order.
+ *     Base64: the standard alphabet, '=' padding, blanks skipped. zlib: RFC 1950 (CM = 8, window <= 32 KiB,
+ *     FCHECK, no FDICT) around RFC 1951 (stored, fixed and dynamic blocks), Adler-32 verified; the stream of an
+ *     array of b bytes is at most b + b / 8 + 64 bytes long.
+ *   - Refused, per spectrum (ASL_MZML_E_*) or per array (ASL_MZML_INF_*): any other precision or compression
+ *     accession (integers, Numpress), a missing one, an arrayLength attribute, a <referenceableParamGroupRef>, a
+ *     missing array, scan start time or selected ion m/z, several MS:1000633 without a MS:1000041, a charge or a
+ *     defaultArrayLength that is not plain digits, and everything the decoders refuse. A comment or a CDATA section
+ *     after the first <spectrum is the structural error ASL_MZML_ERR_COMMENT.
+ * The calls go as for the MGF reader: asl_mzml_measure(text), asl_mzml_fill(the same text), the deferred numerals
+ * stored, asl_mgf_sort on the pack. A record is <spectrum ...> ... </spectrum>. */
+#define ASL_MZML_MAX_TAG 4096       /* bytes of one tag, '<' to '>': one thread walks a tag */
+#define ASL_MZML_SMALL_PEAKS 512    /* arrays up to this many values are decoded by the small-window kernel */
+/* counts[] of asl_mzml_measure: ASL_MGF_N_LINES (tags) .. ASL_MGF_OPEN as for the MGF reader (N_SPECTRA: the closed
+ * MS2 spectra; N_DEFERRED: 0), and */
+#define ASL_MZML_N_ELEMENTS 9       /* closed <spectrum> elements of every MS level */
+#define ASL_MZML_ERR_ELEMENT 10     /* <spectrum> elements of the chunk opened up to the structural error's tag */
+#define ASL_MZML_COUNTS 11
+#define ASL_MZML_ERR_NESTED 1       /* <spectrum> inside a <spectrum> */
+#define ASL_MZML_ERR_COMMENT 2      /* a comment or CDATA section after the first <spectrum */
+#define ASL_MZML_ERR_TAG 3          /* a tag inside a spectrum that the next '<' or the file's end cuts */
+/* errors[] of asl_mzml_fill, per spectrum. What fails while the reference iterates over the file ... */
+#define ASL_MZML_E_LENGTH 0x1       /* defaultArrayLength missing or not digits */
+#define ASL_MZML_E_NO_MZ 0x2        /* no m/z array, or one without <binary> */
+#define ASL_MZML_E_NO_INTENSITY 0x4
+#define ASL_MZML_E_PRECISION 0x8    /* missing or unsupported, on either array */
+#define ASL_MZML_E_COMPRESSION 0x10
+#define ASL_MZML_E_ARRAY_LENGTH 0x20 /* an arrayLength attribute on a <binaryDataArray> */
+#define ASL_MZML_E_PARAM_GROUP 0x40 /* <referenceableParamGroupRef> */
+#define ASL_MZML_E_FILE 0x7f
+/* ... and what fails after the identifier is read (a spectrum the identifier rule drops never gets here) */
+#define ASL_MZML_E_NO_RT 0x100
+#define ASL_MZML_E_NO_PRECURSOR 0x200
+#define ASL_MZML_E_CHARGES 0x400    /* several MS:1000633 without a MS:1000041 */
+#define ASL_MZML_E_CHARGE 0x800     /* a charge that is not digits in 1 .. 255 */
+/* flags[] of asl_mzml_fill, per spectrum */
+#define ASL_MZML_F_MZ_ZLIB 0x1
+#define ASL_MZML_F_MZ_F64 0x2
+#define ASL_MZML_F_INTENSITY_ZLIB 0x4
+#define ASL_MZML_F_INTENSITY_F64 0x8
+/* text: device memory, n bytes. last: bit 0: the chunk ends the file; bit 1: a <spectrum was seen before this chunk
+ * (a comment anywhere in it is refused). Errors as asl_mgf_measure, with ASL_MZML_MAX_TAG for ASL_MGF_MAX_LINE and
+ * defaultArrayLength for the peak lines. counts: [ASL_MZML_COUNTS], host. */
+int asl_mzml_measure(const uint8_t *text, int64_t n, int32_t last, int64_t *counts);
+/* The measured chunk into caller-allocated arrays, host or device memory; per MS2 spectrum s. identifier: the byte
+ * range (offset, length) of the id attribute's value, length -1 without one. element: the ordinal of the spectrum
+ * among the chunk's <spectrum> elements. numerals: (offset, length) of the scan start time's and of the selected
+ * ion m/z's value where the device deferred it (then the column holds NaN), length -1 elsewhere. array_errors:
+ * ASL_MZML_INF_* (csrc/inflate.hpp) of the m/z and of the intensity array, 0: decoded. A spectrum with errors[s] != 0
+ * or an array error has undefined peaks: the caller refuses it. The arrays are decoded by one thread each over global scratch
+ * (34 bytes a peak and 1.4 KiB an array, kept by the library); ASL_MZML_DECODE=wave in the environment decodes with
+ * one wavefront per array over LDS instead: the same core, the same bytes and error codes, measured slower
+ * (profiles/mzml_cost.json). */
+int asl_mzml_fill(const uint8_t *text, int64_t n,
+                  int32_t *offsets            /* [n_spectra + 1] */,
+                  float *mz                   /* [n_peaks] */,
+                  float *intensity            /* [n_peaks] */,
+                  uint8_t *charge             /* [n_peaks], zeros */,
+                  double *precursor_mz        /* [n_spectra] */,
+                  int32_t *precursor_charge   /* [n_spectra], 0: unknown */,
+                  double *retention_time      /* [n_spectra] */,
+                  int32_t *identifier         /* [n_spectra, 2] */,
+                  int32_t *first_tag          /* [n_spectra] */,
+                  int32_t *element            /* [n_spectra] */,
+                  int32_t *numerals           /* [n_spectra, 4] */,
+                  int32_t *errors             /* [n_spectra] */,
+                  int32_t *flags              /* [n_spectra] */,
+                  int32_t *array_errors       /* [n_spectra, 2] */);
+/* Host only: the decoder core of csrc/inflate.hpp as the device runs it, over one array's characters b64[0 .. n):
+ * base64, then zlib where zlib_flag != 0. out: [cap]; *n_out: the bytes written. Returns 0 or ASL_MZML_INF_*
+ * (1 bad byte, 2 length, 3 padding, 4 input too long, 5 zlib header, 6 block type, 7 stored lengths, 8 code
+ * lengths, 9 invalid symbol, 10 distance too far back, 11 truncated, 12 more than cap bytes, 13 Adler-32,
+ * 14 fewer bytes than expected), -1 for a null argument. */
+int asl_mzml_inflate(const uint8_t *b64, int64_t n, int32_t zlib_flag, uint8_t *out, int64_t cap, int64_t *n_out);
+
 /* ------------------------------------------------------------------ hot path
  * One batch of same-charge queries through
  *   SpectralLibrary._search_batch / _get_library_candidates
