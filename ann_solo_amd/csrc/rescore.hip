@@ -970,12 +970,23 @@ struct FlatLds {   // per wave
   uint32_t cmask[RF_NC][2];        // matched candidate peaks (<= 64)
   uint32_t emax[RF_NC];            // largest exponent byte of a product | bit 31: doubly matched peak
   uint32_t emin[RF_NC];
-  int base[RF_NC];                 // first peak in the library arrays
-  uint32_t rec[RF_NC];             // peaks | shifts << 8 | precursor charge << 16
-  uint16_t pref[RF_NC];            // first stream position
+  // where a candidate's peaks are: the address of its peak record, or (no records) its first peak
+  // in the library arrays
+  unsigned long long cptr[RF_NC];
+  // bits 0-23: rf_key(candidate, shifts) - first stream position, so that adding a stream position
+  // gives the peak's key (modulo 2^16); bits 24-31: peaks
+  uint32_t ckey[RF_NC];
   uint8_t owner[RF_PMAX];
-  uint16_t mq[RF_MQ];              // queued (peak | shift << 10) items whose bin is marked
+  uint16_t mq[RF_MQ];              // queued (peak of its candidate | candidate << 6 | shift << 11) items whose bin is marked
 };
+
+// (a peak record's address comes out of LDS as a number: these say that it is global memory)
+using gfloat_p = const __attribute__((address_space(1))) float *;
+using gbyte_p = const __attribute__((address_space(1))) uint8_t *;
+// What a stream step and a queued item need to know of a peak's candidate, in 16 bits: the peak's
+// index in the candidate (< 64) | the candidate's lane << 6 | the shifts it probes, as the bits
+// below S (S <= RF_SMAX), << 11.
+__device__ __forceinline__ uint32_t rf_key(int t, int S) { return ((uint32_t)t << 6) | (((1u << S) - 1u) << 11); }
 
 // Winner-only requests (`prune`, one block per query): a candidate deferred for a doubly matched
 // peak or a wide exponent span still has, in sum[], the sum of ALL its generated matches -- an upper
@@ -1183,9 +1194,11 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
       cmaxw = rl_i(wave_max_to_lane63(cmaxw), 63);     // (both >= 0)
       Smaxw = rl_i(wave_max_to_lane63(Smaxw), 63);
       if (take && hi == 0) {
-        Wv.base[t] = m_co;
-        Wv.rec[t] = (uint32_t)cn_eff | ((uint32_t)S << 8) | ((uint32_t)m_chg << 16);
-        Wv.pref[t] = (uint16_t)excl;
+        Wv.cptr[t] = (L.records && cv.flt.meta)
+                         ? (unsigned long long)(reinterpret_cast<const float *>(L.records) + (uint32_t)m_co)
+                         : (unsigned long long)(uint32_t)m_co;
+        // (a candidate with more shifts has no peak in the stream: cn_eff = 0)
+        Wv.ckey[t] = ((uint32_t)cn_eff << 24) | ((rf_key(t, min(S, RF_SMAX)) - (uint32_t)excl) & 0xffffffu);
         Wv.pmd[t] = pmd;
         Wv.sum[t] = 0.0;
         Wv.qmask[t][0] = Wv.qmask[t][1] = Wv.qmask[t][2] = Wv.qmask[t][3] = 0u;
@@ -1200,54 +1213,63 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
       if (Smaxw > 3) {          // wave-uniform: the fp64 division only where a charge-3 candidate is
         if (take && hi == 0) Wv.mdf[t][2] = (float)(pmd / 3.0);
       }
-      for (int j0 = 0; j0 < cmaxw; j0 += 2) {
-        const int j = j0 + hi;
-        if (take && j < cn_eff) Wv.owner[excl + j] = (uint8_t)t;
+      // (a lane past its candidate's last peak writes that peak's byte again: one predicate for the
+      // whole loop instead of one per store)
+      if (take && cn_eff > 0) {
+        for (int j0 = 0; j0 < cmaxw; j0 += 2) Wv.owner[excl + min(j0 + hi, cn_eff - 1)] = (uint8_t)t;
       }
       wave_sync();
 
       // ---- the chunk's peaks as one stream, loads one step ahead. The stream needs a peak's m/z
       // and fragment charge only; intensities are read by the drain, for the peaks that hit
       float n_cm = 0.0f;
-      int n_cc = 0, n_tt = 0;
-      uint32_t n_rec = 0;
+      int n_cc = 0;
+      uint32_t n_key = 0u;      // rf_key + the peak's index; 0 where the lane holds no peak: no shift is probed
       auto fetch = [&](int p0) {
-        const int p = p0 + lane;
-        const bool act = p < P;
-        n_tt = act ? (int)Wv.owner[p] : 0;
-        n_rec = act ? Wv.rec[n_tt] : 0u;
-        const int n_j = p - (int)Wv.pref[n_tt];
-        const int n_co = Wv.base[n_tt];
+        // A lane beyond the stream reads the stream's last peak again and gets the key 0: neither the
+        // table reads nor the loads need a predicate (P > 0 here).
+        const bool act = p0 + lane < P;
+        const int p = min(p0 + lane, P - 1);
+        const uint32_t n_tt = (uint32_t)Wv.owner[p];
+        const unsigned long long cp = Wv.cptr[n_tt];
+        const uint32_t ck = Wv.ckey[n_tt];
+        const uint32_t k = (ck + (uint32_t)p) & 0xffffu;
+        const int n_j = (int)(k & 63u);
+        n_key = act ? k : 0u;
         if (L.records && cv.flt.meta) {      // [mz x cn][charge x cn][intensity x cn], one record
-          const float *rf = reinterpret_cast<const float *>(L.records) + (uint32_t)n_co;
-          const int cnr = (int)(n_rec & 0xffu);
-          n_cm = act ? rf[n_j] : 0.0f;
-          n_cc = act ? (int)reinterpret_cast<const uint8_t *>(rf)[4 * cnr + n_j] : 0;
+          const gfloat_p rf = (gfloat_p)cp;
+          const int cnr = (int)(ck >> 24);
+          n_cm = rf[n_j];
+          n_cc = (int)((gbyte_p)rf)[4 * cnr + n_j];
         } else {
-          n_cm = act ? L.mz[n_co + n_j] : 0.0f;
-          n_cc = (act && L.charge) ? (int)L.charge[n_co + n_j] : 0;
+          const int n_co = (int)(uint32_t)cp;
+          n_cm = L.mz[n_co + n_j];
+          n_cc = L.charge ? (int)L.charge[n_co + n_j] : 0;
         }
       };
-      // ---- queued (peak, shift) items, a row at a time: everything about the item is looked up
-      // again (the peak's values come from the lines the stream has just read)
+      // ---- queued (peak, shift) items, a row at a time: an item names its candidate and its peak
+      // there (the peak's values come from the lines the stream has just read)
       int mq_n = 0;
       auto drain = [&]() {
         wave_sync();
         for (int e0 = 0; e0 < mq_n; e0 += 64) {
           const bool on = e0 + lane < mq_n;
-          const uint32_t ent = on ? (uint32_t)Wv.mq[e0 + lane] : 0u;
-          const int s = (int)(ent >> 10), p = (int)(ent & 1023u);
-          const int tt = (int)Wv.owner[p];
-          const int j = p - (int)Wv.pref[tt], co = Wv.base[tt];
-          const int cn = (int)(Wv.rec[tt] & 0xffu);
+          // Read by every lane: e0 is a multiple of 64 below mq_n <= RF_MQ, so e0 + lane < RF_MQ, and a
+          // stale or never written item beyond mq_n is masked into the tables (tt < RF_NC); whatever is
+          // dereferenced from it sits under `on`.
+          static_assert(RF_MQ % 64 == 0 && RF_MQ >= 128, "the drain reads the queue in rows of 64; a probe appends up to 64");
+          const uint32_t ent = (uint32_t)Wv.mq[e0 + lane];
+          const int s = on ? (int)(ent >> 11) : 0, tt = (int)((ent >> 6) & (uint32_t)(RF_NC - 1)), j = (int)(ent & 63u);
+          const unsigned long long cp = Wv.cptr[tt];
+          const int co = (int)(uint32_t)cp, cn = (int)(Wv.ckey[tt] >> 24);
           float cm = 0.0f, ci = 0.0f;
           int cc = 0;
           if (on) {
             if (L.records && cv.flt.meta) {
-              const float *rf = reinterpret_cast<const float *>(L.records) + (uint32_t)co;
+              const gfloat_p rf = (gfloat_p)cp;
               cm = rf[j];
               ci = rf[rec_int0(cn) + j];
-              cc = (int)reinterpret_cast<const uint8_t *>(rf)[4 * cn + j];
+              cc = (int)((gbyte_p)rf)[4 * cn + j];
             } else {
               cm = L.mz[co + j];
               ci = L.intensity[co + j];
@@ -1258,7 +1280,10 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
             const float mdv = s ? Wv.mdf[tt][s - 1] : 0.0f;
             const int b = (int)floorf((cm + mdv) * inv_w_f);
             const double pm = Wv.pmd[tt];
-            const double md = s == 0 ? 0.0 : s == 1 ? pm : s == 2 ? pm * 0.5 : s == 4 ? pm * 0.25 : pm / (double)s;
+            // mass_diff[s] = pmd / s: exact scalings but for s = 3, and a shift beyond 2 is queued only in
+            // a chunk that holds a candidate of charge >= 3 (wave-uniform, as at the set-up)
+            double md = s == 0 ? 0.0 : s == 2 ? pm * 0.5 : pm;
+            if (Smaxw > 3) md = s == 3 ? pm / 3.0 : s == 4 ? pm * 0.25 : md;
             const double mult = (s == 0 || cc == s) ? 1.0 : 2.0 / 3.0;
             uint32_t h = hbin(b);
             for (;;) {
@@ -1275,10 +1300,7 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
                   // must pass the window test too (differs only on fp boundaries)
                   bool run = true;
                   for (int jj = j; jj > 0; --jj) {
-                    const float *pm_ = (L.records && cv.flt.meta)
-                                           ? reinterpret_cast<const float *>(L.records) + (uint32_t)co
-                                           : L.mz + co;
-                    const double xp = (double)pm_[jj - 1] + md;
+                    const double xp = (double)((L.records && cv.flt.meta) ? ((gfloat_p)cp)[jj - 1] : L.mz[co + jj - 1]) + md;
                     if (lim > xp) break;
                     if (!(fabs(qm - xp) <= tl)) {
                       run = false;
@@ -1311,29 +1333,59 @@ __global__ __launch_bounds__(64 * RS_WAVES, RF_OCC) void rescore_flat_kernel(
       if (P > 0) fetch(0);
       for (int p0 = 0; p0 < P; p0 += 64) {
         const float cm = n_cm;
-        const int cc = n_cc, tt = n_tt;
-        const int Sc = (int)((n_rec >> 8) & 0xffu);
-        const bool act = p0 + lane < P;
+        const int cc = n_cc;
+        const uint32_t key = n_key;
         if (p0 + 64 < P) fetch(p0 + 64);
         // shifts this peak takes part in (cpp:58-75): every s < S for an unannotated peak, else
-        // s = 0 and s = its fragment charge. A (peak, shift) whose bin is marked goes to the
-        // wave's queue; the probing proper runs over full rows of queued items (drain) instead
-        // of inside this loop with the one or two lanes that hit.
-        const uint32_t smask = !act ? 0u : cc == 0 ? (1u << Sc) - 1u : (1u | (cc < Sc ? 1u << cc : 0u));
-        auto probe = [&](int s, float mdv) {
-          const bool can = (smask >> s) & 1u;
-          const int b = (int)floorf((cm + mdv) * inv_w_f);
-          const bool maybe = can && bm_test(H, b);
-          const unsigned long long mm = __ballot(maybe);
-          if (!mm) return;                        // wave-uniform
+        // s = 0 and s = its fragment charge where that is < S (none where the lane holds no peak: the
+        // key is 0). As bits below S, so that no lane branches: a charge byte beyond 31 is a bit
+        // beyond every S
+        const uint32_t sall = key >> 11;
+        const uint32_t smask = (cc == 0 ? sall : (1u | (1u << min(cc, 31)))) & sall;
+        // The bins of all the chunk's shifts are tested first, by every lane and without a branch (a
+        // bin index is masked into the bitmap): the bitmap reads are in flight together, behind one
+        // read of the candidate's shift table.
+        auto bin_of = [&](float mdv) -> int { return (int)floorf((cm + mdv) * inv_w_f); };
+        auto bm_word = [&](int b) -> uint32_t { return H.bm[(b >> 5) & (RS_BM_BITS / 32 - 1)]; };
+        auto bm_bit = [&](uint32_t w, int b) -> uint32_t { return __builtin_amdgcn_ubfe(w, (uint32_t)b, 1u); };   // (bit b & 31)
+        const int b0 = (int)floorf(cm * inv_w_f);      // (the bin of cm + 0.0f, also for -0.0f)
+        uint32_t hits;
+        if (Smaxw > 1) {          // wave-uniform
+          const float *mr = Wv.mdf[(key >> 6) & (uint32_t)(RF_NC - 1)];
+          const float2 m12 = *reinterpret_cast<const float2 *>(mr);
+          const int b1 = bin_of(m12.x), b2 = bin_of(m12.y);
+          const uint32_t w0 = bm_word(b0), w1 = bm_word(b1), w2 = bm_word(b2);
+          hits = bm_bit(w0, b0) | (bm_bit(w1, b1) << 1) | (bm_bit(w2, b2) << 2);
+          if (Smaxw > 3) {
+            const float2 m34 = *reinterpret_cast<const float2 *>(mr + 2);
+            const int b3 = bin_of(m34.x), b4 = bin_of(m34.y);
+            const uint32_t w3 = bm_word(b3), w4 = bm_word(b4);
+            hits |= (bm_bit(w3, b3) << 3) | (bm_bit(w4, b4) << 4);
+          }
+        } else {
+          hits = bm_bit(bm_word(b0), b0);
+        }
+        hits &= smask;
+        // A (peak, shift) whose bin is marked goes to the wave's queue, shift by shift; the probing
+        // proper runs over full rows of queued items (drain) instead of inside this loop with the one
+        // or two lanes that hit.
+        const uint32_t item = key & 0x7ffu;
+        for (int s = 0; s < Smaxw; ++s) {        // wave-uniform bound
+          uint32_t hs = hits & (1u << s);
+          // (keeps `hs` one value, so that the ballot and the store share one v_and + v_cmp: 2 vector
+          // instructions a shift instead of the 5 the compiler makes of two separate bit tests
+          // (profiles/rescore_flat_diet_isa.txt). Results do not depend on it: removing the line is safe.)
+          asm volatile("" : "+v"(hs));
+          const unsigned long long mm = __ballot(hs != 0u);
+          if (!mm) continue;                      // wave-uniform
           const int c = __popcll(mm);
           if (mq_n + c > RF_MQ) drain();
-          if (maybe)
-            Wv.mq[mq_n + __popcll(mm & ((1ull << lane) - 1ull))] = (uint16_t)((p0 + lane) | (s << 10));
+          if (hs) {
+            const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, (uint32_t)mq_n));
+            Wv.mq[at] = (uint16_t)(item | ((uint32_t)s << 11));
+          }
           mq_n += c;
-        };
-        probe(0, 0.0f);
-        for (int s = 1; s < Smaxw; ++s) probe(s, Wv.mdf[tt][s - 1]);        // wave-uniform bound
+        }
       }
       drain();
       wave_sync();
