@@ -21,9 +21,13 @@
 //     nothing for the value (a DPP operand of the v_fmac). Entries beyond a query's count are
 //     (dimension 0, value +0): fmaf(+0, c, acc) leaves acc unchanged, bit for bit.
 // Per step and wave: 1 v_add_u32_dpp (address) + 1 ds_read_b64 + 2 v_fmac_f32_dpp for 4 queries
-// x 32 lists, eight reads in flight -- 16 x fewer multiply-adds than the GEMM. The kernel is
-// LDS-bound (13.4 GB of tile reads per 16 384 queries x 4 096 lists = 85 us at 256 B/clk/CU):
-// 0.23 ms measured against 0.86 ms for the dense MFMA GEMM at 125 TFLOP/s.
+// x 32 lists, eight reads in flight -- 16 x fewer multiply-adds than the GEMM. The kernel is at
+// VECTOR ISSUE, not at LDS bandwidth (13.4 GB of tile reads per 16 384 queries x 4 096 lists are
+// 85 us at 256 B/clk/CU): 3.7 vector instructions per LDS instruction, the vector unit active 3.2
+// times as long as the LDS unit (profiles/coarse_select_before_after.txt); the three DPP
+// instructions of its 58.7 M wave-steps alone, at the DPP issue rate, are 0.31 ms of the 0.50 ms a
+// 32 768-query batch takes. 0.23 ms at 16 384 queries against 0.86 ms for the dense MFMA GEMM at
+// 125 TFLOP/s.
 // Queries with more than 64 non-zeros (none among processed spectra: max_peaks_used = 50) are
 // walked entry by entry from the dense row instead.
 #include "common.hpp"
@@ -242,15 +246,18 @@ int transpose_f32(const float *in, int rows, int cols, float *out) {
 // (Ct[d][nlist]); ent / cnt: scratch of nq * CS_CAP uint2 and nq ints; n_over: one int, left
 // holding the number of rows with more than CS_CAP non-zeros. With more than over_max such rows
 // the kernel leaves the batch alone (the caller's gated dense GEMM then runs instead): the
-// decision is taken on the device, nothing waits.
+// decision is taken on the device, nothing waits. lists_ready: ent / cnt / n_over hold the rows' lists already
+// (the encoder wrote them with the rows, encode.hip; n_over was zeroed in front of it): nothing is listed here.
 int coarse_sparse(const float *xq, int nq, int d, const float *Ct, int nlist, uint2 *ent,
-                  int32_t *cnt, int *n_over, int over_max, float *scores, int ld, int64_t ldq) {
+                  int32_t *cnt, int *n_over, int over_max, float *scores, int ld, int64_t ldq, bool lists_ready) {
   if (ldq <= 0) ldq = d;
   if (nq <= 0) return ASL_OK;
-  HIP_TRY(hipMemsetAsync(n_over, 0, sizeof(int), stream()));
-  hipLaunchKernelGGL(list_nonzeros_kernel, dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, stream(), xq,
-                     nq, d, ldq, ent, cnt, n_over);
-  ASL_CHECK_LAUNCH();
+  if (!lists_ready) {
+    HIP_TRY(hipMemsetAsync(n_over, 0, sizeof(int), stream()));
+    hipLaunchKernelGGL(list_nonzeros_kernel, dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, stream(), xq,
+                       nq, d, ldq, ent, cnt, n_over);
+    ASL_CHECK_LAUNCH();
+  }
   const int tiles = (int)cdiv(nlist, CS_TL);
   // one workgroup per CU (the tile fills LDS): cover the chip about twice over
   int parts = std::max(1, std::min((512 + tiles - 1) / tiles, (nq + 4 * CS_NW - 1) / (4 * CS_NW)));

@@ -162,8 +162,10 @@ constexpr int QE_DIM_SHIFT = 7;    // an entry holds dimension * 128: the byte o
 // cnt = their number or -1 - count beyond 64 -- exactly what list_nonzeros_kernel
 // (coarse_sparse.hip) makes of the dense row; the scans take their queries in this form, and a
 // sharded search encodes the other ranks' queries straight into it (no 3.2 KB row per query
-// written and read again).
-template <bool ENTRIES>
+// written and read again). DENSE_TOO (with ENTRIES): both, the entry list from the vector the wave holds in LDS --
+// the unsharded search's form: its coarse stage and scans read the lists, the gated GEMM and rows with more
+// than 64 non-zeros the dense row, and nothing lists the row again.
+template <bool ENTRIES, bool DENSE_TOO = false>
 __global__ __launch_bounds__(64 * ENC_WAVES) void encode_kernel(
     const float *__restrict__ mz, const float *__restrict__ inten,
     const int32_t *__restrict__ offsets, int32_t n, double min_bound, double bin_size,
@@ -222,10 +224,10 @@ __global__ __launch_bounds__(64 * ENC_WAVES) void encode_kernel(
     }
     nrm = __builtin_sqrtf(acc);
   }
-  if (!ENTRIES) {
+  if (!ENTRIES || DENSE_TOO) {
     float *row = out + (size_t)spec * hash_len;
     for (int i = lane; i < hash_len; i += 64) row[i] = norm ? vec[i] / nrm : vec[i];
-    return;
+    if (!ENTRIES) return;
   }
   // the entry list of the row the dense form would hold (the test is on the STORED value, as
   // list_nonzeros applies it: a component that underflows to zero in the division is no entry)
@@ -250,17 +252,16 @@ __global__ __launch_bounds__(64 * ENC_WAVES) void encode_kernel(
   }
 }
 
-template <bool ENTRIES>
-static int encode_launch(const float *mz, const float *inten, const int32_t *offsets, int32_t n,
+template <typename K>
+static int encode_launch(K kern, const float *mz, const float *inten, const int32_t *offsets, int32_t n,
                          double min_bound, double bin_size, int32_t hash_len, uint32_t seed, int norm,
                          float *out, uint2 *ent, int32_t *ent_cnt, int *n_over) {
   size_t lds = (size_t)ENC_WAVES * hash_len * sizeof(float);
   if (lds > 160 * 1024) return fail(ASL_ERR_CAPACITY, "encode: hash_len %d too large for LDS", hash_len);
   dim3 grid((unsigned)cdiv(n, ENC_WAVES));
   if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute((const void *)encode_kernel<ENTRIES>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(encode_kernel<ENTRIES>, grid, dim3(64 * ENC_WAVES), lds, stream(), mz, inten,
+    HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, grid, dim3(64 * ENC_WAVES), lds, stream(), mz, inten,
                      offsets, n, min_bound, bin_size, hash_len, seed, norm, out, ent, ent_cnt, n_over);
   ASL_CHECK_LAUNCH();
   return ASL_OK;
@@ -271,7 +272,7 @@ int encode_device(const float *mz, const float *inten, const int32_t *offsets, i
                   int norm, float *out) {
   if (n == 0) return ASL_OK;
   ProfScope ps("encode");
-  return encode_launch<false>(mz, inten, offsets, n, min_bound, bin_size, hash_len, seed, norm, out,
+  return encode_launch(encode_kernel<false>, mz, inten, offsets, n, min_bound, bin_size, hash_len, seed, norm, out,
                               nullptr, nullptr, nullptr);
 }
 
@@ -282,8 +283,18 @@ int encode_entries_device(const float *mz, const float *inten, const int32_t *of
                           uint2 *ent, int32_t *cnt, int *n_over) {
   if (n == 0) return ASL_OK;
   ProfScope ps("encode");
-  return encode_launch<true>(mz, inten, offsets, n, min_bound, bin_size, hash_len, seed, norm, nullptr,
-                             ent, cnt, n_over);
+  return encode_launch(encode_kernel<true>, mz, inten, offsets, n, min_bound, bin_size, hash_len, seed, norm,
+                       nullptr, ent, cnt, n_over);
+}
+
+// the dense rows AND their entry lists (n_over: a device int the caller has zeroed, not null)
+int encode_both_device(const float *mz, const float *inten, const int32_t *offsets, int32_t n,
+                       double min_bound, double bin_size, int32_t hash_len, uint32_t seed, int norm,
+                       float *out, uint2 *ent, int32_t *cnt, int *n_over) {
+  if (n == 0) return ASL_OK;
+  ProfScope ps("encode");
+  return encode_launch(encode_kernel<true, true>, mz, inten, offsets, n, min_bound, bin_size, hash_len, seed, norm, out,
+                       ent, cnt, n_over);
 }
 
 }  // namespace asl

@@ -41,6 +41,11 @@ struct IndexSearch {
   const int32_t *pre_I = nullptr;   // IVF-Flat reads pre_I alone
   const uint2 *pre_ent = nullptr;   // the queries as entry lists [nq, 64] + counts [nq] (list_nonzeros /
   const int32_t *pre_cnt = nullptr; // encode_entries_device); a hint when xq is given as well
+  // pre_ent / pre_cnt WITHOUT pre_I: lists ready, probes still to find -- the coarse stage of this call scores
+  // from them instead of listing the rows of xq again. pre_over travels with them: the device count of rows
+  // with more than 64 non-zeros that their producer (encode_both_device) added to, zeroed in front of it
+  // (coarse_lists_begin); the coarse kernels' gate reads it.
+  int *pre_over = nullptr;
   const int *gate = nullptr;        // device-side count: only the first *gate rows are searched
   int rows = ROWS_ORDERED;          // IndexRows; a mode set with asl_index_set_unordered goes before ORDERED / SET
   const IndexPostFilter *post = nullptr;   // precursor window applied in the scan's finish where the scan can
@@ -232,12 +237,18 @@ int selector_words(asl_index *ix, const IndexSearch &rq, bool window, const unsi
 int index_search_device(asl_index *ix, IndexSearch &rq);
 int index_nprobe(const asl_index *ix, int nprobe);
 int index_prepare(asl_index *ix);
+// pre_ent / pre_cnt / pre_over: the rows' entry lists where their producer made them already (IndexSearch)
 int coarse_search(asl_index *ix, const float *xq, int nq, int nprobe, float *out_D, int32_t *out_I, uint2 *ent_out,
-                  int32_t *cnt_out, bool *have_ent);
+                  int32_t *cnt_out, bool *have_ent, const uint2 *pre_ent = nullptr, const int32_t *pre_cnt = nullptr,
+                  int *pre_over = nullptr);
+// Will the coarse stage of an nq-row search of this index take entry lists from the encoder? Then *over is the
+// zeroed device counter the encoder adds to (on this stream). ASL_COARSE_LISTS=0: never (lists rebuilt from the rows).
+int coarse_lists_begin(asl_index *ix, int nq, int **over);
 int index_window_prepare(asl_index *ix, uint64_t serial, uint64_t gen, const float *key, int64_t n, int nq,
                          int nprobe);
 int index_refine_k(const asl_index *ix);
-int coarse_scores_all(asl_index *ix, const float *xq, int m, float *scores, uint2 *ent = nullptr, int32_t *cnt = nullptr);
+int coarse_scores_all(asl_index *ix, const float *xq, int m, float *scores, uint2 *ent = nullptr, int32_t *cnt = nullptr,
+                      int *ready_over = nullptr);
 int index_codebooks_transposed(asl_index *ix);
 int index_codes_mmajor(asl_index *ix);   // index_search.hip: the sub-quantiser-major copy, built when missing (mm_ready)
 // n zeros (grow-only, cleared when it grows): the coarse_D of an IVF-PQ index with by_residual off

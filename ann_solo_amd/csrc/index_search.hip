@@ -20,7 +20,8 @@ static int coarse_transposed(asl_index *ix) {
 // (<= ~50 of 800 components): the scores come from the sparse kernel, bit-identical to the GEMM. Both are
 // enqueued; a device-side count of dense rows (more than 64 non-zeros) decides which of the two does the
 // work (the other returns at once). ent / cnt (may be null: the index's own buffers): the rows' entry lists.
-int coarse_scores_all(asl_index *ix, const float *xq, int m, float *scores, uint2 *ent, int32_t *cnt) {
+// ready_over: ent / cnt hold the lists already and this is their count of dense rows (nothing is listed).
+int coarse_scores_all(asl_index *ix, const float *xq, int m, float *scores, uint2 *ent, int32_t *cnt, int *ready_over) {
   const int nlist = ix->nlist, d = ix->d;
   const bool sparse = ix->scan_variant == 0 && coarse_sparse_supported(d, nlist);
   const int over_max = m / 64;
@@ -30,9 +31,10 @@ int coarse_scores_all(asl_index *ix, const float *xq, int m, float *scores, uint
     ASL_TRY(ix->cs_cnt.reserve((size_t)m));
     ASL_TRY(ix->cs_over.reserve(1));
     ASL_TRY(coarse_sparse(xq, m, d, ix->centroids_t.p, nlist, ent ? ent : ix->cs_ent.p, cnt ? cnt : ix->cs_cnt.p,
-                          ix->cs_over.p, over_max, scores, nlist));
+                          ready_over ? ready_over : ix->cs_over.p, over_max, scores, nlist, 0, ready_over != nullptr));
   }
-  return gemm_nt_f32(xq, ix->centroids.p, scores, m, nlist, d, d, d, nlist, sparse ? ix->cs_over.p : nullptr, over_max);
+  return gemm_nt_f32(xq, ix->centroids.p, scores, m, nlist, d, d, d, nlist,
+                     sparse ? (ready_over ? ready_over : ix->cs_over.p) : nullptr, over_max);
 }
 
 // coarse quantiser: top-nprobe centroids by inner product -> ix->coarse_D / coarse_I
@@ -40,7 +42,7 @@ int coarse_scores_all(asl_index *ix, const float *xq, int m, float *scores, uint
 // the sparse coarse kernel lists anyway, for the scan that follows (*have_ent says whether they were
 // produced: only the sparse formulation makes them)
 int coarse_search(asl_index *ix, const float *xq, int nq, int nprobe, float *out_D, int32_t *out_I, uint2 *ent_out,
-                  int32_t *cnt_out, bool *have_ent) {
+                  int32_t *cnt_out, bool *have_ent, const uint2 *pre_ent, const int32_t *pre_cnt, int *pre_over) {
   const int nlist = ix->nlist, d = ix->d;
   if (have_ent) *have_ent = false;
   if (!out_D) {
@@ -52,12 +54,19 @@ int coarse_search(asl_index *ix, const float *xq, int nq, int nprobe, float *out
   int rows = (int)std::min<int64_t>(nq, std::max<int64_t>(1, (int64_t)(SCORE_CHUNK_BYTES / ((size_t)nlist * 4))));
   ASL_TRY(ix->ws_scores.reserve((size_t)rows * nlist));
   const bool sparse = ix->scan_variant == 0 && coarse_sparse_supported(d, nlist);
+  // the encoder's lists serve a batch scored as one chunk (their count of dense rows is the batch's); the scan
+  // then reads them where they lie
+  const bool ready = sparse && pre_ent && pre_cnt && pre_over && nq <= rows && coarse_sparse_cap() == 64;
   for (int r0 = 0; r0 < nq; r0 += rows) {
     const int m = std::min(rows, nq - r0);
     {
       ProfScope ps("coarse_gemm");
-      ASL_TRY(coarse_scores_all(ix, xq + (size_t)r0 * d, m, ix->ws_scores.p, ent_out ? ent_out + (size_t)r0 * 64 : nullptr,
-                                cnt_out ? cnt_out + (size_t)r0 : nullptr));
+      if (ready)
+        ASL_TRY(coarse_scores_all(ix, xq, m, ix->ws_scores.p, const_cast<uint2 *>(pre_ent),
+                                  const_cast<int32_t *>(pre_cnt), pre_over));
+      else
+        ASL_TRY(coarse_scores_all(ix, xq + (size_t)r0 * d, m, ix->ws_scores.p, ent_out ? ent_out + (size_t)r0 * 64 : nullptr,
+                                  cnt_out ? cnt_out + (size_t)r0 : nullptr));
     }
     {
       ProfScope ps("coarse_select");
@@ -67,6 +76,25 @@ int coarse_search(asl_index *ix, const float *xq, int nq, int nprobe, float *out
   }
   // (own buffers: valid for the whole batch only when it was one chunk)
   if (have_ent) *have_ent = sparse && coarse_sparse_cap() == 64 && ((ent_out && cnt_out) || nq <= rows);
+  return ASL_OK;
+}
+
+// ASL_COARSE_LISTS=0 keeps the lists rebuilt from the dense rows (A/B runs of one build). Read at every batch,
+// not once: one process can then run both routes over the same queries (tests/test_gpu_coarse_select.py).
+static bool coarse_lists_enabled() {
+  const char *e = getenv("ASL_COARSE_LISTS");
+  return !(e && e[0] == '0');
+}
+
+int coarse_lists_begin(asl_index *ix, int nq, int **over) {
+  *over = nullptr;
+  if (!coarse_lists_enabled() || nq <= 0 || ix->nlist <= 0) return ASL_OK;
+  if (ix->kind != ASL_INDEX_IVFFLAT && ix->kind != ASL_INDEX_IVFPQ) return ASL_OK;
+  if (!(ix->scan_variant == 0 && coarse_sparse_supported(ix->d, ix->nlist)) || coarse_sparse_cap() != 64) return ASL_OK;
+  if ((size_t)nq > SCORE_CHUNK_BYTES / ((size_t)ix->nlist * 4)) return ASL_OK;      // more than one chunk
+  ASL_TRY(ix->cs_over.reserve(1));
+  HIP_TRY(hipMemsetAsync(ix->cs_over.p, 0, sizeof(int), stream()));
+  *over = ix->cs_over.p;
   return ASL_OK;
 }
 
@@ -171,9 +199,12 @@ static int validate(asl_index *ix, const IndexSearch &rq, SearchPlan &pl) {
   // then be null -- only the layout-specific scans read their queries in that form, and a row
   // whose count is negative (more than 64 non-zeros) is searched as an all-zero query: the
   // caller watches the producer's n_over
-  if (rq.pre_ent && (!rq.pre_cnt || !rq.pre_I || (!rq.xq && !rq.pre_D) || ix->kind == ASL_INDEX_FLAT))
-    return fail(ASL_ERR_STATE, "entry-list search: needs the counts, the caller's probe lists (with their scores when "
-                               "no dense rows are given) and an IVF index");
+  // Without probe lists (no pre_I): lists ready, probes still to find -- with the dense rows and pre_over.
+  if (rq.pre_ent && (!rq.pre_cnt || ix->kind == ASL_INDEX_FLAT ||
+                     (rq.pre_I ? (!rq.xq && !rq.pre_D) : (!rq.xq || !rq.pre_over || rq.pre_D != nullptr))))
+    return fail(ASL_ERR_STATE, "entry-list search: needs the counts, an IVF index, and the caller's probe lists (with "
+                               "their scores when no dense rows are given) or the dense rows and the lists' count "
+                               "of dense rows");
   // (with dense rows given as well, entry lists are a hint: a scan that does not read them ignores them)
   if (!rq.xq && !rq.pre_ent) return fail(ASL_ERR_INVALID, "search: null queries");
   // gate: a device-side count -- only the first *gate rows are searched (layout-specific scans only)
@@ -323,7 +354,9 @@ static int search_gemm_topk(asl_index *ix, const IndexSearch &rq, const int32_t 
 static int search_ivfflat(asl_index *ix, IndexSearch &rq, const SearchPlan &pl) {
   const int nq = rq.nq, nprobe = pl.nprobe;
   bool own_ent = false;
-  if (!rq.pre_I) ASL_TRY(coarse_search(ix, rq.xq, nq, nprobe, nullptr, nullptr, nullptr, nullptr, &own_ent));
+  if (!rq.pre_I)
+    ASL_TRY(coarse_search(ix, rq.xq, nq, nprobe, nullptr, nullptr, nullptr, nullptr, &own_ent, rq.pre_ent, rq.pre_cnt,
+                          rq.pre_over));
   // search_preassigned: the caller's probe lists are read where they lie (device memory that
   // stays valid until the scan has run: the pipeline's per-parity buffers, a caller's tensor on
   // this stream); the coarse scores are unused
@@ -463,7 +496,9 @@ static int scan_pq_tiled(asl_index *ix, IndexSearch &rq, const SearchPlan &pl, c
 static int search_ivfpq(asl_index *ix, IndexSearch &rq, const SearchPlan &pl) {
   const int nq = rq.nq, nprobe = pl.nprobe;
   bool own_ent = false;
-  if (!rq.pre_D) ASL_TRY(coarse_search(ix, rq.xq, nq, nprobe, nullptr, nullptr, nullptr, nullptr, &own_ent));
+  if (!rq.pre_D)
+    ASL_TRY(coarse_search(ix, rq.xq, nq, nprobe, nullptr, nullptr, nullptr, nullptr, &own_ent, rq.pre_ent, rq.pre_cnt,
+                          rq.pre_over));
   // search_preassigned: the caller's probe lists, read where they lie (see search_ivfflat)
   const float *cD = rq.pre_D ? rq.pre_D : ix->coarse_D.p;
   const int32_t *cI = rq.pre_D ? rq.pre_I : ix->coarse_I.p;

@@ -2,8 +2,8 @@
 // quantizer.hip; the tiled IVF-PQ scan, the postings scan, the re-rank, the exchange and the rank scan have units
 // of their own).
 //
-//   row_select_kernel exact top-k of a SHORT score row held in registers (the coarse
-//                     top-nprobe of nlist): one histogram pass, one small sort
+//   wave_select_kernel exact top-k of a SHORT score row held in one wave's registers (the coarse
+//                     top-nprobe of nlist): one histogram pass, one small sort, no workgroup barrier
 //   row_topk_kernel   exact streaming top-k of one score row per workgroup (IndexFlatIP,
 //                     long rows, and IVF-Flat through a probed-list bitmap mask)
 //   topk_merge_hist_kernel / topk_merge_kernel  merge of per-shard partial top-k lists
@@ -66,114 +66,253 @@ __global__ __launch_bounds__(TK_NT) void row_topk_kernel(
   if (upper_out && tid == 0) upper_out[r] = ctl[0] >= k ? buf[k - 1] : 0ull;
 }
 
-// Short rows (n <= 4096, k <= 256; the coarse quantiser's top-nprobe of nlist): the whole row
-// sits in registers, one histogram pass over [row min, row max] finds the bucket of the k-th
-// score, the <= RS_SEL keys at or above it are compacted and sorted once. Rows whose
-// threshold bucket is overfull (mass ties: an all-zero query scores every centroid 0)
-// take the streaming path below inside the same launch.
+// Short rows (n <= 4096, k <= 256; the coarse quantiser's top-nprobe of nlist): ONE WAVE per row, four
+// rows per workgroup and no workgroup barrier anywhere, so a wave on the rare path never holds up its
+// neighbours. The row sits in the wave's registers (CH * 4 values a lane; 16-byte loads where the row's
+// address allows). One histogram pass over [row min, row max] in wave-private LDS finds the bucket of the
+// k-th score; the <= SEL_CAP keys at or above it are compacted (v_mbcnt) and sorted inside the wave.
+// A row whose threshold bucket is overfull (mass ties: an all-zero query scores every centroid 0; a range
+// that overflows fp32) is refined inside the wave: further histogram passes over the 64-bit KEYS of the
+// bucket's own range, 9 bits a pass. Keys are unique, so the passes end (at the latest with one key per
+// bucket), and among equal scores the lower id is the larger key: ties resolve in column order.
 constexpr int SEL_VPT = 16, SEL_CAP = 512, SEL_NB = 512;
+constexpr int SEL_WAVES = TK_NT / 64;   // rows per workgroup
 
-__global__ __launch_bounds__(TK_NT) void row_select_kernel(
-    const float *__restrict__ scores, int64_t ld, int n, int k, int cap, float *__restrict__ D,
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+
+// min and max over the wave (every source lane of these DPP patterns is inside its row), wave-uniform
+__device__ __forceinline__ void wave_minmax(float &lo, float &hi) {
+  lo = fminf(lo, dpp_f32<0xB1>(lo));    // quad_perm [1,0,3,2]
+  hi = fmaxf(hi, dpp_f32<0xB1>(hi));
+  lo = fminf(lo, dpp_f32<0x4E>(lo));    // quad_perm [2,3,0,1]
+  hi = fmaxf(hi, dpp_f32<0x4E>(hi));
+  lo = fminf(lo, dpp_f32<0x141>(lo));   // row_half_mirror
+  hi = fmaxf(hi, dpp_f32<0x141>(hi));
+  lo = fminf(lo, dpp_f32<0x140>(lo));   // row_mirror
+  hi = fmaxf(hi, dpp_f32<0x140>(hi));
+  float l4[4], h4[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    l4[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lo), 16 * i));
+    h4[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hi), 16 * i));
+  }
+  lo = fminf(fminf(l4[0], l4[1]), fminf(l4[2], l4[3]));
+  hi = fmaxf(fmaxf(h4[0], h4[1]), fmaxf(h4[2], h4[3]));
+}
+
+struct SelThr {
+  int b, ge, gt;   // the threshold bucket, the values at or above it, the values above it
+};
+
+// The highest bucket of the wave's histogram with >= need values at or above it (lane t owns the eight
+// buckets SEL_NB-8-8t .. SEL_NB-1-8t; suffix sums inside the wave). Fewer than `need` values in all:
+// bucket 0, everything at or above it.
+__device__ __forceinline__ SelThr wave_threshold(const int *hist, int lane, int need) {
+  const int first = SEL_NB - 8 - 8 * lane;
+  const int4 a = *reinterpret_cast<const int4 *>(hist + first);
+  const int4 c = *reinterpret_cast<const int4 *>(hist + first + 4);
+  const int h[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
+  const int s = ((h[0] + h[1]) + (h[2] + h[3])) + ((h[4] + h[5]) + (h[6] + h[7]));
+  int incl = s;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += t;
+  }
+  int acc = incl - s, b = 0, ge = 0, gt = 0;
+  const bool mine = acc < need && incl >= need;
+  bool done = false;
+#pragma unroll
+  for (int i = 7; i >= 0; --i) {
+    const int nxt = acc + h[i];
+    if (!done && nxt >= need) {
+      b = first + i;
+      ge = nxt;
+      gt = acc;
+      done = true;
+    }
+    acc = nxt;
+  }
+  const u64 m = __ballot(mine);
+  SelThr t;
+  if (m == 0ull) {
+    t.b = 0;
+    t.ge = __builtin_amdgcn_readlane(incl, 63);
+    t.gt = 0;
+  } else {
+    const int src = __ffsll((long long)m) - 1;
+    t.b = __builtin_amdgcn_readlane(b, src);
+    t.ge = __builtin_amdgcn_readlane(ge, src);
+    t.gt = __builtin_amdgcn_readlane(gt, src);
+  }
+  return t;
+}
+
+__device__ __forceinline__ void wave_hist_clear(int *hist, int lane) {
+  wave_lds_sync();   // other lanes' reads of the last pass stay in front of the stores
+  reinterpret_cast<int4 *>(hist)[2 * lane] = make_int4(0, 0, 0, 0);
+  reinterpret_cast<int4 *>(hist)[2 * lane + 1] = make_int4(0, 0, 0, 0);
+  wave_lds_sync();
+}
+
+// CH: 16-byte chunks a lane holds (value j of a lane is column ((j / 4) * 64 + lane) * 4 + j % 4).
+// FULL: n == CH * 256 and every row 16-byte aligned: no column is out of range, no load is narrow.
+template <int CH, bool FULL>
+__global__ __launch_bounds__(TK_NT, 4) void wave_select_kernel(
+    const float *__restrict__ scores, int64_t ld, int rows, int n, int k, float *__restrict__ D,
     int64_t *__restrict__ I64, int32_t *__restrict__ I32, int64_t out_ld) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  u64 *buf = reinterpret_cast<u64 *>(smem);              // max(SEL_CAP, cap) keys
-  const int nkeys = cap > SEL_CAP ? cap : SEL_CAP;
-  u64 *thr = buf + nkeys;
-  int *ctl = reinterpret_cast<int *>(thr + 1);            // 4 ints (StreamTopK) + 8 for scans
-  int *hist = ctl + 12;                                   // SEL_NB
-  float *red = reinterpret_cast<float *>(hist + SEL_NB);  // 8 floats
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = blockIdx.x;
+  constexpr int NV = CH * 4;
+  __shared__ __attribute__((aligned(16))) int s_hist[SEL_WAVES][SEL_NB];
+  __shared__ __attribute__((aligned(16))) u64 s_buf[SEL_WAVES][SEL_CAP];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = blockIdx.x * SEL_WAVES + wave;
+  if (r >= rows) return;      // wave-uniform; nothing below waits for another wave
+  int *hist = s_hist[wave];
+  u64 *buf = s_buf[wave];
   const float *row = scores + (size_t)r * ld;
-  float v[SEL_VPT];
+  const int c0 = lane * 4;    // column of the lane's value e of chunk u: c0 + u * 256 + e
+  // n or ld not a multiple of 4: every second row starts off a 16-byte boundary and loads by the value
+  const bool wide = FULL || (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+  auto chunk = [&](int u, float *x) {
+    const int c = c0 + u * 256;
+    if (FULL || (wide && c + 3 < n)) {
+      const float4 t = *reinterpret_cast<const float4 *>(row + c);
+      x[0] = t.x, x[1] = t.y, x[2] = t.z, x[3] = t.w;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) x[e] = c + e < n ? row[c + e] : 0.0f;
+    }
+  };
+  auto col = [&](int j) { return c0 + (j >> 2) * 256 + (j & 3); };
+  auto valid = [&](int c) { return FULL || c < n; };
+
+  float v[NV];
+#pragma unroll
+  for (int u = 0; u < CH; ++u) chunk(u, v + 4 * u);
   float lo = 3.402823466e+38f, hi = -3.402823466e+38f;
 #pragma unroll
-  for (int u = 0; u < SEL_VPT; ++u) {
-    const int c = tid + u * TK_NT;
-    v[u] = c < n ? row[c] : 0.0f;
-    if (c < n) {
-      lo = fminf(lo, v[u]);
-      hi = fmaxf(hi, v[u]);
+  for (int j = 0; j < NV; ++j)
+    if (valid(col(j))) {
+      lo = fminf(lo, v[j]);
+      hi = fmaxf(hi, v[j]);
     }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, o, 64));
-    hi = fmaxf(hi, __shfl_xor(hi, o, 64));
-  }
-  if (lane == 0) {
-    red[wave] = lo;
-    red[4 + wave] = hi;
-  }
-  for (int i = tid; i < SEL_NB; i += TK_NT) hist[i] = 0;
-  __syncthreads();
-  lo = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
-  hi = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+  wave_minmax(lo, hi);
   const float scale = hi > lo ? (float)(SEL_NB - 1) / (hi - lo) : 0.0f;   // monotone in the score
-  int bk[SEL_VPT];
+  // The bucket of a value is recomputed where it is needed (three instructions) and not kept: the second
+  // pass reads lo and scale through an empty asm, or the compiler would hold 64 buckets a lane.
+  float plo = lo, pscale = scale;
+  auto bucket = [&](float x) {
+    const float t = fminf(fmaxf((x - plo) * pscale, 0.0f), (float)(SEL_NB - 1));
+    return (int)t;
+  };
+  wave_hist_clear(hist, lane);
 #pragma unroll
-  for (int u = 0; u < SEL_VPT; ++u) {
-    const int c = tid + u * TK_NT;
-    float t = (v[u] - lo) * scale;
-    t = fminf(fmaxf(t, 0.0f), (float)(SEL_NB - 1));
-    bk[u] = (int)t;
-    if (c < n) atomicAdd(&hist[bk[u]], 1);
-  }
-  __syncthreads();
-  // bstar = highest bucket with >= k values at or above it (thread t owns the two buckets
-  // SEL_NB-1-2t, SEL_NB-2-2t)
-  {
-    const int h0 = hist[SEL_NB - 1 - 2 * tid], h1 = hist[SEL_NB - 2 - 2 * tid];
-    int tot;
-    const int above = block_excl_scan256(h0 + h1, ctl + 4, tid, tot);
-    if (tid == 0) ctl[3] = 0;                 // fewer than k values in the row: keep everything
-    __syncthreads();
-    if (above < k && above + h0 + h1 >= k) ctl[3] = (above + h0 >= k) ? SEL_NB - 1 - 2 * tid : SEL_NB - 2 - 2 * tid;
-    __syncthreads();
-  }
-  const int bstar = ctl[3];
-  int cnt = 0;
+  for (int j = 0; j < NV; ++j)
+    if (valid(col(j))) atomicAdd(&hist[bucket(v[j])], 1);
+  wave_lds_sync();
+  const SelThr th = wave_threshold(hist, lane, k);
+
+  // compaction of the selected values' keys, any order: position = keys so far + v_mbcnt of the ballot
+  int total = 0;
+  auto append = [&](float x, int c, bool sel) {
+    const u64 m = __ballot(sel);
+    const int pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, total));
+    if (sel && pos < SEL_CAP) buf[pos] = make_key(x, (uint32_t)c);
+    total += __popcll(m);
+  };
+  asm volatile("" : "+v"(plo), "+v"(pscale));
+  if (th.ge <= SEL_CAP) {     // wave-uniform; the usual case
 #pragma unroll
-  for (int u = 0; u < SEL_VPT; ++u) cnt += (tid + u * TK_NT < n) && bk[u] >= bstar;
-  int total;
-  int pos = block_excl_scan256(cnt, ctl + 8, tid, total);
-  if (total <= SEL_CAP) {    // block-uniform
-    for (int i = total + tid; i < SEL_CAP; i += TK_NT) buf[i] = 0ull;
+    for (int j = 0; j < NV; ++j) append(v[j], col(j), valid(col(j)) && bucket(v[j]) >= th.b);
+  } else {
+    // The threshold bucket is overfull: the th.gt values above it are in; the rest come from the bucket, by
+    // histogram passes over its keys' own range [klo, khi]. Rare, so these passes read the row again (it is
+    // in the cache) in rolled loops and keep the registers of the usual path out of scratch.
+    int in = th.gt;
+    u64 klo = ~0ull, khi = 0ull;
+#pragma nounroll
+    for (int u = 0; u < CH; ++u) {
+      float x[4];
+      chunk(u, x);
 #pragma unroll
-    for (int u = 0; u < SEL_VPT; ++u) {
-      const int c = tid + u * TK_NT;
-      if (c < n && bk[u] >= bstar) buf[pos++] = make_key(v[u], (uint32_t)c);
+      for (int e = 0; e < 4; ++e) {
+        const int c = c0 + u * 256 + e;
+        const u64 key = make_key(x[e], (uint32_t)c);
+        if (valid(c) && bucket(x[e]) == th.b) {
+          klo = key < klo ? key : klo;
+          khi = key > khi ? key : khi;
+        }
+      }
     }
-    __syncthreads();
-    if (total <= TK_NT)      // block-uniform; the usual case (k = nprobe <= 128): half the sort
-      block_sort_desc<TK_NT, 1>(buf, tid, TK_NT);
-    else
-      block_sort_desc<TK_NT, SEL_CAP / TK_NT>(buf, tid, SEL_CAP);
-    const int f = total < k ? total : k;
-    for (int i = tid; i < k; i += TK_NT) {
-      const u64 key = buf[i];
-      const bool ok = i < f;
-      if (D) D[(size_t)r * out_ld + i] = ok ? key_score(key) : -3.402823466e+38f;
-      if (I64) I64[(size_t)r * out_ld + i] = ok ? (int64_t)key_id(key) : -1;
-      if (I32) I32[(size_t)r * out_ld + i] = ok ? (int32_t)key_id(key) : -1;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const u64 a = __shfl_xor(klo, o, 64), c = __shfl_xor(khi, o, 64);
+      klo = a < klo ? a : klo;
+      khi = c > khi ? c : khi;
     }
-    return;
+    u64 kthr;
+#pragma nounroll
+    for (;;) {
+      const u64 range = khi - klo;
+      const int sh = (range >> 9) ? 64 - 9 - __clzll((long long)range) : 0;   // (range >> sh) < SEL_NB
+      wave_hist_clear(hist, lane);
+#pragma nounroll
+      for (int u = 0; u < CH; ++u) {
+        float x[4];
+        chunk(u, x);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int c = c0 + u * 256 + e;
+          const u64 key = make_key(x[e], (uint32_t)c);
+          if (valid(c) && key >= klo && key <= khi) atomicAdd(&hist[(int)((key - klo) >> sh)], 1);
+        }
+      }
+      wave_lds_sync();
+      const SelThr t2 = wave_threshold(hist, lane, k - in);
+      kthr = klo + ((u64)t2.b << sh);
+      if (in + t2.ge <= SEL_CAP) break;
+      // still overfull: sh > 0 here (a bucket of single keys holds one), and the next range is 2^sh wide
+      in += t2.gt;
+      klo = kthr;
+      const u64 top = kthr + ((1ull << sh) - 1ull);
+      khi = top < khi ? top : khi;
+      wave_lds_sync();
+    }
+#pragma nounroll
+    for (int u = 0; u < CH; ++u) {
+      float x[4];
+      chunk(u, x);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int c = c0 + u * 256 + e;
+        append(x[e], c, valid(c) && make_key(x[e], (uint32_t)c) >= kthr);
+      }
+    }
+    total = total < SEL_CAP ? total : SEL_CAP;
   }
-  __syncthreads();
-  StreamTopK<TK_NT> tk;      // mass ties at the threshold: exact streaming selection
-  tk.init(buf, ctl, thr, cap, k, tid);
-  for (int base = 0; base < n; base += TK_NT) {   // re-read the row: keeps v[] out of scratch
-    const int c = base + tid;
-    u64 key = 0ull;
-    if (c < n) {
-      const float x = row[c];
-      const float t = fminf(fmaxf((x - lo) * scale, 0.0f), (float)(SEL_NB - 1));
-      if ((int)t >= bstar) key = make_key(x, (uint32_t)c);
-    }
-    tk.push(key, tid);
+  const int cap = total <= 64 ? 64 : total <= 128 ? 128 : total <= 256 ? 256 : SEL_CAP;
+  for (int i = total + lane; i < cap; i += 64) buf[i] = 0ull;
+  wave_lds_sync();
+  if (cap == 64)             // wave-uniform: the smallest sort that holds the keys
+    block_sort_desc<64, 1, true>(buf, lane, k);
+  else if (cap == 128)
+    block_sort_desc<64, 2, true>(buf, lane, k);
+  else if (cap == 256)
+    block_sort_desc<64, 4, true>(buf, lane, k);
+  else
+    block_sort_desc<64, 8, true>(buf, lane, k);
+  const int f = total < k ? total : k;
+  for (int i = lane; i < k; i += 64) {
+    const u64 key = buf[i];
+    const bool ok = i < f;
+    if (D) D[(size_t)r * out_ld + i] = ok ? key_score(key) : -3.402823466e+38f;
+    if (I64) I64[(size_t)r * out_ld + i] = ok ? (int64_t)key_id(key) : -1;
+    if (I32) I32[(size_t)r * out_ld + i] = ok ? (int32_t)key_id(key) : -1;
   }
-  tk.finish(D ? D + (size_t)r * out_ld : nullptr, I64 ? I64 + (size_t)r * out_ld : nullptr,
-            I32 ? I32 + (size_t)r * out_ld : nullptr, tid);
 }
 
 int row_topk(const float *scores, int64_t ld, int rows, int n, int k, const int32_t *ids,
@@ -183,10 +322,20 @@ int row_topk(const float *scores, int64_t ld, int rows, int n, int k, const int3
   if (rows <= 0) return ASL_OK;
   if (k <= 0 || k > TK_MAX_K) return fail(ASL_ERR_CAPACITY, "top-k: k=%d outside 1..%d", k, TK_MAX_K);
   const int cap = topk_cap_for(k);
+  // Short plain rows: wave_select_kernel covers this whole domain (ties and degenerate ranges included,
+  // inside the wave), so there is no second selection kernel and no second launch.
   if (n <= SEL_VPT * TK_NT && k <= 256 && !ids && id_base == 0 && !bitmap && !upper_in && !upper_out) {
-    const size_t lds_sel = (size_t)std::max(cap, SEL_CAP) * 8 + 8 + 12 * 4 + SEL_NB * 4 + 8 * 4;
-    hipLaunchKernelGGL(row_select_kernel, dim3(rows), dim3(TK_NT), lds_sel, stream(), scores, ld,
-                       n, k, cap, D, I64, I32, out_ld);
+    const dim3 grid((rows + SEL_WAVES - 1) / SEL_WAVES), block(TK_NT);
+    const bool full = n == SEL_VPT * TK_NT && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(scores) & 15) == 0;
+    if (full)
+      hipLaunchKernelGGL((wave_select_kernel<SEL_VPT, true>), grid, block, 0, stream(), scores, ld, rows,
+                         n, k, D, I64, I32, out_ld);
+    else if (n <= SEL_VPT / 4 * TK_NT)
+      hipLaunchKernelGGL((wave_select_kernel<SEL_VPT / 4, false>), grid, block, 0, stream(), scores, ld,
+                         rows, n, k, D, I64, I32, out_ld);
+    else
+      hipLaunchKernelGGL((wave_select_kernel<SEL_VPT, false>), grid, block, 0, stream(), scores, ld, rows,
+                         n, k, D, I64, I32, out_ld);
     ASL_CHECK_LAUNCH();
     return ASL_OK;
   }

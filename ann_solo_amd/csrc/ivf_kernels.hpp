@@ -31,7 +31,8 @@ int coarse_sparse_cap();
 int list_nonzeros(const float *xq, int nq, int d, int64_t ldq, uint2 *ent, int32_t *cnt, int *n_over);
 int transpose_f32(const float *in, int rows, int cols, float *out);
 int coarse_sparse(const float *xq, int nq, int d, const float *Ct, int nlist, uint2 *ent,
-                  int32_t *cnt, int *n_over, int over_max, float *scores, int ld, int64_t ldq = 0);
+                  int32_t *cnt, int *n_over, int over_max, float *scores, int ld, int64_t ldq = 0,
+                  bool lists_ready = false);
 
 // ---- ivf_kernels.hip: top-k and merges, gathers, the ADC table and the generic IVF-PQ scan
 int row_topk(const float *scores, int64_t ld, int rows, int n, int k, const int32_t *ids,

@@ -39,6 +39,8 @@ struct asl_library {
   asl::DevBuf<int32_t> sorted_row;
   // scratch
   asl::DevBuf<float> qvec;
+  asl::DevBuf<uint2> q_ent;             // the synchronous batch's entry lists, written by the encoder with qvec
+  asl::DevBuf<int32_t> q_cnt;
   asl::DevBuf<int32_t> knn, cand, lo, cnt, woff;
   // buffers that cross the two streams of the pipeline, by batch parity
   asl::DevBuf<float> p_qvec[2], p_cD[2];

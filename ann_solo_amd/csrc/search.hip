@@ -16,6 +16,9 @@ namespace asl {
 int encode_device(const float *mz, const float *inten, const int32_t *offsets, int32_t n,
                   double min_bound, double bin_size, int32_t hash_len, uint32_t seed,
                   int norm, float *out);
+int encode_both_device(const float *mz, const float *inten, const int32_t *offsets, int32_t n,
+                       double min_bound, double bin_size, int32_t hash_len, uint32_t seed, int norm,
+                       float *out, uint2 *ent, int32_t *cnt, int *n_over);
 }  // namespace asl
 
 using namespace asl;
@@ -70,16 +73,17 @@ struct BatchScan {
 // xq: the hashed queries; I32: the neighbour rows the rescoring reads; I64: the caller's ordered neighbour
 // list -- without one the candidates are consumed as a set (filter + best match: no final sort) and the scan
 // may apply the precursor window itself, row_len then receives the rows' lengths; pre_*: the coarse stage's
-// results where it has run already (the entry lists when it made them: the scan does not list the rows again).
+// results where it has run already (the entry lists when it made them: the scan does not list the rows again);
+// pre_ent / pre_cnt / pre_over without pre_I: the encoder's entry lists for the coarse stage of the scan's own call.
 static void batch_scan(BatchScan &s, const SearchBatch &b, const asl_index *idx, int nprobe, const float *xq,
                        int64_t *I64, int32_t *I32, int32_t *row_len, const float *pre_D = nullptr,
                        const int32_t *pre_I = nullptr, const uint2 *pre_ent = nullptr,
-                       const int32_t *pre_cnt = nullptr) {
+                       const int32_t *pre_cnt = nullptr, int *pre_over = nullptr) {
   const asl_library *L = b.L;
   const asl_search_params_t *P = b.P;
   const bool as_set = I64 == nullptr;
   s.rq = {.nq = b.Q.n, .xq = xq, .k = P->k, .nprobe = nprobe, .I64 = I64, .I32 = I32, .pre_D = pre_D, .pre_I = pre_I,
-          .pre_ent = pre_ent, .pre_cnt = pre_cnt, .rows = as_set ? ROWS_SET : ROWS_ORDERED};
+          .pre_ent = pre_ent, .pre_cnt = pre_cnt, .pre_over = pre_over, .rows = as_set ? ROWS_SET : ROWS_ORDERED};
   // what every ANN batch tells the index of its library: whose columns it may have derived a layout from
   // (serial, generation) and, with a selection installed, the selector
   s.rq.serial = L->serial;
@@ -152,10 +156,21 @@ static int search_batch_sync(asl_library *L, asl_index *idx, const asl_peaks_t *
     ASL_TRY(L->rows_len.reserve((size_t)nq));
     if (window_mode(idx))
       ASL_TRY(index_window_prepare(idx, L->serial, L->sel_gen, L->window_col(), L->n, nq, P->nprobe));
-    ASL_TRY(encode_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
-                          d, P->hash_seed, 1, L->qvec.p));
+    // the rows and, where the coarse stage will score from them, their entry lists in the same kernel
+    int *over = nullptr;
+    ASL_TRY(coarse_lists_begin(idx, nq, &over));
+    if (over) {
+      ASL_TRY(L->q_ent.reserve((size_t)nq * 64));
+      ASL_TRY(L->q_cnt.reserve((size_t)nq));
+      ASL_TRY(encode_both_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
+                                 d, P->hash_seed, 1, L->qvec.p, L->q_ent.p, L->q_cnt.p, over));
+    } else {
+      ASL_TRY(encode_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
+                            d, P->hash_seed, 1, L->qvec.p));
+    }
     BatchScan s;
-    batch_scan(s, b, idx, P->nprobe, L->qvec.p, o_knn.d, L->knn.p, L->rows_len.p);
+    batch_scan(s, b, idx, P->nprobe, L->qvec.p, o_knn.d, L->knn.p, L->rows_len.p, nullptr, nullptr,
+               over ? L->q_ent.p : nullptr, over ? L->q_cnt.p : nullptr, over);
     ASL_TRY(index_search_device(idx, s.rq));
     ASL_TRY(rescore_device(rows_request(b, {.rows32 = L->knn.p,
                                             .row_counts = s.rq.rows_filtered ? L->rows_len.p : nullptr})));
@@ -235,13 +250,22 @@ static int search_batch_pipelined(asl_library *L, asl_index *idx, const asl_peak
     // runs under the next scan instead, is worse -- the scan loses 1.3 ms to a 0.9 ms GEMM
     // beside it (9.88 ms per step), the rescoring only 0.6 ms (9.35 ms).
     if (pp.scan_recorded[par]) HIP_TRY(hipStreamWaitEvent(pp.A, pp.ev_scan[par], 0));
-    ASL_TRY(encode_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
-                          d, P->hash_seed, 1, L->p_qvec[par].p));
+    // (entry lists from the encoder into this parity's buffers: the coarse stage scores from them and, as
+    // when it listed them itself, the scan reads them there)
+    int *over = nullptr;
+    if (!winflat) ASL_TRY(coarse_lists_begin(idx, nq, &over));
+    if (over)
+      ASL_TRY(encode_both_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
+                                 d, P->hash_seed, 1, L->p_qvec[par].p, L->p_ent[par].p, L->p_cnt[par].p, over));
+    else
+      ASL_TRY(encode_device(Q.dev.mz, Q.dev.intensity, Q.dev.offsets, nq, P->min_bound, P->bin_size,
+                            d, P->hash_seed, 1, L->p_qvec[par].p));
     if (winflat)
       L->p_have_ent[par] = false;
     else
       ASL_TRY(coarse_search(idx, L->p_qvec[par].p, nq, nprobe, L->p_cD[par].p, L->p_cI[par].p,
-                                  L->p_ent[par].p, L->p_cnt[par].p, &L->p_have_ent[par]));
+                            L->p_ent[par].p, L->p_cnt[par].p, &L->p_have_ent[par],
+                            over ? L->p_ent[par].p : nullptr, over ? L->p_cnt[par].p : nullptr, over));
     HIP_TRY(hipEventRecord(pp.ev_front[par], pp.A));
   }
   {

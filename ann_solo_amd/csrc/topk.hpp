@@ -105,12 +105,15 @@ __device__ __forceinline__ u64 dpp_u64(u64 v) {
   return ((u64)(uint32_t)hi << 32) | (u64)(uint32_t)lo;
 }
 
-template <int NT, int P>
+// WAVE (NT == 64): the sorter is one wave of a larger workgroup with an LDS image of its own; no partner
+// is ever in another wave, and the workgroup barriers become wave-local LDS ordering.
+template <int NT, int P, bool WAVE = false>
 __device__ __forceinline__ void block_sort_desc(u64 *buf, int tid, int n_out) {
+  static_assert(!WAVE || NT == 64, "a wave-local sort has 64 threads");
   u64 x[P];
 #pragma unroll
   for (int r = 0; r < P; ++r) x[r] = buf[r * NT + tid];   // any initial arrangement will do
-  __syncthreads();
+  if constexpr (WAVE) wave_lds_sync(); else __syncthreads();
   // stages whose pairs never leave the thread
 #pragma unroll
   for (int k = 2; k <= P; k <<= 1) {
@@ -138,7 +141,7 @@ __device__ __forceinline__ void block_sort_desc(u64 *buf, int tid, int n_out) {
       const int jj = j / P;
       const bool keep_max = (((tid & jj) == 0) == desc);
       u64 y[P];
-      if (jj >= 64) {          // partner in another wave: through the LDS image
+      if (!WAVE && jj >= 64) { // partner in another wave: through the LDS image
 #pragma unroll
         for (int r = 0; r < P; ++r) buf[r * NT + tid] = x[r];
         __syncthreads();
@@ -176,13 +179,13 @@ __device__ __forceinline__ void block_sort_desc(u64 *buf, int tid, int n_out) {
       }
     }
   }
-  __syncthreads();
+  if constexpr (WAVE) wave_lds_sync(); else __syncthreads();
   // natural order write-back of the leading n_out keys (position tid*P + r)
   if (tid * P < n_out) {
 #pragma unroll
     for (int r = 0; r < P; ++r) buf[tid * P + r] = x[r];
   }
-  __syncthreads();
+  if constexpr (WAVE) wave_lds_sync(); else __syncthreads();
 }
 
 template <int NT, int CAP = 0>
