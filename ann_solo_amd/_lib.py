@@ -98,6 +98,7 @@ EXPORTS = [
     'asl_mgf_measure', 'asl_mgf_fill', 'asl_mgf_sort', 'asl_mgf_number',
     'asl_mgf_sort_charged', 'asl_sptxt_measure', 'asl_sptxt_fill', 'asl_sptxt_fragment_charge',
     'asl_mzml_measure', 'asl_mzml_fill', 'asl_mzml_inflate',
+    'asl_mzxml_measure', 'asl_mzxml_fill', 'asl_mzxml_duration', 'asl_mzxml_pairs',
 ]
 
 SVM_MAX_DIM = 63          # include/annsolo_mi.h: ASL_SVM_MAX_DIM
@@ -366,6 +367,11 @@ def lib():
             L.asl_mzml_measure.argtypes = [C.c_void_p, C.c_int64, C.c_int32, c_i64p]
             L.asl_mzml_fill.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 14
             L.asl_mzml_inflate.argtypes = [C.c_char_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, c_i64p]
+        if hasattr(L, 'asl_mzxml_measure'):
+            L.asl_mzxml_measure.argtypes = [C.c_void_p, C.c_int64, C.c_int32, c_i64p]
+            L.asl_mzxml_fill.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 14
+            L.asl_mzxml_duration.argtypes = [C.c_char_p, C.c_int32, c_f64p]
+            L.asl_mzxml_pairs.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         if hasattr(L, 'asl_index_set_by_residual'):
             L.asl_index_set_by_residual.argtypes = [C.c_void_p, C.c_int32]
             L.asl_index_get_by_residual.argtypes = [C.c_void_p]
@@ -761,3 +767,25 @@ def ssm_groups(mass_diff, min_group_size: int, profile: bool = False):
     if not profile:
         return group, int(n_labels.value)
     return group, int(n_labels.value), mass[:n_peaks.value], size[:n_peaks.value]
+
+
+def mzxml_duration(value):
+    """``asl_mzxml_duration``: the value of a ``retentionTime`` attribute (bytes or str) as the device converts it --
+    ``(0, minutes)``, or ``(1, None)`` where the device defers the value to ``mzxml.duration_minutes``. Host only:
+    needs no GPU."""
+    b = value.encode('utf-8') if isinstance(value, str) else bytes(value)
+    out = C.c_double(0.0)
+    rc = lib().asl_mzxml_duration(b, len(b), byref(out))
+    return (0, out.value) if rc == 0 else (1, None)
+
+
+def mzxml_pairs(raw, n_peaks: int, precision: int):
+    """``asl_mzxml_pairs``: the decoded ``<peaks>`` stream ``raw`` (big-endian m/z, intensity pairs of ``precision``
+    bits) as the device converts it: ``(mz, intensity)``, float32 numpy arrays. Host only: needs no GPU."""
+    b = bytes(raw)
+    if precision not in (32, 64) or len(b) != n_peaks * 2 * (precision // 8):
+        raise ValueError(f'asl_mzxml_pairs: {len(b)} bytes for {n_peaks} peaks of {precision} bits')
+    mz, it = np.empty(n_peaks, np.float32), np.empty(n_peaks, np.float32)
+    if lib().asl_mzxml_pairs(b, n_peaks, precision, mz.ctypes.data, it.ctypes.data) != 0:
+        raise ValueError('asl_mzxml_pairs: an invalid argument')
+    return mz, it

@@ -7,7 +7,7 @@
 ``precursor_window_open``, ``fragment_tolerance_unit``, ``score_stats``, ``device_decoys``,
 ``decoy_tolerance_unit``, ``localize_modifications``, ``device_fdr``, ``device_forest``,
 ``forest_trees``, ``device_qvalues``, ``device_groups``, ``chimeric_search``, ``chimeric_window``,
-``device_mgf``, ``device_mzml``, ``device_library``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
+``device_mgf``, ``device_mzml``, ``device_mzxml``, ``device_library``). Defaults are the reference's: ``precursor_tolerance_mass_open`` /
 ``_mode_open`` are ``None`` (cascade off, config.py:151-156) and ``allow_peak_shifts`` is False
 (a ``store_true`` flag, config.py:157), as a parsed reference configuration without those flags
 has them. The one deviation: ``precursor_tolerance_mass`` / ``precursor_tolerance_mode`` /
@@ -161,6 +161,10 @@ class Config:
     # zlib arrays decoded by kernels (mzml.py, csrc/mzml.hip, csrc/inflate.hpp; DESIGN.md 3 "Query files"), in place
     # of ``query_reader`` (the reference's pyteomics reader) and ``pack_queries``. Off: nothing new is launched
     device_mzml: bool = False
+    # The same for a query file whose name ends in ``.mzxml`` (any letter case): nested scans, the precursor's element
+    # text, ISO-8601 retention times and the one interleaved big-endian base64 / zlib stream of each MS2 scan are read
+    # by kernels (mzxml.py, csrc/mzxml.hip; DESIGN.md 3 "Query files"). Off: nothing new is launched
+    device_mzxml: bool = False
     # ``SpectralLibrary(filename)`` reads a library whose name ends in ``.sptxt`` (any letter case) with the engine's
     # own reader (sptxt.py, csrc/sptxt.hip; DESIGN.md 3 "Library files") in place of ``reader_factory``: the text is
     # parsed by kernels, the raw peaks go to the preprocessing where they lie, and the packed store is what
@@ -266,6 +270,7 @@ class Config:
             raise ValueError('chimeric_search does not run on a sharded index (num_gpus > 1)')
         self.device_mgf = bool(self.device_mgf)
         self.device_mzml = bool(self.device_mzml)
+        self.device_mzxml = bool(self.device_mzxml)
         self.device_library = bool(self.device_library)
         if self.precursor_window_open is not None:
             try:
@@ -467,7 +472,12 @@ def add_arguments(parser) -> None:
                         help='read a query file whose name ends in .mzML with the GPU reader: tags and parameters are '
                              'parsed and the base64 / zlib peak arrays decoded by kernels; the same queries as the '
                              'host reader gives; only MS2 spectra are read; malformed spectra raise an error naming '
-                             'the spectrum; mzXML is read as before (default: off)')
+                             'the spectrum; mzXML has a switch of its own, --device_mzxml (default: off)')
+    parser.add_argument('--device_mzxml', action='store_true', default=d.device_mzxml,
+                        help='read a query file whose name ends in .mzXML with the GPU reader: nested scans, precursor '
+                             'text and ISO-8601 retention times are parsed and the interleaved big-endian base64 / '
+                             'zlib peak streams decoded by kernels; the same queries as the host reader gives; only '
+                             'MS2 scans are read; malformed scans raise an error naming the scan (default: off)')
     parser.add_argument('--device_library', action='store_true', default=d.device_library,
                         help='read a spectral library whose name ends in .sptxt with the GPU reader: records, '
                              'precursors, peaks and annotations are parsed by kernels, no reference package is '

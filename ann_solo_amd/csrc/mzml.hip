@@ -40,6 +40,7 @@
 #include "inflate.hpp"
 #include "mgf_number.hpp"
 #include "text_records.hpp"
+#include "xml_tag.hpp"
 
 namespace asl {
 
@@ -57,7 +58,6 @@ enum : uint32_t {   // a cvParam's accession (aux)
 enum : uint32_t { ZF_SPEC = 0, ZF_SCANLIST, ZF_SCAN, ZF_PRECLIST, ZF_PREC, ZF_SION, ZF_BDA, ZF_N };
 constexpr uint32_t ZF_CLEAR_ALL = 0x2AAAu;
 static_assert(ZF_N == 7, "ZF_CLEAR_ALL clears seven fields");
-constexpr uint32_t NONE = ~0u;
 
 struct MzCtx {   // the context scan's element; also the scratch type of the unit's other scans (the widest)
   uint32_t spec, bda;              // sums: <spectrum> and <binaryDataArray> opened
@@ -100,65 +100,7 @@ __device__ __forceinline__ uint32_t zm_pack(const MzCtx &c) {
 __device__ __forceinline__ bool zm_in(uint32_t w, uint32_t f) { return ((w >> f) & 1u) != 0u; }
 
 // ---------------------------------------------------------------------------------------------- one tag
-// The '>' that ends the tag at a, outside quotes; lim when there is none before lim.
-__device__ __forceinline__ uint32_t zm_tag_end(const uint8_t *__restrict__ t, uint32_t a, uint32_t lim) {
-  uint8_t quote = 0;
-  for (uint32_t i = a + 1u; i < lim; ++i) {
-    const uint8_t c = t[i];
-    if (quote != 0) {
-      if (c == quote) quote = 0;
-    } else if (c == '"' || c == '\'') {
-      quote = c;
-    } else if (c == '>') {
-      return i;
-    }
-  }
-  return lim;
-}
-__device__ __forceinline__ bool zm_is(const uint8_t *__restrict__ t, uint32_t p, uint32_t len, const char *lit,
-                                      uint32_t lit_len) {
-  if (len != lit_len) return false;
-  for (uint32_t k = 0; k < lit_len; ++k)
-    if (t[p + k] != (uint8_t)lit[k]) return false;
-  return true;
-}
-// The value [*va, *vb) of attribute `name` among the attributes in [p, e), e the tag's '>'.
-__device__ __forceinline__ bool zm_attr(const uint8_t *__restrict__ t, uint32_t p, uint32_t e, const char *name,
-                                        uint32_t name_len, uint32_t *va, uint32_t *vb) {
-  while (p < e) {
-    while (p < e && mg_ws(t[p])) ++p;
-    const uint32_t na = p;
-    while (p < e && t[p] != '=' && !mg_ws(t[p])) ++p;
-    const uint32_t nb = p;
-    while (p < e && mg_ws(t[p])) ++p;
-    if (p >= e) return false;
-    if (t[p] != '=') continue;   // (a name without a value, as the '/' of a self-closing tag: nb > na, so p moved)
-    ++p;
-    while (p < e && mg_ws(t[p])) ++p;
-    if (p >= e) return false;
-    const uint8_t quote = t[p];
-    if (quote != '"' && quote != '\'') return false;
-    const uint32_t a = ++p;
-    while (p < e && t[p] != quote) ++p;
-    if (p >= e) return false;
-    if (zm_is(t, na, nb - na, name, name_len)) {
-      *va = a, *vb = p;
-      return true;
-    }
-    ++p;
-  }
-  return false;
-}
-// plain digits -> the number (at most 10^9), else NONE
-__device__ __forceinline__ uint32_t zm_uint(const uint8_t *__restrict__ t, uint32_t a, uint32_t b) {
-  if (a >= b) return NONE;
-  uint32_t v = 0u;
-  for (; a < b; ++a) {
-    if (t[a] < '0' || t[a] > '9' || v > 100000000u) return NONE;
-    v = v * 10u + (uint32_t)(t[a] - '0');
-  }
-  return v;
-}
+// (where a tag ends, its name, its attributes, plain digits: xml_tag.hpp, shared with mzxml.hip)
 __device__ __forceinline__ uint32_t zm_accession(const uint8_t *__restrict__ t, uint32_t a, uint32_t b) {
   if (b - a != 10u || !zm_is(t, a, 3u, "MS:", 3u)) return CV_NONE;
   const uint32_t v = zm_uint(t, a + 3u, b);

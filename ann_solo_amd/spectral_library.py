@@ -822,7 +822,8 @@ class SpectralLibrary:
         dropped (:225-228). With ``Config.device_mgf`` a file name ending in ``.mgf`` (any letter case)
         is read by ``mgf.read_mgf_packed`` -- parsed on the device, the same packed queries -- instead of
         ``query_reader`` and ``pack_queries``; with ``Config.device_mzml`` a name ending in ``.mzml`` is read by
-        ``mzml.read_mzml_packed`` in the same way. Returns the identifications as SSM records with the attributes
+        ``mzml.read_mzml_packed`` in the same way, and with ``Config.device_mzxml`` a name ending in ``.mzxml`` by
+        ``mzxml.read_mzxml_packed``. Returns the identifications as SSM records with the attributes
         ``writer.write_mztab`` consumes (writer.py:129-148)."""
         if isinstance(query, dict):
             return self.search_packed(query, query_meta, library_meta, score_ssms)
@@ -839,6 +840,12 @@ class SpectralLibrary:
             from .mzml import read_mzml_packed
             logging.info('Process file %s', query)
             query_spectra, qmeta = read_mzml_packed(os.fspath(query), self.config, self.device)
+        elif (self.config.device_mzxml and isinstance(query, (str, os.PathLike)) and
+                os.fspath(query).lower().endswith('.mzxml')):
+            # nested scans parsed and their streams decoded by kernels (mzxml.py)
+            from .mzxml import read_mzxml_packed
+            logging.info('Process file %s', query)
+            query_spectra, qmeta = read_mzxml_packed(os.fspath(query), self.config, self.device)
         else:
             if isinstance(query, (str, os.PathLike)):
                 logging.info('Process file %s', query)

@@ -1194,6 +1194,107 @@ int asl_mzml_fill(const uint8_t *text, int64_t n,
  * 14 fewer bytes than expected), -1 for a null argument. */
 int asl_mzml_inflate(const uint8_t *b64, int64_t n, int32_t zlib_flag, uint8_t *out, int64_t cap, int64_t *n_out);
 
+/* ------------------------------------------------------------------ mzXML query files
+ * A chunk of an mzXML file, resident in device memory, parsed and decoded by kernels (csrc/mzxml.hip, on the tag
+ * helpers of csrc/xml_tag.hpp and the decoder of csrc/inflate.hpp; DESIGN.md 3 "Query files") into the raw pack
+ * asl_process_batch takes. The dialect (what the reference's read_mzxml reads through pyteomics' mzxml.MzXML,
+ * restated; tests/mzxml_ref.py is the same statement in Python):
+ *   - Tags as for mzML: each from a '<' to the first '>' outside quotes, newlines mean nothing, a tag of more than
+ *     ASL_MZML_MAX_TAG bytes: ASL_ERR_CAPACITY. A comment or CDATA section after the first <scan is the structural
+ *     error ASL_MZXML_ERR_COMMENT; the schema's <comment> element is an ordinary ignored tag. The reader is NOT an
+ *     XML validator: well-formedness beyond what is listed here is not checked.
+ *   - Every <scan opening tag has the 0-based ordinal `index` among all <scan opening tags in document order,
+ *     whatever its MS level or nesting depth. A scan's HEAD is the run of tags from its opening tag to the next
+ *     <scan or </scan> tag (the schema puts precursorMz and peaks before child scans, so every tag a scan owns lies
+ *     in its head); a self-closing <scan .../> is a head with nothing in it. A <precursorMz or <peaks tag outside
+ *     any head: ASL_MZXML_ERR_OUTSIDE. The record of the chunk protocol is the head: it is closed once a complete
+ *     <scan or </scan> tag follows it, so a chunk may end inside a scan whose children are still to come.
+ *   - Only scans whose msLevel attribute is the digits "2" are read; a missing msLevel is skipped; other levels cost
+ *     the tag pass alone, their <peaks> are never decoded (a corrupt MS1 array goes unnoticed). An msLevel that is
+ *     not plain digits: ASL_MZXML_ERR_LEVEL.
+ *   - Identifier: the value of num, handed to the host as a byte range (Python's int() is applied there).
+ *   - Retention time: retentionTime, in minutes. "PT<seconds>S" with <seconds> = digits [. digits*] is converted as
+ *     seconds / 60.0, one fp64 division behind asl_mgf_number; a value that does not begin with 'P' is the numeral
+ *     as written; everything else (hours, minutes, a date part, a numeral the converter defers) is handed back as a
+ *     byte range. asl_mzxml_duration is the same function on the host.
+ *   - Precursor m/z: the text of the first <precursorMz> of the head, from its '>' to the next '<', blanks stripped,
+ *     converted by asl_mgf_number or deferred; charge: its precursorCharge attribute (digits, 1 .. 255), absent:
+ *     unknown (0).
+ *   - Peaks: peaksCount on the scan (digits; above ASL_MGF_MAX_PEAKS: ASL_ERR_CAPACITY); the first <peaks> of the
+ *     head, a second one is refused; precision "32" or "64"; byteOrder, where present, "network"; contentType or
+ *     pairOrder, where present, "m/z-int"; compressionType absent, "none" or "zlib"; compressedLen is ignored. The
+ *     content runs from '>' to the next '<'; base64 and zlib exactly as for mzML (above); the decoded stream is
+ *     exactly peaksCount * 2 * precision / 8 bytes, and a compressed stream for b such bytes at most b + b / 8 + 64
+ *     bytes long. peaksCount = 0 with no characters is an empty spectrum, whatever the compression. Values are
+ *     big-endian, m/z every even element and intensity every odd one; 64-bit values become float32 by
+ *     round-to-nearest (asl_mzxml_pairs is the same function on the host).
+ * The calls go as for the mzML reader: asl_mzxml_measure(text), asl_mzxml_fill(the same text), the deferred values
+ * stored, asl_mgf_sort on the pack. */
+/* counts[] of asl_mzxml_measure: ASL_MGF_N_LINES (tags) .. ASL_MGF_OPEN as for the MGF reader (N_SPECTRA: the MS2
+ * scans whose head is closed; N_DEFERRED: 0), and */
+#define ASL_MZXML_N_ELEMENTS 9      /* <scan opening tags of every MS level whose head is closed */
+#define ASL_MZXML_ERR_ELEMENT 10    /* <scan opening tags of the chunk up to the structural error's tag */
+#define ASL_MZXML_DEPTH_ALL 11      /* <scan> elements open behind the chunk's last tag ... */
+#define ASL_MZXML_DEPTH_CONSUMED 12 /* ... and behind tag ASL_MGF_CONSUMED_LINES - 1 */
+#define ASL_MZXML_COUNTS 13
+#define ASL_MZXML_ERR_OUTSIDE 1     /* <precursorMz or <peaks outside any scan's head */
+#define ASL_MZXML_ERR_COMMENT 2     /* a comment or CDATA section after the first <scan */
+#define ASL_MZXML_ERR_TAG 3         /* a tag after the first <scan that the next '<' or the file's end cuts */
+#define ASL_MZXML_ERR_LEVEL 4       /* an msLevel that is not plain digits, on a scan of any level */
+/* errors[] of asl_mzxml_fill, per MS2 scan. What fails while the reference iterates over the file (with a scan
+ * without num, and with array_errors) ... */
+#define ASL_MZXML_E_COUNT 0x1       /* peaksCount missing or not digits */
+#define ASL_MZXML_E_NO_PEAKS 0x2    /* no <peaks> in the head */
+#define ASL_MZXML_E_PEAKS_TWICE 0x4 /* more than one <peaks> in the head */
+#define ASL_MZXML_E_PRECISION 0x8   /* missing, or neither 32 nor 64 */
+#define ASL_MZXML_E_BYTE_ORDER 0x10 /* byteOrder other than network */
+#define ASL_MZXML_E_CONTENT_TYPE 0x20 /* contentType or pairOrder other than m/z-int */
+#define ASL_MZXML_E_COMPRESSION 0x40 /* compressionType other than none or zlib */
+#define ASL_MZXML_E_FILE 0x7f
+/* ... and what fails after the identifier is read (a scan the identifier rule drops never gets here) */
+#define ASL_MZXML_E_NO_RT 0x100     /* no retentionTime attribute */
+#define ASL_MZXML_E_NO_PRECURSOR 0x200 /* no <precursorMz> in the head */
+#define ASL_MZXML_E_CHARGE 0x400    /* a precursorCharge that is not digits in 1 .. 255 */
+/* flags[] of asl_mzxml_fill, per MS2 scan */
+#define ASL_MZXML_F_ZLIB 0x1
+#define ASL_MZXML_F_F64 0x2
+#define ASL_MZXML_F_NESTED 0x4      /* the head opened inside another scan's element */
+/* text: device memory, n bytes. last: bit 0: the chunk ends the file; bit 1: a <scan was seen before this chunk;
+ * bits 8 .. 15: the <scan> elements open in front of the chunk (at most 255; only ASL_MZXML_F_NESTED and the two
+ * depth counts depend on it). Errors as asl_mzml_measure, with peaksCount for defaultArrayLength.
+ * counts: [ASL_MZXML_COUNTS], host. */
+int asl_mzxml_measure(const uint8_t *text, int64_t n, int32_t last, int64_t *counts);
+/* The measured chunk into caller-allocated arrays, host or device memory; per MS2 scan s. identifier: the byte
+ * range (offset, length) of num's value, length -1 without one. element: the ordinal of the scan among the chunk's
+ * <scan opening tags. numerals: (offset, length) of retentionTime's value and of the precursor m/z's text where
+ * the device deferred it (then the column holds NaN), length -1 elsewhere. array_errors: ASL_MZML_INF_* of the
+ * scan's one stream, 0: decoded. A scan with errors[s] != 0 or an array error has undefined peaks: the caller
+ * refuses it. One thread decodes one stream over windows in global scratch that the library keeps (34 bytes a peak
+ * and 1.4 KiB a scan): the raw window of a scan is up to ASL_MGF_MAX_PEAKS * 16 bytes = 64 KiB, twice DEFLATE's
+ * largest distance, and serves the inflater as its history. */
+int asl_mzxml_fill(const uint8_t *text, int64_t n,
+                   int32_t *offsets            /* [n_spectra + 1] */,
+                   float *mz                   /* [n_peaks] */,
+                   float *intensity            /* [n_peaks] */,
+                   uint8_t *charge             /* [n_peaks], zeros */,
+                   double *precursor_mz        /* [n_spectra] */,
+                   int32_t *precursor_charge   /* [n_spectra], 0: unknown */,
+                   double *retention_time      /* [n_spectra], minutes */,
+                   int32_t *identifier         /* [n_spectra, 2] */,
+                   int32_t *first_tag          /* [n_spectra] */,
+                   int32_t *element            /* [n_spectra] */,
+                   int32_t *numerals           /* [n_spectra, 4] */,
+                   int32_t *errors             /* [n_spectra] */,
+                   int32_t *flags              /* [n_spectra] */,
+                   int32_t *array_errors       /* [n_spectra] */);
+/* Host only: the value s[0 .. n) of a retentionTime attribute as the device converts it (csrc/mzxml_value.hpp).
+ * 0: *minutes written; 1: deferred to the caller's full rule, *minutes untouched. */
+int asl_mzxml_duration(const char *s, int32_t n, double *minutes);
+/* Host only: a decoded <peaks> stream raw[0 .. n_peaks * 2 * precision / 8) as the device converts it: big-endian
+ * (m/z, intensity) pairs into mz[n_peaks] and intensity[n_peaks]. precision: 32 or 64. Returns 0, or -1 for a null
+ * argument, a negative n_peaks or another precision. */
+int asl_mzxml_pairs(const uint8_t *raw, int32_t n_peaks, int32_t precision, float *mz, float *intensity);
+
 /* ------------------------------------------------------------------ hot path
  * One batch of same-charge queries through
  *   SpectralLibrary._search_batch / _get_library_candidates
